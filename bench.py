@@ -10,7 +10,9 @@ disjoint across steps and ranks; all batches are generated on the device before 
 depth-150 piles are 9 GB of the 288), so `steps x windows_per_step x n_gpus` distinct windows are corrected per run (20 steps =
 327 680 >= 2^18).  Rank r of N works on its own windows; there is no collective on the data path (windows are
 independent), so scaling is weak.  `python bench.py --gpus N` without a torch.distributed environment re-launches itself as N ranks.
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run times `--steps` steps once and reports only that; `--full` adds
+the repetitions, the native-driver leg, the roofline, PCIe-inclusive and CPU-baseline legs.  `--dump-outputs DIR` writes what the last
+timed step computed (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -42,6 +44,41 @@ MAX_RESIDENT_BATCHES = 48  # distinct input batches kept in HBM; runs with more 
 def algorithmic_bytes(seq_len, n_windows, cons_len, solid_len):
     """sum ceil(len/4) + 4*N + 16/window + consensus bytes + 4*|solid| + 8/window."""
     return int(np.sum((seq_len.astype(np.int64) + 3) // 4) + 4 * len(seq_len) + 16 * n_windows + int(np.sum(cons_len)) + 4 * int(np.sum(solid_len)) + 8 * n_windows)
+
+
+DUMP_SAMPLE_WINDOWS = 2048  # windows whose consensus and solid k-mers --dump-outputs writes (a fixed, seeded sample)
+DUMP_SEED = 20261016
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, n_win, cons_cap, solid_cap):
+    """--dump-outputs: what the caller of cw_run_device receives from the last timed step, as float32 .npy files -- status, consensus length and
+    solid-k-mer count of every window; the consensus bases (ASCII codes) and solid k-mers (2-bit codes, < 2^24: exact in float32) of a fixed
+    sample of windows, concatenated in window order.  At most DUMP_MAX_BYTES in all."""
+    import torch
+
+    cons, clen, stat, solid, slen = res
+    os.makedirs(out_dir, exist_ok=True)
+    status, cons_len, solid_len = stat.cpu().numpy(), clen.cpu().numpy().astype(np.int64), slen.cpu().numpy().astype(np.int64)
+    wins = np.sort(np.random.default_rng(DUMP_SEED).choice(n_win, min(n_win, DUMP_SAMPLE_WINDOWS), replace=False))
+    w_dev = torch.from_numpy(wins).to(cons.device)
+    cons_rows = cons.view(n_win, cons_cap)[w_dev].cpu().numpy()
+    solid_rows = solid.view(n_win, solid_cap)[w_dev].cpu().numpy()
+    arrays = {
+        "status": status,
+        "consensus_len": cons_len,
+        "solid_len": solid_len,
+        "sample_windows": wins,
+        "consensus_sample": np.concatenate([cons_rows[i, : min(cons_len[w], cons_cap)] for i, w in enumerate(wins)]),
+        "solid_sample": np.concatenate([solid_rows[i, : min(solid_len[w], solid_cap)] for i, w in enumerate(wins)]),
+    }
+    arrays = {k: v.astype(np.float32) for k, v in arrays.items()}
+    over = sum(v.nbytes for v in arrays.values()) - DUMP_MAX_BYTES
+    if over > 0:  # (a bound, not the rule: a 500-bp window has some 500 consensus bases and a few hundred solid k-mers)
+        arrays["solid_sample"] = arrays["solid_sample"][: max(0, arrays["solid_sample"].size - (over + 3) // 4)]
+        print(f"[bench] --dump-outputs: solid_sample cut to {arrays['solid_sample'].size} k-mers to stay within {DUMP_MAX_BYTES >> 20} MB", file=sys.stderr)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
 
 
 def effective_cores():
@@ -150,25 +187,33 @@ def main():
     ap.add_argument("--driver-cov", type=int, default=30)
     ap.add_argument("--driver-copies", type=int, default=1)
     ap.add_argument("--driver-reps", type=int, default=2)
-    ap.add_argument("--driver-leg", type=int, default=1, help="kernel mode: after the timed region rank 0 also runs the native driver (ONE process over the --gpus devices) on the fixed BASELINE configs[3]-scale read set and reports it under `driver_strong_scaling` of the same JSON line (strong scaling: the set does not grow with N); 0 disables")
+    ap.add_argument("--full", action="store_true",
+                    help="kernel mode: everything besides the headline figure -- --reps timed repetitions (default 3), the native-driver leg, the one-batch-in-flight kernel times and `roofline`, the PCIe-inclusive leg and the CPU baseline.  "
+                         "Without it a run sets up, warms up, times --steps steps once, writes --dump-outputs and prints the line; an option given explicitly still holds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy (float32): every window's status and lengths, and the consensus bases and solid k-mers of a fixed, seeded sample of windows")
+    ap.add_argument("--driver-leg", type=int, default=None, help="kernel mode: before the timed region rank 0 also runs the native driver (ONE process over the --gpus devices) on the fixed BASELINE configs[3]-scale read set and reports it under `driver_strong_scaling` of the same JSON line (strong scaling: the set does not grow with N); 0 disables (default: 1 with --full, else 0)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=int(os.environ.get("CW_BENCH_REPS", "3")),
-                    help="timed repetitions of the K-step region inside this process (SURVEY 8d: warm-up, then several timed runs, the MEDIAN reported): every repetition is exactly --steps steps between a barrier + synchronize on both sides, max over ranks; value / ms_per_step are the median repetition's, min and max beside them")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed repetitions of the K-step region inside this process (SURVEY 8d: warm-up, then several timed runs, the MEDIAN reported): every repetition is exactly --steps steps between a barrier + synchronize on both sides, max over ranks; value / ms_per_step are the median repetition's, min and max beside them (default: CW_BENCH_REPS or 3 with --full, else 1)")
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
     ap.add_argument("--windows", type=int, default=0, help="windows per step per GPU (default: per workload)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="windows timed on the CPU oracle (rank 0, N=1); 0 disables")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="windows timed on the CPU oracle (rank 0, N=1); 0 disables, -1 = by the usable cores (default: -1 with --full, else 0)")
     # (round 5: three -- four alternating runs each on one box: 53.4 52.8 54.2 52.2 ms per step with two engines and eight queues, 52.0 52.5 52.9 51.7 with three
     # and sixteen; the native driver takes a third worker per device on long runs for the same reason)
     # (round 6: four, with 24 hardware queues -- four alternating runs each on one box: 52.4 54.7 53.0 53.1 ms per step with three engines on 16 queues, 50.6 49.1 49.5 51.6 with
     # four on 24, 51.5 51.9 52.2 50.3 with four on 16; the scratch plan went from 24 to 18 GB an engine in the same round)
     ap.add_argument("--engines", type=int, default=int(os.environ.get("CW_BENCH_ENGINES", "4")),
                     help="engines per GPU taking the steps in turn (each has its own scratch and streams): batch n+1's index/chain kernels fill the CUs that the tail of batch n's POA stage leaves idle")
-    ap.add_argument("--alone-steps", type=int, default=3, help="untimed steps after the timed region with ONE batch in flight: per-kernel HIP-event times that are work, not waiting (roofline.launch_ms)")
+    ap.add_argument("--alone-steps", type=int, default=None, help="untimed steps after the timed region with ONE batch in flight: per-kernel HIP-event times that are work, not waiting (roofline.launch_ms) (default: 3 with --full, else 0)")
     ap.add_argument("--pcie-engines", type=int, default=3, help="engines the PCIe-inclusive leg spreads its host batches over (round 6: three, six host batches in flight)")
-    ap.add_argument("--pcie-steps", type=int, default=-1, help="batches timed through cw_submit/cw_wait from pinned host memory (rank 0, N=1); 0 disables")
+    ap.add_argument("--pcie-steps", type=int, default=None, help="batches timed through cw_submit/cw_wait from pinned host memory (rank 0, N=1); 0 disables, -1 = by --steps (default: -1 with --full, else 0)")
     args = ap.parse_args()
+    for name, full_default in (("driver_leg", 1), ("reps", int(os.environ.get("CW_BENCH_REPS", "3"))), ("cpu_sample", -1), ("alone_steps", 3), ("pcie_steps", -1)):
+        if getattr(args, name) is None:  # the extra legs run by default only with --full; a plain run does what its headline figure needs
+            setattr(args, name, full_default if args.full else (1 if name == "reps" else 0))
 
     if args.mode == "driver":
         if int(os.environ.get("RANK", "0")) == 0:  # one process feeds every device
@@ -365,6 +410,8 @@ def main():
     n_reps = max(1, args.reps)
     rep_dt = [timed_region() for _ in range(n_reps)]
     dt = float(np.median(rep_dt))
+    if args.dump_outputs and rank == 0:  # before the untimed legs below reuse the result arrays
+        dump_outputs(args.dump_outputs, ([(t_cons, t_clen, t_stat, t_solid, t_slen)] + keep_r)[e_last], n_win, cons_cap, solid_cap)
     if os.environ.get("CW_PROFILE"):
         print("host ms per step: enqueue", round(host_ms[0] / (args.steps * n_reps), 3), "wait + read stage timings", round(host_ms[1] / (args.steps * n_reps), 3), file=sys.stderr)
     if ne > 1:
@@ -400,12 +447,13 @@ def main():
     # The dominant kernel is the one that does the largest share of the work, by the wave-cycles the POA kernels count themselves
     # (cw_debug_profile; the tier kernels run side by side between one fork and one join, so wall time does not tell them apart).
     tier_stage = ["poa", "poa_m1", "poa_m2", "poa_large", "poa_q", "poa_h"]  # wave-cycles per tier kernel (tiers Q and H: as the first task of each wave saw them)
-    busy_share = None
-    _, prof = eng.profile()
-    busy = [float(prof[8 + 5 * t : 13 + 5 * t].sum()) for t in range(4)] + [float(prof[28:33].sum()), float(prof[64:69].sum())]
-    if sum(busy) > 0:
-        busy_share = {tier_stage[t]: busy[t] / sum(busy) for t in range(6)}
-    dom = max(busy_share, key=busy_share.get) if busy_share else (max((k for k in alone_avg if k != "total"), key=alone_avg.get) if alone_avg else None)
+    busy_share = dom = None
+    if args.full:  # `roofline` is a --full figure
+        _, prof = eng.profile()
+        busy = [float(prof[8 + 5 * t : 13 + 5 * t].sum()) for t in range(4)] + [float(prof[28:33].sum()), float(prof[64:69].sum())]
+        if sum(busy) > 0:
+            busy_share = {tier_stage[t]: busy[t] / sum(busy) for t in range(6)}
+        dom = max(busy_share, key=busy_share.get) if busy_share else (max((k for k in alone_avg if k != "total"), key=alone_avg.get) if alone_avg else None)
     total_windows = n_win * world * args.steps
     value = total_windows / dt
 

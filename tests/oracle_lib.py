@@ -1,6 +1,9 @@
 """ctypes access to the CPU oracle (oracle/liboracle.so) and to the reference-built checker (oracle/_ref).
 Test infrastructure only."""
+import atexit
 import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -27,6 +30,76 @@ def ref():
     if _R is None and os.path.exists(p):
         _R = C.CDLL(p)
     return _R
+
+
+# Digests of the reference's answers, recorded from oracle/_ref (CW_RECORD_REF_DIGESTS=1 python -m pytest tests -m "not gpu" where it is built):
+# the tests that pin the product or the oracle to the reference's own code check against them where oracle/_ref is absent.
+REF_DIGESTS = os.path.join(ROOT, "tests", "golden", "ref_digests.json")
+_DIGESTS = None
+_RECORDED = {}
+
+
+def _canon(x):
+    if isinstance(x, (bytes, bytearray)):
+        return {"hex": bytes(x).hex()}
+    if isinstance(x, np.ndarray):
+        return x.tolist()
+    if isinstance(x, np.generic):
+        return x.item()
+    if isinstance(x, (list, tuple)):
+        return [_canon(v) for v in x]
+    return x
+
+
+def digest(x):
+    return hashlib.sha256(json.dumps(_canon(x), sort_keys=True).encode()).hexdigest()
+
+
+class RecordedAnswer:
+    """The reference's answer known by its digest only: equal to a value whose digest is the same."""
+
+    __hash__ = None
+
+    def __init__(self, d):
+        self.digest = d
+
+    def __eq__(self, other):
+        return digest(other) == self.digest
+
+    def __ne__(self, other):
+        return not self.__eq__(other)
+
+    def __repr__(self):
+        return f"<reference answer sha256:{self.digest[:16]}>"
+
+
+def ref_answer(inputs, live, have_ref=None):
+    """The reference's answer on `inputs` (JSON-like, everything that determines it: file contents, not paths).  With oracle/_ref built
+    (have_ref() true; default: libconsent_ref.so loads) it is live(ref()), and its digest is recorded; without it, the digest committed under
+    tests/golden/ (a RecordedAnswer).  Inputs never recorded skip."""
+    import pytest
+
+    key = digest(inputs)
+    if (have_ref() if have_ref else ref() is not None):
+        val = live(ref())
+        _RECORDED[key] = digest(val)
+        return val
+    global _DIGESTS
+    if _DIGESTS is None:
+        _DIGESTS = json.load(open(REF_DIGESTS)) if os.path.exists(REF_DIGESTS) else {}
+    if key not in _DIGESTS:
+        pytest.skip("oracle/_ref not built and no recorded reference answer for these inputs")
+    return RecordedAnswer(_DIGESTS[key])
+
+
+@atexit.register
+def _write_recorded():
+    if os.environ.get("CW_RECORD_REF_DIGESTS") and _RECORDED:
+        old = json.load(open(REF_DIGESTS)) if os.path.exists(REF_DIGESTS) else {}
+        old.update(_RECORDED)
+        with open(REF_DIGESTS, "w") as f:
+            json.dump(old, f, indent=0, sort_keys=True)
+            f.write("\n")
 
 
 STAT_NAMES = ["kmers", "tpl_anchors", "chain_len", "pair_tests", "segments", "poa_segments", "alignments", "dp_cells", "max_nodes", "max_seg_len", "link_calls", "nbr_calls", "alignments_routed", "dp_cells_routed"]

@@ -119,7 +119,7 @@ def test_bench_gpus_2_spawns_two_ranks_without_a_launcher():
     and say n_gpus: 2; with a launcher environment it would be one rank of that launch."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(CW_BENCH_SINGLE_DEVICE="1", CW_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "256", "--workload", "pacbio_d30_msa20"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "256", "--workload", "pacbio_d30_msa20"],
                          capture_output=True, text=True, env=env, timeout=560)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -129,6 +129,38 @@ def test_bench_gpus_2_spawns_two_ranks_without_a_launcher():
     assert j["value"] > 0 and "roofline" in j
 
 
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_steps_once_and_dumps_the_last_step(tmp_path):
+    """Without --full: exactly --steps timed steps, one repetition, none of the extra legs; --dump-outputs holds the last timed step's results,
+    which equal the oracle's on the same synthetic windows."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--windows", "256", "--workload", "pacbio_d30_msa20",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=560)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(line) == 1, out.stdout
+    j = json.loads(line[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["reps"] == 1 and len(j["ms_per_step_reps"]) == 1
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and j["unit"] == "windows/s" and j["higher_is_better"] is True and "dtype" in j
+    for k in ("roofline", "driver_strong_scaling", "pcie_inclusive", "cpu_baseline", "secondary"):
+        assert k not in j, k
+    d = {k: np.load(tmp_path / f"{k}.npy") for k in ("status", "consensus_len", "solid_len", "sample_windows", "consensus_sample", "solid_sample")}
+    assert all(v.dtype == np.float32 for v in d.values()) and sum(v.nbytes for v in d.values()) <= 64 << 20
+    assert len(d["status"]) == 256 and len(d["sample_windows"]) == 256
+    # the last timed step's batch: step warmup + steps - 1 of rank 0 (bench.py: first_window = (rank * (warmup + steps) + i) * windows)
+    prm = ca.Params(9, 4, 8, 2, 20)
+    exp, _ = oracle_lib.oracle_run(prm, synth_host(ca.SynthSpec.pacbio(256, 30, first_window=3 * 256)))
+    cons = d["consensus_sample"].astype(np.uint8).tobytes().decode()
+    solid = d["solid_sample"].astype(np.int64)
+    co = so = 0
+    for w in d["sample_windows"].astype(np.int64):
+        assert int(d["status"][w]) == int(exp.status[w]), w
+        n_c, n_s = int(d["consensus_len"][w]), int(d["solid_len"][w])
+        assert cons[co : co + n_c] == exp.consensus(w), w
+        assert np.array_equal(solid[so : so + n_s], exp.solid_kmers(w).astype(np.int64)), w
+        co, so = co + n_c, so + n_s
+    assert co == len(cons) and so == len(solid)
+
+
 @pytest.mark.timeout(1500)
 def test_bench_gpus_8_runs_eight_ranks_and_the_driver_leg_on_one_box():
     """The command the driver runs once on an 8-GPU node, here with all eight ranks on the one GPU of the box (CW_BENCH_SINGLE_DEVICE, gloo): rank 0's
@@ -136,7 +168,7 @@ def test_bench_gpus_8_runs_eight_ranks_and_the_driver_leg_on_one_box():
     n_gpus 8, a driver_strong_scaling object without an error, three timed repetitions and their median."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(CW_BENCH_SINGLE_DEVICE="1", CW_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--windows", "1024", "--steps", "4", "--warmup", "3"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--windows", "1024", "--steps", "4", "--warmup", "3"],
                          capture_output=True, text=True, env=env, timeout=1400)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -1,5 +1,6 @@
 """CPU: the wrapper plumbing of the library (cw_paf_reformat / cw_paf_explode / cw_paf_merge) against the reference's own
-reformatPAF.cpp, explode.cpp and merge.cpp compiled unmodified into oracle/_ref: byte-identical files."""
+reformatPAF.cpp, explode.cpp and merge.cpp compiled unmodified into oracle/_ref: byte-identical files (without oracle/_ref: the digests of
+the reference programs' files recorded under tests/golden/, oracle_lib.ref_answer)."""
 import glob
 import os
 import random
@@ -8,15 +9,31 @@ import subprocess
 import pytest
 
 import consent_amd as ca
+import oracle_lib
 
 REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
 
 
 def tool(name):
-    p = os.path.join(REF, name)
-    if not os.path.exists(p):
-        pytest.skip("oracle/_ref tools not built")
-    return p
+    return os.path.join(REF, name)
+
+
+def have_tools():
+    return all(os.path.exists(tool(t)) for t in ("ref_reformatPAF", "ref_explode", "ref_merge"))
+
+
+def read(path):
+    return open(path, "rb").read()
+
+
+def ref_explode(src, prefix):
+    """the reference explode's slices of src (their bytes, in slice order)"""
+
+    def live(_):
+        subprocess.check_call([tool("ref_explode"), src, prefix])
+        return [read(p) for p in sorted(glob.glob(prefix + "_*"), key=lambda p: int(p.rsplit("_", 1)[1]))]
+
+    return oracle_lib.ref_answer(["explode", read(src)], live, have_tools)
 
 
 def make_paf(path, rng, n_reads=15, n_lines=400, shuffle_level=0.3):
@@ -41,9 +58,13 @@ def test_reformat_matches_reference(tmp_path):
     rng = random.Random(1)
     src = str(tmp_path / "a.paf")
     make_paf(src, rng)
-    subprocess.check_call([tool("ref_reformatPAF"), src, str(tmp_path / "ref.paf")])
+
+    def live(_):
+        subprocess.check_call([tool("ref_reformatPAF"), src, str(tmp_path / "ref.paf")])
+        return read(tmp_path / "ref.paf")
+
     ca.paf_reformat(src, str(tmp_path / "got.paf"))
-    assert open(tmp_path / "got.paf", "rb").read() == open(tmp_path / "ref.paf", "rb").read()
+    assert read(tmp_path / "got.paf") == oracle_lib.ref_answer(["reformat", read(src)], live, have_tools)
     # swapping twice gives the original back
     ca.paf_reformat(str(tmp_path / "got.paf"), str(tmp_path / "back.paf"))
     assert open(tmp_path / "back.paf", "rb").read() == open(src, "rb").read()
@@ -54,20 +75,22 @@ def test_explode_and_merge_match_reference(tmp_path, seed):
     rng = random.Random(seed)
     src = str(tmp_path / "a.paf")
     names = make_paf(src, rng, n_reads=10 + seed, n_lines=300 + 100 * seed)
-    subprocess.check_call([tool("ref_explode"), src, str(tmp_path / "refx")])
+    exp = ref_explode(src, str(tmp_path / "refx"))
     got = ca.paf_explode(src, str(tmp_path / "gotx"))
-    ref_chunks = sorted(glob.glob(str(tmp_path / "refx_*")), key=lambda p: int(p.rsplit("_", 1)[1]))
-    assert len(got) == len(ref_chunks) > 1
-    for g, r in zip(got, ref_chunks):
-        assert open(g, "rb").read() == open(r, "rb").read()
+    assert len(got) > 1 and [read(g) for g in got] == exp
     # merge: headers in an order of our choosing (the wrapper takes them from the read file), with names that have no overlap at all
     order = names[:] + ["ghost"]
     rng.shuffle(order)
     hdr = str(tmp_path / "headers.txt")
     open(hdr, "w").write("".join(f">{n}\n" for n in order))
-    subprocess.check_call([tool("ref_merge"), str(tmp_path / "ref_merged.paf"), hdr] + ref_chunks)
+
+    def live(_):  # over the library's slices, equal to the reference's (asserted above)
+        subprocess.check_call([tool("ref_merge"), str(tmp_path / "ref_merged.paf"), hdr] + got)
+        return read(tmp_path / "ref_merged.paf")
+
+    b = oracle_lib.ref_answer(["merge", read(hdr), [read(g) for g in got]], live, have_tools)
     ca.paf_merge(str(tmp_path / "got_merged.paf"), hdr, got)
-    a, b = open(tmp_path / "got_merged.paf", "rb").read(), open(tmp_path / "ref_merged.paf", "rb").read()
+    a = read(tmp_path / "got_merged.paf")
     assert a == b and len(a) > 0
 
 
@@ -85,12 +108,9 @@ def test_explode_edge_cases_match_reference(tmp_path, name, text):
     """the one-pass slice writer of cw_paf_explode against the reference program on the inputs where line handling shows"""
     src = str(tmp_path / "e.paf")
     open(src, "wb").write(text.encode())
-    subprocess.check_call([tool("ref_explode"), src, str(tmp_path / "refx")])
+    exp = ref_explode(src, str(tmp_path / "refx"))
     got = ca.paf_explode(src, str(tmp_path / "gotx"))
-    ref_chunks = sorted(glob.glob(str(tmp_path / "refx_*")), key=lambda p: int(p.rsplit("_", 1)[1]))
-    assert len(got) == len(ref_chunks) >= 1, name
-    for g, r in zip(got, ref_chunks):
-        assert open(g, "rb").read() == open(r, "rb").read(), (name, g)
+    assert len(got) >= 1 and [read(g) for g in got] == exp, name
 
 
 def test_wrapper_errors(tmp_path):

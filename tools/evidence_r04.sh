@@ -9,9 +9,9 @@ FZ=${1:-300}
 EV=gpurun_out/ev_r04
 mkdir -p $EV
 bash tools/verify_codes.sh > $EV/verify.txt 2>&1
-python bench.py --steps 20 --warmup 5 > $EV/bench_r04_pacbio_d150_msa150.json 2> $EV/bench_d150.err
-python bench.py --steps 20 --warmup 5 --workload pacbio_d30_msa20 > $EV/bench_r04_pacbio_d30_msa20.json 2> $EV/bench_d30.err
-python bench.py --steps 10 --warmup 3 --engines 1 --cpu-sample 0 --pcie-steps 0 > $EV/bench_r04_pacbio_d150_msa150_one_engine.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $EV/bench_r04_pacbio_d150_msa150.json 2> $EV/bench_d150.err
+python bench.py --full --steps 20 --warmup 5 --workload pacbio_d30_msa20 > $EV/bench_r04_pacbio_d30_msa20.json 2> $EV/bench_d30.err
+python bench.py --full --steps 10 --warmup 3 --engines 1 --cpu-sample 0 --pcie-steps 0 > $EV/bench_r04_pacbio_d150_msa150_one_engine.json 2>/dev/null
 for wl in pacbio_d150_msa150 pacbio_d30_msa20; do
   W=16384
   bash tools/profile_r03.sh r04 $wl all > $EV/prof_$wl.log 2>&1
@@ -22,8 +22,8 @@ for wl in pacbio_d150_msa150 pacbio_d30_msa20; do
 done
 # bench once more with the fresh counters beside it (roofline.traffic comes from profiles/latest_*.json)
 cp $EV/latest_pacbio_d150_msa150.json profiles/latest_pacbio_d150_msa150.json; cp $EV/latest_pacbio_d30_msa20.json profiles/latest_pacbio_d30_msa20.json
-python bench.py --steps 20 --warmup 5 > $EV/bench_r04_pacbio_d150_msa150.json 2> $EV/bench_d150.err
-python bench.py --steps 20 --warmup 5 --workload pacbio_d30_msa20 > $EV/bench_r04_pacbio_d30_msa20.json 2> $EV/bench_d30.err
+python bench.py --full --steps 20 --warmup 5 > $EV/bench_r04_pacbio_d150_msa150.json 2> $EV/bench_d150.err
+python bench.py --full --steps 20 --warmup 5 --workload pacbio_d30_msa20 > $EV/bench_r04_pacbio_d30_msa20.json 2> $EV/bench_d30.err
 export CW_KEEP_DATA=/tmp/cw_drv_data
 python bench.py --mode driver --gpus 1 --driver-copies 1 > $EV/driver_r04_x1.json 2> $EV/driver_x1.err
 python bench.py --mode driver --gpus 1 --driver-copies 8 > $EV/driver_r04_x8.json 2> $EV/driver_x8.err

@@ -10,7 +10,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_${TAG}_${WL}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
-BASE="python bench.py --steps 5 --warmup 2 --cpu-sample 0 --pcie-steps 0 --driver-leg 0 --workload $WL"
+BASE="python bench.py --full --steps 5 --warmup 2 --cpu-sample 0 --pcie-steps 0 --driver-leg 0 --workload $WL"
 if [ "$WHAT" != pmc ]; then
   timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace_e1" -o trace -- $BASE --engines 1 > "$OUT/bench_trace_e1.log" 2>&1
   timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace_e2" -o trace -- $BASE --engines 2 > "$OUT/bench_trace_e2.log" 2>&1
