@@ -197,7 +197,7 @@ struct Worker {
            one set of arrays planned for the whole job.  The re-assembly then walks each read's windows over the whole job, so a read --
            or a contig of any length -- may span slices and runs.  (Usually: one slice, one run.) */
         uint64_t desc_budget = 1ull << 26;
-        uint32_t run_windows = CW_MAX_BATCH_WINDOWS;
+        uint32_t run_windows = cw_max_batch_windows(eng); /* (CW_MAX_BATCH_WINDOWS, fewer for long windows: include/consent_amd.h) */
         if (const char* env = CW_AID_ENV("CW_DRIVER_SLICE_DESC")) { const long long v = atoll(env); if (v >= 1) desc_budget = (uint64_t)v; }           /* test aids */
         if (const char* env = CW_AID_ENV("CW_DRIVER_RUN_WINDOWS")) { const long v = atol(env); if (v >= 1 && v < (long)run_windows) run_windows = (uint32_t)v; }
         struct Slice { uint32_t w0, w1, n_seqs; uint64_t n_words, seq_base, word_base; };
@@ -576,7 +576,9 @@ extern "C" int cw_run_correction(const cw_driver_args* a, int out_fd, cw_driver_
        it is close to template bases / (window size - overlap); floor 4096 windows (below that a job no longer fills a GPU). */
     size_t n_distinct_devs;
     { std::vector<int> distinct(devs); std::sort(distinct.begin(), distinct.end()); distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end()); n_distinct_devs = distinct.size(); }
-    uint32_t per_job = a->windows_per_batch ? (a->windows_per_batch > CW_MAX_BATCH_WINDOWS ? CW_MAX_BATCH_WINDOWS : a->windows_per_batch) : 32768u;
+    const uint32_t max_batch = cw_plan_max_batch_windows(a->mer_size, a->window_size); /* what cw_max_batch_windows will say of the workers' engines */
+    uint32_t per_job = a->windows_per_batch ? (a->windows_per_batch > max_batch ? max_batch : a->windows_per_batch) : 32768u;
+    if (per_job > max_batch) per_job = max_batch;
     if (!a->windows_per_batch) {
         const uint64_t est_windows = tpl_bases / (a->window_size - a->window_overlap) + 1;
         /* jobs per device.  Eight (four per worker with two workers) while a device gets 1e5 windows or more; THREE below that (round 6): a device that gets
@@ -588,7 +590,7 @@ extern "C" int cw_run_correction(const cw_driver_args* a, int out_fd, cw_driver_
         const uint64_t want = est_windows / (jobs_per_dev * n_distinct_devs) + 1;
         if (want < per_job) per_job = (uint32_t)(want < 4096 ? 4096 : want);
     }
-    if (const char* env = CW_AID_ENV("CW_JOB_WINDOWS")) { const long v = atol(env); if (v >= 1 && v <= (long)CW_MAX_BATCH_WINDOWS) per_job = (uint32_t)v; } /* test aid: jobs of a few windows, so that a small data set reaches every worker */
+    if (const char* env = CW_AID_ENV("CW_JOB_WINDOWS")) { const long v = atol(env); if (v >= 1 && v <= (long)max_batch) per_job = (uint32_t)v; } /* test aid: jobs of a few windows, so that a small data set reaches every worker */
     cw_paf_reader* paf = nullptr;
     rc = cw_paf_open(a->alignment_file, index, a->max_support, &paf);
     uint64_t n_piles = 0, n_windows = 0, n_overlaps = 0;
@@ -672,7 +674,7 @@ extern "C" int cw_run_correction(const cw_driver_args* a, int out_fd, cw_driver_
                 /* a job's extraction scratch is one descriptor per (window, overlap of its pile): polishing with -S 20000 looks at every
                    overlap of the contig for every window (alignmentWindows.cpp:105), so jobs are also cut by that product -- 2^26
                    descriptors = 1 GiB; only a single pile larger than that still makes a larger job (a read's windows are never split) */
-                if (!cur->wj.empty() && (cur->wj.size() + np > CW_MAX_BATCH_WINDOWS || cur->cost + (uint64_t)np * (n + 1) > job_cost_cap) && !push_job()) return CW_E_INTERNAL;
+                if (!cur->wj.empty() && (cur->wj.size() + np > max_batch || cur->cost + (uint64_t)np * (n + 1) > job_cost_cap) && !push_job()) return CW_E_INTERNAL;
                 cw_stitch_read sr_{p.tpl, (uint32_t)cur->wj.size(), np};
                 const uint32_t ovl_first = (uint32_t)cur->ovl.size();
                 cur->ovl.insert(cur->ovl.end(), r.ov.begin() + (ptrdiff_t)p.ov_off, r.ov.begin() + (ptrdiff_t)(p.ov_off + n));

@@ -104,7 +104,11 @@ struct ScratchPlan {
 
 /* tmax: template k-mers per window the plan provides for -- 1024 (templates of up to 1032 bases at k = 9: every window of the wrappers' defaults) unless the
    engine was configured for longer ones (cw_configure, up to CW_TMAX): the index kernel takes any template of up to CW_TMAX k-mers, what grows is the plan */
-ScratchPlan plan_scratch(const cw_params& prm, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t big_slots, uint32_t scale = 1, uint32_t tmax = 1024) {
+/* the global position-matrix slot of the index kernel: rows (sequences) per template k-mer at most -- what a re-run after CW_WHY_MATRIX gets */
+constexpr uint64_t kPfRowsMax = 4100;
+
+ScratchPlan plan_scratch(const cw_params& prm, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t big_slots, uint32_t scale = 1, uint32_t tmax = 1024,
+                         bool pf_full = false) {
     ScratchPlan p;
     memset(&p, 0, sizeof(p));
     p.solid_cap = (16ull * n_words) / prm.solid + n_windows + 16;
@@ -148,10 +152,11 @@ ScratchPlan plan_scratch(const cw_params& prm, uint32_t n_windows, uint32_t n_se
     p.ablock_units = ((uint64_t)n_seqs * (2ull * tmax + 2 + tmax / 8) + (uint64_t)n_windows * (tmax * (4ull + 8 + 8 + 8) + 256)) / 16 + 64;
     put(p.ablock, (size_t)p.ablock_units * 16);
     /* the position matrix of a window whose matrix does not fit LDS: up to tmax anchors x the sequences of a pile -- sixteen times the batch's mean depth, at
-       least 1024 and at most ~4096 of them (round 6; 4100 whatever the batch through round 5: 2.1 GB of a driver job's plan at depth 30).  A pile deeper
-       than that with more anchors than LDS holds is a reported capacity (CW_WHY_MATRIX), as it always was beyond 4100 */
+       least 1024 and at most ~4096 of them (round 6; 4100 whatever the batch through round 5: 2.1 GB of a driver job's plan at depth 30).  The mean depth
+       says nothing about the deepest pile, so a window that stops on this slot (CW_WHY_MATRIX) is run again with the slot at kPfRowsMax rows (pf_full,
+       grow_if_that_helps): whether it fits does not depend on its neighbours.  Beyond kPfRowsMax it is a reported capacity, as it always was */
     const uint64_t mean_n = n_windows ? (uint64_t)n_seqs / n_windows + 1 : 1;
-    const uint64_t pf_n = mean_n * 16 < 1024 ? 1024 : mean_n * 16 > 4100 ? 4100 : mean_n * 16;
+    const uint64_t pf_n = pf_full ? kPfRowsMax : mean_n * 16 < 1024 ? 1024 : mean_n * 16 > kPfRowsMax ? kPfRowsMax : mean_n * 16;
     p.pfall_elems = (uint64_t)tmax * pf_n;
     const size_t idx_wgs = n_windows < (uint32_t)cus ? n_windows : (size_t)cus; /* work-groups of the index kernel: one fallback slot each */
     put(p.pfall, idx_wgs * p.pfall_elems * 2);
@@ -164,6 +169,22 @@ ScratchPlan plan_scratch(const cw_params& prm, uint32_t n_windows, uint32_t n_se
     put(p.finbig, (size_t)64 * 3 * CW_FIN_CB_BIG);
     p.total = o;
     return p;
+}
+
+/* The largest batch a plan for templates of tmax k-mers can address: per-window offsets into the segment table and the arena are 32-bit, and
+   their totals are n_windows x (tmax + 2) and n_windows x (16 (tmax + 16) + 4096) at scale 1 -- at most CW_MAX_BATCH_WINDOWS (include/consent_amd.h
+   cw_max_batch_windows).  115 704 windows at tmax 2048, CW_MAX_BATCH_WINDOWS at the default 1024. */
+uint32_t max_batch_windows(uint32_t tmax) {
+    const uint64_t per_seg = (uint64_t)tmax + 2, per_arena = 16ull * (tmax + 16) + 4096;
+    uint64_t n = CW_MAX_BATCH_WINDOWS;
+    n = std::min<uint64_t>(n, 0xFFFFFFFFull / per_seg);
+    n = std::min<uint64_t>(n, 0xFFFFFFFFull / per_arena);
+    return (uint32_t)n;
+}
+
+uint32_t plan_tmax(uint32_t k, uint32_t max_template_len) { /* cw_configure's number */
+    uint32_t kmers = max_template_len >= k ? max_template_len - k + 1u : 1u;
+    return kmers < 128u ? 128u : kmers;
 }
 
 int ensure(void** ptr, size_t* have, size_t need) {
@@ -330,21 +351,22 @@ void cw_destroy(cw_engine* e) {
 namespace {
 
 /* the body of cw_run_device; the caller holds e->mu */
-int run_device_locked(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream) {
+/* pf_full: the index kernel's global matrix slot at its full kPfRowsMax rows (a re-run after CW_WHY_MATRIX, grow_if_that_helps) */
+int run_device_locked(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream, bool pf_full = false) {
     if (!e || !batch || !res || !res->cons || !res->cons_off || !res->cons_len || !res->win_status) return CW_E_INVALID;
     if ((res->solid != nullptr) != (res->solid_off != nullptr) || (res->solid != nullptr) != (res->solid_len != nullptr)) return CW_E_INVALID;
     if (batch->n_windows == 0) return CW_OK;
     if (!batch->win_first_seq || !batch->seq_len || !batch->seq_word_off || !batch->bases) return CW_E_INVALID;
     /* per-window offsets into the arena, the solid table and the segment table are 32-bit (WinInfo, PoaTask): a batch is
-       limited so that none of them can wrap -- split larger inputs (the library's own drivers do) */
-    if (batch->n_windows > CW_MAX_BATCH_WINDOWS) return CW_E_INVALID;
+       limited so that none of them can wrap -- split larger inputs (the library's own drivers do; cw_max_batch_windows) */
+    if (batch->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
     CW_HIP(hipSetDevice(e->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
 
     uint32_t big_slots = 64; /* tier G's kernel is sixteen work-groups of four waves at most (big_wgs below): 64 slabs of 16.8 MB are all it can use (256 through round 5: 4.3 GB) */
     if (const char* env = CW_AID_ENV("CW_BIG_SLOTS")) { int v = atoi(env); if (v >= 4 && v <= 4096) big_slots = (uint32_t)v / 4 * 4; }
     const int cus = e->prop.multiProcessorCount > 0 ? e->prop.multiProcessorCount : 256;
-    const ScratchPlan p = plan_scratch(e->prm, batch->n_windows, batch->n_seqs, batch->n_words, cus, big_slots, e->cap_scale, e->tmax_plan);
+    const ScratchPlan p = plan_scratch(e->prm, batch->n_windows, batch->n_seqs, batch->n_words, cus, big_slots, e->cap_scale, e->tmax_plan, pf_full);
     if (p.solid_cap > 0xFFFFFFFFull || p.seg_cap > 0xFFFFFFFFull || p.arena_cap > 0xFFFFFFFFull) return CW_E_INVALID; /* see CW_MAX_BATCH_WINDOWS */
     e->last_windows = batch->n_windows; e->last_seqs = batch->n_seqs; e->last_words = batch->n_words; e->last_big_slots = big_slots;
     e->last_ctr_off = p.ctr;
@@ -466,7 +488,9 @@ int run_device_locked(cw_engine* e, const cw_batch* batch, const cw_result* res,
     CW_HIP(hipMemsetAsync(sc.over_list[3], 0xFF, (size_t)p.task_cap * 4, st)); /* live queue: an entry is its own flag */
     sid = stage_begin(e, st, "setup");
     cw_setup_need_kernel<<<(batch->n_windows + 3) / 4, 256, 0, st>>>(db, sc, e->prm);
-    cw_setup_kernel<<<1, 1024, 0, st>>>(db, sc, e->prm, p.solid_cap, p.seg_cap, p.arena_cap, p.arena_scale);
+    uint32_t arena_div = 1; /* test aid: every window's arena slice divided, so that an ordinary window stops on it at x1 (CW_WHY_ARENA) */
+    if (const char* env = CW_AID_ENV("CW_ARENA_DIV")) { const int v = atoi(env); if (v >= 2 && v <= 4096) arena_div = (uint32_t)v; }
+    cw_setup_kernel<<<1, 1024, 0, st>>>(db, sc, e->prm, p.solid_cap, p.seg_cap, p.arena_cap, p.arena_scale, e->tmax_plan, arena_div);
     stage_end(e, st, sid);
     sid = stage_begin(e, st, "index");
     {
@@ -615,16 +639,26 @@ int cw_run_device(cw_engine* e, const cw_batch* batch, const cw_result* res, voi
     return run_device_locked(e, batch, res, hip_stream);
 }
 
+uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len) {
+    const uint32_t t = plan_tmax(k ? k : 1u, max_template_len);
+    return max_batch_windows(t < (uint32_t)CW_TMAX ? t : (uint32_t)CW_TMAX);
+}
+
+uint32_t cw_max_batch_windows(cw_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return max_batch_windows(e->tmax_plan);
+}
+
 /* Templates longer than the default plan provides for (include/consent_amd.h): the scratch plan and the chain kernel's instance follow; takes effect with
    the engine's next run. */
 int cw_configure(cw_engine* e, uint32_t max_template_len) {
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
-    const uint32_t k = e->prm.k ? e->prm.k : 1u;
-    uint32_t kmers = max_template_len >= k ? max_template_len - k + 1u : 1u;
+    /* (a caller that knows its windows are shorter than the default plan assumes -- the native driver: `-l 500` is 492 k-mers -- gets the smaller
+       plan: anchor blocks, segment slots and the arena go by this number, at least 128) */
+    const uint32_t kmers = plan_tmax(e->prm.k ? e->prm.k : 1u, max_template_len);
     if (kmers > (uint32_t)CW_TMAX) return CW_E_INVALID; /* beyond what the index kernel holds (CW_WHY_TEMPLATE) */
-    if (kmers < 128u) kmers = 128u; /* (a caller that knows its windows are shorter than the default plan assumes -- the native driver: `-l 500` is 492
-                                       k-mers -- gets the smaller plan: anchor blocks, segment slots and the arena go by this number) */
     e->tmax_plan = kmers;
     return CW_OK;
 }
@@ -688,6 +722,17 @@ int cw_debug_plan(uint32_t k, uint32_t solid, uint32_t n_windows, uint32_t n_seq
                             slab(0), slab(1), slab(2), slab(3), slab(4), (uint64_t)p.hslab - p.qslab + ((uint64_t)p.ablock - p.hslab), p.ablock_units * 16,
                             (uint64_t)(p.exg - p.pfall) + (uint64_t)(p.tdbg - p.exg)};
     for (int i = 0; i < 15; ++i) out15[i] = v[i];
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): the capacities of that plan and the batch limit of its tmax (host arithmetic only). */
+int cw_debug_plan_caps(uint32_t k, uint32_t solid, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t scale, uint32_t tmax, int pf_full, uint64_t* out8) {
+    if (!out8 || !n_windows || !solid) return CW_E_INVALID;
+    cw_params prm{k, solid, 8, 2, 150};
+    const uint32_t t = tmax ? tmax : 1024;
+    const ScratchPlan p = plan_scratch(prm, n_windows, n_seqs, n_words, cus, 64, scale ? scale : 1, t, pf_full != 0);
+    const uint64_t v[8] = {p.total, p.solid_cap, p.seg_cap, p.arena_cap, p.arena_scale, p.pfall_elems / t, max_batch_windows(t), p.task_cap};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
     return CW_OK;
 }
 
@@ -992,7 +1037,11 @@ int cw_debug_stitch_trace(cw_engine* e, uint32_t n_windows, uint32_t* out) {
  * H2D on its own stream, the kernels on the compute stream, the results compacted on the device (cw_pack_*: only the bytes the
  * windows actually produced cross PCIe, not the capacities the caller reserved), D2H on a third stream into pinned staging, then
  * scattered into the caller's arrays.  With two batches in flight the copies of one overlap the kernels of the other. */
-int cw_submit(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket) {
+static int submit_locked(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket, bool pf_full);
+int cw_submit(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket) { return submit_locked(e, b, r, ticket, false); }
+
+/* pf_full: see run_device_locked (cw_run's re-run after CW_WHY_MATRIX) */
+static int submit_locked(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket, bool pf_full) {
     if (!e || !b || !r || !ticket || !r->cons || !r->cons_off || !r->cons_len || !r->win_status) return CW_E_INVALID;
     *ticket = -1;
     if (b->n_windows && (!b->win_first_seq || !b->seq_len || !b->seq_word_off || !b->bases)) return CW_E_INVALID;
@@ -1008,6 +1057,7 @@ int cw_submit(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket) 
     const bool want_solid = r->solid != nullptr;
     if (want_solid && (!r->solid_off || !r->solid_len)) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
+    if (W > max_batch_windows(e->tmax_plan)) return CW_E_INVALID; /* cw_max_batch_windows: refused before anything is copied or launched */
     /* the copy streams exist only for callers of the host-batch path, and are created after the four kernel streams: the runtime
        multiplexes streams onto a handful of hardware queues in creation order, and two POA tiers that land on one queue run one after
        the other instead of side by side (measured: tier M1 started only when tier M2 had ended) */
@@ -1037,7 +1087,7 @@ int cw_submit(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket) 
     sl.o_slen = put((size_t)W * 4);
     sl.o_pc = put(sl.cons_cap); sl.o_ps = put(sl.solid_cap * 4); /* the compacted copies */
     const size_t o_pco = put((size_t)(W + 1) * 8), o_pso = put((size_t)(W + 1) * 8);
-    sl.o_tot = put(40);
+    sl.o_tot = put(48);
     sl.o_cons = o_cons; sl.o_solid = o_solid;
     const size_t out_bytes = o;
     int rc = ensure(&sl.dev_in, &sl.dev_in_bytes, in_bytes);
@@ -1067,7 +1117,7 @@ int cw_submit(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket) 
     dr.solid = want_solid ? (uint32_t*)(dout + o_solid) : nullptr;
     dr.solid_off = want_solid ? (const uint64_t*)(dout + o_soff) : nullptr;
     dr.solid_len = want_solid ? (uint32_t*)(dout + sl.o_slen) : nullptr;
-    rc = run_device_locked(e, &db, &dr, st);
+    rc = run_device_locked(e, &db, &dr, st, pf_full);
     if (rc) return rc;
     PackArgs pa;
     pa.n_windows = W; pa.cons = dr.cons; pa.cons_off = dr.cons_off; pa.cons_len = dr.cons_len; pa.win_status = dr.win_status;
@@ -1076,6 +1126,7 @@ int cw_submit(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket) 
     pa.pc_off = (uint64_t*)(dout + o_pco); pa.ps_off = (uint64_t*)(dout + o_pso); pa.totals = (uint64_t*)(dout + sl.o_tot);
     pa.win = (const WinInfo*)e->scratch; /* this batch's: the pack kernels follow its finish kernel on the compute stream */
     pa.used = (const uint32_t*)((const uint8_t*)e->scratch + e->last_ctr_off + offsetof(BatchCounters, n_tasks));
+    pa.pf_full_elems = (uint64_t)e->tmax_plan * kPfRowsMax;
     static_assert(offsetof(BatchCounters, n_members) == offsetof(BatchCounters, n_tasks) + 4, "cw_pack_scan_kernel reads the two counters as a pair");
     cw_pack_scan_kernel<<<1, 1024, 0, st>>>(pa);
     cw_pack_copy_kernel<<<(W + 3) / 4, 256, 0, st>>>(pa);
@@ -1086,13 +1137,14 @@ int cw_submit(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket) 
     return CW_OK;
 }
 
-static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* used = nullptr);
+static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* used = nullptr, uint32_t* why_matrix = nullptr);
 int cw_wait(cw_engine* e, int ticket) { return wait_ticket(e, ticket, nullptr); }
 
-/* why_tasks (may be NULL): how many windows of THIS ticket stopped on the batch's task / member / arena capacities */
+/* why_tasks (may be NULL): how many windows of THIS ticket stopped on the batch's task / member / arena capacities; why_matrix: on the matrix slot */
 /* used (may be NULL): this ticket's task and member counts */
-static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* used) {
+static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* used, uint32_t* why_matrix) {
     if (why_tasks) *why_tasks = 0;
+    if (why_matrix) *why_matrix = 0;
     if (used) used[0] = used[1] = 0xFFFFFFFFu;
     if (!e || ticket < 0 || ticket >= CW_SLOTS) return CW_E_INVALID;
     cw_slot& sl = e->slot[ticket];
@@ -1109,9 +1161,9 @@ static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* 
     const cw_result& r = sl.res;
     uint8_t* dout = (uint8_t*)sl.dev_out;
     hipStream_t co = e->copy_out;
-    uint64_t tot[5] = {0, 0, 0, 0, 0};
+    uint64_t tot[6] = {0, 0, 0, 0, 0, 0};
     int rc = CW_OK;
-    if (hipMemcpyAsync(tot, dout + sl.o_tot, 40, hipMemcpyDeviceToHost, co) != hipSuccess ||
+    if (hipMemcpyAsync(tot, dout + sl.o_tot, 48, hipMemcpyDeviceToHost, co) != hipSuccess ||
         hipMemcpyAsync(r.cons_len, dout + sl.o_clen, (size_t)W * 4, hipMemcpyDeviceToHost, co) != hipSuccess ||
         hipMemcpyAsync(r.win_status, dout + sl.o_stat, W, hipMemcpyDeviceToHost, co) != hipSuccess ||
         (sl.want_solid && hipMemcpyAsync(r.solid_len, dout + sl.o_slen, (size_t)W * 4, hipMemcpyDeviceToHost, co) != hipSuccess) ||
@@ -1119,6 +1171,7 @@ static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* 
         return fail(CW_E_NO_DEVICE);
     if (tot[0] > sl.cons_cap || tot[1] > sl.solid_cap) return fail(CW_E_INTERNAL);
     if (why_tasks) *why_tasks = tot[2];
+    if (why_matrix) *why_matrix = (uint32_t)tot[5];
     if (used) { used[0] = (uint32_t)tot[3]; used[1] = (uint32_t)tot[4]; }
     const size_t need = align_up(tot[0], 256) + tot[1] * 4 + 256;
     if (sl.pin_out_bytes < need) {
@@ -1155,15 +1208,18 @@ static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* 
    heuristics of the batch)?  Then the plan grows (x4, up to x64) and the caller runs the batch again -- if the larger plan is one the engine can
    actually run: inside the 32-bit offsets (plan_scratch clamps the arena's own scale) and inside the device's free memory.  A scale that is not
    is refused here, and the run that has finished stands with its overflow statuses (it used to end the batch with CW_E_INVALID or
-   CW_E_NOMEM).  known_any: -1 = look at the last run's WinInfo in scratch (cw_run_device_sync: the caller has just waited for that very run);
-   0 / 1 / 2 / 3 = the caller knows from its own ticket which kinds of such windows exist (bit 0 task / member slots, bit 1 arena slices) (cw_run: scratch may already belong to another thread's batch). */
-static int grow_if_that_helps(cw_engine* e, bool* again, hipStream_t st, int known_any, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words) {
+   CW_E_NOMEM).  Windows stopped on the index kernel's global matrix slot (CW_WHY_MATRIX: sized from the batch's mean depth) have the batch run
+   again with that slot at its full kPfRowsMax rows (*pf_full, for the re-run only: the scale stays) -- unless each of them needs more than that
+   (the index kernel leaves the need in WinInfo::arena_used): a pile too deep for any slot does not make the batch run twice.  known_any: -1 = look at the last run's
+   WinInfo in scratch (cw_run_device_sync: the caller has just waited for that very run); 0..7 = the caller knows from its own ticket which kinds
+   of such windows exist (bit 0 task / member slots, bit 1 arena slices, bit 2 the matrix slot) (cw_run: scratch may already belong to another
+   thread's batch). */
+static int grow_if_that_helps(cw_engine* e, bool* again, bool* pf_full, hipStream_t st, int known_any, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words) {
     *again = false;
     std::lock_guard<std::mutex> lk(e->mu);
-    if (!e->scratch || n_windows == 0 || e->cap_scale >= 64u) return CW_OK;
-    if (CW_AID_ENV("CW_TASK_CAP") || CW_AID_ENV("CW_MEMBER_CAP")) return CW_OK; /* (test aids that shrink exactly these capacities) */
+    if (!e->scratch || n_windows == 0) return CW_OK;
     CW_HIP(hipSetDevice(e->device));
-    int kinds = known_any > 0 ? known_any : 0; /* bit 0: windows stopped on task / member slots, bit 1: on their arena slices */
+    int kinds = known_any > 0 ? known_any : 0; /* bit 0: windows stopped on task / member slots, bit 1: on their arena slices, bit 2: on the matrix slot */
     if (known_any < 0) {
         if (e->last_windows != n_windows) return CW_OK;
         /* copies on the caller's stream, not hipMemcpy: the null stream would wait for every other stream of the device -- the other worker's job */
@@ -1175,21 +1231,26 @@ static int grow_if_that_helps(cw_engine* e, bool* again, hipStream_t st, int kno
         CW_HIP(hipMemcpyAsync(wi.data(), e->scratch, (size_t)e->last_windows * sizeof(WinInfo), hipMemcpyDeviceToHost, st));
         CW_HIP(hipStreamSynchronize(st));
         /* (windows stopped for other reasons stay stopped: the loop ends when no window names these capacities, or at x64) */
-        for (const WinInfo& w : wi) if (w.status == CW_WIN_OVERFLOW) kinds |= w.pad_ == CW_WHY_TASKS ? 1 : w.pad_ == CW_WHY_ARENA ? 2 : 0;
+        for (const WinInfo& w : wi)
+            if (w.status == CW_WIN_OVERFLOW)
+                kinds |= w.pad_ == CW_WHY_TASKS ? 1 : w.pad_ == CW_WHY_ARENA ? 2 : w.pad_ == CW_WHY_MATRIX && w.arena_used <= (uint64_t)e->tmax_plan * kPfRowsMax ? 4 : 0;
     }
+    if (CW_AID_ENV("CW_TASK_CAP") || CW_AID_ENV("CW_MEMBER_CAP")) kinds &= 4; /* (test aids that shrink exactly the task / member capacities) */
     if (!kinds) return CW_OK;
-    const uint32_t next = e->cap_scale * 4u;
     const int cus = e->prop.multiProcessorCount > 0 ? e->prop.multiProcessorCount : 256;
-    const ScratchPlan p = plan_scratch(e->prm, n_windows, n_seqs, n_words, cus, e->last_big_slots ? e->last_big_slots : 64, next, e->tmax_plan);
-    {   /* does the larger plan grow what ran out?  (the arena's own scale is clamped to 32-bit offsets: a batch stopped on its arena slices
+    const uint32_t bs = e->last_big_slots ? e->last_big_slots : 64;
+    const ScratchPlan cur = plan_scratch(e->prm, n_windows, n_seqs, n_words, cus, bs, e->cap_scale, e->tmax_plan, *pf_full);
+    const bool pf_grows = (kinds & 4) && cur.pfall_elems < (uint64_t)e->tmax_plan * kPfRowsMax;
+    uint32_t next = e->cap_scale;
+    if ((kinds & 3) && e->cap_scale < 64u) {
+        /* does the larger plan grow what ran out?  (the arena's own scale is clamped to 32-bit offsets: a batch stopped on its arena slices
            at a clamped scale is the same batch with the same arena at x4, x16 and x64) */
-        const ScratchPlan cur = plan_scratch(e->prm, n_windows, n_seqs, n_words, cus, e->last_big_slots ? e->last_big_slots : 64, e->cap_scale, e->tmax_plan);
-        const bool helps = ((kinds & 1) && (p.task_cap > cur.task_cap || p.member_cap > cur.member_cap)) || ((kinds & 2) && p.arena_scale > cur.arena_scale);
-        if (!helps) {
-            fprintf(stderr, "[consent_amd] windows stopped on the batch's %s capacity; a plan x%u does not enlarge it: keeping the run's result\n", (kinds & 2) ? "arena" : "task / member", next);
-            return CW_OK;
-        }
+        const ScratchPlan up = plan_scratch(e->prm, n_windows, n_seqs, n_words, cus, bs, e->cap_scale * 4u, e->tmax_plan, *pf_full);
+        if (((kinds & 1) && (up.task_cap > cur.task_cap || up.member_cap > cur.member_cap)) || ((kinds & 2) && up.arena_scale > cur.arena_scale)) next = e->cap_scale * 4u;
+        else fprintf(stderr, "[consent_amd] windows stopped on the batch's %s capacity; a plan x%u does not enlarge it: keeping the run's result\n", (kinds & 2) ? "arena" : "task / member", e->cap_scale * 4u);
     }
+    if (next == e->cap_scale && !pf_grows) return CW_OK;
+    const ScratchPlan p = plan_scratch(e->prm, n_windows, n_seqs, n_words, cus, bs, next, e->tmax_plan, *pf_full || pf_grows);
     size_t free_b = 0, total_b = 0;
     const bool mem_known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
     if (!mem_known) (void)hipGetLastError();
@@ -1197,12 +1258,16 @@ static int grow_if_that_helps(cw_engine* e, bool* again, hipStream_t st, int kno
     const bool fits = p.solid_cap <= 0xFFFFFFFFull && p.seg_cap <= 0xFFFFFFFFull && p.arena_cap <= 0xFFFFFFFFull &&
                       (!mem_known || p.total <= e->scratch_bytes || p.total - e->scratch_bytes + margin <= free_b);
     if (!fits) {
-        fprintf(stderr, "[consent_amd] windows stopped on the batch's task / member / arena capacities; a plan x%u (%.1f GB) does not fit this device now: keeping the run's result\n",
+        fprintf(stderr, "[consent_amd] windows stopped on the batch's task / member / arena / matrix capacities; a plan x%u (%.1f GB) does not fit this device now: keeping the run's result\n",
                 next, (double)p.total / 1e9);
         return CW_OK;
     }
-    e->cap_scale = next; *again = true;
-    fprintf(stderr, "[consent_amd] windows stopped on the batch's task / member / arena capacities: running the batch again with the plan x%u\n", e->cap_scale);
+    if (pf_grows) *pf_full = true;
+    if (next != e->cap_scale) {
+        e->cap_scale = next;
+        fprintf(stderr, "[consent_amd] windows stopped on the batch's task / member / arena capacities: running the batch again with the plan x%u\n", e->cap_scale);
+    }
+    *again = true;
     return CW_OK;
 }
 
@@ -1235,10 +1300,11 @@ static void decay_scale(cw_engine* e, hipStream_t st, uint32_t n_windows, uint32
    with a larger plan (cw_private.h; what the native driver and cw_run call: the asynchronous cw_run_device cannot look at its own result) */
 int cw_run_device_sync(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream) {
     if (!e || !batch) return CW_E_INVALID;
-    bool grown = false;
+    bool grown = false, pf_full = false;
     uint32_t scale_before = 1;
     for (;;) {
-        int rc = cw_run_device(e, batch, res, hip_stream);
+        int rc;
+        { std::lock_guard<std::mutex> lk(e->mu); rc = run_device_locked(e, batch, res, hip_stream, pf_full); }
         if (rc != CW_OK) {
             if (grown && (rc == CW_E_INVALID || rc == CW_E_NOMEM)) { /* the larger plan could not be set up after all (memory went to another engine meanwhile):
                                                                          no kernel of the re-run was launched, the run before it stands, the scale goes back */
@@ -1253,7 +1319,7 @@ int cw_run_device_sync(cw_engine* e, const cw_batch* batch, const cw_result* res
         CW_HIP(hipStreamSynchronize(st));
         bool again = false;
         { std::lock_guard<std::mutex> lk(e->mu); scale_before = e->cap_scale; }
-        if ((rc = grow_if_that_helps(e, &again, st, -1, batch->n_windows, batch->n_seqs, batch->n_words)) != CW_OK) return rc;
+        if ((rc = grow_if_that_helps(e, &again, &pf_full, st, -1, batch->n_windows, batch->n_seqs, batch->n_words)) != CW_OK) return rc;
         if (!again) {
             if (!grown) decay_scale(e, st, batch->n_windows, batch->n_seqs, batch->n_words);
             return CW_OK;
@@ -1263,25 +1329,26 @@ int cw_run_device_sync(cw_engine* e, const cw_batch* batch, const cw_result* res
 }
 
 int cw_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
-    bool grown = false;
+    bool grown = false, pf_full = false;
     uint32_t scale_before = 1;
     int first_rc = CW_OK;
     for (;;) {
         int t = -1;
-        int rc = cw_submit(e, b, r, &t);
+        int rc = submit_locked(e, b, r, &t, pf_full);
         if (rc != CW_OK) {
             if (grown && (rc == CW_E_INVALID || rc == CW_E_NOMEM)) { std::lock_guard<std::mutex> lk(e->mu); e->cap_scale = scale_before; return first_rc; } /* see cw_run_device_sync */
             return rc;
         }
         uint64_t why_tasks = 0;
-        uint32_t used[2];
-        const int wrc = wait_ticket(e, t, &why_tasks, used);
+        uint32_t used[2], why_matrix = 0;
+        const int wrc = wait_ticket(e, t, &why_tasks, used, &why_matrix);
         if (wrc != CW_OK && wrc != CW_E_CAPACITY) return wrc;
         bool again = false;
         { std::lock_guard<std::mutex> lk(e->mu); scale_before = e->cap_scale; }
         /* the decision comes from this ticket's own totals (cw_pack_scan_kernel counts the windows stopped on CW_WHY_TASKS): other threads may have
            submitted since, and the WinInfo in scratch may be theirs */
-        if (wrc == CW_E_CAPACITY && (rc = grow_if_that_helps(e, &again, e->stream, ((uint32_t)why_tasks ? 1 : 0) | ((why_tasks >> 32) ? 2 : 0), b->n_windows, b->n_seqs, b->n_words)) != CW_OK) return rc;
+        if (wrc == CW_E_CAPACITY && (rc = grow_if_that_helps(e, &again, &pf_full, e->stream, ((uint32_t)why_tasks ? 1 : 0) | ((why_tasks >> 32) ? 2 : 0) | (why_matrix ? 4 : 0),
+                                                             b->n_windows, b->n_seqs, b->n_words)) != CW_OK) return rc;
         if (!again) {
             if (!grown && wrc == CW_OK) decay_scale(e, e->stream, b->n_windows, b->n_seqs, b->n_words, used); /* the host path never lowered a grown scale */
             return wrc;

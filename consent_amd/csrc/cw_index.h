@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(256) cw_setup_need_kernel(DevBatch b, DevScrat
 }
 
 __global__ void __launch_bounds__(1024) cw_setup_kernel(DevBatch b, DevScratch sc, cw_params prm, uint64_t solid_total_cap,
-                                                         uint64_t seg_total_cap, uint64_t arena_total_cap, uint32_t arena_scale) {
+                                                         uint64_t seg_total_cap, uint64_t arena_total_cap, uint32_t arena_scale, uint32_t tmax, uint32_t arena_div) {
     __shared__ uint32_t part[4][1024];
     __shared__ uint64_t run[4];
     const int tid = threadIdx.x;
@@ -92,13 +92,19 @@ __global__ void __launch_bounds__(1024) cw_setup_kernel(DevBatch b, DevScratch s
         const uint32_t w = w0 + tid;
         uint32_t need_solid = 0, need_seg = 0, need_arena = 0, need_ab = 0;
         uint32_t nk = 0, tl = 0, ns = 0;
+        bool too_long = false;
         if (w < b.n_windows) {
             ns = sc.win[w].n_seqs; tl = sc.win[w].tpl_len; nk = sc.win[w].n_kmers; /* cw_setup_need_kernel */
-            need_solid = nk / prm.solid + 1;
-            need_seg = (tl >= prm.k) ? tl - prm.k + 3 : 1;
-            need_arena = (16 * tl + 4096) * arena_scale;
-            const uint32_t nk0 = (tl >= prm.k && tl - prm.k + 1 <= CW_TMAX) ? tl - prm.k + 1 : 0;
-            need_ab = (uint32_t)(cw_ab_bytes(nk0, ns, ns) >> 4);
+            /* a template of more k-mers than the plan provides for (tmax: 1024, or cw_configure's number) stops here, whatever its batch: its slices
+               would be larger than the plan's per-window share, and whether they fit would depend on the slack its neighbours leave */
+            too_long = tl >= prm.k && tl - prm.k + 1 > tmax;
+            if (!too_long) {
+                need_solid = nk / prm.solid + 1;
+                need_seg = (tl >= prm.k) ? tl - prm.k + 3 : 1;
+                need_arena = (16 * tl + 4096) * arena_scale / arena_div; /* (arena_div: 1 but for a test aid, CW_ARENA_DIV) */
+                const uint32_t nk0 = tl >= prm.k ? tl - prm.k + 1 : 0;
+                need_ab = (uint32_t)(cw_ab_bytes(nk0, ns, ns) >> 4);
+            }
         }
         part[0][tid] = need_solid; part[1][tid] = need_seg; part[2][tid] = need_arena; part[3][tid] = need_ab;
         __syncthreads();
@@ -126,6 +132,7 @@ __global__ void __launch_bounds__(1024) cw_setup_kernel(DevBatch b, DevScratch s
             wi.arena_base = (uint32_t)ab; wi.arena_cap = need_arena; wi.arena_used = 0;
             wi.ab_base = (uint32_t)kb; wi.ab_cap = need_ab; wi.pad_ = 0;
             if (over) { wi.status = CW_WIN_OVERFLOW; wi.pad_ = CW_WHY_SETUP; wi.solid_cap = wi.seg_cap = wi.arena_cap = wi.ab_cap = 0; wi.solid_base = wi.seg_base = wi.arena_base = wi.ab_base = 0; }
+            if (too_long) { wi.status = CW_WIN_OVERFLOW; wi.pad_ = CW_WHY_TEMPLATE; sc.ctr->any_overflow = 1; }
             sc.win[w] = wi;
         }
         __syncthreads();
@@ -1006,7 +1013,8 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
         /* LDS needs: the matrix (A*Np u16) + presence bitsets (A*Nw u64) + dirty list (N u16) */
         const bool pg = !tfit && (uint64_t)A * Np * 2 + (uint64_t)A * Nw * 8 + (uint64_t)N * 2 + 16 > (uint64_t)p_cap * 2;
         if (pg && (uint64_t)A * Np > sc.p_fallback_elems) {
-            if (tid == 0) { wi->status = CW_WIN_OVERFLOW; wi->pad_ = CW_WHY_MATRIX; sc.ctr->any_overflow = 1; }
+            /* (arena_used of a window stopped here: the slot elements it needed -- the host re-runs the batch with a larger slot only if that helps) */
+            if (tid == 0) { wi->status = CW_WIN_OVERFLOW; wi->pad_ = CW_WHY_MATRIX; wi->arena_used = (uint64_t)A * Np > 0xFFFFFFFFull ? 0xFFFFFFFFu : A * Np; sc.ctr->any_overflow = 1; }
             __builtin_amdgcn_wave_barrier(); /* the wave meets again before the back edge (see cw_stitch.h) */
             continue;
         }
@@ -1161,7 +1169,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
         {
             uint8_t* blk = sc.ablock + ((size_t)w_ab_base << 4);
             if (cw_ab_bytes(A, N, n_dirty, n_rows) > ((uint64_t)w_ab_cap << 4)) { /* cannot happen: sized from the template length */
-                if (tid == 0) { wi->status = CW_WIN_OVERFLOW; wi->pad_ = CW_WHY_MATRIX; sc.ctr->any_overflow = 1; }
+                if (tid == 0) { wi->status = CW_WIN_OVERFLOW; wi->pad_ = CW_WHY_MATRIX; wi->arena_used = 0xFFFFFFFFu; sc.ctr->any_overflow = 1; } /* (no slot helps) */
                 __builtin_amdgcn_wave_barrier(); /* the wave meets again before the back edge (see cw_stitch.h) */
                 continue;
             }

@@ -13,12 +13,19 @@ extern "C" {
 #endif
 
 /* copies the engine's per-window bookkeeping of the last run to host, 16 uint32 per window: status, n_seqs, tpl_len, n_kmers,
- * solid_base, solid_cap, n_solid, seg_base, seg_cap, n_segs, arena_base, arena_cap, arena_used, 3 reserved */
+ * solid_base, solid_cap, n_solid, seg_base, seg_cap, n_segs, arena_base, arena_cap, arena_used (of a window stopped on CW_WHY_MATRIX: the
+ * matrix slot elements it needed), ab_base, ab_cap, why (CW_WHY_*) */
 int cw_debug_win_info(cw_engine* e, uint32_t n_windows, uint32_t* out16);
 /* The scratch plan of a batch of these dimensions on a device of `cus` compute units, in bytes, without a device: out[0] total, then windows' records,
    solid table, segments, arena, tasks + members, tier lists, slabs of tiers S, M1, M2, L, G, tier Q's + H's rows, anchor blocks, position-matrix
    fallbacks, exact-count fallbacks, finish pass buffers (15 numbers; tools/plan_sizes.py). */
 int cw_debug_plan(uint32_t k, uint32_t solid, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t scale, uint32_t tmax, uint64_t* out15);
+/* The capacities of that plan (pf_full: the matrix slot of a re-run after CW_WHY_MATRIX), without a device: out[0] total bytes, [1] solid table entries,
+   [2] segment slots, [3] arena bytes, [4] the arena's scale after its 32-bit clamp, [5] rows per template k-mer of the matrix slot, [6] the batch limit
+   of an engine with this tmax (cw_max_batch_windows), [7] task slots. */
+int cw_debug_plan_caps(uint32_t k, uint32_t solid, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t scale, uint32_t tmax, int pf_full, uint64_t* out8);
+/* cw_max_batch_windows of an engine that cw_configure(max_template_len) will be called on (the native driver sizes its jobs before it has engines) */
+uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len);
 
 /* a32[i] += add32 for i < n32 and a64[i] += add64 for i < n64, on the stream: how the driver turns the window -> sequence and sequence -> word
    offsets of a pile extracted in several calls into offsets of one batch (cw_driver.cpp) */
@@ -28,7 +35,7 @@ int cw_add_offsets_device(uint32_t* a32, uint64_t n32, uint32_t add32, uint64_t*
  * 8+5t..12+5t: metadata, fill, traceback, merge, consensus; 36+t: the longest single task of tier t; 72+12t..: row counts of a -DCW_DIAG
  * build).  The caller passes the capacity of each buffer in words and receives min(capacity, available); the counts come back through
  * counters_n / prof_n when those are not NULL. */
-/* cw_run_device + wait for the stream + one more run with larger task / member / arena capacities when windows stopped on those only */
+/* cw_run_device + wait for the stream + one more run with larger task / member / arena capacities, or the full matrix slot, when windows stopped on those only */
 int cw_run_device_sync(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream);
 int cw_debug_profile(cw_engine* e, uint32_t* counters, uint32_t counters_cap, unsigned long long* prof, uint32_t prof_cap, uint32_t* counters_n, uint32_t* prof_n);
 

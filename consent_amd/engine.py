@@ -132,6 +132,8 @@ def _load(p):
     lib.cw_poll.argtypes = [C.c_void_p]
     lib.cw_poll.restype = C.c_int
     lib.cw_configure.argtypes = [C.c_void_p, C.c_uint32]
+    lib.cw_max_batch_windows.argtypes = [C.c_void_p]
+    lib.cw_max_batch_windows.restype = C.c_uint32
     lib.cw_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_int)]
     lib.cw_debug_win_info.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.cw_debug_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -207,6 +209,21 @@ class HostBatch:
     def slice(self, w0, w1):
         s0, s1 = int(self.win_first_seq[w0]), int(self.win_first_seq[w1])
         return HostBatch(self.win_first_seq[w0 : w1 + 1] - s0, self.seq_len[s0:s1], self.seq_word_off[s0:s1], self.bases)
+
+
+def concat_batches(batches):
+    """One HostBatch of the windows of `batches` (HostBatch, slices included), in order: sequences and words appended, offsets moved."""
+    wfs, lens, offs, bases = [np.zeros(1, np.uint32)], [], [], []
+    s_run = w_run = 0
+    for b in batches:
+        s0, s1 = int(b.win_first_seq[0]), int(b.win_first_seq[-1])
+        wfs.append(b.win_first_seq[1:].astype(np.uint64) - s0 + s_run)
+        lens.append(b.seq_len[s0:s1])
+        offs.append(b.seq_word_off[s0:s1].astype(np.uint64) + w_run)
+        bases.append(b.bases)
+        s_run += s1 - s0
+        w_run += len(b.bases)
+    return HostBatch(np.concatenate(wfs).astype(np.uint32), np.concatenate(lens), np.concatenate(offs), np.concatenate(bases))
 
 
 def pack_piles(piles):
@@ -525,6 +542,10 @@ class Engine:
         """cw_configure: the longest template (window) this engine will see, before its first run -- templates beyond 1024 + k - 1 bases need a larger
         scratch plan and the chain kernel's long instance (up to 2048 + k - 1 bases)."""
         _check(self.lib, self.lib.cw_configure(self.handle, int(max_template_len)), "cw_configure")
+
+    def max_batch_windows(self):
+        """cw_max_batch_windows: the largest batch this engine accepts under its current configuration (at most CW_MAX_BATCH_WINDOWS)."""
+        return int(self.lib.cw_max_batch_windows(self.handle))
 
     def idle(self):
         """cw_poll: True when the last run_device on this engine has completed (never blocks)."""

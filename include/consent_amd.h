@@ -103,7 +103,7 @@ const char* cw_strerror(int status);
  * of streams, and every entry point that takes a cw_engine* locks the engine's mutex for the time it enqueues work: calls from
  * several host threads on ONE engine are safe and are serialised; they do not run concurrently.  For concurrency use one engine per
  * host thread or per device (any number of engines may share a GPU; results do not depend on how windows are spread over engines,
- * batches or GPUs).  cw_run_device is asynchronous: the caller's device buffers must stay valid, and the engine's next call on
+ * batches or GPUs, but for the capacity stops listed at CW_MAX_BATCH_WINDOWS).  cw_run_device is asynchronous: the caller's device buffers must stay valid, and the engine's next call on
  * another stream must be ordered by the caller, until that stream has been synchronised.  The host feeders (cw_index_reads,
  * cw_paf_*) keep their state in their own handles: one thread per handle (cw_paf_open starts parser threads of its own; they end in
  * cw_paf_close, which must come before cw_read_index_free of the index it was opened with).
@@ -117,24 +117,44 @@ void cw_destroy(cw_engine* e);
 /* Templates longer than 1024 + k - 1 bases (windows beyond the wrappers' `-l 500`: the reference takes any `-l`, src/main.cpp:46-47).  The engine takes
  * templates of up to 2048 + k - 1 bases; its scratch plan provides for 1024 k-mers per template unless told otherwise -- call this once, before the
  * first run, with the longest template the engine will see (the window size): anchor blocks, segment slots and the chain kernel's work-groups are then
- * sized for it (up to twice the scratch).  Without it, windows with longer templates may stop on a capacity (status 2: CW_WHY_SETUP / CW_WHY_ANCHORS),
- * never with a wrong result.  CW_E_INVALID beyond 2048 + k - 1 (such a window's status is 2, CW_WHY_TEMPLATE).  A caller whose windows are all SHORTER than
- * 1024 + k - 1 bases may say so too: the plan shrinks with the number (anchor blocks, segment slots, arena).  cw_run_correction calls it with its window size. */
+ * sized for it (up to twice the scratch).  A window whose template has more k-mers than the plan provides for (1024, or max_template_len - k + 1, at
+ * least 128) stops with status 2, CW_WHY_TEMPLATE, in every batch -- never a wrong result, and never an outcome that depends on its neighbours.
+ * CW_E_INVALID beyond 2048 + k - 1.  A caller whose windows are all SHORTER than 1024 + k - 1 bases may say so too: the plan shrinks with the number
+ * (anchor blocks, segment slots, arena).  The batch limit follows the number (cw_max_batch_windows).  cw_run_correction calls it with its window size. */
 int cw_configure(cw_engine* e, uint32_t max_template_len);
 
 /* Largest batch one call accepts (per-window offsets into the engine's scratch are 32-bit); CW_E_INVALID beyond it.  Split larger
- * inputs: results do not depend on the batch composition. */
+ * inputs: results do not depend on the batch composition, with the exceptions below.  cw_max_batch_windows(e) is the limit of an engine
+ * under its current configuration, at most CW_MAX_BATCH_WINDOWS: 131 072 up to 1775 template k-mers (cw_configure), 115 704 at 2048;
+ * cw_submit, cw_run and cw_run_device refuse a larger batch before anything is copied or launched, and so does every call whose batch has so
+ * many bases that its solid table would pass 2^32 entries (16 x n_words / solidThresh).
+ * What may depend on the batch.  A window's consensus and solid set never do, and neither does any outcome of a window that does not stop.
+ * Three capacities of a window are slices of what the batch's plan holds: its POA tasks and members (status 2, CW_WHY_TASKS), its slice of
+ * the segment arena (CW_WHY_ARENA) and the index kernel's position-matrix slot, sized from the batch's mean depth (CW_WHY_MATRIX).  Whether a
+ * window stops on one of these may depend on the batch:
+ *   - cw_run (and the native driver, cw_run_correction) run a batch again with a larger plan when windows stopped on them: tasks and arena
+ *     x4 up to x64, the matrix slot at its full 4100 rows a sequence.  The arena's scale stays inside 32-bit offsets -- x4 for batches of up
+ *     to 51 781 windows at the default plan, x2 up to 103 563 -- so a window stopped on CW_WHY_ARENA may be corrected in a small batch and stop
+ *     in a large one.  A re-run is also skipped when the larger plan does not fit the device's free memory at that moment (stderr says so):
+ *     then every such stop stands.
+ *   - cw_run_device and cw_submit + cw_wait run a batch once: a window may stop on CW_WHY_TASKS, CW_WHY_ARENA or CW_WHY_MATRIX in one batch
+ *     and be corrected in another (a deep pile among shallow windows, for one).  The caller may run such windows again in a batch of their own.
+ * Every other outcome -- a stop for any other reason, a template longer than the plan (CW_WHY_TEMPLATE) included -- is a function of the
+ * window, the parameters and the engine's cw_configure number alone. */
 #define CW_MAX_BATCH_WINDOWS 131072u
+uint32_t cw_max_batch_windows(cw_engine* e);
 
 /* Host buffers in, host buffers out: H2D, kernels, D2H of the bytes the windows actually produced (not of the reserved
- * capacities), synchronous.  Equivalent to cw_submit + cw_wait. */
+ * capacities), synchronous.  cw_submit + cw_wait, and then -- when windows stopped on a capacity of the batch's plan (CW_WHY_TASKS,
+ * CW_WHY_ARENA, CW_WHY_MATRIX) and a larger plan would hold them -- the same batch once more with that plan (see CW_MAX_BATCH_WINDOWS). */
 int cw_run(cw_engine* e, const cw_batch* batch, const cw_result* result);
 
 /* The same in two halves, so that a caller can keep the GPU busy: cw_submit enqueues the H2D copies and the kernels of a batch and
  * returns a ticket; cw_wait blocks until that batch is done and fills `result`.  Up to two batches may be in flight per engine
  * (submit n+1, then wait n: the copies of one overlap the kernels of the other); a third cw_submit returns CW_E_INVALID.  Every
  * array named by `batch` and `result` must stay valid and untouched until cw_wait has returned.  Arrays from cw_host_alloc (pinned)
- * are moved by real DMA that overlaps the kernels; plain pageable arrays work too, the runtime then stages them itself. */
+ * are moved by real DMA that overlaps the kernels; plain pageable arrays work too, the runtime then stages them itself.  The batch runs
+ * once: no re-run after capacity stops (CW_MAX_BATCH_WINDOWS says which stops that leaves depending on the batch). */
 int cw_submit(cw_engine* e, const cw_batch* batch, const cw_result* result, int* ticket);
 int cw_wait(cw_engine* e, int ticket);
 
@@ -143,7 +163,7 @@ int cw_host_alloc(void** ptr, size_t bytes);
 void cw_host_free(void* ptr);
 
 /* Every pointer inside batch/result is a DEVICE pointer; asynchronous on `hip_stream` (a hipStream_t,
- * NULL = the engine's own stream); statuses are checked by the caller after synchronising.  */
+ * NULL = the engine's own stream); statuses are checked by the caller after synchronising.  The batch runs once (as cw_submit). */
 int cw_run_device(cw_engine* e, const cw_batch* batch, const cw_result* result, void* hip_stream);
 
 /* 1 when everything the last cw_run_device on this engine launched has completed (or nothing was launched yet), 0 while it is

@@ -41,7 +41,7 @@
      matrix and packed fills (members of more than 63 bases, tiers M2 / L):  SMAX * (nodes + bases) <= 29000;
      recorded decisions (values x 4, members of at most 63 bases):            4 * SMAX * (nodes + 64) <= 29000.
    Every tier's capacities satisfy both up to SMAX = 16 except tier L's 1536 nodes + 1023 bases, which do up to SMAX = 11: beyond that tier L hands a
-   graph of more than 29000 / SMAX - 1023 nodes on to the int32 tier G (cw_poa.h CW_POA_NCAP_I16).  The oracle computes in int32. */
+   graph of more than 29000 / SMAX - 1023 nodes on to the int32 tier G (cw_poa.h cw_poa_slab_kernel: n_cap = CW_POA_I16_BOUND / CW_POA_SMAX - LC).  The oracle computes in int32. */
 #define CW_POA_ABS_(x) ((x) < 0 ? -(x) : (x))
 #define CW_POA_MAX2_(a, b) ((a) > (b) ? (a) : (b))
 #define CW_POA_SMAX CW_POA_MAX2_(CW_POA_MATCH, CW_POA_MAX2_(CW_POA_ABS_(CW_POA_MISMATCH), CW_POA_ABS_(CW_POA_GAP)))

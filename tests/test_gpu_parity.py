@@ -9,7 +9,7 @@ import pytest
 
 import consent_amd as ca
 import oracle_lib
-from consent_amd.engine import synth_host
+from consent_amd.engine import concat_batches, synth_host
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -512,7 +512,8 @@ def test_templates_of_up_to_2048_kmers_after_cw_configure():
     """Round 6 (`-l 1500` must run: the reference takes any window size, src/main.cpp:46-47).  The index kernel holds templates of up to 2048 k-mers (1024
     through round 5); an engine told about them (cw_configure: scratch plan, the chain kernel's 32 KB instance) corrects windows of 1500 and 2000 bases
     exactly as the oracle does -- synthetic piles at three depths, and a near-identical pile in which almost every template k-mer is an anchor (more than
-    1240 of them: what the default chain instance cannot hold) -- and a template beyond 2048 k-mers is a reported capacity (CW_WHY_TEMPLATE)."""
+    1240 of them: what the default chain instance cannot hold) -- and a template beyond 2048 k-mers is a reported capacity (CW_WHY_TEMPLATE), as is one
+    beyond the 1024 k-mers of an engine that was not configured, in every batch."""
     rng = random.Random(61)
     # k = 11 for the long windows: with k = 9 a 1500-base sequence holds a chance copy of one template k-mer in 170, whose misplaced hits make pieces of
     # more than the POA tiers' 1023 bases -- a reported capacity here, and the reason nobody runs k = 9 on such windows
@@ -538,11 +539,15 @@ def test_templates_of_up_to_2048_kmers_after_cw_configure():
     exp, _ = oracle_lib.oracle_run(prm, hb, threads=2)
     got = eng.run(hb)
     assert_same(got, exp, 2, "near-identical pile of 1800 bases")
-    # without cw_configure the same windows never give a wrong answer: they are corrected or stop on a capacity
+    # without cw_configure the same windows (templates of more than 1024 k-mers) stop with CW_WHY_TEMPLATE, whatever their batch -- alone or
+    # among windows the default plan holds, which used to lend them their slack (tests/test_gpu_batch_invariance.py)
     plain = ca.Engine(prm)
-    got2 = plain.run(hb)
-    for w in range(2):
-        assert int(got2.status[w]) == 2 or (int(got2.status[w]) == int(exp.status[w]) and got2.consensus(w) == exp.consensus(w))
+    short = synth_host(ca.SynthSpec.pacbio(24, 20, first_window=900))
+    for hb_plain, ws in ((hb, (0, 1)), (concat_batches([short, hb]), (24, 25))):
+        got2 = plain.run(hb_plain)
+        info = plain.win_info(hb_plain.n_windows)
+        for w in ws:
+            assert int(got2.status[w]) == 2 and int(info[w, 15]) == 4, (w, int(got2.status[w]), int(info[w, 15]))  # CW_WHY_TEMPLATE
     # beyond the index kernel's 2048 k-mers: a capacity, and cw_configure says so up front
     hb3 = ca.pack_piles([[rand_seq(rng, 2100)] * 4])
     got3 = eng.run(hb3)

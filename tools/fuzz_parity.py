@@ -1,5 +1,9 @@
 """Randomised differential test on the GPU box: engine vs oracle over random parameters, error profiles, depths and window
-lengths.  Prints one line per configuration and a summary; exit code 1 on any difference."""
+lengths.  Prints one line per configuration and a summary; exit code 1 on any difference.
+  python tools/fuzz_parity.py [seconds [seed]]
+  python tools/fuzz_parity.py --mixed [--configs N] [--seed S]   one batch of windows of several generators per parameter set (depths 0-3000,
+      lengths 60-2000, low-complexity families, template-only windows), each window compared with its result in a batch of its own kind and with
+      the oracle: a mixed-vs-own-kind difference is a difference, and so is a stop that happens only in the mixed batch"""
 import os
 import random
 import sys
@@ -11,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import consent_amd as ca  # noqa: E402
-from consent_amd.engine import synth_host  # noqa: E402
+from consent_amd.engine import concat_batches as concat, synth_host  # noqa: E402
 import oracle_lib  # noqa: E402
 
 
@@ -49,7 +53,89 @@ def low_complexity(batch, rng, kind):
             bases[o : o + len(pad) // 16] = (pad.reshape(-1, 16) << shifts[None, :]).sum(axis=1, dtype=np.uint64).astype(np.uint32)
 
 
+def outcome(res, info, w):
+    st = int(res.status[w])
+    return st, (int(info[w, 15]) if st == ca.WIN_OVERFLOW else 0), res.consensus(w), bytes(np.asarray(res.solid_kmers(w)).tobytes())
+
+
+def mixed(n_configs, seed):
+    rng = random.Random(seed)
+    n_win = n_diff = n_mixed_only = n_oracle = n_stops = 0
+    why_hist = {}
+    for cfg in range(n_configs):
+        k = rng.choice([7, 8, 9, 9, 9, 10, 11, 13])
+        prm = ca.Params(k, rng.choice([2, 3, 4, 4, 6]), rng.choice([2, 4, 8, 8, 12]), rng.choice([1, 2, 2, 5]), rng.choice([5, 20, 50, 150]))
+        kinds = []
+        for _ in range(rng.randint(3, 6)):
+            r = rng.random()
+            if r < 0.12:  # deep: a few piles of 1000-3000 sequences at low error (what keeps the counter table inside its capacity)
+                depth, wlen, err, nw = rng.choice([1000, 2000, 3000]), rng.choice([200, 300, 500]), rng.choice([3, 5, 10]), rng.randint(1, 2)
+            elif r < 0.22:  # template-only windows
+                depth, wlen, err, nw = 0, rng.choice([16, 60, 300, 900]), 0, rng.randint(1, 8)  # (synthetic windows have 16 bases at least)
+            elif r < 0.4:  # long windows (cw_configure below)
+                depth, wlen, err, nw = rng.choice([4, 12, 30]), rng.choice([1200, 1500, 2000]), rng.choice([30, 60, 120]), rng.randint(1, 6)
+            else:
+                depth, wlen, err = rng.choice([1, 2, 4, 8, 16, 30, 60, 100, 150]), rng.choice([60, 150, 300, 500, 500, 700, 900]), rng.choice([0, 10, 50, 120, 150, 200])
+                nw = max(2, min(48, 6000 // ((depth + 1) * max(wlen, 100) // 100)))
+            mix = rng.choice([(10, 60, 30), (30, 30, 40), (34, 33, 33)])
+            spec = ca.SynthSpec(rng.getrandbits(40), rng.getrandbits(20), nw, depth, wlen, err, mix[0], mix[1], mix[2], (wlen + 60 + wlen // 3) // 16 + 2)
+            b = synth_host(spec)
+            family = rng.choice(["random"] * 8 + ["homopolymer", "tandem", "identical"]) if depth else "random"
+            if family != "random":
+                low_complexity(b, rng, family)
+            kinds.append((b, f"d{depth}/l{wlen}/e{err}/{family}"))
+        conf = max(int(b.seq_len[b.win_first_seq[:-1]].max()) for b, _ in kinds)
+        conf = conf if conf > 1024 + k - 1 else None
+        own = []
+        eng = ca.Engine(prm)
+        try:
+            if conf:
+                eng.configure(conf)
+            for b, _ in kinds:
+                res = eng.run(b)
+                info = eng.win_info(b.n_windows)
+                own.append([outcome(res, info, w) for w in range(b.n_windows)])
+        finally:
+            eng.close()
+        order = [(i, w) for i, (b, _) in enumerate(kinds) for w in range(b.n_windows)]
+        rng.shuffle(order)
+        hb = concat([kinds[i][0].slice(w, w + 1) for i, w in order])
+        eng = ca.Engine(prm)
+        try:
+            if conf:
+                eng.configure(conf)
+            res = eng.run(hb)
+            info = eng.win_info(hb.n_windows)
+        finally:
+            eng.close()
+        exp, _ = oracle_lib.oracle_run(prm, hb, threads=16)
+        diff = mixed_only = bad_oracle = stops = 0
+        for pos, (i, w) in enumerate(order):
+            got, ref = outcome(res, info, pos), own[i][w]
+            if got[0] == ca.WIN_OVERFLOW:
+                stops += 1
+                why_hist[WHY.get(got[1], str(got[1]))] = why_hist.get(WHY.get(got[1], str(got[1])), 0) + 1
+                if ref[0] != ca.WIN_OVERFLOW:
+                    mixed_only += 1
+            if got != ref:
+                diff += 1
+                print(f"  window {pos} ({kinds[i][1]} #{w}): mixed status {got[0]} why {got[1]}, own kind status {ref[0]} why {ref[1]}", flush=True)
+            elif got[0] != ca.WIN_OVERFLOW and (got[0] != int(exp.status[pos]) or got[2] != exp.consensus(pos) or got[3] != bytes(np.asarray(exp.solid_kmers(pos)).tobytes())):
+                bad_oracle += 1
+                print(f"  window {pos} ({kinds[i][1]} #{w}): differs from the oracle", flush=True)
+        n_win += len(order); n_diff += diff; n_mixed_only += mixed_only; n_oracle += bad_oracle; n_stops += stops
+        print(f"mixed {cfg}: k={prm.k} solid={prm.solid} c={prm.common_kmers} A={prm.min_anchors} M={prm.max_msa} configure={conf} windows={len(order)} "
+              f"kinds={[d for _, d in kinds]} stops={stops} DIFF={diff} MIXED_ONLY_STOPS={mixed_only} ORACLE_DIFF={bad_oracle}", flush=True)
+    print(f"mixed: seed {seed}, {n_configs} configurations, {n_win} windows, {n_diff} differences mixed vs own kind, {n_mixed_only} mixed-only stops, "
+          f"{n_oracle} differences from the oracle, {n_stops} stops by reason {why_hist}")
+    return 1 if n_diff or n_mixed_only or n_oracle else 0
+
+
 def main():
+    if "--mixed" in sys.argv:
+        a = sys.argv[1:]
+        opt = lambda name, d: int(a[a.index(name) + 1]) if name in a else d  # noqa: E731
+        return mixed(opt("--configs", 200), opt("--seed", 1))
     seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 120
     rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
     t_end = time.time() + seconds
