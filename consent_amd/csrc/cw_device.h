@@ -48,7 +48,7 @@ struct WinInfo {
 #define CW_WHY_MATRIX 5     /* position matrix larger than the fallback slot / the anchor block      */
 #define CW_WHY_SEGMENTS 6   /* more chain segments than slots                                        */
 #define CW_WHY_TASKS 7      /* task / member / list capacity of the batch                            */
-#define CW_WHY_POA 8        /* a POA task outgrew every tier, or its output slot                     */
+#define CW_WHY_POA 8        /* a POA task outgrew tier X (65 534 nodes or edges, members of 4 095 bases, the matrix in tier G's pool), or its output slot */
 #define CW_WHY_FIN_LEN 9    /* consensus longer than the finish kernel's string buffers              */
 #define CW_WHY_FIN_SOLID 10 /* more solid k-mers than the visited bitmap covers                      */
 #define CW_WHY_FIN_POLISH 11/* the polish outgrew a buffer                                           */
@@ -98,6 +98,10 @@ struct BatchCounters {
                                                counts of tier t in a -DCW_DIAG build (cw_poa.h PoaMem::diag) */
     uint32_t n_fin_retry;         /* windows the finish kernel's first pass handed to its second (cw_finish.h) */
     uint32_t next_fin_retry;
+    uint32_t x_routed;            /* tier X (cw_poa.h): tasks tier G handed on (its list holds the first list_cap of them) */
+    uint32_t x_done;              /* ... that it aligned */
+    uint32_t x_stopped;           /* ... that outgrew it too (their windows stop on CW_WHY_POA) */
+    uint32_t x_cells;             /* the largest alignment it was asked for, in int32 cells (all three layers under the affine gap model) */
 };
 
 struct DevBatch {

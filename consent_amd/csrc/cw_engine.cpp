@@ -607,6 +607,7 @@ int run_device_locked(cw_engine* e, const cw_batch* batch, const cw_result* res,
     sid = stage_begin(e, st, "poa_overflow");
     cw_poa_slab_kernel<L_ARGS, 1><<<pass1_wgs, thr_l, lds_l, st>>>(db, sc);
     cw_poa_big_kernel<<<big_wgs, 64 * CW_POA_WAVES, 0, st>>>(db, sc);
+    cw_poa_x_kernel<<<1, 64, 0, st>>>(db, sc, CW_AID_ENV("CW_NO_TIER_X") ? 1 : 0); /* what outgrew tier G, in its slab pool (ends at once when tier G handed nothing on) */
     stage_end(e, st, sid);
     sid = stage_begin(e, st, "finish");
     {
@@ -762,6 +763,18 @@ int cw_debug_profile(cw_engine* e, uint32_t* counters, uint32_t counters_cap, un
     memcpy(prof, c.prof, (size_t)np * sizeof(unsigned long long));
     if (counters_n) *counters_n = nc;
     if (prof_n) *prof_n = np;
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): tier X's counters of the last run -- routed, done, stopped, largest cell count (BatchCounters::x_*) */
+int cw_debug_tier_x(cw_engine* e, uint32_t* out4) {
+    if (!e || !e->scratch || !out4) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    CW_HIP(hipSetDevice(e->device));
+    CW_HIP(hipDeviceSynchronize());
+    BatchCounters c;
+    CW_HIP(hipMemcpy(&c, (uint8_t*)e->scratch + e->last_ctr_off, sizeof(c), hipMemcpyDeviceToHost));
+    out4[0] = c.x_routed; out4[1] = c.x_done; out4[2] = c.x_stopped; out4[3] = c.x_cells;
     return CW_OK;
 }
 

@@ -5,6 +5,7 @@
  *   S        (cw_poa_kernel)        graph + DP matrix in LDS                              small segments (most tasks)
  *   M1/M2/L  (cw_poa_slab_kernel)   graph in LDS, matrix in an L2-resident per-wave slab   long segments, 3 size classes
  *   G        (cw_poa_big_kernel)    everything in a per-wave global slab                   the rare huge graph
+ *   X        (cw_poa_x_kernel)      one wave, tier G's whole slab pool once tier G is done  what outgrows tier G
  * A task that outgrows its tier is handed to the next one and redone there from scratch.
  *
  * Per member of the pile (policies: include/cw_policy.h):
@@ -61,6 +62,18 @@
 #define CW_POAB_EC 8192
 #define CW_POAB_LC 2047 /* round 6 (1023 through round 5): a window of 1500 bases whose chain is sparse has pieces of more than 1023 bases; the cell budget is what it was */
 #define CW_POAB_HC ((CW_POAB_NC + 1) * 1024) /* cells of the int32 matrix: rows x (bases + 1) of an alignment must fit (4096 nodes against 1023 bases, 2047 against 2047) */
+/* tier X: the tasks tier G hands on, one at a time on one wave, in tier G's slab pool after tier G has finished (int32 cells).  The row word keeps n_pred in
+   bits 8..31 and its x field moves to its own array (PoaMem::rx); members of more than 2047 bases are filled in blocks of 2048 columns (poa_fill, j0) */
+#define CW_POAX_NC 65534 /* the graph's 16-bit ids, CW_NONE16 the sentinel */
+#define CW_POAX_EC 65534
+#define CW_POAX_LC 4095  /* twice the longest template */
+#define CW_POAX_LIST 4   /* its list: tier_list[4], which the chain kernel never fills (what it routes to "tier 4" goes to list 0, tier Q's) */
+/* The pool tier X may use: the slabs EVERY plan gives tier G.  tier_config gives it n_windows / 16 + 8 slabs rounded down to a multiple of four, at most
+   big_slots -- so at least min(8, big_slots), whatever the batch: what stops in tier X is then a function of the window alone (8 slabs: 135.7 MB) */
+#define CW_POAX_MIN_SLABS 8u
+#define CW_POAX_PLIST_EC (2 * (CW_POAX_NC + 1)) /* plist doubles as the merge's u32 histogram of n + 1 counters: carved for that many u16 entries */
+#define CW_POAX_GRAPH_BYTES (CW_POA_GRAPH_BYTES(CW_POAX_NC, CW_POAX_PLIST_EC, CW_POAX_LC) + (4 * CW_POAX_NC + 255) / 256 * 256) /* + PoaMem::rx */
+#define CW_RMX_NP(m) (int)((m) >> 8) /* tier X's row word: n_pred in 24 bits, no x field */
 
 /* bytes of the graph part of a slab when every array lives in it (tiers S and G) */
 #define CW_POA_EW_BYTES(EC) (CW_CONS_HEAVIEST_BUNDLE ? 2 * (EC) : 0) /* edge weights, kept only under the heaviest-bundle policy (cw_policy.h) */
@@ -141,6 +154,7 @@ struct PoaMem {
     HT* H;
     unsigned long long* dirs; /* traceback codes, 2 bits per cell as two ballots per (row, chunk): 0 diagonal and
                                  1 vertical through the first predecessor, 2 horizontal, 3 = compare cell values */
+    uint32_t* rx;       /* tier X only (else NULL): rank -> the row word's x field, which its rows and list offsets outgrow (the word then holds n_pred in bits 8..31) */
     uint32_t* rmeta;    /* rank -> the row word (CW_RM_*): base, n_pred (the virtual start counts as 1), sink = no out-edge, linear = the only predecessor is
                            the rank before, x = that predecessor's DP row when n_pred is 1, else the offset of the node's list in plist; kind and slab
                            bit: what cw_poa_c.h's fill does with the row.  The fills read this ONE word per row */
@@ -195,6 +209,7 @@ __device__ __forceinline__ PoaMem<HT> poa_carve(uint8_t* base, uint32_t nc, uint
     else { M.H = (HT*)p; p += (size_t)hc * sizeof(HT); }
     if (d_ext) M.dirs = d_ext;
     else { M.dirs = (unsigned long long*)p; p += (size_t)dc * 16; }
+    M.rx = nullptr;
     M.rmeta = (uint32_t*)p; p += 4 * nc;
     M.plist = (uint16_t*)p; p += 2 * ec;   /* 4-byte aligned: follows rmeta */
     M.ew = nullptr;
@@ -231,8 +246,10 @@ __device__ __forceinline__ PoaMem<HT> poa_carve(uint8_t* base, uint32_t nc, uint
  * fetched for all chunks at once (one round trip per row).  The next row's metadata is requested while the
  * current row computes.
  */
-template <typename HT, int NCH, bool DIRS, bool PAD = false>
-__device__ __forceinline__ void poa_fill(const PoaMem<HT>& M, const int n, const int cols, const int lane, const bool use_dirs_) {
+/* WX (tier X): the row word's x in M.rx, n_pred in 24 bits; the call fills the block of columns [j0, j0 + 64 NCH) of every row, the blocks left to right
+   (a block's column j0 - 1 -- the diagonal's and the horizontal recurrence's carry into it -- is read back from the matrix) */
+template <typename HT, int NCH, bool DIRS, bool PAD = false, bool WX = false>
+__device__ __forceinline__ void poa_fill(const PoaMem<HT>& M, const int n, const int cols, const int lane, const bool use_dirs_, const int j0 = 0) {
     const int hs = cols; /* row stride of the matrix.  PAD (slab tiers, NCH == 1): every lane stores and loads without an execution mask -- a lane beyond
                             the member's columns then writes into the first cells of the NEXT row(s), which are computed and stored later (rows are
                             written in rank order, read only when complete), and reads cells nobody uses; the slab has 64 cells of slack */
@@ -246,21 +263,25 @@ __device__ __forceinline__ void poa_fill(const PoaMem<HT>& M, const int n, const
     bool act[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-        const int j = c * 64 + lane;
+        const int j = (WX ? j0 : 0) + c * 64 + lane;
         act[c] = j < cols;
         sq_[c] = (j > 0 && act[c]) ? (int)M.sq[j - 1] : -1;
 #pragma unroll
         for (int k = 0; k < RC; ++k) rc_[k][c] = CW_POA_SW ? 0 : j * G; /* row 0 */
     }
     uint32_t meta_n = M.rmeta[0];
+    uint32_t x_n = WX ? M.rx[0] : 0u;
 #ifdef CW_DIAG
     uint32_t dg_lin = 0, dg_far = 0, dg_pred = 0, dg_far16 = 0;
 #endif
     for (int r = 0; r < n; ++r) {
         const int i = r + 1;
         const uint32_t meta = (uint32_t)__builtin_amdgcn_readfirstlane((int)meta_n);
-        if (r + 1 < n) meta_n = M.rmeta[r + 1];
-        const int base = (int)(meta & 3u), np = CW_RM_NP(meta), off = CW_RM_X(meta), pr0 = off; /* pr0 is meaningful when np == 1 */
+        const int x_r = WX ? __builtin_amdgcn_readfirstlane((int)x_n) : 0;
+        if (r + 1 < n) { meta_n = M.rmeta[r + 1]; if (WX) x_n = M.rx[r + 1]; }
+        const int base = (int)(meta & 3u), np = WX ? CW_RMX_NP(meta) : CW_RM_NP(meta), off = WX ? x_r : CW_RM_X(meta), pr0 = off; /* pr0 is meaningful when np == 1 */
+        /* tier X, a block right of the first: the cells in column j0 - 1 of the rows the diagonal and the horizontal recurrence carry in from */
+        const int jl = WX ? j0 - 1 : 0;
 #ifdef CW_DIAG
         if (CW_RM_LIN(meta)) dg_lin++; else { dg_pred += (uint32_t)np; for (int q = 0; q < np; ++q) { const int prow = (np == 1) ? pr0 : (int)M.plist[off + q]; if (i - prow > RC) dg_far++; if (i - prow > 16) dg_far16++; } }
 #endif
@@ -269,6 +290,7 @@ __device__ __forceinline__ void poa_fill(const PoaMem<HT>& M, const int n, const
         for (int c = 0; c < NCH; ++c) { v[c] = CW_NEG; dgv[c] = CW_NEG; upv[c] = CW_NEG; }
         if (CW_RM_LIN(meta)) { /* see poa_fill_pk */
             int carry_in = CW_NEG;
+            if (WX && jl >= 0) carry_in = (int)M.H[(i - 1) * hs + jl];
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 const int upc = rc_[0][c];
@@ -296,13 +318,14 @@ __device__ __forceinline__ void poa_fill(const PoaMem<HT>& M, const int n, const
                 const int pr = prow * hs;
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
-                    const int j = c * 64 + lane;
+                    const int j = (WX ? j0 : 0) + c * 64 + lane;
                     up[c] = (PAD || act[c]) ? (int)M.H[pr + j] : CW_NEG;
                 }
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) asm volatile("" : "+v"(up[c])); /* see poa_fill_pk: keeps the wait for this load out of the common path */
             }
             int carry_in = CW_NEG;
+            if (WX && jl >= 0) carry_in = (int)M.H[prow * hs + jl];
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 const int dg = cw_wave_shr1(up[c], carry_in); /* the cell up-left: lane l-1 of the same row, column 0 has none */
@@ -312,15 +335,16 @@ __device__ __forceinline__ void poa_fill(const PoaMem<HT>& M, const int n, const
                 v[c] = max(v[c], max(dgv[c], upv[c]));
             }
         }
-        if (CW_POA_OV) v[0] = lane == 0 ? 0 : v[0]; /* overlap mode: the graph's prefix is free */
+        if (CW_POA_OV && !(WX && j0 > 0)) v[0] = lane == 0 ? 0 : v[0]; /* overlap mode: the graph's prefix is free */
         if (CW_POA_SW) {
 #pragma unroll
             for (int c = 0; c < NCH; ++c) v[c] = max(v[c], 0); /* local mode: no cell below 0 (clamping the candidates is clamping the cells: a gap from a clamped cell is negative) */
         }
         int carry = CW_NEG;
+        if (WX && jl >= 0) carry = (int)M.H[i * hs + jl] - jl * G; /* max over the columns left of the block of (cell - column x gap) */
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            const int j = c * 64 + lane;
+            const int j = (WX ? j0 : 0) + c * 64 + lane;
             /* (no mask for the lanes beyond the member's columns: a prefix max runs left to right, and everything to the right of the last
                column -- in this chunk and in the chunks after it -- is beyond the columns too: what they hold reaches no cell that is read) */
             int w = v[c] - j * G;
@@ -632,12 +656,13 @@ __device__ __forceinline__ void poa_fill_pk4(const PoaMem<int16_t>& M, const int
  * values in the order of preference of cw_policy.h: diagonal through the in-edges in order, then vertical through them, then
  * horizontal.  Lanes = in-edges: every candidate cell is requested at once, one memory round trip for the whole step.
  * Returns false when no move explains the cell (capacity/overflow paths report it). */
-template <typename HT>
+template <typename HT, bool WX = false>
 __device__ __forceinline__ bool poa_slow_step(const PoaMem<HT>& M, const int i, const int j, const int hs, const int pr0, const int lane,
                                               int* pi_out, int* pj_out) {
     const int G = CW_POA_GAP, MS = CW_POA_MATCH, XS = CW_POA_MISMATCH;
     const uint32_t meta = (uint32_t)__builtin_amdgcn_readfirstlane((int)M.rmeta[i - 1]);
-    const int base = (int)(meta & 3u), np = CW_RM_NP(meta), off = CW_RM_X(meta); /* off: only read when np > 1 */
+    const int base = (int)(meta & 3u), np = WX ? CW_RMX_NP(meta) : CW_RM_NP(meta);
+    const int off = WX ? __builtin_amdgcn_readfirstlane((int)M.rx[i - 1]) : CW_RM_X(meta); /* off: only read when np > 1 */
     int pi = i, pj = j;
     bool found = false;
     if (np <= 64) {
@@ -717,7 +742,7 @@ __device__ __forceinline__ uint32_t poa_consensus_hb(const PoaMem<HT>& M, const 
 #endif
 #include "cw_poa_a.h"
 
-template <typename HT, int PK, int CM = 0, int LCAP = 1023> /* LCAP: the tier's longest member -- fills for wider rows are not compiled into its kernel */
+template <typename HT, int PK, int CM = 0, int LCAP = 1023, bool WX = false> /* LCAP: the tier's longest member -- fills for wider rows are not compiled into its kernel; WX: tier X's row word */
 __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, const DevBatch& b, const DevScratch& sc, const int lane,
                        unsigned long long (&acc)[6]) {
     if constexpr (CW_POA_AFFINE && sizeof(HT) != 4) return 2; /* the affine gap model keeps three int32 layers: every task is handed on to the global-memory tier */
@@ -802,6 +827,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
         const bool pad = PK != 0 && !packed && M.pad64 && cols <= 64;
 #endif
         const int hs = grp ? CW_GF_HS : packed ? ((cols + 1) & ~1) : cols;    /* row stride of the DP matrix */
+        if constexpr (WX) { if (lane == 0) atomicMax(&sc.ctr->x_cells, (uint32_t)((n + 1) * hs) * (CW_POA_AFFINE ? 3u : 1u)); } /* the largest alignment tier X was asked for */
         if ((uint32_t)((n + 1) * hs + (pad ? 64 : 0)) > M.h_cap) return 2;
 
         /* ---- per-rank metadata (parallel over ranks) ---- */
@@ -836,9 +862,10 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                        store (any earlier row in tier S; at most CW_RING ranks back in tiers M1 / M2); 5 everything else */
                     uint32_t kind_ = lin_ ? 0u : 5u;
                     if (CM != 0 && !lin_ && np_ <= 3u && first != 0 && !far_) kind_ = np_;
-                    M.rmeta[r] = CW_RM_WORD(M.nbase[node], np_, lin_, !M.has_out[node], kind_, np_ == 1u ? first : off);
+                    if constexpr (WX) { M.rmeta[r] = CW_RM_WORD(M.nbase[node], 0u, lin_, !M.has_out[node], kind_, 0u) | (np_ << 8); M.rx[r] = np_ == 1u ? (uint32_t)first : (uint32_t)off; }
+                    else M.rmeta[r] = CW_RM_WORD(M.nbase[node], np_, lin_, !M.has_out[node], kind_, np_ == 1u ? first : off);
                 }
-                if (__ballot(r < n && (uint32_t)d > CW_RM_MAX_PRED) != 0ull) return 2; /* more in-edges than the row word's 11 bits count: a node needs more than 2047 distinct sources for that
+                if (!WX && __ballot(r < n && (uint32_t)d > CW_RM_MAX_PRED) != 0ull) return 2; /* more in-edges than the row word's 11 bits count: a node needs more than 2047 distinct sources for that
                                                                                       (members > 2047; tier G then reports rc 2 and the window stops on CW_WHY_POA) */
                 run += cw_lane_value(inc, 63);
             }
@@ -879,7 +906,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
 #endif
         if constexpr (CW_POA_AFFINE && sizeof(HT) == 4) { /* cw_poa_a.h: fill, end cell and walk back under the affine gap model */
             int end_row = 0;
-            const int arc = poa_affine_align(M, n, L, lane, &end_row);
+            const int arc = poa_affine_align<HT, WX>(M, n, L, lane, &end_row);
             if (arc) return arc;
             POA_PROF(1);
         }
@@ -928,6 +955,13 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                     else if constexpr (PK == 2 && LCAP > 511) poa_fill_pk<8, PK == 2>(M, n, cols, hs, lane, use_dirs);
                 }
             }
+        } else if constexpr (WX) { /* tier X: the wide row word; members of more than 2047 bases in blocks of 2048 columns */
+            if (cols <= 64) poa_fill<HT, 1, false, false, true>(M, n, cols, lane, false);
+            else if (cols <= 128) poa_fill<HT, 2, false, false, true>(M, n, cols, lane, false);
+            else if (cols <= 256) poa_fill<HT, 4, false, false, true>(M, n, cols, lane, false);
+            else if (cols <= 512) poa_fill<HT, 8, false, false, true>(M, n, cols, lane, false);
+            else if (cols <= 1024) poa_fill<HT, 16, false, false, true>(M, n, cols, lane, false);
+            else for (int j0 = 0; j0 < cols; j0 += 2048) poa_fill<HT, 32, false, false, true>(M, n, cols, lane, false, j0);
         } else {
             if (cols <= 64) poa_fill<HT, 1, PK == 2>(M, n, cols, lane, use_dirs);
             else if (cols <= 128) poa_fill<HT, 2, PK == 2>(M, n, cols, lane, use_dirs);
@@ -998,7 +1032,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                     } else if (code0 == 3) {
                         /* several predecessors: decide from the cell values (same order of preference) */
                         int pi, pj;
-                        if (!poa_slow_step(V, i, j, hs, pr0, lane, &pi, &pj)) return 3;
+                        if (!poa_slow_step<HT, WX>(V, i, j, hs, pr0, lane, &pi, &pj)) return 3;
                         if (pj != j && pi != i && lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
                         i = pi; j = pj;
                     } else if (pr0 != i - 1) {
@@ -1030,7 +1064,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                         j--;
                     } else {
                         int pi, pj;
-                        if (!poa_slow_step(V, i, j, hs, pr0, lane, &pi, &pj)) return 3;
+                        if (!poa_slow_step<HT, WX>(V, i, j, hs, pr0, lane, &pi, &pj)) return 3;
                         if (pj != j && pi != i && lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
                         i = pi; j = pj;
                     }
@@ -1100,7 +1134,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                     /* (selects, not branches: as an if-chain this was six nested execution-mask regions per tile) */
                     const bool c_start = row <= 0 || (CW_POA_OV && col <= 0) || (CW_POA_SW && valid && hv == 0), c_edge = tr == 7 || (tc == 7 && col > 0); /* (overlap mode: the walk stops in column 0; local mode: also at a cell of value 0) */
                     const bool c_d = col > 0 && hv == av + (sq_c == (meta_r & 3) ? MS : XS);
-                    const bool c_m = CW_RM_NP((uint32_t)meta_r) != 1, c_v = hv == bv + G, c_h = col > 0 && hv == lv + G;
+                    const bool c_m = (WX ? CW_RMX_NP((uint32_t)meta_r) : CW_RM_NP((uint32_t)meta_r)) != 1, c_v = hv == bv + G, c_h = col > 0 && hv == lv + G;
                     const int code = c_start ? 6 : c_edge ? 5 : c_d ? 0 : c_m ? 3 : c_v ? 1 : c_h ? 2 : 4;
                     const unsigned long long m_d = __ballot(code == 0), m_v = __ballot(code == 1), m_h = __ballot(code == 2);
                     /* the walk, a whole diagonal run per trip: the cells pos, pos + 9, ... are one 64-bit mask; the first of them that does not
@@ -1132,7 +1166,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
 #ifdef CW_DIAG
                         if (lane == 0 && M.diag) atomicAdd(&M.diag[8], 1ull);
 #endif
-                        if (!poa_slow_step(V, i, j, hs, pr0, lane, &pi, &pj)) return 3;
+                        if (!poa_slow_step<HT, WX>(V, i, j, hs, pr0, lane, &pi, &pj)) return 3;
                         if (pj != j && pi != i && lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
                         i = pi; j = pj;
                     }
@@ -1406,6 +1440,15 @@ __device__ __forceinline__ void poa_hand_over(const DevScratch& sc, const PoaTas
         sc.win[t.window].status = CW_WIN_OVERFLOW; sc.win[t.window].pad_ = CW_WHY_POA; sc.ctr->any_overflow = 1;
     }
     sc.tasks[ti].state = (uint32_t)rc;
+}
+
+/* tier G's hand-over (lane 0): a task that outgrows it goes on tier X's list; a full list, or rc 3, stops the window as before */
+__device__ __forceinline__ void poa_hand_over_x(const DevScratch& sc, const PoaTask& t, uint32_t ti, int rc) {
+    if (rc == 2) {
+        const uint32_t xi = atomicAdd(&sc.ctr->x_routed, 1u);
+        if (xi < sc.list_cap) { sc.tier_list[CW_POAX_LIST][xi] = ti; sc.tasks[ti].state = 2u; return; }
+    }
+    poa_hand_over(sc, t, ti, rc, CW_TIERS);
 }
 
 /* a producing tier's work-group is done: publish (release) and count it */
@@ -1795,10 +1838,46 @@ __global__ void __launch_bounds__(64 * CW_POA_WAVES) cw_poa_big_kernel(DevBatch 
         const uint32_t ti = sc.over_list[4][bi];
         const PoaTask t = sc.tasks[ti];
         const int rc = poa_run<int32_t, 0, 0>(M, t, b, sc, lane, acc);
-        if (lane == 0) poa_hand_over(sc, t, ti, rc, CW_TIERS);
+        if (lane == 0) poa_hand_over_x(sc, t, ti, rc);
         cw_wave_sync();
     }
     poa_flush_prof(sc, 8 + 5 * 4, acc, lane);
+}
+
+/* ---- tier X: what outgrows tier G, on one wave, in tier G's slab pool (launched after tier G on the same stream) -------------------
+ * The graph arrays at their full capacities (CW_POAX_NC nodes and edges, members of CW_POAX_LC bases: 3.2 MB) at the start of the pool, the int32
+ * matrix -- three layers under the affine gap model -- in all the rest: an alignment whose (nodes + 1) x (bases + 1) cells do not fit stops its
+ * window (CW_WHY_POA).  Only CW_POAX_MIN_SLABS slabs are used, the pool every plan has, so that the outcome does not depend on the batch.  The
+ * tasks are rare (none in the bench's batch): the kernel reads one counter and ends when there are none. */
+/* stop_all (test aid CW_NO_TIER_X, cw_engine.cpp): every listed task stops its window as it did before tier X existed -- shows which outputs need it */
+__global__ void __launch_bounds__(64) cw_poa_x_kernel(DevBatch b, DevScratch sc, int stop_all) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t n_x = min(sc.ctr->x_routed, sc.list_cap); /* (a task beyond a full list stopped its window already: poa_hand_over_x) */
+    if (n_x == 0) return;
+    uint8_t* const pool = sc.slab[4];
+    const uint64_t pool_bytes = (uint64_t)min(sc.slots[4], CW_POAX_MIN_SLABS) * sc.slab_bytes[4];
+    const uint64_t cells = pool_bytes > (uint64_t)CW_POAX_GRAPH_BYTES ? (pool_bytes - (uint64_t)CW_POAX_GRAPH_BYTES) / 4u : 0u;
+    PoaMem<int32_t> M = poa_carve<int32_t>(pool, CW_POAX_NC, CW_POAX_PLIST_EC, CW_POAX_LC, (uint32_t)min(cells, (uint64_t)0xFFFFFFFFu), 0,
+                                           (int32_t*)(pool + CW_POAX_GRAPH_BYTES));
+    M.e_cap = CW_POAX_EC;
+    M.rx = (uint32_t*)(pool + CW_POA_GRAPH_BYTES(CW_POAX_NC, CW_POAX_PLIST_EC, CW_POAX_LC));
+    unsigned long long acc[6] = {0, 0, 0, 0, 0, 0}; /* (tier X keeps no cycle totals: cw_debug_profile's slots are tiers S .. G's) */
+    for (uint32_t xi = 0; xi < n_x; ++xi) {
+        const uint32_t ti = sc.tier_list[CW_POAX_LIST][xi];
+        const PoaTask t = sc.tasks[ti];
+        const unsigned long long w0 = wall_clock64();
+        const int rc = stop_all ? 2 : poa_run<int32_t, 0, 0, CW_POAX_LC, true>(M, t, b, sc, lane, acc);
+        if (lane == 0) {
+            if (sc.task_dbg) { /* CW_TASK_TRACE: tier 6 */
+                uint4 d;
+                d.x = (uint32_t)(w0 - sc.ctr->prof[41]); d.y = (uint32_t)(wall_clock64() - w0); d.z = 6u | ((uint32_t)rc << 8) | (1u << 16); d.w = 0u;
+                sc.task_dbg[ti] = d;
+            }
+            atomicAdd(rc == 1 ? &sc.ctr->x_done : &sc.ctr->x_stopped, 1u);
+            poa_hand_over(sc, t, ti, rc, CW_TIERS); /* rc 2 or 3: the window stops (CW_WHY_POA) */
+        }
+        cw_wave_sync();
+    }
 }
 
 #endif

@@ -21,7 +21,7 @@
 #define CW_AFF_NEG (-(1 << 28))
 
 /* returns 0, or poa_run's codes: 2 = the three planes do not fit this slab, 3 = no move explains a cell (cannot happen) */
-template <typename HT>
+template <typename HT, bool WX = false> /* WX: tier X's row word (n_pred in 24 bits, x in PoaMem::rx) */
 __device__ __forceinline__ int poa_affine_align(const PoaMem<HT>& M, const int n, const int L, const int lane, int* end_row) {
     static_assert(sizeof(HT) == 4, "the affine model runs in the int32 tier");
     const int GO = CW_POA_GAP_OPEN, GE = CW_POA_GAP_EXT, MS = CW_POA_MATCH, XS = CW_POA_MISMATCH;
@@ -39,7 +39,7 @@ __device__ __forceinline__ int poa_affine_align(const PoaMem<HT>& M, const int n
     cw_wave_sync();
     for (int r = 0; r < n; ++r) {
         const uint32_t meta = M.rmeta[r];
-        const int np = CW_RM_NP(meta), x = CW_RM_X(meta), base = (int)(meta & 3u);
+        const int np = WX ? CW_RMX_NP(meta) : CW_RM_NP(meta), x = WX ? (int)M.rx[r] : CW_RM_X(meta), base = (int)(meta & 3u);
         int* const hrow = Hp + (size_t)(r + 1) * cols;
         int* const frow = Fp + (size_t)(r + 1) * cols;
         int* const erow = Ep + (size_t)(r + 1) * cols;
@@ -93,7 +93,7 @@ __device__ __forceinline__ int poa_affine_align(const PoaMem<HT>& M, const int n
             bool found = false;
             if (i != 0 && j != 0) {
                 const uint32_t meta = M.rmeta[i - 1];
-                const int np = CW_RM_NP(meta), x = CW_RM_X(meta);
+                const int np = WX ? CW_RMX_NP(meta) : CW_RM_NP(meta), x = WX ? (int)M.rx[i - 1] : CW_RM_X(meta);
                 const int s = (int)M.sq[j - 1] == (int)(meta & 3u) ? MS : XS;
                 for (int p = 0; p < np && !found; ++p) {
                     const int pr = np == 1 ? x : (int)M.plist[x + p];
@@ -111,7 +111,7 @@ __device__ __forceinline__ int poa_affine_align(const PoaMem<HT>& M, const int n
         } else if (layer == 1) {
             const int f = Fp[at];
             const uint32_t meta = M.rmeta[i - 1];
-            const int np = CW_RM_NP(meta), x = CW_RM_X(meta);
+            const int np = WX ? CW_RMX_NP(meta) : CW_RM_NP(meta), x = WX ? (int)M.rx[i - 1] : CW_RM_X(meta);
             bool found = false;
             for (int p = 0; p < np && !found; ++p) {
                 const int pr = np == 1 ? x : (int)M.plist[x + p];

@@ -38,8 +38,11 @@ int cw_add_offsets_device(uint32_t* a32, uint64_t n32, uint32_t add32, uint64_t*
 /* cw_run_device + wait for the stream + one more run with larger task / member / arena capacities, or the full matrix slot, when windows stopped on those only */
 int cw_run_device_sync(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream);
 int cw_debug_profile(cw_engine* e, uint32_t* counters, uint32_t counters_cap, unsigned long long* prof, uint32_t prof_cap, uint32_t* counters_n, uint32_t* prof_n);
+/* tier X's counters of the last run (4 uint32): tasks tier G handed on to it, tasks it aligned, tasks that outgrew it too (their windows stop on
+ * CW_WHY_POA), the largest alignment it was asked for in int32 cells (three layers under the affine gap model) */
+int cw_debug_tier_x(cw_engine* e, uint32_t* out4);
 
-/* with CW_TASK_TRACE set in the environment: 12 words per POA task of the last run (see cw_engine.cpp) */
+/* with CW_TASK_TRACE set in the environment: 12 words per POA task of the last run (see cw_engine.cpp); tier 6 = tier X */
 int cw_debug_task_trace(cw_engine* e, uint32_t cap_tasks, uint32_t* out12, uint32_t* n_tasks);
 
 /* with CW_STITCH_TRACE set in the environment the last cw_stitch_device call records, per window, 8 words (al_pos, size_al, score,

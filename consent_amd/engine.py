@@ -136,6 +136,8 @@ def _load(p):
     lib.cw_max_batch_windows.restype = C.c_uint32
     lib.cw_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_int)]
     lib.cw_debug_win_info.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    if hasattr(lib, "cw_debug_tier_x"):  # (a library built before tier X has no such entry)
+        lib.cw_debug_tier_x.argtypes = [C.c_void_p, C.c_void_p]
     lib.cw_debug_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.cw_extract_piles_device.argtypes = [C.c_void_p, C.POINTER(ReadSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p]
@@ -573,6 +575,13 @@ class Engine:
         p = np.zeros(128, np.uint64)  # phase cycle totals (cw_device.h BatchCounters::prof)
         _check(self.lib, self.lib.cw_debug_profile(self.handle, _ptr(c), len(c), _ptr(p), len(p), None, None), "cw_debug_profile")
         return c, p
+
+    def tier_x_counters(self):
+        """Tier X's counters of the last run (cw_debug_tier_x): tasks tier G handed on, tasks aligned, tasks that outgrew tier X too
+        (their windows stop on CW_WHY_POA), and the largest alignment it was asked for in int32 cells."""
+        c = np.zeros(4, np.uint32)
+        _check(self.lib, self.lib.cw_debug_tier_x(self.handle, _ptr(c)), "cw_debug_tier_x")
+        return {"routed": int(c[0]), "done": int(c[1]), "stopped": int(c[2]), "max_cells": int(c[3])}
 
     def win_info(self, n_windows):
         a = np.zeros((n_windows, 16), np.uint32)

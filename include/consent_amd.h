@@ -139,7 +139,8 @@ int cw_configure(cw_engine* e, uint32_t max_template_len);
  *     then every such stop stands.
  *   - cw_run_device and cw_submit + cw_wait run a batch once: a window may stop on CW_WHY_TASKS, CW_WHY_ARENA or CW_WHY_MATRIX in one batch
  *     and be corrected in another (a deep pile among shallow windows, for one).  The caller may run such windows again in a batch of their own.
- * Every other outcome -- a stop for any other reason, a template longer than the plan (CW_WHY_TEMPLATE) included -- is a function of the
+ * Every other outcome -- a stop for any other reason, a template longer than the plan (CW_WHY_TEMPLATE) and a POA task beyond the last tier's
+ * capacities (CW_WHY_POA: 65 534 nodes or edges, pieces of 4 095 bases, an int32 matrix of 135.7 MB) included -- is a function of the
  * window, the parameters and the engine's cw_configure number alone. */
 #define CW_MAX_BATCH_WINDOWS 131072u
 uint32_t cw_max_batch_windows(cw_engine* e);

@@ -115,7 +115,7 @@ def count(ins, pred):
     return sum(1 for _, mn, s in ins if mn and pred(mn, s))
 
 
-STEP = ("cw_index_kernel", "cw_chain_kernel", "cw_poa_kernel", "cw_poa_q_kernel", "cw_poa_slab_kernel", "cw_poa_big_kernel", "cw_finish_kernel",
+STEP = ("cw_index_kernel", "cw_chain_kernel", "cw_poa_kernel", "cw_poa_q_kernel", "cw_poa_slab_kernel", "cw_poa_big_kernel", "cw_poa_x_kernel", "cw_finish_kernel",
         "cw_stitch_kernel", "cw_extract", "cw_sort_tier_kernel", "cw_setup_kernel")
 
 

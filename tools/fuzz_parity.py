@@ -3,7 +3,10 @@ lengths.  Prints one line per configuration and a summary; exit code 1 on any di
   python tools/fuzz_parity.py [seconds [seed]]
   python tools/fuzz_parity.py --mixed [--configs N] [--seed S]   one batch of windows of several generators per parameter set (depths 0-3000,
       lengths 60-2000, low-complexity families, template-only windows), each window compared with its result in a batch of its own kind and with
-      the oracle: a mixed-vs-own-kind difference is a difference, and so is a stop that happens only in the mixed batch"""
+      the oracle: a mixed-vs-own-kind difference is a difference, and so is a stop that happens only in the mixed batch
+  CW_FUZZ_CAP_BAR=0 python tools/fuzz_parity.py --family divergent [--configs N] [--seed S]   (opt-in) piles of unrelated middles between a shared head
+      and tail -- graphs beyond tier G's cells and members of 1 300-3 800 bases, widths on both sides of the 2 048-column blocks of tier X's fill --
+      every window compared with the oracle; fails when no task reached tier X, and on any capacity stop above the bar"""
 import os
 import random
 import sys
@@ -131,7 +134,60 @@ def mixed(n_configs, seed):
     return 1 if n_diff or n_mixed_only or n_oracle else 0
 
 
+def divergent(n_configs, seed):
+    rng = random.Random(seed)
+    n_win = n_diff = n_stops = routed = done = 0
+    widths = [(1300, 1500), (1940, 2000), (2030, 2070), (2080, 2160), (2400, 2800), (3000, 3800)]  # member middles (a piece is its middle and a few flank bases)
+    for cfg in range(n_configs):
+        k = rng.choice([9, 9, 10, 11, 12])
+        prm = ca.Params(k, rng.choice([2, 3]), 8, rng.choice([1, 2]), rng.choice([20, 50, 150]))
+        piles = []
+        for _ in range(rng.randint(1, 3)):
+            lo, hi = rng.choice(widths)
+            members = rng.randint(8, 24 if hi <= 1500 else 12 if hi <= 2200 else 8)  # (keeps every alignment inside tier X's cells)
+            head, tail = "".join(rng.choice("ACGT") for _ in range(60)), "".join(rng.choice("ACGT") for _ in range(60))
+            tpl = head + "".join(rng.choice("ACGT") for _ in range(rng.randrange(400, 1900))) + tail
+            piles.append([tpl] + [head + "".join(rng.choice("ACGT") for _ in range(rng.randrange(lo, hi + 1))) + tail for _ in range(members - 1)])
+        hb = ca.pack_piles(piles)
+        eng = ca.Engine(prm)
+        try:
+            eng.configure(2048 + k - 1)
+            got = eng.run(hb)
+            info = eng.win_info(hb.n_windows)
+            x = eng.tier_x_counters()
+        finally:
+            eng.close()
+        exp, _ = oracle_lib.oracle_run(prm, hb, threads=16)
+        diff = stops = 0
+        for w in range(hb.n_windows):
+            if got.status[w] == ca.WIN_OVERFLOW:
+                stops += 1
+                print(f"  window {w}: stopped, why {WHY.get(int(info[w, 15]), int(info[w, 15]))}", flush=True)
+            elif got.status[w] != exp.status[w] or got.consensus(w) != exp.consensus(w) or not np.array_equal(got.solid_kmers(w), exp.solid_kmers(w)):
+                diff += 1
+                print(f"  window {w}: differs from the oracle", flush=True)
+        n_win += hb.n_windows; n_diff += diff; n_stops += stops; routed += x["routed"]; done += x["done"]
+        print(f"divergent {cfg}: k={prm.k} solid={prm.solid} A={prm.min_anchors} M={prm.max_msa} windows={hb.n_windows} members={[len(p) for p in piles]} "
+              f"tier X {x} stops={stops} DIFF={diff}", flush=True)
+    share = n_stops / max(1, n_win)
+    print(f"divergent: seed {seed}, {n_configs} configurations, {n_win} windows, {n_diff} differences from the oracle, {n_stops} stops, tier X routed {routed} done {done}")
+    if not routed:
+        print("FAILED: no task reached tier X")
+        return 1
+    if share > MAX_OVERFLOW_SHARE:
+        print(f"FAILED: capacity stops above {MAX_OVERFLOW_SHARE} of the windows ({share:.5f})")
+        return 1
+    return 1 if n_diff else 0
+
+
 def main():
+    if "--family" in sys.argv:
+        a = sys.argv[1:]
+        opt = lambda name, d: int(a[a.index(name) + 1]) if name in a else d  # noqa: E731
+        if a[a.index("--family") + 1] != "divergent":
+            print("--family: only 'divergent' (the default run draws random, homopolymer, tandem and identical piles)")
+            return 2
+        return divergent(opt("--configs", 20), opt("--seed", 1))
     if "--mixed" in sys.argv:
         a = sys.argv[1:]
         opt = lambda name, d: int(a[a.index(name) + 1]) if name in a else d  # noqa: E731
