@@ -28,12 +28,6 @@
 #endif
 #define CW_CH_SLAB_LONG 32768 /* ... of the instance an engine configured for long templates launches (cw_configure; round 6): up to CW_TMAX anchors, one work-group per CU */
 #define CW_CH_LIST_BYTES 1792
-#ifndef CW_POALW_MIN_MEAN
-#define CW_POALW_MIN_MEAN 160 /* tier LW takes the tier-L tasks whose mean member length is at least this (two or more chunks per row for most members) ... */
-#endif
-#ifndef CW_POALW_MIN_MEMBERS
-#define CW_POALW_MIN_MEMBERS 6 /* ... and that have at least this many members */
-#endif
 #define CW_CH_TILE_STRIDE 66u /* u16 per row of phase D's tile: 64 sequences + 2 (33 words: a column read by 64 lanes hits every bank twice) */
 
 /* the successor's index inside a chain key (length + 1 << 48 | score << 16 | this): the largest key wins, so the field is 0xFFFF - b when equal
@@ -423,9 +417,6 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                                           : ((sc.m1_route_depth && est_s > est ? est_s : est) <= (uint32_t)CW_POAM1_ROUTE && e_mx <= (uint32_t)CW_POAM1_LC) ? 1u
                                           : (est <= (uint32_t)CW_POAM2_ROUTE && e_mx <= (uint32_t)CW_POAM2_LC) ? 2u
                                                                                             : 3u;
-                    /* tier LW (round 6, cw_poa_w.h): a tier-L task whose members are wide ON AVERAGE (several 128-column chunks per DP row) and many runs
-                       on the four waves of a work-group -- list 5, which the product build has free (tier H is a test aid; with it on, no tier LW) */
-                    if (tier == 3u && sc.use_lw && e_n >= (uint32_t)CW_POALW_MIN_MEMBERS && q_sl[lane] / e_n >= (uint32_t)CW_POALW_MIN_MEAN) tier = 5u;
                     const unsigned long long below = (1ull << lane) - 1ull;
                     const unsigned long long pm = __ballot(poa);
                     const unsigned long long tm1 = __ballot(tier == 1u), tm2 = __ballot(tier == 2u), tm3 = __ballot(tier == 3u), tmq = __ballot(tier == 4u), tmh = __ballot(tier == 5u);

@@ -85,9 +85,6 @@
 #define CW_POA_CODES 0
 #define CW_Q_CODES 0
 #endif
-#ifndef CW_POA_VPROBE
-#define CW_POA_VPROBE 1 /* the tile traceback looks down the column when it is inside a long vertical run (poa_run, poa_trace_c) */
-#endif
 #define CW_POA_GRAPH_BYTES(NC, EC, LC) (((NC) * 29 + (EC) * 6 + CW_POA_EW_BYTES(EC) + 7 * ((LC) + 1) + 64 + 15) / 16 * 16)
 
 /* Slab tiers (M1 / M2 / L): LDS holds only what the fill and the traceback read ("hot": rank metadata, predecessor lists, first
@@ -109,32 +106,10 @@
 /* LDS per wave of slab tier T (1 = M1, 2 = M2): the ring and the flags only where the recorded-decision fill runs (tier M2 carried their 2.1 KB
    per wave unused until round 4: LDS is what the tiers compete for) */
 #define CW_POA_HOTC_OF_TIER(T) ((T) == 1 || CW_M2_CODES)
-#ifndef CW_M2_DIRS
-#define CW_M2_DIRS 0 /* 1: tier M2 writes tier L's direction words (in its slab, where tier M1 keeps code words) and walks them run by run instead of reading 8x8 tiles of
-                        the matrix back: its traceback costs as many wave-cycles as its fill (15.0 against 16.5 G per depth-150 batch), tier L's a quarter */
-#endif
-#ifndef CW_M2_CHAIN_TABS
-#define CW_M2_CHAIN_TABS 0 /* 1: tier M2 keeps the traceback's chain tables p2 / p4 in LDS (2 KB per wave: a tile's eight rows in three dependent reads instead of
-                              seven).  Without them its work-group is 38.6 KB -- the size of M1's, L's and Q's: any four fit a CU -- and the two-engine step 1.8 ms
-                              shorter (61.6 -> 59.8 ms, four alternating runs each on one box) */
-#endif
-#define CW_POA_HOT2T_BYTES(T, NC, EC, LC) (CW_POA_HOTC_OF_TIER(T) ? CW_POA_HOT2C_BYTES(NC, EC, LC) : CW_POA_HOT2_BYTES(NC, EC, LC) + (CW_M2_CHAIN_TABS ? (4 * (NC) + 15) / 16 * 16 : 0))
-#ifndef CW_L_COLD_NODES
-#define CW_L_COLD_NODES 0 /* 1: tier L keeps in_head / indeg / nbase / nalc / has_out in its slab, not in LDS (37 -> 26 KB per wave).  Measured: depth 150 unchanged within
-                             noise, depth 30 -- where tier L is the long pole -- 1 ms slower with one engine (tier L 16.0 -> 17.1 ms).  Off. */
-#endif
-#define CW_POA_HOT2L_BYTES(NC, EC, LC) (CW_L_COLD_NODES ? ((NC) * 10 + (EC) * 2 + 3 * ((LC) + 1) + 64 + 15) / 16 * 16 : CW_POA_HOT2_BYTES(NC, EC, LC))
-#define CW_POA_COLD2_BYTES(NC, EC, LC) (((NC) * 19 + (EC) * 4 + CW_POA_EW_BYTES(EC) + 4 * ((LC) + 1) + 255) / 256 * 256) /* (NC * 7 of it: tier L's per-node arrays, CW_L_COLD_NODES) */
-#ifndef CW_S_EDGES_LDS
-#define CW_S_EDGES_LDS 1 /* tier S keeps its in-edge lists and coverage counts in LDS (1.8 KB): the metadata pass walks them for every member */
-#endif
-#ifndef CW_S_LCODES_WORDS
-#define CW_S_LCODES_WORDS 0 /* tier S: code words of an alignment in LDS when groups of eight rows x columns + 64 fit this many words (cw_poa_c.h), so that the
-                               traceback's tile trips wait for LDS, not for the L2.  Measured with 384 words (93 % of tier S's members fit): traceback -11 %
-                               wave-cycles, tier S's kernel 34.5 -> 33.2 ms -- and the step +1.4 ms, because the 1.5 KB per wave are LDS the other tiers'
-                               work-groups no longer get.  Off. */
-#endif
-#define CW_POA_SLAB_BYTES (CW_POA_HOT2C_BYTES(CW_POA_NC, CW_POA_EC, CW_POA_LC) + (CW_S_EDGES_LDS ? 4 * CW_POA_EC + CW_POA_EW_BYTES(CW_POA_EC) + 2 * CW_POA_NC : 0) + 4 * CW_S_LCODES_WORDS) /* tier S, LDS per wave (round 4: laid out like M1 / M2) */
+#define CW_POA_HOT2T_BYTES(T, NC, EC, LC) (CW_POA_HOTC_OF_TIER(T) ? CW_POA_HOT2C_BYTES(NC, EC, LC) : CW_POA_HOT2_BYTES(NC, EC, LC))
+#define CW_POA_HOT2L_BYTES(NC, EC, LC) CW_POA_HOT2_BYTES(NC, EC, LC)
+#define CW_POA_COLD2_BYTES(NC, EC, LC) (((NC) * 19 + (EC) * 4 + CW_POA_EW_BYTES(EC) + 4 * ((LC) + 1) + 255) / 256 * 256) /* (NC * 7 of it is slack: the arrays carved from it take NC * 12) */
+#define CW_POA_SLAB_BYTES (CW_POA_HOT2C_BYTES(CW_POA_NC, CW_POA_EC, CW_POA_LC) + 4 * CW_POA_EC + CW_POA_EW_BYTES(CW_POA_EC) + 2 * CW_POA_NC) /* tier S, LDS per wave (round 4: laid out like M1 / M2, plus its in-edge lists and coverage counts, 1.8 KB: the metadata pass walks them for every member) */
 #define CW_POA_HSLAB_BYTES(NC, LC) ((((NC) + 1) * ((LC) + 1) * 2 + 255) / 256 * 256)
 #define CW_POA_DSLAB_PAIRS(NC, LC) ((NC) * (((LC) + 64) / 64))
 #define CW_POA_DSLAB_BYTES(NC, LC) ((CW_POA_DSLAB_PAIRS(NC, LC) * 16 + 255) / 256 * 256)
@@ -148,7 +123,6 @@
 static_assert(CW_POAB_EC <= 8192 && CW_POAL_EC <= 8192 && CW_POAM2_EC <= 8192 && CW_POAM1_EC <= 8192 && CW_POA_EC <= 8192, "the row word's x field (13 bits) holds a list offset < EC or a DP row <= NC");
 static_assert(CW_POAB_NC <= 8191 && CW_POAL_NC <= 8191, "the row word's x field (13 bits) holds a DP row <= NC");
 #define CW_RM_WORD(base, np, lin, sink, kind, x) ((uint32_t)(base) | ((lin) ? 4u : 0u) | ((sink) ? 8u : 0u) | ((uint32_t)(kind) << 5) | ((uint32_t)(np) << 8) | ((uint32_t)(x) << 19))
-struct PoaComm; /* cw_poa_w.h: mailbox and boundary words of a multi-wave tier-L work-group */
 template <typename HT>
 struct PoaMem {
     HT* H;
@@ -187,13 +161,10 @@ struct PoaMem {
     uint32_t* gflag;    /* cw_poa_c.h: one bit per rank: the row is also written to the slab (a later row needs it from more than CW_RING ranks back,
                            or it belongs to a node with more than three in-edges, or it is the fourth or a later predecessor of such a node); NULL where every row is kept anyway */
     uint32_t c_cap;
-    uint32_t* lcodes;   /* cw_poa_c.h, tier S: room in LDS for the code words of a small alignment (lc_cap words), or NULL */
-    uint32_t lc_cap;
 #ifdef CW_DIAG
     unsigned long long* diag; /* diagnostic build: ten counters of this tier in BatchCounters::prof (rows / linear rows / far loads / predecessor trips of the
                                  unpacked fill, rows / linear / far loads of the packed fill, traceback trips, slow steps, members) */
 #endif
-    PoaComm* comm;      /* cw_poa_w.h: non-NULL in a tier-L work-group of several waves (this is wave 0, the others serve its FILL commands) */
     bool pad64;         /* the matrix is in a slab with 64 cells of slack behind it: rows of <= 64 columns are stored and loaded by all 64 lanes
                            (no execution mask round the store of a row, no mask round a far row's load; see poa_fill) */
 };
@@ -201,7 +172,7 @@ struct PoaMem {
 template <typename HT>
 __device__ __forceinline__ PoaMem<HT> poa_carve(uint8_t* base, uint32_t nc, uint32_t ec, uint32_t lc, uint32_t hc, uint32_t dc,
                                                 HT* h_ext = nullptr, unsigned long long* d_ext = nullptr, uint8_t* cold = nullptr,
-                                                bool cold_edges = false, bool chain_tabs = false, bool cold_nodes = false) {
+                                                bool cold_edges = false, bool chain_tabs = false) {
     PoaMem<HT> M;
     uint8_t* p = base;
     uint8_t* pc = cold; /* merge-only arrays: in the slab when given, else with the rest */
@@ -218,9 +189,9 @@ __device__ __forceinline__ PoaMem<HT> poa_carve(uint8_t* base, uint32_t nc, uint
     if (chain_tabs) { M.p2 = (uint16_t*)p; p += 2 * nc; M.p4 = (uint16_t*)p; p += 2 * nc; } else { M.p2 = nullptr; M.p4 = nullptr; }
     if (!(pc && cold_edges)) { M.ncov = (uint16_t*)p; p += 2 * nc; }
     if (pc) { M.nal = (uint16_t*)pc; pc += 6 * nc; } else { M.nal = (uint16_t*)p; p += 6 * nc; }
-    if (pc && cold_nodes) { M.in_head = (uint16_t*)pc; pc += 2 * nc; } else { M.in_head = (uint16_t*)p; p += 2 * nc; }
+    M.in_head = (uint16_t*)p; p += 2 * nc;
     if (pc) { M.in_tail = (uint16_t*)pc; pc += 2 * nc; } else { M.in_tail = (uint16_t*)p; p += 2 * nc; }
-    if (pc && cold_nodes) { M.indeg = (uint16_t*)pc; pc += 2 * nc; } else { M.indeg = (uint16_t*)p; p += 2 * nc; }
+    M.indeg = (uint16_t*)p; p += 2 * nc;
     M.r2n = (uint16_t*)p; p += 2 * nc;
     M.n2r = (uint16_t*)p; p += 2 * nc;
     if (pc) { M.rtmp = (uint16_t*)pc; pc += 2 * nc; } else { M.rtmp = (uint16_t*)p; p += 2 * nc; }
@@ -228,12 +199,10 @@ __device__ __forceinline__ PoaMem<HT> poa_carve(uint8_t* base, uint32_t nc, uint
     if (pc) { M.pcur = (uint16_t*)pc; pc += 2 * (lc + 1); M.pat = (uint16_t*)pc; pc += 2 * (lc + 1); }
     else { M.pcur = (uint16_t*)p; p += 2 * (lc + 1); M.pat = (uint16_t*)p; p += 2 * (lc + 1); }
     if (pc && cold_edges) { M.efrom = (uint16_t*)pc; pc += 2 * ec; M.enext = (uint16_t*)pc; pc += 2 * ec; if (CW_CONS_HEAVIEST_BUNDLE) { M.ew = (uint16_t*)pc; pc += 2 * ec; } M.ncov = (uint16_t*)pc; pc += 2 * nc; }
-    if (pc && cold_nodes) { M.nbase = pc; pc += nc; M.nalc = pc; pc += nc; M.has_out = pc; pc += nc; } /* tier L: per-node arrays the metadata pass, the end cell and the merge read once per
-                                                                                                           member -- next to a millisecond of fill -- leave LDS (10.5 of its 37 KB per wave) */
-    else { M.nbase = p; p += nc; M.nalc = p; p += nc; M.has_out = p; p += nc; }
+    M.nbase = p; p += nc; M.nalc = p; p += nc; M.has_out = p; p += nc;
     M.sq = p; p += lc + 1;
     M.n_cap = nc; M.e_cap = ec; M.l_cap = lc; M.h_cap = hc; M.d_cap = dc; M.runs = false; M.pad64 = false;
-    M.codes = nullptr; M.ring = nullptr; M.gflag = nullptr; M.c_cap = 0; M.lcodes = nullptr; M.lc_cap = 0; M.comm = nullptr;
+    M.codes = nullptr; M.ring = nullptr; M.gflag = nullptr; M.c_cap = 0;
 #ifdef CW_DIAG
     M.diag = nullptr;
 #endif
@@ -634,23 +603,6 @@ __device__ __forceinline__ void poa_fill_pk4(const PoaMem<int16_t>& M, const int
 #ifndef CW_POA_REPLAY
 #define CW_POA_REPLAY 1 /* 0: every member is aligned, as through round 5 (tests/test_gpu_variants.py builds both replay switches off) */
 #endif
-#ifndef CW_POA_LW
-#define CW_POA_LW 0 /* round 6, tier "LW" (-DCW_POA_LW=1; not with the local alignment mode): tier-L tasks whose members are wide on average run on the four waves
-                       of a work-group (cw_poa_w.h; a second instance of the tier-L kernel on its own list and stream).  Bit-identical (tests/test_gpu_variants.py)
-                       and OFF: measured on one box at depth 150 (three runs each, alternating), a batch alone on the GPU takes 76.3 -> 70.6 ms with it (the
-                       batch's eight such tasks: the longest 26 -> 19 ms; tier L's kernel 60 -> 40 ms), and the step with three batches in flight 52.5 -> 53.1 ms
-                       (four engines: 50.8 -> 52.1): the fifth stream and the four-wave work-groups cost the other tiers more than the stragglers' tail,
-                       which other batches' work fills anyway, was costing.  The native driver's runs did not move (0.92-1.24 s either way). */
-#endif
-#if CW_POA_LW && CW_POA_SW
-#error "cw_poa.h: tier LW (cw_poa_w.h) has no local alignment mode"
-#endif
-#define CW_POAL_MW 4 /* waves of such a work-group */
-#if CW_POA_LW
-#include "cw_poa_w.h"
-#else
-#define CW_POA_COMM_BYTES 0
-#endif
 
 /* One traceback step at a node with several predecessors (or whose step the direction words left open), decided from the cell
  * values in the order of preference of cw_policy.h: diagonal through the in-edges in order, then vertical through them, then
@@ -945,9 +897,6 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                 }
             }
             else if (cols <= 128) poa_fill_pk<1, PK == 2>(M, n, cols, hs, lane, use_dirs);
-#if CW_POA_LW
-            else if (PK == 2 && M.comm != nullptr) { if constexpr (PK == 2 && sizeof(HT) == 2) poa_fill_mw<true>(M, n, cols, hs, lane, use_dirs); } /* tier L: the chunks of the row on the waves of the work-group (cw_poa_w.h) */
-#endif
             else if constexpr (LCAP > 127) {
                 if (cols <= 256) poa_fill_pk<2, PK == 2>(M, n, cols, hs, lane, use_dirs);
                 else if constexpr (LCAP > 255) {
@@ -1086,7 +1035,6 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                     if (lane == 0 && M.diag) atomicAdd(&M.diag[7], 1ull);
 #endif
                     i = __builtin_amdgcn_readfirstlane(i); j = __builtin_amdgcn_readfirstlane(j); /* wave-uniform: keep the walk on the scalar unit */
-#if CW_POA_VPROBE
                     /* Round 5: the tall tiers align short members against graphs of hundreds of nodes -- most of such a path is ONE vertical run of
                        hundreds of moves, seven per tile trip.  Inside a run the sixty-four lanes look down the column instead: lane t holds cell
                        (i - t, j); along a stretch of the graph where every node's only predecessor is the rank before, the cell moves vertically iff
@@ -1109,7 +1057,6 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                         vprobe = run >= 32;
                         if (run > 0) continue;
                     }
-#endif
                     int row = i;
                     if (M.p2) { /* tr steps up the chain: 4 + 2 + 1 (unconditional reads and selects, see cw_poa_c.h) */
                         { uint32_t v = M.p4[row - 1]; asm volatile("" : "+v"(v)); row = (tr & 4) ? (v == CW_NONE16 ? -1 : (int)v) : row; }
@@ -1156,7 +1103,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                     const int end_code = __builtin_amdgcn_readlane(code, pos);
                     i = __builtin_amdgcn_readlane(row, pos);
                     j -= pos & 7;
-                    vprobe = CW_POA_VPROBE && pos == 56 && on_diag == 0ull; /* seven vertical moves, no other: probably inside a long run */
+                    vprobe = pos == 56 && on_diag == 0ull; /* seven vertical moves, no other: probably inside a long run */
                     if (end_code == 4) return 3;
                     if (end_code == 6) i = 0;
                     if (end_code == 3) {
@@ -1186,14 +1133,13 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
         if constexpr (CM != 0 && CW_POA_CODES != 0) {
             if (coded) {
                 cw_wave_sync();
-                const bool lc = M.lcodes != nullptr && (uint32_t)(((n + 7) >> 3) * cols + 64) <= M.lc_cap; /* the code words fit the LDS area (stride = columns) */
 #ifdef CW_DIAG
-                if (lane == 0 && M.diag) { atomicAdd(&M.diag[9], 1ull); if (lc) atomicAdd(&M.diag[8], 1ull); } /* members on this path / with their code words in LDS */
+                if (lane == 0 && M.diag) atomicAdd(&M.diag[9], 1ull); /* members on this path */
 #endif
-                const int be_c = poa_fill_c<CM>(M, n, cols, lane, lc);
+                const int be_c = poa_fill_c<CM>(M, n, cols, lane);
                 const int bi_c = be_c & 0xFFFF, bj_c = be_c >> 16; /* end row, end column (the last one unless cw_policy.h's overlap mode) */
                 POA_PROF(1);
-                if (!poa_trace_c<CM>(M, n, bi_c, bj_c, cols, lane, lc)) return 3;
+                if (!poa_trace_c<CM>(M, n, bi_c, bj_c, cols, lane)) return 3;
 #ifdef CW_POA_VERIFY
                 cw_wave_sync();
                 {
@@ -1492,14 +1438,13 @@ __global__ void __launch_bounds__(64 * CW_POA_WAVES, CW_S_EU) cw_poa_kernel(DevB
     int16_t* hslab = (int16_t*)my_slab;
     unsigned long long* dslab = (unsigned long long*)(my_slab + CW_POA_HSLAB_BYTES(CW_POA_NC, CW_POA_LC));
     uint8_t* cold = my_slab + CW_POA_HSLAB_BYTES(CW_POA_NC, CW_POA_LC) + CW_POA_DSLAB_BYTES(CW_POA_NC, CW_POA_LC);
-    PoaMem<int16_t> M = poa_carve<int16_t>(lds + (size_t)wave * CW_POA_SLAB_BYTES, CW_POA_NC, CW_POA_EC, CW_POA_LC, (CW_POA_NC + 1) * (CW_POA_LC + 1), 0, hslab, dslab, cold, !CW_S_EDGES_LDS, true);
+    PoaMem<int16_t> M = poa_carve<int16_t>(lds + (size_t)wave * CW_POA_SLAB_BYTES, CW_POA_NC, CW_POA_EC, CW_POA_LC, (CW_POA_NC + 1) * (CW_POA_LC + 1), 0, hslab, dslab, cold, false, true);
     static_assert(CW_POA_SMAX * (CW_POA_NC + CW_POA_LC) <= CW_POA_I16_BOUND && 4 * CW_POA_SMAX * (CW_POA_NC + 64) <= CW_POA_I16_BOUND, "include/cw_policy.h \"Bounds\": tier S");
     M.H = hslab; M.dirs = dslab;
     {
-        uint8_t* extra = lds + (size_t)wave * CW_POA_SLAB_BYTES + (CW_POA_SLAB_BYTES - 4 * CW_S_LCODES_WORDS - CW_POA_RING_BYTES - CW_POA_GFLAG_BYTES(CW_POA_NC));
+        uint8_t* extra = lds + (size_t)wave * CW_POA_SLAB_BYTES + (CW_POA_SLAB_BYTES - CW_POA_RING_BYTES - CW_POA_GFLAG_BYTES(CW_POA_NC));
         M.ring = (int16_t*)extra; M.gflag = (uint32_t*)(extra + CW_POA_RING_BYTES);
         M.codes = (uint32_t*)dslab; M.c_cap = (uint32_t)(CW_POA_DSLAB_BYTES(CW_POA_NC, CW_POA_LC) / 4);
-        if (CW_S_LCODES_WORDS) { M.lcodes = (uint32_t*)(lds + (size_t)wave * CW_POA_SLAB_BYTES + (CW_POA_SLAB_BYTES - 4 * CW_S_LCODES_WORDS)); M.lc_cap = CW_S_LCODES_WORDS; }
     }
     M.pad64 = true;
     const uint32_t n_tasks = min(sc.ctr->n_tasks, sc.task_cap);
@@ -1547,18 +1492,12 @@ __global__ void __launch_bounds__(64 * CW_POA_WAVES, CW_S_EU) cw_poa_kernel(DevB
 /* PASS 0 works through the tasks the index kernel routed to this tier (all tiers run concurrently on their own
    streams); tier L additionally drains the live overflow queue.  PASS 1 (tier L only, after the join) takes what is left. */
 #define CW_POAL_LDS_BYTES (CW_POA_HOT2L_BYTES(CW_POAL_NC, CW_POAL_EC, CW_POAL_LC) * CW_POAL_WAVES) /* tier L's work-group */
-#define CW_POALW_LDS_BYTES (CW_POA_HOT2L_BYTES(CW_POAL_NC, CW_POAL_EC, CW_POAL_LC) + CW_POA_COMM_BYTES) /* ... and the four-wave one's (tier LW: one task) */
-/* MW > 1 (tier LW, TIER = 3): ONE task per work-group of MW waves -- wave 0 is "the" wave of the code below, the others serve its FILL commands
-   (cw_poa_w.h) and share its LDS arrays; LIST: the routed list the kernel works through (tier LW: list 5, which the product build has free) */
-template <int NC, int EC, int LC, int WAVES, int TIER, int PASS, int MW = 1, int LIST = TIER>
-__global__ void __launch_bounds__(64 * WAVES * MW, TIER == 1 ? CW_M1_EU : TIER == 2 ? 4 : 1) /* M1 and M2: four waves per SIMD (128 VGPRs; M1 at five spilled 17 VGPRs, round 6; M2 spills 3 at four and none at three -- 148 VGPRs -- where a batch alone on the GPU measured 60.2-60.4 ms against 59.6-59.7: left at four) */
+template <int NC, int EC, int LC, int WAVES, int TIER, int PASS>
+__global__ void __launch_bounds__(64 * WAVES, TIER == 1 ? CW_M1_EU : TIER == 2 ? 4 : 1) /* M1 and M2: four waves per SIMD (128 VGPRs; M1 at five spilled 17 VGPRs, round 6; M2 spills 3 at four and none at three -- 148 VGPRs -- where a batch alone on the GPU measured 60.2-60.4 ms against 59.6-59.7: left at four) */
 cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x & 63;
-    static_assert(MW == 1 || (TIER == 3 && WAVES == 1 && MW == CW_POAL_MW && CW_POA_LW), "several waves per task: tier L's wide tasks only");
-    const int mw_wave = MW > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-    const int wave = MW > 1 ? 0 : (int)(threadIdx.x >> 6);
-    PoaComm* const comm = MW > 1 ? (PoaComm*)(lds + CW_POA_HOT2L_BYTES(NC, EC, LC) * WAVES) : nullptr;
+    const int wave = (int)(threadIdx.x >> 6);
     /* Yielding persistence.  The four tier kernels run side by side and share each CU's LDS; a work-group that loops until its tier's
        list is empty keeps its LDS for the whole stage, so whichever kernel reaches a CU first owns it (measured: tier S held every CU
        for 27 ms of a depth-150 batch while the long tasks of tier L had not started).  Here only the LAST persist_wgs work-groups of
@@ -1566,7 +1505,7 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
        work-group of ANY tier: the mix on a CU follows the remaining work instead of the launch order.  A wave's slab is therefore
        not tied to its block index: it claims a free one (there are more slabs than waves the hardware can hold at once). */
     uint32_t gw = 0;
-    if (lane == 0 && mw_wave == 0) {
+    if (lane == 0) {
         const uint32_t n_slots = sc.slots[TIER];
         uint32_t s = (uint32_t)(((unsigned long long)(blockIdx.x * WAVES + wave) * 2654435761ull) % n_slots);
         for (;;) {
@@ -1575,15 +1514,9 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
             s = s + 1u == n_slots ? 0u : s + 1u;
         }
         gw = s;
-#if CW_POA_LW
-        if constexpr (MW > 1) { comm->slab = s; comm->seq = 0u; comm->cmd = 0u; for (int x = 0; x < CW_POAL_MW; ++x) { comm->done[x] = 0u; comm->ready[x] = 0u; } }
-#endif
     }
-#if CW_POA_LW
-    if constexpr (MW > 1) { __syncthreads(); if (lane == 0) gw = comm->slab; } /* (the one barrier of the kernel: the helpers learn the slab) */
-#endif
     gw = (uint32_t)__builtin_amdgcn_readfirstlane((int)gw);
-    const bool yields = PASS == 0 && MW == 1 && blockIdx.x + sc.persist_wgs[TIER] < gridDim.x; /* (the few work-groups of tier LW stay until their list is empty) */
+    const bool yields = PASS == 0 && blockIdx.x + sc.persist_wgs[TIER] < gridDim.x;
     /* the slab is global memory: say so, or every access to the DP matrix is a flat_* instruction (both wait counters, aperture check) */
     typedef __attribute__((address_space(1))) uint8_t* cw_gptr;
     uint8_t* my_slab = (uint8_t*)(cw_gptr)(sc.slab[TIER] + (size_t)gw * sc.slab_bytes[TIER]);
@@ -1591,8 +1524,8 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
     unsigned long long* dslab = (unsigned long long*)(my_slab + CW_POA_HSLAB_BYTES(NC, LC));
     uint8_t* cold = my_slab + CW_POA_HSLAB_BYTES(NC, LC) + CW_POA_DSLAB_BYTES(NC, LC);
     constexpr uint32_t slab = TIER <= 2 ? CW_POA_HOT2T_BYTES(TIER, NC, EC, LC) : CW_POA_HOT2L_BYTES(NC, EC, LC);
-    PoaMem<int16_t> M = poa_carve<int16_t>(lds + (size_t)wave * slab, NC, EC, LC, (NC + 1) * (LC + 1), (TIER >= 3 || (TIER == 2 && CW_M2_DIRS)) ? CW_POA_DSLAB_PAIRS(NC, LC) : 0, hslab, dslab, cold,
-                                           true, TIER == 1 || (TIER == 2 && (CW_M2_CHAIN_TABS || CW_M2_CODES)), TIER >= 3 && CW_L_COLD_NODES);
+    PoaMem<int16_t> M = poa_carve<int16_t>(lds + (size_t)wave * slab, NC, EC, LC, (NC + 1) * (LC + 1), TIER >= 3 ? CW_POA_DSLAB_PAIRS(NC, LC) : 0, hslab, dslab, cold,
+                                           true, TIER == 1 || (TIER == 2 && CW_M2_CODES));
     M.H = hslab; M.dirs = dslab; /* again, without poa_carve's either-or: these two are now provably global pointers */
     /* include/cw_policy.h "Bounds": the int16 values of this tier's fills stay inside +-CW_POA_I16_BOUND -- by its capacities, or (tier L under scores
        beyond 11) by handing a graph of more nodes than that allows on to tier G */
@@ -1605,8 +1538,7 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
         M.ring = (int16_t*)extra; M.gflag = (uint32_t*)(extra + CW_POA_RING_BYTES);
         M.codes = (uint32_t*)dslab; M.c_cap = (uint32_t)(CW_POA_DSLAB_BYTES(NC, LC) / 4);
     }
-    M.runs = TIER >= 3 || (TIER == 2 && CW_M2_DIRS); /* tier L: long graphs against short members, long vertical runs (direction words, whole runs per round trip) */
-    M.comm = comm;
+    M.runs = TIER >= 3; /* tier L: long graphs against short members, long vertical runs (direction words, whole runs per round trip) */
 #ifdef CW_DIAG
     M.diag = &sc.ctr->prof[72 + 12 * TIER];
 #endif
@@ -1614,11 +1546,6 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
     /* the large tiers have few, long tasks and share their SIMDs with up to three waves of the small tiers: let them issue first,
        or tier L is still running long after the others have finished (depth 150) */
     if (TIER == 3) __builtin_amdgcn_s_setprio(3);
-#if CW_POA_LW
-    if constexpr (MW > 1) {
-        if (mw_wave > 0) { poa_mw_serve<true>(M, lane, mw_wave); return; } /* until wave 0 posts EXIT */
-    }
-#endif
 #ifndef CW_M2_PRIO
 #define CW_M2_PRIO 1
 #endif
@@ -1630,31 +1557,32 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
         const unsigned long long _t0 = __builtin_readcyclecounter(), _w0 = wall_clock64();
         /* tier M2's rows are 85 % linear (long graphs, short members): there the matrix fill's 37-instruction row beats the recorded
            decisions' 52, and its slower traceback does not make up for it (measured: 35.8 against 38.5 G wave-cycles per batch) */
-        const int rc = poa_run<int16_t, ((TIER < 3 && !(TIER == 2 && CW_M2_DIRS)) ? 1 : 2), (TIER == 1 || (TIER == 2 && CW_M2_CODES) ? 2 : 0), LC>(M, t, b, sc, lane, acc);
+        const int rc = poa_run<int16_t, (TIER < 3 ? 1 : 2), (TIER == 1 || (TIER == 2 && CW_M2_CODES) ? 2 : 0), LC>(M, t, b, sc, lane, acc);
         const unsigned long long _t1 = __builtin_readcyclecounter();
         acc[5] = _t1 - _t0 > acc[5] ? _t1 - _t0 : acc[5];
-        if (lane == 0 && sc.task_dbg) { /* inspection aid (CW_TASK_TRACE): when each task of the slab tiers ran (10 ns units since the tier sort), where, and how it ended */
+        if (lane == 0 && sc.task_dbg) { /* inspection aid (CW_TASK_TRACE): when each task of the slab tiers ran (10 ns units since the tier sort), where, and how it ended.
+                                           The third word is tier | rc << 8 | pass << 16; its bit 24, which through round 6 marked a task run on four waves, is no longer set */
             uint4 d;
-            d.x = (uint32_t)(_w0 - sc.ctr->prof[41]); d.y = (uint32_t)(wall_clock64() - _w0); d.z = (uint32_t)TIER | ((uint32_t)rc << 8) | ((uint32_t)PASS << 16) | (MW > 1 ? 1u << 24 : 0u); d.w = gw;
+            d.x = (uint32_t)(_w0 - sc.ctr->prof[41]); d.y = (uint32_t)(wall_clock64() - _w0); d.z = (uint32_t)TIER | ((uint32_t)rc << 8) | ((uint32_t)PASS << 16); d.w = gw;
             sc.task_dbg[ti] = d;
         }
         if (lane == 0) poa_hand_over(sc, t, ti, rc, TIER < 3 ? 3 : 4);
         cw_wave_sync();
     };
     if (PASS == 0) {
-        const uint32_t* list = sc.tier_list[LIST];
-        const uint32_t n_work = min(sc.ctr->n_tier[LIST], sc.list_cap);
+        const uint32_t* list = sc.tier_list[TIER];
+        const uint32_t n_work = min(sc.ctr->n_tier[TIER], sc.list_cap);
         uint32_t ran = 0;
         for (;;) {
             uint32_t mi = 0;
-            if (lane == 0) mi = atomicAdd(&sc.ctr->next_tier[LIST], 1u);
+            if (lane == 0) mi = atomicAdd(&sc.ctr->next_tier[TIER], 1u);
             mi = (uint32_t)__shfl((int)mi, 0);
             if (mi >= n_work) break;
             run_task(list[mi]);
             if (yields && ++ran >= (TIER == 1 ? CW_POA_CHUNK_M1 : 1u)) break;
         }
     }
-    if (TIER == 3 && MW == 1 && !yields && (PASS == 1 || gridDim.x - 1u - blockIdx.x < sc.linger_wgs)) {
+    if (TIER == 3 && !yields && (PASS == 1 || gridDim.x - 1u - blockIdx.x < sc.linger_wgs)) {
         /* Live queue (only the last few work-groups of the grid stay for it: a lingering tier-L work-group holds 37 KB of LDS that
            the other tiers could use): tasks that outgrow tiers S/M1/M2 while those kernels are still running on their own streams are
            picked up here at once instead of waiting for a later pass.  An entry is its own flag (0xFFFFFFFF = not yet
@@ -1695,13 +1623,6 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
     } else if (PASS == 1) {
         /* not used for tiers below L */
     }
-#if CW_POA_LW
-    if constexpr (MW > 1) { /* the helpers leave */
-        if (lane == 0) comm->cmd = CW_MW_CMD_EXIT;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) cww_store(&comm->seq, cww_load(&comm->seq) + 1u);
-    }
-#endif
     poa_flush_prof(sc, 8 + 5 * TIER, acc, lane);
     if (lane == 0) __hip_atomic_store(&sc.slot_busy[TIER][gw], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); /* the slab goes back */
     if (PASS == 0 && TIER < 3) poa_producer_done(sc);
@@ -1726,10 +1647,6 @@ __device__ __forceinline__ uint32_t cw_sort_class(uint32_t n_members, uint32_t l
     uint32_t c;
     if (tier == 0) { /* tier Q: the four tasks of a wave advance in lock step, so neighbours in the list should be alike: longest members first,
                         then by how many there are */
-#ifdef CW_Q_SORT_R4 /* rounds 3-4: longest member first, three steps of eight members */
-        const uint32_t nm = n_members >> 3;
-        return (CW_SORT_CLASSES - 1) - ((max_len < 32u ? max_len : 31u) * 4u + (nm < 3u ? nm : 3u));
-#else
         /* round 5: a wave's four tasks end when its longest one does, and a task's time is members x rows x ...: since tier Q also takes the deep piles'
            tasks (up to maxMSA members), the member count comes first -- eight classes, roughly geometric -- then the longest member in steps of two */
         /* (round 6, after the replay of repeated members: sixteen classes of member count and eight of length instead -- tier Q's kernel 8.86 -> 8.70 ms, the step
@@ -1737,7 +1654,6 @@ __device__ __forceinline__ uint32_t cw_sort_class(uint32_t n_members, uint32_t l
            it writes the member lists: tier Q's kernel 8.85 -> 8.45 ms, the chain kernel 2.61 -> 3.05 ms for reading every member's bases: even) */
         const uint32_t mc = n_members < 4u ? 0u : n_members < 8u ? 1u : n_members < 12u ? 2u : n_members < 16u ? 3u : n_members < 24u ? 4u : n_members < 32u ? 5u : n_members < 64u ? 6u : 7u;
         return (CW_SORT_CLASSES - 1) - (mc * 16u + ((max_len < 32u ? max_len : 31u) >> 1));
-#endif
     }
     if (tier == 5) { /* tier H (cw_poa_q.h): as tier Q, the longest member in steps of four */
         const uint32_t mc = n_members < 4u ? 0u : n_members < 8u ? 1u : n_members < 12u ? 2u : n_members < 16u ? 3u : n_members < 24u ? 4u : n_members < 32u ? 5u : n_members < 64u ? 6u : 7u;
@@ -1762,7 +1678,6 @@ __global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc, uint3
     extern __shared__ __attribute__((aligned(16))) uint8_t cls_lds[]; /* lds_cls bytes (<= CW_SORT_LDS_CLS) */
     const int tier = blockIdx.x == 3 ? 0 : blockIdx.x == 4 ? 5 : 1 + (int)blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63; /* 0 = tier Q's list, 5 = tier H's */
     if (blockIdx.x == 0 && threadIdx.x == 0) sc.ctr->prof[41] = wall_clock64(); /* time base of the task trace */
-    const int cls_tier = tier == 5 && sc.use_lw ? 3 : tier; /* list 5 holds tier L's wide tasks (tier LW): ordered like tier L's */
     const uint32_t n = min(sc.ctr->n_tier[tier], sc.list_cap);
     const uint32_t nthr = blockDim.x, nwv = nthr >> 6; /* 4 .. 16 waves: a small work-group finds room beside another batch's persistent kernels */
     uint32_t* list = sc.tier_list[tier];
@@ -1783,7 +1698,7 @@ __global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc, uint3
         for (int j = 0; j < 8; ++j) {
             const uint32_t x = x0 + (uint32_t)j * 64u + (uint32_t)lane;
             if (ti[j] != 0xFFFFFFFFu) {
-                const uint32_t c = cw_sort_class(nm[j].x, nm[j].y, cls_tier);
+                const uint32_t c = cw_sort_class(nm[j].x, nm[j].y, tier);
                 atomicAdd(&cnt[wave][c], 1u);
                 if (x < lds_cls) cls_lds[x] = (uint8_t)c;
             }
@@ -1808,7 +1723,7 @@ __global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc, uint3
             if (ti[j] != 0xFFFFFFFFu) {
                 uint32_t c;
                 if (x < lds_cls) c = cls_lds[x];
-                else { const uint2 v = *(const uint2*)&sc.tasks[ti[j]].n_members; c = cw_sort_class(v.x, v.y, cls_tier); }
+                else { const uint2 v = *(const uint2*)&sc.tasks[ti[j]].n_members; c = cw_sort_class(v.x, v.y, tier); }
                 tmp[atomicAdd(&cnt[wave][c], 1u)] = ti[j];
             }
         }

@@ -738,17 +738,6 @@ __device__ int poaq_run(const PoaQ<T>& M, const PoaTask& t, const DevBatch& b, c
 }
 
 /* ---- tier Q (four tasks per wave) and tier H (two): one kernel body ------------------------------------------------------------------ */
-#ifndef CW_POAQ_FLAT
-#define CW_POAQ_FLAT 0 /* 1: the flat loop below (built, bit-identical, measured slower: off; the variant `qflat` of tests/test_gpu_variants.py) */
-#endif
-/* Round 6, the flat loop -- tried, measured, off.  The groups of a wave share one instruction stream, so the loop "per group: take a task, run all its members"
-   makes every group wait, task after task, for the slowest of the four: the consensus phase of the profile, which the first group's clock charges with that wait,
-   is 10.2 of this tier's 62.2 G wave-cycles per depth-150 batch although the tier list is sorted by size.  The flat loop is over ALIGNMENTS instead: each round
-   every group brings one member of its own task to the alignment (a new task, its first member's chain, its repeated members and the consensus of the task it has
-   just finished on the way, in a loop of its own), and a group whose task ends takes the next one without waiting.  Measured (same box, four alternating runs):
-   the kernel 8.84 -> 9.24 ms.  The wait is gone (consensus 10.2 -> 1.3 G) and comes back twice: the work at a task's boundary (a chain of five dependent loads,
-   the chain, the consensus) now runs once per GROUP with the other three idle, where the per-task loop runs it once per wave for all four (+6.0 G), and groups
-   that are at different members of their tasks meet graphs of different sizes -- the fill runs as many rows as the largest (+4.9 G). */
 template <class T, int TIER_LIST, int NEXT_TIER, int PROF_BASE, bool PRODUCER>
 __device__ __forceinline__ void poaq_kernel_body(const DevBatch& b, const DevScratch& sc, uint8_t* lds, uint8_t* slab_base) {
     const int gl = threadIdx.x & (T::GW - 1);
@@ -758,52 +747,6 @@ __device__ __forceinline__ void poaq_kernel_body(const DevBatch& b, const DevScr
     const uint32_t* list = sc.tier_list[TIER_LIST];
     const uint32_t n_work = min(sc.ctr->n_tier[TIER_LIST], sc.list_cap);
     unsigned long long acc[5] = {0, 0, 0, 0, 0};
-#if CW_POAQ_FLAT
-    PoaQSt S;
-    S.reset(); S.pt = __builtin_readcyclecounter();
-    PoaTask t = {};
-    uint32_t ti = 0, mi = 0;
-    bool have = false, done = false;
-    for (;;) {
-        bool aligning = false;
-        int L = 0;
-        while (!done) { /* (per group) until this group has a member to align or the list is empty */
-            if (have && mi >= t.n_members) { /* the task's last member is in: its consensus */
-                const int rc = poaq_finish<T>(M, S, t, sc, gl, acc);
-                if (gl == 0) poa_hand_over(sc, t, ti, rc, NEXT_TIER);
-                cw_wave_sync();
-                have = false;
-            }
-            if (!have) {
-                uint32_t m = 0;
-                if (gl == 0) m = atomicAdd(&sc.ctr->next_tier[TIER_LIST], 1u);
-                m = (uint32_t)g_bcast<T>((int)m, 0);
-                if (m >= n_work) { done = true; break; }
-                ti = list[m];
-                t = sc.tasks[ti];
-                if (t.n_members == 0) continue; /* a neutral entry (cw_chain.h "cap_ok") */
-                if (t.n_members > 255u) { if (gl == 0) poa_hand_over(sc, t, ti, 2, NEXT_TIER); continue; } /* coverage counts and edge weights are bytes here */
-                S.reset();
-                mi = 0; have = true;
-            }
-            PoaMember pm = sc.members[t.member_off + mi];
-            poaq_replay<T>(M, S, t, b, sc, mi, pm, gl);
-            if (mi >= t.n_members) continue;
-            const int tk = poaq_take<T>(M, S, pm, b, gl);
-            if (tk == 2) { if (gl == 0) poa_hand_over(sc, t, ti, 2, NEXT_TIER); cw_wave_sync(); have = false; continue; }
-            if (tk == 1) { ++mi; continue; } /* the first member: a chain */
-            L = (int)pm.len;
-            aligning = true;
-            break;
-        }
-        if (__ballot(aligning) == 0ull) break; /* every group has seen the end of the list */
-        if (aligning) {
-            const int rc = poaq_member<T>(M, S, L, gl, acc);
-            if (rc) { if (gl == 0) poa_hand_over(sc, t, ti, rc, NEXT_TIER); cw_wave_sync(); have = false; }
-            else ++mi;
-        }
-    }
-#else
     for (;;) {
         uint32_t mi = 0;
         if (gl == 0) mi = atomicAdd(&sc.ctr->next_tier[TIER_LIST], 1u);
@@ -816,7 +759,6 @@ __device__ __forceinline__ void poaq_kernel_body(const DevBatch& b, const DevScr
         if (gl == 0) poa_hand_over(sc, t, ti, rc, NEXT_TIER);
         cw_wave_sync();
     }
-#endif
     /* per-phase cycles as the first group of every wave saw them (the groups of a wave share one instruction stream) */
     if ((threadIdx.x & 63) == 0) for (int q = 0; q < 5; ++q) atomicAdd(&sc.ctr->prof[PROF_BASE + q], acc[q]);
     if (PRODUCER) poa_producer_done(sc);

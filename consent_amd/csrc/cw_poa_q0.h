@@ -1,6 +1,7 @@
 /*
  * cw_poa_q0.h -- tier Q as rounds 3-4 ran it (-DCW_Q_CODES=0): the DP matrix of every task in LDS (40 nodes / 120 edges / 31 bases), a step-wise
  * traceback over its values.  Kept as a build variant of cw_poa_q.h (same results; tests/test_gpu_variants.py), included from there.
+ * Still in use: cw_poa.h forces CW_Q_CODES to 0 under the local alignment mode and the affine gap model, so those policy builds of cw_policy.h run tier Q here.
  */
 #ifndef CW_POA_Q0_H
 #define CW_POA_Q0_H

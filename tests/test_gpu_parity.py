@@ -307,14 +307,12 @@ def test_tier_h_two_tasks_per_wave(aids, monkeypatch):
     ctr, _ = e.profile()
     assert int(ctr[11]) > 0, ctr[6:12]  # tasks routed to tier H
     assert_same(got, exp, len(piles), "tier H")
-    monkeypatch.setenv("CW_LW", "0")  # (list 5 is tier H's only while tier LW is off: with tier H off, tier LW counts its tasks there -- round 6)
     for mode in ("1", "0"):
         monkeypatch.setenv("CW_TIER_H", mode)
         got = e.run(hb)
         ctr2, _ = e.profile()
         assert (int(ctr2[11]) <= int(ctr[11])) if mode == "1" else int(ctr2[11]) == 0
         assert_same(got, exp, len(piles), f"CW_TIER_H={mode}")
-    monkeypatch.delenv("CW_LW")
     monkeypatch.delenv("CW_TIER_H")
     hb2 = synth_host(ca.SynthSpec.pacbio(96, 150, first_window=7000))
     exp2, _ = oracle_lib.oracle_run(ca.Params(*prm), hb2, threads=os.cpu_count() or 1)

@@ -4,11 +4,7 @@
   -DCW_POA_CODES=0  tiers S / M1 on the matrix path (fill writes the DP matrix, the traceback reads tiles of it back) instead of the
                     recorded-decision path of cw_poa_c.h,
   -DCW_M2_CODES=1   tier M2 on the recorded-decision path too,
-  -DCW_POA_LW=1     tier LW (round 6, cw_poa_w.h): the tier-L tasks whose members are wide on average on the four waves of a work-group, the chunks of a wide
-                    packed row pipelined by rows (measured: a batch alone on the GPU 7 % faster, the step with batches in flight 1-2 % slower: off by default),
-  ... -DCW_POALW_MIN_MEAN=1 -DCW_POALW_MIN_MEMBERS=2   EVERY tier-L task in tier LW (narrow members too: the one-chunk rows stay on wave 0),
   -DCW_POA_GROUP_FILL=0  tiers M2 / L fill every member on its own (round 5's default fills up to four consecutive short members together),
-  -DCW_POA_VPROBE=0 the tile traceback without the look down the column inside a long vertical run,
   -DCW_POAQ_REPLAY=0 -DCW_POA_REPLAY=0  every tier aligns every member (round 6's default does not align a member that repeats the one before it: cw_poa_q.h),
   -DCW_Q_CODES=0    tier Q with the DP matrix in LDS and a walk over its values (rounds 3-4, cw_poa_q0.h) instead of recorded decisions,
 each compared with the oracle on piles of several depths (all tiers)."""
@@ -20,7 +16,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VARIANTS = {"nopad": ["-DCW_NO_PAD64"], "matrix": ["-DCW_POA_CODES=0"], "m2codes": ["-DCW_M2_CODES=1"], "qmatrix": ["-DCW_Q_CODES=0"], "noreplay": ["-DCW_POAQ_REPLAY=0", "-DCW_POA_REPLAY=0"], "qflat": ["-DCW_POAQ_FLAT=1"], "lw": ["-DCW_POA_LW=1"], "lwall": ["-DCW_POA_LW=1", "-DCW_POALW_MIN_MEAN=1", "-DCW_POALW_MIN_MEMBERS=2"], "nogroup": ["-DCW_POA_GROUP_FILL=0", "-DCW_POA_VPROBE=0"]}
+VARIANTS = {"nopad": ["-DCW_NO_PAD64"], "matrix": ["-DCW_POA_CODES=0"], "m2codes": ["-DCW_M2_CODES=1"], "qmatrix": ["-DCW_Q_CODES=0"], "noreplay": ["-DCW_POAQ_REPLAY=0", "-DCW_POA_REPLAY=0"], "nogroup": ["-DCW_POA_GROUP_FILL=0"]}
 
 CHILD = r"""
 import os, sys
@@ -39,7 +35,7 @@ for depth, n, msa, wlen in ((150, 32, 150, 500), (30, 96, 20, 500), (60, 32, 150
     exp, _ = oracle_lib.oracle_run(prm, hb, threads=os.cpu_count() or 1)
     for w in range(n):
         same = same and got.consensus(w) == exp.consensus(w) and int(got.status[w]) == int(exp.status[w])
-# few anchors -> segments of hundreds of bases: the wide packed rows of tiers M2 / L (what tier LW spreads over waves)
+# few anchors -> segments of hundreds of bases: the wide packed rows of tiers M2 / L
 import random
 rng = random.Random(5)
 def mutate(s, rate):

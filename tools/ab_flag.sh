@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of one compile-time flag on the GPU box: tools/ab_flag.sh "-DCW_S_EDGES_LDS=0" [workload]  -- two-engine bench steps of the default
+# A/B of one compile-time flag on the GPU box: tools/ab_flag.sh "-DCW_M2_CODES=1" [workload]  -- two-engine bench steps of the default
 # build and of the build with the flag, and the one-engine phase cycle totals of both.
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
