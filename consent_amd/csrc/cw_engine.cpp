@@ -1,6 +1,10 @@
 /*
- * cw_engine.cpp -- host side of libconsent_amd.so: engine life cycle, scratch sizing, kernel launches,
- * host-buffer staging, per-stage timing.  C ABI declared in include/consent_amd.h.
+ * cw_engine.cpp -- the engine of libconsent_amd.so, host side (C ABI: include/consent_amd.h; inspection: csrc/cw_private.h).  In this order: the launch
+ * table (every kernel's dynamic LDS size, named once); one device run = validate, plan and bind (cw_plan.h -> DevScratch), launch shape (grids and routing
+ * from batch and knobs), enqueue (the order of a step); engine life cycle (cw_create / cw_destroy: streams in a fixed order of creation); per-stage timing
+ * and the inspection entry points; the launchers of the path's neighbours (pile extraction, result planning, read re-assembly); host batches (cw_submit /
+ * cw_wait) and the loop that runs a batch again with a larger plan (cw_run, cw_run_device_sync).
+ * The scratch plan is cw_plan.h (host arithmetic only); the host feeders, cw_window_positions among them, are cw_hostio.cpp.
  */
 #include "cw_internal.h"
 #include "cw_private.h"
@@ -13,6 +17,7 @@
 #include "cw_extract.h"
 #include "cw_stitch.h"
 #include "cw_pack.h"
+#include "cw_plan.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -32,151 +37,28 @@ static_assert(CW_IDX_STAGE_OFF + 16 + CW_IDX_STAGE_N * 8 + 4 * CW_IDX_STAGE_WORD
 
 static_assert(CW_FIN_CB_BIG == CW_CONS_SLOT_MAX, "the largest consensus slot (include/consent_amd.h CW_CONS_SLOT_BYTES, engine.py cons_slot_bytes) is what the finish kernel's second pass holds");
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+/* ---- launch table: the dynamic LDS of every kernel that asks for some -- a constant, or a function of the work-group's waves where a knob chooses them.
+   set_kernel_attributes allows each kernel the most its launch can ask for, and the launch passes the same name. */
+constexpr size_t kLdsIndex = CW_IDX_LDS_BYTES;
+constexpr size_t lds_chain(size_t slab) { return CW_CH_WAVES * slab; } /* CW_CH_SLAB, or CW_CH_SLAB_LONG for an engine configured for long templates */
+constexpr size_t kLdsSortMax = CW_SORT_LDS_CLS; /* the launch keeps CW_SORT_LDS bytes of classes of it (launch_shape) */
+constexpr size_t kLdsTierS = (size_t)CW_POA_SLAB_BYTES * CW_POA_WAVES;
+constexpr size_t lds_tier_q(uint32_t waves) { return (size_t)CW_POAQ_TASK_BYTES * 4 * waves; } /* four tasks per wave */
+constexpr size_t lds_tier_h(uint32_t waves) { return (size_t)CW_POAH_TASK_BYTES * 2 * waves; } /* two tasks per wave; six waves at most: cw_poa_h_kernel's launch bounds */
+constexpr size_t kLdsFinish = (size_t)CW_FIN_SLAB * CW_FIN_WAVES, kLdsFinishBig = CW_FIN_SLAB_OF(0);
+constexpr size_t kLdsStitch = (size_t)CW_ST_WAVES * CW_ST_SLAB; /* what the wide re-assembly kernel needs (it is given more: stitch_lds_one) */
+constexpr size_t kLdsStitchNarrow = (size_t)CW_STN_WAVES * CW_ST_SLAB_OF(CW_STN_QMAX, CW_STN_RMAX);
 
-struct TierCfg { uint32_t slots; size_t slab_bytes; };
-
-size_t big_slab_bytes() {
-    return align_up((size_t)CW_POAB_HC * 4 + CW_POA_GRAPH_BYTES(CW_POAB_NC, CW_POAB_EC, CW_POAB_LC), 256);
-}
-
-/* Work-groups per CU of the four concurrent POA tier kernels (S, M1, M2, L).  The tiers share each CU's 160 KiB of LDS, every kernel
-   is persistent, and which kernel's work-groups get onto a CU first is up to the hardware dispatcher: whatever is resident keeps its
-   LDS until its list is empty.  Measured with the task timeline (tools/task_trace.py): with the shallow mix on depth-150 piles tier S
-   (3 x 45 KB) held every CU for the first 27 ms and tier L, the long pole, started late (POA stage 79 ms); with fewer S and M2
-   work-groups and one more of tier L it takes 69 ms; the shallow piles of config 2 prefer the old mix (19.6 vs 21.5 ms).  The choice
-   goes by the mean pile depth of the batch.  Slabs are sized for the larger of the two, so the scratch layout does not depend on it.
-   CW_WGS_S / _M1 / _M2 / _L override (experiments). */
-struct TierMix { uint32_t s, m1, m2, l; };
-TierMix tier_mix(bool deep) {
-    TierMix m = deep ? TierMix{4, 5, 4, 2u} : TierMix{4, 5, 4, 2u}; /* see DESIGN.md: no static mix was robustly better than this one (round 4: tier S's work-groups take 24 KB, not 45) */
-    auto knob = [](const char* name, uint32_t dflt) { const char* v = CW_AID_ENV(name); if (!v) return dflt; const int x = atoi(v); return x >= 1 && x <= 12 ? (uint32_t)x : dflt; };
-    m.s = knob("CW_WGS_S", m.s); m.m1 = knob("CW_WGS_M1", m.m1); m.m2 = knob("CW_WGS_M2", m.m2); m.l = knob("CW_WGS_L", m.l);
-    if (m.s > 6) m.s = 6;
-    if (m.m1 > 12) m.m1 = 12;
-    if (m.m2 > 12) m.m2 = 12;
-    if (m.l > 8) m.l = 8;
-    return m;
-}
-
-/* Work-groups of tier t (0 = S, 1 = M1, 2 = M2, 3 = L) worth launching for a batch of n_windows: the full persistent grid for a full batch,
-   fewer for a small one (a 16384-window batch at depth 150 has ~5 tier-S, ~4 tier-M1, ~0.7 tier-M2 and ~0.25 tier-L tasks per window) --
-   and with the grids the slabs: an engine used to hold ~10 GB of them whatever the batch, a 24-window batch now holds ~0.3 GB. */
-uint32_t tier_wgs_cap(int t, uint32_t n_windows, uint32_t full) {
-    static const uint32_t div[4] = {2, 4, 8, 8};
-    const uint64_t want = (uint64_t)n_windows / div[t] + 4u;
-    return want < full ? (uint32_t)want : full;
-}
-
-void tier_config(int cus, uint32_t big_slots, uint32_t n_windows, TierCfg (&t)[CW_TIERS]) {
-    /* slabs: one per wave the hardware can hold at once plus a margin; waves claim them (slot_busy) */
-    const TierMix mix = tier_mix(false);
-    const uint32_t pass1 = 64u < (uint32_t)cus * 2u ? 64u : (uint32_t)cus * 2u;
-    uint32_t l_wgs = tier_wgs_cap(3, n_windows, (uint32_t)cus * mix.l); /* (3.5 MB a slab: a generous count here was 12 GB, and allocating it stalled an engine's first job by 1-2 s) */
-    if (l_wgs < pass1) l_wgs = pass1; /* the overflow pass launches its own tier-L work-groups */
-    t[0] = {(tier_wgs_cap(0, n_windows, (uint32_t)cus * mix.s) * 2u + 8u) * CW_POA_WAVES, CW_POA_SLAB2_TOTAL(CW_POA_NC, CW_POA_EC, CW_POA_LC)}; /* tier S (round 4: cold arrays, flagged rows and code words in a slab) */
-    /* round 6: a margin of an eighth over the waves the grids hold (a half through round 5): the plan of a 10 240-window job was 16.6 GB, most of it slabs,
-       and a fresh process with four workers on a device spent 0.6-1.6 s allocating before its first job ran (tools/plan_sizes.py) */
-    t[1] = {(tier_wgs_cap(1, n_windows, (uint32_t)cus * mix.m1) * 9u / 8u + 8u) * CW_POAM1_WAVES, CW_POA_SLAB2_TOTAL(CW_POAM1_NC, CW_POAM1_EC, CW_POAM1_LC)};
-    t[2] = {(tier_wgs_cap(2, n_windows, (uint32_t)cus * mix.m2) * 9u / 8u + 8u) * CW_POAM2_WAVES, CW_POA_SLAB2_TOTAL(CW_POAM2_NC, CW_POAM2_EC, CW_POAM2_LC)};
-    t[3] = {(l_wgs * 9u / 8u + 8u) * CW_POAL_WAVES, CW_POA_SLAB2_TOTAL(CW_POAL_NC, CW_POAL_EC, CW_POAL_LC)};
-    const uint64_t bs = (uint64_t)n_windows / 16u + 8u;
-    t[4] = {bs < big_slots ? (uint32_t)bs / 4u * 4u : big_slots, big_slab_bytes()};
-    t[5] = {8u, 64u}; /* (tier H's slabs go by resident task, not by claim: ScratchPlan::hslab) */
-}
-
-struct ScratchPlan {
-    size_t win, solid_key, solid_cnt, seg_off, seg_len, arena, tasks, members, ctr, list[CW_TIERS], over[CW_TIERS], slab[CW_TIERS], qslab, hslab, finretry, finbig, pfall, ablock, finvis, exg, tdbg, sbusy[CW_TIERS], total;
-    uint64_t pfall_elems, ablock_units;
-    uint64_t solid_cap, seg_cap, arena_cap;
-    uint32_t task_cap, member_cap, arena_scale;
-    TierCfg tier[CW_TIERS];
+/* tiers M1, M2 and L are instances of cw_poa_slab_kernel: a tier's template arguments and the LDS of its work-group, PASS 0 = its own list, 1 = the overflow pass */
+template <int NC, int EC, int LC, int WAVES, int TIER, size_t LDS>
+struct SlabTier {
+    static constexpr size_t lds = LDS;
+    template <int PASS> static const void* kernel() { return (const void*)cw_poa_slab_kernel<NC, EC, LC, WAVES, TIER, PASS>; }
+    template <int PASS> static void launch(uint32_t grid, hipStream_t st, const DevBatch& db, const DevScratch& sc) { cw_poa_slab_kernel<NC, EC, LC, WAVES, TIER, PASS><<<grid, 64 * WAVES, LDS, st>>>(db, sc); }
 };
-
-/* tmax: template k-mers per window the plan provides for -- 1024 (templates of up to 1032 bases at k = 9: every window of the wrappers' defaults) unless the
-   engine was configured for longer ones (cw_configure, up to CW_TMAX): the index kernel takes any template of up to CW_TMAX k-mers, what grows is the plan */
-/* the global position-matrix slot of the index kernel: rows (sequences) per template k-mer at most -- what a re-run after CW_WHY_MATRIX gets */
-constexpr uint64_t kPfRowsMax = 4100;
-
-ScratchPlan plan_scratch(const cw_params& prm, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t big_slots, uint32_t scale = 1, uint32_t tmax = 1024,
-                         bool pf_full = false) {
-    ScratchPlan p;
-    memset(&p, 0, sizeof(p));
-    p.solid_cap = (16ull * n_words) / prm.solid + n_windows + 16;
-    p.seg_cap = (uint64_t)n_windows * (tmax + 2);
-    /* scale: 1, or 4 / 16 / 64 after a run whose windows stopped on the task / member / arena capacities -- heuristics of the batch, which a batch of
-       few, heavy windows (900-base windows at depth 100) outgrows: cw_run_device_sync runs such a batch again with the larger plan */
-    /* the arena is addressed with 32-bit offsets (WinInfo, PoaTask): its scale is the largest one <= scale that keeps the batch's arena inside them
-       (x4 of a 52 000-window batch did not, and the re-run ended in CW_E_INVALID); tasks and members scale on their own */
-    const uint64_t arena1 = (uint64_t)n_windows * (16ull * (tmax + 16) + 4096);
-    uint64_t as = scale;
-    while (as > 1 && arena1 * as > 0xFFFFFFFFull) as /= 2;
-    p.arena_scale = (uint32_t)as;
-    p.arena_cap = arena1 * as;
-    uint64_t tc = (64ull * n_windows + 1024) * scale, mc = (2048ull * n_windows + 4096) * scale;
-    if (const char* v = CW_AID_ENV("CW_PLAN_DIV")) { const long x = atol(v); if (x >= 2) { tc = tc / (uint64_t)x + 1; mc = mc / (uint64_t)x + 1; } } /* test aid: a first plan that is too small, so that the growth of cw_run / cw_run_device_sync is exercised */
-    p.task_cap = (uint32_t)(tc > 0x7FFFFFFFull ? 0x7FFFFFFFull : tc);
-    p.member_cap = (uint32_t)(mc > 0x7FFFFFFFull ? 0x7FFFFFFFull : mc);
-    /* test aid: shrink the two heuristic capacities so that the overflow path of the chain kernel's task emission can be exercised */
-    if (const char* v = CW_AID_ENV("CW_TASK_CAP")) { const long x = atol(v); if (x >= 1 && (uint64_t)x < p.task_cap) p.task_cap = (uint32_t)x; }
-    if (const char* v = CW_AID_ENV("CW_MEMBER_CAP")) { const long x = atol(v); if (x >= 1 && (uint64_t)x < p.member_cap) p.member_cap = (uint32_t)x; }
-    tier_config(cus, big_slots, n_windows, p.tier);
-    size_t o = 0;
-    auto put = [&](size_t& slot, size_t bytes) { slot = o; o = align_up(o + bytes, 256); };
-    put(p.win, (size_t)n_windows * sizeof(WinInfo));
-    put(p.solid_key, p.solid_cap * 4);
-    put(p.solid_cnt, p.solid_cap * 4);
-    put(p.seg_off, p.seg_cap * 4);
-    put(p.seg_len, p.seg_cap * 4);
-    put(p.arena, p.arena_cap);
-    put(p.tasks, ((size_t)p.task_cap + 1) * sizeof(PoaTask)); /* + the batch's neutral task at index task_cap (cw_setup_kernel; cw_chain.h "cap_ok") */
-    put(p.members, (size_t)p.member_cap * sizeof(PoaMember));
-    put(p.ctr, sizeof(BatchCounters));
-    for (int t = 0; t < CW_TIERS; ++t) put(p.list[t], (size_t)p.task_cap * 4); /* list 0 = tier Q */
-    for (int t = 0; t < CW_TIERS; ++t) put(p.over[t], (size_t)p.task_cap * 4);
-    for (int t = 0; t < CW_TIERS; ++t) put(p.slab[t], (size_t)p.tier[t].slots * p.tier[t].slab_bytes);
-    put(p.qslab, (size_t)cus * CW_POAQ_WAVES * 4 * CW_POAQ_SLAB_BYTES); /* tier Q: kept rows of every task a CU can hold */
-    put(p.hslab, (size_t)cus * CW_POAH_WAVES * 2 * CW_POAH_SLAB_BYTES); /* tier H: kept rows and code words */
-    /* anchor blocks (cw_ab_bytes): header + keys + presence bitsets + dirty list + the position matrix, 2 bytes per (template k-mer,
-       sequence); at most CW_TMAX template k-mers per window, so the bound is per sequence, whatever the pieces' lengths are
-       (a pile of many pieces only k bases long has few packed words but a full-width matrix) */
-    p.ablock_units = ((uint64_t)n_seqs * (2ull * tmax + 2 + tmax / 8) + (uint64_t)n_windows * (tmax * (4ull + 8 + 8 + 8) + 256)) / 16 + 64;
-    put(p.ablock, (size_t)p.ablock_units * 16);
-    /* the position matrix of a window whose matrix does not fit LDS: up to tmax anchors x the sequences of a pile -- sixteen times the batch's mean depth, at
-       least 1024 and at most ~4096 of them (round 6; 4100 whatever the batch through round 5: 2.1 GB of a driver job's plan at depth 30).  The mean depth
-       says nothing about the deepest pile, so a window that stops on this slot (CW_WHY_MATRIX) is run again with the slot at kPfRowsMax rows (pf_full,
-       grow_if_that_helps): whether it fits does not depend on its neighbours.  Beyond kPfRowsMax it is a reported capacity, as it always was */
-    const uint64_t mean_n = n_windows ? (uint64_t)n_seqs / n_windows + 1 : 1;
-    const uint64_t pf_n = pf_full ? kPfRowsMax : mean_n * 16 < 1024 ? 1024 : mean_n * 16 > kPfRowsMax ? kPfRowsMax : mean_n * 16;
-    p.pfall_elems = (uint64_t)tmax * pf_n;
-    const size_t idx_wgs = n_windows < (uint32_t)cus ? n_windows : (size_t)cus; /* work-groups of the index kernel: one fallback slot each */
-    put(p.pfall, idx_wgs * p.pfall_elems * 2);
-    for (int t = 0; t < CW_TIERS; ++t) put(p.sbusy[t], (size_t)p.tier[t].slots * 4);
-    put(p.exg, idx_wgs * CW_EXG_SLOTS * 8);
-    put(p.tdbg, getenv("CW_TASK_TRACE") ? (size_t)p.task_cap * 16 : 0);
-    /* one visited bitmap per wave of the first finish pass -- and of the second (one wave per work-group, up to 64 of them): the larger of the two */
-    put(p.finvis, std::max<size_t>((size_t)cus * CW_FIN_WGS_PER_CU * CW_FIN_WAVES, 64) * CW_FIN_VIS_GLB_WORDS * 4);
-    put(p.finretry, (size_t)n_windows * 4);
-    put(p.finbig, (size_t)64 * 3 * CW_FIN_CB_BIG);
-    p.total = o;
-    return p;
-}
-
-/* The largest batch a plan for templates of tmax k-mers can address: per-window offsets into the segment table and the arena are 32-bit, and
-   their totals are n_windows x (tmax + 2) and n_windows x (16 (tmax + 16) + 4096) at scale 1 -- at most CW_MAX_BATCH_WINDOWS (include/consent_amd.h
-   cw_max_batch_windows).  115 704 windows at tmax 2048, CW_MAX_BATCH_WINDOWS at the default 1024. */
-uint32_t max_batch_windows(uint32_t tmax) {
-    const uint64_t per_seg = (uint64_t)tmax + 2, per_arena = 16ull * (tmax + 16) + 4096;
-    uint64_t n = CW_MAX_BATCH_WINDOWS;
-    n = std::min<uint64_t>(n, 0xFFFFFFFFull / per_seg);
-    n = std::min<uint64_t>(n, 0xFFFFFFFFull / per_arena);
-    return (uint32_t)n;
-}
-
-uint32_t plan_tmax(uint32_t k, uint32_t max_template_len) { /* cw_configure's number */
-    uint32_t kmers = max_template_len >= k ? max_template_len - k + 1u : 1u;
-    return kmers < 128u ? 128u : kmers;
-}
+using TierM1 = SlabTier<CW_POAM1_NC, CW_POAM1_EC, CW_POAM1_LC, CW_POAM1_WAVES, 1, (size_t)CW_POA_HOT2C_BYTES(CW_POAM1_NC, CW_POAM1_EC, CW_POAM1_LC) * CW_POAM1_WAVES>;
+using TierM2 = SlabTier<CW_POAM2_NC, CW_POAM2_EC, CW_POAM2_LC, CW_POAM2_WAVES, 2, (size_t)CW_POA_HOT2T_BYTES(2, CW_POAM2_NC, CW_POAM2_EC, CW_POAM2_LC) * CW_POAM2_WAVES>;
+using TierL = SlabTier<CW_POAL_NC, CW_POAL_EC, CW_POAL_LC, CW_POAL_WAVES, 3, (size_t)CW_POAL_LDS_BYTES>;
 
 int ensure(void** ptr, size_t* have, size_t need) {
     if (*have >= need) return CW_OK;
@@ -204,7 +86,7 @@ int check_params(const cw_params* p) {
 /* LDS request of the wide re-assembly kernel: what it needs, or -- to keep a second work-group off the CU (cw_stitch_device) -- a little more than
    half of what the DEVICE's CUs have (the constant 84 KB encoded gfx950's 160 KB), never more than a work-group may ask for */
 size_t stitch_lds_one(const hipDeviceProp_t& prop) {
-    size_t need = (size_t)CW_ST_WAVES * CW_ST_SLAB, half = prop.sharedMemPerMultiprocessor / 2 + 4096, cap = prop.sharedMemPerBlock;
+    size_t need = kLdsStitch, half = prop.sharedMemPerMultiprocessor / 2 + 4096, cap = prop.sharedMemPerBlock;
     if (prop.sharedMemPerMultiprocessor == 0) half = 84u * 1024u;
     size_t want = half > need ? half : need;
     if (cap >= need && want > cap) want = cap;
@@ -212,48 +94,280 @@ size_t stitch_lds_one(const hipDeviceProp_t& prop) {
 }
 
 int set_kernel_attributes(const hipDeviceProp_t& prop) {
-    const int lds_st = (int)stitch_lds_one(prop);
-    if (hipFuncSetAttribute((const void*)cw_index_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CW_IDX_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_chain_kernel<CW_CH_SLAB>, hipFuncAttributeMaxDynamicSharedMemorySize, CW_CH_WAVES * CW_CH_SLAB) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_chain_kernel<CW_CH_SLAB_LONG>, hipFuncAttributeMaxDynamicSharedMemorySize, CW_CH_WAVES * CW_CH_SLAB_LONG) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_sort_tier_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CW_SORT_LDS_CLS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_poa_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CW_POA_SLAB_BYTES * CW_POA_WAVES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_poa_q_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CW_POAQ_TASK_BYTES * 4 * CW_POAQ_WAVES) != hipSuccess ||
+    auto allow = [](const void* kernel, size_t lds) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; };
+    const size_t lds_st = stitch_lds_one(prop);
+    const bool ok = allow((const void*)cw_index_kernel, kLdsIndex) &&
+        allow((const void*)cw_chain_kernel<CW_CH_SLAB>, lds_chain(CW_CH_SLAB)) && allow((const void*)cw_chain_kernel<CW_CH_SLAB_LONG>, lds_chain(CW_CH_SLAB_LONG)) &&
+        allow((const void*)cw_sort_tier_kernel, kLdsSortMax) &&
+        allow((const void*)cw_poa_kernel, kLdsTierS) && allow((const void*)cw_poa_q_kernel, lds_tier_q(CW_POAQ_WAVES)) &&
 #if CW_Q_CODES && defined(CW_TEST_AIDS) /* tier H: an opt-in kernel of the test-aid build (CW_TIER_H), not in the product's code object */
-        hipFuncSetAttribute((const void*)cw_poa_h_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CW_POAH_TASK_BYTES * 2 * 6) != hipSuccess ||
+        allow((const void*)cw_poa_h_kernel, lds_tier_h(6)) &&
 #endif
-        hipFuncSetAttribute((const void*)cw_poa_slab_kernel<CW_POAM1_NC, CW_POAM1_EC, CW_POAM1_LC, CW_POAM1_WAVES, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CW_POA_HOT2C_BYTES(CW_POAM1_NC, CW_POAM1_EC, CW_POAM1_LC) * CW_POAM1_WAVES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_poa_slab_kernel<CW_POAM2_NC, CW_POAM2_EC, CW_POAM2_LC, CW_POAM2_WAVES, 2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CW_POA_HOT2T_BYTES(2, CW_POAM2_NC, CW_POAM2_EC, CW_POAM2_LC) * CW_POAM2_WAVES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_poa_slab_kernel<CW_POAL_NC, CW_POAL_EC, CW_POAL_LC, CW_POAL_WAVES, 3, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CW_POAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_poa_slab_kernel<CW_POAM1_NC, CW_POAM1_EC, CW_POAM1_LC, CW_POAM1_WAVES, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CW_POA_HOT2C_BYTES(CW_POAM1_NC, CW_POAM1_EC, CW_POAM1_LC) * CW_POAM1_WAVES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_poa_slab_kernel<CW_POAM2_NC, CW_POAM2_EC, CW_POAM2_LC, CW_POAM2_WAVES, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CW_POA_HOT2T_BYTES(2, CW_POAM2_NC, CW_POAM2_EC, CW_POAM2_LC) * CW_POAM2_WAVES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_poa_slab_kernel<CW_POAL_NC, CW_POAL_EC, CW_POAL_LC, CW_POAL_WAVES, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CW_POAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_finish_kernel<CW_FIN_CB, CW_FIN_WAVES, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CW_FIN_SLAB * CW_FIN_WAVES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_finish_kernel<CW_FIN_CB_BIG, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CW_FIN_SLAB_OF(0)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_st) != hipSuccess ||
+        allow(TierM1::kernel<0>(), TierM1::lds) && allow(TierM2::kernel<0>(), TierM2::lds) && allow(TierL::kernel<0>(), TierL::lds) &&
+        allow(TierM1::kernel<1>(), TierM1::lds) && allow(TierM2::kernel<1>(), TierM2::lds) && allow(TierL::kernel<1>(), TierL::lds) &&
+        allow((const void*)cw_finish_kernel<CW_FIN_CB, CW_FIN_WAVES, false>, kLdsFinish) && allow((const void*)cw_finish_kernel<CW_FIN_CB_BIG, 1, true>, kLdsFinishBig) &&
+        allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES, false>, lds_st) &&
 #ifdef CW_TEST_AIDS
-        hipFuncSetAttribute((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_st) != hipSuccess ||
-        hipFuncSetAttribute((const void*)cw_stitch_kernel<CW_STN_QMAX, CW_STN_RMAX, 5, CW_STN_WAVES, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CW_STN_WAVES * CW_ST_SLAB_OF(CW_STN_QMAX, CW_STN_RMAX)) != hipSuccess ||
+        allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES, true>, lds_st) &&
+        allow((const void*)cw_stitch_kernel<CW_STN_QMAX, CW_STN_RMAX, 5, CW_STN_WAVES, false>, kLdsStitchNarrow) &&
 #endif
-        false)
-        return CW_E_NO_DEVICE;
-    return CW_OK;
+        true;
+    return ok ? CW_OK : CW_E_NO_DEVICE;
 }
 
-int stage_begin(cw_engine* e, hipStream_t st, const char* name) {
+/* one named stage of a run: what `launch` enqueues on st, between the two events cw_last_timings and cw_poll read */
+template <class L>
+void stage(cw_engine* e, hipStream_t st, const char* name, L launch) {
     const int i = e->n_stages < CW_MAX_STAGES ? e->n_stages++ : CW_MAX_STAGES - 1;
     e->stage_name[i] = name;
     (void)hipEventRecord(e->ev0[i], st);
-    return i;
+    launch();
+    (void)hipEventRecord(e->ev1[i], st);
 }
-void stage_end(cw_engine* e, hipStream_t st, int i) { (void)hipEventRecord(e->ev1[i], st); }
+
+/* what a plan of this engine is made from, for a batch of these totals: its parameters, its device, the tier-G slots of its last run, its current scale and
+   template length, the matrix slot by the mean depth.  Callers change what they ask about (a scale to try, pf_full). */
+PlanInput plan_input(const cw_engine* e, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words) { return PlanInput{e->prm, n_windows, n_seqs, n_words, e->cus, e->last_big_slots ? e->last_big_slots : 64u, e->cap_scale, e->tmax_plan, false}; }
+
+/* The last run's BatchCounters in scratch: `bytes` of them from `off`, by an asynchronous copy on st into dst -- pinned: cw_host_fb -- and a wait for st:
+   hipMemcpy's null stream would wait for every other stream of the device, the other worker's job among them.  The caller holds e->mu and has checked e->scratch. */
+int read_counters(cw_engine* e, hipStream_t st, size_t off, size_t bytes, void* dst) {
+    CW_HIP(hipSetDevice(e->device));
+    CW_HIP(hipMemcpyAsync(dst, (const uint8_t*)e->scratch + e->last_ctr_off + off, bytes, hipMemcpyDeviceToHost, st)); CW_HIP(hipStreamSynchronize(st));
+    return CW_OK;
+}
+int read_counters_idle(cw_engine* e, BatchCounters* c) { /* all of them, once everything on the device has ended: the inspection entry points */
+    CW_HIP(hipSetDevice(e->device));
+    CW_HIP(hipDeviceSynchronize());
+    CW_HIP(hipMemcpy(c, (const uint8_t*)e->scratch + e->last_ctr_off, sizeof(*c), hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+/* ---- one device run: validate, plan and bind, launch shape, enqueue ----------------------------------------------------------- */
+
+/* CW_OK for a batch that can run -- and for an empty one, which the caller answers without running */
+int validate_run(const cw_engine* e, const cw_batch* batch, const cw_result* res) {
+    if (!e || !batch || !res || !res->cons || !res->cons_off || !res->cons_len || !res->win_status) return CW_E_INVALID;
+    if ((res->solid != nullptr) != (res->solid_off != nullptr) || (res->solid != nullptr) != (res->solid_len != nullptr)) return CW_E_INVALID;
+    if (batch->n_windows == 0) return CW_OK;
+    if (!batch->win_first_seq || !batch->seq_len || !batch->seq_word_off || !batch->bases) return CW_E_INVALID;
+    /* per-window offsets into the arena, the solid table and the segment table are 32-bit (WinInfo, PoaTask): a batch is
+       limited so that none of them can wrap -- split larger inputs (the library's own drivers do; cw_max_batch_windows) */
+    if (batch->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
+    return CW_OK;
+}
+
+/* every pointer and capacity of DevScratch that comes from the plan; what depends on the batch and the knobs is launch_shape's */
+DevScratch bind_scratch(const ScratchPlan& p, uint8_t* base) {
+    DevScratch sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.win = (WinInfo*)(base + p.win);
+    sc.solid_key = (uint32_t*)(base + p.solid_key); sc.solid_cnt = (uint32_t*)(base + p.solid_cnt);
+    sc.seg_off = (uint32_t*)(base + p.seg_off); sc.seg_len = (uint32_t*)(base + p.seg_len);
+    sc.arena = base + p.arena;
+    sc.tasks = (PoaTask*)(base + p.tasks); sc.task_cap = p.task_cap;
+    sc.members = (PoaMember*)(base + p.members); sc.member_cap = p.member_cap;
+    sc.ctr = (BatchCounters*)(base + p.ctr);
+    sc.list_cap = p.task_cap;
+    for (int t = 0; t < CW_TIERS; ++t) {
+        sc.tier_list[t] = (uint32_t*)(base + p.list[t]); sc.over_list[t] = (uint32_t*)(base + p.over[t]);
+        sc.slab[t] = base + p.slab[t]; sc.slab_bytes[t] = p.tier[t].slab_bytes; sc.slots[t] = p.tier[t].slots;
+        sc.slot_busy[t] = (uint32_t*)(base + p.sbusy[t]);
+    }
+    sc.q_slab = base + p.qslab; sc.h_slab = base + p.hslab;
+    sc.p_fallback = (uint16_t*)(base + p.pfall); sc.p_fallback_elems = p.pfall_elems;
+    sc.ablock = base + p.ablock; sc.ablock_units = p.ablock_units;
+    sc.ex_fallback = (unsigned long long*)(base + p.exg);
+    sc.task_dbg = getenv("CW_TASK_TRACE") ? (uint4*)(base + p.tdbg) : nullptr; /* (the plan gives it room under the same condition) */
+    sc.fin_vis = (uint32_t*)(base + p.finvis); sc.fin_vis_words = CW_FIN_VIS_GLB_WORDS;
+    sc.fin_retry = (uint32_t*)(base + p.finretry); sc.fin_big = base + p.finbig;
+    return sc;
+}
+
+/* plan the batch's scratch (cw_plan.h), see that the engine holds that much, bind it; remembers what the inspection entry points and the re-run loop need */
+int plan_and_bind(cw_engine* e, const cw_batch* batch, bool pf_full, ScratchPlan* plan, DevScratch* sc) {
+    uint32_t big_slots = 64; /* tier G's kernel is sixteen work-groups of four waves at most (big_wgs, launch_shape): 64 slabs of 16.8 MB are all it can use (256 through round 5: 4.3 GB) */
+    if (const char* env = CW_AID_ENV("CW_BIG_SLOTS")) { int v = atoi(env); if (v >= 4 && v <= 4096) big_slots = (uint32_t)v / 4 * 4; }
+    PlanInput in = plan_input(e, batch->n_windows, batch->n_seqs, batch->n_words);
+    in.big_slots = big_slots; in.pf_full = pf_full;
+    const ScratchPlan& p = *plan = plan_scratch(in);
+    if (p.solid_cap > 0xFFFFFFFFull || p.seg_cap > 0xFFFFFFFFull || p.arena_cap > 0xFFFFFFFFull) return CW_E_INVALID; /* see CW_MAX_BATCH_WINDOWS */
+    e->last_windows = batch->n_windows; e->last_big_slots = big_slots; e->last_ctr_off = p.ctr;
+    if (int rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) return rc;
+    e->last_tasks_off = p.tasks; e->last_tdbg_off = p.tdbg; e->last_task_cap = p.task_cap;
+    if (!e->step_clock) { CW_HIP(hipMalloc((void**)&e->step_clock, 16)); CW_HIP(hipMemset(e->step_clock, 0, 16)); }
+    *sc = bind_scratch(p, (uint8_t*)e->scratch);
+    sc->step_clock = e->step_clock;
+    return CW_OK;
+}
+
+/* grids and work-group shapes of one run, but for the tier kernels' grids: those are DevScratch::persist_wgs, with the routing margins and the linger count */
+struct LaunchShape {
+    uint32_t h_waves, q_grid, q_waves, sort_lds, sort_thr, pass1_wgs, big_wgs, arena_div, no_tier_x; /* (pass1_wgs, big_wgs: the overflow pass -- tier L's second launch, tier G) */
+};
+
+uint32_t knob_u(const char* name, uint32_t dflt, uint32_t lo, uint32_t hi) { const char* v = CW_AID_ENV(name); if (!v) return dflt; const long x = atol(v); return x >= (long)lo && x <= (long)hi ? (uint32_t)x : dflt; }
+
+/* what depends on the batch and the knobs: the grids, and in sc the routing margins, the tiers in use and the linger count */
+LaunchShape launch_shape(cw_engine* e, const cw_batch* batch, const ScratchPlan& p, DevScratch& sc) {
+    LaunchShape ls;
+    const uint32_t cus = (uint32_t)e->cus, W = batch->n_windows;
+    /* how many tier-L work-groups stay on the live overflow queue: about half of what the last finished batch handed over (few when
+       nothing overflows, since a lingering work-group holds LDS the other tiers could use).  The count arrives in pinned host memory
+       by an asynchronous copy at the end of each run: nothing here waits for the device */
+    if (e->timings_valid) { /* a run has been enqueued before: its count, or that of the one before it, is there */
+        const uint32_t want = e->host_fb->handed_over / 2;
+        e->linger_wgs = want < 16 ? 16 : want > 256 ? 256 : want;
+    }
+    sc.linger_wgs = e->linger_wgs ? e->linger_wgs : 64;
+    if (const char* env = CW_AID_ENV("CW_LINGER_WGS")) { int v = atoi(env); if (v >= 0 && v <= 1024) sc.linger_wgs = (uint32_t)v; }
+    /* grids of the four concurrent tier kernels: every work-group loops until its tier's list is empty (sc.persist_wgs: see cw_poa_slab_kernel; none for tier G) */
+    const TierMix mix = tier_mix();
+    sc.persist_wgs[0] = tier_wgs_cap(0, W, cus * mix.s); sc.persist_wgs[1] = tier_wgs_cap(1, W, cus * mix.m1);
+    sc.persist_wgs[2] = tier_wgs_cap(2, W, cus * mix.m2); sc.persist_wgs[3] = tier_wgs_cap(3, W, cus * mix.l);
+    /* Tier H (two tasks per wave on 32-lane halves, cw_poa_q.h; round 5: tier Q's code instantiated for members of up to 63 bases and graphs of up
+       to 128 nodes -- byte-sized graph arrays, recorded decisions, code words in the task's slab; it replaces round 3's opt-in kernel).  Bit-identical
+       (tests/test_gpu_tier_q.py, test_gpu_parity.py) and OFF: measured on one box at depth 150 it takes tier S's 41.7 k tasks in 27.4 ms where tier
+       S needs 28.4 -- 64 G wave-cycles against 69 -- and with its 18 waves per CU the other tiers slow down (M2 30.8 -> 36.7, L 41 -> 44 ms): step
+       61-63 ms against 55-58; depth 30: 23.6 against 22.7.  Four tasks per wave (tier Q) beat tier S's scalar-controlled row loop six to one in
+       machine time; two per wave do not: a per-lane row loop is ~100 instructions, tier S's 45.  CW_TIER_H=1|2 (test-aid build) turns it on. */
+    /* Routing margins against late hand-overs.  A task that outgrows tier S or M1 is redone in tier L, whose work-groups only turn to the
+       hand-over queue once their own list is empty: measured on a depth-150 batch (tools/task_trace.py), the ~150 tasks of 24-45 members
+       x 27-31 bases that the depth-aware estimate put just inside tier S's 2048 cells, and the ~45 tasks of 52-64 members x 90-120 bases
+       that outgrew tier M1's 256 nodes, kept a handful of tier-L waves busy for 10-20 ms after every other tier had finished.  With tier S
+       taking only what is expected to stay below 1700 cells and tier M1 chosen by the depth-aware estimate as well, one task per batch is
+       handed over instead of ~195, and the step (two engines) goes from 73.1 to 68.8 ms on the same box.  CW_S_ROUTE_CELLS /
+       CW_M1_ROUTE_DEPTH=0 give the old routing (experiments; results do not depend on the tier). */
+    sc.s_route_cells = 112; /* round 4: tier S has no cell limit any more; it takes a task whose graph is expected to stay below this many NODES (its capacity: CW_POA_NC) */
+    if (const char* env = CW_AID_ENV("CW_S_ROUTE_NODES")) { const int v = atoi(env); if (v >= 8 && v <= CW_POA_NC) sc.s_route_cells = (uint32_t)v; }
+    sc.m1_route_depth = 1u;
+    if (const char* env = CW_AID_ENV("CW_M1_ROUTE_DEPTH")) sc.m1_route_depth = (uint32_t)atoi(env);
+    sc.use_h = 0u; sc.h_min_len = CW_POAH_MIN_LEN;
+    if (const char* env = CW_AID_ENV("CW_TIER_H")) { const int v = atoi(env); if (v >= 0 && v <= 2 && CW_Q_CODES) sc.use_h = (uint32_t)v; }
+    if (const char* env = CW_AID_ENV("CW_H_MIN_LEN")) { const int v = atoi(env); if (v >= 1 && v <= CW_POAH_LC) sc.h_min_len = (uint32_t)v; }
+    const uint32_t lds_cu = e->prop.sharedMemPerMultiprocessor ? (uint32_t)e->prop.sharedMemPerMultiprocessor : 160u * 1024u;
+    auto wgs_lds_fit = [&](size_t lds) { return lds_cu / (((uint32_t)lds + 1023u) / 1024u * 1024u); }; /* work-groups whose LDS a CU holds (allocation granule: at most 1 KB) */
+    ls.h_waves = 3; /* waves per tier-H work-group (two tasks per wave) */
+    if (sc.use_h) {
+        const uint32_t fit = wgs_lds_fit(lds_tier_h(ls.h_waves));
+        uint32_t per_cu = fit < CW_POAH_WAVES / ls.h_waves ? (fit ? fit : 1u) : CW_POAH_WAVES / ls.h_waves;
+        if (const char* env = CW_AID_ENV("CW_WGS_H")) { const int v = atoi(env); if (v >= 1 && (uint32_t)v <= per_cu) per_cu = (uint32_t)v; }
+        sc.persist_wgs[5] = cus * per_cu;
+    }
+    const uint32_t* wgs = sc.persist_wgs;
+    sc.producer_wgs = wgs[0] + wgs[1] + wgs[2] + wgs[5];
+    if (CW_AID_ENV("CW_DEBUG_DONE")) fprintf(stderr, "[debug] producer_wgs %u = S %u + M1 %u + M2 %u, L %u, linger %u\n", sc.producer_wgs, wgs[0], wgs[1], wgs[2], wgs[3], sc.linger_wgs);
+    sc.use_q = (CW_AID_ENV("CW_NO_TIER_Q") || CW_POA_AFFINE) ? 0u : 1u; /* (the affine gap model runs in the global-memory tier only: cw_poa_a.h) */
+    /* Launch shapes chosen for two batches in flight on one GPU (two engines, or the driver's two workers): while the other batch's
+       persistent tier kernels hold the LDS of every CU, a work-group that needs most of a CU waits for tens of milliseconds in the
+       middle of this batch's chain (rocprofv3 timeline, depth 150: tier sort 0.45 -> 13-34 ms, tier Q 8.7 -> 55-94 ms with tier S
+       queued behind it, the two overflow passes 0.05 -> 12-32 ms).  So: the sort keeps 16 KB of classes in LDS instead of 128 (the
+       rest are recomputed), tier Q runs as two-wave work-groups (38 KB; the same 8 waves per CU when it has the machine to itself),
+       and the overflow passes -- normally a handful of tasks -- are 64 / 16 work-groups instead of two per CU.  Alone on the GPU the
+       step time is unchanged. */
+    ls.sort_lds = knob_u("CW_SORT_LDS", 16384, 0, kLdsSortMax);
+    ls.sort_thr = knob_u("CW_SORT_THREADS", 256, 128, 1024) / 64 * 64;
+    ls.q_waves = knob_u("CW_Q_WAVES", CW_POAQ_WAVES % 3 == 0 ? 3 : CW_POAQ_WAVES % 2 == 0 ? 2 : 1, 1, CW_POAQ_WAVES); /* waves per tier-Q work-group (four tasks per wave; round 5: three-wave work-groups of 40 KB, four per CU) */
+    const uint32_t q_fit = wgs_lds_fit(lds_tier_q(ls.q_waves));
+    const uint32_t q_most = q_fit < CW_POAQ_WAVES / ls.q_waves ? (q_fit ? q_fit : 1u) : CW_POAQ_WAVES / ls.q_waves;
+    ls.q_grid = cus * knob_u("CW_Q_WGS_PER_CU", q_most, 1, q_most);
+    const uint32_t pass1_most = 64u < cus * 2u ? 64u : cus * 2u;
+    ls.pass1_wgs = knob_u("CW_PASS1_WGS", pass1_most, 1, pass1_most);
+    const uint32_t big_cap = p.tier[4].slots / CW_POA_WAVES;
+    ls.big_wgs = knob_u("CW_BIG_WGS", big_cap < 16 ? big_cap : 16, 1, big_cap);
+    ls.arena_div = 1; /* test aid: every window's arena slice divided, so that an ordinary window stops on it at x1 (CW_WHY_ARENA) */
+    if (const char* env = CW_AID_ENV("CW_ARENA_DIV")) { const int v = atoi(env); if (v >= 2 && v <= 4096) ls.arena_div = (uint32_t)v; }
+    ls.no_tier_x = CW_AID_ENV("CW_NO_TIER_X") ? 1 : 0;
+    return ls;
+}
+
+/* The order of a step: setup, index, chain, sort, fork; tiers L / M2 / M1 on the side streams and Q (H) S on the engine's own, all concurrently; join;
+   the overflow pass (L, G, X), finish, the feedback copy.  The stage names and their order are what bench.py and cw_poll match on.  A tier's grid is
+   its persist_wgs (launch_shape). */
+int enqueue(cw_engine* e, hipStream_t st, const cw_batch* batch, const DevBatch& db, const DevScratch& sc, const ScratchPlan& p, const LaunchShape& ls, const FinOut& fo) {
+    const uint32_t cus = (uint32_t)e->cus, W = batch->n_windows, *wgs = sc.persist_wgs;
+    if (sc.task_dbg) CW_HIP(hipMemsetAsync(sc.task_dbg, 0, (size_t)p.task_cap * 16, st));
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    CW_HIP(hipMemsetAsync(sc.ctr, 0, sizeof(BatchCounters), st));
+    CW_HIP(hipMemsetAsync(sc.slot_busy[0], 0, p.sbusy[CW_TIERS - 1] + (size_t)p.tier[CW_TIERS - 1].slots * 4 - p.sbusy[0], st)); /* every slab free */
+    CW_HIP(hipMemsetAsync(sc.over_list[3], 0xFF, (size_t)p.task_cap * 4, st)); /* live queue: an entry is its own flag */
+    stage(e, st, "setup", [&] {
+        cw_setup_need_kernel<<<(W + 3) / 4, 256, 0, st>>>(db, sc, e->prm);
+        cw_setup_kernel<<<1, 1024, 0, st>>>(db, sc, e->prm, p.solid_cap, p.seg_cap, p.arena_cap, p.arena_scale, e->tmax_plan, ls.arena_div);
+    });
+    stage(e, st, "index", [&] { cw_index_kernel<<<W < cus ? W : cus, CW_IDX_THREADS, kLdsIndex, st>>>(db, sc, e->prm); });
+    stage(e, st, "chain", [&] {
+        const uint32_t want = (W + CW_CH_WAVES - 1) / CW_CH_WAVES;
+        const uint32_t cap = cus * 2u; /* 2 work-groups x 4 waves x 20 KiB per CU */
+        if (e->tmax_plan > 1024u) /* an engine configured for long templates (cw_configure): 32 KiB per wave, up to CW_TMAX anchors, one work-group per CU */
+            cw_chain_kernel<CW_CH_SLAB_LONG><<<want < cus ? want : cus, 64 * CW_CH_WAVES, lds_chain(CW_CH_SLAB_LONG), st>>>(db, sc, e->prm);
+        else
+            cw_chain_kernel<CW_CH_SLAB><<<want < cap ? want : cap, 64 * CW_CH_WAVES, lds_chain(CW_CH_SLAB), st>>>(db, sc, e->prm);
+    });
+    cw_sort_tier_kernel<<<5, ls.sort_thr, ls.sort_lds, st>>>(sc, ls.sort_lds); /* tiers M1, M2 and L: largest tasks first; tiers Q and H: like with like */
+    /* pass 0: every tier works through its own routed list, all four concurrently; the long-running large tiers are
+       dispatched first so that their tail overlaps the bulk of the small tasks */
+    CW_HIP(hipEventRecord(e->ev_fork, st));
+    for (int i = 0; i < 3; ++i) CW_HIP(hipStreamWaitEvent(e->side[i], e->ev_fork, 0));
+    /* tier L also consumes the live overflow queue; only sc.linger_wgs of its work-groups stay for that (far fewer than
+       CUs, so they can never keep the producers they wait for off the machine) */
+    stage(e, e->side[2], "poa_large", [&] { TierL::launch<0>(wgs[3], e->side[2], db, sc); });
+    stage(e, e->side[1], "poa_m2", [&] { TierM2::launch<0>(wgs[2], e->side[1], db, sc); });
+    stage(e, e->side[0], "poa_m1", [&] { TierM1::launch<0>(wgs[1], e->side[0], db, sc); });
+    /* Tiers Q and S go on the ENGINE's stream, also when the caller brought its own: the runtime multiplexes streams onto a few hardware
+       queues, and a caller's stream that shares a queue with tier L's stream would make tier S wait for tier L's kernel to end --
+       whose last work-groups wait for tier S to sign off (measured in the native driver: 131 ms per job until the bounded wait ran out).
+       The engine's four streams were created together and first. */
+    hipStream_t ms = e->stream;
+    if (ms != st) CW_HIP(hipStreamWaitEvent(ms, e->ev_fork, 0));
+    stage(e, ms, "poa_q", [&] { cw_poa_q_kernel<<<ls.q_grid, 64 * ls.q_waves, lds_tier_q(ls.q_waves), ms>>>(db, sc); }); /* four tasks per wave */
+#if CW_Q_CODES && defined(CW_TEST_AIDS)
+    if (wgs[5]) /* two tasks per wave; hands what outgrows it to tier L's live queue, as tier S does */
+        stage(e, ms, "poa_h", [&] { cw_poa_h_kernel<<<wgs[5], 64 * ls.h_waves, lds_tier_h(ls.h_waves), ms>>>(db, sc); });
+#endif
+    stage(e, ms, "poa", [&] { cw_poa_kernel<<<wgs[0], 64 * CW_POA_WAVES, kLdsTierS, ms>>>(db, sc); }); /* 11.3 KiB per wave: three work-groups per CU */
+    if (ms != st) { CW_HIP(hipEventRecord(e->ev_join_s, ms)); CW_HIP(hipStreamWaitEvent(st, e->ev_join_s, 0)); }
+    for (int i = 0; i < 3; ++i) { CW_HIP(hipEventRecord(e->ev_join[i], e->side[i])); CW_HIP(hipStreamWaitEvent(st, e->ev_join[i], 0)); }
+    /* pass 1: tasks that outgrew their tier (normally a handful) go straight to tier L, and from there to G */
+    stage(e, st, "poa_overflow", [&] {
+        TierL::launch<1>(ls.pass1_wgs, st, db, sc);
+        cw_poa_big_kernel<<<ls.big_wgs, 64 * CW_POA_WAVES, 0, st>>>(db, sc);
+        cw_poa_x_kernel<<<1, 64, 0, st>>>(db, sc, ls.no_tier_x); /* what outgrew tier G, in its slab pool (ends at once when tier G handed nothing on) */
+    });
+    stage(e, st, "finish", [&] {
+        uint32_t grid = (W + CW_FIN_WAVES - 1) / CW_FIN_WAVES;
+        if (grid > cus * CW_FIN_WGS_PER_CU) grid = cus * CW_FIN_WGS_PER_CU;
+        cw_finish_kernel<CW_FIN_CB, CW_FIN_WAVES, false><<<grid, 64 * CW_FIN_WAVES, kLdsFinish, st>>>(db, sc, e->prm, fo);
+        /* second pass: the windows whose strings outgrew the first pass's buffers (normally none: the kernel reads one counter and ends) */
+        cw_finish_kernel<CW_FIN_CB_BIG, 1, true><<<W < 64u ? W : 64u, 64, kLdsFinishBig, st>>>(db, sc, e->prm, fo);
+    });
+    /* feedback for the next batch's linger_wgs (pinned destination: asynchronous) */
+    CW_HIP(hipMemcpyAsync(&e->host_fb->handed_over, &sc.ctr->n_over[3], 4, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
+}
+
+/* the body of cw_run_device; the caller holds e->mu */
+/* pf_full: the index kernel's global matrix slot at its full kPfRowsMax rows (a re-run after CW_WHY_MATRIX, grow_if_that_helps) */
+int run_device_locked(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream, bool pf_full = false) {
+    int rc = validate_run(e, batch, res);
+    if (rc || batch->n_windows == 0) return rc;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    ScratchPlan p; DevScratch sc;
+    if ((rc = plan_and_bind(e, batch, pf_full, &p, &sc)) != CW_OK) return rc;
+    const LaunchShape ls = launch_shape(e, batch, p, sc);
+    DevBatch db;
+    db.n_windows = batch->n_windows; db.win_first_seq = batch->win_first_seq; db.seq_len = batch->seq_len; db.seq_word_off = batch->seq_word_off; db.bases = batch->bases;
+    FinOut fo;
+    fo.cons = res->cons; fo.cons_off = res->cons_off; fo.cons_len = res->cons_len; fo.win_status = res->win_status;
+    fo.solid = res->solid; fo.solid_off = res->solid_off; fo.solid_len = res->solid_len;
+    return enqueue(e, st, batch, db, sc, p, ls, fo);
+}
 
 } // namespace
 
@@ -289,10 +403,11 @@ int cw_create(const cw_params* params, int device, cw_engine** out) {
         delete e;
         return CW_E_NO_DEVICE;
     }
+    e->cus = e->prop.multiProcessorCount > 0 ? e->prop.multiProcessorCount : 256;
     bool ok = hipEventCreate(&e->ev_fork) == hipSuccess && hipEventCreate(&e->ev_begin) == hipSuccess && hipEventCreate(&e->ev_end) == hipSuccess &&
               hipEventCreateWithFlags(&e->ev_join_s, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&e->host_fb, 64, hipHostMallocDefault) == hipSuccess;
-    if (ok) memset(e->host_fb, 0, 64);
+    ok = ok && hipHostMalloc((void**)&e->host_fb, sizeof(cw_host_fb), hipHostMallocDefault) == hipSuccess;
+    if (ok) memset(e->host_fb, 0, sizeof(cw_host_fb));
     for (int i = 0; i < 3 && ok; ++i) ok = hipStreamCreateWithFlags(&e->side[i], hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming) == hipSuccess;
     ok = ok && hipStreamCreateWithFlags(&e->stagger, hipStreamNonBlocking) == hipSuccess; /* (cw_internal.h: created here, after the side streams, for its place in the order) */
     for (int i = 0; i < CW_MAX_STAGES && ok; ++i) ok = hipEventCreate(&e->ev0[i]) == hipSuccess && hipEventCreate(&e->ev1[i]) == hipSuccess;
@@ -334,282 +449,6 @@ void cw_destroy(cw_engine* e) {
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
-
-} // extern "C"
-
-namespace {
-
-/* the body of cw_run_device; the caller holds e->mu */
-/* pf_full: the index kernel's global matrix slot at its full kPfRowsMax rows (a re-run after CW_WHY_MATRIX, grow_if_that_helps) */
-int run_device_locked(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream, bool pf_full = false) {
-    if (!e || !batch || !res || !res->cons || !res->cons_off || !res->cons_len || !res->win_status) return CW_E_INVALID;
-    if ((res->solid != nullptr) != (res->solid_off != nullptr) || (res->solid != nullptr) != (res->solid_len != nullptr)) return CW_E_INVALID;
-    if (batch->n_windows == 0) return CW_OK;
-    if (!batch->win_first_seq || !batch->seq_len || !batch->seq_word_off || !batch->bases) return CW_E_INVALID;
-    /* per-window offsets into the arena, the solid table and the segment table are 32-bit (WinInfo, PoaTask): a batch is
-       limited so that none of them can wrap -- split larger inputs (the library's own drivers do; cw_max_batch_windows) */
-    if (batch->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
-    CW_HIP(hipSetDevice(e->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
-
-    uint32_t big_slots = 64; /* tier G's kernel is sixteen work-groups of four waves at most (big_wgs below): 64 slabs of 16.8 MB are all it can use (256 through round 5: 4.3 GB) */
-    if (const char* env = CW_AID_ENV("CW_BIG_SLOTS")) { int v = atoi(env); if (v >= 4 && v <= 4096) big_slots = (uint32_t)v / 4 * 4; }
-    const int cus = e->prop.multiProcessorCount > 0 ? e->prop.multiProcessorCount : 256;
-    const ScratchPlan p = plan_scratch(e->prm, batch->n_windows, batch->n_seqs, batch->n_words, cus, big_slots, e->cap_scale, e->tmax_plan, pf_full);
-    if (p.solid_cap > 0xFFFFFFFFull || p.seg_cap > 0xFFFFFFFFull || p.arena_cap > 0xFFFFFFFFull) return CW_E_INVALID; /* see CW_MAX_BATCH_WINDOWS */
-    e->last_windows = batch->n_windows; e->last_seqs = batch->n_seqs; e->last_words = batch->n_words; e->last_big_slots = big_slots;
-    e->last_ctr_off = p.ctr;
-    int rc = ensure(&e->scratch, &e->scratch_bytes, p.total);
-    if (rc) return rc;
-    if (!e->step_clock) { CW_HIP(hipMalloc((void**)&e->step_clock, 16)); CW_HIP(hipMemset(e->step_clock, 0, 16)); }
-    uint8_t* base = (uint8_t*)e->scratch;
-
-    DevBatch db;
-    db.n_windows = batch->n_windows;
-    db.win_first_seq = batch->win_first_seq; db.seq_len = batch->seq_len; db.seq_word_off = batch->seq_word_off; db.bases = batch->bases;
-    DevScratch sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.win = (WinInfo*)(base + p.win);
-    sc.solid_key = (uint32_t*)(base + p.solid_key); sc.solid_cnt = (uint32_t*)(base + p.solid_cnt);
-    sc.seg_off = (uint32_t*)(base + p.seg_off); sc.seg_len = (uint32_t*)(base + p.seg_len);
-    sc.arena = base + p.arena;
-    sc.tasks = (PoaTask*)(base + p.tasks); sc.task_cap = p.task_cap;
-    sc.members = (PoaMember*)(base + p.members); sc.member_cap = p.member_cap;
-    sc.ctr = (BatchCounters*)(base + p.ctr);
-    sc.list_cap = p.task_cap;
-    /* how many tier-L work-groups stay on the live overflow queue: about half of what the last finished batch handed over (few when
-       nothing overflows, since a lingering work-group holds LDS the other tiers could use).  The count arrives in pinned host memory
-       by an asynchronous copy at the end of each run: nothing here waits for the device */
-    if (e->timings_valid) { /* a run has been enqueued before: its count, or that of the one before it, is there */
-        const uint32_t want = e->host_fb[0] / 2;
-        e->linger_wgs = want < 16 ? 16 : want > 256 ? 256 : want;
-    }
-    sc.p_fallback = (uint16_t*)(base + p.pfall); sc.p_fallback_elems = p.pfall_elems;
-    sc.ablock = base + p.ablock; sc.ablock_units = p.ablock_units;
-    sc.ex_fallback = (unsigned long long*)(base + p.exg);
-    sc.step_clock = e->step_clock;
-    sc.task_dbg = getenv("CW_TASK_TRACE") ? (uint4*)(base + p.tdbg) : nullptr;
-    e->last_tasks_off = p.tasks; e->last_tdbg_off = p.tdbg; e->last_task_cap = p.task_cap;
-    if (sc.task_dbg) CW_HIP(hipMemsetAsync(sc.task_dbg, 0, (size_t)p.task_cap * 16, st));
-    sc.fin_vis = (uint32_t*)(base + p.finvis); sc.fin_vis_words = CW_FIN_VIS_GLB_WORDS;
-    sc.fin_retry = (uint32_t*)(base + p.finretry);
-    sc.fin_big = base + p.finbig;
-    sc.linger_wgs = e->linger_wgs ? e->linger_wgs : 64;
-    if (const char* env = CW_AID_ENV("CW_LINGER_WGS")) { int v = atoi(env); if (v >= 0 && v <= 1024) sc.linger_wgs = (uint32_t)v; }
-    /* grids of the four concurrent tier kernels: `yield` work-groups that run one chunk of tasks and end, then `persist` ones that loop
-       until the list is empty (see cw_poa_slab_kernel).  The yielding part is sized for the lists of a full batch and shrinks with the
-       batch, so that a small batch does not pay for thousands of empty work-groups. */
-    const TierMix mix = tier_mix(batch->n_seqs / batch->n_windows > 64u);
-    const uint32_t W_ = batch->n_windows;
-    auto ymin = [](uint32_t a, uint32_t b_) { return a < b_ ? a : b_; };
-    uint32_t yield_wgs[4] = {ymin(8192u, W_ / 2u + 1u), ymin(16384u, W_), ymin(4096u, W_ / 4u + 1u), ymin(4096u, W_ / 4u + 1u)};
-    /* measured: with every tier on the machine all the time the stage is SLOWER (depth 150: 86-92 ms against 69-82; depth 30:
-       25.3 against 19.6) -- the CUs are short of issue slots, not of resident waves -- so yielding is off unless CW_YIELD is set */
-    if (!CW_AID_ENV("CW_YIELD")) yield_wgs[0] = yield_wgs[1] = yield_wgs[2] = yield_wgs[3] = 0;
-    sc.persist_wgs[0] = tier_wgs_cap(0, W_, (uint32_t)cus * mix.s); sc.persist_wgs[1] = tier_wgs_cap(1, W_, (uint32_t)cus * mix.m1);
-    sc.persist_wgs[2] = tier_wgs_cap(2, W_, (uint32_t)cus * mix.m2); sc.persist_wgs[3] = tier_wgs_cap(3, W_, (uint32_t)cus * mix.l);
-    sc.persist_wgs[4] = 0;
-    const uint32_t wgs_s = yield_wgs[0] + sc.persist_wgs[0], wgs_m1 = yield_wgs[1] + sc.persist_wgs[1], wgs_m2 = yield_wgs[2] + sc.persist_wgs[2],
-                   wgs_l = yield_wgs[3] + sc.persist_wgs[3];
-    /* Tier H (two tasks per wave on 32-lane halves, cw_poa_q.h; round 5: tier Q's code instantiated for members of up to 63 bases and graphs of up
-       to 128 nodes -- byte-sized graph arrays, recorded decisions, code words in the task's slab; it replaces round 3's opt-in kernel).  Bit-identical
-       (tests/test_gpu_tier_q.py, test_gpu_parity.py) and OFF: measured on one box at depth 150 it takes tier S's 41.7 k tasks in 27.4 ms where tier
-       S needs 28.4 -- 64 G wave-cycles against 69 -- and with its 18 waves per CU the other tiers slow down (M2 30.8 -> 36.7, L 41 -> 44 ms): step
-       61-63 ms against 55-58; depth 30: 23.6 against 22.7.  Four tasks per wave (tier Q) beat tier S's scalar-controlled row loop six to one in
-       machine time; two per wave do not: a per-lane row loop is ~100 instructions, tier S's 45.  CW_TIER_H=1|2 (test-aid build) turns it on. */
-    /* Routing margins against late hand-overs.  A task that outgrows tier S or M1 is redone in tier L, whose work-groups only turn to the
-       hand-over queue once their own list is empty: measured on a depth-150 batch (tools/task_trace.py), the ~150 tasks of 24-45 members
-       x 27-31 bases that the depth-aware estimate put just inside tier S's 2048 cells, and the ~45 tasks of 52-64 members x 90-120 bases
-       that outgrew tier M1's 256 nodes, kept a handful of tier-L waves busy for 10-20 ms after every other tier had finished.  With tier S
-       taking only what is expected to stay below 1700 cells and tier M1 chosen by the depth-aware estimate as well, one task per batch is
-       handed over instead of ~195, and the step (two engines) goes from 73.1 to 68.8 ms on the same box.  CW_S_ROUTE_CELLS /
-       CW_M1_ROUTE_DEPTH=0 give the old routing (experiments; results do not depend on the tier). */
-    sc.s_route_cells = 112; /* round 4: tier S has no cell limit any more; it takes a task whose graph is expected to stay below this many NODES (its capacity: CW_POA_NC) */
-    if (const char* env = CW_AID_ENV("CW_S_ROUTE_NODES")) { const int v = atoi(env); if (v >= 8 && v <= CW_POA_NC) sc.s_route_cells = (uint32_t)v; }
-    sc.m1_route_depth = 1u;
-    if (const char* env = CW_AID_ENV("CW_M1_ROUTE_DEPTH")) sc.m1_route_depth = (uint32_t)atoi(env);
-    sc.use_h = 0u; sc.h_min_len = CW_POAH_MIN_LEN;
-    if (const char* env = CW_AID_ENV("CW_TIER_H")) { const int v = atoi(env); if (v >= 0 && v <= 2 && CW_Q_CODES) sc.use_h = (uint32_t)v; }
-    if (const char* env = CW_AID_ENV("CW_H_MIN_LEN")) { const int v = atoi(env); if (v >= 1 && v <= CW_POAH_LC) sc.h_min_len = (uint32_t)v; }
-    uint32_t wgs_h = 0;
-    const uint32_t h_waves = 3; /* waves per tier-H work-group (two tasks per wave) */
-    if (sc.use_h) {
-        const uint32_t lds_cu = e->prop.sharedMemPerMultiprocessor ? (uint32_t)e->prop.sharedMemPerMultiprocessor : 160u * 1024u;
-        const uint32_t fit = lds_cu / (((uint32_t)(CW_POAH_TASK_BYTES * 2 * h_waves) + 1023u) / 1024u * 1024u);
-        uint32_t per_cu = fit < CW_POAH_WAVES / h_waves ? (fit ? fit : 1u) : CW_POAH_WAVES / h_waves;
-        if (const char* env = CW_AID_ENV("CW_WGS_H")) { const int v = atoi(env); if (v >= 1 && (uint32_t)v <= per_cu) per_cu = (uint32_t)v; }
-        wgs_h = (uint32_t)cus * per_cu;
-    }
-    sc.persist_wgs[5] = wgs_h;
-    sc.producer_wgs = wgs_s + wgs_m1 + wgs_m2 + wgs_h;
-    if (CW_AID_ENV("CW_DEBUG_DONE")) fprintf(stderr, "[debug] producer_wgs %u = S %u + M1 %u + M2 %u, L %u, linger %u\n", sc.producer_wgs, wgs_s, wgs_m1, wgs_m2, wgs_l, sc.linger_wgs);
-    sc.tier_list[0] = (uint32_t*)(base + p.list[0]); sc.over_list[0] = (uint32_t*)(base + p.over[0]);
-    sc.use_q = (CW_AID_ENV("CW_NO_TIER_Q") || CW_POA_AFFINE) ? 0u : 1u; /* (the affine gap model runs in the global-memory tier only: cw_poa_a.h) */
-    sc.q_slab = base + p.qslab;
-    sc.h_slab = base + p.hslab;
-    for (int t = 0; t < CW_TIERS; ++t) {
-        if (t) { sc.tier_list[t] = (uint32_t*)(base + p.list[t]); sc.over_list[t] = (uint32_t*)(base + p.over[t]); }
-        sc.slab[t] = base + p.slab[t]; sc.slab_bytes[t] = p.tier[t].slab_bytes; sc.slots[t] = p.tier[t].slots;
-        sc.slot_busy[t] = (uint32_t*)(base + p.sbusy[t]);
-    }
-    FinOut fo;
-    fo.cons = res->cons; fo.cons_off = res->cons_off; fo.cons_len = res->cons_len; fo.win_status = res->win_status;
-    fo.solid = res->solid; fo.solid_off = res->solid_off; fo.solid_len = res->solid_len;
-
-    e->n_stages = 0;
-    e->timings_valid = false;
-#define M1_ARGS CW_POAM1_NC, CW_POAM1_EC, CW_POAM1_LC, CW_POAM1_WAVES, 1
-#define M2_ARGS CW_POAM2_NC, CW_POAM2_EC, CW_POAM2_LC, CW_POAM2_WAVES, 2
-#define L_ARGS CW_POAL_NC, CW_POAL_EC, CW_POAL_LC, CW_POAL_WAVES, 3
-    const size_t lds_m1 = CW_POA_HOT2C_BYTES(CW_POAM1_NC, CW_POAM1_EC, CW_POAM1_LC) * CW_POAM1_WAVES;
-    const size_t lds_m2 = CW_POA_HOT2T_BYTES(2, CW_POAM2_NC, CW_POAM2_EC, CW_POAM2_LC) * CW_POAM2_WAVES;
-    const size_t lds_l = CW_POAL_LDS_BYTES;
-    const uint32_t thr_l = 64 * CW_POAL_WAVES;
-    int sid;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
-    CW_HIP(hipMemsetAsync(sc.ctr, 0, sizeof(BatchCounters), st));
-    CW_HIP(hipMemsetAsync(base + p.sbusy[0], 0, p.sbusy[CW_TIERS - 1] + (size_t)p.tier[CW_TIERS - 1].slots * 4 - p.sbusy[0], st)); /* every slab free */
-    CW_HIP(hipMemsetAsync(sc.over_list[3], 0xFF, (size_t)p.task_cap * 4, st)); /* live queue: an entry is its own flag */
-    sid = stage_begin(e, st, "setup");
-    cw_setup_need_kernel<<<(batch->n_windows + 3) / 4, 256, 0, st>>>(db, sc, e->prm);
-    uint32_t arena_div = 1; /* test aid: every window's arena slice divided, so that an ordinary window stops on it at x1 (CW_WHY_ARENA) */
-    if (const char* env = CW_AID_ENV("CW_ARENA_DIV")) { const int v = atoi(env); if (v >= 2 && v <= 4096) arena_div = (uint32_t)v; }
-    cw_setup_kernel<<<1, 1024, 0, st>>>(db, sc, e->prm, p.solid_cap, p.seg_cap, p.arena_cap, p.arena_scale, e->tmax_plan, arena_div);
-    stage_end(e, st, sid);
-    sid = stage_begin(e, st, "index");
-    {
-        const uint32_t grid = batch->n_windows < (uint32_t)cus ? batch->n_windows : (uint32_t)cus;
-        cw_index_kernel<<<grid, CW_IDX_THREADS, CW_IDX_LDS_BYTES, st>>>(db, sc, e->prm);
-    }
-    stage_end(e, st, sid);
-    sid = stage_begin(e, st, "chain");
-    {
-        const uint32_t want = (batch->n_windows + CW_CH_WAVES - 1) / CW_CH_WAVES;
-        const uint32_t cap = (uint32_t)cus * 2u; /* 2 work-groups x 4 waves x 20 KiB per CU */
-        if (e->tmax_plan > 1024u) /* an engine configured for long templates (cw_configure): 32 KiB per wave, up to CW_TMAX anchors, one work-group per CU */
-            cw_chain_kernel<CW_CH_SLAB_LONG><<<want < (uint32_t)cus ? want : (uint32_t)cus, 64 * CW_CH_WAVES, CW_CH_WAVES * CW_CH_SLAB_LONG, st>>>(db, sc, e->prm);
-        else
-            cw_chain_kernel<CW_CH_SLAB><<<want < cap ? want : cap, 64 * CW_CH_WAVES, CW_CH_WAVES * CW_CH_SLAB, st>>>(db, sc, e->prm);
-    }
-    stage_end(e, st, sid);
-    auto knob_u = [](const char* name, uint32_t dflt, uint32_t lo, uint32_t hi) { const char* v = CW_AID_ENV(name); if (!v) return dflt; const long x = atol(v); return x >= (long)lo && x <= (long)hi ? (uint32_t)x : dflt; };
-    /* Launch shapes chosen for two batches in flight on one GPU (two engines, or the driver's two workers): while the other batch's
-       persistent tier kernels hold the LDS of every CU, a work-group that needs most of a CU waits for tens of milliseconds in the
-       middle of this batch's chain (rocprofv3 timeline, depth 150: tier sort 0.45 -> 13-34 ms, tier Q 8.7 -> 55-94 ms with tier S
-       queued behind it, the two overflow passes 0.05 -> 12-32 ms).  So: the sort keeps 16 KB of classes in LDS instead of 128 (the
-       rest are recomputed), tier Q runs as two-wave work-groups (38 KB; the same 8 waves per CU when it has the machine to itself),
-       and the overflow passes -- normally a handful of tasks -- are 64 / 16 work-groups instead of two per CU.  Alone on the GPU the
-       step time is unchanged. */
-    const uint32_t sort_lds = knob_u("CW_SORT_LDS", 16384, 0, CW_SORT_LDS_CLS);
-    const uint32_t sort_thr = knob_u("CW_SORT_THREADS", 256, 128, 1024) / 64 * 64;
-    const uint32_t q_waves = knob_u("CW_Q_WAVES", CW_POAQ_WAVES % 3 == 0 ? 3 : CW_POAQ_WAVES % 2 == 0 ? 2 : 1, 1, CW_POAQ_WAVES); /* waves per tier-Q work-group (four tasks per wave; round 5: three-wave work-groups of 40 KB, four per CU) */
-    const uint32_t q_lds_cu = e->prop.sharedMemPerMultiprocessor ? (uint32_t)e->prop.sharedMemPerMultiprocessor : 160u * 1024u;
-    const uint32_t q_fit = q_lds_cu / (((uint32_t)(CW_POAQ_TASK_BYTES * 4 * q_waves) + 1023u) / 1024u * 1024u);   /* work-groups whose LDS a CU holds (allocation granule: at most 1 KB) */
-    const uint32_t q_most = q_fit < CW_POAQ_WAVES / q_waves ? (q_fit ? q_fit : 1u) : CW_POAQ_WAVES / q_waves;
-    const uint32_t q_per_cu = knob_u("CW_Q_WGS_PER_CU", q_most, 1, q_most);
-    const uint32_t q_grid = (uint32_t)cus * q_per_cu;
-    const uint32_t pass1_wgs = knob_u("CW_PASS1_WGS", 64u < (uint32_t)cus * 2u ? 64u : (uint32_t)cus * 2u, 1, 64u < (uint32_t)cus * 2u ? 64u : (uint32_t)cus * 2u);
-    const uint32_t big_cap = p.tier[4].slots / CW_POA_WAVES;
-    const uint32_t big_wgs = knob_u("CW_BIG_WGS", big_cap < 16 ? big_cap : 16, 1, big_cap);
-    cw_sort_tier_kernel<<<5, sort_thr, sort_lds, st>>>(sc, sort_lds); /* tiers M1, M2 and L: largest tasks first; tiers Q and H: like with like */
-    /* pass 0: every tier works through its own routed list, all four concurrently; the long-running large tiers are
-       dispatched first so that their tail overlaps the bulk of the small tasks */
-    const char* ph_env = CW_AID_ENV("CW_PHASES");
-    const int phases = ph_env ? atoi(ph_env) : 0;
-    const uint32_t grid_l = wgs_l;
-    if (phases == 2) {
-        /* experiment: tier Q, then S + M1 + M2 side by side, then tier L alone with every hand-over already on its list */
-        sid = stage_begin(e, st, "poa_q");
-        cw_poa_q_kernel<<<q_grid, 64 * q_waves, CW_POAQ_TASK_BYTES * 4 * q_waves, st>>>(db, sc);
-        stage_end(e, st, sid);
-#if CW_Q_CODES && defined(CW_TEST_AIDS)
-        if (wgs_h) {
-            sid = stage_begin(e, st, "poa_h");
-            cw_poa_h_kernel<<<wgs_h, 64 * h_waves, CW_POAH_TASK_BYTES * 2 * h_waves, st>>>(db, sc);
-            stage_end(e, st, sid);
-        }
-#endif
-        CW_HIP(hipEventRecord(e->ev_fork, st));
-        for (int i = 0; i < 2; ++i) CW_HIP(hipStreamWaitEvent(e->side[i], e->ev_fork, 0));
-        sid = stage_begin(e, e->side[1], "poa_m2");
-        cw_poa_slab_kernel<M2_ARGS, 0><<<wgs_m2, 64 * CW_POAM2_WAVES, lds_m2, e->side[1]>>>(db, sc);
-        stage_end(e, e->side[1], sid);
-        sid = stage_begin(e, e->side[0], "poa_m1");
-        cw_poa_slab_kernel<M1_ARGS, 0><<<wgs_m1, 64 * CW_POAM1_WAVES, lds_m1, e->side[0]>>>(db, sc);
-        stage_end(e, e->side[0], sid);
-        sid = stage_begin(e, st, "poa");
-        cw_poa_kernel<<<wgs_s, 64 * CW_POA_WAVES, CW_POA_SLAB_BYTES * CW_POA_WAVES, st>>>(db, sc);
-        stage_end(e, st, sid);
-        for (int i = 0; i < 2; ++i) { CW_HIP(hipEventRecord(e->ev_join[i], e->side[i])); CW_HIP(hipStreamWaitEvent(st, e->ev_join[i], 0)); }
-        sid = stage_begin(e, st, "poa_large");
-        cw_poa_slab_kernel<L_ARGS, 0><<<grid_l, thr_l, lds_l, st>>>(db, sc);
-        stage_end(e, st, sid);
-    } else {
-    CW_HIP(hipEventRecord(e->ev_fork, st));
-    for (int i = 0; i < 3; ++i) CW_HIP(hipStreamWaitEvent(e->side[i], e->ev_fork, 0));
-    /* tier L also consumes the live overflow queue; only sc.linger_wgs of its work-groups stay for that (far fewer than
-       CUs, so they can never keep the producers they wait for off the machine) */
-    sid = stage_begin(e, e->side[2], "poa_large");
-    cw_poa_slab_kernel<L_ARGS, 0><<<grid_l, thr_l, lds_l, e->side[2]>>>(db, sc);
-    stage_end(e, e->side[2], sid);
-    sid = stage_begin(e, e->side[1], "poa_m2");
-    cw_poa_slab_kernel<M2_ARGS, 0><<<wgs_m2, 64 * CW_POAM2_WAVES, lds_m2, e->side[1]>>>(db, sc);
-    stage_end(e, e->side[1], sid);
-    sid = stage_begin(e, e->side[0], "poa_m1");
-    cw_poa_slab_kernel<M1_ARGS, 0><<<wgs_m1, 64 * CW_POAM1_WAVES, lds_m1, e->side[0]>>>(db, sc);
-    stage_end(e, e->side[0], sid);
-    /* Tiers Q and S go on the ENGINE's stream, also when the caller brought its own: the runtime multiplexes streams onto a few hardware
-       queues, and a caller's stream that shares a queue with tier L's stream would make tier S wait for tier L's kernel to end --
-       whose last work-groups wait for tier S to sign off (measured in the native driver: 131 ms per job until the bounded wait ran out).
-       The engine's four streams were created together and first. */
-    hipStream_t ms = e->stream;
-    if (ms != st) CW_HIP(hipStreamWaitEvent(ms, e->ev_fork, 0));
-    sid = stage_begin(e, ms, "poa_q");
-    cw_poa_q_kernel<<<q_grid, 64 * q_waves, CW_POAQ_TASK_BYTES * 4 * q_waves, ms>>>(db, sc); /* four tasks per wave */
-    stage_end(e, ms, sid);
-#if CW_Q_CODES && defined(CW_TEST_AIDS)
-    if (wgs_h) { /* two tasks per wave; hands what outgrows it to tier L's live queue, as tier S does */
-        sid = stage_begin(e, ms, "poa_h");
-        cw_poa_h_kernel<<<wgs_h, 64 * h_waves, CW_POAH_TASK_BYTES * 2 * h_waves, ms>>>(db, sc);
-        stage_end(e, ms, sid);
-    }
-#endif
-    sid = stage_begin(e, ms, "poa");
-    cw_poa_kernel<<<wgs_s, 64 * CW_POA_WAVES, CW_POA_SLAB_BYTES * CW_POA_WAVES, ms>>>(db, sc); /* 11.3 KiB per wave: three work-groups per CU */
-    stage_end(e, ms, sid);
-    if (ms != st) { CW_HIP(hipEventRecord(e->ev_join_s, ms)); CW_HIP(hipStreamWaitEvent(st, e->ev_join_s, 0)); }
-    for (int i = 0; i < 3; ++i) { CW_HIP(hipEventRecord(e->ev_join[i], e->side[i])); CW_HIP(hipStreamWaitEvent(st, e->ev_join[i], 0)); }
-    }
-    /* pass 1: tasks that outgrew their tier (normally a handful) go straight to tier L, and from there to G */
-    sid = stage_begin(e, st, "poa_overflow");
-    cw_poa_slab_kernel<L_ARGS, 1><<<pass1_wgs, thr_l, lds_l, st>>>(db, sc);
-    cw_poa_big_kernel<<<big_wgs, 64 * CW_POA_WAVES, 0, st>>>(db, sc);
-    cw_poa_x_kernel<<<1, 64, 0, st>>>(db, sc, CW_AID_ENV("CW_NO_TIER_X") ? 1 : 0); /* what outgrew tier G, in its slab pool (ends at once when tier G handed nothing on) */
-    stage_end(e, st, sid);
-    sid = stage_begin(e, st, "finish");
-    {
-        uint32_t grid = (batch->n_windows + CW_FIN_WAVES - 1) / CW_FIN_WAVES;
-        if (grid > (uint32_t)cus * CW_FIN_WGS_PER_CU) grid = (uint32_t)cus * CW_FIN_WGS_PER_CU;
-        cw_finish_kernel<CW_FIN_CB, CW_FIN_WAVES, false><<<grid, 64 * CW_FIN_WAVES, CW_FIN_SLAB * CW_FIN_WAVES, st>>>(db, sc, e->prm, fo);
-        /* second pass: the windows whose strings outgrew the first pass's buffers (normally none: the kernel reads one counter and ends) */
-        const uint32_t grid2 = batch->n_windows < 64u ? batch->n_windows : 64u;
-        cw_finish_kernel<CW_FIN_CB_BIG, 1, true><<<grid2, 64, CW_FIN_SLAB_OF(0), st>>>(db, sc, e->prm, fo);
-    }
-    stage_end(e, st, sid);
-    /* feedback for the next batch's linger_wgs (pinned destination: asynchronous) */
-    CW_HIP(hipMemcpyAsync(&e->host_fb[0], &sc.ctr->n_over[3], 4, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipEventRecord(e->ev_end, st));
-#undef M1_ARGS
-#undef M2_ARGS
-#undef L_ARGS
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
-    return CW_OK;
-}
-
-} // namespace
-
-extern "C" {
 
 int cw_run_device(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream) {
     if (!e) return CW_E_INVALID;
@@ -674,7 +513,6 @@ int cw_last_timings(cw_engine* e, float* ms, const char** names, int cap, int* n
     for (int i = 0; i < e->n_stages && k < cap; ++i, ++k) {
         float t = 0.f;
         CW_HIP(hipEventElapsedTime(&t, e->ev0[i], e->ev1[i]));
-        e->stage_ms[i] = t;
         if (ms) ms[k] = t;
         if (names) names[k] = e->stage_name[i];
     }
@@ -693,7 +531,7 @@ int cw_last_timings(cw_engine* e, float* ms, const char** names, int cap, int* n
 int cw_debug_plan(uint32_t k, uint32_t solid, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t scale, uint32_t tmax, uint64_t* out15) {
     if (!out15 || !n_windows || !solid) return CW_E_INVALID;
     cw_params prm{k, solid, 8, 2, 150};
-    const ScratchPlan p = plan_scratch(prm, n_windows, n_seqs, n_words, cus, 64, scale ? scale : 1, tmax ? tmax : 1024);
+    const ScratchPlan p = plan_scratch(PlanInput{prm, n_windows, n_seqs, n_words, cus, 64, scale ? scale : 1, tmax ? tmax : 1024, false});
     auto slab = [&](int t) { return (uint64_t)p.tier[t].slots * p.tier[t].slab_bytes; };
     const uint64_t v[15] = {p.total, (uint64_t)n_windows * sizeof(WinInfo), p.solid_cap * 8, p.seg_cap * 8, p.arena_cap,
                             ((uint64_t)p.task_cap + 1) * sizeof(PoaTask) + (uint64_t)p.member_cap * sizeof(PoaMember), (uint64_t)p.task_cap * 4 * 2 * CW_TIERS,
@@ -708,7 +546,7 @@ int cw_debug_plan_caps(uint32_t k, uint32_t solid, uint32_t n_windows, uint32_t 
     if (!out8 || !n_windows || !solid) return CW_E_INVALID;
     cw_params prm{k, solid, 8, 2, 150};
     const uint32_t t = tmax ? tmax : 1024;
-    const ScratchPlan p = plan_scratch(prm, n_windows, n_seqs, n_words, cus, 64, scale ? scale : 1, t, pf_full != 0);
+    const ScratchPlan p = plan_scratch(PlanInput{prm, n_windows, n_seqs, n_words, cus, 64, scale ? scale : 1, t, pf_full != 0});
     const uint64_t v[8] = {p.total, p.solid_cap, p.seg_cap, p.arena_cap, p.arena_scale, p.pfall_elems / t, max_batch_windows(t), p.task_cap};
     for (int i = 0; i < 8; ++i) out8[i] = v[i];
     return CW_OK;
@@ -730,10 +568,8 @@ int cw_debug_win_info(cw_engine* e, uint32_t n_windows, uint32_t* out16) {
 int cw_debug_profile(cw_engine* e, uint32_t* counters, uint32_t counters_cap, unsigned long long* prof, uint32_t prof_cap, uint32_t* counters_n, uint32_t* prof_n) {
     if (!e || !e->scratch || !counters || !prof) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
-    CW_HIP(hipSetDevice(e->device));
-    CW_HIP(hipDeviceSynchronize());
     BatchCounters c;
-    CW_HIP(hipMemcpy(&c, (uint8_t*)e->scratch + e->last_ctr_off, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters_idle(e, &c)) return rc;
     const uint32_t nc = counters_cap < 6u + 4u * CW_TIERS ? counters_cap : 6u + 4u * CW_TIERS; /* n_tasks .. any_overflow, then n_tier, next_tier, n_over, next_over [CW_TIERS] each */
     const uint32_t np = prof_cap < (uint32_t)CW_PROF_SLOTS ? prof_cap : (uint32_t)CW_PROF_SLOTS;
     memcpy(counters, &c, (size_t)nc * 4);
@@ -747,10 +583,8 @@ int cw_debug_profile(cw_engine* e, uint32_t* counters, uint32_t counters_cap, un
 int cw_debug_tier_x(cw_engine* e, uint32_t* out4) {
     if (!e || !e->scratch || !out4) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
-    CW_HIP(hipSetDevice(e->device));
-    CW_HIP(hipDeviceSynchronize());
     BatchCounters c;
-    CW_HIP(hipMemcpy(&c, (uint8_t*)e->scratch + e->last_ctr_off, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters_idle(e, &c)) return rc;
     out4[0] = c.x_routed; out4[1] = c.x_done; out4[2] = c.x_stopped; out4[3] = c.x_cells;
     return CW_OK;
 }
@@ -760,10 +594,8 @@ int cw_debug_tier_x(cw_engine* e, uint32_t* out4) {
 int cw_debug_task_trace(cw_engine* e, uint32_t cap_tasks, uint32_t* out12, uint32_t* n_tasks) {
     if (!e || !e->scratch || !out12 || !n_tasks || !getenv("CW_TASK_TRACE")) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
-    CW_HIP(hipSetDevice(e->device));
-    CW_HIP(hipDeviceSynchronize());
     BatchCounters c;
-    CW_HIP(hipMemcpy(&c, (uint8_t*)e->scratch + e->last_ctr_off, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters_idle(e, &c)) return rc;
     uint32_t n = c.n_tasks < e->last_task_cap ? c.n_tasks : e->last_task_cap;
     if (n > cap_tasks) n = cap_tasks;
     std::vector<uint32_t> a((size_t)n * 8), d((size_t)n * 4);
@@ -772,58 +604,6 @@ int cw_debug_task_trace(cw_engine* e, uint32_t cap_tasks, uint32_t* out12, uint3
     for (uint32_t i = 0; i < n; ++i) { memcpy(out12 + (size_t)i * 12, &a[(size_t)i * 8], 32); memcpy(out12 + (size_t)i * 12 + 8, &d[(size_t)i * 4], 16); }
     *n_tasks = n;
     return CW_OK;
-}
-
-/* getCoverages + getAlignmentWindowsPositions (src/alignmentWindows.cpp:5-85) on the host: per-base overlap depth over
- * [q_start, q_end] inclusive; a window [beg, beg+window_size-1] whenever window_size consecutive bases have depth >=
- * min_support, then rewind by window_overlap (:40-47); a base below min_support resets (:48-51); finally ONE trailing window
- * = the last window_size covered bases found scanning backwards from the end, never looking at base 0 (:58-79). */
-int cw_window_positions(uint32_t tpl_len, const cw_overlap* overlaps, uint32_t n_overlaps, uint32_t min_support, uint32_t window_size,
-                        int32_t window_overlap, uint32_t* out_beg_end, uint32_t cap_pairs, uint32_t* n_pairs) {
-    if (!n_pairs || (n_overlaps && !overlaps) || (cap_pairs && !out_beg_end)) return CW_E_INVALID;
-    *n_pairs = 0;
-    /* the reference loops for ever on windowOverlap >= windowSize (the rewind undoes the whole window) and indexes out of bounds on a
-       negative one: an error here */
-    if (window_size == 0 || window_overlap < 0 || (uint32_t)window_overlap >= window_size) return CW_E_INVALID;
-    if (tpl_len == 0) return CW_OK;
-    /* getCoverages (:5-25) adds one to every base of every overlap; the same depths from a difference array and one prefix sum:
-       O(overlaps + length) instead of O(sum of the overlap lengths), which was most of the host time per pile */
-    std::vector<uint32_t> cov;
-    try { cov.assign((size_t)tpl_len + 1, 0); } catch (...) { return CW_E_NOMEM; }
-    for (uint32_t o = 0; o < n_overlaps; ++o) {
-        if (overlaps[o].q_end < overlaps[o].q_start || overlaps[o].q_end >= tpl_len) return CW_E_INVALID; /* the reference would write out of bounds */
-        cov[overlaps[o].q_start]++;
-        cov[(size_t)overlaps[o].q_end + 1]--; /* wraps; the prefix sum below brings it back */
-    }
-    for (uint32_t i = 1; i < tpl_len; ++i) cov[i] += cov[i - 1];
-    uint32_t count = 0;
-    bool over = false;
-    auto push = [&](uint32_t b, uint32_t e2) {
-        if (count < cap_pairs) { out_beg_end[2 * count] = b; out_beg_end[2 * count + 1] = e2; } else over = true;
-        ++count;
-    };
-    uint32_t cur = 0, beg = 0, i = 0;
-    while (i < tpl_len) {
-        if (cur >= window_size) {
-            push(beg, beg + cur - 1);
-            if (window_overlap) i = i - (uint32_t)window_overlap;
-            beg = i;
-            cur = 0;
-        }
-        if (cov[i] < min_support) { cur = 0; i++; beg = i; }
-        else { cur++; i++; }
-    }
-    bool pushed = false;
-    uint32_t end = tpl_len - 1;
-    cur = 0;
-    i = tpl_len - 1;
-    while (i > 0 && !pushed) {
-        if (cur >= window_size) { push(end - cur + 1, end); pushed = true; end = i; cur = 0; }
-        if (cov[i] < min_support) { cur = 0; i--; end = i; }
-        else { cur++; i--; }
-    }
-    *n_pairs = count;
-    return over ? CW_E_CAPACITY : CW_OK;
 }
 
 int cw_extract_piles_device(cw_engine* e, const cw_read_set* reads, const cw_overlap* overlaps, uint64_t n_overlaps,
@@ -960,14 +740,12 @@ int cw_stitch_device(cw_engine* e, const cw_read_set* reads, const cw_stitch_rea
        faster alone on its SIMD (measured with the register count deciding it: 55.3 ms per job at one wave per SIMD, 60.5 at two).  The kernel
        fits two per CU by registers and LDS; asking for more than half of the LDS keeps the second one off (CW_STITCH_TWO_PER_CU=1: don't). */
     const size_t lds_one = CW_AID_ENV("CW_STITCH_TWO_PER_CU") ? 0 : stitch_lds_one(e->prop);
-    const size_t lds_need = (size_t)CW_ST_WAVES * CW_ST_SLAB;
-    const size_t lds = lds_need > lds_one ? lds_need : lds_one, lds_n = (size_t)CW_STN_WAVES * CW_ST_SLAB_OF(CW_STN_QMAX, CW_STN_RMAX);
+    const size_t lds = kLdsStitch > lds_one ? kLdsStitch : lds_one, lds_n = kLdsStitchNarrow;
     uint32_t wgs = (n_reads + CW_ST_WAVES - 1) / CW_ST_WAVES;
     if (wgs > CW_ST_MAX_WGS) wgs = CW_ST_MAX_WGS;
     /* the narrow kernel holds four work-groups of four waves per CU (29 KB of LDS each, <= 128 VGPRs) */
-    const int cus_st = e->prop.multiProcessorCount > 0 ? e->prop.multiProcessorCount : 256;
     uint32_t wgs_n = (n_reads + CW_STN_WAVES - 1) / CW_STN_WAVES;
-    if (wgs_n > (uint32_t)cus_st * 4u) wgs_n = (uint32_t)cus_st * 4u;
+    if (wgs_n > (uint32_t)e->cus * 4u) wgs_n = (uint32_t)e->cus * 4u;
     /* Opt-in (CW_STITCH_NARROW=1).  Measured on the E. coli-scale ONT-profile set (10 jobs of 32768 windows, rocprofv3): the narrow kernel takes
        63 ms per job where the wide one takes ~75 -- a launch lasts as long as its longest read's serial chain of windows (a 30 kbp read: 66
        windows), which twice the resident waves do not shorten -- and the reads it hands on (a consensus above 640 in any of their windows)
@@ -977,7 +755,7 @@ int cw_stitch_device(cw_engine* e, const cw_read_set* reads, const cw_stitch_rea
     const bool sys = !narrow && CW_AID_ENV("CW_STITCH_SYS") && (uint64_t)window_size + 2ull * window_overlap <= CW_STS_RMAX;
     const size_t lds_s = (((size_t)CW_ST_SLAB_OF(CW_STS_QMAX, CW_STS_RMAX) + 15u) & ~(size_t)15u) + sizeof(StSys);
     uint32_t wgs_s = n_reads;
-    if (wgs_s > (uint32_t)cus_st * 6u) wgs_s = (uint32_t)cus_st * 6u;
+    if (wgs_s > (uint32_t)e->cus * 6u) wgs_s = (uint32_t)e->cus * 6u;
     uint32_t wgs_max = narrow && wgs_n > wgs ? wgs_n : wgs;
     if (sys && (wgs_s + CW_ST_WAVES - 1) / CW_ST_WAVES > wgs_max) wgs_max = (wgs_s + CW_ST_WAVES - 1) / CW_ST_WAVES;
     /* test aid: CW_STITCH_DIR_BYTES shrinks the banded-traceback scratch so that the capacity path can be exercised */
@@ -1027,9 +805,6 @@ int cw_debug_stitch_trace(cw_engine* e, uint32_t n_windows, uint32_t* out) {
  * H2D on its own stream, the kernels on the compute stream, the results compacted on the device (cw_pack_*: only the bytes the
  * windows actually produced cross PCIe, not the capacities the caller reserved), D2H on a third stream into pinned staging, then
  * scattered into the caller's arrays.  With two batches in flight the copies of one overlap the kernels of the other. */
-static int submit_locked(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket, bool pf_full);
-int cw_submit(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket) { return submit_locked(e, b, r, ticket, false); }
-
 /* pf_full: see run_device_locked (cw_run's re-run after CW_WHY_MATRIX) */
 static int submit_locked(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket, bool pf_full) {
     if (!e || !b || !r || !ticket || !r->cons || !r->cons_off || !r->cons_len || !r->win_status) return CW_E_INVALID;
@@ -1127,12 +902,11 @@ static int submit_locked(cw_engine* e, const cw_batch* b, const cw_result* r, in
     return CW_OK;
 }
 
-static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* used = nullptr, uint32_t* why_matrix = nullptr);
-int cw_wait(cw_engine* e, int ticket) { return wait_ticket(e, ticket, nullptr); }
+int cw_submit(cw_engine* e, const cw_batch* b, const cw_result* r, int* ticket) { return submit_locked(e, b, r, ticket, false); }
 
 /* why_tasks (may be NULL): how many windows of THIS ticket stopped on the batch's task / member / arena capacities; why_matrix: on the matrix slot */
 /* used (may be NULL): this ticket's task and member counts */
-static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* used, uint32_t* why_matrix) {
+static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* used = nullptr, uint32_t* why_matrix = nullptr) {
     if (why_tasks) *why_tasks = 0;
     if (why_matrix) *why_matrix = 0;
     if (used) used[0] = used[1] = 0xFFFFFFFFu;
@@ -1194,6 +968,8 @@ static int wait_ticket(cw_engine* e, int ticket, uint64_t* why_tasks, uint32_t* 
     return fail(rc);
 }
 
+int cw_wait(cw_engine* e, int ticket) { return wait_ticket(e, ticket, nullptr); }
+
 /* After a finished run: did windows stop on a capacity that a larger scratch plan cures (CW_WHY_TASKS: the task, member and arena slots are
    heuristics of the batch)?  Then the plan grows (x4, up to x64) and the caller runs the batch again -- if the larger plan is one the engine can
    actually run: inside the 32-bit offsets (plan_scratch clamps the arena's own scale) and inside the device's free memory.  A scale that is not
@@ -1212,11 +988,8 @@ static int grow_if_that_helps(cw_engine* e, bool* again, bool* pf_full, hipStrea
     int kinds = known_any > 0 ? known_any : 0; /* bit 0: windows stopped on task / member slots, bit 1: on their arena slices, bit 2: on the matrix slot */
     if (known_any < 0) {
         if (e->last_windows != n_windows) return CW_OK;
-        /* copies on the caller's stream, not hipMemcpy: the null stream would wait for every other stream of the device -- the other worker's job */
-        uint32_t* flag = e->host_fb + 8; /* pinned */
-        CW_HIP(hipMemcpyAsync(flag, (uint8_t*)e->scratch + e->last_ctr_off + offsetof(BatchCounters, any_overflow), 4, hipMemcpyDeviceToHost, st));
-        CW_HIP(hipStreamSynchronize(st));
-        if (!*flag) return CW_OK;
+        if (int rc = read_counters(e, st, offsetof(BatchCounters, any_overflow), 4, &e->host_fb->any_overflow)) return rc;
+        if (!e->host_fb->any_overflow) return CW_OK;
         std::vector<WinInfo> wi(e->last_windows);
         CW_HIP(hipMemcpyAsync(wi.data(), e->scratch, (size_t)e->last_windows * sizeof(WinInfo), hipMemcpyDeviceToHost, st));
         CW_HIP(hipStreamSynchronize(st));
@@ -1227,20 +1000,21 @@ static int grow_if_that_helps(cw_engine* e, bool* again, bool* pf_full, hipStrea
     }
     if (CW_AID_ENV("CW_TASK_CAP") || CW_AID_ENV("CW_MEMBER_CAP")) kinds &= 4; /* (test aids that shrink exactly the task / member capacities) */
     if (!kinds) return CW_OK;
-    const int cus = e->prop.multiProcessorCount > 0 ? e->prop.multiProcessorCount : 256;
-    const uint32_t bs = e->last_big_slots ? e->last_big_slots : 64;
-    const ScratchPlan cur = plan_scratch(e->prm, n_windows, n_seqs, n_words, cus, bs, e->cap_scale, e->tmax_plan, *pf_full);
+    PlanInput in = plan_input(e, n_windows, n_seqs, n_words), in_up = in;
+    in.pf_full = in_up.pf_full = *pf_full; in_up.scale = e->cap_scale * 4u;
+    const ScratchPlan cur = plan_scratch(in);
     const bool pf_grows = (kinds & 4) && cur.pfall_elems < (uint64_t)e->tmax_plan * kPfRowsMax;
     uint32_t next = e->cap_scale;
     if ((kinds & 3) && e->cap_scale < 64u) {
         /* does the larger plan grow what ran out?  (the arena's own scale is clamped to 32-bit offsets: a batch stopped on its arena slices
            at a clamped scale is the same batch with the same arena at x4, x16 and x64) */
-        const ScratchPlan up = plan_scratch(e->prm, n_windows, n_seqs, n_words, cus, bs, e->cap_scale * 4u, e->tmax_plan, *pf_full);
+        const ScratchPlan up = plan_scratch(in_up);
         if (((kinds & 1) && (up.task_cap > cur.task_cap || up.member_cap > cur.member_cap)) || ((kinds & 2) && up.arena_scale > cur.arena_scale)) next = e->cap_scale * 4u;
         else fprintf(stderr, "[consent_amd] windows stopped on the batch's %s capacity; a plan x%u does not enlarge it: keeping the run's result\n", (kinds & 2) ? "arena" : "task / member", e->cap_scale * 4u);
     }
     if (next == e->cap_scale && !pf_grows) return CW_OK;
-    const ScratchPlan p = plan_scratch(e->prm, n_windows, n_seqs, n_words, cus, bs, next, e->tmax_plan, *pf_full || pf_grows);
+    in.scale = next; in.pf_full = *pf_full || pf_grows;
+    const ScratchPlan p = plan_scratch(in);
     size_t free_b = 0, total_b = 0;
     const bool mem_known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
     if (!mem_known) (void)hipGetLastError();
@@ -1270,12 +1044,11 @@ static void decay_scale(cw_engine* e, hipStream_t st, uint32_t n_windows, uint32
     std::lock_guard<std::mutex> lk(e->mu);
     if (e->cap_scale <= 1u || !e->scratch || (!known && e->last_windows != n_windows)) return;
     if (hipSetDevice(e->device) != hipSuccess) return;
-    uint32_t* used = e->host_fb + 10; /* pinned: n_tasks, n_members */
+    uint32_t* used = e->host_fb->used; /* n_tasks, n_members */
     if (known) { if (known[0] == 0xFFFFFFFFu) return; used[0] = known[0]; used[1] = known[1]; }
-    else if (hipMemcpyAsync(used, (uint8_t*)e->scratch + e->last_ctr_off + offsetof(BatchCounters, n_tasks), 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return; }
-    const int cus = e->prop.multiProcessorCount > 0 ? e->prop.multiProcessorCount : 256;
-    const ScratchPlan lower = plan_scratch(e->prm, n_windows, n_seqs, n_words, cus, e->last_big_slots ? e->last_big_slots : 64, e->cap_scale / 4u, e->tmax_plan);
+    else if (read_counters(e, st, offsetof(BatchCounters, n_tasks), 8, used) != CW_OK) { (void)hipGetLastError(); return; }
+    PlanInput in = plan_input(e, n_windows, n_seqs, n_words); in.scale = e->cap_scale / 4u;
+    const ScratchPlan lower = plan_scratch(in);
     if ((uint64_t)used[0] * 2u > lower.task_cap || (uint64_t)used[1] * 2u > lower.member_cap) return;
     e->cap_scale /= 4u;
     bool in_flight = false;
@@ -1286,65 +1059,67 @@ static void decay_scale(cw_engine* e, hipStream_t st, uint32_t n_windows, uint32
     }
 }
 
-/* cw_run_device, then wait for the stream, then -- when windows stopped on the batch's task / member / arena capacities only -- once more
-   with a larger plan (cw_private.h; what the native driver and cw_run call: the asynchronous cw_run_device cannot look at its own result) */
-int cw_run_device_sync(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream) {
-    if (!e || !batch) return CW_E_INVALID;
-    bool grown = false, pf_full = false;
-    uint32_t scale_before = 1;
-    for (;;) {
-        int rc;
-        { std::lock_guard<std::mutex> lk(e->mu); rc = run_device_locked(e, batch, res, hip_stream, pf_full); }
-        if (rc != CW_OK) {
-            if (grown && (rc == CW_E_INVALID || rc == CW_E_NOMEM)) { /* the larger plan could not be set up after all (memory went to another engine meanwhile):
-                                                                         no kernel of the re-run was launched, the run before it stands, the scale goes back */
-                std::lock_guard<std::mutex> lk(e->mu);
-                e->cap_scale = scale_before;
-                return CW_OK;
-            }
-            return rc;
-        }
-        CW_HIP(hipSetDevice(e->device));
-        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
-        CW_HIP(hipStreamSynchronize(st));
-        bool again = false;
-        { std::lock_guard<std::mutex> lk(e->mu); scale_before = e->cap_scale; }
-        if ((rc = grow_if_that_helps(e, &again, &pf_full, st, -1, batch->n_windows, batch->n_seqs, batch->n_words)) != CW_OK) return rc;
-        if (!again) {
-            if (!grown) decay_scale(e, st, batch->n_windows, batch->n_seqs, batch->n_words);
-            return CW_OK;
-        }
-        grown = true;
-    }
-}
+/* One finished attempt at a batch.  launch_rc not CW_OK: it could not be set up and none of its kernels was launched.  rc, of the finished run: CW_OK, CW_E_CAPACITY
+   (windows stopped: the result stands), or an error that ends the loop.  known_any, used: grow_if_that_helps' and decay_scale's `known`.  st: the stream the two read scratch with. */
+struct Attempt { int launch_rc, rc, known_any; const uint32_t* used; hipStream_t st; };
 
-int cw_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
+/* Run a batch, and -- when windows stopped on the batch's task / member / arena / matrix capacities only -- once more with a larger plan, up to x64
+   (grow_if_that_helps); after a run that needed no growth, see whether a grown scale can go back (decay_scale).  attempt(pf_full) launches one run and waits for it.
+   A re-run whose larger plan could not be set up after all (memory went to another engine meanwhile) launched nothing: the run before it stands and the scale goes back. */
+extern "C++" { /* (a template cannot have C linkage) */
+template <class F>
+static int run_and_regrow(cw_engine* e, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words, F attempt) {
     bool grown = false, pf_full = false;
     uint32_t scale_before = 1;
     int first_rc = CW_OK;
     for (;;) {
-        int t = -1;
-        int rc = submit_locked(e, b, r, &t, pf_full);
-        if (rc != CW_OK) {
-            if (grown && (rc == CW_E_INVALID || rc == CW_E_NOMEM)) { std::lock_guard<std::mutex> lk(e->mu); e->cap_scale = scale_before; return first_rc; } /* see cw_run_device_sync */
-            return rc;
+        const Attempt a = attempt(pf_full);
+        if (a.launch_rc != CW_OK) {
+            if (!grown || (a.launch_rc != CW_E_INVALID && a.launch_rc != CW_E_NOMEM)) return a.launch_rc;
+            std::lock_guard<std::mutex> lk(e->mu);
+            e->cap_scale = scale_before;
+            return first_rc;
         }
-        uint64_t why_tasks = 0;
-        uint32_t used[2], why_matrix = 0;
-        const int wrc = wait_ticket(e, t, &why_tasks, used, &why_matrix);
-        if (wrc != CW_OK && wrc != CW_E_CAPACITY) return wrc;
+        if (a.rc != CW_OK && a.rc != CW_E_CAPACITY) return a.rc;
         bool again = false;
         { std::lock_guard<std::mutex> lk(e->mu); scale_before = e->cap_scale; }
-        /* the decision comes from this ticket's own totals (cw_pack_scan_kernel counts the windows stopped on CW_WHY_TASKS): other threads may have
-           submitted since, and the WinInfo in scratch may be theirs */
-        if (wrc == CW_E_CAPACITY && (rc = grow_if_that_helps(e, &again, &pf_full, e->stream, ((uint32_t)why_tasks ? 1 : 0) | ((why_tasks >> 32) ? 2 : 0) | (why_matrix ? 4 : 0),
-                                                             b->n_windows, b->n_seqs, b->n_words)) != CW_OK) return rc;
+        if (a.known_any < 0 || a.rc == CW_E_CAPACITY)
+            if (const int rc = grow_if_that_helps(e, &again, &pf_full, a.st, a.known_any, n_windows, n_seqs, n_words)) return rc;
         if (!again) {
-            if (!grown && wrc == CW_OK) decay_scale(e, e->stream, b->n_windows, b->n_seqs, b->n_words, used); /* the host path never lowered a grown scale */
-            return wrc;
+            if (!grown && a.rc == CW_OK) decay_scale(e, a.st, n_windows, n_seqs, n_words, a.used); /* the host path never lowered a grown scale */
+            return a.rc;
         }
-        grown = true; first_rc = wrc;
+        grown = true; first_rc = a.rc;
     }
+}
+} // extern "C++"
+
+/* cw_run_device, then wait for the stream, then -- when windows stopped on the batch's task / member / arena capacities only -- once more
+   with a larger plan (cw_private.h; what the native driver calls: the asynchronous cw_run_device cannot look at its own result; the statuses stay on the device) */
+int cw_run_device_sync(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream) {
+    if (!e || !batch) return CW_E_INVALID;
+    return run_and_regrow(e, batch->n_windows, batch->n_seqs, batch->n_words, [&](bool pf_full) {
+        int lrc;
+        { std::lock_guard<std::mutex> lk(e->mu); lrc = run_device_locked(e, batch, res, hip_stream, pf_full); }
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+        const bool waited = lrc != CW_OK || (hipSetDevice(e->device) == hipSuccess && hipStreamSynchronize(st) == hipSuccess);
+        return Attempt{lrc, waited ? CW_OK : CW_E_NO_DEVICE, -1, nullptr, st};
+    });
+}
+
+/* cw_submit + cw_wait in the same loop.  The decision comes from this ticket's own totals (cw_pack_scan_kernel counts the windows stopped on CW_WHY_TASKS /
+   _ARENA / _MATRIX and the tasks and members used): other threads may have submitted since, and the WinInfo in scratch may be theirs */
+int cw_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
+    if (!e || !b) return CW_E_INVALID;
+    uint32_t used[2];
+    return run_and_regrow(e, b->n_windows, b->n_seqs, b->n_words, [&](bool pf_full) {
+        int t = -1;
+        uint64_t why_tasks = 0;
+        uint32_t why_matrix = 0;
+        const int lrc = submit_locked(e, b, r, &t, pf_full);
+        const int rc = lrc == CW_OK ? wait_ticket(e, t, &why_tasks, used, &why_matrix) : CW_OK;
+        return Attempt{lrc, rc, ((uint32_t)why_tasks ? 1 : 0) | ((why_tasks >> 32) ? 2 : 0) | (why_matrix ? 4 : 0), used, e->stream};
+    });
 }
 
 /* pinned host memory for batches and results: copies from and to it are real DMA transfers that overlap the kernels; plain

@@ -1,6 +1,7 @@
 /*
- * cw_hostio.cpp -- host feeders of the path: the read indexer and the PAF pile reader.
+ * cw_hostio.cpp -- host feeders of the path: the window positions of a pile, the read indexer and the PAF pile reader.
  *
+ *   cw_window_positions <- getCoverages + getAlignmentWindowsPositions (src/alignmentWindows.cpp:5-85)
  *   cw_index_reads      <- indexReads      (src/utils.cpp:166-205): FASTA/FASTQ -> 2-bit reads keyed by name
  *   cw_paf_next_pile    <- getNextReadPile (src/alignmentPiles.cpp:22-58) + Overlap(std::string) (src/Overlap.h:26-58)
  *   cw_paf_reformat / cw_paf_explode / cw_paf_merge <- the wrapper tools reformatPAF.cpp, explode.cpp, merge.cpp
@@ -330,6 +331,58 @@ static int index_file(cw_read_index* ix, const char* path) {
     }
     if (n) munmap((void*)p, n);
     return rc;
+}
+
+/* getCoverages + getAlignmentWindowsPositions (src/alignmentWindows.cpp:5-85) on the host: per-base overlap depth over
+ * [q_start, q_end] inclusive; a window [beg, beg+window_size-1] whenever window_size consecutive bases have depth >=
+ * min_support, then rewind by window_overlap (:40-47); a base below min_support resets (:48-51); finally ONE trailing window
+ * = the last window_size covered bases found scanning backwards from the end, never looking at base 0 (:58-79). */
+int cw_window_positions(uint32_t tpl_len, const cw_overlap* overlaps, uint32_t n_overlaps, uint32_t min_support, uint32_t window_size,
+                        int32_t window_overlap, uint32_t* out_beg_end, uint32_t cap_pairs, uint32_t* n_pairs) {
+    if (!n_pairs || (n_overlaps && !overlaps) || (cap_pairs && !out_beg_end)) return CW_E_INVALID;
+    *n_pairs = 0;
+    /* the reference loops for ever on windowOverlap >= windowSize (the rewind undoes the whole window) and indexes out of bounds on a
+       negative one: an error here */
+    if (window_size == 0 || window_overlap < 0 || (uint32_t)window_overlap >= window_size) return CW_E_INVALID;
+    if (tpl_len == 0) return CW_OK;
+    /* getCoverages (:5-25) adds one to every base of every overlap; the same depths from a difference array and one prefix sum:
+       O(overlaps + length) instead of O(sum of the overlap lengths), which was most of the host time per pile */
+    std::vector<uint32_t> cov;
+    try { cov.assign((size_t)tpl_len + 1, 0); } catch (...) { return CW_E_NOMEM; }
+    for (uint32_t o = 0; o < n_overlaps; ++o) {
+        if (overlaps[o].q_end < overlaps[o].q_start || overlaps[o].q_end >= tpl_len) return CW_E_INVALID; /* the reference would write out of bounds */
+        cov[overlaps[o].q_start]++;
+        cov[(size_t)overlaps[o].q_end + 1]--; /* wraps; the prefix sum below brings it back */
+    }
+    for (uint32_t i = 1; i < tpl_len; ++i) cov[i] += cov[i - 1];
+    uint32_t count = 0;
+    bool over = false;
+    auto push = [&](uint32_t b, uint32_t e2) {
+        if (count < cap_pairs) { out_beg_end[2 * count] = b; out_beg_end[2 * count + 1] = e2; } else over = true;
+        ++count;
+    };
+    uint32_t cur = 0, beg = 0, i = 0;
+    while (i < tpl_len) {
+        if (cur >= window_size) {
+            push(beg, beg + cur - 1);
+            if (window_overlap) i = i - (uint32_t)window_overlap;
+            beg = i;
+            cur = 0;
+        }
+        if (cov[i] < min_support) { cur = 0; i++; beg = i; }
+        else { cur++; i++; }
+    }
+    bool pushed = false;
+    uint32_t end = tpl_len - 1;
+    cur = 0;
+    i = tpl_len - 1;
+    while (i > 0 && !pushed) {
+        if (cur >= window_size) { push(end - cur + 1, end); pushed = true; end = i; cur = 0; }
+        if (cov[i] < min_support) { cur = 0; i--; end = i; }
+        else { cur++; i--; }
+    }
+    *n_pairs = count;
+    return over ? CW_E_CAPACITY : CW_OK;
 }
 
 int cw_index_reads(const char* path, cw_read_index** out) {

@@ -33,6 +33,12 @@ struct cw_slot {
 
 #include "cw_env.h"
 
+struct cw_host_fb { /* pinned: what asynchronous copies bring back from the device */
+    uint32_t handed_over;  /* tasks the last finished batch handed to tier L's live queue (BatchCounters::n_over[3]; feeds linger_wgs): copied at the end of every run */
+    uint32_t any_overflow; /* BatchCounters::any_overflow of the run grow_if_that_helps looks at */
+    uint32_t used[2];      /* n_tasks, n_members of the run decay_scale looks at */
+};
+
 struct cw_engine {
     std::mutex mu; /* every entry point that touches the engine takes it: one engine = one caller at a time (see consent_amd.h "Threading") */
     cw_params prm{};
@@ -40,6 +46,7 @@ struct cw_engine {
     hipStream_t stream = nullptr;
     hipStream_t copy_in = nullptr, copy_out = nullptr; /* H2D / D2H of host batches, beside the compute stream */
     hipDeviceProp_t prop{};
+    int cus = 256; /* compute units of the device (cw_create): what grids and the scratch plan go by */
     /* growable device scratch owned by the engine (never shrinks) */
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -49,7 +56,7 @@ struct cw_engine {
     size_t xscratch_bytes = 0;
     void* stitch_scratch = nullptr; /* banded-traceback directions of cw_stitch_device, per wave */
     size_t stitch_scratch_bytes = 0;
-    uint32_t* host_fb = nullptr; /* pinned: [0] tasks the last finished batch handed to tier L (feeds linger_wgs), [1] its sequence number */
+    cw_host_fb* host_fb = nullptr;
     /* per-stage timing of the last run */
     hipStream_t side[3] = {nullptr, nullptr, nullptr}; /* POA tiers run concurrently on their own streams (M1, M2, L) */
     hipStream_t stagger = nullptr; /* never used: the runtime hands hardware queues to streams round robin in the order of their creation, and with four queues
@@ -60,13 +67,11 @@ struct cw_engine {
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     int n_stages = 0;
     const char* stage_name[CW_MAX_STAGES] = {};
-    float stage_ms[CW_MAX_STAGES] = {};
     bool timings_valid = false;
-    uint32_t last_windows = 0, last_big_slots = 0, last_seqs = 0;
+    uint32_t last_windows = 0, last_big_slots = 0; /* of the last run: its batch, and tier G's slots as CW_BIG_SLOTS had them */
     uint32_t tmax_plan = 1024; /* template k-mers per window the scratch plan provides for (cw_configure) */
     uint32_t linger_wgs = 0; /* tier-L work-groups kept on the live overflow queue (adapted from the previous batch) */
     uint32_t cap_scale = 1;  /* multiplier of the batch's task / member / arena capacities: grows (x4) after a run that stopped on them (cw_run_device_sync) */
-    uint64_t last_words = 0;
     size_t last_ctr_off = 0; /* where the last run's BatchCounters sit in scratch */
     size_t last_tasks_off = 0, last_tdbg_off = 0;
     uint32_t last_task_cap = 0;

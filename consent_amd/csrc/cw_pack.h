@@ -29,7 +29,7 @@ struct PackArgs {
     uint64_t* ps_off;  /* [n_windows + 1]        */
     uint64_t* totals;  /* [0] consensus bytes, [1] solid k-mers, [2] windows stopped on the batch's task / member capacities (CW_WHY_TASKS, low half) and on their arena slices (CW_WHY_ARENA, high half), [5] on the index kernel's global matrix slot (CW_WHY_MATRIX) whose need (WinInfo::arena_used) a slot of pf_full_elems holds */
     const WinInfo* win; /* the batch's per-window records in the engine's scratch (read for [2] and [5] only) */
-    uint64_t pf_full_elems; /* u16 elements of the matrix slot at its full size (cw_engine.cpp kPfRowsMax) */
+    uint64_t pf_full_elems; /* u16 elements of the matrix slot at its full size (cw_plan.h kPfRowsMax) */
     const uint32_t* used; /* the batch's counters n_tasks, n_members (BatchCounters): copied to totals[3], [4] -- what cw_run's scale decay goes by */
 };
 

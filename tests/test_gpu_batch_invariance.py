@@ -1,6 +1,6 @@
 """Batch-composition invariance (include/consent_amd.h: a window's result does not depend on the batch it comes in).
 
-The engine sizes its scratch from batch totals and hands out per-window slices in window order (cw_engine.cpp plan_scratch,
+The engine sizes its scratch from batch totals and hands out per-window slices in window order (cw_plan.h plan_scratch,
 cw_index.h cw_setup_kernel), so whether a window fits could depend on the windows beside it.  Here a catalogue of probe windows, each
 aimed at one code path, is run alone and in other batches -- among copies of itself, among shallow fillers (low mean depth), inside the
 bench batch, on an engine that has just run something larger, through the device-buffer path -- and every run must give the same

@@ -4,6 +4,9 @@ Per-window offsets into the solid table, the segment slots and the arena are 32-
 (cw_max_batch_windows) must keep all three inside them, for every template length cw_configure can set; the index kernel's matrix
 fallback slot must have the size its re-run after CW_WHY_MATRIX promises; the bench batch's plan must not grow."""
 import ctypes as C
+import itertools
+import json
+import os
 
 import pytest
 
@@ -11,7 +14,7 @@ import consent_amd as ca
 
 U32 = 0xFFFFFFFF
 MAX_BATCH = 131072  # include/consent_amd.h CW_MAX_BATCH_WINDOWS
-PF_ROWS_MAX = 4100  # cw_engine.cpp kPfRowsMax
+PF_ROWS_MAX = 4100  # cw_plan.h kPfRowsMax
 CUS = 256
 
 
@@ -103,3 +106,43 @@ def test_the_bench_batch_plan_is_unchanged(lib):
     assert int(out[0]) == c["total"]
     assert c["pf_rows"] == 16 * 152
     assert int(out[0]) == 17975889152  # (the plan of the parent tree, byte for byte)
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_numbers.json")
+GRID_AXES = {"cus": [256, 64], "windows": [1, 24, 2048, 16384, 115704, 131072], "depth": [4, 30, 150], "tmax": [128, 492, 1024, 2048],
+             "scale": [1, 4, 64], "pf_full": [0, 1]}
+
+
+def plan_grid(lib, k=9, solid=4, wlen=500):
+    """cw_debug_plan (15 numbers; it has no pf_full argument: recorded once per point of the other axes) and cw_debug_plan_caps (8 numbers)
+    over GRID_AXES, in the order of itertools.product over the axes as listed; piles of depth + 1 sequences of wlen bases, as in caps()."""
+    plan, caps8, rejected = [], [], []
+    for cus, windows, depth, tmax, scale, pf_full in itertools.product(*GRID_AXES.values()):
+        n_seqs = windows * (depth + 1)
+        n_words = n_seqs * ((wlen + 15) // 16 + 1)
+        if not pf_full:
+            out15 = (C.c_uint64 * 15)()
+            rc = lib.cw_debug_plan(k, solid, windows, n_seqs, n_words, cus, scale, tmax, out15)
+            plan.append([int(x) for x in out15] if rc == 0 else None)
+            if rc:
+                rejected.append(["cw_debug_plan", cus, windows, depth, tmax, scale, pf_full, rc])
+        out8 = (C.c_uint64 * 8)()
+        rc = lib.cw_debug_plan_caps(k, solid, windows, n_seqs, n_words, cus, scale, tmax, pf_full, out8)
+        caps8.append([int(x) for x in out8] if rc == 0 else None)
+        if rc:
+            rejected.append(["cw_debug_plan_caps", cus, windows, depth, tmax, scale, pf_full, rc])
+    return {"axes": GRID_AXES, "k": k, "solid": solid, "wlen": wlen, "plan": plan, "caps": caps8, "rejected": rejected}
+
+
+def test_the_plan_numbers_are_those_recorded_before_the_plan_moved(lib):
+    """tests/golden/plan_numbers.json holds what the tree BEFORE the plan moved to cw_plan.h computed (the commit is named in the file): every
+    number of every point of the grid, exactly."""
+    gold = json.load(open(GOLDEN))
+    got = plan_grid(lib, gold["k"], gold["solid"], gold["wlen"])
+    assert gold["axes"] == GRID_AXES
+    assert len(gold["plan"]) == 432 and len(gold["caps"]) == 864
+    assert got["rejected"] == gold["rejected"]
+    for name in ("plan", "caps"):
+        assert len(got[name]) == len(gold[name]), name
+        diff = [i for i, (a, b) in enumerate(zip(got[name], gold[name])) if a != b]
+        assert not diff, (name, diff[:5], got[name][diff[0]], gold[name][diff[0]])
