@@ -83,8 +83,8 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
             const uint8_t* gdelta = growid + cw_ab_align((uint64_t)A);
             const uint16_t* P = (const uint16_t*)(n_rows ? gdelta + (size_t)n_rows * Ap : growid);
             const int sup_min = min((int)prm.common_kmers, (int)N / 2); /* correctionMSA.cpp:31 */
-            if (lane == 0) { atomicAdd(&sc.ctr->prof[50], (ab_flags & 4u) ? 1ull : 0ull); atomicAdd(&sc.ctr->prof[51], (unsigned long long)n_rows); atomicAdd(&sc.ctr->prof[52], has_bm ? 1ull : 0ull); }
-            if (lane == 0) { atomicAdd(&sc.ctr->prof[42], (unsigned long long)A); atomicAdd(&sc.ctr->prof[43], (unsigned long long)n_dirty); atomicAdd(&sc.ctr->prof[44], 1ull); }
+            if (lane == 0) { atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_FIX_WINDOWS], (ab_flags & 4u) ? 1ull : 0ull); atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_FIX_ROWS], (unsigned long long)n_rows); atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_BAD_MASKS], has_bm ? 1ull : 0ull); }
+            if (lane == 0) { atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_ANCHORS], (unsigned long long)A); atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_DIRTY], (unsigned long long)n_dirty); atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_WINDOWS], 1ull); }
             const uint32_t seg_base = ch_uni(wi->seg_base), seg_cap = ch_uni(wi->seg_cap);
             const uint32_t arena_base = ch_uni(wi->arena_base), arena_cap = ch_uni(wi->arena_cap);
 
@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
             }
             if (lane == 0) smax[A] = -1;
             cw_wave_sync();
-            CW_PROF(sc.ctr, 48, lane == 0);
+            CW_PROF(sc.ctr, CW_PS_CHAIN_STAGE, lane == 0);
 
             /* ================= phase C: chain ================= */
             /* The recurrence is serial over the anchors, so its cost is the latency of one step.  In the usual case (presence bitsets in
@@ -322,7 +322,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                 }
                 cw_wave_sync();
             }
-            if (!fast_path && lane == 0) { atomicAdd(&sc.ctr->prof[53], 1ull); atomicAdd(&sc.ctr->prof[54], __builtin_readcyclecounter() - _c0); }
+            if (!fast_path && lane == 0) { atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_SLOW], 1ull); atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_SLOW_CYCLES], __builtin_readcyclecounter() - _c0); }
             /* chain start: longest, then best score, then largest index; a chain needs at least one edge */
             uint32_t m = 0;
             {
@@ -347,7 +347,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                 }
                 cw_wave_sync();
             }
-            CW_PROF(sc.ctr, 5, lane == 0);
+            CW_PROF(sc.ctr, CW_PS_CHAIN, lane == 0);
 
             if (m == 0 || m < prm.min_anchors) {
                 new_status = CW_WIN_TEMPLATE;
@@ -612,11 +612,11 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                     cw_wave_sync();
                 }
                 if (!over && q_cnt) flush();
-                if (lane == 0) atomicAdd(&sc.ctr->prof[49], t_flush);
+                if (lane == 0) atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_FLUSH], t_flush);
                 if (over) { new_status = CW_WIN_OVERFLOW; why = over_arena ? CW_WHY_ARENA : CW_WHY_TASKS; }
                 else n_segs_out = m + 1;
             }
-            CW_PROF(sc.ctr, 6, lane == 0);
+            CW_PROF(sc.ctr, CW_PS_SEGMENTS, lane == 0);
         }
         new_status = ch_uni(new_status); n_segs_out = ch_uni(n_segs_out); arena_used = ch_uni(arena_used);
         if (lane == 0) {

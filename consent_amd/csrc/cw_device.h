@@ -79,6 +79,36 @@ struct PoaMember {
 #define CW_TIERS 6 /* POA memory tiers: 0 = S (LDS), 1 = M1, 2 = M2, 3 = L (graph in LDS, matrix in a slab), 4 = G (all global), 5 = H (two tasks per wave,
                       cw_poa_q.h); list 0 is tier Q's (four tasks per wave, cw_poa_q.h) */
 #define CW_PROF_SLOTS 128
+/* Who writes which slot of BatchCounters::prof.  bench.py, tools/ and the tests read the array by number (cw_debug_profile): the numbers are that interface
+   and stay what they are.  "Phases" of a POA tier are five slots: metadata, fill, traceback, merge, consensus. */
+enum CwProfSlot : int {
+    CW_PS_IDX_COUNT = 0, CW_PS_IDX_EXACT = 1, CW_PS_IDX_EXPORT = 2, CW_PS_IDX_SUPPORT = 3, CW_PS_IDX_HANDOVER = 4, /* index kernel, cycles per phase */
+    CW_PS_CHAIN = 5, CW_PS_SEGMENTS = 6,                      /* chain kernel: chaining, segment extraction */
+    CW_PS_IDX_TPLHASH = 7,
+    CW_PS_POA = 8, CW_PS_POA_STRIDE = 5,                      /* phases of slab tier t at CW_PS_POA + CW_PS_POA_STRIDE * t: 0 S, 1 M1, 2 M2, 3 L, 4 G ... */
+    CW_PS_POAQ = 28,                                          /* ... tier Q's, in the slots tier G's rare tasks add to as well */
+    CW_PS_LONGEST = 36,                                       /* + t: the longest single task of slab tier t */
+    CW_PS_SORT_CLOCK = 41,                                    /* wall clock at the tier sort: time base of the task trace */
+    CW_PS_CHAIN_ANCHORS = 42, CW_PS_CHAIN_DIRTY = 43, CW_PS_CHAIN_WINDOWS = 44, /* chain kernel: anchors, dirty sequences, windows */
+    CW_PS_L_CHUNK_ROWS = 46, CW_PS_L_ROWS = 47,               /* tier L's fills: rows x direction-word chunks, rows */
+    CW_PS_CHAIN_STAGE = 48, CW_PS_CHAIN_FLUSH = 49,           /* chain kernel, cycles: stage-in, segment flush */
+    CW_PS_CHAIN_FIX_WINDOWS = 50, CW_PS_CHAIN_FIX_ROWS = 51, CW_PS_CHAIN_BAD_MASKS = 52, /* ... windows with correction rows, those rows, windows with bad masks */
+    CW_PS_CHAIN_SLOW = 53, CW_PS_CHAIN_SLOW_CYCLES = 54,      /* ... windows on the slow path, cycles there */
+    CW_PS_IDX_STAGE = 55, CW_PS_IDX_EXPORT_SCAN = 56,         /* index kernel detail, cycles */
+    CW_PS_IDLE_GAP = 57,                                      /* 10 ns units between the batch before and this one */
+    CW_PS_IDX_CAND = 58, CW_PS_IDX_PFILL = 59, CW_PS_IDX_CLEAN = 60, CW_PS_IDX_DIRTY = 61, CW_PS_IDX_PRESENCE = 62,
+    CW_PS_POAH = 64,                                          /* tier H's phases */
+    CW_PS_DIAG = 72, CW_PS_DIAG_STRIDE = 12,                  /* -DCW_DIAG: row / trip counts of slab tier t (S .. L) at CW_PS_DIAG + CW_PS_DIAG_STRIDE * t (PoaMem::diag) */
+    CW_PS_VERIFY_MEMBERS = 120, CW_PS_VERIFY_DIFFER = 121,    /* -DCW_POA_VERIFY: members compared, members differing ... */
+    CW_PS_VERIFY_WHERE = 122, CW_PS_VERIFY_SIZE = 123, CW_PS_VERIFY_END = 124, CW_PS_VERIFY_COLS = 125 /* ... and the first difference: window | member, columns | rows, end rows, columns */
+};
+static_assert(CW_PS_POA == 8 && CW_PS_POA_STRIDE == 5 && CW_PS_POAQ == 28 && CW_PS_POAH == 64, "phase slots: bench.py reads them by number");
+static_assert(CW_PS_POA + CW_PS_POA_STRIDE * 4 == CW_PS_POAQ, "tier G's phases share tier Q's slots");
+static_assert(CW_PS_LONGEST == 36 && CW_PS_LONGEST + 4 < CW_PS_SORT_CLOCK && CW_PS_SORT_CLOCK == 41, "longest-task slots, sort clock");
+static_assert(CW_PS_L_CHUNK_ROWS == 46 && CW_PS_L_ROWS == 47, "tier L's fill-row counters");
+static_assert(CW_PS_DIAG == 72 && CW_PS_DIAG_STRIDE == 12 && CW_PS_DIAG + CW_PS_DIAG_STRIDE * 4 == CW_PS_VERIFY_MEMBERS, "diag slots end where the verify slots begin");
+static_assert(CW_PS_VERIFY_MEMBERS == 120 && CW_PS_VERIFY_COLS == 125 && CW_PS_VERIFY_COLS < CW_PROF_SLOTS, "verify slots: tools/verify_codes.py reads them by number");
+static_assert(CW_PS_CHAIN_ANCHORS == 42 && CW_PS_CHAIN_STAGE == 48 && CW_PS_CHAIN_SLOW_CYCLES == 54 && CW_PS_IDX_STAGE == 55 && CW_PS_IDX_PRESENCE == 62, "chain and index slots");
 
 /* Batch-wide counters (one struct in scratch, zeroed before every run). */
 struct BatchCounters {

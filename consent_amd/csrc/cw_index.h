@@ -68,7 +68,7 @@ __host__ __device__ __forceinline__ uint64_t cw_ab_bytes(uint32_t A, uint32_t N,
 __global__ void __launch_bounds__(256) cw_setup_need_kernel(DevBatch b, DevScratch sc, cw_params prm) {
     const int lane = threadIdx.x & 63;
     const uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (blockIdx.x == 0 && threadIdx.x == 0) sc.ctr->prof[57] = wall_clock64() - sc.step_clock[0]; /* 10 ns units since the batch before ended */
+    if (blockIdx.x == 0 && threadIdx.x == 0) sc.ctr->prof[CW_PS_IDLE_GAP] = wall_clock64() - sc.step_clock[0]; /* 10 ns units since the batch before ended */
     if (w >= b.n_windows) return;
     const uint32_t s0 = b.win_first_seq[w], s1 = b.win_first_seq[w + 1];
     uint32_t nk = 0;
@@ -475,7 +475,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
             for (uint32_t h = 0; h < n_half; ++h) {
                 for (uint32_t i = tid; i < bwords; i += CW_IDX_THREADS) tab[i] = 0;
                 __syncthreads(); /* (flags[2], the byte sum, runs on over the halves: cleared with the other flags above) */
-                if (h == 0) CW_PROF(sc.ctr, 55, tid == 0);
+                if (h == 0) CW_PROF(sc.ctr, CW_PS_IDX_STAGE, tid == 0);
 #if CW_IDX_BYTES_RTN /* rounds 4: a returning add, the old byte looked at */
                 CW_IDX_PASS_BLOCKR({
                     if (n_half > 1u && (key >> 17) != h) continue;
@@ -501,7 +501,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
                 })
 #endif
                 __syncthreads();
-                CW_PROF(sc.ctr, 0, tid == 0);
+                CW_PROF(sc.ctr, CW_PS_IDX_COUNT, tid == 0);
                 if (flags[0]) { ok8 = false; break; }
                 /* export of this half, as the nibble table's fast export below: wave v owns a sixteenth of the table and reads it lane-interleaved,
                    four words (sixteen keys) per lane and read; key order = (read, lane, bit) */
@@ -525,7 +525,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
 #if !CW_IDX_BYTES_RTN
                 { const uint32_t ws_ = (uint32_t)cw_wave_sum((int)bsum); if (lane == 0) atomicAdd(&flags[2], ws_); } /* complete after the barriers of the scan below */
 #endif
-                CW_PROF(sc.ctr, 56, tid == 0);
+                CW_PROF(sc.ctr, CW_PS_IDX_EXPORT_SCAN, tid == 0);
                 uint32_t offs[8], wtot = 0;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
@@ -608,7 +608,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
         for (uint32_t i = tid; i < CW_EX_SLOTS; i += CW_IDX_THREADS) ex[i] = 0ull;
         if (tid < 8) flags[tid] = 0;
         __syncthreads();
-        CW_PROF(sc.ctr, 55, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_STAGE, tid == 0);
         CW_IDX_PASS_BLOCKR({
             const uint32_t wd = key >> 3, sh = (key & 7) * 4;
             uint32_t old = tab[wd];
@@ -662,8 +662,8 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
             big_ex = true;
         }
 #undef CW_IDX_COUNT_PASS
-        CW_PROF(sc.ctr, 0, tid == 0);
-        CW_PROF(sc.ctr, 1, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_COUNT, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_EXACT, tid == 0);
         if (flags[0]) { /* more saturated keys than even the global exact table holds */
             if (tid == 0) { wi->status = CW_WIN_OVERFLOW; wi->pad_ = CW_WHY_COUNT; sc.ctr->any_overflow = 1; }
             __builtin_amdgcn_wave_barrier(); /* the wave meets again before the back edge (see cw_stitch.h) */
@@ -736,7 +736,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
                         m[i] = cmask(v4.x) | (cmask(v4.y) << 8) | (cmask(v4.z) << 16) | (cmask(v4.w) << 24);
                     }
                 }
-                CW_PROF(sc.ctr, 56, tid == 0);
+                CW_PROF(sc.ctr, CW_PS_IDX_EXPORT_SCAN, tid == 0);
                 uint32_t offs[8], wtot = 0;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
@@ -794,7 +794,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
                     scan_word(tab[w_beg + r], w_beg + r);
                 }
             }
-            CW_PROF(sc.ctr, 56, tid == 0);
+            CW_PROF(sc.ctr, CW_PS_IDX_EXPORT_SCAN, tid == 0);
             uint32_t total;
             const uint32_t off = cw_block_exscan(mine, scan_tmp, &total);
             const bool fits = total <= w_solid_cap;
@@ -842,7 +842,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
         } /* the nibble path */
         } /* direct table */
 
-        CW_PROF(sc.ctr, 2, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_EXPORT, tid == 0);
         /* ================= phase B: anchor candidates ================= */
         const uint32_t nk0 = L0 >= k ? L0 - k + 1 : 0;
         const int sup_min = min((int)prm.common_kmers, (int)N / 2); /* correctionMSA.cpp:31 */
@@ -895,7 +895,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
             }
         }
         __syncthreads();
-        CW_PROF(sc.ctr, 7, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_TPLHASH, tid == 0);
         /* support + repeat detection: one wave per sequence, four consecutive k-mers per lane out of one 64-bit window of the packed bases.  The
            four template-table lookups of a lane are requested together, one bucket each (nine in ten end there: not a template k-mer), and so
            are the hits' updates: the four "seen in this sequence" bits go out together, and the wave takes its places in the hit list with
@@ -989,7 +989,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
             cw_wave_sync();
         }
         __syncthreads();
-        CW_PROF(sc.ctr, 3, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_SUPPORT, tid == 0);
         /* candidates in template order */
         uint32_t A;
         {
@@ -1009,7 +1009,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
             }
         }
         __syncthreads();
-        CW_PROF(sc.ctr, 58, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_CAND, tid == 0);
         /* LDS needs: the matrix (A*Np u16) + presence bitsets (A*Nw u64) + dirty list (N u16) */
         const bool pg = !tfit && (uint64_t)A * Np * 2 + (uint64_t)A * Nw * 8 + (uint64_t)N * 2 + 16 > (uint64_t)p_cap * 2;
         if (pg && (uint64_t)A * Np > sc.p_fallback_elems) {
@@ -1051,7 +1051,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
             }
             __syncthreads();
         }
-        CW_PROF(sc.ctr, 59, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_PFILL, tid == 0);
 
         /* A sequence whose anchor positions increase with the anchor index ("clean") satisfies pos(a) < pos(b) for every
            pair a < b it holds, so its contribution to score(a,b) is one bit of presence(a) & presence(b); only the few
@@ -1100,7 +1100,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
             }
             if (tid == 0) misc[3] = 0;
             __syncthreads();
-            CW_PROF(sc.ctr, 60, tid == 0);
+            CW_PROF(sc.ctr, CW_PS_IDX_CLEAN, tid == 0);
             for (uint32_t s = tid; s < N; s += CW_IDX_THREADS)
                 if (clean[s] != 1) dirty[atomicAdd(&misc[3], 1u)] = (uint16_t)s;
             __syncthreads();
@@ -1142,7 +1142,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
                 if (has_bm && (uint32_t)tid < nd) { const uint32_t s = dirty[tid]; clean[s] = (uint8_t)0x80u; if (N <= 1024u) didx[s] = (uint8_t)tid; else clean[s] = (uint8_t)(0x80u | (uint32_t)tid); }
                 __syncthreads();
             }
-            CW_PROF(sc.ctr, 61, tid == 0);
+            CW_PROF(sc.ctr, CW_PS_IDX_DIRTY, tid == 0);
             for (uint32_t w = 0; w < Nw; ++w) { /* what a lane knows about its sequence is read once, not once per anchor */
                 const uint32_t s = w * 64 + lane;
                 const uint32_t c = s < N ? (uint32_t)clean[s] : 0u;
@@ -1159,7 +1159,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
             __syncthreads();
         }
         const uint32_t n_dirty = use_bits ? misc[3] : 0u;
-        CW_PROF(sc.ctr, 62, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_PRESENCE, tid == 0);
 
         /* ================= hand-over: the window's anchor block =================
            Chaining is a serial recurrence over the anchors: one wave's work.  Doing it here would idle 15 of this
@@ -1236,7 +1236,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
             /* no flag, no fence: every early exit above changes wi->status, so "still CW_WIN_CONSENSUS when the kernel has ended"
                means the block is complete, and the kernel boundary makes it visible to cw_chain_kernel */
         }
-        CW_PROF(sc.ctr, 4, tid == 0);
+        CW_PROF(sc.ctr, CW_PS_IDX_HANDOVER, tid == 0);
     }
 }
 

@@ -683,7 +683,6 @@ __device__ __forceinline__ uint32_t poa_consensus_hb(const PoaMem<HT>& M, const 
 }
 #endif
 
-/* Returns 1 = done, 2 = a capacity of this memory class was exceeded, 3 = output capacity exceeded / internal. */
 /* PK: 0 = one column per lane (int32 tier G); 1 = two columns per lane in packed int16 for rows wider than 64 columns (tiers S, M1,
    M2, whose capacities keep every score far inside int16); 2 = the same for tier L while nodes + columns <= CW_POA_PK_SPAN, i.e.
    while |score| <= 8 * span stays clear of the packed "minus infinity" even after the per-column gap offsets are taken out. */
@@ -694,637 +693,613 @@ __device__ __forceinline__ uint32_t poa_consensus_hb(const PoaMem<HT>& M, const 
 #endif
 #include "cw_poa_a.h"
 
-template <typename HT, int PK, int CM = 0, int LCAP = 1023, bool WX = false> /* LCAP: the tier's longest member -- fills for wider rows are not compiled into its kernel; WX: tier X's row word */
-__device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, const DevBatch& b, const DevScratch& sc, const int lane,
-                       unsigned long long (&acc)[6]) {
-    if constexpr (CW_POA_AFFINE && sizeof(HT) != 4) return 2; /* the affine gap model keeps three int32 layers: every task is handed on to the global-memory tier */
-    unsigned long long _pt = __builtin_readcyclecounter();
-#define POA_PROF(slot) do { const unsigned long long _n = __builtin_readcyclecounter(); acc[slot] += _n - _pt; _pt = _n; } while (0)
-    const int G = CW_POA_GAP, MS = CW_POA_MATCH, XS = CW_POA_MISMATCH;
-    int n = 0, ne = 0, nseq = 0, tpl_nodes = 0;
-    bool meta_ok = false;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    int gf_left = 0, gf_idx = 0; /* group fill (poa_fill_pk4): members behind the current one whose rows are already in the matrix; the current one's place in the group */
-    /* the replay of a repeated member (round 6; cw_poa_q.h has the same in its per-group form): a member that is, base for base, the member aligned just before
-       it -- which changed nothing in the graph but coverage counts -- would make the same fill, walk and path: its merge is that path's coverage counts
-       once more (M.pcur, M.sq still hold path and bases).  Measured on the checker: half of the members of the large tiers' tasks (the short ragged pieces of a
-       window's first and last segment), 2 % of tier S's.  Not under the heaviest-bundle policy (the path's edge weights would have to go up too). */
-    bool prev_clean = false; /* the member before this one was aligned and added neither a node nor an edge */
-    int prev_L = -1;
+/* What a wave carries from member to member of its task (wave-uniform: sizes steer every loop, they stay in scalar registers). */
+struct PoaSt {
+    int n, ne, nseq, tpl_nodes;
+    int gf_left, gf_idx;   /* group fill (poa_fill_pk4): members behind the current one whose rows are already in the matrix; the current one's place in the group */
+    int prev_L;
+    bool meta_ok;          /* the row metadata (poa_row_meta) matches the graph: no merge has changed its structure since */
+    bool prev_clean;       /* the member before this one was aligned and added neither a node nor an edge */
+    unsigned long long pt; /* phase clock (POA_PROF) */
+    __device__ __forceinline__ void reset() { n = 0; ne = 0; nseq = 0; tpl_nodes = 0; gf_left = 0; gf_idx = 0; prev_L = -1; meta_ok = false; prev_clean = false; }
+};
+#define POA_PROF(slot) do { const unsigned long long _n = __builtin_readcyclecounter(); acc[slot] += _n - S.pt; S.pt = _n; } while (0)
 
-    for (uint32_t mi = 0; mi < t.n_members; ++mi) {
-        const PoaMember pm = sc.members[t.member_off + mi];
-        const int L = __builtin_amdgcn_readfirstlane((int)pm.len); /* sizes steer every loop below: keep them in scalar registers */
-        n = __builtin_amdgcn_readfirstlane(n); ne = __builtin_amdgcn_readfirstlane(ne);
-        if ((uint32_t)L > M.l_cap) return 2;
+/* Where one member's alignment lies in the matrix (wave-uniform; poa_run sets it up for every member on the matrix path). */
+struct PoaFillPlan {
+    int cols, hs, nch;  /* the member's bases + 1; row stride of the DP matrix; direction-word chunks per row */
+    int jo, gk;         /* group fill: this member's first column in the shared rows; members that open a group fill together (1: none) */
+    bool grp, grp_fill; /* the member's fill is (grp) or is being made as (grp_fill) part of a group fill */
+    bool packed, pad, use_dirs;
+};
+/* group fill: tiers M2 / L, matrix path */
+template <typename HT, int PK, int CM, int LCAP>
+constexpr bool poa_group_tier = CW_POA_GROUP_FILL != 0 && PK != 0 && CM == 0 && sizeof(HT) == 2 && LCAP >= 511;
+
+/* The replay of a repeated member (round 6; cw_poa_q.h has the same in its per-group form): a member that is, base for base, the member aligned just
+   before it -- which changed nothing in the graph but coverage counts -- would make the same fill, walk and path: its merge is that path's coverage
+   counts once more (M.pcur, M.sq still hold path and bases).  Measured on the checker: half of the members of the large tiers' tasks (the short ragged
+   pieces of a window's first and last segment), 2 % of tier S's.  Not under the heaviest-bundle policy (the path's edge weights would have to go up too).
+   true: member pm (L bases) was taken here.  (pm by value: by reference it cost tier M2 ten more spilled registers, tiers G and X twenty and tier L a
+   wave per SIMD, docs/DESIGN_history_r6.md) */
+template <typename HT, int PK, int CM, int LCAP>
+__device__ __forceinline__ bool poa_replay(const PoaMem<HT>& M, PoaSt& S, const PoaMember pm, const int L, const DevBatch& b, const int lane) {
 #if CW_POA_REPLAY
-        if (!CW_CONS_HEAVIEST_BUNDLE && prev_clean && L == prev_L) {
-            const uint32_t* words_ = b.bases + b.seq_word_off[pm.seq];
-            bool same = true;
-            for (int j = lane; j < L; j += 64) same = same && M.sq[j] == (uint8_t)cw_base_at(words_, pm.start + j);
-            if (__ballot(!same) == 0ull) {
-                for (int j = lane; j < L; j += 64) { const int cur = M.pcur[j]; M.ncov[cur] = (uint16_t)(M.ncov[cur] + 1); } /* (a path visits a node once; lane j owns position j, as in the merge) */
-                nseq++;
-                if constexpr (CW_POA_GROUP_FILL != 0 && PK != 0 && CM == 0 && sizeof(HT) == 2 && LCAP >= 511) {
-                    if (gf_left > 0 && meta_ok) { ++gf_idx; --gf_left; } /* its rows of a group fill stay unread */
-                }
-                cw_wave_sync();
-                continue;
-            }
-        }
-#endif
-        {
-            const uint32_t* words = b.bases + b.seq_word_off[pm.seq];
-            for (int j = lane; j < L; j += 64) M.sq[j] = (uint8_t)cw_base_at(words, pm.start + j);
-        }
-        cw_wave_sync();
-        nseq++;
-        prev_clean = false; prev_L = L;
-        if (n == 0) { /* first member: a chain */
-            if ((uint32_t)L > M.n_cap || (uint32_t)L > M.e_cap) return 2;
-            for (int j = lane; j < L; j += 64) {
-                M.nbase[j] = M.sq[j]; M.ncov[j] = 1; M.nalc[j] = 0;
-                M.in_head[j] = j ? (uint16_t)(j - 1) : CW_NONE16; M.in_tail[j] = M.in_head[j];
-                M.indeg[j] = j ? 1 : 0; M.has_out[j] = (j < L - 1) ? 1 : 0;
-                M.r2n[j] = (uint16_t)j; M.n2r[j] = (uint16_t)j;
-                if (j) { M.efrom[j - 1] = (uint16_t)(j - 1); M.enext[j - 1] = CW_NONE16; if (CW_CONS_HEAVIEST_BUNDLE) M.ew[j - 1] = 1; }
-            }
-            n = L; ne = L - 1; tpl_nodes = L; meta_ok = false;
-            cw_wave_sync();
-            continue;
-        }
-        const int cols = L + 1;
-        /* group fill (tiers M2 / L, matrix path): is this member's fill already in the matrix -- filled together with its predecessor, and has no merge
-           since changed the graph's structure (meta_ok) -- or does it open a group with the members behind it? */
-        bool grp = false, grp_fill = false;
-        int jo = 0, gk = 1;
-        if constexpr (CW_POA_GROUP_FILL != 0 && PK != 0 && CM == 0 && sizeof(HT) == 2 && LCAP >= 511) {
-            if (gf_left > 0 && meta_ok) { grp = true; jo = 32 * (++gf_idx); --gf_left; }
-            else {
-                gf_left = 0; gf_idx = 0;
-                if (L <= CW_GF_LC && (uint32_t)((n + 1) * CW_GF_HS) <= M.h_cap && n + 32 <= CW_POA_PK_SPAN) {
-                    while (gk < 4 && mi + (uint32_t)gk < t.n_members && __builtin_amdgcn_readfirstlane((int)sc.members[t.member_off + mi + gk].len) <= CW_GF_LC) ++gk;
-                    if (gk >= 2) { grp = true; grp_fill = true; gf_left = gk - 1; }
-                }
-            }
-        }
-        const bool packed = grp || (PK && cols > 64 && (PK == 1 || n + cols <= CW_POA_PK_SPAN)); /* two columns per lane (int16 tiers, wide rows) */
-        /* pad64 rests on an ordering the HSA memory model does not spell out: a lane beyond the member's columns stores into the first
-           cells of LATER rows, which another lane of the same wave overwrites when that row is finished -- correct iff two stores of one wave to
-           one address commit in issue order (they do on gfx9: one wave's vector memory instructions reach the L2 in order).  -DCW_NO_PAD64 builds
-           the masked variant; tests/test_gpu_variants.py runs both against the oracle. */
-#ifdef CW_NO_PAD64
-        const bool pad = false;
-#else
-        const bool pad = PK != 0 && !packed && M.pad64 && cols <= 64;
-#endif
-        const int hs = grp ? CW_GF_HS : packed ? ((cols + 1) & ~1) : cols;    /* row stride of the DP matrix */
-        if constexpr (WX) { if (lane == 0) atomicMax(&sc.ctr->x_cells, (uint32_t)((n + 1) * hs) * (CW_POA_AFFINE ? 3u : 1u)); } /* the largest alignment tier X was asked for */
-        if ((uint32_t)((n + 1) * hs + (pad ? 64 : 0)) > M.h_cap) return 2;
-
-        /* ---- per-rank metadata (parallel over ranks) ---- */
-        if (!meta_ok) {
-            int run = 0;
-            if (CM == 2 && M.gflag) { /* cw_poa_c.h: which rows the fill also writes to the slab */
-                for (int w = lane; w < (int)(M.n_cap / 32 + 2); w += 64) M.gflag[w] = 0u;
-                cw_wave_sync();
-            }
-            for (int r0 = 0; r0 < n; r0 += 64) {
-                const int r = r0 + lane;
-                const int node = r < n ? M.r2n[r] : 0;
-                const int d = r < n ? M.indeg[node] : 0;
-                const int inc = cw_wave_scan_add(d);
-                const int off = run + inc - d;
-                if (r < n) {
-                    int q = off, first = 0;
-                    bool far_ = false; /* a predecessor more than CW_RING ranks back */
-                    for (uint32_t e = M.in_head[node]; e != CW_NONE16; e = M.enext[e]) {
-                        const int pr = M.n2r[M.efrom[e]] + 1;
-                        if (q == off) first = pr;
-                        M.plist[q++] = (uint16_t)pr;
-                        far_ = far_ || r + 1 - pr > CW_RING;
-                        if (CM == 2 && M.gflag && (r + 1 - pr > CW_RING || q - off > 3)) /* (the fourth in-edge and later: the traceback compares their cells, cw_poa_c.h) */
-                            __hip_atomic_fetch_or((cwc_l32)M.gflag + ((pr - 1) >> 5), 1u << ((pr - 1) & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    }
-                    if (CM == 2 && M.gflag && d > 3) __hip_atomic_fetch_or((cwc_l32)M.gflag + (r >> 5), 1u << (r & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    M.rpred0[r] = (uint16_t)first;
-                    const uint32_t np_ = (uint32_t)(d ? d : 1);
-                    const bool lin_ = np_ == 1u && first == r;
-                    /* cw_poa_c.h row kinds: 0 the rank before (registers); 1 / 2 / 3 one, two, three predecessors that are all in the row
-                       store (any earlier row in tier S; at most CW_RING ranks back in tiers M1 / M2); 5 everything else */
-                    uint32_t kind_ = lin_ ? 0u : 5u;
-                    if (CM != 0 && !lin_ && np_ <= 3u && first != 0 && !far_) kind_ = np_;
-                    if constexpr (WX) { M.rmeta[r] = CW_RM_WORD(M.nbase[node], 0u, lin_, !M.has_out[node], kind_, 0u) | (np_ << 8); M.rx[r] = np_ == 1u ? (uint32_t)first : (uint32_t)off; }
-                    else M.rmeta[r] = CW_RM_WORD(M.nbase[node], np_, lin_, !M.has_out[node], kind_, np_ == 1u ? first : off);
-                }
-                if (!WX && __ballot(r < n && (uint32_t)d > CW_RM_MAX_PRED) != 0ull) return 2; /* more in-edges than the row word's 11 bits count: a node needs more than 2047 distinct sources for that
-                                                                                      (members > 2047; tier G then reports rc 2 and the window stops on CW_WHY_POA) */
-                run += cw_lane_value(inc, 63);
-            }
-            meta_ok = true;
-            cw_wave_sync();
-            if (CM == 2 && M.gflag) { /* the slab bit of the row word: set by the rows that will read the row back from the slab */
-                for (int r = lane; r < n; r += 64) if ((M.gflag[r >> 5] >> (r & 31)) & 1u) M.rmeta[r] |= 16u;
-                cw_wave_sync();
-            }
-            if (M.p2) { /* two and four steps up the first-predecessor chain: a traceback tile gets its eight rows in three reads, not seven */
-                for (int r = lane; r < n; r += 64) {
-                    const int a = M.rpred0[r];
-                    M.p2[r] = a > 0 ? M.rpred0[a - 1] : CW_NONE16;
-                }
-                cw_wave_sync();
-                for (int r = lane; r < n; r += 64) {
-                    const uint32_t b2 = M.p2[r];
-                    M.p4[r] = (b2 != CW_NONE16 && b2 > 0) ? M.p2[b2 - 1] : CW_NONE16;
-                }
-                cw_wave_sync();
-            }
-        }
-        POA_PROF(0);
-
-        /* ---- DP fill, end cell, traceback ---- */
-        for (int j = lane; j < L; j += 64) M.seqrank[j] = CW_NONE16;
-        bool coded = false; /* members of <= 63 bases in tiers S / M1 / M2: the fill records the traceback's decisions (cw_poa_c.h) */
-        if constexpr (CM != 0 && CW_POA_CODES != 0) {
-            if (cols <= 64 && M.codes != nullptr) {
-                if ((uint32_t)(((n + 7) >> 3) * 64) > M.c_cap || (uint32_t)((n + 1) * 64) > M.h_cap) return 2;
-                coded = true;
-            }
-        }
-#ifdef CW_POA_VERIFY
-        const bool run_matrix_path = true;
-#else
-        const bool run_matrix_path = !coded && !CW_POA_AFFINE;
-#endif
-        if constexpr (CW_POA_AFFINE && sizeof(HT) == 4) { /* cw_poa_a.h: fill, end cell and walk back under the affine gap model */
-            int end_row = 0;
-            const int arc = poa_affine_align<HT, WX>(M, n, L, lane, &end_row);
-            if (arc) return arc;
-            POA_PROF(1);
-        }
-        if (run_matrix_path) {
-        PoaMem<HT> V = M; /* the member's view of the matrix: in a group fill its columns begin at jo */
-        V.H = M.H + jo;
-        if (!grp) { for (int j = lane; j < cols; j += 64) M.H[j] = (HT)(CW_POA_SW ? 0 : j * G); }
-        cw_wave_sync();
-        const int nch = grp ? 1 : packed ? (cols + 127) >> 7 : (cols + 63) >> 6; /* direction-word chunks per row */
-        const bool use_dirs = !CW_POA_OV && (uint32_t)(n * nch * (packed ? 2 : 1)) <= M.d_cap; /* (overlap mode: the tile walk below only) */
-        if constexpr (PK != 0) {
-            if (grp) {
-                if constexpr (CW_POA_GROUP_FILL != 0 && CM == 0 && sizeof(HT) == 2 && LCAP >= 511) {
-                    if (grp_fill) { /* this member and the gk - 1 behind it, one per 16-lane row: their bases side by side in M.sq */
-                        for (int x = lane; x < 128; x += 64) { const int g_ = x >> 5, j_ = x & 31; if (g_ >= 1) M.sq[x] = 255; (void)j_; }
-                        if (lane >= L && lane < 32) M.sq[lane] = 255;
-                        uint32_t lens4 = (uint32_t)L;
-                        for (int g_ = 1; g_ < gk; ++g_) {
-                            const PoaMember pg = sc.members[t.member_off + mi + g_];
-                            const uint32_t* wg = b.bases + b.seq_word_off[pg.seq];
-                            if (lane < (int)pg.len) M.sq[32 * g_ + lane] = (uint8_t)cw_base_at(wg, pg.start + lane);
-                            lens4 |= (uint32_t)__builtin_amdgcn_readfirstlane((int)pg.len) << (8 * g_);
-                        }
-                        cw_wave_sync();
-                        poa_fill_pk4<PK == 2>(M, n, lane, use_dirs, lens4);
-                    }
-                }
-            }
-            else if (!packed) {
-                if (cols <= 64) { if (pad) poa_fill<HT, 1, PK == 2, true>(M, n, cols, lane, use_dirs); else poa_fill<HT, 1, PK == 2>(M, n, cols, lane, use_dirs); }
-                else if constexpr (PK == 2 && LCAP > 511) { /* a very large graph in tier L: one column per lane */
-                    if (cols <= 128) poa_fill<HT, 2, PK == 2>(M, n, cols, lane, use_dirs);
-                    else if (cols <= 256) poa_fill<HT, 4, PK == 2>(M, n, cols, lane, use_dirs);
-                    else if (cols <= 512) poa_fill<HT, 8, PK == 2>(M, n, cols, lane, use_dirs);
-                    else poa_fill<HT, 16, PK == 2>(M, n, cols, lane, use_dirs);
-                }
-            }
-            else if (cols <= 128) poa_fill_pk<1, PK == 2>(M, n, cols, hs, lane, use_dirs);
-            else if constexpr (LCAP > 127) {
-                if (cols <= 256) poa_fill_pk<2, PK == 2>(M, n, cols, hs, lane, use_dirs);
-                else if constexpr (LCAP > 255) {
-                    if (cols <= 512) poa_fill_pk<4, PK == 2>(M, n, cols, hs, lane, use_dirs);
-                    else if constexpr (PK == 2 && LCAP > 511) poa_fill_pk<8, PK == 2>(M, n, cols, hs, lane, use_dirs);
-                }
-            }
-        } else if constexpr (WX) { /* tier X: the wide row word; members of more than 2047 bases in blocks of 2048 columns */
-            if (cols <= 64) poa_fill<HT, 1, false, false, true>(M, n, cols, lane, false);
-            else if (cols <= 128) poa_fill<HT, 2, false, false, true>(M, n, cols, lane, false);
-            else if (cols <= 256) poa_fill<HT, 4, false, false, true>(M, n, cols, lane, false);
-            else if (cols <= 512) poa_fill<HT, 8, false, false, true>(M, n, cols, lane, false);
-            else if (cols <= 1024) poa_fill<HT, 16, false, false, true>(M, n, cols, lane, false);
-            else for (int j0 = 0; j0 < cols; j0 += 2048) poa_fill<HT, 32, false, false, true>(M, n, cols, lane, false, j0);
-        } else {
-            if (cols <= 64) poa_fill<HT, 1, PK == 2>(M, n, cols, lane, use_dirs);
-            else if (cols <= 128) poa_fill<HT, 2, PK == 2>(M, n, cols, lane, use_dirs);
-            else if (cols <= 256) poa_fill<HT, 4, PK == 2>(M, n, cols, lane, use_dirs);
-            else if (cols <= 512) poa_fill<HT, 8, PK == 2>(M, n, cols, lane, use_dirs);
-            else if (cols <= 1024) poa_fill<HT, 16, PK == 2>(M, n, cols, lane, use_dirs);
-            else poa_fill<HT, 32, PK == 2>(M, n, cols, lane, use_dirs); /* tier G only: members of up to 2047 bases (round 6) */
-        }
-        POA_PROF(1);
-        if (PK == 2 && LCAP > 511 && lane == 0) { atomicAdd(&sc.ctr->prof[46], (unsigned long long)n * (unsigned long long)nch); atomicAdd(&sc.ctr->prof[47], (unsigned long long)n); }
-
-        /* ---- end cell: best sink in the last column, lowest rank on ties ---- */
-        int bi, bj = L;
-        if (CW_POA_OV) { /* overlap mode: the best cell of a sink's row, columns 1..L; lowest rank, then lowest column on ties */
-            int bs = CW_NEG * 2, br = 0x7FFFFFFF, bc = L;
-            for (int r = lane; r < n; r += 64) {
-                if (!CW_POA_SW && M.has_out[M.r2n[r]]) continue; /* (local mode: any row) */
-                for (int j = 1; j <= L; ++j) {
-                    const int h = V.H[(r + 1) * hs + j];
-                    if (h > bs) { bs = h; br = r; bc = j; } /* ranks ascend within a lane, columns within a row */
-                }
-            }
-            for (int o = 32; o > 0; o >>= 1) {
-                const int os = __shfl_xor(bs, o), orr = __shfl_xor(br, o), oc = __shfl_xor(bc, o);
-                if (os > bs || (os == bs && orr < br)) { bs = os; br = orr; bc = oc; }
-            }
-            bi = __builtin_amdgcn_readfirstlane(br) + 1;
-            bj = __builtin_amdgcn_readfirstlane(bc);
-        } else {
-            int bs = CW_NEG * 2, br = 0x7FFFFFFF;
-            for (int r = lane; r < n; r += 64) {
-                if (M.has_out[M.r2n[r]]) continue;
-                const int h = V.H[(r + 1) * hs + L];
-                if (h > bs) { bs = h; br = r; } /* ranks ascend within a lane */
-            }
-            for (int o = 32; o > 0; o >>= 1) {
-                const int os = __shfl_xor(bs, o), orr = __shfl_xor(br, o);
-                if (os > bs || (os == bs && orr < br)) { bs = os; br = orr; }
-            }
-            bi = __builtin_amdgcn_readfirstlane(br) + 1; /* wave-uniform from here on */
-        }
-
-        /* ---- traceback (wave-uniform); records seqrank[j] = rank aligned to sequence position j ---- */
-        {
-            int i = bi, j = bj;
-            if (use_dirs && M.runs) {
-                /* Direction words: every lane looks at the cell it would reach if the path kept going the way it starts
-                   (diagonal: (i-t, j-t); vertical: (i-t, j); horizontal: (i, j-t)) along a linear stretch of the graph
-                   (first predecessor == previous rank), so one round trip consumes a whole run of equal moves. */
-                while (i > 0) {
-                    const int t = lane;
-                    const int row = i - t;
-                    const bool rvalid = row >= 1;
-                    const int prow = rvalid ? (int)M.rpred0[row - 1] : -1;
-                    const bool linear = rvalid && prow == row - 1;
-                    int cD = 3, cV = 3, cH = 3;
-                    if (rvalid) {
-                        cV = poa_dir_code(M.dirs, row - 1, j + jo, nch, packed);
-                        if (j - t >= 1) cD = poa_dir_code(M.dirs, row - 1, j - t + jo, nch, packed);
-                    }
-                    if (j - t >= 1) cH = poa_dir_code(M.dirs, i - 1, j - t + jo, nch, packed);
-                    const int code0 = __builtin_amdgcn_readlane(cV, 0);
-                    const int pr0 = __builtin_amdgcn_readlane(prow, 0);
-                    if (code0 == 2) {
-                        const unsigned long long bad = ~__ballot(cH == 2);
-                        const int run = bad ? (__ffsll((long long)bad) - 1) : 64;
-                        j -= run;
-                    } else if (code0 == 3) {
-                        /* several predecessors: decide from the cell values (same order of preference) */
-                        int pi, pj;
-                        if (!poa_slow_step<HT, WX>(V, i, j, hs, pr0, lane, &pi, &pj)) return 3;
-                        if (pj != j && pi != i && lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
-                        i = pi; j = pj;
-                    } else if (pr0 != i - 1) {
-                        /* the predecessor is not the previous rank: a single step */
-                        if (code0 == 0) { if (lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1); j--; }
-                        i = pr0;
-                    } else if (code0 == 0) {
-                        const unsigned long long bad = ~__ballot(cD == 0 && linear);
-                        const int run = bad ? (__ffsll((long long)bad) - 1) : 64;
-                        if (t < run) M.seqrank[j - 1 - t] = (uint16_t)(i - 1 - t);
-                        i -= run; j -= run;
-                    } else {
-                        const unsigned long long bad = ~__ballot(cV == 1 && linear);
-                        const int run = bad ? (__ffsll((long long)bad) - 1) : 64;
-                        i -= run;
-                    }
-                }
-            } else if (use_dirs) {
-                /* direction words, one step per LDS round trip: the row's words and its first predecessor together */
-                while (i > 0) {
-                    const int code = poa_dir_code(M.dirs, i - 1, j + jo, nch, packed);
-                    const int pr0 = M.rpred0[i - 1];
-                    if (code == 0) {
-                        if (lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
-                        i = pr0; j--;
-                    } else if (code == 1) {
-                        i = pr0;
-                    } else if (code == 2) {
-                        j--;
-                    } else {
-                        int pi, pj;
-                        if (!poa_slow_step<HT, WX>(V, i, j, hs, pr0, lane, &pi, &pj)) return 3;
-                        if (pj != j && pi != i && lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
-                        i = pi; j = pj;
-                    }
-                }
-            } else {
-                /* no direction words (matrix lives in the slab): walk 8x8 tiles of the matrix held one cell per lane, so
-                   that up to 14 steps cost one memory round trip.  The tile's rows are the first-predecessor chain
-                   i, p(i), p(p(i)), ...; lane (tr,tc) = (lane>>3, lane&7) holds H[chain[tr]][j-tc].  Every lane decides the move
-                   out of its own cell from its three neighbours in the tile (same order of preference as everywhere: diagonal
-                   through the first predecessor, other predecessors, vertical, horizontal); the path is then three ballots
-                   followed on the scalar unit. */
-                const int tr = lane >> 3, tc = lane & 7;
-#ifdef CW_DIAG
-                if (lane == 0 && M.diag) atomicAdd(&M.diag[9], 1ull);
-#endif
-                bool vprobe = false; /* the last trip was seven vertical moves in one column: look down the column */
-                while (i > 0) {
-#ifdef CW_DIAG
-                    if (lane == 0 && M.diag) atomicAdd(&M.diag[7], 1ull);
-#endif
-                    i = __builtin_amdgcn_readfirstlane(i); j = __builtin_amdgcn_readfirstlane(j); /* wave-uniform: keep the walk on the scalar unit */
-                    /* Round 5: the tall tiers align short members against graphs of hundreds of nodes -- most of such a path is ONE vertical run of
-                       hundreds of moves, seven per tile trip.  Inside a run the sixty-four lanes look down the column instead: lane t holds cell
-                       (i - t, j); along a stretch of the graph where every node's only predecessor is the rank before, the cell moves vertically iff
-                       the diagonal candidate does not explain it (the order of preference) and the cell above + gap does.  The leading lanes that
-                       do are consumed at once: up to 63 moves per round trip. */
-                    if (vprobe) {
-                        const int row_t = i - lane;
-                        const uint32_t m_t = row_t >= 1 ? M.rmeta[row_t - 1] : 0u;
-                        int c_t = 0, d_t = 0;
-                        if (row_t >= 0) c_t = (int)V.H[row_t * hs + j];
-                        if (row_t >= 1 && j > 0) d_t = (int)V.H[(row_t - 1) * hs + j - 1];
-                        const int u_t = __shfl_down(c_t, 1); /* the cell above: lane t + 1's */
-                        const int s_t = (j > 0 && (int)M.sq[j - 1] == (int)(m_t & 3u)) ? MS : XS;
-                        bool vert_t = row_t >= 1 && lane < 63 && CW_RM_LIN(m_t) && !(j > 0 && c_t == d_t + s_t) && c_t == u_t + G;
-                        if (CW_POA_SW) vert_t = vert_t && c_t != 0; /* (local mode: the walk stops at a cell of value 0) */
-                        if (CW_POA_OV && j <= 0) vert_t = false;    /* (overlap mode: it stops in column 0: the tile's business) */
-                        const unsigned long long vb = __ballot(vert_t);
-                        const int run = __ffsll((long long)~vb) - 1;
-                        i -= run;
-                        vprobe = run >= 32;
-                        if (run > 0) continue;
-                    }
-                    int row = i;
-                    if (M.p2) { /* tr steps up the chain: 4 + 2 + 1 (unconditional reads and selects, see cw_poa_c.h) */
-                        { uint32_t v = M.p4[row - 1]; asm volatile("" : "+v"(v)); row = (tr & 4) ? (v == CW_NONE16 ? -1 : (int)v) : row; }
-                        { uint32_t v = M.p2[max(row, 1) - 1]; asm volatile("" : "+v"(v)); row = (tr & 2) ? ((row > 0 && v != CW_NONE16) ? (int)v : -1) : row; }
-                        { uint32_t v = M.rpred0[max(row, 1) - 1]; asm volatile("" : "+v"(v)); row = (tr & 1) ? (row > 0 ? (int)v : -1) : row; }
-                    } else {
-                        int ch[8];
-                        ch[0] = i;
-#pragma unroll
-                        for (int q = 1; q < 8; ++q) ch[q] = ch[q - 1] > 0 ? (int)M.rpred0[ch[q - 1] - 1] : -1;
-#pragma unroll
-                        for (int q = 1; q < 8; ++q) row = (tr == q) ? ch[q] : row;
-                    }
-                    const int col = j - tc;
-                    const bool valid = row >= 0 && col >= 0;
-                    const int hv = valid ? (int)V.H[row * hs + col] : 0;
-                    const int meta_r = row >= 1 ? (int)M.rmeta[row - 1] : 0; /* the 8 lanes of a tile row read one word */
-                    const int sq_c = col >= 1 ? (int)M.sq[col - 1] : 255;
-                    const int av = __shfl_down(hv, 9), bv = __shfl_down(hv, 8), lv = __shfl_down(hv, 1); /* (tr+1,tc+1), (tr+1,tc), (tr,tc+1) */
-                    /* 0 diagonal, 1 vertical, 2 horizontal; 3 several predecessors, 4 no move explains the cell, 5 neighbours outside
-                       the tile, 6 the virtual start row */
-                    /* (selects, not branches: as an if-chain this was six nested execution-mask regions per tile) */
-                    const bool c_start = row <= 0 || (CW_POA_OV && col <= 0) || (CW_POA_SW && valid && hv == 0), c_edge = tr == 7 || (tc == 7 && col > 0); /* (overlap mode: the walk stops in column 0; local mode: also at a cell of value 0) */
-                    const bool c_d = col > 0 && hv == av + (sq_c == (meta_r & 3) ? MS : XS);
-                    const bool c_m = (WX ? CW_RMX_NP((uint32_t)meta_r) : CW_RM_NP((uint32_t)meta_r)) != 1, c_v = hv == bv + G, c_h = col > 0 && hv == lv + G;
-                    const int code = c_start ? 6 : c_edge ? 5 : c_d ? 0 : c_m ? 3 : c_v ? 1 : c_h ? 2 : 4;
-                    const unsigned long long m_d = __ballot(code == 0), m_v = __ballot(code == 1), m_h = __ballot(code == 2);
-                    /* the walk, a whole diagonal run per trip: the cells pos, pos + 9, ... are one 64-bit mask; the first of them that does not
-                       move diagonally ends the run (every diagonal of the tile ends in an edge cell, which never does), then one vertical or
-                       horizontal step.  A step at a time on the scalar unit was ~20 instructions for each of up to 14 steps. */
-                    int pos = 0;
-                    unsigned long long on_diag = 0ull;
-                    for (;;) {
-                        const unsigned long long dm = 0x8040201008040201ull << pos;
-                        const unsigned long long stop = ~m_d & dm;
-                        const int first = stop ? __ffsll((long long)stop) - 1 : 63;
-                        on_diag |= dm & ((1ull << first) - 1ull);
-                        pos = first;
-                        if ((m_v >> pos) & 1ull) pos += 8;
-                        else if ((m_h >> pos) & 1ull) pos += 1;
-                        else break;
-                    }
-                    if ((on_diag >> lane) & 1ull) M.seqrank[col - 1] = (uint16_t)(row - 1);
-                    const int end_code = __builtin_amdgcn_readlane(code, pos);
-                    i = __builtin_amdgcn_readlane(row, pos);
-                    j -= pos & 7;
-                    vprobe = pos == 56 && on_diag == 0ull; /* seven vertical moves, no other: probably inside a long run */
-                    if (end_code == 4) return 3;
-                    if (end_code == 6) i = 0;
-                    if (end_code == 3) {
-                        /* a node with several predecessors: one step decided from direct reads (same order of preference) */
-                        const int pr0 = __builtin_amdgcn_readfirstlane((int)M.rpred0[i - 1]);
-                        int pi, pj;
-#ifdef CW_DIAG
-                        if (lane == 0 && M.diag) atomicAdd(&M.diag[8], 1ull);
-#endif
-                        if (!poa_slow_step<HT, WX>(V, i, j, hs, pr0, lane, &pi, &pj)) return 3;
-                        if (pj != j && pi != i && lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
-                        i = pi; j = pj;
-                    }
-                }
-            }
-            /* i == 0: the remaining sequence positions are insertions, already CW_NONE16 */
-        }
-#ifdef CW_POA_VERIFY
-        if (coded) { /* keep the matrix path's answer, then let the recorded-decision path give its own */
-            cw_wave_sync();
-            for (int j = lane; j < L; j += 64) { M.pat[j] = M.seqrank[j]; M.seqrank[j] = CW_NONE16; }
-            if (lane == 0) M.pat[L] = (uint16_t)bi;
-            cw_wave_sync();
-        }
-#endif
-        }
-        if constexpr (CM != 0 && CW_POA_CODES != 0) {
-            if (coded) {
-                cw_wave_sync();
-#ifdef CW_DIAG
-                if (lane == 0 && M.diag) atomicAdd(&M.diag[9], 1ull); /* members on this path */
-#endif
-                const int be_c = poa_fill_c<CM>(M, n, cols, lane);
-                const int bi_c = be_c & 0xFFFF, bj_c = be_c >> 16; /* end row, end column (the last one unless cw_policy.h's overlap mode) */
-                POA_PROF(1);
-                if (!poa_trace_c<CM>(M, n, bi_c, bj_c, cols, lane)) return 3;
-#ifdef CW_POA_VERIFY
-                cw_wave_sync();
-                {
-                    bool bad = false;
-                    for (int j = lane; j < L; j += 64) bad = bad || M.pat[j] != M.seqrank[j];
-                    const unsigned long long bb = __ballot(bad);
-                    const bool bad_bi = (int)M.pat[L] != bi_c;
-                    if (lane == 0) {
-                        atomicAdd(&sc.ctr->prof[120], 1ull);
-                        if (bb != 0ull || bad_bi) {
-                            if (atomicAdd(&sc.ctr->prof[121], 1ull) == 0ull) { /* the first difference: task window, member, columns, rows, end rows */
-                                sc.ctr->prof[122] = ((unsigned long long)t.window << 32) | mi;
-                                sc.ctr->prof[123] = ((unsigned long long)cols << 32) | (unsigned)n;
-                                sc.ctr->prof[124] = ((unsigned long long)M.pat[L] << 32) | (unsigned)bi_c;
-                                sc.ctr->prof[125] = bb;
-                            }
-                        }
-                    }
-                }
-#endif
-            }
-        }
-        cw_wave_sync();
-        POA_PROF(2);
-
-        /* ---- merge the path into the graph: one lane per sequence position ---- */
-        {
-            const int n_old = n;
-            bool edges_added = false;
-            const int chunks = (L + 63) >> 6;
-            /* pass A (last chunk first): resolve existing nodes, find the rank slot of fresh ones */
-            int next_rank = -1; /* rank aligned to the nearest later position that has one */
-            for (int c = chunks - 1; c >= 0; --c) {
-                const int j = c * 64 + lane;
-                const bool act = j < L;
-                const uint32_t rk = act ? M.seqrank[j] : CW_NONE16;
-                const unsigned long long has = __ballot(act && rk != CW_NONE16);
-                /* nearest later aligned position: inside this chunk if any, else carried from later chunks */
-                const unsigned long long later = has & ~(lt_mask | (1ull << lane));
-                const int later_rank = (int)(uint32_t)__shfl((int)rk, later ? (__ffsll((long long)later) - 1) : 0);
-                const int qr = later ? later_rank : next_rank;
-                const int first_rank = (int)(uint32_t)__shfl((int)rk, has ? (__ffsll((long long)has) - 1) : 0);
-                uint32_t cur = CW_NONE16, at = CW_NONE16;
-                if (act) {
-                    const int bcode = M.sq[j];
-                    if (rk != CW_NONE16) {
-                        const int pn = M.r2n[rk];
-                        if (M.nbase[pn] == bcode) cur = (uint32_t)pn;
-                        else {
-                            const int ac = M.nalc[pn];
-                            int last = (int)rk;
-                            for (int a = 0; a < ac; ++a) {
-                                const int v = M.nal[pn * 3 + a];
-                                if (M.nbase[v] == bcode) cur = (uint32_t)v;
-                                last = max(last, (int)M.n2r[v]);
-                            }
-                            if (cur == CW_NONE16) at = (uint32_t)(last + 1); /* new member of pn's column */
-                        }
-                    } else if (qr < 0) {
-                        at = (uint32_t)n_old; /* insertion with no aligned position after it: goes last */
-                    } else {
-                        /* insertion: in front of the column of the next position that is aligned to a node */
-                        const int q = M.r2n[qr];
-                        int first = qr;
-                        for (int a = 0; a < M.nalc[q]; ++a) first = min(first, (int)M.n2r[M.nal[q * 3 + a]]);
-                        at = (uint32_t)first;
-                    }
-                    M.pcur[j] = (uint16_t)cur;
-                    M.pat[j] = (uint16_t)at;
-                }
-                if (has) next_rank = first_rank;
+    if (!CW_CONS_HEAVIEST_BUNDLE && S.prev_clean && L == S.prev_L) {
+        const uint32_t* words_ = b.bases + b.seq_word_off[pm.seq];
+        bool same = true;
+        for (int j = lane; j < L; j += 64) same = same && M.sq[j] == (uint8_t)cw_base_at(words_, pm.start + j);
+        if (__ballot(!same) == 0ull) {
+            for (int j = lane; j < L; j += 64) { const int cur = M.pcur[j]; M.ncov[cur] = (uint16_t)(M.ncov[cur] + 1); } /* (a path visits a node once; lane j owns position j, as in the merge) */
+            S.nseq++;
+            if constexpr (poa_group_tier<HT, PK, CM, LCAP>) {
+                if (S.gf_left > 0 && S.meta_ok) { ++S.gf_idx; --S.gf_left; } /* its rows of a group fill stay unread */
             }
             cw_wave_sync();
-            /* pass B (first chunk first): ids for fresh nodes, node records, coverage */
-            int fresh_total = 0;
-            for (int c = 0; c < chunks; ++c) {
-                const int j = c * 64 + lane;
-                const bool act = j < L;
-                const bool fresh = act && M.pcur[j] == CW_NONE16;
-                const unsigned long long fb = __ballot(fresh);
-                if (fresh) {
-                    const int cur = n_old + fresh_total + __popcll(fb & lt_mask);
-                    if ((uint32_t)cur < M.n_cap) {
-                        M.pcur[j] = (uint16_t)cur;
-                        M.nbase[cur] = M.sq[j]; M.ncov[cur] = 1; M.nalc[cur] = 0;
-                        M.in_head[cur] = CW_NONE16; M.in_tail[cur] = CW_NONE16; M.indeg[cur] = 0; M.has_out[cur] = 0;
-                        const uint32_t rk = M.seqrank[j];
-                        if (rk != CW_NONE16) { /* joins the column of the node it was aligned to */
-                            const int pn = M.r2n[rk];
-                            const int ac = M.nalc[pn];
-                            for (int a = 0; a < ac; ++a) {
-                                const int v = M.nal[pn * 3 + a];
-                                M.nal[cur * 3 + a] = (uint16_t)v;
-                                M.nal[v * 3 + M.nalc[v]] = (uint16_t)cur; M.nalc[v] = (uint8_t)(M.nalc[v] + 1);
-                            }
-                            M.nal[cur * 3 + ac] = (uint16_t)pn; M.nalc[cur] = (uint8_t)(ac + 1);
-                            M.nal[pn * 3 + ac] = (uint16_t)cur; M.nalc[pn] = (uint8_t)(ac + 1);
-                        }
-                    }
-                } else if (act) {
-                    const int cur = M.pcur[j];
-                    M.ncov[cur] = (uint16_t)(M.ncov[cur] + 1);
-                }
-                fresh_total += __popcll(fb);
-            }
-            if ((uint32_t)(n_old + fresh_total) > M.n_cap) return 2;
-            cw_wave_sync();
-            /* pass C: place the fresh nodes in the rank order (one histogram + one prefix sum) */
-            if (fresh_total > 0) {
-                uint32_t* hist = (uint32_t*)M.plist; /* n_old + 1 counters */
-                for (int r = lane; r <= n_old; r += 64) hist[r] = 0;
-                cw_wave_sync();
-                for (int c = 0; c < chunks; ++c) {
-                    const int j = c * 64 + lane;
-                    if (j < L && M.pat[j] != CW_NONE16) atomicAdd(&hist[M.pat[j]], 1u);
-                }
-                cw_wave_sync();
-                int run = 0;
-                for (int r0 = 0; r0 < n_old; r0 += 64) {
-                    const int r = r0 + lane;
-                    const int hcount = r < n_old ? (int)hist[r] : 0;
-                    const int inc = cw_wave_scan_add(hcount);
-                    if (r < n_old) {
-                        const int nr = r + run + inc; /* shifted by every fresh node placed at a slot <= r */
-                        const int v = M.r2n[r];
-                        M.rtmp[nr] = (uint16_t)v;
-                        M.n2r[v] = (uint16_t)nr;
-                    }
-                    run += cw_lane_value(inc, 63);
-                }
-                for (int c = 0; c < chunks; ++c) {
-                    const int j = c * 64 + lane;
-                    if (j < L && M.pat[j] != CW_NONE16) {
-                        const int cur = M.pcur[j];
-                        const int nr = (int)M.pat[j] + (cur - n_old); /* slot + fresh nodes before it on the path */
-                        M.rtmp[nr] = (uint16_t)cur;
-                        M.n2r[cur] = (uint16_t)nr;
-                    }
-                }
-                cw_wave_sync();
-                n = n_old + fresh_total;
-                for (int r = lane; r < n; r += 64) M.r2n[r] = M.rtmp[r];
-                meta_ok = false;
-                cw_wave_sync();
-            }
-            /* pass D: edges between consecutive sequence positions */
-            for (int c = 0; c < chunks; ++c) {
-                const int j = c * 64 + lane;
-                const bool act = j < L && j > 0;
-                int head = 0, cur = 0;
-                bool add = false;
-                if (act) {
-                    head = M.pcur[j - 1]; cur = M.pcur[j];
-                    add = true;
-                    for (uint32_t e = M.in_head[cur]; e != CW_NONE16; e = M.enext[e])
-                        if (M.efrom[e] == (uint16_t)head) { add = false; if (CW_CONS_HEAVIEST_BUNDLE) M.ew[e] = (uint16_t)(M.ew[e] + 1); break; } /* (a path uses an edge once: no two lanes meet here) */
-                }
-                const unsigned long long ab = __ballot(add);
-                const int total = __popcll(ab);
-                if ((uint32_t)(ne + total) > M.e_cap) return 2;
-                if (add) {
-                    const int e = ne + __popcll(ab & lt_mask);
-                    M.efrom[e] = (uint16_t)head; M.enext[e] = CW_NONE16;
-                    if (CW_CONS_HEAVIEST_BUNDLE) M.ew[e] = 1;
-                    const uint32_t tl = M.in_tail[cur];
-                    if (tl == CW_NONE16) M.in_head[cur] = (uint16_t)e; else M.enext[tl] = (uint16_t)e;
-                    M.in_tail[cur] = (uint16_t)e;
-                    M.indeg[cur] = (uint16_t)(M.indeg[cur] + 1);
-                    M.has_out[head] = 1;
-                }
-                if (total) { ne += total; meta_ok = false; edges_added = true; }
-            }
-            cw_wave_sync();
-            prev_clean = n == n_old && !edges_added; /* nothing but coverage counts changed: the next member may be a replay of this one */
+            return true;
         }
-        POA_PROF(3);
     }
+#endif
+    return false;
+}
 
-    /* ---- consensus: column-majority vote, or the heaviest bundle (cw_policy.h CW_POA_CONSENSUS) ---- */
-    uint32_t out_len = 0;
-#if CW_CONS_HEAVIEST_BUNDLE
+/* first member: a chain.  false = beyond this memory class */
+template <typename HT>
+__device__ __forceinline__ bool poa_first_member(const PoaMem<HT>& M, PoaSt& S, const int L, const int lane) {
+    if ((uint32_t)L > M.n_cap || (uint32_t)L > M.e_cap) return false;
+    for (int j = lane; j < L; j += 64) {
+        M.nbase[j] = M.sq[j]; M.ncov[j] = 1; M.nalc[j] = 0;
+        M.in_head[j] = j ? (uint16_t)(j - 1) : CW_NONE16; M.in_tail[j] = M.in_head[j];
+        M.indeg[j] = j ? 1 : 0; M.has_out[j] = (j < L - 1) ? 1 : 0;
+        M.r2n[j] = (uint16_t)j; M.n2r[j] = (uint16_t)j;
+        if (j) { M.efrom[j - 1] = (uint16_t)(j - 1); M.enext[j - 1] = CW_NONE16; if (CW_CONS_HEAVIEST_BUNDLE) M.ew[j - 1] = 1; }
+    }
+    S.n = L; S.ne = L - 1; S.tpl_nodes = L; S.meta_ok = false;
     cw_wave_sync();
-    if (lane == 0) out_len = poa_consensus_hb(M, n, t, sc);
-    out_len = (uint32_t)__shfl((int)out_len, 0);
+    return true;
+}
+
+    /* group fill (tiers M2 / L, matrix path): is this member's fill already in the matrix -- filled together with its predecessor, and has no merge
+       since changed the graph's structure (meta_ok) -- or does it open a group with the members behind it? */
+template <typename HT, int PK, int CM, int LCAP>
+__device__ __forceinline__ void poa_group_plan(const PoaMem<HT>& M, PoaSt& S, PoaFillPlan& P, const PoaTask& t, const DevScratch& sc, const uint32_t mi, const int L) {
+    const int n = S.n;
+    int gf_left = S.gf_left, gf_idx = S.gf_idx;
+    bool grp = false, grp_fill = false;
+    int jo = 0, gk = 1;
+    if constexpr (poa_group_tier<HT, PK, CM, LCAP>) {
+        if (gf_left > 0 && S.meta_ok) { grp = true; jo = 32 * (++gf_idx); --gf_left; }
+        else {
+            gf_left = 0; gf_idx = 0;
+            if (L <= CW_GF_LC && (uint32_t)((n + 1) * CW_GF_HS) <= M.h_cap && n + 32 <= CW_POA_PK_SPAN) {
+                while (gk < 4 && mi + (uint32_t)gk < t.n_members && __builtin_amdgcn_readfirstlane((int)sc.members[t.member_off + mi + gk].len) <= CW_GF_LC) ++gk;
+                if (gk >= 2) { grp = true; grp_fill = true; gf_left = gk - 1; }
+            }
+        }
+    }
+    S.gf_left = gf_left; S.gf_idx = gf_idx;
+    P.grp = grp; P.grp_fill = grp_fill; P.jo = jo; P.gk = gk;
+}
+
+/* The member's rows: part of a group fill or not, two columns per lane or one, stored by all 64 lanes or masked, and the row stride that follows. */
+template <typename HT, int PK, int CM, int LCAP>
+__device__ __forceinline__ void poa_matrix_plan(const PoaMem<HT>& M, PoaSt& S, PoaFillPlan& P, const PoaTask& t, const DevScratch& sc, const uint32_t mi, const int L) {
+    const int n = S.n, cols = L + 1;
+    P.cols = cols;
+    poa_group_plan<HT, PK, CM, LCAP>(M, S, P, t, sc, mi, L);
+    P.packed = P.grp || (PK && cols > 64 && (PK == 1 || n + cols <= CW_POA_PK_SPAN)); /* two columns per lane (int16 tiers, wide rows) */
+    /* pad64 rests on an ordering the HSA memory model does not spell out: a lane beyond the member's columns stores into the first
+       cells of LATER rows, which another lane of the same wave overwrites when that row is finished -- correct iff two stores of one wave to
+       one address commit in issue order (they do on gfx9: one wave's vector memory instructions reach the L2 in order).  -DCW_NO_PAD64 builds
+       the masked variant; tests/test_gpu_variants.py runs both against the oracle. */
+#ifdef CW_NO_PAD64
+    P.pad = false;
 #else
+    P.pad = PK != 0 && !P.packed && M.pad64 && cols <= 64;
+#endif
+    P.hs = P.grp ? CW_GF_HS : P.packed ? ((cols + 1) & ~1) : cols;    /* row stride of the DP matrix */
+}
+
+/* ---- per-rank metadata (parallel over ranks): the predecessor lists, the row words, the slab-row flags of cw_poa_c.h, the chain tables.  false = beyond this memory class ---- */
+template <typename HT, int CM, bool WX>
+__device__ __forceinline__ bool poa_row_meta(const PoaMem<HT>& M, PoaSt& S, const int lane) {
+    const int n = S.n;
+    int run = 0;
+    if (CM == 2 && M.gflag) { /* cw_poa_c.h: which rows the fill also writes to the slab */
+        for (int w = lane; w < (int)(M.n_cap / 32 + 2); w += 64) M.gflag[w] = 0u;
+        cw_wave_sync();
+    }
+    for (int r0 = 0; r0 < n; r0 += 64) {
+        const int r = r0 + lane;
+        const int node = r < n ? M.r2n[r] : 0;
+        const int d = r < n ? M.indeg[node] : 0;
+        const int inc = cw_wave_scan_add(d);
+        const int off = run + inc - d;
+        if (r < n) {
+            int q = off, first = 0;
+            bool far_ = false; /* a predecessor more than CW_RING ranks back */
+            for (uint32_t e = M.in_head[node]; e != CW_NONE16; e = M.enext[e]) {
+                const int pr = M.n2r[M.efrom[e]] + 1;
+                if (q == off) first = pr;
+                M.plist[q++] = (uint16_t)pr;
+                far_ = far_ || r + 1 - pr > CW_RING;
+                if (CM == 2 && M.gflag && (r + 1 - pr > CW_RING || q - off > 3)) /* (the fourth in-edge and later: the traceback compares their cells, cw_poa_c.h) */
+                    __hip_atomic_fetch_or((cwc_l32)M.gflag + ((pr - 1) >> 5), 1u << ((pr - 1) & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            }
+            if (CM == 2 && M.gflag && d > 3) __hip_atomic_fetch_or((cwc_l32)M.gflag + (r >> 5), 1u << (r & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            M.rpred0[r] = (uint16_t)first;
+            const uint32_t np_ = (uint32_t)(d ? d : 1);
+            const bool lin_ = np_ == 1u && first == r;
+            /* cw_poa_c.h row kinds: 0 the rank before (registers); 1 / 2 / 3 one, two, three predecessors that are all in the row
+               store (any earlier row in tier S; at most CW_RING ranks back in tiers M1 / M2); 5 everything else */
+            uint32_t kind_ = lin_ ? 0u : 5u;
+            if (CM != 0 && !lin_ && np_ <= 3u && first != 0 && !far_) kind_ = np_;
+            if constexpr (WX) { M.rmeta[r] = CW_RM_WORD(M.nbase[node], 0u, lin_, !M.has_out[node], kind_, 0u) | (np_ << 8); M.rx[r] = np_ == 1u ? (uint32_t)first : (uint32_t)off; }
+            else M.rmeta[r] = CW_RM_WORD(M.nbase[node], np_, lin_, !M.has_out[node], kind_, np_ == 1u ? first : off);
+        }
+        if (!WX && __ballot(r < n && (uint32_t)d > CW_RM_MAX_PRED) != 0ull) return false; /* more in-edges than the row word's 11 bits count: a node needs more than 2047 distinct sources for that
+                                                                              (members > 2047; tier G then reports rc 2 and the window stops on CW_WHY_POA) */
+        run += cw_lane_value(inc, 63);
+    }
+    S.meta_ok = true;
+    cw_wave_sync();
+    if (CM == 2 && M.gflag) { /* the slab bit of the row word: set by the rows that will read the row back from the slab */
+        for (int r = lane; r < n; r += 64) if ((M.gflag[r >> 5] >> (r & 31)) & 1u) M.rmeta[r] |= 16u;
+        cw_wave_sync();
+    }
+    if (M.p2) { /* two and four steps up the first-predecessor chain: a traceback tile gets its eight rows in three reads, not seven */
+        for (int r = lane; r < n; r += 64) {
+            const int a = M.rpred0[r];
+            M.p2[r] = a > 0 ? M.rpred0[a - 1] : CW_NONE16;
+        }
+        cw_wave_sync();
+        for (int r = lane; r < n; r += 64) {
+            const uint32_t b2 = M.p2[r];
+            M.p4[r] = (b2 != CW_NONE16 && b2 > 0) ? M.p2[b2 - 1] : CW_NONE16;
+        }
+        cw_wave_sync();
+    }
+    return true;
+}
+
+/* ---- DP fill: the one the row width asks for, of the widths this tier compiles (PK, WX, LCAP); a member that opens a group fill first lays the group's bases side by side ---- */
+template <typename HT, int PK, int CM, int LCAP, bool WX>
+__device__ __forceinline__ void poa_fill_matrix(const PoaMem<HT>& M, const int n, const int L, const PoaFillPlan P, const PoaTask& t, const uint32_t mi, const DevBatch& b,
+                                                const DevScratch& sc, const int lane) {
+    const int cols = P.cols, hs = P.hs, gk = P.gk;
+    const bool grp = P.grp, grp_fill = P.grp_fill, packed = P.packed, pad = P.pad, use_dirs = P.use_dirs;
+    if constexpr (PK != 0) {
+        if (grp) {
+            if constexpr (poa_group_tier<HT, PK, CM, LCAP>) {
+                if (grp_fill) { /* this member and the gk - 1 behind it, one per 16-lane row: their bases side by side in M.sq */
+                    for (int x = lane; x < 128; x += 64) { const int g_ = x >> 5, j_ = x & 31; if (g_ >= 1) M.sq[x] = 255; (void)j_; }
+                    if (lane >= L && lane < 32) M.sq[lane] = 255;
+                    uint32_t lens4 = (uint32_t)L;
+                    for (int g_ = 1; g_ < gk; ++g_) {
+                        const PoaMember pg = sc.members[t.member_off + mi + g_];
+                        const uint32_t* wg = b.bases + b.seq_word_off[pg.seq];
+                        if (lane < (int)pg.len) M.sq[32 * g_ + lane] = (uint8_t)cw_base_at(wg, pg.start + lane);
+                        lens4 |= (uint32_t)__builtin_amdgcn_readfirstlane((int)pg.len) << (8 * g_);
+                    }
+                    cw_wave_sync();
+                    poa_fill_pk4<PK == 2>(M, n, lane, use_dirs, lens4);
+                }
+            }
+        }
+        else if (!packed) {
+            if (cols <= 64) { if (pad) poa_fill<HT, 1, PK == 2, true>(M, n, cols, lane, use_dirs); else poa_fill<HT, 1, PK == 2>(M, n, cols, lane, use_dirs); }
+            else if constexpr (PK == 2 && LCAP > 511) { /* a very large graph in tier L: one column per lane */
+                if (cols <= 128) poa_fill<HT, 2, PK == 2>(M, n, cols, lane, use_dirs);
+                else if (cols <= 256) poa_fill<HT, 4, PK == 2>(M, n, cols, lane, use_dirs);
+                else if (cols <= 512) poa_fill<HT, 8, PK == 2>(M, n, cols, lane, use_dirs);
+                else poa_fill<HT, 16, PK == 2>(M, n, cols, lane, use_dirs);
+            }
+        }
+        else if (cols <= 128) poa_fill_pk<1, PK == 2>(M, n, cols, hs, lane, use_dirs);
+        else if constexpr (LCAP > 127) {
+            if (cols <= 256) poa_fill_pk<2, PK == 2>(M, n, cols, hs, lane, use_dirs);
+            else if constexpr (LCAP > 255) {
+                if (cols <= 512) poa_fill_pk<4, PK == 2>(M, n, cols, hs, lane, use_dirs);
+                else if constexpr (PK == 2 && LCAP > 511) poa_fill_pk<8, PK == 2>(M, n, cols, hs, lane, use_dirs);
+            }
+        }
+    } else if constexpr (WX) { /* tier X: the wide row word; members of more than 2047 bases in blocks of 2048 columns */
+        if (cols <= 64) poa_fill<HT, 1, false, false, true>(M, n, cols, lane, false);
+        else if (cols <= 128) poa_fill<HT, 2, false, false, true>(M, n, cols, lane, false);
+        else if (cols <= 256) poa_fill<HT, 4, false, false, true>(M, n, cols, lane, false);
+        else if (cols <= 512) poa_fill<HT, 8, false, false, true>(M, n, cols, lane, false);
+        else if (cols <= 1024) poa_fill<HT, 16, false, false, true>(M, n, cols, lane, false);
+        else for (int j0 = 0; j0 < cols; j0 += 2048) poa_fill<HT, 32, false, false, true>(M, n, cols, lane, false, j0);
+    } else {
+        if (cols <= 64) poa_fill<HT, 1, PK == 2>(M, n, cols, lane, use_dirs);
+        else if (cols <= 128) poa_fill<HT, 2, PK == 2>(M, n, cols, lane, use_dirs);
+        else if (cols <= 256) poa_fill<HT, 4, PK == 2>(M, n, cols, lane, use_dirs);
+        else if (cols <= 512) poa_fill<HT, 8, PK == 2>(M, n, cols, lane, use_dirs);
+        else if (cols <= 1024) poa_fill<HT, 16, PK == 2>(M, n, cols, lane, use_dirs);
+        else poa_fill<HT, 32, PK == 2>(M, n, cols, lane, use_dirs); /* tier G only: members of up to 2047 bases (round 6) */
+    }
+}
+
+/* ---- end cell: best sink in the last column, lowest rank on ties (V: the member's view of the matrix, see poa_run) ---- */
+template <typename HT>
+__device__ __forceinline__ void poa_end_cell(const PoaMem<HT>& M, const PoaMem<HT>& V, const int n, const int L, const int hs, const int lane, int* bi_out, int* bj_out) {
+    int bi, bj = L;
+    if (CW_POA_OV) { /* overlap mode: the best cell of a sink's row, columns 1..L; lowest rank, then lowest column on ties */
+        int bs = CW_NEG * 2, br = 0x7FFFFFFF, bc = L;
+        for (int r = lane; r < n; r += 64) {
+            if (!CW_POA_SW && M.has_out[M.r2n[r]]) continue; /* (local mode: any row) */
+            for (int j = 1; j <= L; ++j) {
+                const int h = V.H[(r + 1) * hs + j];
+                if (h > bs) { bs = h; br = r; bc = j; } /* ranks ascend within a lane, columns within a row */
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const int os = __shfl_xor(bs, o), orr = __shfl_xor(br, o), oc = __shfl_xor(bc, o);
+            if (os > bs || (os == bs && orr < br)) { bs = os; br = orr; bc = oc; }
+        }
+        bi = __builtin_amdgcn_readfirstlane(br) + 1;
+        bj = __builtin_amdgcn_readfirstlane(bc);
+    } else {
+        int bs = CW_NEG * 2, br = 0x7FFFFFFF;
+        for (int r = lane; r < n; r += 64) {
+            if (M.has_out[M.r2n[r]]) continue;
+            const int h = V.H[(r + 1) * hs + L];
+            if (h > bs) { bs = h; br = r; } /* ranks ascend within a lane */
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const int os = __shfl_xor(bs, o), orr = __shfl_xor(br, o);
+            if (os > bs || (os == bs && orr < br)) { bs = os; br = orr; }
+        }
+        bi = __builtin_amdgcn_readfirstlane(br) + 1; /* wave-uniform from here on */
+    }
+    *bi_out = bi; *bj_out = bj;
+}
+
+/* ---- traceback (wave-uniform), three walks from the end cell (bi, bj); each records seqrank[j] = rank aligned to sequence position j and ends at i == 0:
+   the remaining sequence positions are insertions, already CW_NONE16.  false = no move explains a cell ---- */
+template <typename HT, bool WX>
+__device__ __forceinline__ bool poa_trace_runs(const PoaMem<HT>& M, const PoaMem<HT>& V, const PoaFillPlan P, const int bi, const int bj, const int lane) {
+    const int hs = P.hs, nch = P.nch, jo = P.jo;
+    const bool packed = P.packed;
+    int i = bi, j = bj;
+    /* Direction words: every lane looks at the cell it would reach if the path kept going the way it starts
+       (diagonal: (i-t, j-t); vertical: (i-t, j); horizontal: (i, j-t)) along a linear stretch of the graph
+       (first predecessor == previous rank), so one round trip consumes a whole run of equal moves. */
+    while (i > 0) {
+        const int t = lane;
+        const int row = i - t;
+        const bool rvalid = row >= 1;
+        const int prow = rvalid ? (int)M.rpred0[row - 1] : -1;
+        const bool linear = rvalid && prow == row - 1;
+        int cD = 3, cV = 3, cH = 3;
+        if (rvalid) {
+            cV = poa_dir_code(M.dirs, row - 1, j + jo, nch, packed);
+            if (j - t >= 1) cD = poa_dir_code(M.dirs, row - 1, j - t + jo, nch, packed);
+        }
+        if (j - t >= 1) cH = poa_dir_code(M.dirs, i - 1, j - t + jo, nch, packed);
+        const int code0 = __builtin_amdgcn_readlane(cV, 0);
+        const int pr0 = __builtin_amdgcn_readlane(prow, 0);
+        if (code0 == 2) {
+            const unsigned long long bad = ~__ballot(cH == 2);
+            const int run = bad ? (__ffsll((long long)bad) - 1) : 64;
+            j -= run;
+        } else if (code0 == 3) {
+            /* several predecessors: decide from the cell values (same order of preference) */
+            int pi, pj;
+            if (!poa_slow_step<HT, WX>(V, i, j, hs, pr0, lane, &pi, &pj)) return false;
+            if (pj != j && pi != i && lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
+            i = pi; j = pj;
+        } else if (pr0 != i - 1) {
+            /* the predecessor is not the previous rank: a single step */
+            if (code0 == 0) { if (lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1); j--; }
+            i = pr0;
+        } else if (code0 == 0) {
+            const unsigned long long bad = ~__ballot(cD == 0 && linear);
+            const int run = bad ? (__ffsll((long long)bad) - 1) : 64;
+            if (t < run) M.seqrank[j - 1 - t] = (uint16_t)(i - 1 - t);
+            i -= run; j -= run;
+        } else {
+            const unsigned long long bad = ~__ballot(cV == 1 && linear);
+            const int run = bad ? (__ffsll((long long)bad) - 1) : 64;
+            i -= run;
+        }
+    }
+    return true;
+}
+
+template <typename HT, bool WX>
+__device__ __forceinline__ bool poa_trace_dirs(const PoaMem<HT>& M, const PoaMem<HT>& V, const PoaFillPlan P, const int bi, const int bj, const int lane) {
+    const int hs = P.hs, nch = P.nch, jo = P.jo;
+    const bool packed = P.packed;
+    int i = bi, j = bj;
+    /* direction words, one step per LDS round trip: the row's words and its first predecessor together */
+    while (i > 0) {
+        const int code = poa_dir_code(M.dirs, i - 1, j + jo, nch, packed);
+        const int pr0 = M.rpred0[i - 1];
+        if (code == 0) {
+            if (lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
+            i = pr0; j--;
+        } else if (code == 1) {
+            i = pr0;
+        } else if (code == 2) {
+            j--;
+        } else {
+            int pi, pj;
+            if (!poa_slow_step<HT, WX>(V, i, j, hs, pr0, lane, &pi, &pj)) return false;
+            if (pj != j && pi != i && lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
+            i = pi; j = pj;
+        }
+    }
+    return true;
+}
+
+template <typename HT, bool WX>
+__device__ __forceinline__ bool poa_trace_tiles(const PoaMem<HT>& M, const PoaMem<HT>& V, const int hs, const int bi, const int bj, const int lane) {
+    const int G = CW_POA_GAP, MS = CW_POA_MATCH, XS = CW_POA_MISMATCH;
+    int i = bi, j = bj;
+    /* no direction words (matrix lives in the slab): walk 8x8 tiles of the matrix held one cell per lane, so
+       that up to 14 steps cost one memory round trip.  The tile's rows are the first-predecessor chain
+       i, p(i), p(p(i)), ...; lane (tr,tc) = (lane>>3, lane&7) holds H[chain[tr]][j-tc].  Every lane decides the move
+       out of its own cell from its three neighbours in the tile (same order of preference as everywhere: diagonal
+       through the first predecessor, other predecessors, vertical, horizontal); the path is then three ballots
+       followed on the scalar unit. */
+    const int tr = lane >> 3, tc = lane & 7;
+#ifdef CW_DIAG
+    if (lane == 0 && M.diag) atomicAdd(&M.diag[9], 1ull);
+#endif
+    bool vprobe = false; /* the last trip was seven vertical moves in one column: look down the column */
+    while (i > 0) {
+#ifdef CW_DIAG
+        if (lane == 0 && M.diag) atomicAdd(&M.diag[7], 1ull);
+#endif
+        i = __builtin_amdgcn_readfirstlane(i); j = __builtin_amdgcn_readfirstlane(j); /* wave-uniform: keep the walk on the scalar unit */
+        /* Round 5: the tall tiers align short members against graphs of hundreds of nodes -- most of such a path is ONE vertical run of
+           hundreds of moves, seven per tile trip.  Inside a run the sixty-four lanes look down the column instead: lane t holds cell
+           (i - t, j); along a stretch of the graph where every node's only predecessor is the rank before, the cell moves vertically iff
+           the diagonal candidate does not explain it (the order of preference) and the cell above + gap does.  The leading lanes that
+           do are consumed at once: up to 63 moves per round trip. */
+        if (vprobe) {
+            const int row_t = i - lane;
+            const uint32_t m_t = row_t >= 1 ? M.rmeta[row_t - 1] : 0u;
+            int c_t = 0, d_t = 0;
+            if (row_t >= 0) c_t = (int)V.H[row_t * hs + j];
+            if (row_t >= 1 && j > 0) d_t = (int)V.H[(row_t - 1) * hs + j - 1];
+            const int u_t = __shfl_down(c_t, 1); /* the cell above: lane t + 1's */
+            const int s_t = (j > 0 && (int)M.sq[j - 1] == (int)(m_t & 3u)) ? MS : XS;
+            bool vert_t = row_t >= 1 && lane < 63 && CW_RM_LIN(m_t) && !(j > 0 && c_t == d_t + s_t) && c_t == u_t + G;
+            if (CW_POA_SW) vert_t = vert_t && c_t != 0; /* (local mode: the walk stops at a cell of value 0) */
+            if (CW_POA_OV && j <= 0) vert_t = false;    /* (overlap mode: it stops in column 0: the tile's business) */
+            const unsigned long long vb = __ballot(vert_t);
+            const int run = __ffsll((long long)~vb) - 1;
+            i -= run;
+            vprobe = run >= 32;
+            if (run > 0) continue;
+        }
+        int row = i;
+        if (M.p2) { /* tr steps up the chain: 4 + 2 + 1 (unconditional reads and selects, see cw_poa_c.h) */
+            { uint32_t v = M.p4[row - 1]; asm volatile("" : "+v"(v)); row = (tr & 4) ? (v == CW_NONE16 ? -1 : (int)v) : row; }
+            { uint32_t v = M.p2[max(row, 1) - 1]; asm volatile("" : "+v"(v)); row = (tr & 2) ? ((row > 0 && v != CW_NONE16) ? (int)v : -1) : row; }
+            { uint32_t v = M.rpred0[max(row, 1) - 1]; asm volatile("" : "+v"(v)); row = (tr & 1) ? (row > 0 ? (int)v : -1) : row; }
+        } else {
+            int ch[8];
+            ch[0] = i;
+#pragma unroll
+            for (int q = 1; q < 8; ++q) ch[q] = ch[q - 1] > 0 ? (int)M.rpred0[ch[q - 1] - 1] : -1;
+#pragma unroll
+            for (int q = 1; q < 8; ++q) row = (tr == q) ? ch[q] : row;
+        }
+        const int col = j - tc;
+        const bool valid = row >= 0 && col >= 0;
+        const int hv = valid ? (int)V.H[row * hs + col] : 0;
+        const int meta_r = row >= 1 ? (int)M.rmeta[row - 1] : 0; /* the 8 lanes of a tile row read one word */
+        const int sq_c = col >= 1 ? (int)M.sq[col - 1] : 255;
+        const int av = __shfl_down(hv, 9), bv = __shfl_down(hv, 8), lv = __shfl_down(hv, 1); /* (tr+1,tc+1), (tr+1,tc), (tr,tc+1) */
+        /* 0 diagonal, 1 vertical, 2 horizontal; 3 several predecessors, 4 no move explains the cell, 5 neighbours outside
+           the tile, 6 the virtual start row */
+        /* (selects, not branches: as an if-chain this was six nested execution-mask regions per tile) */
+        const bool c_start = row <= 0 || (CW_POA_OV && col <= 0) || (CW_POA_SW && valid && hv == 0), c_edge = tr == 7 || (tc == 7 && col > 0); /* (overlap mode: the walk stops in column 0; local mode: also at a cell of value 0) */
+        const bool c_d = col > 0 && hv == av + (sq_c == (meta_r & 3) ? MS : XS);
+        const bool c_m = (WX ? CW_RMX_NP((uint32_t)meta_r) : CW_RM_NP((uint32_t)meta_r)) != 1, c_v = hv == bv + G, c_h = col > 0 && hv == lv + G;
+        const int code = c_start ? 6 : c_edge ? 5 : c_d ? 0 : c_m ? 3 : c_v ? 1 : c_h ? 2 : 4;
+        const unsigned long long m_d = __ballot(code == 0), m_v = __ballot(code == 1), m_h = __ballot(code == 2);
+        /* the walk, a whole diagonal run per trip: the cells pos, pos + 9, ... are one 64-bit mask; the first of them that does not
+           move diagonally ends the run (every diagonal of the tile ends in an edge cell, which never does), then one vertical or
+           horizontal step.  A step at a time on the scalar unit was ~20 instructions for each of up to 14 steps. */
+        int pos = 0;
+        unsigned long long on_diag = 0ull;
+        for (;;) {
+            const unsigned long long dm = 0x8040201008040201ull << pos;
+            const unsigned long long stop = ~m_d & dm;
+            const int first = stop ? __ffsll((long long)stop) - 1 : 63;
+            on_diag |= dm & ((1ull << first) - 1ull);
+            pos = first;
+            if ((m_v >> pos) & 1ull) pos += 8;
+            else if ((m_h >> pos) & 1ull) pos += 1;
+            else break;
+        }
+        if ((on_diag >> lane) & 1ull) M.seqrank[col - 1] = (uint16_t)(row - 1);
+        const int end_code = __builtin_amdgcn_readlane(code, pos);
+        i = __builtin_amdgcn_readlane(row, pos);
+        j -= pos & 7;
+        vprobe = pos == 56 && on_diag == 0ull; /* seven vertical moves, no other: probably inside a long run */
+        if (end_code == 4) return false;
+        if (end_code == 6) i = 0;
+        if (end_code == 3) {
+            /* a node with several predecessors: one step decided from direct reads (same order of preference) */
+            const int pr0 = __builtin_amdgcn_readfirstlane((int)M.rpred0[i - 1]);
+            int pi, pj;
+#ifdef CW_DIAG
+            if (lane == 0 && M.diag) atomicAdd(&M.diag[8], 1ull);
+#endif
+            if (!poa_slow_step<HT, WX>(V, i, j, hs, pr0, lane, &pi, &pj)) return false;
+            if (pj != j && pi != i && lane == 0) M.seqrank[j - 1] = (uint16_t)(i - 1);
+            i = pi; j = pj;
+        }
+    }
+    return true;
+}
+
+/* ---- merge the path into the graph: one lane per sequence position.  0, or 2 = beyond this memory class ---- */
+template <typename HT>
+__device__ __forceinline__ int poa_merge(const PoaMem<HT>& M, PoaSt& S, const int L, const int lane, const unsigned long long lt_mask) {
+    int n = S.n, ne = S.ne; /* (locals, written back at the end: the passes below keep them in scalar registers) */
+    bool meta_ok = S.meta_ok;
+    const int n_old = n;
+    bool edges_added = false;
+    const int chunks = (L + 63) >> 6;
+    /* pass A (last chunk first): resolve existing nodes, find the rank slot of fresh ones */
+    int next_rank = -1; /* rank aligned to the nearest later position that has one */
+    for (int c = chunks - 1; c >= 0; --c) {
+        const int j = c * 64 + lane;
+        const bool act = j < L;
+        const uint32_t rk = act ? M.seqrank[j] : CW_NONE16;
+        const unsigned long long has = __ballot(act && rk != CW_NONE16);
+        /* nearest later aligned position: inside this chunk if any, else carried from later chunks */
+        const unsigned long long later = has & ~(lt_mask | (1ull << lane));
+        const int later_rank = (int)(uint32_t)__shfl((int)rk, later ? (__ffsll((long long)later) - 1) : 0);
+        const int qr = later ? later_rank : next_rank;
+        const int first_rank = (int)(uint32_t)__shfl((int)rk, has ? (__ffsll((long long)has) - 1) : 0);
+        uint32_t cur = CW_NONE16, at = CW_NONE16;
+        if (act) {
+            const int bcode = M.sq[j];
+            if (rk != CW_NONE16) {
+                const int pn = M.r2n[rk];
+                if (M.nbase[pn] == bcode) cur = (uint32_t)pn;
+                else {
+                    const int ac = M.nalc[pn];
+                    int last = (int)rk;
+                    for (int a = 0; a < ac; ++a) {
+                        const int v = M.nal[pn * 3 + a];
+                        if (M.nbase[v] == bcode) cur = (uint32_t)v;
+                        last = max(last, (int)M.n2r[v]);
+                    }
+                    if (cur == CW_NONE16) at = (uint32_t)(last + 1); /* new member of pn's column */
+                }
+            } else if (qr < 0) {
+                at = (uint32_t)n_old; /* insertion with no aligned position after it: goes last */
+            } else {
+                /* insertion: in front of the column of the next position that is aligned to a node */
+                const int q = M.r2n[qr];
+                int first = qr;
+                for (int a = 0; a < M.nalc[q]; ++a) first = min(first, (int)M.n2r[M.nal[q * 3 + a]]);
+                at = (uint32_t)first;
+            }
+            M.pcur[j] = (uint16_t)cur;
+            M.pat[j] = (uint16_t)at;
+        }
+        if (has) next_rank = first_rank;
+    }
+    cw_wave_sync();
+    /* pass B (first chunk first): ids for fresh nodes, node records, coverage */
+    int fresh_total = 0;
+    for (int c = 0; c < chunks; ++c) {
+        const int j = c * 64 + lane;
+        const bool act = j < L;
+        const bool fresh = act && M.pcur[j] == CW_NONE16;
+        const unsigned long long fb = __ballot(fresh);
+        if (fresh) {
+            const int cur = n_old + fresh_total + __popcll(fb & lt_mask);
+            if ((uint32_t)cur < M.n_cap) {
+                M.pcur[j] = (uint16_t)cur;
+                M.nbase[cur] = M.sq[j]; M.ncov[cur] = 1; M.nalc[cur] = 0;
+                M.in_head[cur] = CW_NONE16; M.in_tail[cur] = CW_NONE16; M.indeg[cur] = 0; M.has_out[cur] = 0;
+                const uint32_t rk = M.seqrank[j];
+                if (rk != CW_NONE16) { /* joins the column of the node it was aligned to */
+                    const int pn = M.r2n[rk];
+                    const int ac = M.nalc[pn];
+                    for (int a = 0; a < ac; ++a) {
+                        const int v = M.nal[pn * 3 + a];
+                        M.nal[cur * 3 + a] = (uint16_t)v;
+                        M.nal[v * 3 + M.nalc[v]] = (uint16_t)cur; M.nalc[v] = (uint8_t)(M.nalc[v] + 1);
+                    }
+                    M.nal[cur * 3 + ac] = (uint16_t)pn; M.nalc[cur] = (uint8_t)(ac + 1);
+                    M.nal[pn * 3 + ac] = (uint16_t)cur; M.nalc[pn] = (uint8_t)(ac + 1);
+                }
+            }
+        } else if (act) {
+            const int cur = M.pcur[j];
+            M.ncov[cur] = (uint16_t)(M.ncov[cur] + 1);
+        }
+        fresh_total += __popcll(fb);
+    }
+    if ((uint32_t)(n_old + fresh_total) > M.n_cap) return 2;
+    cw_wave_sync();
+    /* pass C: place the fresh nodes in the rank order (one histogram + one prefix sum) */
+    if (fresh_total > 0) {
+        uint32_t* hist = (uint32_t*)M.plist; /* n_old + 1 counters */
+        for (int r = lane; r <= n_old; r += 64) hist[r] = 0;
+        cw_wave_sync();
+        for (int c = 0; c < chunks; ++c) {
+            const int j = c * 64 + lane;
+            if (j < L && M.pat[j] != CW_NONE16) atomicAdd(&hist[M.pat[j]], 1u);
+        }
+        cw_wave_sync();
+        int run = 0;
+        for (int r0 = 0; r0 < n_old; r0 += 64) {
+            const int r = r0 + lane;
+            const int hcount = r < n_old ? (int)hist[r] : 0;
+            const int inc = cw_wave_scan_add(hcount);
+            if (r < n_old) {
+                const int nr = r + run + inc; /* shifted by every fresh node placed at a slot <= r */
+                const int v = M.r2n[r];
+                M.rtmp[nr] = (uint16_t)v;
+                M.n2r[v] = (uint16_t)nr;
+            }
+            run += cw_lane_value(inc, 63);
+        }
+        for (int c = 0; c < chunks; ++c) {
+            const int j = c * 64 + lane;
+            if (j < L && M.pat[j] != CW_NONE16) {
+                const int cur = M.pcur[j];
+                const int nr = (int)M.pat[j] + (cur - n_old); /* slot + fresh nodes before it on the path */
+                M.rtmp[nr] = (uint16_t)cur;
+                M.n2r[cur] = (uint16_t)nr;
+            }
+        }
+        cw_wave_sync();
+        n = n_old + fresh_total;
+        for (int r = lane; r < n; r += 64) M.r2n[r] = M.rtmp[r];
+        meta_ok = false;
+        cw_wave_sync();
+    }
+    /* pass D: edges between consecutive sequence positions */
+    for (int c = 0; c < chunks; ++c) {
+        const int j = c * 64 + lane;
+        const bool act = j < L && j > 0;
+        int head = 0, cur = 0;
+        bool add = false;
+        if (act) {
+            head = M.pcur[j - 1]; cur = M.pcur[j];
+            add = true;
+            for (uint32_t e = M.in_head[cur]; e != CW_NONE16; e = M.enext[e])
+                if (M.efrom[e] == (uint16_t)head) { add = false; if (CW_CONS_HEAVIEST_BUNDLE) M.ew[e] = (uint16_t)(M.ew[e] + 1); break; } /* (a path uses an edge once: no two lanes meet here) */
+        }
+        const unsigned long long ab = __ballot(add);
+        const int total = __popcll(ab);
+        if ((uint32_t)(ne + total) > M.e_cap) return 2;
+        if (add) {
+            const int e = ne + __popcll(ab & lt_mask);
+            M.efrom[e] = (uint16_t)head; M.enext[e] = CW_NONE16;
+            if (CW_CONS_HEAVIEST_BUNDLE) M.ew[e] = 1;
+            const uint32_t tl = M.in_tail[cur];
+            if (tl == CW_NONE16) M.in_head[cur] = (uint16_t)e; else M.enext[tl] = (uint16_t)e;
+            M.in_tail[cur] = (uint16_t)e;
+            M.indeg[cur] = (uint16_t)(M.indeg[cur] + 1);
+            M.has_out[head] = 1;
+        }
+        if (total) { ne += total; meta_ok = false; edges_added = true; }
+    }
+    cw_wave_sync();
+    S.prev_clean = n == n_old && !edges_added; /* nothing but coverage counts changed: the next member may be a replay of this one */
+    S.n = n; S.ne = ne; S.meta_ok = meta_ok;
+    return 0;
+}
+
+/* ---- consensus: column-majority vote, one lane per rank, ordered compaction by ballot.  Returns the consensus length; writes what fits ---- */
+template <typename HT>
+__device__ __forceinline__ uint32_t poa_consensus_vote(const PoaMem<HT>& M, const PoaSt& S, const PoaTask& t, const DevScratch& sc, const int lane, const unsigned long long lt_mask) {
+    const int n = S.n, nseq = S.nseq, tpl_nodes = S.tpl_nodes;
+    uint32_t out_len = 0;
     for (int r0 = 0; r0 < n; r0 += 64) {
         const int r = r0 + lane;
         int emit = -1;
@@ -1360,18 +1335,160 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
         if (emit >= 0 && idx < t.out_cap) sc.arena[t.out_off + idx] = CW_ACGT(emit);
         out_len += (uint32_t)__popcll(bal);
     }
+    return out_len;
+}
+
+#ifdef CW_POA_VERIFY
+/* -DCW_POA_VERIFY (tools/verify_codes.sh): a member of the recorded-decision path is aligned by the matrix path first; keep that answer ... */
+template <typename HT>
+__device__ __forceinline__ void poa_verify_keep(const PoaMem<HT>& M, const int L, const int bi, const int lane) { /* keep the matrix path's answer, then let the recorded-decision path give its own */
+    cw_wave_sync();
+    for (int j = lane; j < L; j += 64) { M.pat[j] = M.seqrank[j]; M.seqrank[j] = CW_NONE16; }
+    if (lane == 0) M.pat[L] = (uint16_t)bi;
+    cw_wave_sync();
+}
+/* ... and count the members whose recorded-decision path differs from it */
+template <typename HT>
+__device__ __forceinline__ void poa_verify_compare(const PoaMem<HT>& M, const DevScratch& sc, const PoaTask& t, const uint32_t mi, const int n, const int L, const int bi_c, const int lane) {
+    const int cols = L + 1;
+    cw_wave_sync();
+    bool bad = false;
+    for (int j = lane; j < L; j += 64) bad = bad || M.pat[j] != M.seqrank[j];
+    const unsigned long long bb = __ballot(bad);
+    const bool bad_bi = (int)M.pat[L] != bi_c;
+    if (lane == 0) {
+        atomicAdd(&sc.ctr->prof[CW_PS_VERIFY_MEMBERS], 1ull);
+        if (bb != 0ull || bad_bi) {
+            if (atomicAdd(&sc.ctr->prof[CW_PS_VERIFY_DIFFER], 1ull) == 0ull) { /* the first difference: task window, member, columns, rows, end rows */
+                sc.ctr->prof[CW_PS_VERIFY_WHERE] = ((unsigned long long)t.window << 32) | mi;
+                sc.ctr->prof[CW_PS_VERIFY_SIZE] = ((unsigned long long)cols << 32) | (unsigned)n;
+                sc.ctr->prof[CW_PS_VERIFY_END] = ((unsigned long long)M.pat[L] << 32) | (unsigned)bi_c;
+                sc.ctr->prof[CW_PS_VERIFY_COLS] = bb;
+            }
+        }
+    }
+}
+#endif
+
+/* Returns 1 = done, 2 = a capacity of this memory class was exceeded, 3 = output capacity exceeded / internal. */
+template <typename HT, int PK, int CM = 0, int LCAP = 1023, bool WX = false> /* LCAP: the tier's longest member -- fills for wider rows are not compiled into its kernel; WX: tier X's row word */
+__device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, const DevBatch& b, const DevScratch& sc, const int lane,
+                       unsigned long long (&acc)[6]) {
+    if constexpr (CW_POA_AFFINE && sizeof(HT) != 4) return 2; /* the affine gap model keeps three int32 layers: every task is handed on to the global-memory tier */
+    const int G = CW_POA_GAP;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull; /* for poa_merge and poa_consensus_vote: held across the task, as the compiler then keeps tier M2's spills at three */
+    PoaSt S;
+    S.reset(); S.pt = __builtin_readcyclecounter();
+
+    for (uint32_t mi = 0; mi < t.n_members; ++mi) {
+        const PoaMember pm = sc.members[t.member_off + mi];
+        const int L = __builtin_amdgcn_readfirstlane((int)pm.len); /* sizes steer every loop below: keep them in scalar registers */
+        S.n = __builtin_amdgcn_readfirstlane(S.n); S.ne = __builtin_amdgcn_readfirstlane(S.ne);
+        if ((uint32_t)L > M.l_cap) return 2;
+        if (poa_replay<HT, PK, CM, LCAP>(M, S, pm, L, b, lane)) continue;
+        {
+            const uint32_t* words = b.bases + b.seq_word_off[pm.seq];
+            for (int j = lane; j < L; j += 64) M.sq[j] = (uint8_t)cw_base_at(words, pm.start + j);
+        }
+        cw_wave_sync();
+        S.nseq++;
+        S.prev_clean = false; S.prev_L = L;
+        if (S.n == 0) {
+            if (!poa_first_member(M, S, L, lane)) return 2;
+            continue;
+        }
+        const int n = S.n, cols = L + 1;
+        PoaFillPlan P;
+        poa_matrix_plan<HT, PK, CM, LCAP>(M, S, P, t, sc, mi, L);
+        const int hs = P.hs;
+        if constexpr (WX) { if (lane == 0) atomicMax(&sc.ctr->x_cells, (uint32_t)((n + 1) * hs) * (CW_POA_AFFINE ? 3u : 1u)); } /* the largest alignment tier X was asked for */
+        if ((uint32_t)((n + 1) * hs + (P.pad ? 64 : 0)) > M.h_cap) return 2;
+        if (!S.meta_ok && !poa_row_meta<HT, CM, WX>(M, S, lane)) return 2;
+        POA_PROF(0);
+
+        /* ---- DP fill, end cell, traceback ---- */
+        for (int j = lane; j < L; j += 64) M.seqrank[j] = CW_NONE16;
+        bool coded = false; /* members of <= 63 bases in tiers S / M1 / M2: the fill records the traceback's decisions (cw_poa_c.h) */
+        if constexpr (CM != 0 && CW_POA_CODES != 0) {
+            if (cols <= 64 && M.codes != nullptr) {
+                if ((uint32_t)(((n + 7) >> 3) * 64) > M.c_cap || (uint32_t)((n + 1) * 64) > M.h_cap) return 2;
+                coded = true;
+            }
+        }
+#ifdef CW_POA_VERIFY
+        const bool run_matrix_path = true;
+#else
+        const bool run_matrix_path = !coded && !CW_POA_AFFINE;
+#endif
+        if constexpr (CW_POA_AFFINE && sizeof(HT) == 4) { /* cw_poa_a.h: fill, end cell and walk back under the affine gap model */
+            int end_row = 0;
+            const int arc = poa_affine_align<HT, WX>(M, n, L, lane, &end_row);
+            if (arc) return arc;
+            POA_PROF(1);
+        }
+        if (run_matrix_path) {
+        PoaMem<HT> V = M; /* the member's view of the matrix: in a group fill its columns begin at jo */
+        V.H = M.H + P.jo;
+        if (!P.grp) { for (int j = lane; j < cols; j += 64) M.H[j] = (HT)(CW_POA_SW ? 0 : j * G); }
+        cw_wave_sync();
+        P.nch = P.grp ? 1 : P.packed ? (cols + 127) >> 7 : (cols + 63) >> 6; /* direction-word chunks per row */
+        P.use_dirs = !CW_POA_OV && (uint32_t)(n * P.nch * (P.packed ? 2 : 1)) <= M.d_cap; /* (overlap mode: the tile walk below only) */
+        poa_fill_matrix<HT, PK, CM, LCAP, WX>(M, n, L, P, t, mi, b, sc, lane);
+        POA_PROF(1);
+        if (PK == 2 && LCAP > 511 && lane == 0) { atomicAdd(&sc.ctr->prof[CW_PS_L_CHUNK_ROWS], (unsigned long long)n * (unsigned long long)P.nch); atomicAdd(&sc.ctr->prof[CW_PS_L_ROWS], (unsigned long long)n); }
+        int bi, bj;
+        poa_end_cell(M, V, n, L, hs, lane, &bi, &bj);
+        bool walked; /* direction words a run at a time (tier L) or a step at a time; without them (the matrix lives in the slab) 8x8 tiles of the matrix */
+        if (P.use_dirs && M.runs) walked = poa_trace_runs<HT, WX>(M, V, P, bi, bj, lane);
+        else if (P.use_dirs) walked = poa_trace_dirs<HT, WX>(M, V, P, bi, bj, lane);
+        else walked = poa_trace_tiles<HT, WX>(M, V, hs, bi, bj, lane);
+        if (!walked) return 3;
+#ifdef CW_POA_VERIFY
+        if (coded) poa_verify_keep(M, L, bi, lane);
+#endif
+        }
+        if constexpr (CM != 0 && CW_POA_CODES != 0) {
+            if (coded) {
+                cw_wave_sync();
+#ifdef CW_DIAG
+                if (lane == 0 && M.diag) atomicAdd(&M.diag[9], 1ull); /* members on this path */
+#endif
+                const int be_c = poa_fill_c<CM>(M, n, cols, lane);
+                const int bi_c = be_c & 0xFFFF, bj_c = be_c >> 16; /* end row, end column (the last one unless cw_policy.h's overlap mode) */
+                POA_PROF(1);
+                if (!poa_trace_c<CM>(M, n, bi_c, bj_c, cols, lane)) return 3;
+#ifdef CW_POA_VERIFY
+                poa_verify_compare(M, sc, t, mi, n, L, bi_c, lane);
+#endif
+            }
+        }
+        cw_wave_sync();
+        POA_PROF(2);
+
+        if (const int mrc = poa_merge(M, S, L, lane, lt_mask)) return mrc;
+        POA_PROF(3);
+    }
+
+    /* ---- consensus: column-majority vote, or the heaviest bundle (cw_policy.h CW_POA_CONSENSUS) ---- */
+    uint32_t out_len = 0;
+#if CW_CONS_HEAVIEST_BUNDLE
+    cw_wave_sync();
+    if (lane == 0) out_len = poa_consensus_hb(M, S.n, t, sc);
+    out_len = (uint32_t)__shfl((int)out_len, 0);
+#else
+    out_len = poa_consensus_vote(M, S, t, sc, lane, lt_mask);
 #endif
     if (out_len > t.out_cap) return 3;
     if (lane == 0) sc.seg_len[t.seg_slot] = out_len;
     POA_PROF(4);
-#undef POA_PROF
     return 1;
 }
+#undef POA_PROF
 
-__device__ __forceinline__ void poa_flush_prof(const DevScratch& sc, int base, const unsigned long long (&acc)[6], int lane) {
+__device__ __forceinline__ void poa_flush_prof(const DevScratch& sc, int tier, const unsigned long long (&acc)[6], int lane) {
     if (lane == 0) {
-        for (int q = 0; q < 5; ++q) atomicAdd(&sc.ctr->prof[base + q], acc[q]);
-        atomicMax(&sc.ctr->prof[36 + (base - 8) / 5], acc[5]); /* the longest single task of this tier */
+        for (int q = 0; q < 5; ++q) atomicAdd(&sc.ctr->prof[CW_PS_POA + CW_PS_POA_STRIDE * tier + q], acc[q]);
+        atomicMax(&sc.ctr->prof[CW_PS_LONGEST + tier], acc[5]); /* the longest single task of this tier */
     }
 }
 
@@ -1407,6 +1524,53 @@ __device__ __forceinline__ void poa_producer_done(const DevScratch& sc) {
     }
 }
 
+/* Yielding persistence.  The four tier kernels run side by side and share each CU's LDS; a work-group that loops until its tier's
+   list is empty keeps its LDS for the whole stage, so whichever kernel reaches a CU first owns it (measured: tier S held every CU
+   for 27 ms of a depth-150 batch while the long tasks of tier L had not started).  Here only the LAST persist_wgs work-groups of
+   a grid are persistent; every earlier one takes a chunk of tasks and ends, and the dispatcher hands its LDS to the next pending
+   work-group of ANY tier: the mix on a CU follows the remaining work instead of the launch order.  A wave's slab is therefore
+   not tied to its block index: it claims a free one (there are more slabs than waves the hardware can hold at once). */
+__device__ __forceinline__ uint32_t poa_claim_slab(const DevScratch& sc, const int tier, const int waves) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t gw = 0;
+    if (lane == 0) {
+        const uint32_t n_slots = sc.slots[tier];
+        uint32_t s = (uint32_t)(((unsigned long long)(blockIdx.x * waves + wave) * 2654435761ull) % n_slots);
+        for (;;) {
+            if (__hip_atomic_load(&sc.slot_busy[tier][s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u &&
+                atomicCAS(&sc.slot_busy[tier][s], 0u, 1u) == 0u) break;
+            s = s + 1u == n_slots ? 0u : s + 1u;
+        }
+        gw = s;
+    }
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)gw);
+}
+__device__ __forceinline__ void poa_release_slab(const DevScratch& sc, const int tier, const uint32_t gw) { /* the slab goes back */
+    if ((threadIdx.x & 63) == 0) __hip_atomic_store(&sc.slot_busy[tier][gw], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* A wave's memory in tiers S / M1 / M2 / L: the hot arrays in its part of LDS (lds_wave, lds_bytes), in slab gw the int16 matrix, then tier L's direction words (dc
+   pairs) or the code words of a recorded-decision tier (codes; cw_poa_c.h: its ring and flags behind the hot arrays in LDS), then the cold arrays. */
+template <int NC, int EC, int LC>
+__device__ __forceinline__ PoaMem<int16_t> poa_slab_mem(const DevScratch& sc, const int tier, const uint32_t gw, uint8_t* lds_wave, const uint32_t lds_bytes, const uint32_t dc,
+                                                        const bool cold_edges, const bool codes) {
+    /* the slab is global memory: say so, or every access to the DP matrix is a flat_* instruction (both wait counters, aperture check) */
+    typedef __attribute__((address_space(1))) uint8_t* cw_gptr;
+    uint8_t* my_slab = (uint8_t*)(cw_gptr)(sc.slab[tier] + (size_t)gw * sc.slab_bytes[tier]);
+    int16_t* hslab = (int16_t*)my_slab;
+    unsigned long long* dslab = (unsigned long long*)(my_slab + CW_POA_HSLAB_BYTES(NC, LC));
+    uint8_t* cold = my_slab + CW_POA_HSLAB_BYTES(NC, LC) + CW_POA_DSLAB_BYTES(NC, LC);
+    PoaMem<int16_t> M = poa_carve<int16_t>(lds_wave, NC, EC, LC, (NC + 1) * (LC + 1), dc, hslab, dslab, cold, cold_edges, codes);
+    M.H = hslab; M.dirs = dslab; /* again, without poa_carve's either-or: these two are now provably global pointers */
+    if (codes) {
+        uint8_t* extra = lds_wave + (lds_bytes - CW_POA_RING_BYTES - CW_POA_GFLAG_BYTES(NC));
+        M.ring = (int16_t*)extra; M.gflag = (uint32_t*)(extra + CW_POA_RING_BYTES);
+        M.codes = (uint32_t*)dslab; M.c_cap = (uint32_t)(CW_POA_DSLAB_BYTES(NC, LC) / 4);
+    }
+    M.pad64 = true; /* the slab's matrix area is (NC + 1) x (LC + 1) cells: a matrix of <= 64 columns leaves more than 64 cells free */
+    return M;
+}
+
 /* ---- tier S: one task per wave, work-stealing over the task list ---------------------------------------------------
  * Round 4: laid out like tiers M1 / M2 -- what the fill and the traceback read in LDS (5.9 KB per wave with the row ring of cw_poa_c.h,
  * where graph, merge arrays, a 2048-cell matrix and the code words took 12.9), everything only the merge and the rank bookkeeping touch,
@@ -1421,38 +1585,15 @@ __device__ __forceinline__ void poa_producer_done(const DevScratch& sc) {
 __global__ void __launch_bounds__(64 * CW_POA_WAVES, CW_S_EU) cw_poa_kernel(DevBatch b, DevScratch sc) { /* round 6: four waves per SIMD (128 VGPRs, no scratch): at five (96 VGPRs) the round-5 kernel spilled 28 VGPRs into its row loops, and its measured residency is 3.6 waves per SIMD (LDS-bound) anyway */
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t gw = 0;
-    if (lane == 0) { /* claim a free slab, see cw_poa_slab_kernel */
-        const uint32_t n_slots = sc.slots[0];
-        uint32_t s = (uint32_t)(((unsigned long long)(blockIdx.x * CW_POA_WAVES + wave) * 2654435761ull) % n_slots);
-        for (;;) {
-            if (__hip_atomic_load(&sc.slot_busy[0][s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u &&
-                atomicCAS(&sc.slot_busy[0][s], 0u, 1u) == 0u) break;
-            s = s + 1u == n_slots ? 0u : s + 1u;
-        }
-        gw = s;
-    }
-    gw = (uint32_t)__builtin_amdgcn_readfirstlane((int)gw);
-    typedef __attribute__((address_space(1))) uint8_t* cw_gptr;
-    uint8_t* my_slab = (uint8_t*)(cw_gptr)(sc.slab[0] + (size_t)gw * sc.slab_bytes[0]);
-    int16_t* hslab = (int16_t*)my_slab;
-    unsigned long long* dslab = (unsigned long long*)(my_slab + CW_POA_HSLAB_BYTES(CW_POA_NC, CW_POA_LC));
-    uint8_t* cold = my_slab + CW_POA_HSLAB_BYTES(CW_POA_NC, CW_POA_LC) + CW_POA_DSLAB_BYTES(CW_POA_NC, CW_POA_LC);
-    PoaMem<int16_t> M = poa_carve<int16_t>(lds + (size_t)wave * CW_POA_SLAB_BYTES, CW_POA_NC, CW_POA_EC, CW_POA_LC, (CW_POA_NC + 1) * (CW_POA_LC + 1), 0, hslab, dslab, cold, false, true);
+    const uint32_t gw = poa_claim_slab(sc, 0, CW_POA_WAVES);
+    PoaMem<int16_t> M = poa_slab_mem<CW_POA_NC, CW_POA_EC, CW_POA_LC>(sc, 0, gw, lds + (size_t)wave * CW_POA_SLAB_BYTES, CW_POA_SLAB_BYTES, 0, false, true);
     static_assert(CW_POA_SMAX * (CW_POA_NC + CW_POA_LC) <= CW_POA_I16_BOUND && 4 * CW_POA_SMAX * (CW_POA_NC + 64) <= CW_POA_I16_BOUND, "include/cw_policy.h \"Bounds\": tier S");
-    M.H = hslab; M.dirs = dslab;
-    {
-        uint8_t* extra = lds + (size_t)wave * CW_POA_SLAB_BYTES + (CW_POA_SLAB_BYTES - CW_POA_RING_BYTES - CW_POA_GFLAG_BYTES(CW_POA_NC));
-        M.ring = (int16_t*)extra; M.gflag = (uint32_t*)(extra + CW_POA_RING_BYTES);
-        M.codes = (uint32_t*)dslab; M.c_cap = (uint32_t)(CW_POA_DSLAB_BYTES(CW_POA_NC, CW_POA_LC) / 4);
-    }
-    M.pad64 = true;
     const uint32_t n_tasks = min(sc.ctr->n_tasks, sc.task_cap);
     unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
 #ifdef CW_DIAG
-    M.diag = &sc.ctr->prof[72];
+    M.diag = &sc.ctr->prof[CW_PS_DIAG];
 #endif
-    /* see cw_poa_slab_kernel: all but the last persist_wgs work-groups take a chunk of tasks and end */
+    /* see poa_claim_slab: all but the last persist_wgs work-groups take a chunk of tasks and end */
     const bool yields = blockIdx.x + sc.persist_wgs[0] < gridDim.x;
     uint32_t ran = 0;
     {   /* what outgrew tier Q (its kernel ran before this one on the same stream: the list is complete) */
@@ -1483,8 +1624,8 @@ __global__ void __launch_bounds__(64 * CW_POA_WAVES, CW_S_EU) cw_poa_kernel(DevB
         cw_wave_sync();
         if (yields && ++ran >= CW_POA_CHUNK_S) break;
     }
-    poa_flush_prof(sc, 8, acc, lane);
-    if (lane == 0) __hip_atomic_store(&sc.slot_busy[0][gw], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); /* the slab goes back */
+    poa_flush_prof(sc, 0, acc, lane);
+    poa_release_slab(sc, 0, gw);
     poa_producer_done(sc);
 }
 
@@ -1498,51 +1639,22 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x & 63;
     const int wave = (int)(threadIdx.x >> 6);
-    /* Yielding persistence.  The four tier kernels run side by side and share each CU's LDS; a work-group that loops until its tier's
-       list is empty keeps its LDS for the whole stage, so whichever kernel reaches a CU first owns it (measured: tier S held every CU
-       for 27 ms of a depth-150 batch while the long tasks of tier L had not started).  Here only the LAST persist_wgs work-groups of
-       a grid are persistent; every earlier one takes a chunk of tasks and ends, and the dispatcher hands its LDS to the next pending
-       work-group of ANY tier: the mix on a CU follows the remaining work instead of the launch order.  A wave's slab is therefore
-       not tied to its block index: it claims a free one (there are more slabs than waves the hardware can hold at once). */
-    uint32_t gw = 0;
-    if (lane == 0) {
-        const uint32_t n_slots = sc.slots[TIER];
-        uint32_t s = (uint32_t)(((unsigned long long)(blockIdx.x * WAVES + wave) * 2654435761ull) % n_slots);
-        for (;;) {
-            if (__hip_atomic_load(&sc.slot_busy[TIER][s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u &&
-                atomicCAS(&sc.slot_busy[TIER][s], 0u, 1u) == 0u) break;
-            s = s + 1u == n_slots ? 0u : s + 1u;
-        }
-        gw = s;
-    }
-    gw = (uint32_t)__builtin_amdgcn_readfirstlane((int)gw);
+    const uint32_t gw = poa_claim_slab(sc, TIER, WAVES);
     const bool yields = PASS == 0 && blockIdx.x + sc.persist_wgs[TIER] < gridDim.x;
-    /* the slab is global memory: say so, or every access to the DP matrix is a flat_* instruction (both wait counters, aperture check) */
-    typedef __attribute__((address_space(1))) uint8_t* cw_gptr;
-    uint8_t* my_slab = (uint8_t*)(cw_gptr)(sc.slab[TIER] + (size_t)gw * sc.slab_bytes[TIER]);
-    int16_t* hslab = (int16_t*)my_slab;
-    unsigned long long* dslab = (unsigned long long*)(my_slab + CW_POA_HSLAB_BYTES(NC, LC));
-    uint8_t* cold = my_slab + CW_POA_HSLAB_BYTES(NC, LC) + CW_POA_DSLAB_BYTES(NC, LC);
     constexpr uint32_t slab = TIER <= 2 ? CW_POA_HOT2T_BYTES(TIER, NC, EC, LC) : CW_POA_HOT2L_BYTES(NC, EC, LC);
-    PoaMem<int16_t> M = poa_carve<int16_t>(lds + (size_t)wave * slab, NC, EC, LC, (NC + 1) * (LC + 1), TIER >= 3 ? CW_POA_DSLAB_PAIRS(NC, LC) : 0, hslab, dslab, cold,
-                                           true, TIER == 1 || (TIER == 2 && CW_M2_CODES));
-    M.H = hslab; M.dirs = dslab; /* again, without poa_carve's either-or: these two are now provably global pointers */
+    constexpr bool codes = TIER == 1 || (TIER == 2 && CW_M2_CODES);
+    PoaMem<int16_t> M = poa_slab_mem<NC, EC, LC>(sc, TIER, gw, lds + (size_t)wave * slab, slab, TIER >= 3 ? CW_POA_DSLAB_PAIRS(NC, LC) : 0, true, codes);
     /* include/cw_policy.h "Bounds": the int16 values of this tier's fills stay inside +-CW_POA_I16_BOUND -- by its capacities, or (tier L under scores
        beyond 11) by handing a graph of more nodes than that allows on to tier G */
     static_assert(TIER == 3 || CW_POA_SMAX * (NC + LC) <= CW_POA_I16_BOUND, "matrix / packed fills of this tier");
     static_assert(4 * CW_POA_SMAX * (NC + 64) <= CW_POA_I16_BOUND || !(TIER == 1 || (TIER == 2 && CW_M2_CODES)), "recorded decisions of this tier");
     if constexpr (TIER == 3 && CW_POA_SMAX * (NC + LC) > CW_POA_I16_BOUND) M.n_cap = (uint32_t)(CW_POA_I16_BOUND / CW_POA_SMAX - LC);
     static_assert(TIER != 3 || CW_POA_I16_BOUND / CW_POA_SMAX > LC + 64, "tier L keeps a useful node capacity under these scores");
-    if (TIER <= 2 && CW_POA_HOTC_OF_TIER(TIER)) { /* cw_poa_c.h: ring and flags behind the hot arrays in LDS, code words where tier L keeps its direction words */
-        uint8_t* extra = lds + (size_t)wave * slab + (slab - CW_POA_RING_BYTES - CW_POA_GFLAG_BYTES(NC));
-        M.ring = (int16_t*)extra; M.gflag = (uint32_t*)(extra + CW_POA_RING_BYTES);
-        M.codes = (uint32_t*)dslab; M.c_cap = (uint32_t)(CW_POA_DSLAB_BYTES(NC, LC) / 4);
-    }
+    static_assert(codes == (TIER <= 2 && CW_POA_HOTC_OF_TIER(TIER)), "ring and flags have their room in LDS exactly where members take the recorded-decision path");
     M.runs = TIER >= 3; /* tier L: long graphs against short members, long vertical runs (direction words, whole runs per round trip) */
 #ifdef CW_DIAG
-    M.diag = &sc.ctr->prof[72 + 12 * TIER];
+    M.diag = &sc.ctr->prof[CW_PS_DIAG + CW_PS_DIAG_STRIDE * TIER];
 #endif
-    M.pad64 = true; /* the slab's matrix area is (NC + 1) x (LC + 1) cells: a matrix of <= 64 columns leaves more than 64 cells free */
     /* the large tiers have few, long tasks and share their SIMDs with up to three waves of the small tiers: let them issue first,
        or tier L is still running long after the others have finished (depth 150) */
     if (TIER == 3) __builtin_amdgcn_s_setprio(3);
@@ -1557,13 +1669,13 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
         const unsigned long long _t0 = __builtin_readcyclecounter(), _w0 = wall_clock64();
         /* tier M2's rows are 85 % linear (long graphs, short members): there the matrix fill's 37-instruction row beats the recorded
            decisions' 52, and its slower traceback does not make up for it (measured: 35.8 against 38.5 G wave-cycles per batch) */
-        const int rc = poa_run<int16_t, (TIER < 3 ? 1 : 2), (TIER == 1 || (TIER == 2 && CW_M2_CODES) ? 2 : 0), LC>(M, t, b, sc, lane, acc);
+        const int rc = poa_run<int16_t, (TIER < 3 ? 1 : 2), (codes ? 2 : 0), LC>(M, t, b, sc, lane, acc);
         const unsigned long long _t1 = __builtin_readcyclecounter();
         acc[5] = _t1 - _t0 > acc[5] ? _t1 - _t0 : acc[5];
         if (lane == 0 && sc.task_dbg) { /* inspection aid (CW_TASK_TRACE): when each task of the slab tiers ran (10 ns units since the tier sort), where, and how it ended.
                                            The third word is tier | rc << 8 | pass << 16; its bit 24, which through round 6 marked a task run on four waves, is no longer set */
             uint4 d;
-            d.x = (uint32_t)(_w0 - sc.ctr->prof[41]); d.y = (uint32_t)(wall_clock64() - _w0); d.z = (uint32_t)TIER | ((uint32_t)rc << 8) | ((uint32_t)PASS << 16); d.w = gw;
+            d.x = (uint32_t)(_w0 - sc.ctr->prof[CW_PS_SORT_CLOCK]); d.y = (uint32_t)(wall_clock64() - _w0); d.z = (uint32_t)TIER | ((uint32_t)rc << 8) | ((uint32_t)PASS << 16); d.w = gw;
             sc.task_dbg[ti] = d;
         }
         if (lane == 0) poa_hand_over(sc, t, ti, rc, TIER < 3 ? 3 : 4);
@@ -1623,8 +1735,8 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
     } else if (PASS == 1) {
         /* not used for tiers below L */
     }
-    poa_flush_prof(sc, 8 + 5 * TIER, acc, lane);
-    if (lane == 0) __hip_atomic_store(&sc.slot_busy[TIER][gw], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); /* the slab goes back */
+    poa_flush_prof(sc, TIER, acc, lane);
+    poa_release_slab(sc, TIER, gw);
     if (PASS == 0 && TIER < 3) poa_producer_done(sc);
 }
 
@@ -1677,7 +1789,7 @@ __global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc, uint3
     __shared__ uint32_t tot_c[CW_SORT_CLASSES];
     extern __shared__ __attribute__((aligned(16))) uint8_t cls_lds[]; /* lds_cls bytes (<= CW_SORT_LDS_CLS) */
     const int tier = blockIdx.x == 3 ? 0 : blockIdx.x == 4 ? 5 : 1 + (int)blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63; /* 0 = tier Q's list, 5 = tier H's */
-    if (blockIdx.x == 0 && threadIdx.x == 0) sc.ctr->prof[41] = wall_clock64(); /* time base of the task trace */
+    if (blockIdx.x == 0 && threadIdx.x == 0) sc.ctr->prof[CW_PS_SORT_CLOCK] = wall_clock64(); /* time base of the task trace */
     const uint32_t n = min(sc.ctr->n_tier[tier], sc.list_cap);
     const uint32_t nthr = blockDim.x, nwv = nthr >> 6; /* 4 .. 16 waves: a small work-group finds room beside another batch's persistent kernels */
     uint32_t* list = sc.tier_list[tier];
@@ -1756,7 +1868,7 @@ __global__ void __launch_bounds__(64 * CW_POA_WAVES) cw_poa_big_kernel(DevBatch 
         if (lane == 0) poa_hand_over_x(sc, t, ti, rc);
         cw_wave_sync();
     }
-    poa_flush_prof(sc, 8 + 5 * 4, acc, lane);
+    poa_flush_prof(sc, 4, acc, lane);
 }
 
 /* ---- tier X: what outgrows tier G, on one wave, in tier G's slab pool (launched after tier G on the same stream) -------------------
@@ -1785,7 +1897,7 @@ __global__ void __launch_bounds__(64) cw_poa_x_kernel(DevBatch b, DevScratch sc,
         if (lane == 0) {
             if (sc.task_dbg) { /* CW_TASK_TRACE: tier 6 */
                 uint4 d;
-                d.x = (uint32_t)(w0 - sc.ctr->prof[41]); d.y = (uint32_t)(wall_clock64() - w0); d.z = 6u | ((uint32_t)rc << 8) | (1u << 16); d.w = 0u;
+                d.x = (uint32_t)(w0 - sc.ctr->prof[CW_PS_SORT_CLOCK]); d.y = (uint32_t)(wall_clock64() - w0); d.z = 6u | ((uint32_t)rc << 8) | (1u << 16); d.w = 0u;
                 sc.task_dbg[ti] = d;
             }
             atomicAdd(rc == 1 ? &sc.ctr->x_done : &sc.ctr->x_stopped, 1u);

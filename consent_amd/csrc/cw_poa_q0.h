@@ -425,7 +425,7 @@ __global__ void __launch_bounds__(64 * CW_POAQ_WAVES) cw_poa_q_kernel(DevBatch b
     }
     /* per-phase cycles as the first row of every wave saw them (the four rows of a wave share one instruction stream): slots of tier G,
        which never runs beside tier Q in practice, offset by 28 */
-    if ((threadIdx.x & 63) == 0) for (int q = 0; q < 5; ++q) atomicAdd(&sc.ctr->prof[28 + q], acc[q]);
+    if ((threadIdx.x & 63) == 0) for (int q = 0; q < 5; ++q) atomicAdd(&sc.ctr->prof[CW_PS_POAQ + q], acc[q]);
 }
 
 #endif
