@@ -1,6 +1,6 @@
 """What the job size costs on ONE GPU, for the multi-GPU model of DESIGN.md: the E. coli-scale ONT set (BASELINE configs[3]:
 4.6 Mbp, 30x, ~3.2e5 windows) through cw_run_correction with two workers on device 0 and the job size forced to what N GPUs would get --
-32768 windows (the default on one or two GPUs) down to the floor the driver picks for sixteen workers (windows / (4 x 16)).  Prints, per job
+32768 windows (the default on one or two GPUs) down to the 4096-window floor; the size the driver would plan for N GPUs is asked of the driver itself (a dry run's `windows_per_job`).  Prints, per job
 size, jobs, seconds inside the driver, the serial part (read index) and windows/s; the model for N GPUs is then
     T(N) = t_index + t_first_job_latency + windows / (N x rate(job size of N)).
 GPU box only."""
@@ -118,9 +118,22 @@ for per_job in sizes:
     rows.append({"workers": n_workers, "windows_per_job": per_job, "jobs": jobs, "windows": windows, "s_total": ms_total / 1e3, "s_index": ms_index / 1e3, "windows_per_s_after_index": windows / ((ms_total - ms_index) / 1e3)})
     print(json.dumps(rows[-1]), flush=True)
 base = rows[0]
-print("model: T(N) = s_index + windows / (N x rate(job size)) with the job size the driver picks for 2N workers (windows / (8N), floor 4096, cap 32768)")
+
+
+def drivers_job_size(n):
+    """windows per job the driver itself plans for this set on n GPUs (csrc/cw_driver_plan.h): the `windows_per_job` of its statistics line, from a dry run
+    (CW_DRIVER_DRY=1, the -DCW_TEST_AIDS library: -j n stands for n devices, none is touched)"""
+    import subprocess
+
+    argv = [os.path.join(ROOT, "bin", "CONSENT-correction"), "-a", paf, "-s", "3", "-S", "150", "-l", "500", "-k", "9", "-c", "8", "-A", "2", "-f", "4", "-m", "50", "-j", str(n), "-r", fa, "-M", "150", "-p", "x"]
+    env = dict(os.environ, CW_DRIVER_DRY="1", CW_DRIVER_STATS="1", LD_LIBRARY_PATH=os.path.join(ROOT, "consent_amd", "aids"))
+    out = subprocess.run(argv, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, env=env, check=True)
+    return json.loads([ln for ln in out.stderr.splitlines() if ln.startswith("{")][-1])["windows_per_job"]
+
+
+print("model: T(N) = s_index + windows / (N x rate(job size)) with the job size the driver plans for N devices (its own windows_per_job, from a dry run)")
 for n in (1, 2, 4, 8):
-    want = max(4096, min(32768, base["windows"] // (8 * n) + 1))
+    want = drivers_job_size(n)
     r = min(rows, key=lambda x: abs(x["windows_per_job"] - want))
     t = base["s_index"] + base["windows"] / (n * r["windows_per_s_after_index"])
     print(f"N={n}: job size {want} (measured at {r['windows_per_job']}), modelled {t:.3f} s, speed-up over N=1 {((base['s_index'] + base['windows'] / rows[0]['windows_per_s_after_index']) / t):.2f}x")
