@@ -75,13 +75,14 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
             const uint32_t n_rows = (ab_flags & 4u) ? ch_uni(hdr[4]) : 0u; /* correction rows: what those anchors add to a pair's score, ready-made */
             const uint32_t Ap = cw_ab_ap(A);
             const uint32_t Np = cw_ab_np(N), Nw = (N + 63u) >> 6;
-            const uint32_t* ckey = (const uint32_t*)(blk + CW_AB_HDR);
-            const unsigned long long* gpres = (const unsigned long long*)((const uint8_t*)ckey + cw_ab_align((uint64_t)A * 4));
-            const uint16_t* gdirty = (const uint16_t*)((const uint8_t*)gpres + cw_ab_align((uint64_t)A * Nw * 8));
-            const unsigned long long* gbadm = (const unsigned long long*)((const uint8_t*)gdirty + cw_ab_align((uint64_t)n_dirty * 2));
-            const uint8_t* growid = (const uint8_t*)gbadm + cw_ab_align((uint64_t)A * 8);
-            const uint8_t* gdelta = growid + cw_ab_align((uint64_t)A);
-            const uint16_t* P = (const uint16_t*)(n_rows ? gdelta + (size_t)n_rows * Ap : growid);
+            const CwAbCarve<const uint8_t*> ab = cw_ab_carve(blk, A, N, n_dirty, n_rows); /* the layout idx_hand_over wrote */
+            const uint32_t* ckey = (const uint32_t*)ab.ckey;
+            const unsigned long long* gpres = (const unsigned long long*)ab.pres;
+            const uint16_t* gdirty = (const uint16_t*)ab.dirty;
+            const unsigned long long* gbadm = (const unsigned long long*)ab.badm;
+            const uint8_t* growid = ab.rowid;
+            const uint8_t* gdelta = ab.delta;
+            const uint16_t* P = (const uint16_t*)ab.P;
             const int sup_min = min((int)prm.common_kmers, (int)N / 2); /* correctionMSA.cpp:31 */
             if (lane == 0) { atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_FIX_WINDOWS], (ab_flags & 4u) ? 1ull : 0ull); atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_FIX_ROWS], (unsigned long long)n_rows); atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_BAD_MASKS], has_bm ? 1ull : 0ull); }
             if (lane == 0) { atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_ANCHORS], (unsigned long long)A); atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_DIRTY], (unsigned long long)n_dirty); atomicAdd(&sc.ctr->prof[CW_PS_CHAIN_WINDOWS], 1ull); }
