@@ -97,6 +97,7 @@ enum CwProfSlot : int {
     CW_PS_IDX_STAGE = 55, CW_PS_IDX_EXPORT_SCAN = 56,         /* index kernel detail, cycles */
     CW_PS_IDLE_GAP = 57,                                      /* 10 ns units between the batch before and this one */
     CW_PS_IDX_CAND = 58, CW_PS_IDX_PFILL = 59, CW_PS_IDX_CLEAN = 60, CW_PS_IDX_DIRTY = 61, CW_PS_IDX_PRESENCE = 62,
+    CW_PS_IDX_ROUTE = 63,                                     /* -DCW_TEST_AIDS: the CW_IR_* bits of every window of the batch, ORed (cw_index.h; no cycles: a probe alone in its batch reads its own route) */
     CW_PS_POAH = 64,                                          /* tier H's phases */
     CW_PS_DIAG = 72, CW_PS_DIAG_STRIDE = 12,                  /* -DCW_DIAG: row / trip counts of slab tier t (S .. L) at CW_PS_DIAG + CW_PS_DIAG_STRIDE * t (PoaMem::diag) */
     CW_PS_VERIFY_MEMBERS = 120, CW_PS_VERIFY_DIFFER = 121,    /* -DCW_POA_VERIFY: members compared, members differing ... */
@@ -109,6 +110,7 @@ static_assert(CW_PS_L_CHUNK_ROWS == 46 && CW_PS_L_ROWS == 47, "tier L's fill-row
 static_assert(CW_PS_DIAG == 72 && CW_PS_DIAG_STRIDE == 12 && CW_PS_DIAG + CW_PS_DIAG_STRIDE * 4 == CW_PS_VERIFY_MEMBERS, "diag slots end where the verify slots begin");
 static_assert(CW_PS_VERIFY_MEMBERS == 120 && CW_PS_VERIFY_COLS == 125 && CW_PS_VERIFY_COLS < CW_PROF_SLOTS, "verify slots: tools/verify_codes.py reads them by number");
 static_assert(CW_PS_CHAIN_ANCHORS == 42 && CW_PS_CHAIN_STAGE == 48 && CW_PS_CHAIN_SLOW_CYCLES == 54 && CW_PS_IDX_STAGE == 55 && CW_PS_IDX_PRESENCE == 62, "chain and index slots");
+static_assert(CW_PS_IDX_ROUTE == 63 && CW_PS_IDX_PRESENCE < CW_PS_IDX_ROUTE && CW_PS_IDX_ROUTE < CW_PS_POAH, "the route witness has the one slot between the index phases and tier H's: consent_amd/engine.py reads it by number");
 
 /* Batch-wide counters (one struct in scratch, zeroed before every run). */
 struct BatchCounters {

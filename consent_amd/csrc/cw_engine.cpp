@@ -195,6 +195,7 @@ int plan_and_bind(cw_engine* e, const cw_batch* batch, bool pf_full, ScratchPlan
     e->last_windows = batch->n_windows; e->last_big_slots = big_slots; e->last_ctr_off = p.ctr;
     if (int rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) return rc;
     e->last_tasks_off = p.tasks; e->last_tdbg_off = p.tdbg; e->last_task_cap = p.task_cap;
+    e->last_solid_key_off = p.solid_key; e->last_solid_cnt_off = p.solid_cnt;
     if (!e->step_clock) { CW_HIP(hipMalloc((void**)&e->step_clock, 16)); CW_HIP(hipMemset(e->step_clock, 0, 16)); }
     *sc = bind_scratch(p, (uint8_t*)e->scratch);
     sc->step_clock = e->step_clock;
@@ -560,6 +561,26 @@ int cw_debug_win_info(cw_engine* e, uint32_t n_windows, uint32_t* out16) {
     CW_HIP(hipSetDevice(e->device));
     CW_HIP(hipDeviceSynchronize());
     CW_HIP(hipMemcpy(out16, e->scratch, (size_t)n_windows * sizeof(WinInfo), hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): the index kernel's count table of one window of the last run -- its slice of solid_key / solid_cnt (WinInfo::solid_base,
+ * n_solid): the ascending solid k-mers and their exact pile-wide counts.  *n = the entries the window has; the first min(*n, cap) are copied. */
+int cw_debug_solid_table(cw_engine* e, uint32_t window, uint32_t* keys, uint32_t* counts, uint32_t cap, uint32_t* n) {
+    if (!e || !e->scratch || !n || (cap && (!keys || !counts))) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (window >= e->last_windows) return CW_E_INVALID;
+    CW_HIP(hipSetDevice(e->device));
+    CW_HIP(hipDeviceSynchronize());
+    WinInfo wi;
+    CW_HIP(hipMemcpy(&wi, (const uint8_t*)e->scratch + (size_t)window * sizeof(WinInfo), sizeof(wi), hipMemcpyDeviceToHost));
+    if (wi.n_solid > wi.solid_cap) return CW_E_INVALID; /* (never: the index kernel writes n_solid only when the set fits) */
+    *n = wi.n_solid;
+    const size_t take = wi.n_solid < cap ? wi.n_solid : cap;
+    if (take) {
+        CW_HIP(hipMemcpy(keys, (const uint8_t*)e->scratch + e->last_solid_key_off + (size_t)wi.solid_base * 4, take * 4, hipMemcpyDeviceToHost));
+        CW_HIP(hipMemcpy(counts, (const uint8_t*)e->scratch + e->last_solid_cnt_off + (size_t)wi.solid_base * 4, take * 4, hipMemcpyDeviceToHost));
+    }
     return CW_OK;
 }
 

@@ -48,6 +48,31 @@ typedef __attribute__((address_space(1))) uint16_t* cw_g16w;      /* ... or in t
 #define CW_IDX_STAGE_N 192
 #define CW_IDX_STAGE_WORDS ((CW_IDX_LDS_BYTES - CW_IDX_STAGE_OFF - 16 - CW_IDX_STAGE_N * 8) / 4)
 
+/* Which way a window went, one bit per decision of this file: a -DCW_TEST_AIDS build ORs them into prof[CW_PS_IDX_ROUTE] (the product's kernel has none of
+   it), and a test that names a path asks for its bit (consent_amd/engine.py INDEX_ROUTE, the same table by name; tests/test_index_counts_cpu.py compares the two) */
+enum CwIdxRoute : unsigned {
+    CW_IR_STAGED = 1u << 0,       /* the pile's words are staged in LDS (IdxPile::stw)                        */
+    CW_IR_BYTES_DONE = 1u << 1,   /* idx_count_bytes counted and exported the window (done8)                  */
+    CW_IR_NIBBLES = 1u << 2,      /* idx_count_nibbles was entered                                            */
+    CW_IR_BIG_EX = 1u << 3,       /* ... and redone with the exact table in global memory (big_ex)            */
+    CW_IR_EXPORT_MASKS = 1u << 4, /* the nibble table was exported by idx_export_masks                        */
+    CW_IR_EXPORT_WALK = 1u << 5,  /* ... by idx_export_walk                                                   */
+    CW_IR_REWALK = 1u << 6,       /* ... and some thread walked its words again (mine > CW_EXP_SLOTS || wide) */
+    CW_IR_HASHED = 1u << 7,       /* idx_count_hashed (k > 9)                                                 */
+    CW_IR_HASH_PASSES = 1u << 8,  /* ... in more than one pass over the pile (P_ > 1)                         */
+    CW_IR_HASH_GSORT = 1u << 9,   /* ... its solid set sorted in the work-group's global table (np2 > 16384)  */
+    CW_IR_WIDE = 1u << 10,        /* the wide template layout (IdxLds::wide)                                  */
+    CW_IR_TFIT = 1u << 11,        /* IdxMatrix::tfit                                                          */
+    CW_IR_PG = 1u << 12,          /* IdxMatrix::pg                                                            */
+    CW_IR_HIT_LIST = 1u << 13,    /* idx_hit_list                                                             */
+    CW_IR_USE_BITS = 1u << 14     /* IdxPres::use_bits                                                        */
+};
+#ifdef CW_TEST_AIDS
+#define CW_IDX_ROUTE(ctr, cond, bits) do { if (cond) atomicOr(&(ctr)->prof[CW_PS_IDX_ROUTE], (unsigned long long)(bits)); } while (0)
+#else
+#define CW_IDX_ROUTE(ctr, cond, bits) do { } while (0)
+#endif
+
 /* ------------------------------------------------------------------------------------------------ */
 /* anchor block of one window (index kernel -> chain kernel): sizes in bytes, everything 16-byte aligned */
 __host__ __device__ __forceinline__ uint32_t cw_ab_np(uint32_t N) { uint32_t Np = (N + 1u) & ~1u; if (((Np >> 1) & 1u) == 0u) Np += 2u; return Np; }
@@ -447,6 +472,7 @@ __device__ __forceinline__ bool idx_count_hashed(const IdxLds& L, const IdxPile&
     uint32_t written = 0;
     bool fits = true;
     if (tid < 8) flags[tid] = 0;
+    CW_IDX_ROUTE(sc.ctr, tid == 0, CW_IR_HASHED | (P_ > 1u ? CW_IR_HASH_PASSES : 0u));
     for (uint32_t pass = 0; pass < P_; ++pass) {
         for (uint32_t i = tid; i < HS; i += CW_IDX_THREADS) hs_tab[i] = 0ull;
         __syncthreads();
@@ -494,6 +520,7 @@ __device__ __forceinline__ bool idx_count_hashed(const IdxLds& L, const IdxPile&
     if (!fits) return false;
     if (written > 1) {
         unsigned long long* const sort_tab = np2 <= HS ? hs_tab : idx_wg_scratch(sc);
+        CW_IDX_ROUTE(sc.ctr, tid == 0 && np2 > HS, CW_IR_HASH_GSORT);
         for (uint32_t x = tid; x < np2; x += CW_IDX_THREADS)
             sort_tab[x] = x < written ? (((unsigned long long)sc.solid_key[win.solid_base + x] << 32) | sc.solid_cnt[win.solid_base + x]) : ~0ull;
         __syncthreads();
@@ -839,6 +866,7 @@ __device__ __forceinline__ bool idx_export_walk(const IdxLds& L, const IdxWin& w
     const bool fits = total <= win.solid_cap;
     if (n_first > mine) n_first = mine; /* never wrapped */
     if (fits && (mine > CW_EXP_SLOTS || wide)) { /* more than the register slots hold (deep piles: a few threads per window): this thread walks its words again, in key order */
+        CW_IDX_ROUTE(sc.ctr, true, CW_IR_REWALK);
         uint32_t o = win.solid_base + off;
         for (uint32_t i = 0; i < w_cnt && mine; ++i) {
             const uint32_t wd = w_beg + i;
@@ -884,6 +912,7 @@ __device__ __forceinline__ bool idx_export_nibbles(const IdxLds& L, const IdxWin
     if (prm.solid <= 15u && (nib_words & 4095u) == 0u && NI >= 1u && NI <= 8u) {
         const uint32_t add = (16u - (prm.solid < 15u ? prm.solid : 15u)) * 0x01010101u;
         uint32_t m[8];
+        CW_IDX_ROUTE(sc.ctr, tid == 0, CW_IR_EXPORT_MASKS);
         idx_read_masks<8>(L.tab(), NI, m, [&](const uint32_t v) -> uint32_t { /* bit q = nibble q of v is >= the threshold */
             const uint32_t c = idx_nibble_cand(v, add);
             return (c | (c >> 6) | (c >> 12) | (c >> 18)) & 0xFFu;
@@ -896,7 +925,10 @@ __device__ __forceinline__ bool idx_export_nibbles(const IdxLds& L, const IdxWin
                 if (c == 15u) c += idx_ex_lookup(L.ex(), exg, big_ex, key); /* exactly 15 occurrences leave no entry */
                 return c;
             });
-    } else fits = idx_export_walk(L, win, sc, prm, n_keys, nib_words, exg, big_ex, total, _pt);
+    } else {
+        CW_IDX_ROUTE(sc.ctr, tid == 0, CW_IR_EXPORT_WALK);
+        fits = idx_export_walk(L, win, sc, prm, n_keys, nib_words, exg, big_ex, total, _pt);
+    }
     if (tid == 0) {
         win.wi->n_solid = fits ? total : 0;
         if (!fits) idx_stop(win.wi, sc.ctr, CW_WHY_SOLIDCAP);
@@ -1340,6 +1372,7 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
         const uint32_t N = win.N, L0 = win.L0;
         L.wide = L0 >= k && L0 - k + 1u > 1024u;
         const IdxPile pl = idx_stage_pile(b, L, s0, N);
+        CW_IDX_ROUTE(sc.ctr, tid == 0, (pl.stw ? CW_IR_STAGED : 0u) | (L.wide ? CW_IR_WIDE : 0u));
         CW_PROF_T0();
         /* ================= phase A: counts, and their export ================= */
         if (!direct) {
@@ -1347,8 +1380,10 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
         } else {
             bool done8, big_ex;
             if (!idx_count_bytes(L, pl, win, sc, prm, kmask, n_keys, done8, _pt)) continue;
+            CW_IDX_ROUTE(sc.ctr, tid == 0, done8 ? CW_IR_BYTES_DONE : CW_IR_NIBBLES);
             if (!done8) {
                 if (!idx_count_nibbles(L, pl, win, sc, prm, kmask, nib_words, big_ex, _pt)) continue;
+                CW_IDX_ROUTE(sc.ctr, tid == 0 && big_ex, CW_IR_BIG_EX);
                 if (!idx_export_nibbles(L, win, sc, prm, n_keys, nib_words, big_ex, _pt)) continue;
             }
         }
@@ -1379,10 +1414,12 @@ __global__ void __launch_bounds__(CW_IDX_THREADS) cw_index_kernel(DevBatch b, De
         const uint32_t A = idx_candidates(L, nk0, sup_min);
         CW_PROF(sc.ctr, CW_PS_IDX_CAND, tid == 0);
         M.pg = !M.tfit && idx_matrix_need(A, N, M.Np) > (uint64_t)L.p_cap() * 2;
+        CW_IDX_ROUTE(sc.ctr, tid == 0, (M.tfit ? CW_IR_TFIT : 0u) | (M.pg ? CW_IR_PG : 0u) | (idx_hit_list(M, N) ? CW_IR_HIT_LIST : 0u));
         if (!idx_fill_matrix(L, pl, win, M, sc, k, kmask, A)) continue;
         CW_PROF(sc.ctr, CW_PS_IDX_PFILL, tid == 0);
         /* ================= presence ================= */
         IdxPres ps = idx_presence_carve(L, M, A, N, nk0);
+        CW_IDX_ROUTE(sc.ctr, tid == 0 && ps.use_bits, CW_IR_USE_BITS);
         if (ps.use_bits) {
             ps = idx_classify_sequences(L, win, M, ps, sc, A, _pt);
             CW_PROF(sc.ctr, CW_PS_IDX_DIRTY, tid == 0);

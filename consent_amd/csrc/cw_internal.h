@@ -74,6 +74,7 @@ struct cw_engine {
     uint32_t cap_scale = 1;  /* multiplier of the batch's task / member / arena capacities: grows (x4) after a run that stopped on them (cw_run_device_sync) */
     size_t last_ctr_off = 0; /* where the last run's BatchCounters sit in scratch */
     size_t last_tasks_off = 0, last_tdbg_off = 0;
+    size_t last_solid_key_off = 0, last_solid_cnt_off = 0; /* the last run's solid table (cw_debug_solid_table) */
     uint32_t last_task_cap = 0;
 };
 

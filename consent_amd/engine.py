@@ -138,6 +138,8 @@ def _load(p):
     lib.cw_debug_win_info.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     if hasattr(lib, "cw_debug_tier_x"):  # (a library built before tier X has no such entry)
         lib.cw_debug_tier_x.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "cw_debug_solid_table"):
+        lib.cw_debug_solid_table.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.cw_debug_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.cw_extract_piles_device.argtypes = [C.c_void_p, C.POINTER(ReadSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p]
@@ -169,6 +171,18 @@ def _load(p):
     lib.cw_synth_device.argtypes = [C.c_void_p, C.POINTER(SynthSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _LIBS[p] = lib
     return lib
+
+
+# The index kernel's route witness (csrc/cw_index.h enum CwIdxRoute, the same bits by name; csrc/cw_device.h CW_PS_IDX_ROUTE): which way the windows of
+# the last batch went through cw_index_kernel.  Only the -DCW_TEST_AIDS library writes it.
+INDEX_ROUTE_SLOT = 63
+INDEX_ROUTE = {"staged": 1 << 0, "bytes_done": 1 << 1, "nibbles": 1 << 2, "big_ex": 1 << 3, "export_masks": 1 << 4, "export_walk": 1 << 5, "rewalk": 1 << 6,
+               "hashed": 1 << 7, "hash_passes": 1 << 8, "hash_gsort": 1 << 9, "wide": 1 << 10, "tfit": 1 << 11, "pg": 1 << 12, "hit_list": 1 << 13, "use_bits": 1 << 14}
+
+
+def route_names(bits):
+    """The names of the INDEX_ROUTE bits set in `bits`, for messages."""
+    return sorted(n for n, b in INDEX_ROUTE.items() if bits & b)
 
 
 def _check(lib, rc, what, allow_capacity=False):
@@ -582,6 +596,18 @@ class Engine:
         c = np.zeros(4, np.uint32)
         _check(self.lib, self.lib.cw_debug_tier_x(self.handle, _ptr(c)), "cw_debug_tier_x")
         return {"routed": int(c[0]), "done": int(c[1]), "stopped": int(c[2]), "max_cells": int(c[3])}
+
+    def solid_table(self, w):
+        """cw_debug_solid_table: (keys, counts) of window w of the last run -- the index kernel's ascending solid k-mers and their exact pile-wide counts."""
+        n = C.c_uint32()
+        _check(self.lib, self.lib.cw_debug_solid_table(self.handle, w, None, None, 0, C.byref(n)), "cw_debug_solid_table")
+        keys, counts = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
+        _check(self.lib, self.lib.cw_debug_solid_table(self.handle, w, _ptr(keys), _ptr(counts), len(keys), C.byref(n)), "cw_debug_solid_table")
+        return keys[: n.value], counts[: n.value]
+
+    def index_route(self):
+        """The INDEX_ROUTE bits of the last batch's windows, ORed (a window alone in its batch: its route).  Zero from the product library."""
+        return int(self.profile()[1][INDEX_ROUTE_SLOT])
 
     def win_info(self, n_windows):
         a = np.zeros((n_windows, 16), np.uint32)

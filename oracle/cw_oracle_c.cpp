@@ -82,6 +82,23 @@ int cwo_run(const cw_params* p, const cw_batch* b, const cw_result* r, uint64_t*
     return rc;
 }
 
+/* The pile-wide k-mer counts of one window as window_consensus has them (A4a), those >= solid in ascending key order: *n receives their number, the
+ * first min(*n, cap) go to keys / counts.  What cwo_run reduces to the solid set; here with the numbers. */
+int cwo_counts(const cw_params* p, const cw_batch* b, uint32_t window, uint64_t* keys, uint32_t* counts, uint32_t cap, uint32_t* n) {
+    if (!p || !b || !n || window >= b->n_windows || (cap && (!keys || !counts))) return CW_E_INVALID;
+    Params prm{p->k, p->solid, p->common_kmers, p->min_anchors, p->max_msa};
+    std::vector<std::string> pile;
+    for (uint32_t s = b->win_first_seq[window]; s < b->win_first_seq[window + 1]; ++s) pile.push_back(unpack(b, s));
+    const WindowResult res = window_consensus(pile, prm, nullptr);
+    std::vector<std::pair<uint64_t, uint32_t>> v;
+    for (auto& kv : res.counts)
+        if (kv.second >= prm.solid) v.emplace_back((uint64_t)kv.first, kv.second);
+    std::sort(v.begin(), v.end());
+    *n = (uint32_t)v.size();
+    for (size_t i = 0; i < v.size() && i < cap; ++i) { keys[i] = v[i].first; counts[i] = v[i].second; }
+    return CW_OK;
+}
+
 /* One segment's POA consensus over ASCII strings (A4d). */
 int cwo_poa(const char* const* seqs, const uint32_t* lens, uint32_t n, char* out, uint32_t cap, uint32_t* out_len) {
     std::vector<std::string> v;

@@ -115,6 +115,21 @@ def oracle_run(params, batch, want_solid=True, threads=1):
     return res, dict(zip(STAT_NAMES, (int(x) for x in stats)))
 
 
+def oracle_counts(params, batch, w=0, lib=None):
+    """cwo_counts: (keys, counts) of window w -- the oracle's pile-wide k-mer counts that reach params.solid, ascending by key.  `lib`: another build of
+    the oracle (a ctypes library), default the checker."""
+    o = lib or oracle()
+    o.cwo_counts.argtypes = [C.POINTER(Params), C.POINTER(Batch), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    b = batch.c_struct()
+    n = C.c_uint32()
+    s0, s1 = int(batch.win_first_seq[w]), int(batch.win_first_seq[w + 1])
+    cap = int(batch.seq_len[s0:s1].astype(np.int64).sum()) + 1  # no more different k-mers than bases
+    keys, counts = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+    rc = o.cwo_counts(C.byref(params), C.byref(b), w, _ptr(keys), _ptr(counts), cap, C.byref(n))
+    assert rc == 0 and n.value <= cap, (rc, n.value)
+    return keys[: n.value], counts[: n.value]
+
+
 def oracle_poa(seqs):
     arr = (C.c_char_p * len(seqs))(*[s.encode() for s in seqs])
     lens = np.array([len(s) for s in seqs], np.uint32)

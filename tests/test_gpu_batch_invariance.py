@@ -18,6 +18,7 @@ import consent_amd as ca
 import oracle_lib
 from consent_amd.engine import Batch, Result, alloc_results, synth_host
 from consent_amd.engine import concat_batches as concat
+from index_probes import aids_engine, assert_route, route_alone
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -199,6 +200,18 @@ def test_every_probe_alone_is_the_oracle_or_a_documented_stop(cat, alone):
             exp, _ = oracle_lib.oracle_run(ca.Params(*prm), hb, threads=THREADS)
             assert r.status == int(exp.status[0]) and r.cons == exp.consensus(0), f"{g} / {name}: differs from the oracle"
             assert np.array_equal(r.solid, exp.solid_kmers(0)), f"{g} / {name}: solid set differs from the oracle"
+
+
+def test_the_1024_and_1025_sequence_probes_lie_on_the_two_sides_of_the_hit_list(cat, alone):
+    """The route witness of the test-aid library (consent_amd/engine.py INDEX_ROUTE): the pile of 1024 sequences fills its matrix from the hit list, the one of
+    1025 does not, and neither has a matrix per template k-mer -- so the two probes are the edge their names say."""
+    prm, conf, probes = cat["default"]
+    with aids_engine(*prm, configure=conf) as e:
+        for n, has, lacks in ((1024, "hit_list", "tfit"), (1025, "", "hit_list tfit")):
+            name = f"pile of {n} sequences"
+            res, route = route_alone(e, probes[name][0])
+            assert_route(route, has=has, lacks=lacks, what=name)
+            assert res.consensus(0) == alone[("default", name)].cons
 
 
 def test_probes_among_copies_of_themselves(cat, alone):

@@ -10,6 +10,7 @@ import pytest
 import consent_amd as ca
 import oracle_lib
 from consent_amd.engine import concat_batches, synth_host
+from index_probes import aids_engine, assert_route, route_alone
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -87,6 +88,10 @@ def test_large_k_on_deep_piles_uses_the_hashed_count_path(engines):
     got = engines(*prm).run(hb)
     exp, _ = oracle_lib.oracle_run(ca.Params(*prm), hb, threads=os.cpu_count() or 1)
     assert_same(got, exp, 12, "k=12 d150")
+    with aids_engine(*prm) as e:  # the route witness of the test-aid library: the window did take the hash table, in several passes
+        one, route = route_alone(e, hb, 0)
+        assert_same(one, exp, 1, "k=12 d150, test-aid library")
+        assert_route(route, has="hashed hash_passes", lacks="bytes_done nibbles", what="k=12 d150")
 
 
 def test_synthetic_ont_profile_matches_oracle(engines):
@@ -144,6 +149,11 @@ def test_high_identity_deep_piles_use_the_global_anchor_matrix(engines):
     exp, _ = oracle_lib.oracle_run(ca.Params(*prm), hb, threads=3)
     assert_same(got, exp, len(piles), "high identity")
     assert all(int(x) == ca.WIN_CONSENSUS for x in got.status[:3])
+    with aids_engine(*prm) as e:  # the route witness: no matrix per template k-mer in any of the three, and the two piles of 151 sequences (~490 anchors x 154
+        for w in range(3):        # positions x 2 bytes against 107 776 of LDS) have theirs in global memory; the third, of 120 sequences, sits near that bound
+            one, route = route_alone(e, hb, w)
+            assert_route(route, lacks="tfit", has="pg hit_list" if w < 2 else "hit_list", what=f"high identity, pile {w}")
+            assert one.consensus(0) == exp.consensus(w)
 
 
 @pytest.mark.parametrize("occ", [254, 255, 256, 257, 300, 511, 512, 513, 1030])
@@ -173,6 +183,10 @@ def test_byte_counters_hand_over_exactly_at_256_occurrences(engines, occ):
     got = engines(*prm).run(hb)
     exp, _ = oracle_lib.oracle_run(ca.Params(*prm), hb, threads=4)
     assert_same(got, exp, 2, f"{occ} occurrences")
+    with aids_engine(*prm) as e:  # the route witness: the bytes finish the window up to 255 occurrences, the nibbles from 256 on
+        one, route = route_alone(e, hb, 0)
+        assert_same(one, exp, 1, f"{occ} occurrences, test-aid library")
+        assert_route(route, has="bytes_done" if occ <= 255 else "nibbles", lacks="nibbles" if occ <= 255 else "bytes_done", what=f"{occ} occurrences")
 
 
 def test_out_of_order_anchors_in_most_of_a_deep_pile(engines):
@@ -233,6 +247,11 @@ def test_pile_layout_in_memory_does_not_matter(engines):
     assert_same(b, a, len(piles), "layout")
     exp, _ = oracle_lib.oracle_run(ca.Params(*prm), hb, threads=3)
     assert_same(a, exp, len(piles), "layout/oracle")
+    with aids_engine(*prm) as e:  # the route witness (the batch's windows ORed): every packed pile is staged, no shuffled one is
+        assert_same(e.run(hb), exp, len(piles), "layout, test-aid library")
+        assert_route(e.index_route(), has="staged", what="packed batch")
+        assert_same(e.run(shuffled), exp, len(piles), "layout, shuffled, test-aid library")
+        assert_route(e.index_route(), lacks="staged", what="shuffled batch")
 
 
 def test_very_deep_piles_score_chains_without_presence_bitsets(engines):
@@ -249,6 +268,9 @@ def test_very_deep_piles_score_chains_without_presence_bitsets(engines):
     exp, _ = oracle_lib.oracle_run(ca.Params(*prm), hb, threads=2)
     assert_same(got, exp, len(piles), "very deep")
     assert all(int(x) == ca.WIN_CONSENSUS for x in got.status[:2])
+    with aids_engine(*prm) as e:  # the route witness: no presence bitsets (and no hit list: a list entry holds the sequence in ten bits)
+        assert_same(e.run(hb), exp, len(piles), "very deep, test-aid library")
+        assert_route(e.index_route(), lacks="use_bits hit_list tfit", what="very deep")
 
 
 def test_long_and_outlier_segments_exercise_all_tiers(engines):
