@@ -47,7 +47,6 @@ constexpr size_t lds_tier_q(uint32_t waves) { return (size_t)CW_POAQ_TASK_BYTES 
 constexpr size_t lds_tier_h(uint32_t waves) { return (size_t)CW_POAH_TASK_BYTES * 2 * waves; } /* two tasks per wave; six waves at most: cw_poa_h_kernel's launch bounds */
 constexpr size_t kLdsFinish = (size_t)CW_FIN_SLAB * CW_FIN_WAVES, kLdsFinishBig = CW_FIN_SLAB_OF(0);
 constexpr size_t kLdsStitch = (size_t)CW_ST_WAVES * CW_ST_SLAB; /* what the wide re-assembly kernel needs (it is given more: stitch_lds_one) */
-constexpr size_t kLdsStitchNarrow = (size_t)CW_STN_WAVES * CW_ST_SLAB_OF(CW_STN_QMAX, CW_STN_RMAX);
 
 /* tiers M1, M2 and L are instances of cw_poa_slab_kernel: a tier's template arguments and the LDS of its work-group, PASS 0 = its own list, 1 = the overflow pass */
 template <int NC, int EC, int LC, int WAVES, int TIER, size_t LDS>
@@ -106,12 +105,7 @@ int set_kernel_attributes(const hipDeviceProp_t& prop) {
         allow(TierM1::kernel<0>(), TierM1::lds) && allow(TierM2::kernel<0>(), TierM2::lds) && allow(TierL::kernel<0>(), TierL::lds) &&
         allow(TierM1::kernel<1>(), TierM1::lds) && allow(TierM2::kernel<1>(), TierM2::lds) && allow(TierL::kernel<1>(), TierL::lds) &&
         allow((const void*)cw_finish_kernel<CW_FIN_CB, CW_FIN_WAVES, false>, kLdsFinish) && allow((const void*)cw_finish_kernel<CW_FIN_CB_BIG, 1, true>, kLdsFinishBig) &&
-        allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES, false>, lds_st) &&
-#ifdef CW_TEST_AIDS
-        allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES, true>, lds_st) &&
-        allow((const void*)cw_stitch_kernel<CW_STN_QMAX, CW_STN_RMAX, 5, CW_STN_WAVES, false>, kLdsStitchNarrow) &&
-#endif
-        true;
+        allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES>, lds_st);
     return ok ? CW_OK : CW_E_NO_DEVICE;
 }
 
@@ -745,7 +739,7 @@ int cw_stitch_device(cw_engine* e, const cw_read_set* reads, const cw_stitch_rea
     const size_t trace_bytes = want_trace ? (size_t)batch->n_windows * 32 : 0;
     int rc = ensure(&e->xscratch, &e->xscratch_bytes, 256 + trace_bytes + (size_t)n_reads * 4);
     if (rc) return rc;
-    CW_HIP(hipMemsetAsync(e->xscratch, 0, 16, st));
+    CW_HIP(hipMemsetAsync(e->xscratch, 0, 16, st)); /* a.cursor: three words (cw_stitch.h) */
     StitchArgs a;
     a.order = (uint32_t*)((uint8_t*)e->xscratch + 256 + trace_bytes);
     a.trace = want_trace ? (uint32_t*)((uint8_t*)e->xscratch + 256) : nullptr;
@@ -761,32 +755,17 @@ int cw_stitch_device(cw_engine* e, const cw_read_set* reads, const cw_stitch_rea
        faster alone on its SIMD (measured with the register count deciding it: 55.3 ms per job at one wave per SIMD, 60.5 at two).  The kernel
        fits two per CU by registers and LDS; asking for more than half of the LDS keeps the second one off (CW_STITCH_TWO_PER_CU=1: don't). */
     const size_t lds_one = CW_AID_ENV("CW_STITCH_TWO_PER_CU") ? 0 : stitch_lds_one(e->prop);
-    const size_t lds = kLdsStitch > lds_one ? kLdsStitch : lds_one, lds_n = kLdsStitchNarrow;
+    const size_t lds = kLdsStitch > lds_one ? kLdsStitch : lds_one;
     uint32_t wgs = (n_reads + CW_ST_WAVES - 1) / CW_ST_WAVES;
     if (wgs > CW_ST_MAX_WGS) wgs = CW_ST_MAX_WGS;
-    /* the narrow kernel holds four work-groups of four waves per CU (29 KB of LDS each, <= 128 VGPRs) */
-    uint32_t wgs_n = (n_reads + CW_STN_WAVES - 1) / CW_STN_WAVES;
-    if (wgs_n > (uint32_t)e->cus * 4u) wgs_n = (uint32_t)e->cus * 4u;
-    /* Opt-in (CW_STITCH_NARROW=1).  Measured on the E. coli-scale ONT-profile set (10 jobs of 32768 windows, rocprofv3): the narrow kernel takes
-       63 ms per job where the wide one takes ~75 -- a launch lasts as long as its longest read's serial chain of windows (a 30 kbp read: 66
-       windows), which twice the resident waves do not shorten -- and the reads it hands on (a consensus above 640 in any of their windows)
-       cost a second such tail, 51 ms: 114 ms per job against 75.  DESIGN.md "Round 3". */
-    const bool narrow = CW_AID_ENV("CW_STITCH_NARROW") && (uint64_t)window_size + 2ull * window_overlap <= CW_STN_RMAX;
-    /* several waves per read (cw_stitch.h, st_sweep_sys): one read per work-group of five waves */
-    const bool sys = !narrow && CW_AID_ENV("CW_STITCH_SYS") && (uint64_t)window_size + 2ull * window_overlap <= CW_STS_RMAX;
-    const size_t lds_s = (((size_t)CW_ST_SLAB_OF(CW_STS_QMAX, CW_STS_RMAX) + 15u) & ~(size_t)15u) + sizeof(StSys);
-    uint32_t wgs_s = n_reads;
-    if (wgs_s > (uint32_t)e->cus * 6u) wgs_s = (uint32_t)e->cus * 6u;
-    uint32_t wgs_max = narrow && wgs_n > wgs ? wgs_n : wgs;
-    if (sys && (wgs_s + CW_ST_WAVES - 1) / CW_ST_WAVES > wgs_max) wgs_max = (wgs_s + CW_ST_WAVES - 1) / CW_ST_WAVES;
     /* test aid: CW_STITCH_DIR_BYTES shrinks the banded-traceback scratch so that the capacity path can be exercised */
     a.dir_bytes = CW_ST_DIR_BYTES;
     if (const char* env = CW_AID_ENV("CW_STITCH_DIR_BYTES")) a.dir_bytes = (uint32_t)strtoul(env, nullptr, 10);
     if (a.dir_bytes < 64) a.dir_bytes = 64;
     /* the last launch (consensuses beyond CW_ST_QMAX characters; one wave per work-group, everything in global memory) has its slabs behind the traceback scratch */
     uint32_t wgs_h = n_reads < CW_STH_MAX_WGS ? n_reads : CW_STH_MAX_WGS;
-    if (wgs_h > wgs_max * CW_ST_WAVES) wgs_h = wgs_max * CW_ST_WAVES; /* (its waves use the first wgs_h traceback scratches) */
-    const size_t dir_total = (((size_t)wgs_max * CW_ST_WAVES * a.dir_bytes) + 255u) & ~(size_t)255u;
+    if (wgs_h > wgs * CW_ST_WAVES) wgs_h = wgs * CW_ST_WAVES; /* (its waves use the first wgs_h traceback scratches) */
+    const size_t dir_total = (((size_t)wgs * CW_ST_WAVES * a.dir_bytes) + 255u) & ~(size_t)255u;
     rc = ensure(&e->stitch_scratch, &e->stitch_scratch_bytes, dir_total + (size_t)wgs_h * CW_STH_WAVE_BYTES);
     if (rc) return rc;
     a.dir_scratch = (int8_t*)e->stitch_scratch;
@@ -794,21 +773,9 @@ int cw_stitch_device(cw_engine* e, const cw_read_set* reads, const cw_stitch_rea
     a.prio = 1;
     if (const char* env = CW_AID_ENV("CW_STITCH_PRIO")) a.prio = atoi(env); /* measured: 69.6 -> 65.3 ms per job of 32768 windows (E. coli-scale ONT set) */
     cw_stitch_order_kernel<<<1, 1024, 0, st>>>(a);
-#ifdef CW_TEST_AIDS /* the two opt-in re-assembly kernels (bit-identical, measured no faster: DESIGN.md) exist in the test-aid build only */
-    if (sys) {
-        cw_stitch_kernel<CW_STS_QMAX, CW_STS_RMAX, 5, 1, false, true><<<wgs_s, 64 * CW_STS_WAVES, lds_s, st>>>(a);
-        cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES, true><<<wgs, 64 * CW_ST_WAVES, lds, st>>>(a); /* the reads it marked (a consensus above 1280: normally none) */
-    } else if (narrow) {
-        cw_stitch_kernel<CW_STN_QMAX, CW_STN_RMAX, 5, CW_STN_WAVES, false><<<wgs_n, 64 * CW_STN_WAVES, lds_n, st>>>(a);
-        cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES, true><<<wgs, 64 * CW_ST_WAVES, lds, st>>>(a); /* the reads it marked (normally none) */
-    } else
-#endif
-    {
-        (void)lds_n; (void)lds_s; (void)wgs_n; (void)wgs_s; (void)narrow; (void)sys;
-        cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES, false><<<wgs, 64 * CW_ST_WAVES, lds, st>>>(a);
-    }
-    /* the reads the launches above marked (a window's consensus beyond CW_ST_QMAX characters: normally none, and the waves find nothing to do) */
-    cw_stitch_kernel<CW_STH_QMAX, CW_ST_RMAX, 0, 1, true><<<wgs_h, 64, 0, st>>>(a);
+    cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES><<<wgs, 64 * CW_ST_WAVES, lds, st>>>(a);
+    /* the reads the launch above marked (a window's consensus beyond CW_ST_QMAX characters: normally none, and the waves find nothing to do) */
+    cw_stitch_kernel<CW_STH_QMAX, CW_ST_RMAX, 0, 1><<<wgs_h, 64, 0, st>>>(a);
     CW_HIP(hipGetLastError());
     return CW_OK;
 }

@@ -4,15 +4,17 @@
  *
  * The local alignment the reference gets from StripedSmithWaterman::Aligner is restated per include/cw_policy.h
  * (library absent: PARITY UNPINNED, bit-identical to the oracle's restatement):
- *   sweep      packed int16, loop over reference columns; H, E and the per-position best in registers; striped since round 5
- *              (st_sweep_st: a slot of NV consecutive positions per lane-half, the in-column gap F down the registers of a lane and ONE
- *              exclusive DPP prefix max per column for its passage between slots, exact because open >= ext; the chunked sweep of
- *              rounds 1-4, st_sweep_pk, is the -DCW_ST_STRIPED=0 variant); forward sweep finds (score, end), reverse sweep on the
- *              reversed prefixes finds begin (stops when the forward score is reached); consensuses beyond 2048 characters: the last
- *              launch with the sweep's state in global memory (st_sweep_mem)
+ *   sweep      packed int16, loop over reference columns; H, E and the per-position best in registers; striped (st_sweep_st: a slot
+ *              of NV consecutive positions per lane-half, the in-column gap F down the registers of a lane and ONE exclusive DPP prefix
+ *              max per column for its passage between slots, exact because open >= ext); forward sweep finds (score, end), reverse
+ *              sweep on the reversed prefixes finds begin (stops when the forward score is reached); consensuses beyond 2048
+ *              characters: the last launch with the sweep's state in global memory (st_sweep_mem)
  *   indels     banded traceback when two overlapping windows disagree and the earlier one wins: its rows on the lanes of the wave
  *   the read   lives in its output slot as a gap buffer (left part at the front, untouched tail right-aligned), so a
  *              replace that changes the length moves only the few hundred characters between the gap and the edit.
+ *
+ * The kernels that were measured slower and retired -- the chunked sweep of rounds 1-4, the narrow kernel and the several-waves-per-read one --
+ * are recorded in docs/DESIGN_history_r6.md ("Retired variants").
  */
 #ifndef CW_STITCH_H
 #define CW_STITCH_H
@@ -20,9 +22,6 @@
 #include "cw_device.h"
 #include "cw_poa.h" /* packed int16 helpers (pk_add, pk_max, pk_splat_lo, ...) */
 
-#ifndef CW_ST_BAND_PAR
-#define CW_ST_BAND_PAR 1 /* 0: the banded traceback's rows cell by cell on lane 0, as rounds 2-4 had them (variant test) */
-#endif
 #ifndef CW_ST_PROF
 #define CW_ST_PROF 0 /* 1 (a scratch build): the debug trace holds the shader clocks of a window's phases instead of its alignment (tools/stitch_phases.py) */
 #endif
@@ -32,8 +31,9 @@
 #define CW_ST_DIR_BYTES (1u << 20) /* banded traceback scratch (directions, and the rows when they outgrow LDS), per wave, global */
 #define CW_ST_MAX_WGS 256
 #define CW_ST_ROWS_BYTES 4096u /* banded traceback rows: 3 x (2*band + 3) int32 -> band <= 169 */
-/* per wave: slice codes | current consensus | previous consensus | traceback rows | query codes forward, reversed */
-#define CW_ST_SLAB (CW_ST_RMAX + 2 * CW_ST_QMAX + CW_ST_ROWS_BYTES + 2 * CW_ST_QMAX)
+/* per wave: slice codes | current consensus | previous consensus | traceback rows | query codes forward, reversed (cw_stitch_kernel carves it) */
+#define CW_ST_SLAB_OF(QMAX, RMAX) ((RMAX) + 2 * (QMAX) + CW_ST_ROWS_BYTES + 2 * (QMAX))
+#define CW_ST_SLAB CW_ST_SLAB_OF(CW_ST_QMAX, CW_ST_RMAX)
 
 struct StitchArgs {
     cw_read_set reads;
@@ -71,22 +71,13 @@ __device__ __forceinline__ bool st_is_upper(uint8_t c) { return c >= 'A' && c <=
 
 /* Ordering point for LDS *and* global traffic between the lanes of one wave: the read under construction lives in global memory
    (gap buffer) and is written and read back by different lanes -- of the SAME wave, whose memory instructions go through one vector L1 in
-   issue order, so work-group scope (wait for the outstanding accesses; nothing to write back or invalidate) is all it takes.  Until round 5
-   these were agent-scope fences: an L2 write-back and invalidate on this XCD at each of the ~30 ordering points of a window, paid by the
-   consensus kernels of the other worker running beside this one as well (CW_ST_FENCE_AGENT=1 is that variant). */
-#ifndef CW_ST_FENCE_AGENT
-#define CW_ST_FENCE_AGENT 0
-#endif
+   issue order, so work-group scope (wait for the outstanding accesses; nothing to write back or invalidate) is all it takes.  (An agent-scope
+   fence here is an L2 write-back and invalidate on this XCD at each of the ~30 ordering points of a window, paid by the consensus kernels of the
+   other worker running beside this one as well.) */
 __device__ __forceinline__ void st_mem_sync() {
-#if CW_ST_FENCE_AGENT
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#else
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#endif
 }
 
 /* the read under construction: logical string = buf[0, L) + buf[cap-R, cap) */
@@ -135,188 +126,18 @@ struct StSweep { int score, col, row; };
 /*
  * One local-alignment sweep.  q[] (m codes, already in sweep order) against r[] walked from r_first in `step` until r_last_excl.
  * Two query positions per lane in packed int16 (scores <= 2 * CW_ST_QMAX fit); the column state (H, E) and the per-position best
- * (value, first column reaching it) stay in registers: no LDS traffic and no per-column reduction.  The in-column gap F is an
- * exclusive prefix max of h'[t] + t*ext in position order (exact because open >= ext).  The reference's "first column reaching
+ * (value, first column reaching it) stay in registers: no LDS traffic and no per-column reduction.  The reference's "first column reaching
  * the best score, smallest query index in it" falls out at the end: the global maximum, the earliest column among the positions
  * holding it, the smallest position among those.  A reverse sweep stops at the first column holding `terminate` (-1: never).
- * NCH2 = chunks of 128 query positions.
+ *
+ * STRIPED: the 128 slots of a wave (two per lane, the halves of a packed register) each hold NV CONSECUTIVE query positions (slot s: positions
+ * s*NV .. s*NV + NV - 1), one per register.  The in-column gap F then runs down the registers of a lane as plain arithmetic
+ * (F' = max(F - ext, H - open)), and only its passage from one slot to the next needs the lanes: ONE exclusive prefix max per column -- over
+ * the slots, of (F leaving the slot + slot * NV * ext).  What enters a slot is then applied to its positions in a second pass
+ * (H = max(H, Fin - v * ext)); exact because open >= ext, so a cell raised by F never opens a better gap than the one that raised it.
+ * Per register and column: 13 + 7 instructions (9 with the reverse sweep's stop test), plus ~25 per column; a five-register column (a 500-base
+ * window) is ~135 issued instructions.
  */
-/* x = (query letters of two positions) ^ (the reference letter in both halves): +MATCH where a half is zero, -MISMATCH elsewhere */
-__device__ __forceinline__ int st_score(int x) {
-    /* min(x, 1) * -(MISMATCH + MATCH) + MATCH in both halves: two packed instructions (written out: the generic vector min was lowered to
-       two compares, two selects, a permute and a shift per call -- nine instructions per chunk and column of the sweep) */
-    int t, r;
-    asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(t) : "v"(x));
-    const int mul = pk_make(-CW_SSW_MISMATCH - CW_SSW_MATCH, -CW_SSW_MISMATCH - CW_SSW_MATCH), add = pk_make(CW_SSW_MATCH, CW_SSW_MATCH);
-    asm("v_pk_mad_i16 %0, %1, %2, %3" : "=v"(r) : "v"(t), "v"(mul), "v"(add));
-    return r;
-}
-
-/* the column of a position's best: where the best changed (a half of ch is not zero) the half takes the column -- a packed min, a packed
-   negate and one bit-field insert instead of two compares and two selects */
-__device__ __forceinline__ int st_keep_col(const int ch, const int ipk, const int bcol) {
-    int t;
-    asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(t) : "v"(ch));
-    const int mask = pk_sub(0, t); /* 0xFFFF where the half changed */
-    return (ipk & mask) | (bcol & ~mask);
-}
-
-/* EXACT: the caller picked NCH2 for this query (m > 128 * (NCH2 - 1) or the next smaller variant does not exist): every chunk is walked
-   without a branch -- a chunk beyond the query is all masks and feeds nothing below it -- so the column is one basic block and the
-   chunks' prefix-max ladders fill each other's wait states. */
-template <int NCH2, bool EXACT = false, bool TERM = true> /* TERM: a reverse sweep (terminate > 0); forward sweeps are compiled without the test */
-__device__ __forceinline__ StSweep st_sweep_pk(const uint8_t* q, int m, const uint8_t* r, int r_first, int r_last_excl, int step, int terminate,
-                                               int lane) {
-    const int GO = CW_SSW_GAP_OPEN, GE = CW_SSW_GAP_EXT;
-    const int GOPK = pk_make(GO, GO), GEPK = pk_make(GE, GE), FADJ = pk_make(GE - GO, GE - GO);
-    m = st_uni(m); r_first = st_uni(r_first); r_last_excl = st_uni(r_last_excl); terminate = st_uni(terminate);
-    const int TERMPK = pk_make(terminate, terminate);
-    int hprev[NCH2], ee[NCH2], jg[NCH2], amask[NCH2], qpk[NCH2], qok[NCH2], bestv[NCH2], bcol[NCH2]; /* bcol: the first column reaching bestv, two 16-bit halves (-1: none) */
-#pragma unroll
-    for (int c = 0; c < NCH2; ++c) {
-        const int j0 = c * 128 + 2 * lane, j1 = j0 + 1;
-        jg[c] = pk_make(j0 * GE, j1 * GE);
-        amask[c] = (j0 < m ? 0xFFFF : 0) | (j1 < m ? (int)0xFFFF0000 : 0);
-        const int q0 = j0 < m ? (int)q[j0] : 4, q1 = j1 < m ? (int)q[j1] : 4;
-        qpk[c] = pk_make(q0, q1);
-        qok[c] = (q0 < 4 ? 0xFFFF : 0) | (q1 < 4 ? (int)0xFFFF0000 : 0);
-        hprev[c] = 0; ee[c] = 0; bestv[c] = 0; bcol[c] = -1;
-    }
-    int hit_col = -1;
-    for (int i = r_first; i != r_last_excl; i += step) {
-        const int rc = st_uni((int)r[i]);
-        int carry_pair = 0;      /* H of the previous column at rows (.., 128c - 1) */
-        unsigned carry_f = (unsigned)(CW_NEG16 + 32768); /* running max of h'[t] + t*GE over the rows of this column so far (biased by 32768) */
-        const int rcpk = rc * 0x00010001, rc_ok = rc <= 3 ? -1 : 0;
-        const int ipk = i * 0x00010001; /* the column in both halves (columns stay below 2048) */
-        unsigned long long hit = 0ull;
-        int zacc = -1;
-        if constexpr (EXACT) {
-            /* the same column written chunk-interleaved: everything that only needs the previous column for all chunks, then the six
-               steps of the prefix-max ladders side by side, then the short chain through the chunks (the running maximum of the gap).
-               The compiler finds this order itself for the forward sweeps and not for the reverse ones (whose columns it left chunk
-               after chunk, a wait state behind every packed instruction: 346 against 246 instructions for five chunks) */
-            int e_[NCH2], hp[NCH2], w[NCH2];
-            unsigned key[NCH2];
-#pragma unroll
-            for (int c = 0; c < NCH2; ++c) {
-                const int hp_ = hprev[c];
-                e_[c] = pk_max(pk_max(pk_sub(ee[c], GEPK), pk_sub(hp_, GOPK)), 0);
-                const int sh = CW_DPP(carry_pair, hp_, 0x138, 0xF);
-                carry_pair = cw_lane_value(hp_, 63);
-                const int dg = __builtin_amdgcn_alignbit(hp_, sh, 16);
-                const int sv = st_score(qpk[c] ^ rcpk) & qok[c] & rc_ok;
-                hp[c] = pk_max(pk_max(pk_add(dg, sv), e_[c]), 0);
-                w[c] = pk_add(hp[c], jg[c]);
-                const int tot = pk_max(w[c], __builtin_amdgcn_perm(w[c], w[c], 0x01000302));
-                key[c] = ((unsigned)tot & 0xFFFFu) ^ 0x8000u;
-            }
-#pragma unroll
-            for (int c = 0; c < NCH2; ++c) key[c] = max(key[c], (unsigned)CW_DPP(0, (int)key[c], 0x111, 0xF));
-#pragma unroll
-            for (int c = 0; c < NCH2; ++c) key[c] = max(key[c], (unsigned)CW_DPP(0, (int)key[c], 0x112, 0xF));
-#pragma unroll
-            for (int c = 0; c < NCH2; ++c) key[c] = max(key[c], (unsigned)CW_DPP(0, (int)key[c], 0x114, 0xF));
-#pragma unroll
-            for (int c = 0; c < NCH2; ++c) key[c] = max(key[c], (unsigned)CW_DPP(0, (int)key[c], 0x118, 0xF));
-#pragma unroll
-            for (int c = 0; c < NCH2; ++c) key[c] = max(key[c], (unsigned)CW_DPP(0, (int)key[c], 0x142, 0xA));
-#pragma unroll
-            for (int c = 0; c < NCH2; ++c) key[c] = max(key[c], (unsigned)CW_DPP(0, (int)key[c], 0x143, 0xC));
-#pragma unroll
-            for (int c = 0; c < NCH2; ++c) {
-                const unsigned ex = max((unsigned)CW_DPP(0, (int)key[c], 0x138, 0xF), carry_f);
-                carry_f = max(carry_f, (unsigned)cw_lane_value((int)key[c], 63));
-                const int pre = pk_max(pk_splat_lo((int)(ex ^ 0x8000u)), (w[c] << 16) | (CW_NEGPK & 0xFFFF));
-                const int f = pk_max(pk_add(pk_sub(pre, jg[c]), FADJ), 0);
-                const int h = pk_max(hp[c], f);
-                hprev[c] = h; ee[c] = e_[c];
-                const int hm = h & amask[c];
-                const int nb = pk_max(bestv[c], hm);
-                const int ch = nb ^ bestv[c];
-                bestv[c] = nb;
-                bcol[c] = st_keep_col(ch, ipk, bcol[c]);
-            }
-        } else
-#pragma unroll
-        for (int c = 0; c < NCH2; ++c) {
-            if (EXACT || c * 128 < m) {
-                const int hp_ = hprev[c];
-                int e = pk_max(pk_sub(ee[c], GEPK), pk_sub(hp_, GOPK));
-                e = pk_max(e, 0);
-                const int sh = CW_DPP(carry_pair, hp_, 0x138, 0xF);
-                carry_pair = cw_lane_value(hp_, 63);
-                const int dg = __builtin_amdgcn_alignbit(hp_, sh, 16);          /* rows (2l-1, 2l) of the previous column */
-                const int sv = st_score(qpk[c] ^ rcpk) & qok[c] & rc_ok; /* positions past the query and letters other than ACGT score 0 */
-                const int hp = pk_max(pk_max(pk_add(dg, sv), e), 0);
-                /* F[j] = max_{t<j}(h'[t] + t*GE) - GO - (j-1)*GE: exclusive prefix max in position order */
-                const int w = pk_add(hp, jg[c]);
-                const int tot = pk_max(w, __builtin_amdgcn_perm(w, w, 0x01000302)); /* both halves = the lane's larger key */
-                /* prefix max over the lanes on biased unsigned keys: six fused v_max_u32_dpp (see poa_fill_pk) */
-                const unsigned inc = cw_wave_scan_max_u32(((unsigned)tot & 0xFFFFu) ^ 0x8000u);
-                const unsigned ex = max((unsigned)CW_DPP(0, (int)inc, 0x138, 0xF), carry_f);
-                carry_f = max(carry_f, (unsigned)cw_lane_value((int)inc, 63));
-                const int pre = pk_max(pk_splat_lo((int)(ex ^ 0x8000u)), (w << 16) | (CW_NEGPK & 0xFFFF)); /* the odd position also sees the even one of its lane */
-                const int f = pk_max(pk_add(pk_sub(pre, jg[c]), FADJ), 0);
-                const int h = pk_max(hp, f);
-                hprev[c] = h; ee[c] = e;
-                const int hm = h & amask[c];
-                const int nb = pk_max(bestv[c], hm);
-                const int ch = nb ^ bestv[c];
-                bestv[c] = nb;
-                bcol[c] = st_keep_col(ch, ipk, bcol[c]);
-            }
-        }
-        if (TERM) { /* a half of zacc is zero iff some position of this column holds the score: one test per column, from the column as stored */
-            typedef unsigned short st_u2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-            for (int c = 0; c < NCH2; ++c)
-                if (EXACT || c * 128 < m)
-                    zacc = __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(st_u2, zacc), __builtin_bit_cast(st_u2, (hprev[c] & amask[c]) ^ TERMPK)));
-            hit = __ballot((zacc & 0xFFFF) == 0 || ((unsigned)zacc >> 16) == 0u);
-        }
-        if (hit) { hit_col = i; break; }
-    }
-    /* the best score, the first column that reached it, the smallest position holding it there */
-    int lm = 0;
-#pragma unroll
-    for (int c = 0; c < NCH2; ++c) lm = max(lm, max((int)(short)(bestv[c] & 0xFFFF), (int)(short)((unsigned)bestv[c] >> 16)));
-    const int M = hit_col >= 0 ? terminate : st_uni(cw_wave_max(lm));
-    StSweep best{0, -1, 0};
-    if (M <= 0) return best;
-    /* sweep order = increasing i*step: compare columns through that key */
-    int kc = 0x7FFFFFFF;
-#pragma unroll
-    for (int c = 0; c < NCH2; ++c) {
-        if ((int)(short)(bestv[c] & 0xFFFF) == M) kc = min(kc, (int)(short)(bcol[c] & 0xFFFF) * step);
-        if ((int)(short)((unsigned)bestv[c] >> 16) == M) kc = min(kc, (int)(short)((unsigned)bcol[c] >> 16) * step);
-    }
-    kc = st_uni(-cw_wave_max(-kc));
-    const int col = kc * step;
-    int jr = 0x7FFFFFFF;
-#pragma unroll
-    for (int c = 0; c < NCH2; ++c) {
-        const int j0 = c * 128 + 2 * lane;
-        if ((int)(short)(bestv[c] & 0xFFFF) == M && (int)(short)(bcol[c] & 0xFFFF) == col) jr = min(jr, j0);
-        if ((int)(short)((unsigned)bestv[c] >> 16) == M && (int)(short)((unsigned)bcol[c] >> 16) == col) jr = min(jr, j0 + 1);
-    }
-    jr = st_uni(-cw_wave_max(-jr));
-    best.score = M; best.col = col; best.row = jr;
-    return best;
-}
-
-/* ---- the sweep of the product build, STRIPED: the 128 slots of a wave (two per lane, the halves of a packed register) each hold NV CONSECUTIVE
- * query positions (slot s: positions s*NV .. s*NV + NV - 1), one per register, instead of every register holding a chunk of 128 consecutive ones.
- * The in-column gap F then runs down the registers of a lane as plain arithmetic (F' = max(F - ext, H - open)), and only its passage from one slot
- * to the next needs the lanes: ONE exclusive prefix max per column -- over the slots, of (F leaving the slot + slot * NV * ext) -- where the chunked
- * sweep above runs one such ladder per chunk.  What enters a slot is then applied to its positions in a second pass (H = max(H, Fin - v * ext));
- * exact for the same reason as the ladder itself: open >= ext, so a cell raised by F never opens a better gap than the one that raised it.
- * Per register and column: 13 + 7 instructions (9 with the reverse sweep's stop test) against 49 for a chunk, plus ~25 per column; a five-register
- * column (a 500-base window) is ~135 issued instructions for 241 / 269.  Same recurrences, same tie rules, same results (CW_ST_STRIPED=0 is the
- * variant; tests/test_gpu_variants.py). ---- */
-#ifndef CW_ST_STRIPED
-#define CW_ST_STRIPED 1
-#endif
 __device__ __forceinline__ int st_subsat(int a, int b) { /* both halves: max(a - b, 0) for unsigned halves */
     int r;
     asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
@@ -569,248 +390,23 @@ __device__ __forceinline__ StSweep st_sweep_mem(const uint8_t* q, int m, const u
     return best;
 }
 
-/* ---- the same sweep on several waves of one work-group (a read is a serial chain of windows, and a window is two sweeps of ~600
- * columns: with one wave per read a launch lasts as long as its longest read, ~0.4 ms per window).  The query's chunks of 128 positions
- * are dealt to the waves in order -- one chunk per wave up to 128 x waves positions, two beyond -- and a column moves down the waves as
- * a pipeline: within a column, chunk c needs from chunk c - 1 only the running maximum of the in-column gap (16 bits) and, for the
- * next column, the H pair of its last lane (32 bits).  Both travel in ONE 64-bit LDS word per column, tagged with the column (ring of
- * eight per wave, the consumer publishes how far it has read).  Everything of a column that does not depend on the word is issued
- * before the wave polls for it.  A reverse sweep ends at the first column that holds the forward score: the wave that finds it lowers
- * `stop`; waves ahead of it have walked a few columns further, which cannot change the result (no cell of the reverse rectangle
- * exceeds the forward score, and a position's first column is only recorded when its best improves).  Results are reduced over the
- * waves through LDS; three work-group barriers per sweep. ---- */
-#define CW_STS_WAVES 5
-#define CW_STS_CPW 2 /* chunks per wave at most: consensuses up to 1280 positions */
-#define CW_STS_QMAX (CW_STS_WAVES * CW_STS_CPW * 128)
-#define CW_STS_RMAX 640
-#define CW_STS_RING 8
-struct StSys {
-    unsigned long long mail[CW_STS_WAVES][CW_STS_RING]; /* [producer][column & 7]: F maximum (biased u16) | H pair << 16 | (column + 1) << 48 */
-    uint32_t progress[8];                                /* [consumer]: columns read so far */
-    int stop;                                            /* first column index (in sweep order) holding the terminate score; INT_MAX: none */
-    int red[3][8];
-    uint32_t q_off, r_off;                               /* the request: LDS byte offsets of the query and the slice */
-    int m, r_first, r_last_excl, step, terminate, quit;
-    int fail;                                            /* a bounded wait ran out (cannot happen): the read is reported as CW_READ_CAPACITY */
-};
-
-__device__ __forceinline__ StSweep st_sweep_sys(StSys* sm, const uint8_t* q, int m, const uint8_t* r, int r_first, int r_last_excl, int step, int terminate,
-                                                const int lane, const int wv) {
-    const int GO = CW_SSW_GAP_OPEN, GE = CW_SSW_GAP_EXT;
-    const int GOPK = pk_make(GO, GO), GEPK = pk_make(GE, GE), FADJ = pk_make(GE - GO, GE - GO);
-    m = st_uni(m); r_first = st_uni(r_first); r_last_excl = st_uni(r_last_excl); terminate = st_uni(terminate); step = st_uni(step);
-    const int TERMPK = pk_make(terminate, terminate);
-    const int cpw = m <= CW_STS_WAVES * 128 ? 1 : 2;
-    const int chunk0 = wv * cpw;
-    const bool active = chunk0 * 128 < m;
-    const bool has_prev = wv > 0, has_next = wv + 1 < CW_STS_WAVES && (wv + 1) * cpw * 128 < m;
-    int hprev[CW_STS_CPW], ee[CW_STS_CPW], jg[CW_STS_CPW], amask[CW_STS_CPW], qpk[CW_STS_CPW], qok[CW_STS_CPW], bestv[CW_STS_CPW], bce[CW_STS_CPW], bco[CW_STS_CPW];
-#pragma unroll
-    for (int c = 0; c < CW_STS_CPW; ++c) {
-        const int j0 = (chunk0 + c) * 128 + 2 * lane, j1 = j0 + 1;
-        jg[c] = pk_make(j0 * GE, j1 * GE);
-        amask[c] = (j0 < m ? 0xFFFF : 0) | (j1 < m ? (int)0xFFFF0000 : 0);
-        const int q0 = j0 < m ? (int)q[j0] : 4, q1 = j1 < m ? (int)q[j1] : 4;
-        qpk[c] = pk_make(q0, q1);
-        qok[c] = (q0 < 4 ? 0xFFFF : 0) | (q1 < 4 ? (int)0xFFFF0000 : 0);
-        hprev[c] = 0; ee[c] = 0; bestv[c] = 0; bce[c] = -1; bco[c] = -1;
-    }
-    const int ncols = (r_last_excl - r_first) * step; /* step is +1 or -1 */
-    typedef __attribute__((address_space(3))) volatile unsigned long long* st_l64;
-    typedef __attribute__((address_space(3))) volatile uint32_t* st_l32;
-    typedef __attribute__((address_space(3))) volatile int* st_li32;
-    int carry_pair = 0;  /* H of the previous column at the last rows of the wave before */
-    uint32_t seen = 0;   /* columns the next wave has read, as last looked up */
-    if (active) {
-        /* the slice letter and the stop column are requested a column ahead, before the wave polls for its word: a column's only
-           dependent round trip to LDS is the poll (a stop seen a column late costs one harmless column, see above) */
-        int rc_v = ncols > 0 ? (int)r[r_first] : 0, stop_v = 0x7FFFFFFF;
-        for (int k = 0; k < ncols; ++k) {
-            if (k > st_uni(stop_v)) break;
-            const int i = r_first + k * step;
-            const int rc = st_uni(rc_v);
-            rc_v = k + 1 < ncols ? (int)r[i + step] : 0;
-            stop_v = *(st_li32)&sm->stop;
-            const int rcpk = rc * 0x00010001, rc_ok = rc <= 3 ? -1 : 0;
-            /* what does not depend on the wave before */
-            int e_[CW_STS_CPW], hp[CW_STS_CPW], w[CW_STS_CPW];
-            unsigned inc[CW_STS_CPW];
-            int cp = carry_pair;
-#pragma unroll
-            for (int c = 0; c < CW_STS_CPW; ++c) {
-                if (c < cpw && (chunk0 + c) * 128 < m) {
-                    const int hp_ = hprev[c];
-                    int e = pk_max(pk_sub(ee[c], GEPK), pk_sub(hp_, GOPK));
-                    e = pk_max(e, 0);
-                    const int sh = CW_DPP(cp, hp_, 0x138, 0xF);
-                    cp = cw_lane_value(hp_, 63);
-                    const int dg = __builtin_amdgcn_alignbit(hp_, sh, 16);
-                    const int sv = st_score(qpk[c] ^ rcpk) & qok[c] & rc_ok;
-                    hp[c] = pk_max(pk_max(pk_add(dg, sv), e), 0);
-                    e_[c] = e;
-                    w[c] = pk_add(hp[c], jg[c]);
-                    const int tot = pk_max(w[c], __builtin_amdgcn_perm(w[c], w[c], 0x01000302));
-                    inc[c] = cw_wave_scan_max_u32(((unsigned)tot & 0xFFFFu) ^ 0x8000u);
-                }
-            }
-            /* the word of the wave before */
-            unsigned carry_f = (unsigned)(CW_NEG16 + 32768);
-            int pair_next = 0;
-            bool gone = false;
-            if (has_prev) {
-                const st_l64 slot = (st_l64)&sm->mail[wv - 1][k & (CW_STS_RING - 1)];
-                for (uint32_t spin = 0;; ++spin) {
-                    const unsigned long long msg = *slot;
-                    const uint32_t lo = st_uni((uint32_t)msg), hi = st_uni((uint32_t)(msg >> 32));
-                    if ((hi >> 16) == (uint32_t)(k + 1)) { carry_f = lo & 0xFFFFu; pair_next = (int)((lo >> 16) | (hi << 16)); break; }
-                    if (k > st_uni(*(st_li32)&sm->stop)) { gone = true; break; }
-                    if (spin > (1u << 22)) { if (lane == 0) { sm->fail = 1; atomicMin(&sm->stop, -1); } gone = true; break; } /* cannot happen: every wait is bounded all the same */
-                }
-                if (gone) break;
-                if (lane == 0) *(st_l32)&sm->progress[wv] = (uint32_t)(k + 1);
-            }
-            unsigned long long hit = 0ull;
-            int h_last = 0;
-#pragma unroll
-            for (int c = 0; c < CW_STS_CPW; ++c) {
-                if (c < cpw && (chunk0 + c) * 128 < m) {
-                    const unsigned ex = max((unsigned)CW_DPP(0, (int)inc[c], 0x138, 0xF), carry_f);
-                    carry_f = max(carry_f, (unsigned)cw_lane_value((int)inc[c], 63));
-                    const int pre = pk_max(pk_splat_lo((int)(ex ^ 0x8000u)), (w[c] << 16) | (CW_NEGPK & 0xFFFF));
-                    const int f = pk_max(pk_add(pk_sub(pre, jg[c]), FADJ), 0);
-                    const int h = pk_max(hp[c], f);
-                    hprev[c] = h; ee[c] = e_[c];
-                    h_last = h;
-                    const int hm = h & amask[c];
-                    const int nb = pk_max(bestv[c], hm);
-                    const int ch = nb ^ bestv[c];
-                    bestv[c] = nb;
-                    bce[c] = (ch & 0xFFFF) ? i : bce[c];
-                    bco[c] = ((unsigned)ch >> 16) ? i : bco[c];
-                    if (terminate >= 0) {
-                        const int d = hm ^ TERMPK;
-                        hit |= __ballot((d & 0xFFFF) == 0 || ((unsigned)d >> 16) == 0u);
-                    }
-                }
-            }
-            if (has_next) { /* hand the column on: not before the next wave has read the word this one replaces */
-                for (uint32_t spin = 0; (uint32_t)k >= seen + CW_STS_RING; ++spin) {
-                    seen = st_uni(*(st_l32)&sm->progress[wv + 1]);
-                    if (k > st_uni(*(st_li32)&sm->stop)) { gone = true; break; }
-                    if (spin > (1u << 22)) { if (lane == 0) { sm->fail = 1; atomicMin(&sm->stop, -1); } gone = true; break; }
-                    if ((uint32_t)k >= seen + CW_STS_RING) __builtin_amdgcn_s_sleep(1);
-                }
-                if (gone) break;
-                const uint32_t pair = (uint32_t)cw_lane_value(h_last, 63);
-                const unsigned long long msg = (unsigned long long)(carry_f & 0xFFFFu) | ((unsigned long long)pair << 16) | ((unsigned long long)(k + 1) << 48);
-                if (lane == 0) *(st_l64)&sm->mail[wv][k & (CW_STS_RING - 1)] = msg;
-            }
-            carry_pair = pair_next;
-            if (hit) { if (lane == 0) atomicMin(&sm->stop, k); break; }
-        }
-    }
-    /* over the waves: the best score, the first column that reached it, the smallest position holding it there */
-    int lm = 0;
-#pragma unroll
-    for (int c = 0; c < CW_STS_CPW; ++c) lm = max(lm, max((int)(short)(bestv[c] & 0xFFFF), (int)(short)((unsigned)bestv[c] >> 16)));
-    lm = st_uni(cw_wave_max(lm));
-    if (lane == 0) sm->red[0][wv] = lm;
-    __syncthreads();
-    const bool was_hit = st_uni(*(st_li32)&sm->stop) != 0x7FFFFFFF;
-    int M = 0;
-    for (int x = 0; x < CW_STS_WAVES; ++x) M = max(M, sm->red[0][x]);
-    M = was_hit ? terminate : st_uni(M);
-    /* the rings are free again: every wave is out of its loop */
-    if (lane < CW_STS_RING) sm->mail[wv][lane] = 0ull;
-    if (lane == 0) sm->progress[wv] = 0u;
-    StSweep best{0, -1, 0};
-    if (M <= 0) { __syncthreads(); return best; } /* (the master may post its next request only when every wave has read this one's results) */
-    int kc = 0x7FFFFFFF;
-#pragma unroll
-    for (int c = 0; c < CW_STS_CPW; ++c) {
-        if ((int)(short)(bestv[c] & 0xFFFF) == M) kc = min(kc, bce[c] * step);
-        if ((int)(short)((unsigned)bestv[c] >> 16) == M) kc = min(kc, bco[c] * step);
-    }
-    kc = st_uni(-cw_wave_max(-kc));
-    if (lane == 0) sm->red[1][wv] = kc;
-    __syncthreads();
-    for (int x = 0; x < CW_STS_WAVES; ++x) kc = min(kc, sm->red[1][x]);
-    kc = st_uni(kc);
-    const int col = kc * step;
-    int jr = 0x7FFFFFFF;
-#pragma unroll
-    for (int c = 0; c < CW_STS_CPW; ++c) {
-        const int j0 = (chunk0 + c) * 128 + 2 * lane;
-        if ((int)(short)(bestv[c] & 0xFFFF) == M && bce[c] == col) jr = min(jr, j0);
-        if ((int)(short)((unsigned)bestv[c] >> 16) == M && bco[c] == col) jr = min(jr, j0 + 1);
-    }
-    jr = st_uni(-cw_wave_max(-jr));
-    if (lane == 0) sm->red[2][wv] = jr;
-    __syncthreads();
-    for (int x = 0; x < CW_STS_WAVES; ++x) jr = min(jr, sm->red[2][x]);
-    best.score = M; best.col = col; best.row = st_uni(jr);
-    return best;
-}
-
-/* the master wave (wave 0, which runs the read) posts a sweep and takes part in it; the other waves wait for requests in st_sys_helper */
-__device__ __forceinline__ StSweep st_sweep_post(StSys* sm, const uint8_t* lds_base, const uint8_t* q, int m, const uint8_t* r, int r_first, int r_last_excl, int step,
-                                                 int terminate, const int lane) {
-    if (lane == 0) {
-        sm->q_off = (uint32_t)(q - lds_base); sm->r_off = (uint32_t)(r - lds_base);
-        sm->m = m; sm->r_first = r_first; sm->r_last_excl = r_last_excl; sm->step = step; sm->terminate = terminate; sm->quit = 0;
-        sm->stop = 0x7FFFFFFF;
-    }
-    __syncthreads();
-    const StSweep sw = st_sweep_sys(sm, q, m, r, r_first, r_last_excl, step, terminate, lane, 0);
-    if (st_uni(sm->fail)) return StSweep{0, -1, 0}; /* no coordinates from a sweep that was given up */
-    return sw;
-}
-__device__ __forceinline__ void st_sys_helper(StSys* sm, const uint8_t* lds_base, const int lane, const int wv) {
-    for (;;) {
-        __syncthreads();
-        if (st_uni(sm->quit)) break;
-        (void)st_sweep_sys(sm, lds_base + st_uni(sm->q_off), st_uni(sm->m), lds_base + st_uni(sm->r_off), st_uni(sm->r_first), st_uni(sm->r_last_excl), st_uni(sm->step),
-                           st_uni(sm->terminate), lane, wv);
-    }
-}
-
-template <int NCHK, bool TERM> /* NCHK: the most registers per slot (chunks) this kernel holds; 0 = the last launch, which has the memory-state sweep for what is longer still */
-__device__ __forceinline__ StSweep st_sweep_any(const uint8_t* q, int m, const uint8_t* r, int r_first, int r_last_excl, int step, int terminate, int lane, uint8_t* state = nullptr) {
-    if constexpr (NCHK == 0) { /* (registers for the common lengths only: the last launch is compiled for 128 of them, so that its work-groups find room beside running kernels) */
-        if (st_uni(m) > 640) return st_sweep_mem<TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane, state);
-    }
-    /* the narrow kernel (consensuses of at most 640 positions: every 500-base window): five chunks, a third of the registers */
-#if CW_ST_STRIPED
+/* HUGE = the last launch, which has the memory-state sweep for what its registers do not hold: it is compiled for 128 of them (so that its
+   work-groups find room beside running kernels) and keeps the register sweeps of the common lengths only */
+template <bool HUGE, bool TERM>
+__device__ __forceinline__ StSweep st_sweep_any(const uint8_t* q, int m, const uint8_t* r, int r_first, int r_last_excl, int step, int terminate, int lane, uint8_t* state) {
     m = st_uni(m);
-    if constexpr (NCHK >= 1 && NCHK <= 8) return st_sweep_st2<NCHK, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
+    if constexpr (HUGE) {
+        if (m > 640) return st_sweep_mem<TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane, state);
+    }
     if (m <= 128) return st_sweep_st2<1, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
     if (m <= 256) return st_sweep_st2<2, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
     if (m <= 384) return st_sweep_st2<3, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
     if (m <= 512) return st_sweep_st2<4, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
-    if (m <= 640 || NCHK == 0) return st_sweep_st2<5, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
+    if (m <= 640 || HUGE) return st_sweep_st2<5, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
     if (m <= 768) return st_sweep_st2<6, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
     if (m <= 1024) return st_sweep_st2<8, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
     if (m <= 1536) return st_sweep_st2<12, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
     return st_sweep_st2<CW_ST_QMAX / 128, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
-#else
-    if constexpr (NCHK >= 1 && NCHK <= 8) return st_sweep_pk<NCHK, false, TERM>(q, st_uni(m), r, r_first, r_last_excl, step, terminate, lane);
-    /* A variant per chunk count for the common lengths (a 500-base window's consensus is 500-600 positions: five chunks), each a
-       branch-free column written chunk-interleaved (st_sweep_pk, EXACT); the rare long ones keep the sixteen-chunk loop that skips the
-       chunks beyond the query with a scalar branch.  Round 2 walked everything up to 1024 positions through an eight-chunk loop with those
-       skips: a basic block per chunk, nothing to fill the wait states of the prefix-max ladders with, the per-position best copied
-       between register sets at every branch -- ~110 issued instructions per chunk and column against 49 now (read in the ISA; a
-       column of five chunks: 550 -> 241 instructions forward, 269 reverse).  Round 1 had 4-, 8- and 16-chunk variants side by side and
-       the 8-chunk one returned garbage rows on gfx950 (ROCm 7.2 hipcc), each of them alone being correct; the present set is checked by
-       tests/test_gpu_stitch.py (lengths on both sides of every boundary), tests/test_gpu_pipeline.py and tools/fuzz_pipeline.py. */
-    m = st_uni(m);
-    if (m <= 128) return st_sweep_pk<1, true, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
-    if (m <= 256) return st_sweep_pk<2, true, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
-    if (m <= 512) return st_sweep_pk<4, true, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
-    if (m <= 640) return st_sweep_pk<5, true, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
-    if (m <= 768) return st_sweep_pk<6, true, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
-    if (m <= 1024) return st_sweep_pk<8, true, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
-    return st_sweep_pk<CW_ST_QMAX / 128, false, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
-#endif
 }
 
 /* banded traceback (ssw banded_sw): totals of inserted / deleted bases between the alignment's ends.  Wave-uniform, serial
@@ -844,7 +440,7 @@ __device__ __forceinline__ bool st_banded_indels(const uint8_t* ref, int refLen,
         dir_cur = dir;
         st_mem_sync();
         int mx = 0;
-        if (CW_ST_BAND_PAR && rows_in_lds && width_d <= 64) {
+        if (rows_in_lds && width_d <= 64) {
             /* a row of the band on the lanes (lane t: cell j = beg + t), the arrays and their index rules -- including the zeroed `edge` slots and whatever
                an earlier row left beyond the cells of the last one -- exactly those of the serial loop below: every lane reads its three cells of the
                row before, then all write; the in-row gap f[t] = max(h[t-1] - open, f[t-1] - ext) is an exclusive prefix max of h'[s] - open + (s+1) ext
@@ -957,24 +553,19 @@ __device__ __forceinline__ bool st_banded_indels(const uint8_t* ref, int refLen,
 struct StAlign { int score, ref_begin, ref_end, query_begin, query_end; };
 
 /* full alignment: forward sweep, reverse sweep.  qfw = query codes; qrv = scratch for the reversed prefix. */
-template <int NCHK, bool SYS = false>
-__device__ __forceinline__ StAlign st_align(const uint8_t* qfw, int m, uint8_t* qrv, const uint8_t* ref, int n, int lane, StSys* sm = nullptr, const uint8_t* lds_base = nullptr,
-                                            uint8_t* state = nullptr) {
+template <bool HUGE>
+__device__ __forceinline__ StAlign st_align(const uint8_t* qfw, int m, uint8_t* qrv, const uint8_t* ref, int n, int lane, uint8_t* state) {
     StAlign a{0, 0, -1, 0, -1};
     m = st_uni(m); n = st_uni(n);
     if (m <= 0 || n <= 0) return a;
-    StSweep fw;
-    if constexpr (SYS) fw = st_sweep_post(sm, lds_base, qfw, m, ref, 0, n, 1, -1, lane);
-    else fw = st_sweep_any<NCHK, false>(qfw, m, ref, 0, n, 1, -1, lane, state);
+    const StSweep fw = st_sweep_any<HUGE, false>(qfw, m, ref, 0, n, 1, -1, lane, state);
     a.score = fw.score;
     if (fw.score <= 0) return a;
     a.ref_end = fw.col; a.query_end = fw.row;
     const int pm = fw.row + 1;
     for (int x = lane; x < pm; x += 64) qrv[x] = qfw[fw.row - x];
     st_mem_sync();
-    StSweep bw;
-    if constexpr (SYS) bw = st_sweep_post(sm, lds_base, qrv, pm, ref, fw.col, -1, -1, fw.score, lane);
-    else bw = st_sweep_any<NCHK, true>(qrv, pm, ref, fw.col, -1, -1, fw.score, lane, state);
+    const StSweep bw = st_sweep_any<HUGE, true>(qrv, pm, ref, fw.col, -1, -1, fw.score, lane, state);
     a.ref_begin = bw.col; a.query_begin = fw.row - bw.row;
     return a;
 }
@@ -1010,37 +601,35 @@ __global__ void __launch_bounds__(1024) cw_stitch_order_kernel(StitchArgs a) {
     for (uint32_t i = threadIdx.x; i < a.n_reads; i += 1024) a.order[atomicAdd(&hist[min(a.jobs[i].win_count, 1023u)], 1u)] = i;
 }
 
-/* The instantiations.  The product build launches the WIDE kernel (consensus and slice of at most 2048 positions, sweeps of 1..16 registers per slot)
-   over all reads, then the LAST one (NCHK = 0: consensuses up to CW_STH_QMAX, everything in global memory) over the reads the wide one marked
-   CW_READ_REDO -- normally none.  REDO = a launch that takes only marked reads.  The test-aid build also has the NARROW kernel (consensus and slice
-   of at most 640 positions -- every window of the wrappers' defaults, 500 + 2 x 50 -- five registers per slot, 7.3 KB of LDS per wave: twice the
-   reads in flight per CU; what does not fit it is marked and taken by the wide one as a REDO launch) and the several-waves-per-read one (SYS);
-   both bit-identical and measured no faster. */
+/* buf[0, n) = buf[from, from + n) in place, from > 0: 64 characters at a time, lowest first (the ranges may overlap) */
+__device__ __forceinline__ void st_shift_down(uint8_t* buf, uint32_t from, uint32_t n, int lane) {
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t x = base + lane;
+        uint8_t v = 0;
+        if (x < n) v = buf[from + x];
+        st_mem_sync();
+        if (x < n) buf[x] = v;
+        st_mem_sync();
+    }
+}
+
+/* The instantiations: the WIDE kernel (consensus and slice of at most 2048 positions, sweeps of 1..16 registers per slot, slabs in LDS) over all
+   reads, then the LAST launch (NCHK = 0: consensuses up to CW_STH_QMAX, one wave per work-group, every buffer and the sweep's state in global
+   memory) over the reads the wide one marked CW_READ_REDO -- normally none.  a.cursor: [0] the wide kernel's reads, [1] the last launch's,
+   [2] how many reads were marked. */
 #define CW_READ_REDO 0xFEu
-#define CW_ST_SLAB_OF(QMAX, RMAX) ((RMAX) + 2 * (QMAX) + CW_ST_ROWS_BYTES + 2 * (QMAX))
-#define CW_STN_QMAX 640
-#define CW_STN_RMAX 640
-#define CW_STN_WAVES 4
-/* SYS: one read per work-group of CW_STS_WAVES waves; wave 0 runs the read exactly as the one-wave kernels do, and every sweep is shared
-   with the other waves (st_sweep_sys).  WAVES = 1 then (slabs and scratch are per read). */
-template <int QMAX, int RMAX, int NCHK, int WAVES, bool REDO, bool SYS = false>
+/* the last launch's slab and the state behind it as the kernel carves them, against what the host sizes per wave (CW_STH_WAVE_BYTES) */
+static_assert((((((size_t)CW_ST_SLAB_OF(CW_STH_QMAX, CW_ST_RMAX) + 255u) & ~(size_t)255u) + CW_STH_STATE_BYTES + 255u) & ~(size_t)255u) == CW_STH_WAVE_BYTES, "the last launch: slab, then the sweep's state");
+template <int QMAX, int RMAX, int NCHK, int WAVES> /* NCHK: 0 = the last launch; otherwise unused */
 /* (the wide kernel needs 243 + 16 registers: one wave per SIMD, 1024 reads in flight.  Capped at 256 for two waves per SIMD the launch
    is SLOWER, 60.5 against 55.3 ms per job of 32768 windows: it lasts as long as its longest read, and that read's wave then shares its SIMD) */
 /* (the last launch is compiled for 128 registers and holds the register sweeps of the common lengths only: normally it has nothing to do, and as a
    334-register kernel its work-groups waited 4 ms for a SIMD that free beside the other workers' kernels) */
-__global__ void __launch_bounds__(SYS ? 64 * CW_STS_WAVES : 64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kernel(StitchArgs a) {
+__global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kernel(StitchArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = threadIdx.x & 63, wave = SYS ? 0 : threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr bool HUGE = NCHK == 0; /* the last launch: one wave per work-group, every buffer in global memory, consensuses up to CW_STH_QMAX */
     const uint32_t too_big = !HUGE && a.huge ? (uint32_t)CW_READ_REDO : (uint32_t)CW_READ_CAPACITY; /* a kernel hands on what the last one reports as a capacity */
-    StSys* const sm = (StSys*)(lds + (((size_t)CW_ST_SLAB_OF(QMAX, RMAX) + 15u) & ~(size_t)15u));
-    if constexpr (SYS) {
-        static_assert(WAVES == 1 && QMAX <= CW_STS_QMAX && RMAX <= CW_STS_RMAX, "one read per work-group");
-        const int wv = threadIdx.x >> 6;
-        if (lane < CW_STS_RING) sm->mail[wv][lane] = 0ull;
-        if (lane == 0) { sm->progress[wv] = 0u; if (wv == 0) sm->fail = 0; }
-        if (wv != 0) { st_sys_helper(sm, lds, lane, wv); return; }
-    }
     uint8_t* slab = HUGE ? a.huge + (size_t)blockIdx.x * CW_STH_WAVE_BYTES : lds + (size_t)wave * CW_ST_SLAB_OF(QMAX, RMAX);
     uint8_t* const state = HUGE ? slab + (((size_t)CW_ST_SLAB_OF(QMAX, RMAX) + 255u) & ~(size_t)255u) : nullptr;
     uint8_t* refc = slab;                              /* RMAX codes of the aligned slice              */
@@ -1050,16 +639,16 @@ __global__ void __launch_bounds__(SYS ? 64 * CW_STS_WAVES : 64 * WAVES, NCHK == 
     uint8_t* qfw = rows + CW_ST_ROWS_BYTES;            /* QMAX query codes                              */
     uint8_t* qrv = qfw + QMAX;                         /* QMAX reversed prefix / build area             */
     int8_t* dirbuf = a.dir_scratch + ((size_t)blockIdx.x * WAVES + wave) * a.dir_bytes;
-    if constexpr (HUGE) { if (st_uni(*(volatile uint32_t*)(a.cursor + 3)) == 0u) return; } /* no read was marked: normally */
+    if constexpr (HUGE) { if (st_uni(*(volatile uint32_t*)(a.cursor + 2)) == 0u) return; } /* no read was marked: normally */
     for (;;) {
         uint32_t ri = 0;
-        if (lane == 0) ri = atomicAdd(a.cursor + (HUGE ? 2 : REDO ? 1 : 0), 1u);
+        if (lane == 0) ri = atomicAdd(a.cursor + (HUGE ? 1 : 0), 1u);
         ri = (uint32_t)cw_lane_value((int)ri, 0);
         if (ri >= a.n_reads) break;
         /* the launch lasts as long as its longest read: the waves that hold the longest reads (handed out first) issue before the others */
         if (a.prio) { if (ri < a.n_reads / 32u + 1u) __builtin_amdgcn_s_setprio(3); else if (ri < a.n_reads / 8u) __builtin_amdgcn_s_setprio(2); else if (ri < a.n_reads / 2u) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
         ri = st_uni(a.order[ri]);
-        if (REDO && st_uni((uint32_t)a.read_status[ri]) != (uint32_t)CW_READ_REDO) continue;
+        if (HUGE && st_uni((uint32_t)a.read_status[ri]) != (uint32_t)CW_READ_REDO) continue;
         cw_stitch_read jb = a.jobs[ri];
         jb.read = st_uni(jb.read); jb.win_first = st_uni(jb.win_first); jb.win_count = st_uni(jb.win_count);
         const uint32_t rlen = st_uni(a.reads.read_len[jb.read]);
@@ -1114,7 +703,7 @@ __global__ void __launch_bounds__(SYS ? 64 * CW_STS_WAVES : 64 * WAVES, NCHK == 
             for (uint32_t x = lane; x < clen; x += 64) qfw[x] = (uint8_t)st_code(cur[x]);
             st_mem_sync();
             ST_PROF(0);
-            const StAlign al = st_align<NCHK, SYS>(qfw, (int)clen, qrv, refc, size_al, lane, sm, lds, state);     /* :90 */
+            const StAlign al = st_align<HUGE>(qfw, (int)clen, qrv, refc, size_al, lane, state);     /* :90 */
             ST_PROF(1);
             if (!CW_ST_PROF && a.trace && lane == 0) {
                 uint32_t* t = a.trace + 8 * (size_t)w;
@@ -1125,16 +714,7 @@ __global__ void __launch_bounds__(SYS ? 64 * CW_STS_WAVES : 64 * WAVES, NCHK == 
             const uint32_t beg = (uint32_t)(al.ref_begin + al_pos), end = (uint32_t)(al.ref_end + al_pos); /* :91-92 */
             /* curCons = curCons.substr(query_begin, ...) (:93): shift down in place */
             uint32_t cl = (uint32_t)(al.query_end - al.query_begin + 1);
-            if (al.query_begin > 0) {
-                for (uint32_t base = 0; base < cl; base += 64) {
-                    const uint32_t x = base + lane;
-                    uint8_t v = 0;
-                    if (x < cl) v = cur[al.query_begin + x];
-                    st_mem_sync();
-                    if (x < cl) cur[x] = v;
-                    st_mem_sync();
-                }
-            }
+            if (al.query_begin > 0) st_shift_down(cur, (uint32_t)al.query_begin, cl, lane);
             bool emptied = false;
             ST_PROF(2);
             if (wi != 0 && have_old && old_end >= beg) {                                                   /* :96 */
@@ -1159,7 +739,7 @@ __global__ void __launch_bounds__(SYS ? 64 * CW_STS_WAVES : 64 * WAVES, NCHK == 
                             if (overlap > RMAX) { status = (uint32_t)CW_READ_CAPACITY; break; } /* (the last launch only: elsewhere a consensus is no longer than a slice may be) */
                             for (uint32_t x = lane; x < overlap; x += 64) { qfw[x] = (uint8_t)st_code(seq1[x]); refc[x] = (uint8_t)st_code(cur[x]); }
                             st_mem_sync();
-                            const StAlign sub = st_align<NCHK, SYS>(qfw, (int)overlap, qrv, refc, (int)overlap, lane, sm, lds, state);
+                            const StAlign sub = st_align<HUGE>(qfw, (int)overlap, qrv, refc, (int)overlap, lane, state);
                             unsigned ins = 0, del = 0;
                             if (sub.score > 0) {
                                 if (!st_banded_indels(refc + sub.ref_begin, sub.ref_end - sub.ref_begin + 1, qfw + sub.query_begin, sub.query_end - sub.query_begin + 1,
@@ -1221,28 +801,14 @@ __global__ void __launch_bounds__(SYS ? 64 * CW_STS_WAVES : 64 * WAVES, NCHK == 
                 fbeg = first; flen = last - first + 1;
                 if ((float)ups / (float)flen < 0.1) { flen = 0; status = 1; }     /* dropRead on the trimmed read (CONSENT-correction.cpp:52) */
             }
-            if (flen && fbeg) {
-                for (uint32_t base = 0; base < flen; base += 64) {
-                    const uint32_t x = base + lane;
-                    uint8_t v = 0;
-                    if (x < flen) v = g.buf[fbeg + x];
-                    st_mem_sync();
-                    if (x < flen) g.buf[x] = v;
-                    st_mem_sync();
-                }
-            }
+            if (flen && fbeg) st_shift_down(g.buf, fbeg, flen, lane);
         }
         flen = st_uni(flen); status = st_uni(status);
-        if constexpr (SYS) { if (st_uni(sm->fail)) { flen = 0; status = (uint32_t)CW_READ_CAPACITY; if (lane == 0) sm->fail = 0; } }
         if (lane == 0) {
             a.out_len[ri] = flen; a.read_status[ri] = (uint8_t)status;
-            if (!HUGE && status == (uint32_t)CW_READ_REDO) atomicAdd(a.cursor + 3, 1u); /* the last launch looks at this count first */
+            if (!HUGE && status == (uint32_t)CW_READ_REDO) atomicAdd(a.cursor + 2, 1u); /* the last launch looks at this count first */
         }
         st_mem_sync();
-    }
-    if constexpr (SYS) { /* the other waves wait for the next request: none */
-        if (lane == 0) sm->quit = 1;
-        __syncthreads();
     }
 }
 

@@ -1,6 +1,6 @@
 """GPU: cw_stitch_device (alignConsensus + trimRead + dropRead on the device) against the oracle's restatement,
 fed with the same window consensuses and solid sets.  Bit-exact strings and statuses."""
-import os
+import ctypes as C
 import random
 
 import numpy as np
@@ -62,7 +62,7 @@ def oracle_stitch_all(reads, jobs, pos, piles, res, do_trim, window_size=500, wi
     return out
 
 
-def run_case(spec, do_trim=True, mutate=None, window_size=500, window_overlap=50, prm=None):
+def run_case(spec, do_trim=True, mutate=None, window_size=500, window_overlap=50, prm=None, probe=None):
     reads, jobs, pos, piles = build(spec, window_size, window_overlap)
     prm = prm or ca.Params(K, SOLID, 8, 2, 150)
     eng = ca.Engine(prm)
@@ -73,6 +73,8 @@ def run_case(spec, do_trim=True, mutate=None, window_size=500, window_overlap=50
         if mutate:
             mutate(res, piles)
         got = eng.stitch(ca.pack_piles([reads]), np.array(jobs, np.uint32), np.array(pos, np.uint32), batch, res, window_size, window_overlap, do_trim)
+        if probe:
+            probe(eng)
     finally:
         eng.close()
     want = oracle_stitch_all(reads, jobs, pos, piles, res, do_trim, window_size, window_overlap, prm.k)
@@ -229,44 +231,60 @@ def test_stitch_capacity_path_reports_status_and_does_not_disturb_other_reads(ai
         assert (st == 2 and g == "") or (st == 0 and g == f)
 
 
-def test_stitch_narrow_kernel_hands_long_consensuses_to_the_wide_one(aids, monkeypatch):
-    """CW_STITCH_NARROW=1: the five-chunk kernel (consensus and slice <= 640) takes every read first; a read with a longer consensus in any window is
-    marked and redone by the wide kernel in a second launch -- same strings either way (the oracle's restatement decides)."""
-    monkeypatch.setenv("CW_STITCH_NARROW", "1")
-    test_stitch_long_consensuses_use_the_wide_sweeps()
-    got, n_up = run_case(make_reads(118, 40, 10, lo=600, hi=1800))
-    assert len(got) == 40 and n_up > 0
+# st_sweep_any picks the sweep's registers per slot from the consensus length: 1, 2, 3, 4, 5, 6, 8, 12, 16 up to 128, 256, 384, 512, 640, 768, 1024, 1536, 2048
+SWEEP_EDGES = (128, 129, 256, 257, 384, 385, 512, 513, 640, 641, 768, 769, 1024, 1025, 1536, 1537, 2048)
+# 2049 sends its whole read to the last launch, whose register sweeps end at 640: 641 is the first length of the memory-state sweep
+LAST_LAUNCH_EDGES = (640, 641, 2049)
+EDGE_WINDOW, EDGE_OVERLAP = 100, 10  # consensuses of about a hundred characters: every length above can be reached by padding
 
 
-def test_stitch_several_waves_per_read(aids, monkeypatch):
-    """CW_STITCH_SYS=1: one read per work-group of five waves, every sweep shared between them as a pipeline over the query's chunks (one chunk
-    per wave up to 640 positions, two up to 1280; longer consensuses are handed to the wide kernel) -- same strings as the oracle's restatement in
-    every case the one-wave kernels are tested on."""
-    monkeypatch.setenv("CW_STITCH_SYS", "1")
-    test_stitch_matches_oracle_pacbio_like()
-    test_stitch_without_trimming_keeps_the_uncorrected_ends()
-    test_stitch_with_sparse_coverage_and_dropped_reads()
-    test_stitch_overlap_reconciliation_paths()
-    test_stitch_short_consensus_falls_back_to_the_template_without_writing()
-    test_stitch_long_consensuses_use_the_wide_sweeps()
-    test_stitch_many_reads_in_one_launch()
-    got, n_up = run_case(make_reads(118, 40, 10, lo=600, hi=1800))
-    assert len(got) == 40 and n_up > 0
+def edge_spec():
+    return make_reads(150, 3, 12, lo=1300, hi=1500)
 
 
+def place_edge_lengths(res, jobs, rng):
+    """Pads consensuses with junk (before, around and after the true window sequence in turn) to exactly SWEEP_EDGES in the windows of every read but
+    the last and LAST_LAUNCH_EDGES in the last read's; returns {window: length}.  A window is passed over when it has no consensus, a longer one than
+    the length that is next, or too small a result slot."""
+    placed = {}
+    for reads_, todo in ((jobs[:-1], list(SWEEP_EDGES)), (jobs[-1:], list(LAST_LAUNCH_EDGES))):
+        for (_, w0, wn) in reads_:
+            for w in range(w0, w0 + wn):
+                o, n = int(res.cons_off[w]), int(res.cons_len[w])
+                if not todo or n == 0 or n > todo[0] or todo[0] > int(res.cons_off[w + 1]) - o:
+                    continue
+                extra = todo.pop(0) - n
+                left = [extra // 2, extra, 0][len(placed) % 3]
+                s = res.cons[o : o + n].tobytes()
+                t = "".join(rng.choice("ACGT") for _ in range(left)).encode() + s + "".join(rng.choice("ACGT") for _ in range(extra - left)).encode()
+                res.cons[o : o + len(t)] = np.frombuffer(t, np.uint8)
+                res.cons_len[w] = len(t)
+                placed[w] = len(t)
+    return placed
 
-@pytest.mark.timeout(1200)
-def test_stitch_chunked_sweep_build_variant(tmp_path):
-    """-DCW_ST_STRIPED=0 -DCW_ST_BAND_PAR=0 -DCW_ST_FENCE_AGENT=1: the re-assembly kernel of rounds 1-4 (the chunked sweep with a prefix-max ladder per
-    chunk of 128 positions, the banded traceback's rows cell by cell on one lane, agent-scope ordering points) instead of round 5's; the same
-    strings in every case of this file that runs on the product library."""
-    import subprocess
-    import sys
 
-    from consent_amd import _build
+def test_stitch_sweep_width_edges(aids, monkeypatch):
+    """Consensus lengths on both sides of every threshold of st_sweep_any, exactly: the wide kernel's nine register sweeps (SWEEP_EDGES, two reads) and,
+    in a read that a 2049-character consensus sends to the last launch, 640 and 641 on the two sides of its register-sweep / memory-state-sweep edge.
+    Every length must have been placed; the kernel's trace (word 7 of a window's record: the consensus length it loaded) shows each was aligned at
+    that length; the strings are the oracle's."""
+    monkeypatch.setenv("CW_STITCH_TRACE", "1")
+    spec = edge_spec()
+    _, jobs, _, piles = build(spec, EDGE_WINDOW, EDGE_OVERLAP)
+    placed, trace = {}, np.zeros((len(piles), 8), np.uint32)
 
-    lib = str(tmp_path / "libconsent_amd_chunked.so")
-    subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DCW_ST_STRIPED=0", "-DCW_ST_BAND_PAR=0", "-DCW_ST_FENCE_AGENT=1", *_build.SRC, "-o", lib], check=True)
-    out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-m", "gpu", "-k", "not aids and not variant and not narrow and not several_waves and not capacity",
-                          "-p", "no:cacheprovider"], capture_output=True, text=True, env=dict(os.environ, CONSENT_AMD_LIB=lib), timeout=1000)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-1000:]
+    def mutate(res, _piles):
+        placed.update(place_edge_lengths(res, jobs, random.Random(23)))
+
+    def probe(eng):
+        eng.lib.cw_debug_stitch_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        rc = eng.lib.cw_debug_stitch_trace(eng.handle, len(piles), trace.ctypes.data_as(C.c_void_p))
+        assert rc == 0, rc
+
+    got, n_up = run_case(spec, mutate=mutate, window_size=EDGE_WINDOW, window_overlap=EDGE_OVERLAP, prm=ca.Params(7, SOLID, 8, 2, 150), probe=probe)
+    assert sorted(placed.values()) == sorted(SWEEP_EDGES + LAST_LAUNCH_EDGES), sorted(placed.values())
+    last_first = jobs[-1][1]
+    assert sorted(n for w, n in placed.items() if w >= last_first) == sorted(LAST_LAUNCH_EDGES)
+    for w, n in placed.items():
+        assert int(trace[w, 7]) == n, (w, n, trace[w].tolist())
+    assert n_up > 0 and all(st == 0 for _, st in got)

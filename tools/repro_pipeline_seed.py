@@ -42,7 +42,7 @@ if __name__ == "__main__":
     fa, paf = make_dataset(d, seed, n_reads=n_reads, glen=glen, rate=rate)
     want = dict(oracle_pipeline(fa, paf, do_trim=trim, **prm))
     print("data set", seed, rate, n_reads, glen, prm, trim, wpb, "oracle reads", len(want))
-    for env in ({}, {"CW_TIER_H": "2"}, {"CW_TIER_H": "1"}, {"CW_STITCH_NARROW": "1"}, {"CW_TIER_H": "2", "CW_STITCH_NARROW": "1"}):
+    for env in ({}, {"CW_TIER_H": "2"}, {"CW_TIER_H": "1"}):
         out = subprocess.run([sys.executable, __file__, "x", "y", json.dumps([fa, paf, prm, trim, wpb])], capture_output=True, text=True, env=dict(os.environ, CW_DRIVER_STATS="1", CW_DRIVER_TIMING="2", **env))
         if out.returncode != 0:
             print(env, "FAILED", out.stderr[-500:])
