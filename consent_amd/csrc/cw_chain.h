@@ -401,6 +401,8 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                     const bool e = (uint32_t)lane < q_cnt;
                     const uint32_t e_n = e ? q_n[lane] : 0u, e_mx = e ? q_mx[lane] : 0u;
                     const bool poa = e && e_n > 1u;
+                    /* (the routing rule below has a copy in cw_poa_op.h, cw_poa_route, for cw_poa_tasks_kernel: calling one shared function from here reordered eight
+                       instructions of this kernel, and its code is to stay what it is -- change the two together) */
                     /* route by the expected graph size: the graph has at least max_len nodes once its longest member is in
                        and typically ends at 1.4-1.6x that; a task that still outgrows its tier is redone in the next one */
                     const uint32_t est = (e_mx * 17u + 9u) / 10u;

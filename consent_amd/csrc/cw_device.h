@@ -134,6 +134,7 @@ struct BatchCounters {
     uint32_t x_done;              /* ... that it aligned */
     uint32_t x_stopped;           /* ... that outgrew it too (their windows stop on CW_WHY_POA) */
     uint32_t x_cells;             /* the largest alignment it was asked for, in int32 cells (all three layers under the affine gap model) */
+    uint32_t poa_arena_used;      /* a POA-only run (cw_poa_op.h): bytes of the arena its groups' slots have taken */
 };
 
 struct DevBatch {

@@ -3,7 +3,8 @@
  * table (every kernel's dynamic LDS size, named once); one device run = validate, plan and bind (cw_plan.h -> DevScratch), launch shape (grids and routing
  * from batch and knobs), enqueue (the order of a step); engine life cycle (cw_create / cw_destroy: streams in a fixed order of creation); per-stage timing
  * and the inspection entry points; the launchers of the path's neighbours (pile extraction, result planning, read re-assembly); host batches (cw_submit /
- * cw_wait) and the loop that runs a batch again with a larger plan (cw_run, cw_run_device_sync).
+ * cw_wait) and the loop that runs a batch again with a larger plan (cw_run, cw_run_device_sync); the POA stage alone on a batch of groups (cw_poa_run_device,
+ * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run).
  * The scratch plan is cw_plan.h (host arithmetic only); the host feeders, cw_window_positions among them, are cw_hostio.cpp.
  */
 #include "cw_internal.h"
@@ -18,6 +19,7 @@
 #include "cw_stitch.h"
 #include "cw_pack.h"
 #include "cw_plan.h"
+#include "cw_poa_op.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -178,15 +180,18 @@ DevScratch bind_scratch(const ScratchPlan& p, uint8_t* base) {
     return sc;
 }
 
-/* plan the batch's scratch (cw_plan.h), see that the engine holds that much, bind it; remembers what the inspection entry points and the re-run loop need */
-int plan_and_bind(cw_engine* e, const cw_batch* batch, bool pf_full, ScratchPlan* plan, DevScratch* sc) {
+/* tier G's slabs at most, for the plans of both run shapes */
+uint32_t plan_big_slots() {
     uint32_t big_slots = 64; /* tier G's kernel is sixteen work-groups of four waves at most (big_wgs, launch_shape): 64 slabs of 16.8 MB are all it can use (256 through round 5: 4.3 GB) */
     if (const char* env = CW_AID_ENV("CW_BIG_SLOTS")) { int v = atoi(env); if (v >= 4 && v <= 4096) big_slots = (uint32_t)v / 4 * 4; }
-    PlanInput in = plan_input(e, batch->n_windows, batch->n_seqs, batch->n_words);
-    in.big_slots = big_slots; in.pf_full = pf_full;
-    const ScratchPlan& p = *plan = plan_scratch(in);
+    return big_slots;
+}
+
+/* a plan of either run shape (plan_scratch, plan_poa): refuse it beyond the 32-bit offsets, see that the engine holds that much, bind it; remembers what the
+   inspection entry points and the re-run loop need */
+int hold_and_bind(cw_engine* e, uint32_t n_windows, uint32_t big_slots, const ScratchPlan& p, DevScratch* sc) {
     if (p.solid_cap > 0xFFFFFFFFull || p.seg_cap > 0xFFFFFFFFull || p.arena_cap > 0xFFFFFFFFull) return CW_E_INVALID; /* see CW_MAX_BATCH_WINDOWS */
-    e->last_windows = batch->n_windows; e->last_big_slots = big_slots; e->last_ctr_off = p.ctr;
+    e->last_windows = n_windows; e->last_big_slots = big_slots; e->last_ctr_off = p.ctr;
     if (int rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) return rc;
     e->last_tasks_off = p.tasks; e->last_tdbg_off = p.tdbg; e->last_task_cap = p.task_cap;
     e->last_solid_key_off = p.solid_key; e->last_solid_cnt_off = p.solid_cnt;
@@ -194,6 +199,15 @@ int plan_and_bind(cw_engine* e, const cw_batch* batch, bool pf_full, ScratchPlan
     *sc = bind_scratch(p, (uint8_t*)e->scratch);
     sc->step_clock = e->step_clock;
     return CW_OK;
+}
+
+/* plan the batch's scratch (cw_plan.h), hold it, bind it */
+int plan_and_bind(cw_engine* e, const cw_batch* batch, bool pf_full, ScratchPlan* plan, DevScratch* sc) {
+    const uint32_t big_slots = plan_big_slots();
+    PlanInput in = plan_input(e, batch->n_windows, batch->n_seqs, batch->n_words);
+    in.big_slots = big_slots; in.pf_full = pf_full;
+    const ScratchPlan& p = *plan = plan_scratch(in);
+    return hold_and_bind(e, batch->n_windows, big_slots, p, sc);
 }
 
 /* grids and work-group shapes of one run, but for the tier kernels' grids: those are DevScratch::persist_wgs, with the routing margins and the linger count */
@@ -276,11 +290,8 @@ LaunchShape launch_shape(cw_engine* e, const cw_batch* batch, const ScratchPlan&
     return ls;
 }
 
-/* The order of a step: setup, index, chain, sort, fork; tiers L / M2 / M1 on the side streams and Q (H) S on the engine's own, all concurrently; join;
-   the overflow pass (L, G, X), finish, the feedback copy.  The stage names and their order are what bench.py and cw_poll match on.  A tier's grid is
-   its persist_wgs (launch_shape). */
-int enqueue(cw_engine* e, hipStream_t st, const cw_batch* batch, const DevBatch& db, const DevScratch& sc, const ScratchPlan& p, const LaunchShape& ls, const FinOut& fo) {
-    const uint32_t cus = (uint32_t)e->cus, W = batch->n_windows, *wgs = sc.persist_wgs;
+/* what every run starts from: no stage recorded, the batch counters at zero, every slab free, tier L's live queue empty */
+int enqueue_begin(cw_engine* e, hipStream_t st, const DevScratch& sc, const ScratchPlan& p) {
     if (sc.task_dbg) CW_HIP(hipMemsetAsync(sc.task_dbg, 0, (size_t)p.task_cap * 16, st));
     e->n_stages = 0;
     e->timings_valid = false;
@@ -288,19 +299,22 @@ int enqueue(cw_engine* e, hipStream_t st, const cw_batch* batch, const DevBatch&
     CW_HIP(hipMemsetAsync(sc.ctr, 0, sizeof(BatchCounters), st));
     CW_HIP(hipMemsetAsync(sc.slot_busy[0], 0, p.sbusy[CW_TIERS - 1] + (size_t)p.tier[CW_TIERS - 1].slots * 4 - p.sbusy[0], st)); /* every slab free */
     CW_HIP(hipMemsetAsync(sc.over_list[3], 0xFF, (size_t)p.task_cap * 4, st)); /* live queue: an entry is its own flag */
-    stage(e, st, "setup", [&] {
-        cw_setup_need_kernel<<<(W + 3) / 4, 256, 0, st>>>(db, sc, e->prm);
-        cw_setup_kernel<<<1, 1024, 0, st>>>(db, sc, e->prm, p.solid_cap, p.seg_cap, p.arena_cap, p.arena_scale, e->tmax_plan, ls.arena_div);
-    });
-    stage(e, st, "index", [&] { cw_index_kernel<<<W < cus ? W : cus, CW_IDX_THREADS, kLdsIndex, st>>>(db, sc, e->prm); });
-    stage(e, st, "chain", [&] {
-        const uint32_t want = (W + CW_CH_WAVES - 1) / CW_CH_WAVES;
-        const uint32_t cap = cus * 2u; /* 2 work-groups x 4 waves x 20 KiB per CU */
-        if (e->tmax_plan > 1024u) /* an engine configured for long templates (cw_configure): 32 KiB per wave, up to CW_TMAX anchors, one work-group per CU */
-            cw_chain_kernel<CW_CH_SLAB_LONG><<<want < cus ? want : cus, 64 * CW_CH_WAVES, lds_chain(CW_CH_SLAB_LONG), st>>>(db, sc, e->prm);
-        else
-            cw_chain_kernel<CW_CH_SLAB><<<want < cap ? want : cap, 64 * CW_CH_WAVES, lds_chain(CW_CH_SLAB), st>>>(db, sc, e->prm);
-    });
+    return CW_OK;
+}
+
+/* ... and ends with: the feedback for the next batch's linger_wgs (pinned destination: asynchronous) */
+int enqueue_end(cw_engine* e, hipStream_t st, const DevScratch& sc) {
+    CW_HIP(hipMemcpyAsync(&e->host_fb->handed_over, &sc.ctr->n_over[3], 4, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
+}
+
+/* The POA stage of a run, window or POA-only: sort, fork; tiers L / M2 / M1 on the side streams and Q (H) S on the engine's own, all concurrently; join; the
+   overflow pass (L, G, X).  It depends on what comes before it only through tasks[], members[], the tier lists and seg_off / seg_len / arena. */
+int enqueue_poa_stage(cw_engine* e, hipStream_t st, const DevBatch& db, const DevScratch& sc, const LaunchShape& ls) {
+    const uint32_t* wgs = sc.persist_wgs;
     cw_sort_tier_kernel<<<5, ls.sort_thr, ls.sort_lds, st>>>(sc, ls.sort_lds); /* tiers M1, M2 and L: largest tasks first; tiers Q and H: like with like */
     /* pass 0: every tier works through its own routed list, all four concurrently; the long-running large tiers are
        dispatched first so that their tail overlaps the bulk of the small tasks */
@@ -331,6 +345,29 @@ int enqueue(cw_engine* e, hipStream_t st, const cw_batch* batch, const DevBatch&
         cw_poa_big_kernel<<<ls.big_wgs, 64 * CW_POA_WAVES, 0, st>>>(db, sc);
         cw_poa_x_kernel<<<1, 64, 0, st>>>(db, sc, ls.no_tier_x); /* what outgrew tier G, in its slab pool (ends at once when tier G handed nothing on) */
     });
+    return CW_OK;
+}
+
+/* The order of a step: setup, index, chain, sort, fork; tiers L / M2 / M1 on the side streams and Q (H) S on the engine's own, all concurrently; join;
+   the overflow pass (L, G, X), finish, the feedback copy.  The stage names and their order are what bench.py and cw_poll match on.  A tier's grid is
+   its persist_wgs (launch_shape). */
+int enqueue(cw_engine* e, hipStream_t st, const cw_batch* batch, const DevBatch& db, const DevScratch& sc, const ScratchPlan& p, const LaunchShape& ls, const FinOut& fo) {
+    const uint32_t cus = (uint32_t)e->cus, W = batch->n_windows;
+    if (int rc = enqueue_begin(e, st, sc, p)) return rc;
+    stage(e, st, "setup", [&] {
+        cw_setup_need_kernel<<<(W + 3) / 4, 256, 0, st>>>(db, sc, e->prm);
+        cw_setup_kernel<<<1, 1024, 0, st>>>(db, sc, e->prm, p.solid_cap, p.seg_cap, p.arena_cap, p.arena_scale, e->tmax_plan, ls.arena_div);
+    });
+    stage(e, st, "index", [&] { cw_index_kernel<<<W < cus ? W : cus, CW_IDX_THREADS, kLdsIndex, st>>>(db, sc, e->prm); });
+    stage(e, st, "chain", [&] {
+        const uint32_t want = (W + CW_CH_WAVES - 1) / CW_CH_WAVES;
+        const uint32_t cap = cus * 2u; /* 2 work-groups x 4 waves x 20 KiB per CU */
+        if (e->tmax_plan > 1024u) /* an engine configured for long templates (cw_configure): 32 KiB per wave, up to CW_TMAX anchors, one work-group per CU */
+            cw_chain_kernel<CW_CH_SLAB_LONG><<<want < cus ? want : cus, 64 * CW_CH_WAVES, lds_chain(CW_CH_SLAB_LONG), st>>>(db, sc, e->prm);
+        else
+            cw_chain_kernel<CW_CH_SLAB><<<want < cap ? want : cap, 64 * CW_CH_WAVES, lds_chain(CW_CH_SLAB), st>>>(db, sc, e->prm);
+    });
+    if (int rc = enqueue_poa_stage(e, st, db, sc, ls)) return rc;
     stage(e, st, "finish", [&] {
         uint32_t grid = (W + CW_FIN_WAVES - 1) / CW_FIN_WAVES;
         if (grid > cus * CW_FIN_WGS_PER_CU) grid = cus * CW_FIN_WGS_PER_CU;
@@ -338,12 +375,7 @@ int enqueue(cw_engine* e, hipStream_t st, const cw_batch* batch, const DevBatch&
         /* second pass: the windows whose strings outgrew the first pass's buffers (normally none: the kernel reads one counter and ends) */
         cw_finish_kernel<CW_FIN_CB_BIG, 1, true><<<W < 64u ? W : 64u, 64, kLdsFinishBig, st>>>(db, sc, e->prm, fo);
     });
-    /* feedback for the next batch's linger_wgs (pinned destination: asynchronous) */
-    CW_HIP(hipMemcpyAsync(&e->host_fb->handed_over, &sc.ctr->n_over[3], 4, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
-    return CW_OK;
+    return enqueue_end(e, st, sc);
 }
 
 /* the body of cw_run_device; the caller holds e->mu */
@@ -362,6 +394,40 @@ int run_device_locked(cw_engine* e, const cw_batch* batch, const cw_result* res,
     fo.cons = res->cons; fo.cons_off = res->cons_off; fo.cons_len = res->cons_len; fo.win_status = res->win_status;
     fo.solid = res->solid; fo.solid_off = res->solid_off; fo.solid_len = res->solid_len;
     return enqueue(e, st, batch, db, sc, p, ls, fo);
+}
+
+/* CW_OK for a batch of groups that can run -- and for an empty one; nothing here touches the device */
+int validate_poa(const cw_engine* e, const cw_batch* groups, const cw_result* res) {
+    if (!e || !groups || !res || !res->cons || !res->cons_off || !res->cons_len || !res->win_status) return CW_E_INVALID;
+    if (res->solid || res->solid_off || res->solid_len) return CW_E_INVALID; /* a group has no solid set */
+    if (groups->n_windows == 0) return CW_OK;
+    if (!groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
+    if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID; /* cw_max_batch_windows */
+    if (plan_poa(groups->n_windows, groups->n_seqs, groups->n_words, 1, 64).arena_cap > 0xFFFFFFFFull) return CW_E_INVALID; /* the arena's 32-bit offsets */
+    return CW_OK;
+}
+
+/* the body of cw_poa_run_device; the caller holds e->mu.  The order of such a run: poa_tasks, the POA stage of a window run, poa_gather. */
+int poa_device_locked(cw_engine* e, const cw_batch* groups, const cw_result* res, void* hip_stream) {
+    int rc = validate_poa(e, groups, res);
+    if (rc || groups->n_windows == 0) return rc;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    const uint32_t G = groups->n_windows, big_slots = plan_big_slots();
+    const ScratchPlan p = plan_poa(G, groups->n_seqs, groups->n_words, e->cus, big_slots); /* exact: no run with a larger plan follows */
+    DevScratch sc;
+    if ((rc = hold_and_bind(e, G, big_slots, p, &sc)) != CW_OK) return rc;
+    const LaunchShape ls = launch_shape(e, groups, p, sc);
+    DevBatch db;
+    db.n_windows = G; db.win_first_seq = groups->win_first_seq; db.seq_len = groups->seq_len; db.seq_word_off = groups->seq_word_off; db.bases = groups->bases;
+    PoaOut po;
+    po.cons = res->cons; po.cons_off = res->cons_off; po.cons_len = res->cons_len; po.win_status = res->win_status;
+    if ((rc = enqueue_begin(e, st, sc, p)) != CW_OK) return rc;
+    const uint32_t grid = (G + CW_POAOP_WAVES - 1) / CW_POAOP_WAVES;
+    stage(e, st, "poa_tasks", [&] { cw_poa_tasks_kernel<<<grid, 64 * CW_POAOP_WAVES, 0, st>>>(db, sc, e->prm.max_msa, groups->n_seqs, p.arena_cap); });
+    if ((rc = enqueue_poa_stage(e, st, db, sc, ls)) != CW_OK) return rc;
+    stage(e, st, "poa_gather", [&] { cw_poa_gather_kernel<<<grid, 64 * CW_POAOP_WAVES, 0, st>>>(db, sc, po); });
+    return enqueue_end(e, st, sc);
 }
 
 } // namespace
@@ -429,6 +495,8 @@ void cw_destroy(cw_engine* e) {
         if (s.ev_done) (void)hipEventDestroy(s.ev_done);
     }
     if (e->xscratch) (void)hipFree(e->xscratch);
+    if (e->poa_in) (void)hipFree(e->poa_in);
+    if (e->poa_out) (void)hipFree(e->poa_out);
     if (e->step_clock) (void)hipFree(e->step_clock);
     if (e->stitch_scratch) (void)hipFree(e->stitch_scratch);
     if (e->host_fb) (void)hipHostFree(e->host_fb);
@@ -449,6 +517,84 @@ int cw_run_device(cw_engine* e, const cw_batch* batch, const cw_result* res, voi
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
     return run_device_locked(e, batch, res, hip_stream);
+}
+
+int cw_poa_run_device(cw_engine* e, const cw_batch* groups, const cw_result* res, void* hip_stream) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return poa_device_locked(e, groups, res, hip_stream);
+}
+
+/* Host buffers in, host buffers out, synchronous: the batch and the slot offsets go up, cw_poa_run_device on the engine's stream, lengths, statuses and the
+   slots come back, and every consensus is copied into the caller's slot -- its own bytes only.  The engine's mutex is held throughout: the two device
+   buffers are the engine's. */
+int cw_poa_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = validate_poa(e, b, r);
+    if (rc || b->n_windows == 0) return rc;
+    const uint32_t G = b->n_windows, S = b->n_seqs;
+    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
+    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g] || r->cons_off[g + 1] < r->cons_off[g]) return CW_E_INVALID;
+    for (uint32_t s = 0; s < S; ++s)
+        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words || b->seq_len[s] > 65535u) return CW_E_INVALID;
+    const uint64_t c0 = r->cons_off[0], cons_bytes = r->cons_off[G] - c0;
+    size_t o = 0;
+    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
+                 i_coff = put((size_t)(G + 1) * 8);
+    const size_t in_bytes = o;
+    o = 0;
+    const size_t o_cons = put(cons_bytes), o_clen = put((size_t)G * 4), o_stat = put(G);
+    const size_t out_bytes = o;
+    std::vector<uint8_t> back;
+    std::vector<uint64_t> coff; /* the slots' offsets in the device copy, which begins at the first slot */
+    try { back.resize(out_bytes); coff.resize((size_t)G + 1); } catch (...) { return CW_E_NOMEM; }
+    for (uint32_t g = 0; g <= G; ++g) coff[g] = r->cons_off[g] - c0;
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    uint8_t *din = (uint8_t*)e->poa_in, *dout = (uint8_t*)e->poa_out;
+    hipStream_t st = e->stream;
+    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
+    if (S) CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    if (S) CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemsetAsync(din + i_bases + (size_t)b->n_words * 4, 0, 4, st));
+    CW_HIP(hipMemcpyAsync(din + i_coff, coff.data(), (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
+    cw_batch db = *b;
+    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
+    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
+    cw_result dr;
+    dr.cons = (char*)(dout + o_cons);
+    dr.cons_off = (const uint64_t*)(din + i_coff); dr.cons_len = (uint32_t*)(dout + o_clen); dr.win_status = dout + o_stat;
+    dr.solid = nullptr; dr.solid_off = nullptr; dr.solid_len = nullptr;
+    if ((rc = poa_device_locked(e, &db, &dr, st)) != CW_OK) return rc;
+    CW_HIP(hipMemcpyAsync(back.data(), dout, out_bytes, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    const uint32_t* clen = (const uint32_t*)(back.data() + o_clen);
+    for (uint32_t g = 0; g < G; ++g) {
+        const bool ok = back[o_stat + g] != CW_WIN_OVERFLOW;
+        if (!ok) rc = CW_E_CAPACITY;
+        r->win_status[g] = back[o_stat + g];
+        r->cons_len[g] = ok ? clen[g] : 0u;
+        if (ok && clen[g]) memcpy(r->cons + r->cons_off[g], back.data() + o_cons + coff[g], clen[g]);
+    }
+    return rc;
+}
+
+/* Debug/inspection (cw_private.h): what plan_poa would allocate, component by component (host arithmetic only). */
+int cw_debug_poa_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint64_t* out15) {
+    if (!out15 || !n_groups || cus < 1) return CW_E_INVALID;
+    const ScratchPlan p = plan_poa(n_groups, n_seqs, n_words, cus, 64);
+    if (p.arena_cap > 0xFFFFFFFFull) return CW_E_INVALID; /* what cw_poa_run refuses before anything is launched */
+    auto slab = [&](int t) { return (uint64_t)p.tier[t].slots * p.tier[t].slab_bytes; };
+    const uint64_t v[15] = {p.total, (uint64_t)n_groups * sizeof(WinInfo), (uint64_t)(p.seg_off - p.solid_key), p.seg_cap * 8, p.arena_cap,
+                            ((uint64_t)p.task_cap + 1) * sizeof(PoaTask) + (uint64_t)p.member_cap * sizeof(PoaMember), (uint64_t)p.task_cap * 4 * 2 * CW_TIERS,
+                            slab(0), slab(1), slab(2), slab(3), slab(4), (uint64_t)p.ablock - p.qslab, (uint64_t)(p.pfall - p.ablock),
+                            (uint64_t)(p.sbusy[0] - p.pfall) + (uint64_t)(p.tdbg - p.exg) + (uint64_t)(p.total - p.finvis)};
+    for (int i = 0; i < 15; ++i) out15[i] = v[i];
+    return CW_OK;
 }
 
 uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len) {

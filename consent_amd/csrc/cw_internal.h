@@ -54,6 +54,8 @@ struct cw_engine {
     unsigned long long* step_clock = nullptr; /* see DevScratch */
     void* xscratch = nullptr; /* pile-extraction scratch */
     size_t xscratch_bytes = 0;
+    void* poa_in = nullptr, *poa_out = nullptr; /* cw_poa_run's device copies of the caller's batch and result slots */
+    size_t poa_in_bytes = 0, poa_out_bytes = 0;
     void* stitch_scratch = nullptr; /* banded-traceback directions of cw_stitch_device, per wave */
     size_t stitch_scratch_bytes = 0;
     cw_host_fb* host_fb = nullptr;

@@ -146,6 +146,44 @@ static inline ScratchPlan plan_scratch(const PlanInput& in) {
     return p;
 }
 
+/* The plan of a POA-only run (cw_poa_run, cw_poa_op.h): G groups of n_seqs sequences in n_words packed words.  Exact, since every group is one task of at most
+   its own sequences: WinInfo[G], a segment slot and a task per group (+ the neutral task), a member per sequence, the lists, the slab pools and tier Q's rows
+   as plan_scratch sizes them for a batch of G windows -- and none of the solid table, the anchor blocks, the matrix and exact-count fallbacks and the finish
+   buffers.  The arena holds every group's slot, CW_POA_SLOT_BYTES of its longest member rounded up to 16 bytes: at most two bytes a base of the batch
+   (16 bases a word) and 32 a group; offsets into it are 32-bit (PoaTask::out_off), a batch beyond them is refused before anything is launched (arena_cap). */
+static inline ScratchPlan plan_poa(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t big_slots) {
+    ScratchPlan p;
+    memset(&p, 0, sizeof(p));
+    p.seg_cap = n_groups;
+    p.arena_scale = 1;
+    p.arena_cap = 32ull * n_words + 32ull * n_groups;
+    p.task_cap = n_groups;
+    p.member_cap = n_seqs ? n_seqs : 1u;
+    tier_config(cus, big_slots, n_groups, p.tier);
+    size_t o = 0;
+    auto put = [&](size_t& slot, size_t bytes) { slot = o; o = align_up(o + bytes, 256); };
+    put(p.win, (size_t)n_groups * sizeof(WinInfo)); /* first, as in plan_scratch: cw_debug_win_info reads it from the start of scratch */
+    put(p.solid_key, 0); put(p.solid_cnt, 0);
+    put(p.seg_off, p.seg_cap * 4);
+    put(p.seg_len, p.seg_cap * 4);
+    put(p.arena, p.arena_cap <= 0xFFFFFFFFull ? (size_t)p.arena_cap : 0); /* (a refused plan: its total says nothing) */
+    put(p.tasks, ((size_t)p.task_cap + 1) * sizeof(PoaTask));
+    put(p.members, (size_t)p.member_cap * sizeof(PoaMember));
+    put(p.ctr, sizeof(BatchCounters));
+    for (int t = 0; t < CW_TIERS; ++t) put(p.list[t], (size_t)p.task_cap * 4);
+    for (int t = 0; t < CW_TIERS; ++t) put(p.over[t], (size_t)p.task_cap * 4);
+    for (int t = 0; t < CW_TIERS; ++t) put(p.slab[t], (size_t)p.tier[t].slots * p.tier[t].slab_bytes);
+    put(p.qslab, (size_t)cus * CW_POAQ_WAVES * 4 * CW_POAQ_SLAB_BYTES);
+    put(p.hslab, (size_t)cus * CW_POAH_WAVES * 2 * CW_POAH_SLAB_BYTES);
+    put(p.ablock, 0); put(p.pfall, 0);
+    for (int t = 0; t < CW_TIERS; ++t) put(p.sbusy[t], (size_t)p.tier[t].slots * 4); /* contiguous: one memset frees every slab */
+    put(p.exg, 0);
+    put(p.tdbg, getenv("CW_TASK_TRACE") ? (size_t)p.task_cap * 16 : 0);
+    put(p.finvis, 0); put(p.finretry, 0); put(p.finbig, 0);
+    p.total = o;
+    return p;
+}
+
 /* The largest batch a plan for templates of tmax k-mers can address: per-window offsets into the segment table and the arena are 32-bit, and
    their totals are n_windows x (tmax + 2) and n_windows x (16 (tmax + 16) + 4096) at scale 1 -- at most CW_MAX_BATCH_WINDOWS (include/consent_amd.h
    cw_max_batch_windows).  115 704 windows at tmax 2048, CW_MAX_BATCH_WINDOWS at the default 1024. */

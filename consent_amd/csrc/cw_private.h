@@ -28,6 +28,10 @@ int cw_debug_plan(uint32_t k, uint32_t solid, uint32_t n_windows, uint32_t n_seq
    [2] segment slots, [3] arena bytes, [4] the arena's scale after its 32-bit clamp, [5] rows per template k-mer of the matrix slot, [6] the batch limit
    of an engine with this tmax (cw_max_batch_windows), [7] task slots. */
 int cw_debug_plan_caps(uint32_t k, uint32_t solid, uint32_t n_windows, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t scale, uint32_t tmax, int pf_full, uint64_t* out8);
+/* The scratch plan of a POA-only run (cw_poa_run) of n_groups groups, n_seqs sequences and n_words packed words, without a device: the fifteen numbers of
+   cw_debug_plan in the same order -- solid table, anchor blocks, the fallbacks and the finish buffers (indices 2, 13, 14) are 0 in it.  CW_E_INVALID for a
+   batch whose arena would pass the 32-bit offsets, as cw_poa_run answers it. */
+int cw_debug_poa_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint64_t* out15);
 /* cw_max_batch_windows of an engine that cw_configure(max_template_len) will be called on (the native driver sizes its jobs before it has engines) */
 uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len);
 

@@ -124,6 +124,10 @@ def _load(p):
     lib.cw_destroy.restype = None
     lib.cw_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result)]
     lib.cw_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.c_void_p]
+    if hasattr(lib, "cw_poa_run"):  # (a library built before the POA operator has no such entries)
+        lib.cw_poa_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result)]
+        lib.cw_poa_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.c_void_p]
+        lib.cw_debug_poa_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p]
     lib.cw_submit.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.POINTER(C.c_int)]
     lib.cw_wait.argtypes = [C.c_void_p, C.c_int]
     lib.cw_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -431,6 +435,23 @@ def alloc_results(batch, want_solid=True, solid_thresh=4, k=9):
     return WindowResults(cons, cons_off, cons_len, status, solid, solid_off, solid_len)
 
 
+def poa_slot_bytes(longest_member):
+    """CW_POA_SLOT_BYTES of include/consent_amd.h: the consensus slot the segment path reserves for members of at most this many bases (numpy-friendly)."""
+    return 2 * np.asarray(longest_member, np.int64) + 2
+
+
+def alloc_poa_results(batch, slot_bytes=None):
+    """WindowResults for Engine.poa: one consensus slot per group -- slot_bytes (a number or one per group), default poa_slot_bytes of its longest sequence."""
+    G = batch.n_windows
+    wfs = batch.win_first_seq.astype(np.int64)
+    if slot_bytes is None:
+        lens = batch.seq_len.astype(np.int64)
+        slot_bytes = poa_slot_bytes(np.array([lens[wfs[g] : wfs[g + 1]].max(initial=0) for g in range(G)], np.int64))
+    cons_off = np.zeros(G + 1, np.uint64)
+    cons_off[1:] = np.cumsum(np.broadcast_to(np.asarray(slot_bytes, np.int64), (G,)))
+    return WindowResults(np.zeros(max(int(cons_off[-1]), 1), np.uint8), cons_off, np.zeros(G, np.uint32), np.full(G, 255, np.uint8))
+
+
 def _result_struct(r):
     return Result(
         _ptr(r.cons), _ptr(r.cons_off), _ptr(r.cons_len), _ptr(r.status),
@@ -483,6 +504,22 @@ class Engine:
 
     def run_device(self, batch_struct, result_struct, stream=None):
         _check(self.lib, self.lib.cw_run_device(self.handle, C.byref(batch_struct), C.byref(result_struct), stream), "cw_run_device")
+
+    def poa(self, groups, slot_bytes=None):
+        """Only the POA (cw_poa_run): `groups` is a list of lists of ACGT strings (or a HostBatch of them); every group's sequences are aligned in the order
+        given -- zero-length ones skipped, the first max_msa others taken -- and its consensus returned: WindowResults with consensus(g) and status[g]
+        (WIN_CONSENSUS, or WIN_OVERFLOW for a group that stopped).  slot_bytes: the consensus slot, one number or one per group (default: poa_slot_bytes
+        of the group's longest sequence, what the window path reserves for a segment)."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        res = alloc_poa_results(batch, slot_bytes)
+        b = batch.c_struct()
+        r = _result_struct(res)
+        _check(self.lib, self.lib.cw_poa_run(self.handle, C.byref(b), C.byref(r)), "cw_poa_run", allow_capacity=True)
+        return res
+
+    def poa_device(self, batch_struct, result_struct, stream=None):
+        """cw_poa_run_device: as run_device, device pointers in both structs (the result's solid fields NULL), asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_poa_run_device(self.handle, C.byref(batch_struct), C.byref(result_struct), stream), "cw_poa_run_device")
 
     def extract_piles(self, reads, overlaps, jobs, k):
         """Device-side getAlignmentWindowsSequences (cw_extract_piles_device).  `reads` is a HostBatch-like packing of the read

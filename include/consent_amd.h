@@ -9,6 +9,8 @@
  *                               i.e. MSABMAAC (call sites correctionMSA.cpp:32,54) + weightConsensus
  *                               (correctionMSA.cpp:6-27) + polishCorrection (correctionDBG.h:11)
  *                               -- batched over windows, because one window per call cannot feed a GPU.
+ *   cw_poa_run / cw_poa_run_device <- only the POA of that operator (BMEAN's consensus of one segment's pieces, A4d of SURVEY), batched over
+ *                               groups of sequences: for callers that have their segments -- or racon-style windows, amplicon / UMI families -- in hand.
  *   cw_window_positions      <- getAlignmentWindowsPositions (alignmentWindows.cpp:27-85), host
  *   cw_extract_piles_device  <- getAlignmentWindowsSequences (alignmentWindows.cpp:87-149) evaluated on the device
  *   cw_stitch_device         <- alignConsensus + trimRead + dropRead (correctionAlignment.cpp:47-140, utils.cpp:96-128, :71-73)
@@ -166,6 +168,28 @@ void cw_host_free(void* ptr);
 /* Every pointer inside batch/result is a DEVICE pointer; asynchronous on `hip_stream` (a hipStream_t,
  * NULL = the engine's own stream); statuses are checked by the caller after synchronising.  The batch runs once (as cw_submit). */
 int cw_run_device(cw_engine* e, const cw_batch* batch, const cw_result* result, void* hip_stream);
+
+/* ---- only the POA: the consensus of every group of a batch of groups ------------------------------------------------------------------------
+ * `groups` is a cw_batch read differently: "window" g is a GROUP, sequences win_first_seq[g] .. win_first_seq[g+1], packed as ever.  They are aligned to one
+ * partial-order graph in the order given, the first non-empty one the backbone (under CW_POA_CONS_TIE, include/cw_policy.h, base ties go to it, as to a
+ * segment's template piece), and the graph's consensus is the group's result: the semantics of ONE segment of the window path (include/cw_policy.h).
+ * Zero-length sequences are skipped; the first params.max_msa non-empty ones are aligned; one non-empty sequence gives that sequence, none gives
+ * length 0 -- both with status CW_WIN_CONSENSUS.  params.k, solid, common_kmers and min_anchors are not read.
+ * `result`: cons, cons_off, cons_len and win_status are used; solid, solid_off and solid_len must be NULL (CW_E_INVALID otherwise).  Output is upper-case
+ * ACGT.  Group g's slot is cons_off[g+1] - cons_off[g] bytes; CW_POA_SLOT_BYTES(longest member of the group) is what the segment path itself reserves.
+ * A consensus that outgrows its slot is status 2 (CW_WHY_OUT_CONS), never a truncation, and nothing is written to that slot.
+ * Stops, each a function of the group alone (status 2, CW_WHY_POA; the other groups of the batch are unaffected): a member of more than 4 095 bases, and
+ * a graph beyond the last tier's capacities (CW_MAX_BATCH_WINDOWS above lists them).
+ * At most cw_max_batch_windows(e) groups a call, and at most 2^32 bytes of consensus working space (32 bytes a packed word of the batch + 32 a group):
+ * CW_E_INVALID beyond either, before anything is launched.  The scratch plan of such a run is exact, so the batch runs once.
+ * cw_poa_run_device: every pointer inside groups / result is a DEVICE pointer; asynchronous on `hip_stream` (NULL = the engine's own stream); returns CW_OK
+ * also when groups stop: the caller reads the statuses after synchronising.  Threading and stream contract: cw_run_device's.
+ * cw_poa_run: host pointers, synchronous; CW_E_CAPACITY when at least one group stopped (its win_status says so; the other groups' results stand).
+ * The engine keeps one scratch allocation for both kinds of run: POA runs and window runs on one engine alternate freely.  cw_last_timings names the stages
+ * of such a run poa_tasks, the POA tiers' names of a window run, poa_gather. */
+#define CW_POA_SLOT_BYTES(longest_member) (2u * (uint32_t)(longest_member) + 2u)
+int cw_poa_run_device(cw_engine* e, const cw_batch* groups, const cw_result* result, void* hip_stream);
+int cw_poa_run(cw_engine* e, const cw_batch* groups, const cw_result* result);
 
 /* 1 when everything the last cw_run_device on this engine launched has completed (or nothing was launched yet), 0 while it is
  * still running, 2 while it is running but past the part that fills the GPU (what is left is the tail: a few long alignment tasks on

@@ -81,6 +81,43 @@ class Engine {
         return out;
     }
 
+    /* Only the POA (cw_poa_run): the consensus of every group of sequences, aligned in the order given -- one segment of the window path each.  A group that
+       stopped (a member beyond 4 095 bases, a graph beyond the last tier) comes back with overflow = true and an empty consensus. */
+    std::vector<WindowConsensus> poaConsensus(const std::vector<std::vector<std::string>>& groups) {
+        std::vector<uint32_t> wfs{0}, len, bases;
+        std::vector<uint64_t> off, coff{0};
+        for (const auto& group : groups) {
+            size_t longest = 0;
+            for (const auto& s : group) {
+                const uint64_t words = (s.size() + 15) / 16;
+                off.push_back(bases.size());
+                len.push_back((uint32_t)s.size());
+                bases.resize(bases.size() + words);
+                if (words && cw_pack_sequence(s.data(), (uint32_t)s.size(), bases.data() + off.back(), words) < 0)
+                    throw std::runtime_error("consent_amd: cw_pack_sequence failed");
+                if (s.size() > longest) longest = s.size();
+            }
+            wfs.push_back((uint32_t)len.size());
+            coff.push_back(coff.back() + CW_POA_SLOT_BYTES(longest));
+        }
+        bases.push_back(0);
+        const uint32_t G = (uint32_t)groups.size();
+        std::vector<char> cons(coff[G] + 1);
+        std::vector<uint32_t> clen(G);
+        std::vector<uint8_t> st(G);
+        std::vector<WindowConsensus> out(G);
+        if (G == 0) return out;
+        cw_batch b{G, (uint32_t)len.size(), (uint64_t)bases.size() - 1, wfs.data(), len.data(), off.data(), bases.data()};
+        cw_result r{cons.data(), coff.data(), clen.data(), st.data(), nullptr, nullptr, nullptr};
+        const int rc = cw_poa_run(eng_, &b, &r);
+        if (rc != CW_OK && rc != CW_E_CAPACITY) throw std::runtime_error(std::string("consent_amd: cw_poa_run: ") + cw_strerror(rc));
+        for (uint32_t g = 0; g < G; ++g) {
+            out[g].overflow = st[g] == CW_WIN_OVERFLOW;
+            if (!out[g].overflow) out[g].consensus.assign(cons.data() + coff[g], clen[g]);
+        }
+        return out;
+    }
+
   private:
     cw_engine* eng_ = nullptr;
     unsigned solid_;
