@@ -9,6 +9,12 @@ from .engine import (  # noqa: F401
     PafReader,
     Params,
     ReadIndex,
+    SW_ALIGNED,
+    SW_IS_REF,
+    SW_NO_INDELS,
+    SW_STOP,
+    SW_WANT_INDELS,
+    SwRows,
     SynthSpec,
     WIN_CONSENSUS,
     WIN_OVERFLOW,

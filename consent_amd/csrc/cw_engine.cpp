@@ -4,7 +4,8 @@
  * from batch and knobs), enqueue (the order of a step); engine life cycle (cw_create / cw_destroy: streams in a fixed order of creation); per-stage timing
  * and the inspection entry points; the launchers of the path's neighbours (pile extraction, result planning, read re-assembly); host batches (cw_submit /
  * cw_wait) and the loop that runs a batch again with a larger plan (cw_run, cw_run_device_sync); the POA stage alone on a batch of groups (cw_poa_run_device,
- * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run).
+ * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run); the re-assembly's local aligner alone on a batch of groups
+ * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h).
  * The scratch plan is cw_plan.h (host arithmetic only); the host feeders, cw_window_positions among them, are cw_hostio.cpp.
  */
 #include "cw_internal.h"
@@ -20,6 +21,7 @@
 #include "cw_pack.h"
 #include "cw_plan.h"
 #include "cw_poa_op.h"
+#include "cw_sw_op.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -49,6 +51,8 @@ constexpr size_t lds_tier_q(uint32_t waves) { return (size_t)CW_POAQ_TASK_BYTES 
 constexpr size_t lds_tier_h(uint32_t waves) { return (size_t)CW_POAH_TASK_BYTES * 2 * waves; } /* two tasks per wave; six waves at most: cw_poa_h_kernel's launch bounds */
 constexpr size_t kLdsFinish = (size_t)CW_FIN_SLAB * CW_FIN_WAVES, kLdsFinishBig = CW_FIN_SLAB_OF(0);
 constexpr size_t kLdsStitch = (size_t)CW_ST_WAVES * CW_ST_SLAB; /* what the wide re-assembly kernel needs (it is given more: stitch_lds_one) */
+constexpr size_t lds_sw(int cls) { return (size_t)CW_SW_WAVES * (cls == 0 ? CW_SW_SLAB_OF(CW_SW_Q0) : CW_SW_SLAB_OF(CW_ST_QMAX)); } /* the alignment operator's two LDS instances */
+static_assert(4 * lds_sw(0) <= 163840, "cw_sw_kernel<0>: the four work-groups a CU its 128 registers allow");
 
 /* tiers M1, M2 and L are instances of cw_poa_slab_kernel: a tier's template arguments and the LDS of its work-group, PASS 0 = its own list, 1 = the overflow pass */
 template <int NC, int EC, int LC, int WAVES, int TIER, size_t LDS>
@@ -107,7 +111,8 @@ int set_kernel_attributes(const hipDeviceProp_t& prop) {
         allow(TierM1::kernel<0>(), TierM1::lds) && allow(TierM2::kernel<0>(), TierM2::lds) && allow(TierL::kernel<0>(), TierL::lds) &&
         allow(TierM1::kernel<1>(), TierM1::lds) && allow(TierM2::kernel<1>(), TierM2::lds) && allow(TierL::kernel<1>(), TierL::lds) &&
         allow((const void*)cw_finish_kernel<CW_FIN_CB, CW_FIN_WAVES, false>, kLdsFinish) && allow((const void*)cw_finish_kernel<CW_FIN_CB_BIG, 1, true>, kLdsFinishBig) &&
-        allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES>, lds_st);
+        allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES>, lds_st) &&
+        allow((const void*)cw_sw_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_kernel<1>, lds_sw(1));
     return ok ? CW_OK : CW_E_NO_DEVICE;
 }
 
@@ -430,6 +435,55 @@ int poa_device_locked(cw_engine* e, const cw_batch* groups, const cw_result* res
     return enqueue_end(e, st, sc);
 }
 
+/* CW_OK for a batch of groups whose pairs can be aligned -- and for one without sequences; nothing here touches the device */
+int validate_sw(const cw_engine* e, const cw_batch* groups, const int32_t* rows, uint32_t flags) {
+    if (!e || !groups || (flags & ~CW_SW_WANT_INDELS)) return CW_E_INVALID;
+    if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID; /* cw_max_batch_windows */
+    if (groups->n_windows == 0 || groups->n_seqs == 0) return groups->n_seqs == 0 ? CW_OK : CW_E_INVALID; /* (sequences belong to groups) */
+    if (!rows || !groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
+    return CW_OK;
+}
+
+/* the body of cw_sw_run_device; the caller holds e->mu.  The order of such a run: sw_order (three small launches), then the alignment launches by query class,
+   one after the other on st: sw_align (up to CW_SW_Q0 bases), sw_align_wide (up to CW_ST_QMAX), sw_align_long (beyond: ends at once when there is no such pair;
+   the order kernel's counts stay on the device, so nothing here waits for it).  The plan lives in the engine's one scratch allocation, like a window run's and a
+   POA run's: runs on one engine are serialised by its mutex and ordered on its stream (or by the caller, include/consent_amd.h "Threading"), so none of them is
+   in flight while another's plan is bound.  (stitch_scratch is cw_stitch_device's alone: nothing here touches it.) */
+int run_sw_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, void* hip_stream) {
+    int rc = validate_sw(e, groups, rows, flags);
+    if (rc || groups->n_seqs == 0) return rc;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    const uint32_t S = groups->n_seqs;
+    const SwPlan p = plan_sw(groups->n_windows, S, groups->n_words, e->cus, flags); /* exact: no run with a larger plan follows */
+    if ((rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) != CW_OK) return rc;
+    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records: the inspection entry points and the re-run loop's look at the last run refuse (cw_debug_win_info, cw_debug_solid_table) or find nothing to do (grow_if_that_helps, decay_scale) */
+    uint8_t* base = (uint8_t*)e->scratch;
+    SwArgs a;
+    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.n_seqs = S; a.rows = rows; a.flags = flags;
+    a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
+    a.dir = p.dir_bytes ? (int8_t*)(base + p.dir) : nullptr; a.dir_bytes = p.dir_bytes;
+    a.gref = base + p.gref; a.lstate = base + p.lstate;
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_SW_CTR_WORDS * 4, st));
+    const uint32_t og = (S + 255u) / 256u;
+    stage(e, st, "sw_order", [&] {
+        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 0);
+        cw_sw_order_kernel<<<1, 256, 0, st>>>(a, 1);
+        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 2);
+    });
+    stage(e, st, "sw_align", [&] { cw_sw_kernel<0><<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(a); });
+    stage(e, st, "sw_align_wide", [&] { cw_sw_kernel<1><<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(a); });
+    stage(e, st, "sw_align_long", [&] { cw_sw_long_kernel<<<p.wgs_long, 64, 0, st>>>(a); });
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -581,6 +635,57 @@ int cw_poa_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
         if (ok && clen[g]) memcpy(r->cons + r->cons_off[g], back.data() + o_cons + coff[g], clen[g]);
     }
     return rc;
+}
+
+int cw_sw_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, void* hip_stream) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_sw_locked(e, groups, rows, flags, hip_stream);
+}
+
+/* Host buffers in, host buffers out, synchronous: the batch goes up (into the buffer cw_poa_run uses for its own), cw_sw_run_device on the engine's stream, the
+   rows come back.  The engine's mutex is held throughout: the device buffers are the engine's. */
+int cw_sw_run(cw_engine* e, const cw_batch* b, int32_t* rows, uint32_t flags) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = validate_sw(e, b, rows, flags);
+    if (rc || b->n_seqs == 0) return rc;
+    const uint32_t G = b->n_windows, S = b->n_seqs;
+    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
+    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
+    for (uint32_t s = 0; s < S; ++s)
+        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
+    size_t o = 0;
+    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4);
+    const size_t in_bytes = o, out_bytes = (size_t)S * CW_SW_ROW * 4;
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    uint8_t* din = (uint8_t*)e->poa_in;
+    hipStream_t st = e->stream;
+    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
+    cw_batch db = *b;
+    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
+    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
+    if ((rc = run_sw_locked(e, &db, (int32_t*)e->poa_out, flags, st)) != CW_OK) return rc;
+    CW_HIP(hipMemcpyAsync(rows, e->poa_out, out_bytes, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    for (uint32_t s = 0; s < S; ++s) if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) rc = CW_E_CAPACITY;
+    return rc;
+}
+
+/* Debug/inspection (cw_private.h): what plan_sw would allocate, part by part, and its grids (host arithmetic only). */
+int cw_debug_sw_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t flags, uint64_t* out10) {
+    if (!out10 || cus < 1 || (flags & ~CW_SW_WANT_INDELS)) return CW_E_INVALID;
+    const SwPlan p = plan_sw(n_groups, n_seqs, n_words, cus, flags);
+    const uint64_t v[10] = {p.total, (uint64_t)p.gref, (uint64_t)(p.lstate - p.gref), (uint64_t)(p.dir - p.lstate), (uint64_t)(p.total - p.dir),
+                            p.wgs0, p.wgs1, p.wgs_long, p.dir_waves, p.dir_bytes};
+    for (int i = 0; i < 10; ++i) out10[i] = v[i];
+    return CW_OK;
 }
 
 /* Debug/inspection (cw_private.h): what plan_poa would allocate, component by component (host arithmetic only). */

@@ -10,6 +10,7 @@
 #include "cw_env.h"
 #include "cw_index.h"  /* CW_EXG_SLOTS; with each of these: cw_device.h (the records' sizes, CW_TIERS) and include/consent_amd.h */
 #include "cw_poa_q.h"  /* slab and graph sizes of every tier (cw_poa.h comes with it) */
+#include "cw_sw_op.h"  /* the alignment operator's per-wave sizes (cw_stitch.h comes with it) */
 #include "cw_finish.h" /* CW_FIN_*.  (These three are kernel headers, taken for their size macros: nothing here runs on the device, but a translation unit that includes this one is still a HIP one) */
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -180,6 +181,42 @@ static inline ScratchPlan plan_poa(uint32_t n_groups, uint32_t n_seqs, uint64_t 
     put(p.exg, 0);
     put(p.tdbg, getenv("CW_TASK_TRACE") ? (size_t)p.task_cap * 16 : 0);
     put(p.finvis, 0); put(p.finretry, 0); put(p.finbig, 0);
+    p.total = o;
+    return p;
+}
+
+/* The plan of an alignment run (cw_sw_run, cw_sw_op.h): n_seqs sequences in n_groups groups, at most a pair per sequence.  Exact -- every part is a function of
+   the batch's counts, the device and the flags, so there is no run with a larger plan: the order kernel's counters, a reference index and a place in the order
+   per sequence, and per wave of the grids the unpacked long reference (cw_sw_kernel), the long launch's buffers and sweep state, and -- only under
+   CW_SW_WANT_INDELS -- the banded traceback's CW_ST_DIR_BYTES.  The three alignment launches follow one another on one stream and share the per-wave parts, so
+   those are sized for the largest grid.  Grids: class 0 (128 registers, 29 KB of LDS a work-group) four work-groups a CU, class 1 one, the long launch one
+   wave a work-group, none larger than the batch has sequences; with the indel totals the grids stop at the stitch's CW_ST_MAX_WGS work-groups, 1 MiB a wave
+   being what it is.  The sizes do not depend on the number of bases: a pair's buffers are its wave's. */
+struct SwPlan {
+    size_t ctr, seq_ref, order, gref, lstate, dir, total;
+    uint32_t wgs0, wgs1, wgs_long, dir_waves, dir_bytes;
+};
+static inline SwPlan plan_sw(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t flags) {
+    (void)n_groups; (void)n_words;
+    SwPlan p;
+    memset(&p, 0, sizeof(p));
+    const bool indels = (flags & CW_SW_WANT_INDELS) != 0u;
+    const uint32_t by_seqs = (n_seqs + CW_SW_WAVES - 1) / CW_SW_WAVES;
+    const uint32_t most0 = indels ? std::min<uint32_t>((uint32_t)cus * 4u, CW_ST_MAX_WGS) : (uint32_t)cus * 4u;
+    const uint32_t most1 = indels ? std::min<uint32_t>((uint32_t)cus, CW_ST_MAX_WGS) : (uint32_t)cus;
+    p.wgs0 = std::max(1u, std::min(by_seqs, most0));
+    p.wgs1 = std::max(1u, std::min(by_seqs, most1));
+    p.wgs_long = std::max(1u, std::min<uint32_t>(n_seqs, CW_SW_LONG_MAX_WGS));
+    p.dir_bytes = indels ? CW_ST_DIR_BYTES : 0u;
+    p.dir_waves = indels ? std::max(std::max(p.wgs0, p.wgs1) * CW_SW_WAVES, p.wgs_long) : 0u;
+    size_t o = 0;
+    auto put = [&](size_t& slot, size_t bytes) { slot = o; o = align_up(o + bytes, 256); };
+    put(p.ctr, (size_t)CW_SW_CTR_WORDS * 4);
+    put(p.seq_ref, (size_t)n_seqs * 4);
+    put(p.order, (size_t)n_seqs * 4);
+    put(p.gref, (size_t)std::max(p.wgs0, p.wgs1) * CW_SW_WAVES * CW_SW_GREF_BYTES);
+    put(p.lstate, (size_t)p.wgs_long * CW_SW_LONG_WAVE_BYTES);
+    put(p.dir, (size_t)p.dir_waves * p.dir_bytes);
     p.total = o;
     return p;
 }

@@ -32,6 +32,11 @@ int cw_debug_plan_caps(uint32_t k, uint32_t solid, uint32_t n_windows, uint32_t 
    cw_debug_plan in the same order -- solid table, anchor blocks, the fallbacks and the finish buffers (indices 2, 13, 14) are 0 in it.  CW_E_INVALID for a
    batch whose arena would pass the 32-bit offsets, as cw_poa_run answers it. */
 int cw_debug_poa_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint64_t* out15);
+/* The scratch plan of an alignment run (cw_sw_run) of n_groups groups, n_seqs sequences and n_words packed words under `flags`, without a device: out[0] total
+   bytes, [1] the order kernel's counters + a reference index and a place in the order per sequence, [2] unpacked long references, [3] the long launch's buffers
+   and sweep state, [4] banded-traceback directions (0 without CW_SW_WANT_INDELS), [5] [6] [7] work-groups of the class-0, class-1 and long launches, [8] waves
+   that have direction scratch, [9] its bytes per wave.  CW_E_INVALID for flags cw_sw_run refuses. */
+int cw_debug_sw_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t flags, uint64_t* out10);
 /* cw_max_batch_windows of an engine that cw_configure(max_template_len) will be called on (the native driver sizes its jobs before it has engines) */
 uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len);
 

@@ -1,0 +1,235 @@
+/*
+ * cw_sw_op.h -- the re-assembly's local aligner as a batched operator (cw_sw_run / cw_sw_run_device, include/consent_amd.h): one wave per
+ * (query, reference) pair around the device functions of cw_stitch.h (st_align over the striped register sweeps and st_sweep_mem, st_banded_indels),
+ * which are unchanged -- and so is cw_stitch_kernel.
+ *
+ *   cw_sw_order_kernel  three small launches (phase 0, 1, 2) over the sequences of the batch: a sequence's reference is its group's first sequence; rows that
+ *                       need no alignment (the reference's own, a pair beyond a capacity, an empty query or reference) are written at once; the others are
+ *                       pairs, counted per (launch class, cost class) and handed out costliest first -- a launch lasts as long as its last-started long pair
+ *                       (cw_stitch_order_kernel's reason).  Launch classes: 0 = query of at most CW_SW_Q0 bases (sweeps of 1..5 registers a slot: 128 registers,
+ *                       four waves a SIMD), 1 = up to CW_ST_QMAX (the full ladder: one wave a SIMD), 2 = up to CW_STH_QMAX (st_sweep_mem, state in global memory).
+ *   cw_sw_kernel<CLS>   classes 0 and 1: query codes and the reversed prefix in the wave's LDS slab, the reference there too up to CW_ST_RMAX bases and in the
+ *                       wave's global scratch beyond; st_align, then under CW_SW_WANT_INDELS st_banded_indels (rows in LDS, directions in the wave's
+ *                       CW_ST_DIR_BYTES of global scratch), then the row.
+ *   cw_sw_long_kernel   class 2: one wave a work-group, every buffer and the sweep's state in the wave's global scratch (CW_SW_LONG_WAVE_BYTES); always
+ *                       enqueued, ends at once when the order kernel counted no such pair.
+ *
+ * The three alignment launches run one after the other on one stream, so they share the per-wave direction scratch and reference scratch.  cw_plan.h plan_sw
+ * sizes everything; cw_engine.cpp run_sw_locked launches by it.
+ */
+#ifndef CW_SW_OP_H
+#define CW_SW_OP_H
+
+#include "cw_device.h"
+#include "cw_stitch.h"
+
+#define CW_SW_WAVES 4            /* waves per work-group of cw_sw_kernel */
+#define CW_SW_Q0 640             /* longest query of launch class 0: st_sweep_any's five-register sweep */
+#define CW_SW_GREF_BYTES 16384u  /* a reference beyond CW_ST_RMAX bases, unpacked: per wave, global (CW_SW_RMAX codes and the slack of whole words) */
+#define CW_SW_COST_CLASSES 128   /* four per power of two of query length x reference length */
+#define CW_SW_CTR_WORDS (8 + 3 * CW_SW_COST_CLASSES) /* cursors [0..2], pairs per launch class [3..5], then the classes' counts / offsets */
+#define CW_SW_LONG_MAX_WGS 256
+/* the long launch, per wave: reference codes | query codes | reversed prefix | the sweep's state */
+#define CW_SW_LONG_WAVE_BYTES ((size_t)CW_SW_GREF_BYTES + 2 * (size_t)CW_STH_QMAX + CW_STH_STATE_BYTES)
+/* per wave of cw_sw_kernel: reference codes | query codes | reversed prefix (and the traceback's directions when they are few) | traceback rows */
+#define CW_SW_SLAB_OF(QMAX) (CW_ST_RMAX + 2 * (QMAX) + CW_ST_ROWS_BYTES)
+
+static_assert(CW_SW_RMAX <= 16383, "a score is at most 2 x min(query, reference) and lives in a signed 16-bit half, as a column does");
+static_assert(((CW_SW_RMAX + 15) & ~15) <= CW_SW_GREF_BYTES && CW_SW_RMAX >= CW_ST_RMAX, "the unpacked reference and the words' slack fit the wave's scratch");
+static_assert(CW_SW_DIR_BYTES == CW_ST_DIR_BYTES, "the per-wave traceback scratch is the stitch's");
+static_assert(CW_SW_QMAX == CW_STH_QMAX, "the header's query capacity is what st_sweep_mem holds");
+static_assert(CW_SW_Q0 % 16 == 0 && CW_ST_QMAX % 16 == 0 && CW_ST_RMAX % 16 == 0 && CW_STH_QMAX % 16 == 0, "sequences are unpacked a word of 16 bases at a time");
+static_assert((uint64_t)CW_SW_QMAX * CW_SW_RMAX < (1ull << 30), "a pair's cost in 32 bits");
+
+struct SwArgs {
+    DevBatch b;          /* the groups */
+    uint32_t n_seqs;
+    int32_t* rows;       /* the caller's [n_seqs * CW_SW_ROW] */
+    uint32_t flags;
+    uint32_t* ctr;       /* CW_SW_CTR_WORDS, zero before phase 0 */
+    uint32_t* seq_ref;   /* [n_seqs] a pair's reference sequence (phase 0) */
+    uint32_t* order;     /* [n_seqs] the pairs: class 0's, then class 1's, then class 2's, each costliest first (phase 2) */
+    int8_t* dir;         /* dir_bytes per wave of the largest grid; NULL without CW_SW_WANT_INDELS */
+    uint32_t dir_bytes;
+    uint8_t* gref;       /* CW_SW_GREF_BYTES per wave of cw_sw_kernel's largest grid */
+    uint8_t* lstate;     /* CW_SW_LONG_WAVE_BYTES per work-group of cw_sw_long_kernel */
+};
+
+__device__ __forceinline__ uint32_t sw_launch_class(uint32_t m) { return m <= (uint32_t)CW_SW_Q0 ? 0u : m <= (uint32_t)CW_ST_QMAX ? 1u : 2u; }
+/* cost class of a pair of m x n cells, both > 0: 4 x floor(log2) + the next two bits -- monotone in the cost */
+__device__ __forceinline__ uint32_t sw_cost_class(uint32_t m, uint32_t n) {
+    const uint32_t c = m * n;
+    const uint32_t lg = 31u - (uint32_t)__builtin_clz(c);
+    const uint32_t frac = lg >= 2u ? (c >> (lg - 2u)) & 3u : 0u;
+    return lg * 4u + frac; /* < 4 * 30 + 4 */
+}
+
+__device__ __forceinline__ void sw_write_row(int32_t* row, int score, int rb, int re, int qb, int qe, unsigned ins, unsigned del, int status) {
+    row[CW_SW_SCORE] = score; row[CW_SW_REF_BEGIN] = rb; row[CW_SW_REF_END] = re; row[CW_SW_QUERY_BEGIN] = qb; row[CW_SW_QUERY_END] = qe;
+    row[CW_SW_INS] = (int32_t)ins; row[CW_SW_DEL] = (int32_t)del; row[CW_SW_STATUS] = status;
+}
+
+/* phase 0: one thread per sequence -- its group by bisection, its row if that needs no alignment, its class count otherwise
+   phase 1: one work-group -- the classes' offsets in order[], launch class by launch class, costliest first; pairs per launch class
+   phase 2: one thread per sequence -- a pair takes the next place of its class */
+__global__ void __launch_bounds__(256) cw_sw_order_kernel(SwArgs a, int phase) {
+    uint32_t* const cls_ctr = a.ctr + 8;
+    if (phase == 1) {
+        if (threadIdx.x == 0 && blockIdx.x == 0) {
+            uint32_t run = 0;
+            for (int lc = 0; lc < 3; ++lc) {
+                const uint32_t before = run;
+                for (int c = CW_SW_COST_CLASSES - 1; c >= 0; --c) { const uint32_t k = cls_ctr[lc * CW_SW_COST_CLASSES + c]; cls_ctr[lc * CW_SW_COST_CLASSES + c] = run; run += k; }
+                a.ctr[3 + lc] = run - before;
+            }
+        }
+        return;
+    }
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= a.n_seqs) return;
+    if (phase == 0) {
+        /* the group of s: the last g with win_first_seq[g] <= s (empty groups share their successor's first sequence) */
+        uint32_t lo = 0, hi = a.b.n_windows; /* win_first_seq[lo] <= s < win_first_seq[hi] = n_seqs */
+        while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (a.b.win_first_seq[mid] <= s) lo = mid; else hi = mid; }
+        const uint32_t r = a.b.win_first_seq[lo];
+        const uint32_t m = a.b.seq_len[s], n = a.b.seq_len[r];
+        int32_t* row = a.rows + (size_t)s * CW_SW_ROW;
+        a.seq_ref[s] = 0xFFFFFFFFu;
+        if (s == r) { sw_write_row(row, 0, 0, -1, 0, -1, 0, 0, CW_SW_IS_REF); return; }
+        if (m > (uint32_t)CW_SW_QMAX || n > (uint32_t)CW_SW_RMAX) { sw_write_row(row, 0, 0, -1, 0, -1, 0, 0, CW_SW_STOP); return; }
+        if (m == 0u || n == 0u) { sw_write_row(row, 0, 0, -1, 0, -1, 0, 0, CW_SW_ALIGNED); return; }
+        a.seq_ref[s] = r;
+        atomicAdd(&cls_ctr[sw_launch_class(m) * CW_SW_COST_CLASSES + sw_cost_class(m, n)], 1u);
+        return;
+    }
+    const uint32_t r = a.seq_ref[s];
+    if (r == 0xFFFFFFFFu) return;
+    const uint32_t m = a.b.seq_len[s], n = a.b.seq_len[r];
+    a.order[atomicAdd(&cls_ctr[sw_launch_class(m) * CW_SW_COST_CLASSES + sw_cost_class(m, n)], 1u)] = s;
+}
+
+/* 2-bit words to one code a byte, a word of 16 bases per lane and step; writes whole words: dst holds len rounded up to 16 */
+__device__ __forceinline__ void sw_unpack(uint8_t* dst, const uint32_t* words, uint32_t len, int lane) {
+    const uint32_t nw = (len + 15u) >> 4;
+    for (uint32_t w = (uint32_t)lane; w < nw; w += 64u) {
+        const uint32_t x = words[w];
+        uint32_t* d = (uint32_t*)(dst + 16u * w);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { /* bases 4k .. 4k+3 of the word: its byte 3-k, most significant pair first */
+            const uint32_t by = (x >> (24 - 8 * k)) & 0xFFu;
+            d[k] = ((by >> 6) & 3u) | (((by >> 4) & 3u) << 8) | (((by >> 2) & 3u) << 16) | ((by & 3u) << 24);
+        }
+    }
+}
+
+/* the sweeps of a launch class: class 0 is st_sweep_any's ladder up to its five-register instance (what a 128-register kernel holds), class 1 the whole
+   ladder, class 2 the last launch's (st_sweep_mem beyond 640 positions) */
+template <int CLS, bool TERM>
+__device__ __forceinline__ StSweep sw_sweep(const uint8_t* q, int m, const uint8_t* r, int r_first, int r_last_excl, int step, int terminate, int lane, uint8_t* state) {
+    if constexpr (CLS == 2) return st_sweep_any<true, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane, state);
+    else if constexpr (CLS == 1) return st_sweep_any<false, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane, state);
+    else {
+        m = st_uni(m);
+        if (m <= 128) return st_sweep_st2<1, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
+        if (m <= 256) return st_sweep_st2<2, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
+        if (m <= 384) return st_sweep_st2<3, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
+        if (m <= 512) return st_sweep_st2<4, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
+        return st_sweep_st2<5, TERM>(q, m, r, r_first, r_last_excl, step, terminate, lane);
+    }
+}
+
+/* st_align over a launch class's sweeps (classes 1 and 2: st_align<false> and st_align<true> themselves) */
+template <int CLS>
+__device__ __forceinline__ StAlign sw_align(const uint8_t* qfw, int m, uint8_t* qrv, const uint8_t* ref, int n, int lane, uint8_t* state) {
+    if constexpr (CLS == 2) return st_align<true>(qfw, m, qrv, ref, n, lane, state);
+    else if constexpr (CLS == 1) return st_align<false>(qfw, m, qrv, ref, n, lane, state);
+    else {
+        StAlign a{0, 0, -1, 0, -1};
+        m = st_uni(m); n = st_uni(n);
+        if (m <= 0 || n <= 0) return a;
+        const StSweep fw = sw_sweep<0, false>(qfw, m, ref, 0, n, 1, -1, lane, state);
+        a.score = fw.score;
+        if (fw.score <= 0) return a;
+        a.ref_end = fw.col; a.query_end = fw.row;
+        const int pm = fw.row + 1;
+        for (int x = lane; x < pm; x += 64) qrv[x] = qfw[fw.row - x];
+        st_mem_sync();
+        const StSweep bw = sw_sweep<0, true>(qrv, pm, ref, fw.col, -1, -1, fw.score, lane, state);
+        a.ref_begin = bw.col; a.query_begin = fw.row - bw.row;
+        return a;
+    }
+}
+
+/* one pair on one wave, its buffers in place: align, the indel totals when asked for, the row */
+template <int CLS>
+__device__ __forceinline__ void sw_pair(const SwArgs& a, uint32_t s, uint8_t* refc, uint8_t* qfw, uint8_t* qrv, uint32_t qrv_bytes, bool qrv_lds, uint8_t* rows, int8_t* dirbuf, uint8_t* state, int lane) {
+    const uint32_t r = st_uni(a.seq_ref[s]);
+    const uint32_t m = st_uni(a.b.seq_len[s]), n = st_uni(a.b.seq_len[r]);
+    sw_unpack(refc, a.b.bases + a.b.seq_word_off[r], n, lane);
+    sw_unpack(qfw, a.b.bases + a.b.seq_word_off[s], m, lane);
+    st_mem_sync();
+    const StAlign al = sw_align<CLS>(qfw, (int)m, qrv, refc, (int)n, lane, state);
+    unsigned ins = 0, del = 0;
+    int status = CW_SW_ALIGNED;
+    if ((a.flags & CW_SW_WANT_INDELS) && al.score > 0) {
+        /* the directions go to the reversed prefix's buffer when it is LDS and they fit, as in the stitch; where they live changes no number */
+        if (!st_banded_indels(refc + al.ref_begin, al.ref_end - al.ref_begin + 1, qfw + al.query_begin, al.query_end - al.query_begin + 1, al.score, rows, CW_ST_ROWS_BYTES,
+                              dirbuf, a.dir_bytes, &ins, &del, lane, qrv_lds ? (int8_t*)qrv : nullptr, qrv_lds ? qrv_bytes : 0u)) {
+            ins = 0; del = 0; status = CW_SW_NO_INDELS;
+        }
+    }
+    if (lane == 0) sw_write_row(a.rows + (size_t)s * CW_SW_ROW, al.score, al.ref_begin, al.ref_end, al.query_begin, al.query_end, ins, del, status);
+    st_mem_sync(); /* the next pair's unpacking overwrites what the traceback's lane 0 read */
+}
+
+/* CLS 0: 128 registers (the five-register sweep is its widest: four waves a SIMD, and the LDS of four work-groups a CU); CLS 1: whatever the sixteen-register
+   sweep takes (one wave a SIMD, as cw_stitch_kernel's wide instance) */
+template <int CLS>
+__global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_sw_kernel(SwArgs a) {
+    constexpr int QMAX = CLS == 0 ? CW_SW_Q0 : CW_ST_QMAX;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint8_t* const slab = lds + (size_t)wave * CW_SW_SLAB_OF(QMAX);
+    uint8_t* const ref_lds = slab;              /* CW_ST_RMAX reference codes */
+    uint8_t* const qfw = ref_lds + CW_ST_RMAX;  /* QMAX query codes           */
+    uint8_t* const qrv = qfw + QMAX;            /* QMAX reversed prefix       */
+    uint8_t* const rows = qrv + QMAX;           /* CW_ST_ROWS_BYTES           */
+    const size_t wv = (size_t)blockIdx.x * CW_SW_WAVES + wave;
+    uint8_t* const ref_glb = a.gref + wv * CW_SW_GREF_BYTES;
+    int8_t* const dirbuf = a.dir ? a.dir + wv * a.dir_bytes : nullptr;
+    const uint32_t n_pairs = st_uni(a.ctr[3 + CLS]), base = CLS == 0 ? 0u : st_uni(a.ctr[3]);
+    for (;;) {
+        uint32_t pi = 0;
+        if (lane == 0) pi = atomicAdd(a.ctr + CLS, 1u);
+        pi = (uint32_t)cw_lane_value((int)pi, 0);
+        if (pi >= n_pairs) break;
+        const uint32_t s = st_uni(a.order[base + pi]);
+        const uint32_t n = st_uni(a.b.seq_len[st_uni(a.seq_ref[s])]);
+        sw_pair<CLS>(a, s, n <= (uint32_t)CW_ST_RMAX ? ref_lds : ref_glb, qfw, qrv, (uint32_t)QMAX, true, rows, dirbuf, nullptr, lane);
+    }
+}
+
+/* (compiled for 256 registers, two waves a SIMD: at the last launch's 128 of cw_stitch_kernel the memory-state sweep spills 90 registers into its column loop --
+   there a launch that normally finds nothing to do, here the path of every long query) */
+__global__ void __launch_bounds__(64, 2) cw_sw_long_kernel(SwArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t rows[CW_ST_ROWS_BYTES];
+    const int lane = threadIdx.x & 63;
+    const uint32_t n_pairs = st_uni(a.ctr[5]);
+    if (n_pairs == 0u) return; /* normally */
+    const uint32_t base = st_uni(a.ctr[3]) + st_uni(a.ctr[4]);
+    uint8_t* const mem = a.lstate + (size_t)blockIdx.x * CW_SW_LONG_WAVE_BYTES;
+    uint8_t* const refc = mem;
+    uint8_t* const qfw = refc + CW_SW_GREF_BYTES;
+    uint8_t* const qrv = qfw + CW_STH_QMAX;
+    uint8_t* const state = qrv + CW_STH_QMAX;
+    int8_t* const dirbuf = a.dir ? a.dir + (size_t)blockIdx.x * a.dir_bytes : nullptr;
+    for (;;) {
+        uint32_t pi = 0;
+        if (lane == 0) pi = atomicAdd(a.ctr + 2, 1u);
+        pi = (uint32_t)cw_lane_value((int)pi, 0);
+        if (pi >= n_pairs) break;
+        sw_pair<2>(a, st_uni(a.order[base + pi]), refc, qfw, qrv, 0u, false, rows, dirbuf, state, lane);
+    }
+}
+
+#endif

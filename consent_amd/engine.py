@@ -9,6 +9,11 @@ import os
 import numpy as np
 
 WIN_CONSENSUS, WIN_TEMPLATE, WIN_OVERFLOW = 0, 1, 2
+# cw_sw_run (include/consent_amd.h): a row's status, its columns, the flag, the capacities
+SW_ALIGNED, SW_NO_INDELS, SW_STOP, SW_IS_REF = 0, 1, 2, 3
+SW_SCORE, SW_REF_BEGIN, SW_REF_END, SW_QUERY_BEGIN, SW_QUERY_END, SW_INS, SW_DEL, SW_STATUS, SW_ROW = 0, 1, 2, 3, 4, 5, 6, 7, 8
+SW_WANT_INDELS = 1
+SW_QMAX, SW_RMAX, SW_DIR_BYTES = 32768, 16383, 1 << 20
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -128,6 +133,10 @@ def _load(p):
         lib.cw_poa_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result)]
         lib.cw_poa_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.c_void_p]
         lib.cw_debug_poa_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p]
+    if hasattr(lib, "cw_sw_run"):  # (a library built before the alignment operator has no such entries)
+        lib.cw_sw_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_uint32]
+        lib.cw_sw_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.cw_debug_sw_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p]
     lib.cw_submit.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.POINTER(C.c_int)]
     lib.cw_wait.argtypes = [C.c_void_p, C.c_int]
     lib.cw_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -452,6 +461,23 @@ def alloc_poa_results(batch, slot_bytes=None):
     return WindowResults(np.zeros(max(int(cons_off[-1]), 1), np.uint8), cons_off, np.zeros(G, np.uint32), np.full(G, 255, np.uint8))
 
 
+class SwRows:
+    """What Engine.sw returns: `rows`, an (n_seqs, SW_ROW) int32 array with one row per sequence of the batch (columns SW_SCORE .. SW_STATUS), and the map
+    from (group, member) -- member 0 is the group's reference -- to its row."""
+
+    def __init__(self, rows, win_first_seq, rc=0):
+        self.rows, self.win_first_seq, self.rc = rows, win_first_seq, rc
+
+    def index(self, group, member):
+        s = int(self.win_first_seq[group]) + member
+        if member < 0 or s >= int(self.win_first_seq[group + 1]):
+            raise IndexError(f"group {group} has no member {member}")
+        return s
+
+    def row(self, group, member):
+        return self.rows[self.index(group, member)]
+
+
 def _result_struct(r):
     return Result(
         _ptr(r.cons), _ptr(r.cons_off), _ptr(r.cons_len), _ptr(r.status),
@@ -520,6 +546,22 @@ class Engine:
     def poa_device(self, batch_struct, result_struct, stream=None):
         """cw_poa_run_device: as run_device, device pointers in both structs (the result's solid fields NULL), asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_poa_run_device(self.handle, C.byref(batch_struct), C.byref(result_struct), stream), "cw_poa_run_device")
+
+    def sw(self, groups, want_indels=False):
+        """Only the local alignment (cw_sw_run): `groups` is a list of lists of ACGT strings (or a HostBatch of them); every group's first sequence is its
+        reference, every other one a query aligned locally against it.  Returns SwRows: .rows is (n_seqs, SW_ROW) int32 -- score, ref_begin, ref_end,
+        query_begin, query_end (inclusive, 0-based; ends -1 when nothing aligns), ins, del (0 unless want_indels), status (SW_ALIGNED, SW_NO_INDELS, SW_STOP
+        for a pair beyond SW_QMAX / SW_RMAX, SW_IS_REF for the reference's own row) -- and .row(group, member) finds a row; .rc is cw_sw_run's return value
+        (0, or -4 when a pair stopped)."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        rows = np.zeros((len(batch.seq_len), SW_ROW), np.int32)
+        b = batch.c_struct()
+        rc = _check(self.lib, self.lib.cw_sw_run(self.handle, C.byref(b), _ptr(rows), SW_WANT_INDELS if want_indels else 0), "cw_sw_run", allow_capacity=True)
+        return SwRows(rows, batch.win_first_seq, rc)
+
+    def sw_device(self, batch_struct, rows_ptr, flags=0, stream=None):
+        """cw_sw_run_device: device pointers in the batch struct, `rows_ptr` a device array of n_seqs * SW_ROW int32; asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_sw_run_device(self.handle, C.byref(batch_struct), rows_ptr, flags, stream), "cw_sw_run_device")
 
     def extract_piles(self, reads, overlaps, jobs, k):
         """Device-side getAlignmentWindowsSequences (cw_extract_piles_device).  `reads` is a HostBatch-like packing of the read

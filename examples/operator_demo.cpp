@@ -1,4 +1,4 @@
-// Minimal C++ caller of the engine through the adapter: one synthetic window, prints the consensus.
+// Minimal C++ caller of the engine through the adapter: one synthetic window, prints the consensus -- and how the first members of the pile lie against it.
 // Build: g++ -std=c++17 -Iinclude examples/operator_demo.cpp -Lconsent_amd -lconsent_amd -Wl,-rpath,$PWD/consent_amd -o /tmp/operator_demo
 #include <cstdio>
 #include <random>
@@ -29,6 +29,14 @@ int main() {
         size_t same = 0;
         for (size_t i = 0; i < std::min(truth.size(), res[0].consensus.size()); ++i) same += std::toupper(res[0].consensus[i]) == truth[i];
         std::printf("positions equal to the truth (no realignment): %zu / %zu\n", same, truth.size());
+        // members against the consensus (cw_sw_run): where each lies on it, its score, its inserted and deleted bases
+        std::vector<std::vector<std::string>> groups(1);
+        groups[0].push_back(res[0].consensus);
+        for (int i = 0; i < 4; ++i) groups[0].push_back(piles[0][i]);
+        auto rows = eng.alignToFirst(groups, /*want_indels*/ true);
+        for (size_t m = 1; m < rows[0].size(); ++m)
+            std::printf("member %zu: consensus %d..%d, member %d..%d, score %d, ins %d, del %d\n", m - 1, rows[0][m][CW_SW_REF_BEGIN], rows[0][m][CW_SW_REF_END],
+                        rows[0][m][CW_SW_QUERY_BEGIN], rows[0][m][CW_SW_QUERY_END], rows[0][m][CW_SW_SCORE], rows[0][m][CW_SW_INS], rows[0][m][CW_SW_DEL]);
     } catch (const std::exception& e) {
         std::printf("engine unavailable: %s\n", e.what());
         return 2;

@@ -11,6 +11,8 @@
  *                               -- batched over windows, because one window per call cannot feed a GPU.
  *   cw_poa_run / cw_poa_run_device <- only the POA of that operator (BMEAN's consensus of one segment's pieces, A4d of SURVEY), batched over
  *                               groups of sequences: for callers that have their segments -- or racon-style windows, amplicon / UMI families -- in hand.
+ *   cw_sw_run / cw_sw_run_device <- StripedSmithWaterman::Aligner::Align as alignConsensus calls it (correctionAlignment.cpp:90, :110), batched over
+ *                               (query, reference) pairs: the local aligner of cw_stitch_device on its own.
  *   cw_window_positions      <- getAlignmentWindowsPositions (alignmentWindows.cpp:27-85), host
  *   cw_extract_piles_device  <- getAlignmentWindowsSequences (alignmentWindows.cpp:87-149) evaluated on the device
  *   cw_stitch_device         <- alignConsensus + trimRead + dropRead (correctionAlignment.cpp:47-140, utils.cpp:96-128, :71-73)
@@ -190,6 +192,38 @@ int cw_run_device(cw_engine* e, const cw_batch* batch, const cw_result* result, 
 #define CW_POA_SLOT_BYTES(longest_member) (2u * (uint32_t)(longest_member) + 2u)
 int cw_poa_run_device(cw_engine* e, const cw_batch* groups, const cw_result* result, void* hip_stream);
 int cw_poa_run(cw_engine* e, const cw_batch* groups, const cw_result* result);
+
+/* ---- only the local alignment: every sequence of a group against the group's first ---------------------------------------------------------------
+ * `groups` is a cw_batch read a third way: "window" g is a GROUP, its first sequence the REFERENCE (as a window's first sequence is its template), every other
+ * sequence of it a QUERY that is aligned locally against that reference by the aligner of the read re-assembly (cw_stitch_device; scores and tie rules in
+ * include/cw_policy.h, CW_SSW_*: match 2, mismatch 2, a gap 3 + 1 per further base, the first best end wins).  Sequences are packed as ever.  params.* is not read.
+ * `rows` holds CW_SW_ROW int32 per SEQUENCE of the batch, row s for sequence s: score, the inclusive 0-based ends of the alignment on the reference and on the
+ * query, the totals of inserted (query-only) and deleted (reference-only) bases between them, a status.  Nothing aligns (or the query or the reference is
+ * empty): score 0, begins 0, ends -1, status CW_SW_ALIGNED.  The reference's own row: the same numbers with status CW_SW_IS_REF.  A group of one sequence or
+ * of none is valid.
+ * Indel totals are computed only under CW_SW_WANT_INDELS (0 otherwise): a banded traceback between the ends, serial in parts.  Its band starts at
+ * |reference span - query span| + 1 and doubles until the banded score reaches the alignment's; a band of b over a reference span of R and a query span of Q
+ * bases needs 3 x min(2b + 1, R + 1) x Q direction bytes -- and 12 x min(2b + 3, R + 3) more, rounded up to 16, once those exceed 4096 (b > 169) -- in the
+ * wave's scratch of CW_SW_DIR_BYTES.  A pair whose band outgrows that keeps its five alignment numbers, ins = del = 0, and gets status CW_SW_NO_INDELS: a
+ * function of the pair alone, never a wrong number.
+ * Capacities, each a function of the pair alone (status CW_SW_STOP, numbers as when nothing aligns; the other pairs are unaffected): a query of more than
+ * CW_SW_QMAX bases, a reference of more than CW_SW_RMAX -- a score is at most twice the shorter of the two and, like a reference column, lives in a signed
+ * 16-bit field of the sweeps.
+ * At most cw_max_batch_windows(e) groups a call; CW_E_INVALID beyond that, for flags other than CW_SW_WANT_INDELS and for NULL arguments, before anything
+ * is launched.  The scratch plan of such a run is exact: the batch runs once.
+ * cw_sw_run_device: every pointer inside groups, and rows, is a DEVICE pointer; asynchronous on `hip_stream` (NULL = the engine's own stream); CW_OK also
+ * when pairs stop.  Threading and stream contract: cw_run_device's.
+ * cw_sw_run: host pointers, synchronous; CW_E_CAPACITY when at least one row has CW_SW_STOP (the other rows stand).  CW_SW_NO_INDELS is not an error.
+ * One engine alternates window runs, POA runs and alignment runs freely (one scratch allocation for all).  cw_last_timings names the stages of such a run
+ * sw_order, sw_align (queries of up to 640 bases), sw_align_wide (up to 2 048), sw_align_long (beyond). */
+enum { CW_SW_SCORE, CW_SW_REF_BEGIN, CW_SW_REF_END, CW_SW_QUERY_BEGIN, CW_SW_QUERY_END, CW_SW_INS, CW_SW_DEL, CW_SW_STATUS, CW_SW_ROW = 8 };
+enum { CW_SW_ALIGNED = 0, CW_SW_NO_INDELS = 1, CW_SW_STOP = 2, CW_SW_IS_REF = 3 };
+#define CW_SW_WANT_INDELS 1u
+#define CW_SW_QMAX 32768      /* longest query    */
+#define CW_SW_RMAX 16383      /* longest reference */
+#define CW_SW_DIR_BYTES (1u << 20) /* banded traceback scratch per wave: the re-assembly's */
+int cw_sw_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows /* [n_seqs * CW_SW_ROW] */, uint32_t flags, void* hip_stream);
+int cw_sw_run(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags);
 
 /* 1 when everything the last cw_run_device on this engine launched has completed (or nothing was launched yet), 0 while it is
  * still running, 2 while it is running but past the part that fills the GPU (what is left is the tail: a few long alignment tasks on

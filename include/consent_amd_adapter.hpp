@@ -12,6 +12,7 @@
 #define CONSENT_AMD_ADAPTER_HPP
 
 #include <cstdint>
+#include <array>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -115,6 +116,37 @@ class Engine {
             out[g].overflow = st[g] == CW_WIN_OVERFLOW;
             if (!out[g].overflow) out[g].consensus.assign(cons.data() + coff[g], clen[g]);
         }
+        return out;
+    }
+
+    /* Only the local alignment (cw_sw_run): every sequence of a group against the group's first.  Row [g][m] is member m of group g: the eight numbers of
+       consent_amd.h (CW_SW_SCORE .. CW_SW_STATUS); [g][0] is the reference's own row (CW_SW_IS_REF).  A pair beyond a capacity has status CW_SW_STOP. */
+    std::vector<std::vector<std::array<int32_t, CW_SW_ROW>>> alignToFirst(const std::vector<std::vector<std::string>>& groups, bool want_indels = false) {
+        std::vector<uint32_t> wfs{0}, len, bases;
+        std::vector<uint64_t> off;
+        for (const auto& group : groups) {
+            for (const auto& s : group) {
+                const uint64_t words = (s.size() + 15) / 16;
+                off.push_back(bases.size());
+                len.push_back((uint32_t)s.size());
+                bases.resize(bases.size() + words);
+                if (words && cw_pack_sequence(s.data(), (uint32_t)s.size(), bases.data() + off.back(), words) < 0)
+                    throw std::runtime_error("consent_amd: cw_pack_sequence failed");
+            }
+            wfs.push_back((uint32_t)len.size());
+        }
+        bases.push_back(0);
+        std::vector<int32_t> rows(len.size() * CW_SW_ROW + 1);
+        cw_batch b{(uint32_t)groups.size(), (uint32_t)len.size(), (uint64_t)bases.size() - 1, wfs.data(), len.data(), off.data(), bases.data()};
+        const int rc = cw_sw_run(eng_, &b, rows.data(), want_indels ? CW_SW_WANT_INDELS : 0u);
+        if (rc != CW_OK && rc != CW_E_CAPACITY) throw std::runtime_error(std::string("consent_amd: cw_sw_run: ") + cw_strerror(rc));
+        std::vector<std::vector<std::array<int32_t, CW_SW_ROW>>> out(groups.size());
+        for (size_t g = 0; g < groups.size(); ++g)
+            for (uint32_t s = wfs[g]; s < wfs[g + 1]; ++s) {
+                std::array<int32_t, CW_SW_ROW> row;
+                for (int k = 0; k < CW_SW_ROW; ++k) row[k] = rows[(size_t)s * CW_SW_ROW + k];
+                out[g].push_back(row);
+            }
         return out;
     }
 

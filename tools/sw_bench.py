@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""Time the alignment operator alone (cw_sw_run_device, include/consent_amd.h): pairs/s and DP cells/s per shape, with and without the indel totals, with
+cw_last_timings' stages.
+
+Input is synthetic: a group is one random reference and `--per-group` queries; a query is a stretch of its reference with 8 % substitutions and one deletion
+of four bases (so the banded traceback starts at a band of 5) -- or, where the query is the longer one, the whole reference treated that way between random
+flanks.  The batch lives in device memory; a step is one cw_sw_run_device and a wait for it.  DP cells of a pair are query length x reference length: the
+forward sweep's; the reverse sweep and the traceback come on top and are not counted, for any implementation.
+
+    python tools/sw_bench.py                              # the five shapes (query x reference), each with and without indel totals
+    python tools/sw_bench.py --shape 500x600 --pairs 65536 --steps 10
+    python tools/sw_bench.py --oracle 4096                # also: so many 500 x 600 pairs through the oracle's cwo_ssw on --threads CPU threads
+
+Prints one JSON line per measurement and a markdown table (DESIGN.md section 4.8 holds the first one).
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import consent_amd as ca  # noqa: E402
+from consent_amd.engine import Batch, HostBatch  # noqa: E402
+
+SHAPES = {"24x150": 262144, "100x600": 131072, "500x600": 65536, "2000x2048": 4096, "8000x2048": 512}  # query x reference -> pairs of the default run
+
+
+def pack(codes):
+    """(n, L) 2-bit codes -> (n, ceil(L / 16)) words, most significant pair first."""
+    n, L = codes.shape
+    words = (L + 15) // 16
+    c = np.zeros((n, words * 16), np.uint32)
+    c[:, :L] = codes
+    return (c.reshape(n, words, 16) << (30 - 2 * np.arange(16, dtype=np.uint32))).sum(axis=2, dtype=np.uint64).astype(np.uint32)
+
+
+def make_groups(n_pairs, qlen, rlen, per_group, seed):
+    """(HostBatch, references (G, rlen) codes, queries (G, per_group, qlen) codes)."""
+    rng = np.random.default_rng(seed)
+    G = max(1, n_pairs // per_group)
+    refs = rng.integers(0, 4, (G, rlen), dtype=np.uint8)
+    span = min(qlen, rlen - 4) if rlen > 8 else rlen  # reference bases a query covers, before the deletion
+    src_len = span + 4 if rlen >= span + 4 else span
+    start = rng.integers(0, rlen - src_len + 1, (G, per_group))
+    src = refs[np.arange(G)[:, None, None], start[:, :, None] + np.arange(src_len)[None, None, :]]
+    cut = rng.integers(1, max(2, span - 4), (G, per_group))
+    keep = np.arange(span)[None, None, :]
+    core = np.take_along_axis(src, np.where(keep < cut[:, :, None], keep, keep + (src_len - span)), axis=2)  # four bases deleted at `cut`
+    sub = rng.random(core.shape) < 0.08
+    core = np.where(sub, (core + rng.integers(1, 4, core.shape, dtype=np.uint8)) & 3, core).astype(np.uint8)
+    queries = rng.integers(0, 4, (G, per_group, qlen), dtype=np.uint8)
+    left = (qlen - span) // 2
+    queries[:, :, left : left + span] = core
+    rw, qw = pack(refs), pack(queries.reshape(-1, qlen))
+    per = 1 + per_group
+    lens = np.tile(np.array([rlen] + [qlen] * per_group, np.uint32), G)
+    wlen = np.tile(np.array([rw.shape[1]] + [qw.shape[1]] * per_group, np.uint64), G)
+    offs = np.concatenate([[0], np.cumsum(wlen)[:-1]]).astype(np.uint64)
+    bases = np.concatenate([np.concatenate([rw[g], qw[g * per_group : (g + 1) * per_group].reshape(-1)]) for g in range(G)])
+    return HostBatch(np.arange(G + 1, dtype=np.uint32) * per, lens, offs, bases), refs, queries
+
+
+def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
+    import torch
+
+    qlen, rlen = (int(v) for v in shape.split("x"))
+    hb, _, _ = make_groups(n_pairs, qlen, rlen, per_group, seed)
+    n_pairs = len(hb.seq_len) - hb.n_windows
+    dev = torch.device("cuda", eng.device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
+
+    t_in = (up(hb.win_first_seq, np.int32), up(hb.seq_len, np.int32), up(hb.seq_word_off, np.int64), up(np.concatenate([hb.bases, np.zeros(4, np.uint32)]), np.int32))
+    t_rows = torch.zeros(len(hb.seq_len) * 8, dtype=torch.int32, device=dev)
+    b = Batch(hb.n_windows, len(hb.seq_len), len(hb.bases), t_in[0].data_ptr(), t_in[1].data_ptr(), t_in[2].data_ptr(), t_in[3].data_ptr())
+    torch.cuda.synchronize(dev)
+    times, stages = [], {}
+    for step in range(warmup + steps):
+        t0 = time.perf_counter()
+        eng.sw_device(b, C.c_void_p(t_rows.data_ptr()), flags)
+        torch.cuda.synchronize(dev)
+        if step >= warmup:
+            times.append((time.perf_counter() - t0) * 1e3)
+            for k, v in eng.timings().items():
+                stages.setdefault(k, []).append(v)
+    rows = t_rows.cpu().numpy().reshape(-1, 8)
+    q = rows[rows[:, 7] != ca.SW_IS_REF]
+    ms = float(np.median(times))
+    return {"shape": shape, "pairs": n_pairs, "indels": bool(flags), "steps": steps, "ms_per_batch": round(ms, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
+            "pairs_per_s": round(n_pairs / ms * 1e3), "dp_cells_per_s": float(f"{n_pairs * qlen * rlen / ms * 1e3:.4g}"), "mean_score": round(float(q[:, 0].mean()), 1),
+            "no_indels_rows": int((q[:, 7] == ca.SW_NO_INDELS).sum()), "stopped_rows": int((q[:, 7] == ca.SW_STOP).sum()),
+            "stage_ms": {k: round(float(np.median(v)), 3) for k, v in stages.items()}}
+
+
+def oracle_rate(n_pairs, threads, seed):
+    """n_pairs 500 x 600 pairs of the same construction through the oracle's cwo_ssw (oracle/liboracle.so) on `threads` threads: pairs/s, cells/s."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib
+
+    fn = oracle_lib.oracle().cwo_ssw
+    _, refs, queries = make_groups(n_pairs, 500, 600, 16, seed)
+    letters = np.frombuffer(b"ACGT", np.uint8)
+    work = [(letters[queries[g, k]].tobytes(), letters[refs[g]].tobytes()) for g in range(len(refs)) for k in range(queries.shape[1])]
+
+    def one(p):
+        out = np.zeros(7, np.int32)
+        fn(p[0], len(p[0]), p[1], len(p[1]), C.c_void_p(out.ctypes.data))  # (ctypes releases the interpreter lock for the call)
+        return int(out[0])
+
+    t0 = time.perf_counter()
+    with ThreadPoolExecutor(threads) as ex:
+        scores = list(ex.map(one, work, chunksize=16))
+    s = time.perf_counter() - t0
+    return {"oracle": "cwo_ssw", "shape": "500x600", "pairs": len(work), "threads": threads, "seconds": round(s, 3), "pairs_per_s": round(len(work) / s),
+            "dp_cells_per_s": float(f"{len(work) * 500 * 600 / s:.4g}"), "mean_score": round(float(np.mean(scores)), 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--shape", action="append", help="query x reference, e.g. 500x600 (repeatable; default: the five of the table)")
+    ap.add_argument("--pairs", type=int, default=0, help="pairs per batch (default: by shape)")
+    ap.add_argument("--per-group", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--seed", type=int, default=0x5A11)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--oracle", type=int, default=0, help="also time so many 500x600 pairs through the oracle on --threads CPU threads")
+    ap.add_argument("--threads", type=int, default=16)
+    a = ap.parse_args()
+    eng = ca.Engine(ca.Params(9, 4, 8, 2, 150), device=a.device)
+    rows = []
+    try:
+        for shape in a.shape or list(SHAPES):
+            for flags in (0, ca.SW_WANT_INDELS):
+                rows.append(bench_shape(eng, shape, a.pairs or SHAPES.get(shape, 16384), a.per_group, flags, a.steps, a.warmup, a.seed))
+                print(json.dumps(rows[-1]), flush=True)
+    finally:
+        eng.close()
+    if a.oracle:
+        print(json.dumps(oracle_rate(a.oracle, a.threads, a.seed)), flush=True)
+    order = ["sw_order", "sw_align", "sw_align_wide", "sw_align_long", "total"]
+    print("\n| query x reference | indel totals | pairs | ms / batch | pairs/s | DP cells/s | " + " | ".join(order) + " |")
+    print("|---|---|---|---|---|---|" + "---|" * len(order))
+    for r in rows:
+        print(f"| {r['shape']} | {'yes' if r['indels'] else 'no'} | {r['pairs']} | {r['ms_per_batch']:.2f} | {r['pairs_per_s']:.3g} | {r['dp_cells_per_s']:.3g} | "
+              + " | ".join(f"{r['stage_ms'].get(k, 0):.2f}" for k in order) + " |")
+
+
+if __name__ == "__main__":
+    main()
