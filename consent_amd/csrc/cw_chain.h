@@ -33,6 +33,30 @@
 /* the successor's index inside a chain key (length + 1 << 48 | score << 16 | this): the largest key wins, so the field is 0xFFFF - b when equal
    length and score go to the SMALLEST successor (the default) and b itself when they go to the largest (cw_policy.h CW_CHAIN_TIE) */
 #define CW_CH_BFIELD(b) (CW_CHAIN_TIE == CW_CHAIN_TIE_LARGEST_SUCCESSOR ? (uint32_t)(b) : 0xFFFFu - (uint32_t)(b))
+
+/* Which way a window went, one bit per decision of this file: a -DCW_TEST_AIDS build ORs them into prof[CW_PS_CHAIN_ROUTE] (the product's kernel has none of
+   this: its code is to stay instruction for instruction what it is, see the flush's routing rule below), and consent_amd/engine.py CHAIN_ROUTE names the same
+   bits (tests/test_chain_ref_cpu.py holds the two together).  The probes of tests/chain_probes.py say which bits they must set: tests/test_gpu_chain.py */
+enum CwChRoute : unsigned {
+    CW_CR_FAST = 1u << 0,              /* phase C in the register window (chain_window)                                   */
+    CW_CR_ROWS_LDS = 1u << 1,          /* ... with the correction rows in LDS (DELTA 1)                                   */
+    CW_CR_ROWS_FAR = 1u << 2,          /* ... with the row ids in LDS and the rows read from the block (DELTA 2)           */
+    CW_CR_PRES_LDS = 1u << 3,          /* the presence bitsets were staged in LDS (either path)                           */
+    CW_CR_WIDE_KEY = 1u << 4,          /* !narrow: the 64-bit chain key                                                   */
+    CW_CR_FAR_SCAN = 1u << 5,          /* a step looked at successors beyond a + 64 (either path): the early stop failed  */
+    CW_CR_INPLACE_ROWS = 1u << 6,      /* the in-place score: correction rows in the block                                */
+    CW_CR_INPLACE_MASKS = 1u << 7,     /* ... one-word bad masks                                                          */
+    CW_CR_INPLACE_ALL_DIRTY = 1u << 8, /* ... every dirty sequence                                                        */
+    CW_CR_INPLACE_MATRIX = 1u << 9,    /* ... the position matrix, no bitsets                                             */
+    CW_CR_EARLY_FLUSH = 1u << 10,      /* phase D flushed its queue inside the segment loop                               */
+    CW_CR_LONG_SINGLE = 1u << 11,      /* the flush wrote a one-member segment with the whole wave                        */
+    CW_CR_LONG_SLAB = 1u << 12         /* the CW_CH_SLAB_LONG instance                                                    */
+};
+#ifdef CW_TEST_AIDS
+#define CW_CH_ROUTE(ctr, cond, bits) do { if (cond) atomicOr(&(ctr)->prof[CW_PS_CHAIN_ROUTE], (unsigned long long)(bits)); } while (0)
+#else
+#define CW_CH_ROUTE(ctr, cond, bits) do { } while (0)
+#endif
 __device__ __forceinline__ int ch_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint32_t ch_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
@@ -199,6 +223,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                     }
                     if (!stop) {
                         for (uint32_t b0 = (uint32_t)a + 65u; b0 < A; b0 += 64) { /* farther successors: from LDS (written at least 64 steps ago) */
+                            CW_CH_ROUTE(sc.ctr, lane == 0, CW_CR_FAR_SCAN);
                             const uint32_t bb = b0 + (uint32_t)lane;
                             unsigned long long key = 0ull;
                             if (bb < A) {
@@ -244,6 +269,8 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
             };
             const bool fast_path = pres_lds && Nw <= 4u && (n_dirty == 0u || use_delta || far_delta);
             const unsigned long long _c0 = __builtin_readcyclecounter();
+            CW_CH_ROUTE(sc.ctr, lane == 0, (fast_path ? CW_CR_FAST | (use_delta ? CW_CR_ROWS_LDS : far_delta ? CW_CR_ROWS_FAR : 0u) : 0u) | (pres_lds ? CW_CR_PRES_LDS : 0u) |
+                                               (narrow ? 0u : CW_CR_WIDE_KEY) | (SLAB == CW_CH_SLAB_LONG ? CW_CR_LONG_SLAB : 0u));
             if (fast_path) {
                 const uint32_t dm = use_delta ? 1u : far_delta ? 2u : 0u;
 #define CW_CH_CASE(NWV)                                                                                                 \
@@ -261,16 +288,19 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                 for (uint32_t b0 = (uint32_t)a + 1u; b0 < A; b0 += 64) {
                     const uint32_t bb = b0 + (uint32_t)lane;
                     unsigned long long key = 0ull;
+                    CW_CH_ROUTE(sc.ctr, lane == 0 && b0 > (uint32_t)a + 1u, CW_CR_FAR_SCAN);
                     if (bb < A) {
                         uint32_t cnt = 0;
                         if (use_bits) {
                             if (pres_lds) { for (uint32_t x = 0; x < Nw; ++x) cnt += (uint32_t)__popcll(lpres[(size_t)a * Nw + x] & lpres[(size_t)bb * Nw + x]); }
                             else { for (uint32_t x = 0; x < Nw; ++x) cnt += (uint32_t)__popcll(gpres[(size_t)a * Nw + x] & gpres[(size_t)bb * Nw + x]); }
                             if (n_rows) { /* correction rows, in the block */
+                                CW_CH_ROUTE(sc.ctr, true, CW_CR_INPLACE_ROWS);
                                 const uint32_t row_a = growid[a], row_b = growid[bb];
                                 if (row_a != 0xFFu) cnt += gdelta[(size_t)row_a * Ap + bb];
                                 if (row_b != 0xFFu) cnt += gdelta[(size_t)row_b * Ap + (uint32_t)a];
                             } else if (has_bm) { /* bad masks: the dirty sequences that are out of order at a or at bb */
+                                CW_CH_ROUTE(sc.ctr, true, CW_CR_INPLACE_MASKS);
                                 unsigned long long mm = gbadm[a] | gbadm[bb];
                                 while (mm) {
                                     const uint32_t d = (uint32_t)__ffsll((long long)mm) - 1u;
@@ -280,6 +310,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                                     cnt += (pa_ < pb && pb != CW_NONE16) ? 1u : 0u;
                                 }
                             } else { /* every dirty sequence */
+                                CW_CH_ROUTE(sc.ctr, true, CW_CR_INPLACE_ALL_DIRTY);
                                 for (uint32_t d = 0; d < n_dirty; ++d) {
                                     const uint32_t sd = gdirty[d];
                                     const uint32_t pa_ = P[(uint32_t)a * Np + sd], pb = P[bb * Np + sd];
@@ -287,6 +318,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                                 }
                             }
                         } else {
+                            CW_CH_ROUTE(sc.ctr, true, CW_CR_INPLACE_MATRIX);
                             const uint32_t* pb_row = (const uint32_t*)(P + bb * Np);
 #pragma unroll 8
                             for (uint32_t s = 0; s < half; ++s) {
@@ -482,6 +514,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                             const uint32_t g_seg = q_seg[q], g_n = q_n[q], g_mx = q_mx[q], g_off = q_off[q];
                             const int g_ca = q_ca[q], g_cb = q_cb[q];
                             if (g_n == 1u) {
+                                CW_CH_ROUTE(sc.ctr, lane == 0, CW_CR_LONG_SINGLE);
                                 const uint32_t* words = b.bases + b.seq_word_off[s0 + q_fs[q]];
                                 const uint32_t fst = q_fst[q];
                                 for (uint32_t i = lane; i < g_mx; i += 64) sc.arena[g_off + i] = CW_ACGT(cw_base_at(words, fst + i));
@@ -602,7 +635,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                            instead of three per task (same-address atomics from 2048 waves serialise in L2) */
                         const unsigned long long sm = __ballot(serial);
                         const uint32_t n_new = (uint32_t)__popcll(sm);
-                        if (q_cnt + n_new > 64u) { flush(); }
+                        if (q_cnt + n_new > 64u) { CW_CH_ROUTE(sc.ctr, lane == 0, CW_CR_EARLY_FLUSH); flush(); }
                         if (serial) {
                             const uint32_t qi = q_cnt + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
                             q_off[qi] = abs_off; q_need[qi] = need; q_seg[qi] = (uint16_t)seg; q_ca[qi] = (int16_t)ca; q_cb[qi] = (int16_t)cb;

@@ -90,6 +90,7 @@ enum CwProfSlot : int {
     CW_PS_LONGEST = 36,                                       /* + t: the longest single task of slab tier t */
     CW_PS_SORT_CLOCK = 41,                                    /* wall clock at the tier sort: time base of the task trace */
     CW_PS_CHAIN_ANCHORS = 42, CW_PS_CHAIN_DIRTY = 43, CW_PS_CHAIN_WINDOWS = 44, /* chain kernel: anchors, dirty sequences, windows */
+    CW_PS_CHAIN_ROUTE = 45,                                   /* -DCW_TEST_AIDS: the CW_CR_* bits of every window of the batch, ORed (cw_chain.h; as CW_PS_IDX_ROUTE) */
     CW_PS_L_CHUNK_ROWS = 46, CW_PS_L_ROWS = 47,               /* tier L's fills: rows x direction-word chunks, rows */
     CW_PS_CHAIN_STAGE = 48, CW_PS_CHAIN_FLUSH = 49,           /* chain kernel, cycles: stage-in, segment flush */
     CW_PS_CHAIN_FIX_WINDOWS = 50, CW_PS_CHAIN_FIX_ROWS = 51, CW_PS_CHAIN_BAD_MASKS = 52, /* ... windows with correction rows, those rows, windows with bad masks */
@@ -109,7 +110,7 @@ static_assert(CW_PS_LONGEST == 36 && CW_PS_LONGEST + 4 < CW_PS_SORT_CLOCK && CW_
 static_assert(CW_PS_L_CHUNK_ROWS == 46 && CW_PS_L_ROWS == 47, "tier L's fill-row counters");
 static_assert(CW_PS_DIAG == 72 && CW_PS_DIAG_STRIDE == 12 && CW_PS_DIAG + CW_PS_DIAG_STRIDE * 4 == CW_PS_VERIFY_MEMBERS, "diag slots end where the verify slots begin");
 static_assert(CW_PS_VERIFY_MEMBERS == 120 && CW_PS_VERIFY_COLS == 125 && CW_PS_VERIFY_COLS < CW_PROF_SLOTS, "verify slots: tools/verify_codes.py reads them by number");
-static_assert(CW_PS_CHAIN_ANCHORS == 42 && CW_PS_CHAIN_STAGE == 48 && CW_PS_CHAIN_SLOW_CYCLES == 54 && CW_PS_IDX_STAGE == 55 && CW_PS_IDX_PRESENCE == 62, "chain and index slots");
+static_assert(CW_PS_CHAIN_ANCHORS == 42 && CW_PS_CHAIN_WINDOWS == 44 && CW_PS_CHAIN_ROUTE == 45 && CW_PS_CHAIN_ROUTE < CW_PS_L_CHUNK_ROWS && CW_PS_CHAIN_STAGE == 48 && CW_PS_CHAIN_SLOW_CYCLES == 54 && CW_PS_IDX_STAGE == 55 && CW_PS_IDX_PRESENCE == 62, "chain and index slots");
 static_assert(CW_PS_IDX_ROUTE == 63 && CW_PS_IDX_PRESENCE < CW_PS_IDX_ROUTE && CW_PS_IDX_ROUTE < CW_PS_POAH, "the route witness has the one slot between the index phases and tier H's: consent_amd/engine.py reads it by number");
 
 /* Batch-wide counters (one struct in scratch, zeroed before every run). */

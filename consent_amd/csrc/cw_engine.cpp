@@ -200,6 +200,7 @@ int hold_and_bind(cw_engine* e, uint32_t n_windows, uint32_t big_slots, const Sc
     if (int rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) return rc;
     e->last_tasks_off = p.tasks; e->last_tdbg_off = p.tdbg; e->last_task_cap = p.task_cap;
     e->last_solid_key_off = p.solid_key; e->last_solid_cnt_off = p.solid_cnt;
+    e->last_seg_len_off = p.seg_len; e->last_members_off = p.members;
     if (!e->step_clock) { CW_HIP(hipMalloc((void**)&e->step_clock, 16)); CW_HIP(hipMemset(e->step_clock, 0, 16)); }
     *sc = bind_scratch(p, (uint8_t*)e->scratch);
     sc->step_clock = e->step_clock;
@@ -395,6 +396,7 @@ int run_device_locked(cw_engine* e, const cw_batch* batch, const cw_result* res,
     const LaunchShape ls = launch_shape(e, batch, p, sc);
     DevBatch db;
     db.n_windows = batch->n_windows; db.win_first_seq = batch->win_first_seq; db.seq_len = batch->seq_len; db.seq_word_off = batch->seq_word_off; db.bases = batch->bases;
+    e->last_win_first_seq = batch->win_first_seq;
     FinOut fo;
     fo.cons = res->cons; fo.cons_off = res->cons_off; fo.cons_len = res->cons_len; fo.win_status = res->win_status;
     fo.solid = res->solid; fo.solid_off = res->solid_off; fo.solid_len = res->solid_len;
@@ -425,6 +427,7 @@ int poa_device_locked(cw_engine* e, const cw_batch* groups, const cw_result* res
     const LaunchShape ls = launch_shape(e, groups, p, sc);
     DevBatch db;
     db.n_windows = G; db.win_first_seq = groups->win_first_seq; db.seq_len = groups->seq_len; db.seq_word_off = groups->seq_word_off; db.bases = groups->bases;
+    e->last_win_first_seq = groups->win_first_seq;
     PoaOut po;
     po.cons = res->cons; po.cons_off = res->cons_off; po.cons_len = res->cons_len; po.win_status = res->win_status;
     if ((rc = enqueue_begin(e, st, sc, p)) != CW_OK) return rc;
@@ -826,6 +829,47 @@ int cw_debug_solid_table(cw_engine* e, uint32_t window, uint32_t* keys, uint32_t
         CW_HIP(hipMemcpy(keys, (const uint8_t*)e->scratch + e->last_solid_key_off + (size_t)wi.solid_base * 4, take * 4, hipMemcpyDeviceToHost));
         CW_HIP(hipMemcpy(counts, (const uint8_t*)e->scratch + e->last_solid_cnt_off + (size_t)wi.solid_base * 4, take * 4, hipMemcpyDeviceToHost));
     }
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): the segmentation of one window of the last run -- WinInfo::n_segs, the window's slots of seg_len, and the task records
+ * that name the window with their members.  Host code only: the task and member arrays are read as the chain kernel (cw_poa_tasks_kernel in an operator
+ * run) left them -- the tiers read the fields returned here and rewrite none of them (PoaTask::state, which they do rewrite, is not returned); seg_len of
+ * a task's slot is the tier's output. */
+int cw_debug_segments(cw_engine* e, uint32_t window, uint32_t* n_segs, uint32_t* seg_len, uint32_t seg_cap, uint32_t* tasks4, uint32_t task_cap, uint32_t* n_tasks,
+                      uint32_t* members3, uint32_t member_cap, uint32_t* n_members) {
+    if (!e || !e->scratch || !n_segs || !n_tasks || !n_members || (seg_cap && !seg_len) || (task_cap && !tasks4) || (member_cap && !members3)) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (window >= e->last_windows || !e->last_win_first_seq) return CW_E_INVALID;
+    BatchCounters c;
+    if (int rc = read_counters_idle(e, &c)) return rc;
+    const uint8_t* base = (const uint8_t*)e->scratch;
+    WinInfo wi;
+    uint32_t s0 = 0;
+    CW_HIP(hipMemcpy(&wi, base + (size_t)window * sizeof(WinInfo), sizeof(wi), hipMemcpyDeviceToHost));
+    CW_HIP(hipMemcpy(&s0, e->last_win_first_seq + window, 4, hipMemcpyDeviceToHost));
+    if (wi.n_segs > wi.seg_cap) return CW_E_INVALID; /* (never: the chain kernel writes n_segs only when the segments fit) */
+    *n_segs = wi.n_segs;
+    const size_t take = wi.n_segs < seg_cap ? wi.n_segs : seg_cap;
+    if (take) CW_HIP(hipMemcpy(seg_len, base + e->last_seg_len_off + (size_t)wi.seg_base * 4, take * 4, hipMemcpyDeviceToHost));
+    const uint32_t nt = c.n_tasks < e->last_task_cap ? c.n_tasks : e->last_task_cap; /* the counter runs on when a capacity stops a window: clamped, as the tiers clamp it */
+    std::vector<PoaTask> tasks(nt);
+    if (nt) CW_HIP(hipMemcpy(tasks.data(), base + e->last_tasks_off, (size_t)nt * sizeof(PoaTask), hipMemcpyDeviceToHost));
+    uint32_t found = 0, mem = 0;
+    std::vector<PoaMember> pm;
+    for (uint32_t t = 0; t < nt; ++t) {
+        const PoaTask& tk = tasks[t];
+        if (tk.window != window) continue;
+        if (found < task_cap) { uint32_t* o = tasks4 + (size_t)found * 4; o[0] = tk.seg_slot - wi.seg_base; o[1] = tk.n_members; o[2] = tk.max_len & 0xFFFFu; o[3] = mem; }
+        if (tk.n_members && mem < member_cap) {
+            const uint32_t n = tk.n_members < member_cap - mem ? tk.n_members : member_cap - mem;
+            pm.resize(n);
+            CW_HIP(hipMemcpy(pm.data(), base + e->last_members_off + (size_t)tk.member_off * sizeof(PoaMember), (size_t)n * sizeof(PoaMember), hipMemcpyDeviceToHost));
+            for (uint32_t i = 0; i < n; ++i) { uint32_t* o = members3 + (size_t)(mem + i) * 3; o[0] = pm[i].seq - s0; o[1] = pm[i].start; o[2] = pm[i].len; }
+        }
+        found++; mem += tk.n_members;
+    }
+    *n_tasks = found; *n_members = mem;
     return CW_OK;
 }
 

@@ -20,6 +20,15 @@ int cw_debug_win_info(cw_engine* e, uint32_t n_windows, uint32_t* out16);
  * the solid table, WinInfo::solid_base / n_solid).  *n receives the number of entries, the first min(*n, cap) of them are copied; a window that was
  * stopped before or in the count phase has none.  Valid when cw_debug_win_info is: after a run, until the next one on this engine. */
 int cw_debug_solid_table(cw_engine* e, uint32_t window, uint32_t* keys, uint32_t* counts, uint32_t cap, uint32_t* n);
+/* the chain kernel's segmentation of one window of the last run.  *n_segs: WinInfo::n_segs (chain anchors + 1; 0 for a window without a chain); seg_len: the
+ * first min(*n_segs, seg_cap) of the window's segment lengths (of a segment that became a POA task: the length of the tier's consensus); tasks4: four words
+ * per task record that names the window, in the order of the task array -- segment index (seg_slot - seg_base), n_members, longest member, index of its
+ * first member in members3; members3: three words per member -- sequence (counted from the window's first), start, length.  *n_tasks and *n_members
+ * receive what the window has, the first task_cap / member_cap of them are copied.  Host code only, in both builds.  The member array is written by the
+ * chain kernel (by cw_poa_tasks_kernel in an operator run) and only read by the tiers, as are the task fields returned here.  Valid when
+ * cw_debug_solid_table is, and for a cw_run_device caller while the batch's win_first_seq array is still allocated. */
+int cw_debug_segments(cw_engine* e, uint32_t window, uint32_t* n_segs, uint32_t* seg_len, uint32_t seg_cap, uint32_t* tasks4, uint32_t task_cap, uint32_t* n_tasks,
+                      uint32_t* members3, uint32_t member_cap, uint32_t* n_members);
 /* The scratch plan of a batch of these dimensions on a device of `cus` compute units, in bytes, without a device: out[0] total, then windows' records,
    solid table, segments, arena, tasks + members, tier lists, slabs of tiers S, M1, M2, L, G, tier Q's + H's rows, anchor blocks, position-matrix
    fallbacks, exact-count fallbacks, finish pass buffers (15 numbers; tools/plan_sizes.py). */
@@ -45,8 +54,8 @@ uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len);
 int cw_add_offsets_device(uint32_t* a32, uint64_t n32, uint32_t add32, uint64_t* a64, uint64_t n64, uint64_t add64, void* hip_stream);
 /* batch counters of the last run (uint32: tasks, members, next_task, next_window, next_finish, any_overflow, then n_tier, next_tier, n_over,
  * next_over with one entry per POA tier: 6 + 4 * 6 = 30 words) and its GPU cycle counts (uint64, 128 words: index kernel 0-7; POA tier t at
- * 8+5t..12+5t: metadata, fill, traceback, merge, consensus; 36+t: the longest single task of tier t; 63: the index kernel's route bits, written by
- * a -DCW_TEST_AIDS build only (cw_index.h CwIdxRoute); 72+12t..: row counts of a -DCW_DIAG build).  The caller passes the capacity of each buffer in words and receives min(capacity, available); the counts come back through
+ * 8+5t..12+5t: metadata, fill, traceback, merge, consensus; 36+t: the longest single task of tier t; 63: the index kernel's route bits and 45: the chain
+ * kernel's, written by a -DCW_TEST_AIDS build only (cw_index.h CwIdxRoute, cw_chain.h CwChRoute); 72+12t..: row counts of a -DCW_DIAG build).  The caller passes the capacity of each buffer in words and receives min(capacity, available); the counts come back through
  * counters_n / prof_n when those are not NULL. */
 /* cw_run_device + wait for the stream + one more run with larger task / member / arena capacities, or the full matrix slot, when windows stopped on those only */
 int cw_run_device_sync(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream);

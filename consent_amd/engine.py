@@ -153,6 +153,9 @@ def _load(p):
         lib.cw_debug_tier_x.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "cw_debug_solid_table"):
         lib.cw_debug_solid_table.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    if hasattr(lib, "cw_debug_segments"):
+        lib.cw_debug_segments.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
+                                          C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.cw_debug_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.cw_extract_piles_device.argtypes = [C.c_void_p, C.POINTER(ReadSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p]
@@ -193,9 +196,15 @@ INDEX_ROUTE = {"staged": 1 << 0, "bytes_done": 1 << 1, "nibbles": 1 << 2, "big_e
                "hashed": 1 << 7, "hash_passes": 1 << 8, "hash_gsort": 1 << 9, "wide": 1 << 10, "tfit": 1 << 11, "pg": 1 << 12, "hit_list": 1 << 13, "use_bits": 1 << 14}
 
 
-def route_names(bits):
-    """The names of the INDEX_ROUTE bits set in `bits`, for messages."""
-    return sorted(n for n, b in INDEX_ROUTE.items() if bits & b)
+# The chain kernel's route witness (csrc/cw_chain.h enum CwChRoute, csrc/cw_device.h CW_PS_CHAIN_ROUTE): the same for cw_chain_kernel.
+CHAIN_ROUTE_SLOT = 45
+CHAIN_ROUTE = {"fast": 1 << 0, "rows_lds": 1 << 1, "rows_far": 1 << 2, "pres_lds": 1 << 3, "wide_key": 1 << 4, "far_scan": 1 << 5, "inplace_rows": 1 << 6,
+               "inplace_masks": 1 << 7, "inplace_all_dirty": 1 << 8, "inplace_matrix": 1 << 9, "early_flush": 1 << 10, "long_single": 1 << 11, "long_slab": 1 << 12}
+
+
+def route_names(bits, table=None):
+    """The names of the bits of `table` (default INDEX_ROUTE) set in `bits`, for messages."""
+    return sorted(n for n, b in (table or INDEX_ROUTE).items() if bits & b)
 
 
 def _check(lib, rc, what, allow_capacity=False):
@@ -687,6 +696,24 @@ class Engine:
     def index_route(self):
         """The INDEX_ROUTE bits of the last batch's windows, ORed (a window alone in its batch: its route).  Zero from the product library."""
         return int(self.profile()[1][INDEX_ROUTE_SLOT])
+
+    def chain_route(self):
+        """The CHAIN_ROUTE bits of the last batch's windows, ORed (a window alone in its batch: its route).  Zero from the product library."""
+        return int(self.profile()[1][CHAIN_ROUTE_SLOT])
+
+    def segments(self, w):
+        """cw_debug_segments: the chain kernel's segmentation of window w of the last run -- (n_segs, seg_len, tasks).  n_segs is chain anchors + 1, or 0 for a
+        window without a chain; seg_len[i] the length of segment i (of a segment that became a POA task: of the tier's consensus); tasks a list, in the order
+        of the task array, of (segment index, n_members, longest member, [(sequence counted from the window's first, start, length), ...])."""
+        ns, nt, nm = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(self.lib, self.lib.cw_debug_segments(self.handle, w, C.byref(ns), None, 0, None, 0, C.byref(nt), None, 0, C.byref(nm)), "cw_debug_segments")
+        seg_len, tasks, members = np.zeros(max(ns.value, 1), np.uint32), np.zeros((max(nt.value, 1), 4), np.uint32), np.zeros((max(nm.value, 1), 3), np.uint32)
+        _check(self.lib, self.lib.cw_debug_segments(self.handle, w, C.byref(ns), _ptr(seg_len), len(seg_len), _ptr(tasks), len(tasks), C.byref(nt),
+                                                    _ptr(members), len(members), C.byref(nm)), "cw_debug_segments")
+        out = []
+        for seg, n, mx, first in tasks[: nt.value].tolist():
+            out.append((seg, n, mx, [tuple(m) for m in members[first : first + n].tolist()]))
+        return ns.value, seg_len[: ns.value], out
 
     def win_info(self, n_windows):
         a = np.zeros((n_windows, 16), np.uint32)

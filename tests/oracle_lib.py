@@ -105,12 +105,15 @@ def _write_recorded():
 STAT_NAMES = ["kmers", "tpl_anchors", "chain_len", "pair_tests", "segments", "poa_segments", "alignments", "dp_cells", "max_nodes", "max_seg_len", "link_calls", "nbr_calls", "alignments_routed", "dp_cells_routed"]
 
 
-def oracle_run(params, batch, want_solid=True, threads=1):
+def oracle_run(params, batch, want_solid=True, threads=1, lib=None):
+    """`lib`: another build of the oracle (a ctypes library: a policy build), default the checker."""
     res = alloc_results(batch, want_solid, params.solid, params.k)
     b = batch.c_struct()
     r = _result_struct(res)
     stats = np.zeros(len(STAT_NAMES), np.uint64)
-    rc = oracle().cwo_run(C.byref(params), C.byref(b), C.byref(r), _ptr(stats), threads)
+    o = lib or oracle()
+    o.cwo_run.argtypes = [C.POINTER(Params), C.POINTER(Batch), C.POINTER(Result), C.c_void_p, C.c_int]
+    rc = o.cwo_run(C.byref(params), C.byref(b), C.byref(r), _ptr(stats), threads)
     assert rc in (0, -4), rc
     return res, dict(zip(STAT_NAMES, (int(x) for x in stats)))
 

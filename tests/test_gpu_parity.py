@@ -9,7 +9,8 @@ import pytest
 
 import consent_amd as ca
 import oracle_lib
-from consent_amd.engine import concat_batches, synth_host
+from chain_probes import arithmetic, reference
+from consent_amd.engine import CHAIN_ROUTE, concat_batches, route_names, synth_host
 from index_probes import aids_engine, assert_route, route_alone
 
 pytestmark = pytest.mark.gpu
@@ -192,8 +193,17 @@ def test_byte_counters_hand_over_exactly_at_256_occurrences(engines, occ):
 def test_out_of_order_anchors_in_most_of_a_deep_pile(engines):
     """Round 2's chain scoring: sequences with an out-of-order anchor stay in the presence bits except at those anchors, whose pairs come
     from correction rows.  Here two unique stretches of the window are exchanged in most sequences (150 dirty sequences: masks of three
-    words, a handful of rows), in a few (masks of one word), and shifted as a block (dozens of out-of-order anchors per sequence: more
-    rows than fit LDS, read from the block); plus 1000-base windows at depth 110, whose hit positions do not pack into the hit list."""
+    words), in a few (masks of one word), and shifted as a block (dozens of out-of-order anchors per sequence: more rows than fit LDS,
+    read from the block); plus 1000-base windows at depth 110, too large for a matrix per template k-mer: the support pass keeps its hits
+    in the hit list.
+    Which way each pile goes is asserted from the two route witnesses of the test-aid library, each pile alone in its batch.  The first
+    four piles reach no correction rows at all: nearly every template k-mer is an anchor in them, and the rows live on the room that
+    template k-mers which are no anchors leave in the window's anchor block (tests/chain_probes.py `index`).  Pile 0 is scored in place
+    over every dirty sequence (masks of three words exist with rows only), pile 1 too (its matrix leaves the index kernel's LDS no room
+    for masks), piles 2 and 3 in place from one-word masks.  Piles 4-6 are piles 0-2 with a tandem repeat behind every sequence -- template
+    k-mers that are no anchors -- and go as described above: 215 rows for three-word masks and 83 rows of the shifted block, both read from
+    the block by the fast path; the few exchanged sequences of pile 5 have more out-of-order anchors than a block carries rows for (325)
+    and are scored from their one-word masks."""
     rng = random.Random(29)
     truth = rand_seq(rng, 1100)
     t500 = truth[:500]
@@ -211,11 +221,29 @@ def test_out_of_order_anchors_in_most_of_a_deep_pile(engines):
         [t500] + [mutate(rng, t500, 0.05) for _ in range(70)] + [mutate(rng, block_moved(t500, 80, 300, 90), 0.03) for _ in range(40)],
         [truth[:1000]] + [mutate(rng, truth[:1000], 0.08) for _ in range(110)],
     ]
+    piles += [[s + ("ACGTT" * 60) for s in piles[w]] for w in range(3)]
     prm = (9, 4, 8, 2, 150)
     hb = ca.pack_piles(piles)
     got = engines(*prm).run(hb)
     exp, _ = oracle_lib.oracle_run(ca.Params(*prm), hb, threads=4)
     assert_same(got, exp, len(piles), "out-of-order anchors")
+    # per pile: dirty sequences, mask words, correction rows the chain kernel gets, its route bits, the index kernel's -- written down here, held against
+    # the plain reference and the constants' arithmetic of tests/chain_probes.py on the CPU side, and against the counters and witnesses of the library
+    said = [(150, 3, 0, "inplace_all_dirty", "hit_list"), (17, 1, 0, "inplace_all_dirty", "hit_list"), (43, 1, 0, "inplace_masks", "hit_list"),
+            (48, 1, 0, "inplace_masks", "hit_list"), (150, 3, 215, "fast rows_far", "hit_list"), (17, 1, 0, "inplace_masks", "hit_list"),
+            (43, 1, 83, "fast rows_far", "hit_list")]
+    with aids_engine(*prm) as e:
+        for w, (n_dirty, words, rows, chain_bits, index_bits) in enumerate(said):
+            ref = reference(piles[w], prm)
+            names, counters, _ = arithmetic(ref)
+            assert len(ref.dirty) == n_dirty and (n_dirty + 63) // 64 == words and counters[1] == rows and set(chain_bits.split()) <= set(names), (w, len(ref.dirty), counters, names)
+            one, route = route_alone(e, hb, w)
+            assert one.consensus(0) == exp.consensus(w)
+            ctr, prof = e.profile()
+            assert int(prof[43]) == n_dirty, f"pile {w}: {int(prof[43])} dirty sequences"
+            assert tuple(int(prof[i]) for i in (50, 51, 52, 53)) == counters, f"pile {w}: {prof[50:54]} against {counters}"
+            assert e.chain_route() == sum(CHAIN_ROUTE[n] for n in names), f"pile {w}: went {route_names(e.chain_route(), CHAIN_ROUTE)}, the description gives {names}"
+            assert_route(route, has=index_bits, lacks="tfit", what=f"out-of-order anchors, pile {w}")
 
 
 def test_pile_layout_in_memory_does_not_matter(engines):
