@@ -24,7 +24,7 @@
 
 #define CW_CH_WAVES 4
 #ifndef CW_CH_SLAB
-#define CW_CH_SLAB 20480 /* bytes of LDS per wave: 12 B per anchor + phase D's tile + the pending list + what fits of the bitsets: up to 1230 anchors */
+#define CW_CH_SLAB 20480 /* bytes of LDS per wave: 12 B per anchor + phase D's tile + the pending list + what fits of the bitsets: up to 1230 anchors (ChSlab below) */
 #endif
 #define CW_CH_SLAB_LONG 32768 /* ... of the instance an engine configured for long templates launches (cw_configure; round 6): up to CW_TMAX anchors, one work-group per CU */
 #define CW_CH_LIST_BYTES 1792
@@ -35,7 +35,7 @@
 #define CW_CH_BFIELD(b) (CW_CHAIN_TIE == CW_CHAIN_TIE_LARGEST_SUCCESSOR ? (uint32_t)(b) : 0xFFFFu - (uint32_t)(b))
 
 /* Which way a window went, one bit per decision of this file: a -DCW_TEST_AIDS build ORs them into prof[CW_PS_CHAIN_ROUTE] (the product's kernel has none of
-   this: its code is to stay instruction for instruction what it is, see the flush's routing rule below), and consent_amd/engine.py CHAIN_ROUTE names the same
+   this; a change of this file is held to the same results, the same resources and the same time in both builds), and consent_amd/engine.py CHAIN_ROUTE names the same
    bits (tests/test_chain_ref_cpu.py holds the two together).  The probes of tests/chain_probes.py say which bits they must set: tests/test_gpu_chain.py */
 enum CwChRoute : unsigned {
     CW_CR_FAST = 1u << 0,              /* phase C in the register window (chain_window)                                   */
@@ -59,6 +59,109 @@ enum CwChRoute : unsigned {
 #endif
 __device__ __forceinline__ int ch_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint32_t ch_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+/* ---- one slab layout ------------------------------------------------------------------------------------------------------------------ */
+/* the last CW_CH_LIST_BYTES of a slab: segments waiting for the whole wave (phase D), 64 entries */
+struct ChQueue {
+    uint32_t off[64];  /* arena offset            */
+    uint32_t need[64]; /* arena bytes reserved    */
+    uint16_t seg[64];
+    int16_t ca[64], cb[64];
+    uint16_t n[64], mx[64], fs[64], fst[64];
+    uint32_t sl[64];   /* sum of the members' lengths */
+    uint16_t spare[64];
+};
+/* The layout of a wave's slab of SLAB bytes by the window's anchor count A, for the capacity test, the carve and phase D: the DP arrays of phase C (clen, cnxt,
+   smax, chain: 8 A + 2 bytes, then csc: 12 bytes per anchor in all), behind them what fits of the block's presence bitsets and correction rows (var, room
+   bytes), phase D's tile and sequence lengths over csc and var (dead by then; the chain in front of them is not), the queue at the end.  Byte offsets: the
+   kernel makes typed pointers of slab + offset, not pointer arithmetic through integers, so that the compiler keeps seeing LDS pointers (ds_ instead of
+   flat_ instructions). */
+template <int SLAB> struct ChSlab {
+    static constexpr uint32_t USABLE = (uint32_t)(SLAB - CW_CH_LIST_BYTES); /* the queue's offset */
+    uint32_t csc;  /* int32 x A, behind clen, cnxt (int16 x A each), smax (int16 x (A + 1)) and chain (uint16 x A) */
+    uint32_t var;  /* what fits of the presence bitsets and correction rows */
+    size_t room;   /* ... in bytes */
+    uint32_t tile; /* phase D: 65 rows x CW_CH_TILE_STRIDE u16, over csc and var */
+    uint32_t len;  /* ... and 64 sequence lengths */
+    __host__ __device__ constexpr ChSlab(const uint32_t A)
+        : csc((8u * A + 2u + 3u) & ~3u), var((csc + 4u * A + 7u) & ~7u), room((size_t)USABLE - var), tile(csc), len(csc + 65u * CW_CH_TILE_STRIDE * 2u + 4u) {}
+    __host__ __device__ constexpr bool fits() const { return var <= USABLE && len + 256u <= USABLE; }
+};
+template <int SLAB> __host__ __device__ constexpr bool ch_fits(const uint32_t A) { return ChSlab<SLAB>(A).fits(); }
+static_assert(sizeof(ChQueue) == CW_CH_LIST_BYTES, "the queue is the slab's last CW_CH_LIST_BYTES");
+#if CW_CH_SLAB == 20480
+static_assert(ch_fits<CW_CH_SLAB>(1230u) && !ch_fits<CW_CH_SLAB>(1231u), "the 20 KB slab holds up to 1230 anchors (the tile term decides)");
+#endif
+static_assert(ch_fits<CW_CH_SLAB_LONG>(CW_TMAX), "the long instance holds an anchor per template k-mer of the longest template");
+
+/* ---- one key ---------------------------------------------------------------------------------------------------------------------------- */
+/* the chain key: the largest wins -- the longer chain, then the higher score, then the successor CW_CH_BFIELD prefers; 0 = no link */
+__device__ __forceinline__ unsigned long long ch_key(const uint32_t len1, const uint32_t score, const uint32_t b) {
+    return ((unsigned long long)len1 << 48) | ((unsigned long long)score << 16) | (unsigned long long)CW_CH_BFIELD(b);
+}
+/* the wave's largest key; narrow: (length + 1, score) fit 11 + 21 bits, b0: the successor lane 0 scored */
+__device__ __forceinline__ unsigned long long ch_wave_best(const bool narrow, const unsigned long long key, const uint32_t b0) {
+    if (!narrow) return cw_wave_max_u64(key);
+    const uint32_t hi = key ? (((uint32_t)(key >> 48) << 21) | (uint32_t)((key >> 16) & 0x1FFFFFull)) : 0u;
+    const uint32_t mx = (uint32_t)cw_lane_value((int)cw_wave_scan_max_u32(hi), 63); /* one fused 32-bit prefix max */
+    if (!mx) return 0ull;
+    const unsigned long long who = __ballot(hi == mx); /* the first lane holding it = the smallest b (the last lane: the largest, CW_CHAIN_TIE) */
+    const uint32_t fb = b0 + (CW_CHAIN_TIE == CW_CHAIN_TIE_LARGEST_SUCCESSOR ? 63u - (uint32_t)__clzll((long long)who) : (uint32_t)(__ffsll((long long)who) - 1));
+    return ch_key(mx >> 21, mx & 0x1FFFFFu, fb);
+}
+
+/* the score of the pair (a, b): the sequences that hold both, in order -- popcount of the presence words -- and what the correction rows add for the dirty
+   ones, row(a)[b] + row(b)[a] (row id 0xFF: the anchor has no row) */
+__device__ __forceinline__ uint32_t ch_pair_bits(const unsigned long long* pa, const unsigned long long* pb, const uint32_t nw) {
+    uint32_t cnt = 0;
+    for (uint32_t x = 0; x < nw; ++x) cnt += (uint32_t)__popcll(pa[x] & pb[x]); /* (no unroll pragma: the window's count is a constant and unrolls by itself, the in-place loops stay rolled) */
+    return cnt;
+}
+template <typename ROW>
+__device__ __forceinline__ uint32_t ch_pair_rows(ROW row_at, const uint32_t row_a, const uint32_t row_b, const uint32_t a, const uint32_t b) {
+    uint32_t cnt = 0;
+    if (row_a != 0xFFu) cnt += row_at(row_a, b);
+    if (row_b != 0xFFu) cnt += row_at(row_b, a);
+    return cnt;
+}
+
+/* the five tier lists of the flush in the order of their tier codes (cw_poa_route) 1 .. 5 = M1, M2, L, Q, H: list li takes tier code li + 1 and is
+   tier_list / n_tier [ch_list_id(li)] */
+#define CW_CH_LISTS 5
+__device__ __forceinline__ constexpr int ch_list_id(const int li) { return li < 3 ? li + 1 : li == 3 ? 0 : 5; }
+
+#if CW_SEG_MISSING_ANCHOR == CW_SEG_MISSING_ANCHOR_EXTRAPOLATE
+/* cw_policy.h CW_SEG_MISSING_ANCHOR_EXTRAPOLATE (a policy build, round 6), in front of phase D: the chain anchors a sequence lacks get the position the
+   template's spacing gives them, counted from the nearest chain anchor the sequence holds (the one before, else the one after), written into the
+   block's position matrix in place -- phase D then cuts the segments as ever.  Lanes = sequences; the template (sequence 0)
+   holds every anchor at its template position. */
+__device__ __forceinline__ void ch_extrapolate(const DevBatch& b, const uint16_t* P, const uint16_t* chain, const uint32_t m, const uint32_t N, const uint32_t Np, const uint32_t s0,
+                                               const int lane) {
+    uint16_t* Pw = const_cast<uint16_t*>(P);
+    for (uint32_t sb = 0; sb < N; sb += 64) {
+        const uint32_t s = sb + (uint32_t)lane;
+        const bool in = s < N;
+        const int top = in ? (int)min(b.seq_len[s0 + s], 65534u) : 0;
+        int last_p = -1, last_t = 0, first_i = -1, first_p = 0, first_t = 0;
+        for (uint32_t i = 0; i < m; ++i) {
+            const uint32_t a = chain[i];
+            const int t_i = (int)P[a * Np];
+            const uint32_t pv = in ? (uint32_t)P[a * Np + s] : (uint32_t)CW_NONE16;
+            if (pv != CW_NONE16) { last_p = (int)pv; last_t = t_i; if (first_i < 0) { first_i = (int)i; first_p = (int)pv; first_t = t_i; } }
+            else if (in && last_p >= 0) Pw[a * Np + s] = (uint16_t)min(top, last_p + (t_i - last_t));
+        }
+        const int lead = cw_wave_max(in ? first_i : -1); /* the longest run of leading anchors any lane has to fill */
+        for (int i = 0; i < lead; ++i) {
+            const uint32_t a = chain[i];
+            const int t_i = (int)P[a * Np];
+            if (in && i < first_i) Pw[a * Np + s] = (uint16_t)min(top, max(0, first_p - (first_t - t_i)));
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); /* the rows are read back by other lanes of this wave, through the vector cache */
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    cw_wave_sync();
+}
+#endif
 
 template <int SLAB>
 __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, DevScratch sc, cw_params prm) {
@@ -84,8 +187,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
         bool fits_slab = true;
         if (ready) {
             const uint32_t A0 = ch_uni(((const uint32_t*)(sc.ablock + ((size_t)ch_uni(wi->ab_base) << 4)))[0]);
-            const uint32_t oc = (8u * A0 + 2u + 3u) & ~3u, ov = (oc + 4u * A0 + 7u) & ~7u;
-            fits_slab = ov <= (uint32_t)(SLAB - CW_CH_LIST_BYTES) && oc + 65u * CW_CH_TILE_STRIDE * 2u + 4u + 256u <= (uint32_t)(SLAB - CW_CH_LIST_BYTES);
+            fits_slab = ch_fits<SLAB>(A0);
             if (!fits_slab) { new_status = CW_WIN_OVERFLOW; why = CW_WHY_ANCHORS; }
         }
         if (ready && fits_slab) {
@@ -114,26 +216,15 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
             const uint32_t arena_base = ch_uni(wi->arena_base), arena_cap = ch_uni(wi->arena_cap);
 
             /* LDS carve */
+            const ChSlab<SLAB> L(A); /* (L.csc's 8 A + 2 is the sum of the four arrays chained here, 2 A + 2 A + 2 (A + 1) + 2 A bytes: change an element type and that formula with it) */
             int16_t* clen = (int16_t*)slab;                    /* A     */
             int16_t* cnxt = clen + A;                          /* A     */
             int16_t* smax = cnxt + A;                          /* A + 1 */
             uint16_t* chain = (uint16_t*)(smax + A + 1);       /* A     */
-            /* offsets, not pointer arithmetic through integers: the compiler must keep seeing LDS pointers (ds_ instead of flat_ instructions) */
-            const uint32_t off_csc = (8u * A + 2u + 3u) & ~3u, off_var = (off_csc + 4u * A + 7u) & ~7u;
-            int32_t* csc = (int32_t*)(slab + off_csc);         /* A     */
-            uint8_t* var = slab + off_var;
-            /* the last CW_CH_LIST_BYTES of the slab: segments waiting for the whole wave (phase D), 64 entries */
-            uint32_t* q_off = (uint32_t*)(slab + SLAB - CW_CH_LIST_BYTES);   /* arena offset            */
-            uint32_t* q_need = q_off + 64;                                           /* arena bytes reserved    */
-            uint16_t* q_seg = (uint16_t*)(q_need + 64);
-            int16_t* q_ca = (int16_t*)(q_seg + 64);
-            int16_t* q_cb = q_ca + 64;
-            uint16_t* q_n = (uint16_t*)(q_cb + 64);
-            uint16_t* q_mx = q_n + 64;
-            uint16_t* q_fs = q_mx + 64;
-            uint16_t* q_fst = q_fs + 64;
-            uint32_t* q_sl = (uint32_t*)(q_fst + 64);                               /* sum of the members' lengths */
-            const size_t var_room = (size_t)(SLAB - CW_CH_LIST_BYTES) - off_var;
+            int32_t* csc = (int32_t*)(slab + L.csc);           /* A     */
+            uint8_t* var = slab + L.var;
+            ChQueue* Q = (ChQueue*)(slab + L.USABLE);
+            const size_t var_room = L.room;
             /* behind the presence bitsets: the correction rows (row ids + rows) when the block has them and they fit */
             const size_t pres_only = use_bits ? (size_t)A * Nw * 8 : 0;
             const size_t delta_bytes = (size_t)Ap + (size_t)n_rows * Ap;
@@ -160,15 +251,6 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                correction row of anchor a+1+l, shifted by one lane per step (DPP), so that a step neither waits for lane 0's LDS writes of
                the step before nor re-reads what it already had; what a step needs from LDS besides is requested one step ahead. */
             const bool narrow = (uint64_t)A * N < (1ull << 21) && A < 2047u; /* (length + 1, score) fit 11 + 21 bits: a chain's score is at most its length x N */
-            auto wave_best = [&](unsigned long long key, uint32_t b0) -> unsigned long long {
-                if (!narrow) return cw_wave_max_u64(key);
-                const uint32_t hi = key ? (((uint32_t)(key >> 48) << 21) | (uint32_t)((key >> 16) & 0x1FFFFFull)) : 0u;
-                const uint32_t mx = (uint32_t)cw_lane_value((int)cw_wave_scan_max_u32(hi), 63); /* one fused 32-bit prefix max */
-                if (!mx) return 0ull;
-                const unsigned long long who = __ballot(hi == mx); /* the first lane holding it = the smallest b (the last lane: the largest, CW_CHAIN_TIE) */
-                const uint32_t fb = b0 + (CW_CHAIN_TIE == CW_CHAIN_TIE_LARGEST_SUCCESSOR ? 63u - (uint32_t)__clzll((long long)who) : (uint32_t)(__ffsll((long long)who) - 1));
-                return ((unsigned long long)(mx >> 21) << 48) | ((unsigned long long)(mx & 0x1FFFFFu) << 16) | (unsigned long long)CW_CH_BFIELD(fb);
-            };
             /* the window path, compiled once per (words of presence, correction rows or not): everything it tests is then a constant */
             auto chain_window = [&](auto nw_tag, auto delta_tag) {
                 constexpr uint32_t NW = decltype(nw_tag)::value;
@@ -214,10 +296,9 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                             for (uint32_t x = 0; x < NW; ++x) cnt += (uint32_t)__popcll(pa[x] & r_p[x]);
                             if (DELTA) { cnt += d_b_cur; if (row_a != 0xFFu) cnt += row_at(row_a, bb); }
                             if ((int)cnt >= sup_min)
-                                key = ((unsigned long long)((uint32_t)r_len + 1u) << 48) | ((unsigned long long)((uint32_t)r_sc + cnt) << 16) |
-                                      (unsigned long long)CW_CH_BFIELD(bb);
+                                key = ch_key((uint32_t)r_len + 1u, (uint32_t)r_sc + cnt, bb);
                         }
-                        best = wave_best(key, b0);
+                        best = ch_wave_best(narrow, key, b0);
                         if (best != 0ull && b0 + 64 < A) stop = sm_far < (int)(best >> 48) - 1;
                         stop = ch_uni(stop ? 1 : 0) != 0u;
                     }
@@ -227,19 +308,12 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                             const uint32_t bb = b0 + (uint32_t)lane;
                             unsigned long long key = 0ull;
                             if (bb < A) {
-                                uint32_t cnt = 0;
-#pragma unroll
-                                for (uint32_t x = 0; x < NW; ++x) cnt += (uint32_t)__popcll(pa[x] & lpres[(size_t)bb * NW + x]);
-                                if (DELTA) {
-                                    const uint32_t row_b = lrowid[bb];
-                                    if (row_a != 0xFFu) cnt += row_at(row_a, bb);
-                                    if (row_b != 0xFFu) cnt += row_at(row_b, (uint32_t)a);
-                                }
+                                uint32_t cnt = ch_pair_bits(pa, lpres + (size_t)bb * NW, NW);
+                                if (DELTA) cnt += ch_pair_rows(row_at, row_a, lrowid[bb], (uint32_t)a, bb);
                                 if ((int)cnt >= sup_min)
-                                    key = ((unsigned long long)((uint32_t)clen[bb] + 1u) << 48) | ((unsigned long long)((uint32_t)csc[bb] + cnt) << 16) |
-                                          (unsigned long long)CW_CH_BFIELD(bb);
+                                    key = ch_key((uint32_t)clen[bb] + 1u, (uint32_t)csc[bb] + cnt, bb);
                             }
-                            key = wave_best(key, b0);
+                            key = ch_wave_best(narrow, key, b0);
                             best = key > best ? key : best;
                             bool st2 = false;
                             if (best != 0ull && b0 + 64 < A) st2 = (int)smax[b0 + 64] < (int)(best >> 48) - 1;
@@ -292,13 +366,11 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                     if (bb < A) {
                         uint32_t cnt = 0;
                         if (use_bits) {
-                            if (pres_lds) { for (uint32_t x = 0; x < Nw; ++x) cnt += (uint32_t)__popcll(lpres[(size_t)a * Nw + x] & lpres[(size_t)bb * Nw + x]); }
-                            else { for (uint32_t x = 0; x < Nw; ++x) cnt += (uint32_t)__popcll(gpres[(size_t)a * Nw + x] & gpres[(size_t)bb * Nw + x]); }
+                            if (pres_lds) cnt = ch_pair_bits(lpres + (size_t)a * Nw, lpres + (size_t)bb * Nw, Nw);
+                            else cnt = ch_pair_bits(gpres + (size_t)a * Nw, gpres + (size_t)bb * Nw, Nw);
                             if (n_rows) { /* correction rows, in the block */
                                 CW_CH_ROUTE(sc.ctr, true, CW_CR_INPLACE_ROWS);
-                                const uint32_t row_a = growid[a], row_b = growid[bb];
-                                if (row_a != 0xFFu) cnt += gdelta[(size_t)row_a * Ap + bb];
-                                if (row_b != 0xFFu) cnt += gdelta[(size_t)row_b * Ap + (uint32_t)a];
+                                cnt += ch_pair_rows([&](const uint32_t row, const uint32_t col) -> uint32_t { return (uint32_t)gdelta[(size_t)row * Ap + col]; }, growid[a], growid[bb], (uint32_t)a, bb);
                             } else if (has_bm) { /* bad masks: the dirty sequences that are out of order at a or at bb */
                                 CW_CH_ROUTE(sc.ctr, true, CW_CR_INPLACE_MASKS);
                                 unsigned long long mm = gbadm[a] | gbadm[bb];
@@ -329,8 +401,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                             }
                         }
                         if ((int)cnt >= sup_min)
-                            key = ((unsigned long long)((uint32_t)clen[bb] + 1u) << 48) | ((unsigned long long)((uint32_t)csc[bb] + cnt) << 16) |
-                                  (unsigned long long)CW_CH_BFIELD(bb);
+                            key = ch_key((uint32_t)clen[bb] + 1u, (uint32_t)csc[bb] + cnt, bb);
                     }
                     key = cw_wave_max_u64(key);
                     best = key > best ? key : best;
@@ -393,87 +464,41 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                    left anchor (all pieces equal and no longer than k), or a single short piece.  The few segments that need
                    the whole wave -- POA tasks and long single pieces -- follow one by one. */
 #if CW_SEG_MISSING_ANCHOR == CW_SEG_MISSING_ANCHOR_EXTRAPOLATE
-                /* cw_policy.h CW_SEG_MISSING_ANCHOR_EXTRAPOLATE (a policy build, round 6): the chain anchors a sequence lacks get the position the template's
-                   spacing gives them, counted from the nearest chain anchor the sequence holds (the one before, else the one after), written into the
-                   block's position matrix in place -- everything below then cuts the segments as ever.  Lanes = sequences; the template (sequence 0)
-                   holds every anchor at its template position. */
-                {
-                    uint16_t* Pw = const_cast<uint16_t*>(P);
-                    for (uint32_t sb = 0; sb < N; sb += 64) {
-                        const uint32_t s = sb + (uint32_t)lane;
-                        const bool in = s < N;
-                        const int top = in ? (int)min(b.seq_len[s0 + s], 65534u) : 0;
-                        int last_p = -1, last_t = 0, first_i = -1, first_p = 0, first_t = 0;
-                        for (uint32_t i = 0; i < m; ++i) {
-                            const uint32_t a = chain[i];
-                            const int t_i = (int)P[a * Np];
-                            const uint32_t pv = in ? (uint32_t)P[a * Np + s] : (uint32_t)CW_NONE16;
-                            if (pv != CW_NONE16) { last_p = (int)pv; last_t = t_i; if (first_i < 0) { first_i = (int)i; first_p = (int)pv; first_t = t_i; } }
-                            else if (in && last_p >= 0) Pw[a * Np + s] = (uint16_t)min(top, last_p + (t_i - last_t));
-                        }
-                        const int lead = cw_wave_max(in ? first_i : -1); /* the longest run of leading anchors any lane has to fill */
-                        for (int i = 0; i < lead; ++i) {
-                            const uint32_t a = chain[i];
-                            const int t_i = (int)P[a * Np];
-                            if (in && i < first_i) Pw[a * Np + s] = (uint16_t)min(top, max(0, first_p - (first_t - t_i)));
-                        }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); /* the rows are read back below by other lanes of this wave, through the vector cache */
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    cw_wave_sync();
-                }
+                ch_extrapolate(b, P, chain, m, N, Np, s0, lane);
 #endif
                 bool over = false, over_arena = false; /* (over_arena is wave-uniform: decided from wave-uniform totals) */
                 uint32_t q_cnt = 0;
                 unsigned long long t_flush = 0;
-                uint16_t* d_tile = (uint16_t*)(slab + off_csc);                         /* 65 rows x 66 u16 */
-                uint32_t* d_len = (uint32_t*)(slab + off_csc + 65u * CW_CH_TILE_STRIDE * 2u + 4u); /* 64 sequence lengths */
+                uint16_t* d_tile = (uint16_t*)(slab + L.tile);
+                uint32_t* d_len = (uint32_t*)(slab + L.len);
                 auto flush = [&]() {
                     const unsigned long long _f0 = __builtin_readcyclecounter();
                     const bool e = (uint32_t)lane < q_cnt;
-                    const uint32_t e_n = e ? q_n[lane] : 0u, e_mx = e ? q_mx[lane] : 0u;
+                    const uint32_t e_n = e ? Q->n[lane] : 0u, e_mx = e ? Q->mx[lane] : 0u;
                     const bool poa = e && e_n > 1u;
-                    /* (the routing rule below has a copy in cw_poa_op.h, cw_poa_route, for cw_poa_tasks_kernel: calling one shared function from here reordered eight
-                       instructions of this kernel, and its code is to stay what it is -- change the two together) */
-                    /* route by the expected graph size: the graph has at least max_len nodes once its longest member is in
-                       and typically ends at 1.4-1.6x that; a task that still outgrows its tier is redone in the next one */
-                    const uint32_t est = (e_mx * 17u + 9u) / 10u;
-                    /* deep piles grow wider graphs: the smallest tier is only worth trying when the graph will very likely stay in it
-                       (a task that outgrows tier S is redone in tier L, the scarcest one) */
-                    const uint32_t est_s = (e_mx * (15u + e_n / 5u) + 9u) / 10u;
-                    /* tier Q (four tasks per wave, cw_poa_q.h): members of at most 31 bases and a graph that should stay small */
-                    /* tier H (two tasks per wave, cw_poa_q.h): members of up to 63 bases, graph expected (depth-aware) to stay inside its 128 nodes */
-                    const bool fits_h = sc.use_h != 0u && e_mx <= (uint32_t)CW_POAH_LC && e_mx >= sc.h_min_len && est_s <= (uint32_t)CW_POAH_ROUTE_NODES;
-                    const bool fits_s = est_s <= sc.s_route_cells && e_mx <= (uint32_t)CW_POA_LC; /* s_route_cells: a node count since round 4 */
-                    uint32_t tier = !poa ? 0xFFu
-                                          : (sc.use_q && e_mx <= (uint32_t)CW_POAQ_LC && est_s <= (uint32_t)CW_POAQ_ROUTE_NODES) ? 4u
-                                          : (fits_h && (sc.use_h > 1u || !fits_s)) ? 5u
-                                          : fits_s ? 0u
-                                          : ((sc.m1_route_depth && est_s > est ? est_s : est) <= (uint32_t)CW_POAM1_ROUTE && e_mx <= (uint32_t)CW_POAM1_LC) ? 1u
-                                          : (est <= (uint32_t)CW_POAM2_ROUTE && e_mx <= (uint32_t)CW_POAM2_LC) ? 2u
-                                                                                            : 3u;
+                    const uint32_t tier = cw_poa_route(sc, poa, e_n, e_mx); /* cw_poa_q.h */
                     const unsigned long long below = (1ull << lane) - 1ull;
                     const unsigned long long pm = __ballot(poa);
-                    const unsigned long long tm1 = __ballot(tier == 1u), tm2 = __ballot(tier == 2u), tm3 = __ballot(tier == 3u), tmq = __ballot(tier == 4u), tmh = __ballot(tier == 5u);
+                    unsigned long long tm[CW_CH_LISTS]; /* who goes on which list, and where this flush's entries of it begin */
+                    uint32_t lb[CW_CH_LISTS];
+#pragma unroll
+                    for (int li = 0; li < CW_CH_LISTS; ++li) { tm[li] = __ballot(tier == (uint32_t)li + 1u); lb[li] = 0; }
                     const int minc = cw_wave_scan_add(poa ? (int)e_n : 0);
                     const uint32_t m_total = (uint32_t)cw_lane_value(minc, 63);
-                    uint32_t tb = 0, mb = 0, b1 = 0, b2 = 0, b3 = 0, bq = 0, bh = 0;
+                    uint32_t tb = 0, mb = 0;
                     if (lane == 0 && pm) {
                         tb = atomicAdd(&sc.ctr->n_tasks, (uint32_t)__popcll(pm));
                         mb = atomicAdd(&sc.ctr->n_members, m_total);
-                        if (tm1) b1 = atomicAdd(&sc.ctr->n_tier[1], (uint32_t)__popcll(tm1));
-                        if (tm2) b2 = atomicAdd(&sc.ctr->n_tier[2], (uint32_t)__popcll(tm2));
-                        if (tm3) b3 = atomicAdd(&sc.ctr->n_tier[3], (uint32_t)__popcll(tm3));
-                        if (tmq) bq = atomicAdd(&sc.ctr->n_tier[0], (uint32_t)__popcll(tmq));
-                        if (tmh) bh = atomicAdd(&sc.ctr->n_tier[5], (uint32_t)__popcll(tmh));
+#pragma unroll
+                        for (int li = 0; li < CW_CH_LISTS; ++li) if (tm[li]) lb[li] = atomicAdd(&sc.ctr->n_tier[ch_list_id(li)], (uint32_t)__popcll(tm[li]));
                     }
                     tb = (uint32_t)cw_lane_value((int)tb, 0); mb = (uint32_t)cw_lane_value((int)mb, 0);
-                    b1 = (uint32_t)cw_lane_value((int)b1, 0); b2 = (uint32_t)cw_lane_value((int)b2, 0); b3 = (uint32_t)cw_lane_value((int)b3, 0);
-                    bq = (uint32_t)cw_lane_value((int)bq, 0); bh = (uint32_t)cw_lane_value((int)bh, 0);
-                    const bool cap_ok = (uint64_t)tb + (uint32_t)__popcll(pm) <= sc.task_cap && (uint64_t)mb + m_total <= sc.member_cap &&
-                                        b1 + (uint32_t)__popcll(tm1) <= sc.list_cap && b2 + (uint32_t)__popcll(tm2) <= sc.list_cap &&
-                                        b3 + (uint32_t)__popcll(tm3) <= sc.list_cap && bq + (uint32_t)__popcll(tmq) <= sc.list_cap &&
-                                        bh + (uint32_t)__popcll(tmh) <= sc.list_cap;
+                    bool cap_ok = (uint64_t)tb + (uint32_t)__popcll(pm) <= sc.task_cap && (uint64_t)mb + m_total <= sc.member_cap;
+#pragma unroll
+                    for (int li = 0; li < CW_CH_LISTS; ++li) {
+                        lb[li] = (uint32_t)cw_lane_value((int)lb[li], 0);
+                        cap_ok = cap_ok && lb[li] + (uint32_t)__popcll(tm[li]) <= sc.list_cap;
+                    }
                     if (!cap_ok) {
                         /* The counters have advanced and are never rolled back; consumers clamp them to the capacities and walk every slot
                            below.  Whatever this flush reserved inside a capacity is therefore given a neutral content -- a finished task
@@ -483,13 +508,11 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                         const uint32_t n_t = (uint32_t)__popcll(pm);
                         for (uint32_t x = lane; x < n_t; x += 64)
                             if ((uint64_t)tb + x < sc.task_cap) { PoaTask t; t.window = w; t.seg_slot = seg_base; t.member_off = 0; t.n_members = 0; t.max_len = 0; t.out_off = 0; t.out_cap = 0; t.state = 1u; sc.tasks[tb + x] = t; }
-                        const uint32_t lb[5] = {bq, b1, b2, b3, bh};
-                        const unsigned long long lm[5] = {tmq, tm1, tm2, tm3, tmh};
-                        const int lt[5] = {0, 1, 2, 3, 5};
-                        for (int li = 0; li < 5; ++li) {
-                            const uint32_t n_l = (uint32_t)__popcll(lm[li]);
+#pragma unroll
+                        for (int li = 0; li < CW_CH_LISTS; ++li) {
+                            const uint32_t n_l = (uint32_t)__popcll(tm[li]);
                             for (uint32_t x = lane; x < n_l; x += 64)
-                                if ((uint64_t)lb[li] + x < sc.list_cap) sc.tier_list[lt[li]][lb[li] + x] = sc.task_cap;
+                                if ((uint64_t)lb[li] + x < sc.list_cap) sc.tier_list[ch_list_id(li)][lb[li] + x] = sc.task_cap;
                         }
                     }
                     else {
@@ -497,26 +520,26 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                         const uint32_t m_off = mb + (uint32_t)minc - (poa ? e_n : 0u);
                         if (poa) { /* task records: one lane each */
                             PoaTask t;
-                            t.window = w; t.seg_slot = seg_base + q_seg[lane]; t.member_off = m_off; t.n_members = e_n;
-                            t.max_len = e_mx | ((e_n ? q_sl[lane] / e_n : 0u) << 16); /* longest member | mean member length: what the tier sort goes by */
-                            t.out_off = q_off[lane]; t.out_cap = q_need[lane];
+                            t.window = w; t.seg_slot = seg_base + Q->seg[lane]; t.member_off = m_off; t.n_members = e_n;
+                            t.max_len = e_mx | ((e_n ? Q->sl[lane] / e_n : 0u) << 16); /* longest member | mean member length: what the tier sort goes by */
+                            t.out_off = Q->off[lane]; t.out_cap = Q->need[lane];
                             t.state = tier ? 2u : 0u; /* 0 = tier S takes it from the task array; anything else is on a list */
                             sc.tasks[t_idx] = t;
-                            if (tier == 1u) sc.tier_list[1][b1 + (uint32_t)__popcll(tm1 & below)] = t_idx;
-                            else if (tier == 2u) sc.tier_list[2][b2 + (uint32_t)__popcll(tm2 & below)] = t_idx;
-                            else if (tier == 3u) sc.tier_list[3][b3 + (uint32_t)__popcll(tm3 & below)] = t_idx;
-                            else if (tier == 4u) sc.tier_list[0][bq + (uint32_t)__popcll(tmq & below)] = t_idx;
-                            else if (tier == 5u) sc.tier_list[5][bh + (uint32_t)__popcll(tmh & below)] = t_idx;
+                            uint32_t* list = nullptr;
+                            uint32_t at = 0;
+#pragma unroll
+                            for (int li = 0; li < CW_CH_LISTS; ++li) if (tier == (uint32_t)li + 1u) { list = sc.tier_list[ch_list_id(li)]; at = lb[li] + (uint32_t)__popcll(tm[li] & below); }
+                            if (tier) list[at] = t_idx;
                             sc.seg_off[t.seg_slot] = t.out_off; sc.seg_len[t.seg_slot] = 0;
                         }
                         /* the wave-wide part, entry by entry: member lists (coalesced matrix rows) and long single pieces */
                         for (uint32_t q = 0; q < q_cnt; ++q) {
-                            const uint32_t g_seg = q_seg[q], g_n = q_n[q], g_mx = q_mx[q], g_off = q_off[q];
-                            const int g_ca = q_ca[q], g_cb = q_cb[q];
+                            const uint32_t g_seg = Q->seg[q], g_n = Q->n[q], g_mx = Q->mx[q], g_off = Q->off[q];
+                            const int g_ca = Q->ca[q], g_cb = Q->cb[q];
                             if (g_n == 1u) {
                                 CW_CH_ROUTE(sc.ctr, lane == 0, CW_CR_LONG_SINGLE);
-                                const uint32_t* words = b.bases + b.seq_word_off[s0 + q_fs[q]];
-                                const uint32_t fst = q_fst[q];
+                                const uint32_t* words = b.bases + b.seq_word_off[s0 + Q->fs[q]];
+                                const uint32_t fst = Q->fst[q];
                                 for (uint32_t i = lane; i < g_mx; i += 64) sc.arena[g_off + i] = CW_ACGT(cw_base_at(words, fst + i));
                                 if (lane == 0) { sc.seg_off[seg_base + g_seg] = g_off; sc.seg_len[seg_base + g_seg] = g_mx; }
                             } else {
@@ -638,8 +661,8 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                         if (q_cnt + n_new > 64u) { CW_CH_ROUTE(sc.ctr, lane == 0, CW_CR_EARLY_FLUSH); flush(); }
                         if (serial) {
                             const uint32_t qi = q_cnt + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
-                            q_off[qi] = abs_off; q_need[qi] = need; q_seg[qi] = (uint16_t)seg; q_ca[qi] = (int16_t)ca; q_cb[qi] = (int16_t)cb;
-                            q_n[qi] = (uint16_t)n_mem; q_mx[qi] = (uint16_t)mx; q_fs[qi] = (uint16_t)first_seq; q_fst[qi] = (uint16_t)first_start; q_sl[qi] = sl;
+                            Q->off[qi] = abs_off; Q->need[qi] = need; Q->seg[qi] = (uint16_t)seg; Q->ca[qi] = (int16_t)ca; Q->cb[qi] = (int16_t)cb;
+                            Q->n[qi] = (uint16_t)n_mem; Q->mx[qi] = (uint16_t)mx; Q->fs[qi] = (uint16_t)first_seq; Q->fst[qi] = (uint16_t)first_start; Q->sl[qi] = sl;
                         }
                         q_cnt += n_new;
                         cw_wave_sync();

@@ -3,7 +3,7 @@
  * stage of a window run (cw_engine.cpp enqueue_poa_stage), which is unchanged.
  *
  *   cw_poa_tasks_kernel   stands where setup + index + chain stand: one POA task per GROUP of the batch (task index = group index), its members the group's
- *                         first max_msa non-empty sequences in the order given, routed by the chain kernel's rule (cw_poa_route below); what the POA stage
+ *                         first max_msa non-empty sequences in the order given, routed by the chain kernel's rule (cw_poa_route, cw_poa_q.h); what the POA stage
  *                         expects from cw_setup_kernel (WinInfo status, the neutral task, seg_off / seg_len) comes from here too.
  *   cw_poa_gather_kernel  stands where cw_finish_kernel stands: per group the status, cons_len and the consensus, copied from the arena to the caller's slot.
  *
@@ -14,26 +14,8 @@
 #define CW_POA_OP_H
 
 #include "cw_device.h"
-#include "cw_poa.h"   /* CW_POAX_LC and the tiers' bounds the routing rule reads */
-#include "cw_poa_q.h"
-
-/* The routing rule: which tier a POA task of e_n members, the longest of e_mx bases, goes to first -- 0xFF none (not a POA task), 4 tier Q (list 0), 5 tier H,
-   0 tier S (no list: it walks the task array), 1 / 2 / 3 tiers M1 / M2 / L.  A COPY of the rule in the chain kernel's flush (cw_chain.h "route by the expected
-   graph size", which explains the estimates): one function called from both reordered instructions of cw_chain_kernel (compared in the disassembly), and that
-   kernel's code is to stay what it is.  Change the two together. */
-__device__ __forceinline__ uint32_t cw_poa_route(const DevScratch& sc, const bool poa, const uint32_t e_n, const uint32_t e_mx) {
-    const uint32_t est = (e_mx * 17u + 9u) / 10u;
-    const uint32_t est_s = (e_mx * (15u + e_n / 5u) + 9u) / 10u;
-    const bool fits_h = sc.use_h != 0u && e_mx <= (uint32_t)CW_POAH_LC && e_mx >= sc.h_min_len && est_s <= (uint32_t)CW_POAH_ROUTE_NODES;
-    const bool fits_s = est_s <= sc.s_route_cells && e_mx <= (uint32_t)CW_POA_LC;
-    return !poa ? 0xFFu
-                : (sc.use_q && e_mx <= (uint32_t)CW_POAQ_LC && est_s <= (uint32_t)CW_POAQ_ROUTE_NODES) ? 4u
-                : (fits_h && (sc.use_h > 1u || !fits_s)) ? 5u
-                : fits_s ? 0u
-                : ((sc.m1_route_depth && est_s > est ? est_s : est) <= (uint32_t)CW_POAM1_ROUTE && e_mx <= (uint32_t)CW_POAM1_LC) ? 1u
-                : (est <= (uint32_t)CW_POAM2_ROUTE && e_mx <= (uint32_t)CW_POAM2_LC) ? 2u
-                                                                                  : 3u;
-}
+#include "cw_poa.h"   /* CW_POAX_LC */
+#include "cw_poa_q.h" /* cw_poa_route */
 
 #define CW_POAOP_WAVES 4 /* groups per work-group of the two kernels: one wave each */
 

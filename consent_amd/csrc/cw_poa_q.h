@@ -779,4 +779,28 @@ __global__ void __launch_bounds__(64 * 6, 5) cw_poa_h_kernel(DevBatch b, DevScra
 #endif
 
 #endif /* CW_Q_CODES */
+
+/* The routing rule (behind both builds of tier Q, so that every bound is in sight): which tier a POA task of e_n members, the longest of e_mx bases, goes to
+   first -- 0xFF none (not a POA task), 4 tier Q (list 0), 5 tier H, 0 tier S (no list: it walks the task array), 1 / 2 / 3 tiers M1 / M2 / L.  The chain
+   kernel's flush (cw_chain.h) and cw_poa_tasks_kernel (cw_poa_op.h) both route by it. */
+__device__ __forceinline__ uint32_t cw_poa_route(const DevScratch& sc, const bool poa, const uint32_t e_n, const uint32_t e_mx) {
+    /* route by the expected graph size: the graph has at least max_len nodes once its longest member is in
+       and typically ends at 1.4-1.6x that; a task that still outgrows its tier is redone in the next one */
+    const uint32_t est = (e_mx * 17u + 9u) / 10u;
+    /* deep piles grow wider graphs: the smallest tier is only worth trying when the graph will very likely stay in it
+       (a task that outgrows tier S is redone in tier L, the scarcest one) */
+    const uint32_t est_s = (e_mx * (15u + e_n / 5u) + 9u) / 10u;
+    /* tier Q (four tasks per wave, cw_poa_q.h): members of at most 31 bases and a graph that should stay small */
+    /* tier H (two tasks per wave, cw_poa_q.h): members of up to 63 bases, graph expected (depth-aware) to stay inside its 128 nodes */
+    const bool fits_h = sc.use_h != 0u && e_mx <= (uint32_t)CW_POAH_LC && e_mx >= sc.h_min_len && est_s <= (uint32_t)CW_POAH_ROUTE_NODES;
+    const bool fits_s = est_s <= sc.s_route_cells && e_mx <= (uint32_t)CW_POA_LC; /* s_route_cells: a node count since round 4 */
+    return !poa ? 0xFFu
+                : (sc.use_q && e_mx <= (uint32_t)CW_POAQ_LC && est_s <= (uint32_t)CW_POAQ_ROUTE_NODES) ? 4u
+                : (fits_h && (sc.use_h > 1u || !fits_s)) ? 5u
+                : fits_s ? 0u
+                : ((sc.m1_route_depth && est_s > est ? est_s : est) <= (uint32_t)CW_POAM1_ROUTE && e_mx <= (uint32_t)CW_POAM1_LC) ? 1u
+                : (est <= (uint32_t)CW_POAM2_ROUTE && e_mx <= (uint32_t)CW_POAM2_LC) ? 2u
+                                                                                  : 3u;
+}
+
 #endif

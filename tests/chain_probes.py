@@ -60,6 +60,9 @@ from index_probes import mutate, pack, rand_seq, substitute
 
 __all__ = ["PROBES", "reference", "arithmetic", "pack"]
 
+# cw_chain.h's CW_CH_SLAB, CW_CH_SLAB_LONG, CW_CH_LIST_BYTES and CW_CH_TILE_STRIDE (tests/test_chain_ref_cpu.py holds them to the header)
+CH_SLAB, CH_SLAB_LONG, CH_LIST_BYTES, CH_TILE_STRIDE = 20480, 32768, 1792, 66
+
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------------------
 class Ref:
@@ -202,7 +205,13 @@ def block_bytes(A, N, n_dirty, n_rows):
     return 64 + al(4 * A) + al(8 * A * ((N + 63) // 64)) + al(2 * n_dirty) + al(8 * A) + rows + al(2 * A * Np)
 
 
-def arithmetic(ref, slab=20480):
+def slab_fits(A, slab=CH_SLAB):
+    """cw_chain.h ch_fits: the DP arrays and what lies behind them, and phase D's tile of 65 rows with its 64 sequence lengths over csc, end in front of the queue."""
+    off_csc = (8 * A + 5) & ~3
+    return ((off_csc + 4 * A + 7) & ~7) <= slab - CH_LIST_BYTES and off_csc + 65 * CH_TILE_STRIDE * 2 + 4 + 256 <= slab - CH_LIST_BYTES
+
+
+def arithmetic(ref, slab=CH_SLAB):
     """(route names, (fix, rows, masks, slow)) by the sums of the module docstring, from the reference's numbers."""
     A, N, nd, nk0 = ref.A, ref.N, len(ref.dirty), ref.template_kmers
     Nw = (N + 63) // 64
@@ -221,7 +230,7 @@ def arithmetic(ref, slab=20480):
     n_rows = ref.rows if fix else 0
     one_word = masks and W == 1
     off_csc = (8 * A + 5) & ~3
-    room = slab - 1792 - ((off_csc + 4 * A + 7) & ~7)
+    room = slab - CH_LIST_BYTES - ((off_csc + 4 * A + 7) & ~7)
     Ap = (A + 15) & ~15
     pres = A * Nw * 8
     pres_lds = use_bits and pres <= room
@@ -234,7 +243,7 @@ def arithmetic(ref, slab=20480):
     elif A >= 2:  # (a lone anchor scores no pair)
         names.append("inplace_matrix" if not use_bits else "inplace_rows" if n_rows else "inplace_masks" if one_word else "inplace_all_dirty")
     names += ["pres_lds"] * pres_lds + ["wide_key"] * (not (A * N < 1 << 21 and A < 2047)) + ["far_scan"] * ref.far_step
-    names += ["early_flush"] * ref.early_flush + ["long_single"] * ref.long_single + ["long_slab"] * (slab == 32768)
+    names += ["early_flush"] * ref.early_flush + ["long_single"] * ref.long_single + ["long_slab"] * (slab == CH_SLAB_LONG)
     return sorted(names), (int(fix), n_rows, int(one_word), int(not fast)), nd
 
 
@@ -404,7 +413,7 @@ class Probe:
 
     @property
     def slab(self):
-        return 32768 if self.configure else 20480
+        return CH_SLAB_LONG if self.configure else CH_SLAB
 
     def __repr__(self):
         return self.name

@@ -10,6 +10,7 @@ import pytest
 
 import consent_amd as ca
 import oracle_lib
+import chain_probes
 from chain_probes import PROBES, SWEEP_DEPTHS, SWEEP_LENGTHS, TIE_PRM, arithmetic, check_designed, pieces, reference
 from index_probes import reference_counts
 from consent_amd import engine
@@ -96,6 +97,18 @@ def test_route_table_is_the_kernels():
     assert bits == engine.CHAIN_ROUTE
     dev = open(os.path.join(ROOT, "consent_amd", "csrc", "cw_device.h")).read()
     assert int(re.search(r"CW_PS_CHAIN_ROUTE = (\d+)", dev).group(1)) == engine.CHAIN_ROUTE_SLOT
+
+
+def test_slab_constants_are_the_kernels():
+    """The slab sizes, the queue's bytes and the tile's row stride that tests/chain_probes.py does its sums with are csrc/cw_chain.h's, and its fit test gives the
+    anchor counts that header's static_asserts pin: 1230 on the 20 KB slab (1231 does not fit), CW_TMAX on the long one."""
+    hdr = open(os.path.join(ROOT, "consent_amd", "csrc", "cw_chain.h")).read()
+    define = lambda n: int(re.search(rf"#define {n} (\d+)", hdr).group(1))
+    assert chain_probes.CH_SLAB == define("CW_CH_SLAB") and chain_probes.CH_SLAB_LONG == define("CW_CH_SLAB_LONG")
+    assert chain_probes.CH_LIST_BYTES == define("CW_CH_LIST_BYTES") and chain_probes.CH_TILE_STRIDE == define("CW_CH_TILE_STRIDE")
+    tmax = int(re.search(r"#define CW_TMAX (\d+)", open(os.path.join(ROOT, "consent_amd", "csrc", "cw_index.h")).read()).group(1))
+    assert chain_probes.slab_fits(1230) and not chain_probes.slab_fits(1231)
+    assert chain_probes.slab_fits(tmax, chain_probes.CH_SLAB_LONG)
 
 
 def test_segments_entry_point_is_in_both_builds_and_refuses_without_an_engine():

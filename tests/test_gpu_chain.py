@@ -4,8 +4,8 @@ window, alone in its batch, aimed at one edge of the kernel's scoring routes, it
 and on the test-aid library.  Each run is compared with the oracle (status, consensus, solid set: that locates a failure) and with the plain reference
 of chain_probes.py, exactly: the window's segment count, every POA task's segment and members in order, the lengths of the segments the kernel writes
 itself (Engine.segments), the kernel's own counters (Engine.profile), and on the test-aid library the route witness (Engine.chain_route), which must be
-the probe's hand-written route.  Then the reference's task segments go through Engine.poa as groups: cw_poa_op.h's copy of the flush's routing rule
-must send them to the same tiers, and each consensus must be the oracle's POA of its members."""
+the probe's hand-written route.  Then the reference's task segments go through Engine.poa as groups: cw_poa_tasks_kernel (cw_poa_op.h) calls the routing
+rule the flush calls (cw_poa_route) and must send them to the same tiers, and each consensus must be the oracle's POA of its members."""
 import os
 
 import numpy as np
@@ -89,7 +89,7 @@ def run_and_compare(e, probe):
     assert tuple(int(prof[i]) for i in (50, 51, 52, 53)) == probe.counters, f"{probe}: fix windows, rows, bad masks, slow {prof[50:54]}, designed {probe.counters}"
     assert (int(ctr[0]), int(ctr[1])) == (len(ref.tasks), ref.n_members), f"{probe}: {ctr[0]} tasks of {ctr[1]} members, the reference {len(ref.tasks)} of {ref.n_members}"
     routes = (int(prof[engine.CHAIN_ROUTE_SLOT]), int(prof[engine.INDEX_ROUTE_SLOT]))
-    # the operator's copy of the routing rule: the same tasks as groups, on the same engine (by_anchor segments stay out: the operator aligns them)
+    # the operator routes by the same rule: the same tasks as groups, on the same engine (by_anchor segments stay out: the operator aligns them)
     if groups:
         window_tiers = tiers_of(ctr)
         res = e.poa(groups)
