@@ -87,6 +87,7 @@ enum CwProfSlot : int {
     CW_PS_IDX_TPLHASH = 7,
     CW_PS_POA = 8, CW_PS_POA_STRIDE = 5,                      /* phases of slab tier t at CW_PS_POA + CW_PS_POA_STRIDE * t: 0 S, 1 M1, 2 M2, 3 L, 4 G ... */
     CW_PS_POAQ = 28,                                          /* ... tier Q's, in the slots tier G's rare tasks add to as well */
+    CW_PS_FIN_ROUTE = 33, CW_PS_FIN_LINKS = 34, CW_PS_FIN_NBRS = 35, /* -DCW_TEST_AIDS: the finish kernel's CW_FR_* bits of every window of the batch, ORed; frames its fin_link entered; fin_neighbours calls made from fin_link (cw_finish.h) */
     CW_PS_LONGEST = 36,                                       /* + t: the longest single task of slab tier t */
     CW_PS_SORT_CLOCK = 41,                                    /* wall clock at the tier sort: time base of the task trace */
     CW_PS_CHAIN_ANCHORS = 42, CW_PS_CHAIN_DIRTY = 43, CW_PS_CHAIN_WINDOWS = 44, /* chain kernel: anchors, dirty sequences, windows */
@@ -111,6 +112,7 @@ static_assert(CW_PS_L_CHUNK_ROWS == 46 && CW_PS_L_ROWS == 47, "tier L's fill-row
 static_assert(CW_PS_DIAG == 72 && CW_PS_DIAG_STRIDE == 12 && CW_PS_DIAG + CW_PS_DIAG_STRIDE * 4 == CW_PS_VERIFY_MEMBERS, "diag slots end where the verify slots begin");
 static_assert(CW_PS_VERIFY_MEMBERS == 120 && CW_PS_VERIFY_COLS == 125 && CW_PS_VERIFY_COLS < CW_PROF_SLOTS, "verify slots: tools/verify_codes.py reads them by number");
 static_assert(CW_PS_CHAIN_ANCHORS == 42 && CW_PS_CHAIN_WINDOWS == 44 && CW_PS_CHAIN_ROUTE == 45 && CW_PS_CHAIN_ROUTE < CW_PS_L_CHUNK_ROWS && CW_PS_CHAIN_STAGE == 48 && CW_PS_CHAIN_SLOW_CYCLES == 54 && CW_PS_IDX_STAGE == 55 && CW_PS_IDX_PRESENCE == 62, "chain and index slots");
+static_assert(CW_PS_FIN_ROUTE == 33 && CW_PS_FIN_LINKS == 34 && CW_PS_FIN_NBRS == 35 && CW_PS_POAQ + CW_PS_POA_STRIDE <= CW_PS_FIN_ROUTE && CW_PS_FIN_NBRS < CW_PS_LONGEST, "the finish kernel's witness has the three slots between tier Q's phases and the longest-task slots: consent_amd/engine.py reads them by number");
 static_assert(CW_PS_IDX_ROUTE == 63 && CW_PS_IDX_PRESENCE < CW_PS_IDX_ROUTE && CW_PS_IDX_ROUTE < CW_PS_POAH, "the route witness has the one slot between the index phases and tier H's: consent_amd/engine.py reads it by number");
 
 /* Batch-wide counters (one struct in scratch, zeroed before every run). */

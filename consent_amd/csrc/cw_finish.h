@@ -40,6 +40,43 @@
 #define CW_FIN_SLAB_OF(CB) (3 * (CB) + 4 * CW_FIN_VIS_WORDS + CW_FIN_FRAMES * 48 + 256 + 4 * CW_FIN_SKEYS + 16)
 #define CW_FIN_SLAB CW_FIN_SLAB_OF(CW_FIN_CB)
 
+/* Which way a window went, one bit per decision of this file, and how far its polish walked: a -DCW_TEST_AIDS build keeps them in three registers of the
+   wave while the window runs (no atomics inside the walk: the test-aid kernel walks as the product does) and lane 0 adds them once, when the window is
+   written, to prof[CW_PS_FIN_ROUTE] (ORed), prof[CW_PS_FIN_LINKS] and prof[CW_PS_FIN_NBRS].  The product's kernel has none of it.  A window the first pass
+   hands to the second is recorded by the second alone.  consent_amd/engine.py FINISH_ROUTE names the same bits. */
+enum CwFinRoute : unsigned {
+    CW_FR_STAGED = 1u << 0,       /* the solid keys as words in LDS (n_solid <= CW_FIN_SKEYS)                          */
+    CW_FR_COMPACT = 1u << 1,      /* the compact 16-bit table (k16)                                                   */
+    CW_FR_GLOBAL = 1u << 2,       /* binary searches in global memory                                                 */
+    CW_FR_CNT16 = 1u << 3,        /* counts from their 16-bit copies in LDS                                           */
+    CW_FR_CNT_GLOBAL = 1u << 4,   /* counts from the global words (no staged table, or a count beyond 65535)          */
+    CW_FR_VIS_LDS = 1u << 5,      /* the visited bitmap in LDS                                                        */
+    CW_FR_VIS_GLOBAL = 1u << 6,   /* ... in the wave's global slot                                                    */
+    CW_FR_FIND4 = 1u << 7,        /* fin_find4 looked a key up                                                        */
+    CW_FR_COUNT_SCAN = 1u << 8,   /* fin_count_scan recounted a non-solid anchor k-mer                                */
+    CW_FR_HEAD = 1u << 9,         /* the head was extended by at least one character                                  */
+    CW_FR_TAIL = 1u << 10,        /* the tail was                                                                     */
+    CW_FR_LINKED = 1u << 11,      /* a link succeeded: a weak region was replaced                                     */
+    CW_FR_FIRST_PASS = 1u << 12,  /* written by the first pass (strings in LDS, CW_FIN_CB)                            */
+    CW_FR_SECOND_PASS = 1u << 13  /* written by the second (RETRY: strings in global memory, CW_FIN_CB_BIG)            */
+};
+#ifdef CW_TEST_AIDS
+#define CW_FIN_ROUTE(c, cond, bits) do { if (cond) (c).w_route |= (bits); } while (0)
+#define CW_FIN_COUNT(c, what) do { (c).what++; } while (0) /* what: w_links (frames of fin_link entered), w_nbrs (fin_neighbours calls made from fin_link) */
+#define CW_FIN_WITNESS_FIELDS mutable uint32_t w_route = 0u, w_links = 0u, w_nbrs = 0u;
+#define CW_FIN_WITNESS_BEGIN(pass) uint32_t wit_route = (pass), wit_links = 0u, wit_nbrs = 0u
+#define CW_FIN_WITNESS_TAKE(c) do { wit_route |= (c).w_route; wit_links += (c).w_links; wit_nbrs += (c).w_nbrs; } while (0)
+#define CW_FIN_WITNESS_WRITE(ctr) do { atomicOr(&(ctr)->prof[CW_PS_FIN_ROUTE], (unsigned long long)wit_route); atomicAdd(&(ctr)->prof[CW_PS_FIN_LINKS], (unsigned long long)wit_links); \
+                                       atomicAdd(&(ctr)->prof[CW_PS_FIN_NBRS], (unsigned long long)wit_nbrs); } while (0)
+#else
+#define CW_FIN_ROUTE(c, cond, bits) do { } while (0)
+#define CW_FIN_COUNT(c, what) do { } while (0)
+#define CW_FIN_WITNESS_FIELDS
+#define CW_FIN_WITNESS_BEGIN(pass) do { } while (0)
+#define CW_FIN_WITNESS_TAKE(c) do { } while (0)
+#define CW_FIN_WITNESS_WRITE(ctr) do { } while (0)
+#endif
+
 struct FinOut {
     char* cons;
     const uint64_t* cons_off;
@@ -66,6 +103,7 @@ struct FinCtx {
     const uint64_t* seq_word_off;
     const uint32_t* bases;
     uint32_t s0, N;
+    CW_FIN_WITNESS_FIELDS /* (-DCW_TEST_AIDS only: the route witness's three words) */
 };
 
 /* The key table is in LDS (staged) or in the scratch arena, the visited bitmap in LDS or in the wave's global slot: said with the address
@@ -122,6 +160,7 @@ __device__ __forceinline__ int fin_find4(const FinCtx& c, uint32_t key_g, int la
     const uint32_t n = c.n_solid;
     const uint32_t pv = (uint32_t)l * 64u;
     const fin_l32 sk = (fin_l32)c.skey; /* only called with the table staged */
+    CW_FIN_ROUTE(c, true, CW_FR_FIND4);
     const bool ge = pv < n && key_g >= sk[pv];
     const uint32_t bits = (uint32_t)(__ballot(ge) >> (16 * g)) & 0xFFFFu;
     int mine = -1;
@@ -149,6 +188,7 @@ __device__ uint32_t fin_count_exact(const FinCtx& c, uint32_t key, int lane) {
 /* a k-mer below the solidity threshold is not in the table: count it in the pile */
 __device__ uint32_t fin_count_scan(const FinCtx& c, uint32_t key, int lane) {
     uint32_t n = 0;
+    CW_FIN_ROUTE(c, true, CW_FR_COUNT_SCAN);
     for (uint32_t s = 0; s < c.N; ++s) {
         const uint32_t len = c.seq_len[c.s0 + s];
         const uint32_t* words = c.bases + c.seq_word_off[c.s0 + s];
@@ -243,9 +283,11 @@ __device__ int fin_link(const FinCtx& c, const FinLds& M, uint32_t src, uint32_t
     for (;;) {
         if (child_ret < 0) {
             /* ---- frame entry (DBG.cpp:100-116) ---- */
+            CW_FIN_COUNT(c, w_links);
             if (branches > CW_DBG_MAX_BRANCHES || dist > max_len) { child_ret = 0; goto frame_return; }
             found = (cur == dst);
             n = fin_neighbours(c, cur, 0, nbk, nbi, lane);
+            CW_FIN_COUNT(c, w_nbrs);
             it = 0;
             /* ---- linear stretch (DBG.cpp:119-138) ---- */
             while (!found && n == 1 && it < n && dist <= max_len) {
@@ -258,6 +300,7 @@ __device__ int fin_link(const FinCtx& c, const FinLds& M, uint32_t src, uint32_t
                     plen++; dist++;
                     cw_wave_sync();
                     n = fin_neighbours(c, ck, 0, nbk, nbi, lane);
+                    CW_FIN_COUNT(c, w_nbrs);
                     it = 0;
                 } else if (found) {
                     if (plen + 2 > M.cb) return -1;
@@ -340,6 +383,7 @@ __device__ int fin_polish(const FinCtx& c, FinLds& M, uint32_t len, int lane) {
         int n = fin_neighbours(c, key, 1, nbk, nbi, lane);
         while (n == 1 && dist < ext_len) { /* DBG.cpp:66 */
             key = nbk[0];
+            CW_FIN_ROUTE(c, true, CW_FR_HEAD);
             if (lane == 0) M.s[i - 1 - dist] = CW_ACGT(key >> (2 * (k - 1)));
             dist++;
             cw_wave_sync();
@@ -434,6 +478,7 @@ __device__ int fin_polish(const FinCtx& c, FinLds& M, uint32_t len, int lane) {
             }
         }
         if (region_len > 0) { /* :169-177 */
+            CW_FIN_ROUTE(c, true, CW_FR_LINKED);
             const uint32_t rl = tmp_dst_end - tmp_src_beg + 1;
             /* first occurrence of s[tmp_src_beg, +rl) in s (:173) -- it exists, at tmp_src_beg at the latest */
             uint32_t bpos = tmp_src_beg;
@@ -471,6 +516,7 @@ __device__ int fin_polish(const FinCtx& c, FinLds& M, uint32_t len, int lane) {
         int n = fin_neighbours(c, key, 0, nbk, nbi, lane);
         while (n > 0 && dist < ext_len) { /* DBG.cpp:87 */
             key = nbk[0];
+            CW_FIN_ROUTE(c, true, CW_FR_TAIL);
             if (lane == 0) M.s[i + 1 + dist] = CW_ACGT(key & 3u);
             dist++;
             cw_wave_sync();
@@ -519,6 +565,7 @@ __global__ void __launch_bounds__(64 * WAVES, RETRY ? 4 : 1) /* (the second pass
         uint32_t why = 0;
         int len = 0;
         M.s = buf0; M.alt = buf1;
+        CW_FIN_WITNESS_BEGIN(RETRY ? CW_FR_SECOND_PASS : CW_FR_FIRST_PASS);
 
         if (status == CW_WIN_TEMPLATE && wi.n_seqs == 0) {
             len = 0; /* a window beyond its template has an empty pile (alignmentWindows.cpp:95-97) */
@@ -592,6 +639,7 @@ __global__ void __launch_bounds__(64 * WAVES, RETRY ? 4 : 1) /* (the second pass
                     }
                     c.k = prm.k; c.solid = prm.solid; c.kmask = (prm.k >= 16) ? 0xFFFFFFFFu : ((1u << (2 * prm.k)) - 1u);
                     c.seq_len = b.seq_len; c.seq_word_off = b.seq_word_off; c.bases = b.bases; c.s0 = s0; c.N = wi.n_seqs;
+                    CW_FIN_ROUTE(c, true, (c.staged ? CW_FR_STAGED : c.k16 ? CW_FR_COMPACT : CW_FR_GLOBAL) | (c.scnt16 ? CW_FR_CNT16 : CW_FR_CNT_GLOBAL) | (vis_glb ? CW_FR_VIS_GLOBAL : CW_FR_VIS_LDS));
                     /* weightConsensus: case[p] = solid(k-mer at min(p, len-k)) */
                     for (uint32_t p0 = 0; p0 < (uint32_t)len; p0 += 64) {
                         const uint32_t p = p0 + lane;
@@ -606,6 +654,7 @@ __global__ void __launch_bounds__(64 * WAVES, RETRY ? 4 : 1) /* (the second pass
                     for (uint32_t q = lane; q < (wi.n_solid + 31) / 32; q += 64) fin_vis_clear(M, q);
                     cw_wave_sync();
                     len = fin_polish(c, M, (uint32_t)len, lane);
+                    CW_FIN_WITNESS_TAKE(c);
                     if (len < 0) { status = CW_WIN_OVERFLOW; why = CW_WHY_FIN_POLISH; len = 0; }
                 }
                 if (status == CW_WIN_CONSENSUS) {
@@ -635,6 +684,7 @@ __global__ void __launch_bounds__(64 * WAVES, RETRY ? 4 : 1) /* (the second pass
             out.cons_len[w] = (uint32_t)len;
             out.win_status[w] = (uint8_t)status;
             if (out.solid) out.solid_len[w] = (status == CW_WIN_OVERFLOW) ? 0u : n_sol;
+            CW_FIN_WITNESS_WRITE(sc.ctr);
         }
         cw_wave_sync();
     }

@@ -202,6 +202,13 @@ CHAIN_ROUTE = {"fast": 1 << 0, "rows_lds": 1 << 1, "rows_far": 1 << 2, "pres_lds
                "inplace_masks": 1 << 7, "inplace_all_dirty": 1 << 8, "inplace_matrix": 1 << 9, "early_flush": 1 << 10, "long_single": 1 << 11, "long_slab": 1 << 12}
 
 
+# The finish kernel's witness (csrc/cw_finish.h enum CwFinRoute, csrc/cw_device.h CW_PS_FIN_ROUTE .. CW_PS_FIN_NBRS): the route bits, and behind them how often
+# fin_link entered a frame and how often it called fin_neighbours, summed over the batch's windows.
+FINISH_ROUTE_SLOT = 33
+FINISH_ROUTE = {"staged": 1 << 0, "compact": 1 << 1, "global": 1 << 2, "cnt16": 1 << 3, "cnt_global": 1 << 4, "vis_lds": 1 << 5, "vis_global": 1 << 6, "find4": 1 << 7,
+                "count_scan": 1 << 8, "head": 1 << 9, "tail": 1 << 10, "linked": 1 << 11, "first_pass": 1 << 12, "second_pass": 1 << 13}
+
+
 def route_names(bits, table=None):
     """The names of the bits of `table` (default INDEX_ROUTE) set in `bits`, for messages."""
     return sorted(n for n, b in (table or INDEX_ROUTE).items() if bits & b)
@@ -700,6 +707,12 @@ class Engine:
     def chain_route(self):
         """The CHAIN_ROUTE bits of the last batch's windows, ORed (a window alone in its batch: its route).  Zero from the product library."""
         return int(self.profile()[1][CHAIN_ROUTE_SLOT])
+
+    def finish_route(self):
+        """(FINISH_ROUTE bits of the last batch's windows, ORed; frames fin_link entered; fin_neighbours calls it made) -- a window alone in its batch: its
+        own.  Zeros from the product library."""
+        p = self.profile()[1]
+        return int(p[FINISH_ROUTE_SLOT]), int(p[FINISH_ROUTE_SLOT + 1]), int(p[FINISH_ROUTE_SLOT + 2])
 
     def segments(self, w):
         """cw_debug_segments: the chain kernel's segmentation of window w of the last run -- (n_segs, seg_len, tasks).  n_segs is chain anchors + 1, or 0 for a
