@@ -405,42 +405,110 @@ struct PoaQSt {
 };
 #define POAQ_PROF(slot) do { const unsigned long long _n = __builtin_readcyclecounter(); acc[slot] += _n - S.pt; S.pt = _n; } while (0)
 
+/* The member window: a task's members GW at a time, in registers.  Lane gl of the group holds member base + gl -- its length and its bases as a KEY, the
+   2-bit codes left-aligned in KW words (base j in word j >> 4, as cw_base_at reads it), zero behind the last base, so that two members are equal base for
+   base iff their lengths and keys are.  Walking a task member by member was three dependent global loads each (the descriptor, the sequence's word offset,
+   the words) with the wave's other groups waiting; a window is the same three loads once for GW members, every lane issuing its own, and a member's turn
+   touches no global memory.  len, key: per lane; base, dup: equal in the group's lanes. */
+template <class T>
+struct PoaQWin {
+    static constexpr int KW = (T::LC + 15) / 16;
+    uint32_t key[KW];
+    int len;       /* -1 behind the task's last member */
+    uint32_t base; /* the window's first member */
+    uint32_t dup;  /* bit l: member base + l has the length and the key of the member before it (bit 0: of the window before's last) */
+    __device__ __forceinline__ void reset() { /* no window yet: member 0 is not in it, and nothing equals the member before member 0 */
+        for (int k = 0; k < KW; ++k) key[k] = 0u;
+        len = -1; base = 0u - (uint32_t)T::GW; dup = 0u;
+    }
+};
+
+/* the window from member `first` on: one load of GW descriptors, one of their word offsets, then the words that hold bases of the piece -- (start >> 4) ..
+   ((start + len - 1) >> 4), at most KW + 1 of them, none behind the piece's last base (the batch promises no padding behind its last sequence).  A member of
+   more than LC bases keeps its length (poaq_take ends the task there) and loads nothing. */
+template <class T>
+__device__ __forceinline__ void poaq_window(PoaQWin<T>& W, const PoaTask& t, const DevBatch& b, const DevScratch& sc, const uint32_t first, const int gl) {
+    constexpr int GW = T::GW, KW = PoaQWin<T>::KW;
+    const int plen = g_bcast<T>(W.len, GW - 1); /* the member before `first`: the last one of the window this one replaces */
+    uint32_t pkey[KW];
+#pragma unroll
+    for (int k = 0; k < KW; ++k) pkey[k] = (uint32_t)g_bcast<T>((int)W.key[k], GW - 1);
+    const uint32_t idx = first + (uint32_t)gl;
+    const bool in = idx < t.n_members;
+    PoaMember pm;
+    pm.seq = 0u; pm.start = 0; pm.len = 0;
+    if (in) pm = sc.members[t.member_off + idx];
+    const int len = in ? (int)pm.len : -1;
+    uint32_t x[KW + 1];
+#pragma unroll
+    for (int k = 0; k <= KW; ++k) x[k] = 0u;
+    if (len >= 1 && len <= T::LC) {
+        const uint32_t* words = b.bases + b.seq_word_off[pm.seq];
+        const uint32_t w0 = (uint32_t)pm.start >> 4, wl = ((uint32_t)pm.start + (uint32_t)len - 1u) >> 4;
+#pragma unroll
+        for (int k = 0; k <= KW; ++k) if (w0 + (uint32_t)k <= wl) x[k] = words[w0 + (uint32_t)k];
+    }
+    const uint32_t sh = 2u * ((uint32_t)pm.start & 15u);
+    const int llen = g_shr1<T>(len, gl); /* the neighbour lane's member (every lane of the group takes part) */
+    bool same = in && len == (gl == 0 ? plen : llen) && len <= T::LC;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        const int nb = len - 16 * k; /* bases of the piece in key word k */
+        const uint32_t keep = nb >= 16 ? 0xFFFFFFFFu : nb <= 0 ? 0u : ~(0xFFFFFFFFu >> (2 * nb));
+        const uint32_t v = (uint32_t)((((((uint64_t)x[k]) << 32) | x[k + 1]) << sh) >> 32) & keep;
+        const uint32_t left = (uint32_t)g_shr1<T>((int)v, gl);
+        same = same && v == (gl == 0 ? pkey[k] : left);
+        W.key[k] = v;
+    }
+    W.len = len; W.base = first;
+    W.dup = g_ballot<T>(same);
+}
+
 /* Round 6, the replay of a repeated member (CW_POAQ_REPLAY).  A member that is, base for base, the member aligned just before it -- and that one changed nothing
    in the graph but coverage counts -- meets the same graph with the same bases: the same fill, the same walk back, the same path.  Its merge is the coverage
-   counts of that path once more (M.pcur still holds it, M.sq the bases), and the alignment is not run.  Measured on the checker (a scratch build of the
+   counts of that path once more (M.pcur still holds it), and the alignment is not run.  Measured on the checker (a scratch build of the
    restatement over the bench piles, every replayed path compared with the one the alignment gives: 0 of 14 000 differ): 38 % of this tier's members at depth
    150 -- the error-free copy of a short piece comes again and again.  The four tasks of a wave share one instruction stream, so a group does not skip a round
    the others run: it takes its repeated members in a short loop of its own HERE and joins the round with the first member that needs an alignment.
    (Not under the heaviest-bundle policy: a replay would have to raise the path's edge weights too.) */
-/* Takes the members from mi on that repeat the member aligned before them; returns with pm = member mi, the first one that needs an alignment (or mi == n_members). */
+/* Brings the window to member mi and, with CW_POAQ_REPLAY, takes the members from mi on that repeat the member before them (the window's dup bits: a member
+   equal to its predecessor is equal to the one aligned last, every member between the two having been a repeat): the run of set bits from mi on in ONE
+   pass over the path -- r at once is what r single additions leave in the bytes of ncov -- and on over a refill of the window.  Returns with mi the first
+   member that needs an alignment, inside the window, or mi == n_members. */
 template <class T>
-__device__ __forceinline__ void poaq_replay(const PoaQ<T>& M, PoaQSt& S, const PoaTask& t, const DevBatch& b, const DevScratch& sc, uint32_t& mi, PoaMember& pm, const int gl) {
-#if CW_POAQ_REPLAY
+__device__ __forceinline__ void poaq_next(const PoaQ<T>& M, PoaQSt& S, PoaQWin<T>& W, const PoaTask& t, const DevBatch& b, const DevScratch& sc, uint32_t& mi, const int gl) {
     constexpr int GW = T::GW;
-    if (!CW_CONS_HEAVIEST_BUNDLE) {
-        while (S.prev_clean && (int)pm.len == S.prev_L) {
-            const uint32_t* words_ = b.bases + b.seq_word_off[pm.seq];
-            bool same = true;
-            for (int j = gl; j < S.prev_L; j += GW) same = same && M.sq[j] == (uint8_t)cw_base_at(words_, pm.start + j);
-            if (g_ballot<T>(!same) != 0u) break;
-            for (int j = gl; j < S.prev_L; j += GW) { const int cur = M.pcur[j]; M.ncov[cur] = (uint8_t)(M.ncov[cur] + 1); } /* (a path visits a node once; lane j owns position j, as in the merge) */
-            S.nseq++;
-            if (++mi >= t.n_members) break;
-            pm = sc.members[t.member_off + mi];
-        }
-    }
+    while (mi < t.n_members) {
+        if (mi - W.base >= (uint32_t)GW) poaq_window<T>(W, t, b, sc, mi, gl);
+        int r = 0;
+#if CW_POAQ_REPLAY
+        if (!CW_CONS_HEAVIEST_BUNDLE && S.prev_clean) r = __ffsll((long long)~(unsigned long long)(W.dup >> (mi - W.base))) - 1;
 #endif
+        if (r == 0) break;
+        for (int j = gl; j < S.prev_L; j += GW) { const int cur = M.pcur[j]; M.ncov[cur] = (uint8_t)(M.ncov[cur] + r); } /* (a path visits a node once; lane j owns position j, as in the merge) */
+        S.nseq += r;
+        mi += (uint32_t)r;
+    }
 }
 
-/* the member's bases into M.sq; the first member of a task becomes a chain (returns 1: nothing to align), a later one is aligned by poaq_member (0); 2 = beyond this tier */
+/* member mi's bases from the window into M.sq; the first member of a task becomes a chain (returns 1: nothing to align), a later one is aligned by poaq_member (0); 2 = beyond this tier */
 template <class T>
-__device__ __forceinline__ int poaq_take(const PoaQ<T>& M, PoaQSt& S, const PoaMember& pm, const DevBatch& b, const int gl) {
-    constexpr int GW = T::GW;
-    const int L = (int)pm.len;
+__device__ __forceinline__ int poaq_take(const PoaQ<T>& M, PoaQSt& S, const PoaQWin<T>& W, const uint32_t mi, const int gl) {
+    constexpr int GW = T::GW, KW = PoaQWin<T>::KW;
+    const int at = (int)(mi - W.base);
+    const int L = g_bcast<T>(W.len, at);
     if ((uint32_t)L > (uint32_t)T::LC) return 2;
     {
-        const uint32_t* words = b.bases + b.seq_word_off[pm.seq];
-        for (int j = gl; j < L; j += GW) M.sq[j] = (uint8_t)cw_base_at(words, pm.start + j);
+        uint32_t key[KW];
+#pragma unroll
+        for (int k = 0; k < KW; ++k) key[k] = (uint32_t)g_bcast<T>((int)W.key[k], at);
+#pragma unroll
+        for (int j0 = 0; j0 < T::LC; j0 += GW) { /* position j0 + gl: key word j0 / 16, or (32 lanes) the one after it for the group's upper lanes */
+            const int j = j0 + gl;
+            uint32_t w = key[j0 >> 4];
+            if constexpr (GW == 32) { const uint32_t up = 0u - (((uint32_t)gl >> 4) & 1u); w = (w & ~up) | (key[(j0 >> 4) + 1] & up); } /* (bitwise: a select of two array elements becomes an indexed load from scratch) */
+            if (j < L) M.sq[j] = (uint8_t)((w >> (30 - 2 * (j & 15))) & 3u);
+        }
     }
     cw_wave_sync();
     S.nseq++;
@@ -724,14 +792,15 @@ __device__ int poaq_run(const PoaQ<T>& M, const PoaTask& t, const DevBatch& b, c
     PoaQSt S;
     S.reset(); S.pt = __builtin_readcyclecounter();
     if (t.n_members > 255u) return 2; /* coverage counts and edge weights are bytes here */
+    PoaQWin<T> W;
+    W.reset();
     for (uint32_t mi = 0; mi < t.n_members; ++mi) {
-        PoaMember pm = sc.members[t.member_off + mi];
-        poaq_replay<T>(M, S, t, b, sc, mi, pm, gl);
+        poaq_next<T>(M, S, W, t, b, sc, mi, gl);
         if (mi >= t.n_members) break;
-        const int tk = poaq_take<T>(M, S, pm, b, gl);
+        const int tk = poaq_take<T>(M, S, W, mi, gl);
         if (tk == 2) return 2;
         if (tk == 1) continue;
-        const int rc = poaq_member<T>(M, S, (int)pm.len, gl, acc);
+        const int rc = poaq_member<T>(M, S, S.prev_L, gl, acc);
         if (rc) return rc;
     }
     return poaq_finish<T>(M, S, t, sc, gl, acc);
