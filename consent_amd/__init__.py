@@ -12,9 +12,16 @@ from .engine import (  # noqa: F401
     SW_ALIGNED,
     SW_IS_REF,
     SW_NO_INDELS,
+    SW_NO_PATH,
+    SW_PATH_EQX,
+    SW_PATH_OPEN,
+    SW_PATH_SLOT,
     SW_STOP,
     SW_WANT_INDELS,
+    SwPathRows,
+    SwPaths,
     SwRows,
+    sw_ops_bound,
     SynthSpec,
     WIN_CONSENSUS,
     WIN_OVERFLOW,

@@ -5,7 +5,7 @@
  * and the inspection entry points; the launchers of the path's neighbours (pile extraction, result planning, read re-assembly); host batches (cw_submit /
  * cw_wait) and the loop that runs a batch again with a larger plan (cw_run, cw_run_device_sync); the POA stage alone on a batch of groups (cw_poa_run_device,
  * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run); the re-assembly's local aligner alone on a batch of groups
- * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h).
+ * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h).
  * The scratch plan is cw_plan.h (host arithmetic only); the host feeders, cw_window_positions among them, are cw_hostio.cpp.
  */
 #include "cw_internal.h"
@@ -22,6 +22,7 @@
 #include "cw_plan.h"
 #include "cw_poa_op.h"
 #include "cw_sw_op.h"
+#include "cw_sw_path.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -112,7 +113,8 @@ int set_kernel_attributes(const hipDeviceProp_t& prop) {
         allow(TierM1::kernel<1>(), TierM1::lds) && allow(TierM2::kernel<1>(), TierM2::lds) && allow(TierL::kernel<1>(), TierL::lds) &&
         allow((const void*)cw_finish_kernel<CW_FIN_CB, CW_FIN_WAVES, false>, kLdsFinish) && allow((const void*)cw_finish_kernel<CW_FIN_CB_BIG, 1, true>, kLdsFinishBig) &&
         allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES>, lds_st) &&
-        allow((const void*)cw_sw_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_kernel<1>, lds_sw(1));
+        allow((const void*)cw_sw_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_kernel<1>, lds_sw(1)) &&
+        allow((const void*)cw_sw_path_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_path_kernel<1>, lds_sw(1));
     return ok ? CW_OK : CW_E_NO_DEVICE;
 }
 
@@ -487,6 +489,56 @@ int run_sw_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t 
     return CW_OK;
 }
 
+/* what cw_sw_path_run and cw_sw_path_run_device refuse, as validate_sw */
+int validate_sw_path(const cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_sw_paths* paths, uint32_t flags) {
+    if (!e || !groups || !paths || (flags & ~CW_SW_PATH_EQX)) return CW_E_INVALID;
+    if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
+    if (groups->n_windows == 0 || groups->n_seqs == 0) return groups->n_seqs == 0 ? CW_OK : CW_E_INVALID;
+    if (!rows || !groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
+    if (!paths->ops || !paths->ops_off || !paths->n_ops) return CW_E_INVALID;
+    return CW_OK;
+}
+
+/* the body of cw_sw_path_run_device, in the shape of run_sw_locked: sw_order, then sw_path, sw_path_wide, sw_path_long one after the other on st; the plan is
+   exact and lives in the engine's one scratch allocation. */
+int run_sw_path_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream) {
+    int rc = validate_sw_path(e, groups, rows, paths, flags);
+    if (rc || groups->n_seqs == 0) return rc;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    const uint32_t S = groups->n_seqs;
+    const SwPathPlan p = plan_sw_path(groups->n_windows, S, groups->n_words, e->cus);
+    if ((rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) != CW_OK) return rc;
+    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (run_sw_locked) */
+    uint8_t* base = (uint8_t*)e->scratch;
+    SwPathArgs pa;
+    SwArgs& a = pa.a;
+    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.n_seqs = S; a.rows = rows; a.flags = flags;
+    a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
+    a.dir = (int8_t*)(base + p.dir); a.dir_bytes = p.dir_bytes;
+    a.gref = base + p.gref; a.lstate = base + p.lstate;
+    pa.ops = paths->ops; pa.ops_off = paths->ops_off; pa.n_ops = paths->n_ops; pa.steps = base + p.steps;
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_SW_CTR_WORDS * 4, st));
+    CW_HIP(hipMemsetAsync(pa.n_ops, 0, (size_t)S * 4, st)); /* rows the order kernel writes, and pairs without a path */
+    const uint32_t og = (S + 255u) / 256u;
+    stage(e, st, "sw_order", [&] {
+        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 0);
+        cw_sw_order_kernel<<<1, 256, 0, st>>>(a, 1);
+        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 2);
+    });
+    stage(e, st, "sw_path", [&] { cw_sw_path_kernel<0><<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(pa); });
+    stage(e, st, "sw_path_wide", [&] { cw_sw_path_kernel<1><<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(pa); });
+    stage(e, st, "sw_path_long", [&] { cw_sw_path_long_kernel<<<p.wgs_long, 64, 0, st>>>(pa); });
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -679,6 +731,78 @@ int cw_sw_run(cw_engine* e, const cw_batch* b, int32_t* rows, uint32_t flags) {
     CW_HIP(hipStreamSynchronize(st));
     for (uint32_t s = 0; s < S; ++s) if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) rc = CW_E_CAPACITY;
     return rc;
+}
+
+int cw_sw_path_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_sw_path_locked(e, groups, rows, paths, flags, hip_stream);
+}
+
+/* Host buffers in, host buffers out, synchronous, as cw_sw_run: the batch and the slots' offsets go up, cw_sw_path_run_device on the engine's stream, rows and
+   op counts come back -- and of the ops only what was written: a slot's words beyond its path, and every slot without one, stay the caller's. */
+int cw_sw_path_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_paths* paths, uint32_t flags) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = validate_sw_path(e, b, rows, paths, flags);
+    if (rc || b->n_seqs == 0) return rc;
+    const uint32_t G = b->n_windows, S = b->n_seqs;
+    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
+    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
+    for (uint32_t s = 0; s < S; ++s) {
+        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
+        if (paths->ops_off[s + 1] < paths->ops_off[s]) return CW_E_INVALID;
+    }
+    const uint64_t p0 = paths->ops_off[0], n_slots = paths->ops_off[S] - p0; /* the device copy begins at the first slot */
+    size_t o = 0;
+    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
+                 i_poff = put((size_t)(S + 1) * 8);
+    const size_t in_bytes = o;
+    o = 0;
+    const size_t o_rows = put((size_t)S * CW_SW_ROW * 4), o_nops = put((size_t)S * 4), o_ops = put((size_t)n_slots * 4);
+    const size_t out_bytes = o;
+    std::vector<uint64_t> poff;
+    std::vector<uint32_t> back;
+    try { poff.resize((size_t)S + 1); back.resize((size_t)n_slots); } catch (...) { return CW_E_NOMEM; }
+    for (uint32_t s = 0; s <= S; ++s) poff[s] = paths->ops_off[s] - p0;
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    uint8_t *din = (uint8_t*)e->poa_in, *dout = (uint8_t*)e->poa_out;
+    hipStream_t st = e->stream;
+    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_poff, poff.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
+    cw_batch db = *b;
+    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
+    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
+    cw_sw_paths dp;
+    dp.ops = (uint32_t*)(dout + o_ops); dp.ops_off = (const uint64_t*)(din + i_poff); dp.n_ops = (uint32_t*)(dout + o_nops);
+    if ((rc = run_sw_path_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st)) != CW_OK) return rc;
+    CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipMemcpyAsync(paths->n_ops, dout + o_nops, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    if (n_slots) CW_HIP(hipMemcpyAsync(back.data(), dout + o_ops, (size_t)n_slots * 4, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    for (uint32_t s = 0; s < S; ++s) {
+        const int status = rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS];
+        if (status == CW_SW_STOP) rc = CW_E_CAPACITY;
+        if (status == CW_SW_ALIGNED && paths->n_ops[s] && paths->n_ops[s] <= poff[s + 1] - poff[s])
+            memcpy(paths->ops + paths->ops_off[s], back.data() + poff[s], (size_t)paths->n_ops[s] * 4);
+    }
+    return rc;
+}
+
+/* Debug/inspection (cw_private.h): what plan_sw_path would allocate, part by part, and its grids (host arithmetic only). */
+int cw_debug_sw_path_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t flags, uint64_t* out12) {
+    if (!out12 || cus < 1 || (flags & ~CW_SW_PATH_EQX)) return CW_E_INVALID;
+    const SwPathPlan p = plan_sw_path(n_groups, n_seqs, n_words, cus);
+    const uint64_t v[12] = {p.total, (uint64_t)p.gref, (uint64_t)(p.lstate - p.gref), (uint64_t)(p.dir - p.lstate), (uint64_t)(p.steps - p.dir), (uint64_t)(p.total - p.steps),
+                            p.wgs0, p.wgs1, p.wgs_long, p.dir_waves, p.dir_bytes, CW_SW_STEP_BYTES};
+    for (int i = 0; i < 12; ++i) out12[i] = v[i];
+    return CW_OK;
 }
 
 /* Debug/inspection (cw_private.h): what plan_sw would allocate, part by part, and its grids (host arithmetic only). */

@@ -10,7 +10,7 @@
 #include "cw_env.h"
 #include "cw_index.h"  /* CW_EXG_SLOTS; with each of these: cw_device.h (the records' sizes, CW_TIERS) and include/consent_amd.h */
 #include "cw_poa_q.h"  /* slab and graph sizes of every tier (cw_poa.h comes with it) */
-#include "cw_sw_op.h"  /* the alignment operator's per-wave sizes (cw_stitch.h comes with it) */
+#include "cw_sw_path.h" /* the alignment operator's per-wave sizes, the path run's too (cw_sw_op.h and cw_stitch.h come with it) */
 #include "cw_finish.h" /* CW_FIN_*.  (These three are kernel headers, taken for their size macros: nothing here runs on the device, but a translation unit that includes this one is still a HIP one) */
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -217,6 +217,37 @@ static inline SwPlan plan_sw(uint32_t n_groups, uint32_t n_seqs, uint64_t n_word
     put(p.gref, (size_t)std::max(p.wgs0, p.wgs1) * CW_SW_WAVES * CW_SW_GREF_BYTES);
     put(p.lstate, (size_t)p.wgs_long * CW_SW_LONG_WAVE_BYTES);
     put(p.dir, (size_t)p.dir_waves * p.dir_bytes);
+    p.total = o;
+    return p;
+}
+
+/* The plan of a path run (cw_sw_path_run, cw_sw_path.h): plan_sw's parts -- counters, pair list, per wave the long reference and the long launch's state --
+   and per wave of the largest grid the traceback's CW_SW_PATH_BYTES (directions, a byte a cell, and the rows once they outgrow LDS) and the walk's
+   CW_SW_STEP_BYTES.  Exact, like plan_sw.  The grids stop where the direction scratch of a run reaches what plan_sw holds under CW_SW_WANT_INDELS:
+   CW_SW_PATH_MAX_WAVES waves x 2 MiB = 1 GiB, so class 0 and class 1 launch at most 128 work-groups of four waves, the long launch its 256 of one. */
+struct SwPathPlan {
+    size_t ctr, seq_ref, order, gref, lstate, dir, steps, total;
+    uint32_t wgs0, wgs1, wgs_long, dir_waves, dir_bytes;
+};
+static inline SwPathPlan plan_sw_path(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus) {
+    (void)n_groups; (void)n_words;
+    SwPathPlan p;
+    memset(&p, 0, sizeof(p));
+    const uint32_t by_seqs = (n_seqs + CW_SW_WAVES - 1) / CW_SW_WAVES, most = CW_SW_PATH_MAX_WAVES / CW_SW_WAVES;
+    p.wgs0 = std::max(1u, std::min(by_seqs, std::min<uint32_t>((uint32_t)cus * 4u, most)));
+    p.wgs1 = std::max(1u, std::min(by_seqs, std::min<uint32_t>((uint32_t)cus, most)));
+    p.wgs_long = std::max(1u, std::min<uint32_t>(n_seqs, CW_SW_LONG_MAX_WGS));
+    p.dir_bytes = CW_SW_PATH_BYTES;
+    p.dir_waves = std::max(std::max(p.wgs0, p.wgs1) * CW_SW_WAVES, p.wgs_long);
+    size_t o = 0;
+    auto put = [&](size_t& slot, size_t bytes) { slot = o; o = align_up(o + bytes, 256); };
+    put(p.ctr, (size_t)CW_SW_CTR_WORDS * 4);
+    put(p.seq_ref, (size_t)n_seqs * 4);
+    put(p.order, (size_t)n_seqs * 4);
+    put(p.gref, (size_t)std::max(p.wgs0, p.wgs1) * CW_SW_WAVES * CW_SW_GREF_BYTES);
+    put(p.lstate, (size_t)p.wgs_long * CW_SW_LONG_WAVE_BYTES);
+    put(p.dir, (size_t)p.dir_waves * p.dir_bytes);
+    put(p.steps, (size_t)p.dir_waves * CW_SW_STEP_BYTES);
     p.total = o;
     return p;
 }

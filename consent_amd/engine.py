@@ -14,7 +14,18 @@ SW_ALIGNED, SW_NO_INDELS, SW_STOP, SW_IS_REF = 0, 1, 2, 3
 SW_SCORE, SW_REF_BEGIN, SW_REF_END, SW_QUERY_BEGIN, SW_QUERY_END, SW_INS, SW_DEL, SW_STATUS, SW_ROW = 0, 1, 2, 3, 4, 5, 6, 7, 8
 SW_WANT_INDELS = 1
 SW_QMAX, SW_RMAX, SW_DIR_BYTES = 32768, 16383, 1 << 20
+# cw_sw_path_run: the statuses only it writes, its flag, the op codes, the per-wave traceback scratch
+SW_NO_PATH, SW_PATH_OPEN, SW_PATH_SLOT = 4, 5, 6
+SW_PATH_EQX = 4
+SW_OP_M, SW_OP_I, SW_OP_D, SW_OP_EQ, SW_OP_X = 0, 1, 2, 7, 8
+SW_PATH_BYTES = 2 << 20
+SW_OP_LETTERS = {SW_OP_M: "M", SW_OP_I: "I", SW_OP_D: "D", SW_OP_EQ: "=", SW_OP_X: "X"}
 _HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def sw_ops_bound(query_len, ref_len):
+    """CW_SW_OPS_BOUND: a slot of this many ops holds any path of the pair."""
+    return query_len + ref_len
 
 
 class EngineError(RuntimeError):
@@ -37,6 +48,12 @@ class Batch(C.Structure):
         ("seq_word_off", C.c_void_p),
         ("bases", C.c_void_p),
     ]
+
+
+class SwPaths(C.Structure):
+    """cw_sw_paths: the op slots of cw_sw_path_run."""
+
+    _fields_ = [("ops", C.c_void_p), ("ops_off", C.c_void_p), ("n_ops", C.c_void_p)]
 
 
 class Result(C.Structure):
@@ -137,6 +154,10 @@ def _load(p):
         lib.cw_sw_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_uint32]
         lib.cw_sw_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_uint32, C.c_void_p]
         lib.cw_debug_sw_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p]
+    if hasattr(lib, "cw_sw_path_run"):
+        lib.cw_sw_path_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwPaths), C.c_uint32]
+        lib.cw_sw_path_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwPaths), C.c_uint32, C.c_void_p]
+        lib.cw_debug_sw_path_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p]
     lib.cw_submit.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.POINTER(C.c_int)]
     lib.cw_wait.argtypes = [C.c_void_p, C.c_int]
     lib.cw_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -494,6 +515,27 @@ class SwRows:
         return self.rows[self.index(group, member)]
 
 
+class SwPathRows(SwRows):
+    """What Engine.sw_path returns: SwRows, and per sequence `n_ops` and its slot ops_buf[ops_off[s] : ops_off[s + 1]] of `length << 4 | op` words, of which
+    the first n_ops are the path (none unless the row's status is SW_ALIGNED)."""
+
+    def __init__(self, rows, win_first_seq, rc, n_ops, ops_buf, ops_off):
+        super().__init__(rows, win_first_seq, rc)
+        self.n_ops, self.ops_buf, self.ops_off = n_ops, ops_buf, ops_off
+
+    def ops(self, group, member):
+        """The path of (group, member) as a list of (length, op code); empty when the row reports none."""
+        s = self.index(group, member)
+        if int(self.rows[s, SW_STATUS]) != SW_ALIGNED:
+            return []
+        o = int(self.ops_off[s])
+        return [(int(w) >> 4, int(w) & 15) for w in self.ops_buf[o : o + int(self.n_ops[s])]]
+
+    def cigar(self, group, member):
+        """The path as a CIGAR string such as "35M2I10M1D4M" ("=" and "X" in place of "M" when the run had eqx=True)."""
+        return "".join(f"{n}{SW_OP_LETTERS[op]}" for n, op in self.ops(group, member))
+
+
 def _result_struct(r):
     return Result(
         _ptr(r.cons), _ptr(r.cons_off), _ptr(r.cons_len), _ptr(r.status),
@@ -578,6 +620,33 @@ class Engine:
     def sw_device(self, batch_struct, rows_ptr, flags=0, stream=None):
         """cw_sw_run_device: device pointers in the batch struct, `rows_ptr` a device array of n_seqs * SW_ROW int32; asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_sw_run_device(self.handle, C.byref(batch_struct), rows_ptr, flags, stream), "cw_sw_run_device")
+
+    def sw_path(self, groups, eqx=False, slot_ops=None):
+        """The local alignment with its path (cw_sw_path_run): `groups` as for sw().  Returns SwPathRows: the rows of sw() with ins / del always filled in,
+        .n_ops, .ops(group, member) and .cigar(group, member).  Statuses beyond sw()'s: SW_NO_PATH (the traceback's directions outgrow a wave's scratch),
+        SW_PATH_OPEN, SW_PATH_SLOT (the ops outgrow the slot: n_ops is the number needed).  slot_ops: ops a sequence's slot holds, one number or one per
+        sequence (default: sw_ops_bound of the sequence and its group's reference, which every path fits)."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        S = len(batch.seq_len)
+        if slot_ops is None:
+            wfs = np.asarray(batch.win_first_seq, np.int64)
+            ref_of = np.repeat(wfs[:-1], np.diff(wfs))
+            lens = np.asarray(batch.seq_len, np.int64)
+            slot_ops = lens + lens[ref_of] if S else np.zeros(0, np.int64)
+        ops_off = np.zeros(S + 1, np.uint64)
+        ops_off[1:] = np.cumsum(np.broadcast_to(np.asarray(slot_ops, np.int64), (S,)))
+        ops_buf = np.zeros(max(int(ops_off[-1]), 1), np.uint32)
+        n_ops = np.zeros(max(S, 1), np.uint32)
+        rows = np.zeros((S, SW_ROW), np.int32)
+        b = batch.c_struct()
+        paths = SwPaths(_ptr(ops_buf), _ptr(ops_off), _ptr(n_ops))
+        rc = _check(self.lib, self.lib.cw_sw_path_run(self.handle, C.byref(b), _ptr(rows), C.byref(paths), SW_PATH_EQX if eqx else 0), "cw_sw_path_run", allow_capacity=True)
+        return SwPathRows(rows, batch.win_first_seq, rc, n_ops[:S], ops_buf, ops_off)
+
+    def sw_path_device(self, batch_struct, rows_ptr, paths_struct, flags=0, stream=None):
+        """cw_sw_path_run_device: device pointers in the batch struct and in `paths_struct` (SwPaths), `rows_ptr` a device array of n_seqs * SW_ROW int32;
+        asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_sw_path_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(paths_struct), flags, stream), "cw_sw_path_run_device")
 
     def extract_piles(self, reads, overlaps, jobs, k):
         """Device-side getAlignmentWindowsSequences (cw_extract_piles_device).  `reads` is a HostBatch-like packing of the read

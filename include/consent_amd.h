@@ -13,6 +13,7 @@
  *                               groups of sequences: for callers that have their segments -- or racon-style windows, amplicon / UMI families -- in hand.
  *   cw_sw_run / cw_sw_run_device <- StripedSmithWaterman::Aligner::Align as alignConsensus calls it (correctionAlignment.cpp:90, :110), batched over
  *                               (query, reference) pairs: the local aligner of cw_stitch_device on its own.
+ *   cw_sw_path_run / cw_sw_path_run_device <- the same pairs with the alignment itself (ssw's banded traceback, its cigar) as run-length encoded ops.
  *   cw_window_positions      <- getAlignmentWindowsPositions (alignmentWindows.cpp:27-85), host
  *   cw_extract_piles_device  <- getAlignmentWindowsSequences (alignmentWindows.cpp:87-149) evaluated on the device
  *   cw_stitch_device         <- alignConsensus + trimRead + dropRead (correctionAlignment.cpp:47-140, utils.cpp:96-128, :71-73)
@@ -224,6 +225,44 @@ enum { CW_SW_ALIGNED = 0, CW_SW_NO_INDELS = 1, CW_SW_STOP = 2, CW_SW_IS_REF = 3 
 #define CW_SW_DIR_BYTES (1u << 20) /* banded traceback scratch per wave: the re-assembly's */
 int cw_sw_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows /* [n_seqs * CW_SW_ROW] */, uint32_t flags, void* hip_stream);
 int cw_sw_run(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags);
+
+/* ---- the alignment itself: cw_sw_path_run ---------------------------------------------------------------------------------------------------------------
+ * `groups` and `rows` as for cw_sw_run; on top of the row, every pair's alignment path as BAM-style ops, `length << 4 | op`: 0 = M, 1 = I (a query base only),
+ * 2 = D (a reference base only); under CW_SW_PATH_EQX -- the only flag -- 7 ('=') and 8 ('X') replace 0.  Sequence s may write ops[ops_off[s] .. ops_off[s+1]);
+ * n_ops[s] is what it wrote.  Ops come in alignment order (begin to end), run-length encoded: no two neighbouring ops have the same code.  Whenever a path is
+ * reported, the lengths of its M (= and X) and I ops add up to the query span and those of its M and D ops to the reference span of the row.
+ * The row holds the five alignment numbers of cw_sw_run bit for bit; CW_SW_INS / CW_SW_DEL are always computed: the totals of the path's I and D ops.
+ * The path is the one ssw's banded traceback walks between the ends: the band starts at |reference span - query span| + 1 and doubles until the banded score
+ * reaches the alignment's (or the band passes both spans together); the walk runs back from the end cell and is closed as ssw closes it: it stops at query row 0,
+ * whose cell is one more M.
+ * Statuses (none of them but CW_SW_STOP an error; each a function of the pair alone, and of its slot for CW_SW_PATH_SLOT):
+ *   CW_SW_ALIGNED    the path is written, n_ops its length (0 when nothing aligns).
+ *   CW_SW_NO_PATH    a band of b over a reference span of R and a query span of Q bases needs min(2b + 1, R + 1) x Q direction bytes, one a cell -- and
+ *                    12 x min(2b + 3, R + 3) more, rounded up to 16, once those exceed 4096 (b > 169 and R > 338) -- in the wave's scratch of CW_SW_PATH_BYTES;
+ *                    the first band that does not fit ends the pair: the five numbers stand, ins = del = 0, n_ops = 0.
+ *   CW_SW_PATH_OPEN  the walk did not close at the begin cell (it left the band or the reference before query row 0, or reached that row at another column than
+ *                    the first): ins / del are what the walk counted until then, n_ops = 0 -- never a path that does not span the ends.
+ *   CW_SW_PATH_SLOT  the ops outgrow the caller's slot: the seven numbers stand, n_ops is the number needed, nothing is written to the slot.
+ *                    CW_SW_OPS_BOUND(query length, reference length) ops always do.
+ *   CW_SW_IS_REF, CW_SW_STOP and the rows of empty queries or references: as in cw_sw_run, n_ops = 0.
+ * CW_E_INVALID for any other flag, NULL arguments (rows, paths and its members) and more than cw_max_batch_windows(e) groups, before anything is launched.  The
+ * scratch plan is exact: the batch runs once.
+ * cw_sw_path_run_device: every pointer inside groups and paths, and rows, is a DEVICE pointer; asynchronous on `hip_stream` (NULL = the engine's own); CW_OK
+ * also when pairs stop.  cw_sw_path_run: host pointers, synchronous, ops_off ascending from any start; CW_E_CAPACITY only when a row has CW_SW_STOP.
+ * Such runs alternate freely with window, POA and cw_sw_run runs on one engine.  cw_last_timings names the stages sw_order, sw_path (queries of up to 640
+ * bases), sw_path_wide (up to 2 048), sw_path_long (beyond). */
+typedef struct cw_sw_paths {
+    uint32_t* ops;            /* BAM-style: length << 4 | op */
+    const uint64_t* ops_off;  /* [n_seqs + 1]: sequence s may write ops[ops_off[s] .. ops_off[s+1]) */
+    uint32_t* n_ops;          /* [n_seqs] */
+} cw_sw_paths;
+enum { CW_SW_NO_PATH = 4, CW_SW_PATH_OPEN = 5, CW_SW_PATH_SLOT = 6 }; /* row statuses only these entry points write */
+enum { CW_SW_OP_M = 0, CW_SW_OP_I = 1, CW_SW_OP_D = 2, CW_SW_OP_EQ = 7, CW_SW_OP_X = 8 };
+#define CW_SW_PATH_EQX 4u
+#define CW_SW_OPS_BOUND(query_len, ref_len) ((query_len) + (ref_len))  /* every run consumes a base of one of them */
+#define CW_SW_PATH_BYTES (2u << 20)   /* direction bytes per wave of the path run */
+int cw_sw_path_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream);
+int cw_sw_path_run(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags);
 
 /* 1 when everything the last cw_run_device on this engine launched has completed (or nothing was launched yet), 0 while it is
  * still running, 2 while it is running but past the part that fills the GPU (what is left is the tail: a few long alignment tasks on

@@ -166,7 +166,8 @@
  *   begin = the same search on the reversed prefixes, scanning the reference backwards from the end column and stopping
  *           at the first column whose running maximum reaches the forward score;
  *   cigar = banded traceback between begin and end (band |ref_len - query_len| + 1, doubled until the score is reached),
- *           only its inserted/deleted base totals are used (correctionAlignment.cpp:28-45,111).
+ *           only its inserted/deleted base totals are used (correctionAlignment.cpp:28-45,111); cw_sw_path_run returns the
+ *           walk itself, closed as the library closes it: it stops at query row 0, whose cell is one more M.
  * str2num on the mixed-case overlap strings (correctionAlignment.cpp:9): every character other than 'A','C','G' counts as T.
  * PARITY UNPINNED (library absent).                                                                                     */
 /* The gap model of the POA.  LINEAR: a gap of length L costs L * CW_POA_GAP (the default: what the three-score engine call of the spoa that BMEAN

@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
-"""Time the alignment operator alone (cw_sw_run_device, include/consent_amd.h): pairs/s and DP cells/s per shape, with and without the indel totals, with
-cw_last_timings' stages.
+"""Time the alignment operator alone (cw_sw_run_device, include/consent_amd.h): pairs/s and DP cells/s per shape, with and without the indel totals -- and with
+--path through cw_sw_path_run_device, which returns the alignment's ops -- with cw_last_timings' stages.
 
 Input is synthetic: a group is one random reference and `--per-group` queries; a query is a stretch of its reference with 8 % substitutions and one deletion
 of four bases (so the banded traceback starts at a band of 5) -- or, where the query is the longer one, the whole reference treated that way between random
-flanks.  The batch lives in device memory; a step is one cw_sw_run_device and a wait for it.  DP cells of a pair are query length x reference length: the
-forward sweep's; the reverse sweep and the traceback come on top and are not counted, for any implementation.
+flanks.  The shape 1540x1540 is another construction, tests/sw_op_probes.py planted(40): reference P + G1 + M + S, query P + M + G2 + S with random 500-base
+P, M, S and unrelated 40-base G1, G2 -- the traceback's band starts at 1 and doubles to 64 (129 cells a row).
 
-    python tools/sw_bench.py                              # the five shapes (query x reference), each with and without indel totals
+The batch lives in device memory; a step is one cw_sw_run_device (or cw_sw_path_run_device) and a wait for it.  DP cells of a pair are query length x
+reference length: the forward sweep's; the reverse sweep and the traceback come on top and are not counted, for any implementation.
+
+    python tools/sw_bench.py                              # the six shapes (query x reference), each with and without indel totals
     python tools/sw_bench.py --shape 500x600 --pairs 65536 --steps 10
+    python tools/sw_bench.py --path                       # a third measurement per shape: the path run
     python tools/sw_bench.py --oracle 4096                # also: so many 500 x 600 pairs through the oracle's cwo_ssw on --threads CPU threads
 
-Prints one JSON line per measurement and a markdown table (DESIGN.md section 4.8 holds the first one).
+Prints one JSON line per measurement and a markdown table (DESIGN.md section 4.8 holds the first one, from a --path run).
 """
 import argparse
 import ctypes as C
@@ -27,9 +31,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import consent_amd as ca  # noqa: E402
-from consent_amd.engine import Batch, HostBatch  # noqa: E402
+from consent_amd.engine import Batch, HostBatch, SwPaths  # noqa: E402
 
-SHAPES = {"24x150": 262144, "100x600": 131072, "500x600": 65536, "2000x2048": 4096, "8000x2048": 512}  # query x reference -> pairs of the default run
+SHAPES = {"24x150": 262144, "100x600": 131072, "500x600": 65536, "2000x2048": 4096, "8000x2048": 512, "1540x1540": 2048}  # query x reference -> pairs of the default run
+PLANTED = {"1540x1540": (500, 40)}  # shapes built as planted pairs: (part, g)
+PATH = "path"  # the third mode beside flags 0 and CW_SW_WANT_INDELS
 
 
 def pack(codes):
@@ -67,11 +73,25 @@ def make_groups(n_pairs, qlen, rlen, per_group, seed):
     return HostBatch(np.arange(G + 1, dtype=np.uint32) * per, lens, offs, bases), refs, queries
 
 
+def make_planted(n_pairs, part, g, seed):
+    """HostBatch of n_pairs groups of one planted pair each (tests/sw_op_probes.py planted): reference P + G1 + M + S, query P + M + G2 + S."""
+    rng = np.random.default_rng(seed)
+    P, M, S = (rng.integers(0, 4, (n_pairs, part), dtype=np.uint8) for _ in range(3))
+    G1, G2 = (rng.integers(0, 4, (n_pairs, g), dtype=np.uint8) for _ in range(2))
+    rw, qw = pack(np.concatenate([P, G1, M, S], axis=1)), pack(np.concatenate([P, M, G2, S], axis=1))
+    L, W = 3 * part + g, rw.shape[1]
+    bases = np.stack([rw, qw], axis=1).reshape(-1)
+    return HostBatch(np.arange(n_pairs + 1, dtype=np.uint32) * 2, np.full(2 * n_pairs, L, np.uint32), np.arange(2 * n_pairs, dtype=np.uint64) * W, bases)
+
+
 def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
     import torch
 
     qlen, rlen = (int(v) for v in shape.split("x"))
-    hb, _, _ = make_groups(n_pairs, qlen, rlen, per_group, seed)
+    if shape in PLANTED:
+        hb = make_planted(n_pairs, *PLANTED[shape], seed)
+    else:
+        hb, _, _ = make_groups(n_pairs, qlen, rlen, per_group, seed)
     n_pairs = len(hb.seq_len) - hb.n_windows
     dev = torch.device("cuda", eng.device)
 
@@ -81,11 +101,20 @@ def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
     t_in = (up(hb.win_first_seq, np.int32), up(hb.seq_len, np.int32), up(hb.seq_word_off, np.int64), up(np.concatenate([hb.bases, np.zeros(4, np.uint32)]), np.int32))
     t_rows = torch.zeros(len(hb.seq_len) * 8, dtype=torch.int32, device=dev)
     b = Batch(hb.n_windows, len(hb.seq_len), len(hb.bases), t_in[0].data_ptr(), t_in[1].data_ptr(), t_in[2].data_ptr(), t_in[3].data_ptr())
+    if flags == PATH:  # the slots: CW_SW_OPS_BOUND of every sequence and its reference
+        wfs, lens = hb.win_first_seq.astype(np.int64), hb.seq_len.astype(np.int64)
+        off = np.concatenate([[0], np.cumsum(lens + lens[np.repeat(wfs[:-1], np.diff(wfs))])]).astype(np.uint64)
+        t_off, t_nops = up(off, np.int64), torch.zeros(len(hb.seq_len), dtype=torch.int32, device=dev)
+        t_ops = torch.zeros(int(off[-1]) + 1, dtype=torch.int32, device=dev)
+        paths = SwPaths(t_ops.data_ptr(), t_off.data_ptr(), t_nops.data_ptr())
     torch.cuda.synchronize(dev)
     times, stages = [], {}
     for step in range(warmup + steps):
         t0 = time.perf_counter()
-        eng.sw_device(b, C.c_void_p(t_rows.data_ptr()), flags)
+        if flags == PATH:
+            eng.sw_path_device(b, C.c_void_p(t_rows.data_ptr()), paths, 0)
+        else:
+            eng.sw_device(b, C.c_void_p(t_rows.data_ptr()), flags)
         torch.cuda.synchronize(dev)
         if step >= warmup:
             times.append((time.perf_counter() - t0) * 1e3)
@@ -94,7 +123,12 @@ def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
     rows = t_rows.cpu().numpy().reshape(-1, 8)
     q = rows[rows[:, 7] != ca.SW_IS_REF]
     ms = float(np.median(times))
-    return {"shape": shape, "pairs": n_pairs, "indels": bool(flags), "steps": steps, "ms_per_batch": round(ms, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
+    extra = {}
+    if flags == PATH:
+        nops = t_nops.cpu().numpy()
+        extra = {"mean_ops": round(float(nops[rows[:, 7] != ca.SW_IS_REF].mean()), 1), "no_path_rows": int((q[:, 7] == ca.SW_NO_PATH).sum()),
+                 "open_rows": int((q[:, 7] == ca.SW_PATH_OPEN).sum()), "mean_indels": round(float(q[:, 5:7].sum(axis=1).mean()), 1)}
+    return {"shape": shape, "pairs": n_pairs, "indels": flags if flags == PATH else bool(flags), "steps": steps, **extra, "ms_per_batch": round(ms, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
             "pairs_per_s": round(n_pairs / ms * 1e3), "dp_cells_per_s": float(f"{n_pairs * qlen * rlen / ms * 1e3:.4g}"), "mean_score": round(float(q[:, 0].mean()), 1),
             "no_indels_rows": int((q[:, 7] == ca.SW_NO_INDELS).sum()), "stopped_rows": int((q[:, 7] == ca.SW_STOP).sum()),
             "stage_ms": {k: round(float(np.median(v)), 3) for k, v in stages.items()}}
@@ -132,6 +166,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0x5A11)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--path", action="store_true", help="also time the path run (cw_sw_path_run_device) on every shape")
     ap.add_argument("--oracle", type=int, default=0, help="also time so many 500x600 pairs through the oracle on --threads CPU threads")
     ap.add_argument("--threads", type=int, default=16)
     a = ap.parse_args()
@@ -139,7 +174,7 @@ def main():
     rows = []
     try:
         for shape in a.shape or list(SHAPES):
-            for flags in (0, ca.SW_WANT_INDELS):
+            for flags in (0, ca.SW_WANT_INDELS) + ((PATH,) if a.path else ()):
                 rows.append(bench_shape(eng, shape, a.pairs or SHAPES.get(shape, 16384), a.per_group, flags, a.steps, a.warmup, a.seed))
                 print(json.dumps(rows[-1]), flush=True)
     finally:
@@ -147,11 +182,13 @@ def main():
     if a.oracle:
         print(json.dumps(oracle_rate(a.oracle, a.threads, a.seed)), flush=True)
     order = ["sw_order", "sw_align", "sw_align_wide", "sw_align_long", "total"]
+    stage_of = {"sw_align": "sw_path", "sw_align_wide": "sw_path_wide", "sw_align_long": "sw_path_long"}  # a path run's stages, in the same columns
     print("\n| query x reference | indel totals | pairs | ms / batch | pairs/s | DP cells/s | " + " | ".join(order) + " |")
     print("|---|---|---|---|---|---|" + "---|" * len(order))
     for r in rows:
-        print(f"| {r['shape']} | {'yes' if r['indels'] else 'no'} | {r['pairs']} | {r['ms_per_batch']:.2f} | {r['pairs_per_s']:.3g} | {r['dp_cells_per_s']:.3g} | "
-              + " | ".join(f"{r['stage_ms'].get(k, 0):.2f}" for k in order) + " |")
+        path = r["indels"] == PATH
+        print(f"| {r['shape']} | {'path' if path else 'yes' if r['indels'] else 'no'} | {r['pairs']} | {r['ms_per_batch']:.2f} ({r['ms_min']:.2f} - {r['ms_max']:.2f}) | {r['pairs_per_s']:.3g} | {r['dp_cells_per_s']:.3g} | "
+              + " | ".join(f"{r['stage_ms'].get(stage_of.get(k, k) if path else k, 0):.2f}" for k in order) + " |")
 
 
 if __name__ == "__main__":
