@@ -5,7 +5,7 @@
  * and the inspection entry points; the launchers of the path's neighbours (pile extraction, result planning, read re-assembly); host batches (cw_submit /
  * cw_wait) and the loop that runs a batch again with a larger plan (cw_run, cw_run_device_sync); the POA stage alone on a batch of groups (cw_poa_run_device,
  * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run); the re-assembly's local aligner alone on a batch of groups
- * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h).
+ * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h; cw_pileup_run_device, cw_pileup_run: cw_pileup.h).
  * The scratch plan is cw_plan.h (host arithmetic only); the host feeders, cw_window_positions among them, are cw_hostio.cpp.
  */
 #include "cw_internal.h"
@@ -23,12 +23,14 @@
 #include "cw_poa_op.h"
 #include "cw_sw_op.h"
 #include "cw_sw_path.h"
+#include "cw_pileup.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -114,7 +116,8 @@ int set_kernel_attributes(const hipDeviceProp_t& prop) {
         allow((const void*)cw_finish_kernel<CW_FIN_CB, CW_FIN_WAVES, false>, kLdsFinish) && allow((const void*)cw_finish_kernel<CW_FIN_CB_BIG, 1, true>, kLdsFinishBig) &&
         allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES>, lds_st) &&
         allow((const void*)cw_sw_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_kernel<1>, lds_sw(1)) &&
-        allow((const void*)cw_sw_path_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_path_kernel<1>, lds_sw(1));
+        allow((const void*)cw_sw_path_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_path_kernel<1>, lds_sw(1)) &&
+        allow((const void*)cw_pileup_kernel<0>, lds_sw(0)) && allow((const void*)cw_pileup_kernel<1>, lds_sw(1));
     return ok ? CW_OK : CW_E_NO_DEVICE;
 }
 
@@ -539,6 +542,57 @@ int run_sw_path_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, cons
     return CW_OK;
 }
 
+/* what cw_pileup_run and cw_pileup_run_device refuse, as validate_sw_path */
+int validate_pileup(const cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_pileup* pile, uint32_t flags) {
+    if (!e || !groups || !pile || (flags & ~CW_PILE_ACCUMULATE)) return CW_E_INVALID;
+    if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
+    if (!rows || !pile->counts || !pile->col_off) return CW_E_INVALID;
+    if (groups->n_windows == 0 || groups->n_seqs == 0) return groups->n_seqs == 0 ? CW_OK : CW_E_INVALID;
+    if (!groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
+    return CW_OK;
+}
+
+/* the body of cw_pileup_run_device, in the shape of run_sw_path_locked: sw_order, pile_clear unless the run accumulates, then pile, pile_wide, pile_long one
+   after the other on st; the plan is plan_sw_path's -- there is no op memory to add -- and lives in the engine's one scratch allocation. */
+int run_pileup_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream) {
+    int rc = validate_pileup(e, groups, rows, pile, flags);
+    if (rc || groups->n_seqs == 0) return rc;
+    if ((uintptr_t)pile->counts & 15u) return CW_E_INVALID; /* the clearing stores 16 bytes at a time */
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    const uint32_t S = groups->n_seqs;
+    const SwPathPlan p = plan_sw_path(groups->n_windows, S, groups->n_words, e->cus);
+    if ((rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) != CW_OK) return rc;
+    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (run_sw_locked) */
+    uint8_t* base = (uint8_t*)e->scratch;
+    PileArgs pa;
+    SwArgs& a = pa.a;
+    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.n_seqs = S; a.rows = rows; a.flags = flags;
+    a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
+    a.dir = (int8_t*)(base + p.dir); a.dir_bytes = p.dir_bytes;
+    a.gref = base + p.gref; a.lstate = base + p.lstate;
+    pa.counts = pile->counts; pa.col_off = pile->col_off; pa.steps = base + p.steps;
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_SW_CTR_WORDS * 4, st));
+    const uint32_t og = (S + 255u) / 256u;
+    stage(e, st, "sw_order", [&] {
+        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 0);
+        cw_sw_order_kernel<<<1, 256, 0, st>>>(a, 1);
+        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 2);
+    });
+    if (!(flags & CW_PILE_ACCUMULATE)) stage(e, st, "pile_clear", [&] { cw_pileup_clear_kernel<<<groups->n_windows, 256, 0, st>>>(pa); });
+    stage(e, st, "pile", [&] { cw_pileup_kernel<0><<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(pa); });
+    stage(e, st, "pile_wide", [&] { cw_pileup_kernel<1><<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(pa); });
+    stage(e, st, "pile_long", [&] { cw_pileup_long_kernel<<<p.wgs_long, 64, 0, st>>>(pa); });
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -792,6 +846,78 @@ int cw_sw_path_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_p
         if (status == CW_SW_ALIGNED && paths->n_ops[s] && paths->n_ops[s] <= poff[s + 1] - poff[s])
             memcpy(paths->ops + paths->ops_off[s], back.data() + poff[s], (size_t)paths->n_ops[s] * 4);
     }
+    return rc;
+}
+
+int cw_pileup_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_pileup_locked(e, groups, rows, pile, flags, hip_stream);
+}
+
+/* Host buffers in, host buffers out, synchronous, as cw_sw_path_run: the batch and the slots' offsets go up -- the caller's counts too, but only under
+   CW_PILE_ACCUMULATE -- cw_pileup_run_device on the engine's stream, the rows come back, and of the counts what a run owns: columns 0 .. ref_len - 1 of every
+   reference whose slot holds them.  A slot's words beyond those, a slot that is too short and every query's slot stay the caller's. */
+int cw_pileup_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileup* pile, uint32_t flags) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = validate_pileup(e, b, rows, pile, flags);
+    if (rc || b->n_seqs == 0) return rc;
+    const uint32_t G = b->n_windows, S = b->n_seqs;
+    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
+    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
+    for (uint32_t s = 0; s < S; ++s) {
+        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
+        if (pile->col_off[s + 1] < pile->col_off[s]) return CW_E_INVALID;
+    }
+    const uint64_t c0 = pile->col_off[0], n_cols = pile->col_off[S] - c0; /* the device copy begins at the first slot */
+    const size_t col_bytes = (size_t)CW_PILE_COL * 4;
+    size_t o = 0;
+    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
+                 i_coff = put((size_t)(S + 1) * 8);
+    const size_t in_bytes = o;
+    o = 0;
+    const size_t o_rows = put((size_t)S * CW_SW_ROW * 4), o_counts = put((size_t)n_cols * col_bytes);
+    const size_t out_bytes = o;
+    std::vector<uint64_t> coff;
+    std::vector<uint32_t> back;
+    try { coff.resize((size_t)S + 1); back.resize((size_t)n_cols * CW_PILE_COL); } catch (...) { return CW_E_NOMEM; }
+    for (uint32_t s = 0; s <= S; ++s) coff[s] = pile->col_off[s] - c0;
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    uint8_t *din = (uint8_t*)e->poa_in, *dout = (uint8_t*)e->poa_out;
+    hipStream_t st = e->stream;
+    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_coff, coff.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
+    /* the references whose columns the run owns: (sequence, columns) */
+    std::vector<std::pair<uint32_t, uint32_t>> owned;
+    try {
+        for (uint32_t g = 0; g < G; ++g) {
+            const uint32_t r = b->win_first_seq[g];
+            if (r < b->win_first_seq[g + 1] && b->seq_len[r] && coff[r + 1] - coff[r] >= b->seq_len[r]) owned.emplace_back(r, b->seq_len[r]);
+        }
+    } catch (...) { return CW_E_NOMEM; }
+    uint32_t* const dcounts = (uint32_t*)(dout + o_counts);
+    if ((flags & CW_PILE_ACCUMULATE) && n_cols) /* every slot in one copy; the run reads and writes the owned columns only */
+        CW_HIP(hipMemcpyAsync(dcounts, pile->counts + c0 * CW_PILE_COL, (size_t)n_cols * col_bytes, hipMemcpyHostToDevice, st));
+    cw_batch db = *b;
+    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
+    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
+    cw_pileup dp;
+    dp.counts = dcounts; dp.col_off = (const uint64_t*)(din + i_coff);
+    if ((rc = run_pileup_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st)) != CW_OK) return rc;
+    CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
+    if (n_cols) CW_HIP(hipMemcpyAsync(back.data(), dcounts, (size_t)n_cols * col_bytes, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    for (const auto& rn : owned)
+        memcpy(pile->counts + pile->col_off[rn.first] * CW_PILE_COL, back.data() + coff[rn.first] * CW_PILE_COL, (size_t)rn.second * col_bytes);
+    for (uint32_t s = 0; s < S; ++s)
+        if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) rc = CW_E_CAPACITY;
     return rc;
 }
 

@@ -20,6 +20,10 @@ SW_PATH_EQX = 4
 SW_OP_M, SW_OP_I, SW_OP_D, SW_OP_EQ, SW_OP_X = 0, 1, 2, 7, 8
 SW_PATH_BYTES = 2 << 20
 SW_OP_LETTERS = {SW_OP_M: "M", SW_OP_I: "I", SW_OP_D: "D", SW_OP_EQ: "=", SW_OP_X: "X"}
+# cw_pileup_run: the status only it writes, its flag, the words of a column
+SW_PILE_SLOT = 7
+PILE_ACCUMULATE = 8
+PILE_A, PILE_C, PILE_G, PILE_T, PILE_DEL, PILE_INS, PILE_BEGIN, PILE_END, PILE_COL = 0, 1, 2, 3, 4, 5, 6, 7, 8
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -54,6 +58,12 @@ class SwPaths(C.Structure):
     """cw_sw_paths: the op slots of cw_sw_path_run."""
 
     _fields_ = [("ops", C.c_void_p), ("ops_off", C.c_void_p), ("n_ops", C.c_void_p)]
+
+
+class Pileup(C.Structure):
+    """cw_pileup: the column slots of cw_pileup_run."""
+
+    _fields_ = [("counts", C.c_void_p), ("col_off", C.c_void_p)]
 
 
 class Result(C.Structure):
@@ -158,6 +168,9 @@ def _load(p):
         lib.cw_sw_path_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwPaths), C.c_uint32]
         lib.cw_sw_path_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwPaths), C.c_uint32, C.c_void_p]
         lib.cw_debug_sw_path_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p]
+    if hasattr(lib, "cw_pileup_run"):
+        lib.cw_pileup_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(Pileup), C.c_uint32]
+        lib.cw_pileup_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(Pileup), C.c_uint32, C.c_void_p]
     lib.cw_submit.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.POINTER(C.c_int)]
     lib.cw_wait.argtypes = [C.c_void_p, C.c_int]
     lib.cw_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -536,6 +549,28 @@ class SwPathRows(SwRows):
         return "".join(f"{n}{SW_OP_LETTERS[op]}" for n, op in self.ops(group, member))
 
 
+class PileupRows(SwRows):
+    """What Engine.pileup returns: SwRows, and the columns: counts_buf is an (n_columns, PILE_COL) uint32 array in which sequence s, where it is its group's
+    reference, owns rows col_off[s] : col_off[s + 1] -- Engine.pileup gives every reference as many columns as it has bases and a query none, so counts_buf
+    is the groups' references one after the other whatever their queries, and the counts_buf of one run can be the `into` of another over the same references."""
+
+    def __init__(self, rows, win_first_seq, rc, counts_buf, col_off, seq_len):
+        super().__init__(rows, win_first_seq, rc)
+        self.counts_buf, self.col_off, self.seq_len = counts_buf, col_off, seq_len
+
+    def counts(self, group):
+        """The (ref_len, PILE_COL) counts of the group's reference: columns PILE_A .. PILE_END (empty for a group of none, or when the slot is too short)."""
+        r = int(self.win_first_seq[group])
+        if r >= int(self.win_first_seq[group + 1]):
+            return self.counts_buf[:0]
+        o, n = int(self.col_off[r]), int(self.seq_len[r])
+        return self.counts_buf[o : o + n] if int(self.col_off[r + 1]) - o >= n else self.counts_buf[:0]
+
+    def coverage(self, group):
+        """Per column of the group's reference the number of counted alignments that cover it: A + C + G + T + DEL."""
+        return self.counts(group)[:, : PILE_DEL + 1].sum(axis=1, dtype=np.int64)
+
+
 def _result_struct(r):
     return Result(
         _ptr(r.cons), _ptr(r.cons_off), _ptr(r.cons_len), _ptr(r.status),
@@ -647,6 +682,50 @@ class Engine:
         """cw_sw_path_run_device: device pointers in the batch struct and in `paths_struct` (SwPaths), `rows_ptr` a device array of n_seqs * SW_ROW int32;
         asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_sw_path_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(paths_struct), flags, stream), "cw_sw_path_run_device")
+
+    def pileup(self, groups, into=None):
+        """The local alignments counted into their reference's columns (cw_pileup_run): `groups` as for sw().  Returns PileupRows: the rows of sw_path() --
+        status SW_PILE_SLOT never occurs with the slots made here -- .counts(group), an (ref_len, PILE_COL) array of how many queries put an A, C, G, T on the
+        column, skip it, insert after it, begin and end on it, and .coverage(group).  into: a PileupRows of an earlier call over the same references, or its
+        counts_buf; the run then adds to those counts (PILE_ACCUMULATE) instead of beginning at zero -- for a reference whose queries are split over calls."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        S = len(batch.seq_len)
+        wfs = np.asarray(batch.win_first_seq, np.int64)
+        lens = np.asarray(batch.seq_len, np.int64)
+        width = np.zeros(S, np.int64)
+        refs = wfs[:-1][np.diff(wfs) > 0]
+        width[refs] = lens[refs]
+        col_off = np.zeros(S + 1, np.uint64)
+        col_off[1:] = np.cumsum(width)
+        n_cols = int(col_off[-1])
+        if into is None:
+            counts = np.zeros((max(n_cols, 1), PILE_COL), np.uint32)
+        else:
+            counts = into.counts_buf if isinstance(into, PileupRows) else into
+            if counts.dtype != np.uint32 or not counts.flags.c_contiguous or counts.shape != (max(n_cols, 1), PILE_COL):
+                raise EngineError(f"pileup: `into` must be a C-contiguous uint32 array of shape {(max(n_cols, 1), PILE_COL)}: the columns of these references")
+        rows = np.zeros((S, SW_ROW), np.int32)
+        b = batch.c_struct()
+        pile = Pileup(_ptr(counts), _ptr(col_off))
+        rc = _check(self.lib, self.lib.cw_pileup_run(self.handle, C.byref(b), _ptr(rows), C.byref(pile), 0 if into is None else PILE_ACCUMULATE), "cw_pileup_run", allow_capacity=True)
+        return PileupRows(rows, batch.win_first_seq, rc, counts, col_off, batch.seq_len)
+
+    def pileup_device(self, batch_struct, rows_ptr, pile_struct, flags=0, stream=None):
+        """cw_pileup_run_device: device pointers in the batch struct and in `pile_struct` (Pileup; counts 16-byte aligned), `rows_ptr` a device array of
+        n_seqs * SW_ROW int32; flags 0 or PILE_ACCUMULATE; asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_pileup_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(pile_struct), flags, stream), "cw_pileup_run_device")
+
+    def poa_support(self, groups):
+        """The support behind every consensus base: poa(groups), then every group's members piled against that group's consensus (packed on the host; two
+        calls).  Returns (WindowResults of poa(), PileupRows): .counts(g)[j] are the counts on base j of consensus(g); member k of group g is member k + 1 of
+        the pileup's group g.  A group without a consensus has no columns."""
+        piles = groups.pile if isinstance(groups, HostBatch) else (lambda g: groups[g])
+        n_groups = groups.n_windows if isinstance(groups, HostBatch) else len(groups)
+        res = self.poa(groups)
+        against = []
+        for g in range(n_groups):
+            against.append([res.consensus(g)] + list(piles(g)))
+        return res, self.pileup(against)
 
     def extract_piles(self, reads, overlaps, jobs, k):
         """Device-side getAlignmentWindowsSequences (cw_extract_piles_device).  `reads` is a HostBatch-like packing of the read

@@ -14,6 +14,8 @@
  *   cw_sw_run / cw_sw_run_device <- StripedSmithWaterman::Aligner::Align as alignConsensus calls it (correctionAlignment.cpp:90, :110), batched over
  *                               (query, reference) pairs: the local aligner of cw_stitch_device on its own.
  *   cw_sw_path_run / cw_sw_path_run_device <- the same pairs with the alignment itself (ssw's banded traceback, its cigar) as run-length encoded ops.
+ *   cw_pileup_run / cw_pileup_run_device <- the same pairs again, their paths counted into the reference's columns on the device (no counterpart: what a caller
+ *                               of the above would do with every pair's cigar).
  *   cw_window_positions      <- getAlignmentWindowsPositions (alignmentWindows.cpp:27-85), host
  *   cw_extract_piles_device  <- getAlignmentWindowsSequences (alignmentWindows.cpp:87-149) evaluated on the device
  *   cw_stitch_device         <- alignConsensus + trimRead + dropRead (correctionAlignment.cpp:47-140, utils.cpp:96-128, :71-73)
@@ -263,6 +265,47 @@ enum { CW_SW_OP_M = 0, CW_SW_OP_I = 1, CW_SW_OP_D = 2, CW_SW_OP_EQ = 7, CW_SW_OP
 #define CW_SW_PATH_BYTES (2u << 20)   /* direction bytes per wave of the path run */
 int cw_sw_path_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream);
 int cw_sw_path_run(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags);
+
+/* ---- what the alignments say about the reference: cw_pileup_run ---------------------------------------------------------------------------------------------
+ * `groups` and `rows` as for cw_sw_path_run; in place of every pair's ops, CW_PILE_COL counts per reference column, summed over the group's queries on the
+ * device: how many queries put an A, C, G or T on the column, how many skip it, how many insert something after it, how many alignments begin and end on it.
+ * The layout is per SEQUENCE, as ops_off is: sequence s, where it is its group's reference, owns columns col_off[s] .. col_off[s+1]; column j of reference r
+ * -- j counts the whole reference from 0, not the aligned span -- is the CW_PILE_COL words at counts[(col_off[r] + j) * CW_PILE_COL].  A query's own slot is never
+ * read or written and may be empty.
+ * Which pairs count: those cw_sw_path_run reports CW_SW_ALIGNED with a positive score -- the pairs with a closed path.  Walking such a path in alignment order,
+ * i the query index and j the reference column, both absolute:
+ *   an M step                   counts[j][code of query base i] += 1 (codes 0..3 as packed: CW_PILE_A .. CW_PILE_T; a non-ACGT letter packs as T, as everywhere)
+ *   a D step                    counts[j][CW_PILE_DEL] += 1
+ *   the first step of an I run  counts[j - 1][CW_PILE_INS] += 1, j - 1 the last reference column consumed before the run: the column counts insertion events,
+ *                               not inserted bases (a path never begins with an insertion -- the walk closes with an M -- so j - 1 >= ref_begin)
+ *   once per pair               counts[ref_begin][CW_PILE_BEGIN] += 1 and counts[ref_end][CW_PILE_END] += 1
+ * so that per column A + C + G + T + DEL is the number of counted alignments that cover it.  The counts are integer sums: they depend on no batch
+ * composition, order or run.
+ * Clearing: without CW_PILE_ACCUMULATE -- the only flag -- the run first zeroes columns 0 .. ref_len - 1 of every reference whose slot holds them; nothing
+ * beyond ref_len in a slot is touched, and nothing in a query's slot.  Under the flag nothing is cleared and the run adds to what is there: a reference whose
+ * queries do not fit one call can be split over calls.
+ * The row: the five alignment numbers and ins / del are cw_sw_path_run's, bit for bit.  Statuses: CW_SW_ALIGNED, CW_SW_NO_PATH, CW_SW_PATH_OPEN, CW_SW_IS_REF and
+ * CW_SW_STOP as there -- all but a positive-score CW_SW_ALIGNED count nothing -- and
+ *   CW_SW_PILE_SLOT  the reference's slot (col_off[r+1] - col_off[r]) is shorter than the reference: every pair of that group that would have counted
+ *                    keeps its seven numbers and has this status; nothing of that slot is cleared or counted; other groups are unaffected.
+ * There are no op slots: CW_SW_PATH_SLOT does not occur.
+ * CW_E_INVALID, before anything is launched: any flag other than CW_PILE_ACCUMULATE, NULL rows / pile / counts / col_off, more than cw_max_batch_windows(e)
+ * groups.  The scratch plan is cw_sw_path_run's without op memory, exact: the batch runs once.
+ * cw_pileup_run_device: every pointer inside groups and pile, and rows, is a DEVICE pointer, counts 16-byte aligned (CW_E_INVALID otherwise); asynchronous on
+ * `hip_stream` (NULL = the engine's own); CW_OK also when pairs stop.  cw_pileup_run: host pointers, synchronous, col_off ascending from any start, no
+ * alignment asked of counts; the caller's counts go up only under the flag, and of the slots only columns 0 .. ref_len - 1 of the references that hold them
+ * come back; CW_E_CAPACITY only when a row has CW_SW_STOP.
+ * Such runs alternate freely with every other kind of run on one engine.  cw_last_timings names the stages sw_order, pile_clear (absent under the flag), pile
+ * (queries of up to 640 bases), pile_wide (up to 2 048), pile_long (beyond). */
+enum { CW_PILE_A, CW_PILE_C, CW_PILE_G, CW_PILE_T, CW_PILE_DEL, CW_PILE_INS, CW_PILE_BEGIN, CW_PILE_END, CW_PILE_COL = 8 };
+typedef struct cw_pileup {
+    uint32_t* counts;         /* CW_PILE_COL uint32 per column */
+    const uint64_t* col_off;  /* [n_seqs + 1]: sequence s, where it is its group's reference, owns columns col_off[s] .. col_off[s+1] */
+} cw_pileup;
+enum { CW_SW_PILE_SLOT = 7 };     /* row status only these entry points write */
+#define CW_PILE_ACCUMULATE 8u     /* the only flag */
+int cw_pileup_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream);
+int cw_pileup_run(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags);
 
 /* 1 when everything the last cw_run_device on this engine launched has completed (or nothing was launched yet), 0 while it is
  * still running, 2 while it is running but past the part that fills the GPU (what is left is the tail: a few long alignment tasks on

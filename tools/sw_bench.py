@@ -1,18 +1,22 @@
 #!/usr/bin/env python3
 """Time the alignment operator alone (cw_sw_run_device, include/consent_amd.h): pairs/s and DP cells/s per shape, with and without the indel totals -- and with
---path through cw_sw_path_run_device, which returns the alignment's ops -- with cw_last_timings' stages.
+--path through cw_sw_path_run_device, which returns the alignment's ops, with --pileup also through cw_pileup_run_device, which counts the paths into their
+reference's columns -- with cw_last_timings' stages.
 
 Input is synthetic: a group is one random reference and `--per-group` queries; a query is a stretch of its reference with 8 % substitutions and one deletion
 of four bases (so the banded traceback starts at a band of 5) -- or, where the query is the longer one, the whole reference treated that way between random
 flanks.  The shape 1540x1540 is another construction, tests/sw_op_probes.py planted(40): reference P + G1 + M + S, query P + M + G2 + S with random 500-base
 P, M, S and unrelated 40-base G1, G2 -- the traceback's band starts at 1 and doubles to 64 (129 cells a row).
 
-The batch lives in device memory; a step is one cw_sw_run_device (or cw_sw_path_run_device) and a wait for it.  DP cells of a pair are query length x
+The shape 500x600x30, which --pileup adds, is 500 x 600 with 30 queries on every reference instead of --per-group: deeper columns, more adds to the same words.
+
+The batch lives in device memory; a step is one cw_sw_run_device (or cw_sw_path_run_device, cw_pileup_run_device) and a wait for it.  DP cells of a pair are query length x
 reference length: the forward sweep's; the reverse sweep and the traceback come on top and are not counted, for any implementation.
 
     python tools/sw_bench.py                              # the six shapes (query x reference), each with and without indel totals
     python tools/sw_bench.py --shape 500x600 --pairs 65536 --steps 10
     python tools/sw_bench.py --path                       # a third measurement per shape: the path run
+    python tools/sw_bench.py --pileup                     # a fourth beside it: the pileup run of the same batch, and the shape 500x600x30
     python tools/sw_bench.py --oracle 4096                # also: so many 500 x 600 pairs through the oracle's cwo_ssw on --threads CPU threads
 
 Prints one JSON line per measurement and a markdown table (DESIGN.md section 4.8 holds the first one, from a --path run).
@@ -31,11 +35,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import consent_amd as ca  # noqa: E402
-from consent_amd.engine import Batch, HostBatch, SwPaths  # noqa: E402
+from consent_amd.engine import Batch, HostBatch, Pileup, SwPaths  # noqa: E402
 
 SHAPES = {"24x150": 262144, "100x600": 131072, "500x600": 65536, "2000x2048": 4096, "8000x2048": 512, "1540x1540": 2048}  # query x reference -> pairs of the default run
 PLANTED = {"1540x1540": (500, 40)}  # shapes built as planted pairs: (part, g)
-PATH = "path"  # the third mode beside flags 0 and CW_SW_WANT_INDELS
+DEEP = {"500x600x30": 61440}  # query x reference x queries per reference: what --pileup adds
+PATH, PILE = "path", "pileup"  # the third and fourth mode beside flags 0 and CW_SW_WANT_INDELS
 
 
 def pack(codes):
@@ -87,7 +92,8 @@ def make_planted(n_pairs, part, g, seed):
 def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
     import torch
 
-    qlen, rlen = (int(v) for v in shape.split("x"))
+    qlen, rlen, *deep = (int(v) for v in shape.split("x"))
+    per_group = deep[0] if deep else per_group
     if shape in PLANTED:
         hb = make_planted(n_pairs, *PLANTED[shape], seed)
     else:
@@ -107,12 +113,21 @@ def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
         t_off, t_nops = up(off, np.int64), torch.zeros(len(hb.seq_len), dtype=torch.int32, device=dev)
         t_ops = torch.zeros(int(off[-1]) + 1, dtype=torch.int32, device=dev)
         paths = SwPaths(t_ops.data_ptr(), t_off.data_ptr(), t_nops.data_ptr())
+    if flags == PILE:  # the slots: a reference's columns, none for a query
+        wfs, lens = hb.win_first_seq.astype(np.int64), hb.seq_len.astype(np.int64)
+        width = np.zeros(len(lens), np.int64)
+        width[wfs[:-1]] = lens[wfs[:-1]]
+        off = np.concatenate([[0], np.cumsum(width)]).astype(np.uint64)
+        t_off, t_counts = up(off, np.int64), torch.zeros((int(off[-1]) + 1, ca.PILE_COL), dtype=torch.int32, device=dev)
+        pile = Pileup(t_counts.data_ptr(), t_off.data_ptr())
     torch.cuda.synchronize(dev)
     times, stages = [], {}
     for step in range(warmup + steps):
         t0 = time.perf_counter()
         if flags == PATH:
             eng.sw_path_device(b, C.c_void_p(t_rows.data_ptr()), paths, 0)
+        elif flags == PILE:
+            eng.pileup_device(b, C.c_void_p(t_rows.data_ptr()), pile, 0)
         else:
             eng.sw_device(b, C.c_void_p(t_rows.data_ptr()), flags)
         torch.cuda.synchronize(dev)
@@ -128,7 +143,13 @@ def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
         nops = t_nops.cpu().numpy()
         extra = {"mean_ops": round(float(nops[rows[:, 7] != ca.SW_IS_REF].mean()), 1), "no_path_rows": int((q[:, 7] == ca.SW_NO_PATH).sum()),
                  "open_rows": int((q[:, 7] == ca.SW_PATH_OPEN).sum()), "mean_indels": round(float(q[:, 5:7].sum(axis=1).mean()), 1)}
-    return {"shape": shape, "pairs": n_pairs, "indels": flags if flags == PATH else bool(flags), "steps": steps, **extra, "ms_per_batch": round(ms, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
+    if flags == PILE:
+        counts = t_counts.cpu().numpy()[:-1].astype(np.int64)
+        counted = int(((q[:, 7] == ca.SW_ALIGNED) & (q[:, 0] > 0)).sum())
+        assert int(counts[:, ca.PILE_BEGIN].sum()) == int(counts[:, ca.PILE_END].sum()) == counted and int(counts[:, ca.PILE_DEL].sum()) == int(q[:, 6].sum())
+        extra = {"counted_rows": counted, "columns": len(counts), "mean_depth": round(float(counts[:, : ca.PILE_DEL + 1].sum() / max(len(counts), 1)), 2),
+                 "no_path_rows": int((q[:, 7] == ca.SW_NO_PATH).sum()), "open_rows": int((q[:, 7] == ca.SW_PATH_OPEN).sum()), "mean_indels": round(float(q[:, 5:7].sum(axis=1).mean()), 1)}
+    return {"shape": shape, "pairs": n_pairs, "indels": flags if flags in (PATH, PILE) else bool(flags), "steps": steps, **extra, "ms_per_batch": round(ms, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
             "pairs_per_s": round(n_pairs / ms * 1e3), "dp_cells_per_s": float(f"{n_pairs * qlen * rlen / ms * 1e3:.4g}"), "mean_score": round(float(q[:, 0].mean()), 1),
             "no_indels_rows": int((q[:, 7] == ca.SW_NO_INDELS).sum()), "stopped_rows": int((q[:, 7] == ca.SW_STOP).sum()),
             "stage_ms": {k: round(float(np.median(v)), 3) for k, v in stages.items()}}
@@ -167,28 +188,30 @@ def main():
     ap.add_argument("--seed", type=int, default=0x5A11)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--path", action="store_true", help="also time the path run (cw_sw_path_run_device) on every shape")
+    ap.add_argument("--pileup", action="store_true", help="time the path run and the pileup run (cw_pileup_run_device) of the same batch on every shape, and on 500x600x30")
     ap.add_argument("--oracle", type=int, default=0, help="also time so many 500x600 pairs through the oracle on --threads CPU threads")
     ap.add_argument("--threads", type=int, default=16)
     a = ap.parse_args()
     eng = ca.Engine(ca.Params(9, 4, 8, 2, 150), device=a.device)
     rows = []
     try:
-        for shape in a.shape or list(SHAPES):
-            for flags in (0, ca.SW_WANT_INDELS) + ((PATH,) if a.path else ()):
-                rows.append(bench_shape(eng, shape, a.pairs or SHAPES.get(shape, 16384), a.per_group, flags, a.steps, a.warmup, a.seed))
+        for shape in a.shape or list(SHAPES) + (list(DEEP) if a.pileup else []):
+            for flags in (0, ca.SW_WANT_INDELS) + ((PATH,) if a.path or a.pileup else ()) + ((PILE,) if a.pileup else ()):
+                rows.append(bench_shape(eng, shape, a.pairs or SHAPES.get(shape) or DEEP.get(shape, 16384), a.per_group, flags, a.steps, a.warmup, a.seed))
                 print(json.dumps(rows[-1]), flush=True)
     finally:
         eng.close()
     if a.oracle:
         print(json.dumps(oracle_rate(a.oracle, a.threads, a.seed)), flush=True)
-    order = ["sw_order", "sw_align", "sw_align_wide", "sw_align_long", "total"]
-    stage_of = {"sw_align": "sw_path", "sw_align_wide": "sw_path_wide", "sw_align_long": "sw_path_long"}  # a path run's stages, in the same columns
+    order = ["sw_order", "sw_align", "sw_align_wide", "sw_align_long", "total"] + (["pile_clear"] if a.pileup else [])
+    # a path run's and a pileup run's stages, in the same columns
+    stage_of = {PATH: {"sw_align": "sw_path", "sw_align_wide": "sw_path_wide", "sw_align_long": "sw_path_long"}, PILE: {"sw_align": "pile", "sw_align_wide": "pile_wide", "sw_align_long": "pile_long"}}
     print("\n| query x reference | indel totals | pairs | ms / batch | pairs/s | DP cells/s | " + " | ".join(order) + " |")
     print("|---|---|---|---|---|---|" + "---|" * len(order))
     for r in rows:
-        path = r["indels"] == PATH
-        print(f"| {r['shape']} | {'path' if path else 'yes' if r['indels'] else 'no'} | {r['pairs']} | {r['ms_per_batch']:.2f} ({r['ms_min']:.2f} - {r['ms_max']:.2f}) | {r['pairs_per_s']:.3g} | {r['dp_cells_per_s']:.3g} | "
-              + " | ".join(f"{r['stage_ms'].get(stage_of.get(k, k) if path else k, 0):.2f}" for k in order) + " |")
+        names = stage_of.get(r["indels"], {})
+        print(f"| {r['shape']} | {r['indels'] if names else 'yes' if r['indels'] else 'no'} | {r['pairs']} | {r['ms_per_batch']:.2f} ({r['ms_min']:.2f} - {r['ms_max']:.2f}) | {r['pairs_per_s']:.3g} | {r['dp_cells_per_s']:.3g} | "
+              + " | ".join(f"{r['stage_ms'].get(names.get(k, k), 0):.2f}" for k in order) + " |")
 
 
 if __name__ == "__main__":
