@@ -5,7 +5,8 @@
  * and the inspection entry points; the launchers of the path's neighbours (pile extraction, result planning, read re-assembly); host batches (cw_submit /
  * cw_wait) and the loop that runs a batch again with a larger plan (cw_run, cw_run_device_sync); the POA stage alone on a batch of groups (cw_poa_run_device,
  * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run); the re-assembly's local aligner alone on a batch of groups
- * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h; cw_pileup_run_device, cw_pileup_run: cw_pileup.h).
+ * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h; cw_pileup_run_device, cw_pileup_run: cw_pileup.h; cw_sw_cut_run_device, cw_sw_cut_run,
+ * cw_cut_groups_device: cw_sw_cut.h).
  * The scratch plan is cw_plan.h (host arithmetic only); the host feeders, cw_window_positions among them, are cw_hostio.cpp.
  */
 #include "cw_internal.h"
@@ -24,6 +25,7 @@
 #include "cw_sw_op.h"
 #include "cw_sw_path.h"
 #include "cw_pileup.h"
+#include "cw_sw_cut.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -117,7 +119,8 @@ int set_kernel_attributes(const hipDeviceProp_t& prop) {
         allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES>, lds_st) &&
         allow((const void*)cw_sw_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_kernel<1>, lds_sw(1)) &&
         allow((const void*)cw_sw_path_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_path_kernel<1>, lds_sw(1)) &&
-        allow((const void*)cw_pileup_kernel<0>, lds_sw(0)) && allow((const void*)cw_pileup_kernel<1>, lds_sw(1));
+        allow((const void*)cw_pileup_kernel<0>, lds_sw(0)) && allow((const void*)cw_pileup_kernel<1>, lds_sw(1)) &&
+        allow((const void*)cw_sw_cut_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_cut_kernel<1>, lds_sw(1));
     return ok ? CW_OK : CW_E_NO_DEVICE;
 }
 
@@ -593,6 +596,56 @@ int run_pileup_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const
     return CW_OK;
 }
 
+/* what cw_sw_cut_run and cw_sw_cut_run_device refuse, as validate_pileup */
+int validate_sw_cut(const cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_sw_cuts* cuts) {
+    if (!e || !groups || !cuts) return CW_E_INVALID;
+    if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
+    if (!rows || !cuts->cuts || !cuts->cut_off || cuts->window == 0u) return CW_E_INVALID;
+    if (groups->n_windows == 0 || groups->n_seqs == 0) return groups->n_seqs == 0 ? CW_OK : CW_E_INVALID;
+    if (!groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
+    return CW_OK;
+}
+
+/* the body of cw_sw_cut_run_device, in the shape of run_pileup_locked: sw_order -- with it the zeros of the queries that are no pair -- then cut, cut_wide,
+   cut_long one after the other on st; the plan is plan_sw_path's and lives in the engine's one scratch allocation. */
+int run_sw_cut_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, void* hip_stream) {
+    int rc = validate_sw_cut(e, groups, rows, cuts);
+    if (rc || groups->n_seqs == 0) return rc;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    const uint32_t S = groups->n_seqs;
+    const SwPathPlan p = plan_sw_path(groups->n_windows, S, groups->n_words, e->cus);
+    if ((rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) != CW_OK) return rc;
+    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (run_sw_locked) */
+    uint8_t* base = (uint8_t*)e->scratch;
+    CutArgs ca;
+    SwArgs& a = ca.a;
+    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.n_seqs = S; a.rows = rows; a.flags = 0u;
+    a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
+    a.dir = (int8_t*)(base + p.dir); a.dir_bytes = p.dir_bytes;
+    a.gref = base + p.gref; a.lstate = base + p.lstate;
+    ca.cuts = cuts->cuts; ca.cut_off = cuts->cut_off; ca.window = cuts->window; ca.steps = base + p.steps;
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_SW_CTR_WORDS * 4, st));
+    const uint32_t og = (S + 255u) / 256u;
+    stage(e, st, "sw_order", [&] {
+        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 0);
+        cw_sw_order_kernel<<<1, 256, 0, st>>>(a, 1);
+        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 2);
+        cw_sw_cut_rest_kernel<<<og, 256, 0, st>>>(ca);
+    });
+    stage(e, st, "cut", [&] { cw_sw_cut_kernel<0><<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(ca); });
+    stage(e, st, "cut_wide", [&] { cw_sw_cut_kernel<1><<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(ca); });
+    stage(e, st, "cut_long", [&] { cw_sw_cut_long_kernel<<<p.wgs_long, 64, 0, st>>>(ca); });
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -919,6 +972,130 @@ int cw_pileup_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileu
     for (uint32_t s = 0; s < S; ++s)
         if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) rc = CW_E_CAPACITY;
     return rc;
+}
+
+int cw_sw_cut_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, void* hip_stream) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_sw_cut_locked(e, groups, rows, cuts, hip_stream);
+}
+
+/* Host buffers in, host buffers out, synchronous, as cw_pileup_run: the batch and the slots' offsets go up, cw_sw_cut_run_device on the engine's stream, the
+   rows come back, and of the slots what a run owns: the T + 1 words of every query whose slot holds them.  A slot's words beyond those, a slot that is too
+   short and every reference's slot stay the caller's. */
+int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cuts* cuts) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = validate_sw_cut(e, b, rows, cuts);
+    if (rc || b->n_seqs == 0) return rc;
+    const uint32_t G = b->n_windows, S = b->n_seqs, W = cuts->window;
+    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
+    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
+    for (uint32_t s = 0; s < S; ++s) {
+        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
+        if (cuts->cut_off[s + 1] < cuts->cut_off[s]) return CW_E_INVALID;
+    }
+    const uint64_t c0 = cuts->cut_off[0], n_slots = cuts->cut_off[S] - c0; /* the device copy begins at the first slot */
+    size_t o = 0;
+    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
+                 i_coff = put((size_t)(S + 1) * 8);
+    const size_t in_bytes = o;
+    o = 0;
+    const size_t o_rows = put((size_t)S * CW_SW_ROW * 4), o_cuts = put((size_t)n_slots * 4);
+    const size_t out_bytes = o;
+    std::vector<uint64_t> coff;
+    std::vector<uint32_t> back;
+    std::vector<std::pair<uint32_t, uint32_t>> owned; /* the queries whose words the run owns: (sequence, words) */
+    try {
+        coff.resize((size_t)S + 1); back.resize((size_t)n_slots);
+        for (uint32_t s = 0; s <= S; ++s) coff[s] = cuts->cut_off[s] - c0;
+        for (uint32_t g = 0; g < G; ++g) {
+            const uint32_t r = b->win_first_seq[g], end = b->win_first_seq[g + 1];
+            if (r >= end) continue;
+            const uint32_t words = CW_SW_CUTS(b->seq_len[r], W);
+            for (uint32_t s = r + 1; s < end; ++s) if (coff[s + 1] - coff[s] >= words) owned.emplace_back(s, words);
+        }
+    } catch (...) { return CW_E_NOMEM; }
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    uint8_t *din = (uint8_t*)e->poa_in, *dout = (uint8_t*)e->poa_out;
+    hipStream_t st = e->stream;
+    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_coff, coff.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
+    cw_batch db = *b;
+    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
+    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
+    cw_sw_cuts dc;
+    dc.cuts = (uint32_t*)(dout + o_cuts); dc.cut_off = (const uint64_t*)(din + i_coff); dc.window = W;
+    if ((rc = run_sw_cut_locked(e, &db, (int32_t*)(dout + o_rows), &dc, st)) != CW_OK) return rc;
+    CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
+    if (n_slots) CW_HIP(hipMemcpyAsync(back.data(), dc.cuts, (size_t)n_slots * 4, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    for (const auto& sw : owned)
+        if (rows[(size_t)sw.first * CW_SW_ROW + CW_SW_STATUS] != CW_SW_CUT_SLOT)
+            memcpy(cuts->cuts + cuts->cut_off[sw.first], back.data() + coff[sw.first], (size_t)sw.second * 4);
+    for (uint32_t s = 0; s < S; ++s)
+        if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) rc = CW_E_CAPACITY;
+    return rc;
+}
+
+/* One work-group sizes the output groups of every input group, a wave per output group counts its members and words, one work-group scans; the totals come to
+   the host (the one synchronisation), and when they fit the same waves fill.  The working arrays live in the engine's scratch allocation -- the cut run's
+   scratch is dead by then -- sized for the most output groups the batch's words can hold: 16 n_words / W + a group's last window each. */
+int cw_cut_groups_device(cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_sw_cuts* cuts, uint32_t* grp_first, uint32_t* win_first_seq,
+                         uint32_t* seq_len, uint64_t* seq_word_off, uint32_t* bases, uint32_t group_cap, uint32_t seq_cap, uint64_t word_cap,
+                         uint32_t* n_groups, uint32_t* n_seqs, uint64_t* n_words, void* hip_stream) {
+    if (!e || !groups || !cuts || !n_groups || !n_seqs || !n_words || cuts->window == 0u) return CW_E_INVALID;
+    *n_groups = 0; *n_seqs = 0; *n_words = 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
+    if (groups->n_seqs != 0 && groups->n_windows == 0) return CW_E_INVALID;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    if (groups->n_seqs == 0) { /* groups of none only: no output group */
+        if (grp_first) CW_HIP(hipMemsetAsync(grp_first, 0, (size_t)(groups->n_windows + 1) * 4, st));
+        if (win_first_seq) CW_HIP(hipMemsetAsync(win_first_seq, 0, 4, st));
+        return CW_OK;
+    }
+    if (!rows || !cuts->cuts || !cuts->cut_off || !groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
+    const uint32_t G = groups->n_windows;
+    const uint64_t most = 16ull * groups->n_words / cuts->window + G;
+    if (most > 0x7FFFFFFFull) return CW_E_INVALID;
+    size_t o = 0;
+    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+    const size_t o_grp = put((size_t)(G + 1) * 4), o_ws = put((size_t)(most + 1) * 4), o_ww = put((size_t)(most + 1) * 8), o_st = put(32);
+    int rc = ensure(&e->scratch, &e->scratch_bytes, o);
+    if (rc) return rc;
+    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (run_sw_locked) */
+    uint8_t* base = (uint8_t*)e->scratch;
+    CW_HIP(hipMemsetAsync(base + o_st, 0, 32, st));
+    CutGroupArgs a;
+    a.b.n_windows = G; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.rows = rows; a.cuts = cuts->cuts; a.cut_off = cuts->cut_off; a.window = cuts->window; a.out_cap = (uint32_t)most;
+    a.grp = (uint32_t*)(base + o_grp); a.win_seqs = (uint32_t*)(base + o_ws); a.win_words = (uint64_t*)(base + o_ww);
+    a.grp_first = grp_first; a.win_first_seq = win_first_seq; a.seq_len = seq_len; a.seq_word_off = seq_word_off; a.bases = bases;
+    a.group_cap = group_cap; a.seq_cap = seq_cap; a.word_cap = word_cap; a.status = (uint32_t*)(base + o_st);
+    const uint32_t wgs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((most + 1 + 3) / 4, (uint64_t)e->cus * 8u));
+    cw_cut_index_kernel<<<1, 1024, 0, st>>>(a);
+    cw_cut_count_kernel<<<wgs, 256, 0, st>>>(a);
+    cw_cut_scan_kernel<<<1, 1024, 0, st>>>(a);
+    uint32_t flags[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the two flags, then the totals the scan left: groups, sequences, words (64 bits) */
+    CW_HIP(hipMemcpyAsync(flags, a.status, 32, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    if (flags[1]) return CW_E_INVALID; /* more windows than the batch's words hold bases for: a malformed batch */
+    const uint32_t tot_g = flags[2], tot_s = flags[3];
+    uint64_t tot_w = 0;
+    memcpy(&tot_w, flags + 4, 8);
+    *n_groups = tot_g; *n_seqs = tot_s; *n_words = tot_w;
+    if (tot_g > group_cap || tot_s > seq_cap || tot_w > word_cap || !grp_first || !win_first_seq || !seq_len || !seq_word_off || !bases) return CW_E_CAPACITY;
+    cw_cut_fill_kernel<<<wgs, 256, 0, st>>>(a);
+    CW_HIP(hipGetLastError());
+    return CW_OK;
 }
 
 /* Debug/inspection (cw_private.h): what plan_sw_path would allocate, part by part, and its grids (host arithmetic only). */

@@ -24,12 +24,20 @@ SW_OP_LETTERS = {SW_OP_M: "M", SW_OP_I: "I", SW_OP_D: "D", SW_OP_EQ: "=", SW_OP_
 SW_PILE_SLOT = 7
 PILE_ACCUMULATE = 8
 PILE_A, PILE_C, PILE_G, PILE_T, PILE_DEL, PILE_INS, PILE_BEGIN, PILE_END, PILE_COL = 0, 1, 2, 3, 4, 5, 6, 7, 8
+# cw_sw_cut_run: the status only it writes
+SW_CUT_SLOT = 8
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def sw_ops_bound(query_len, ref_len):
     """CW_SW_OPS_BOUND: a slot of this many ops holds any path of the pair."""
     return query_len + ref_len
+
+
+def sw_cuts(ref_len, window):
+    """CW_SW_CUTS: the words of a query's slot -- the windows of its reference + 1 (numpy-friendly)."""
+    ref_len = np.asarray(ref_len, np.int64)
+    return ref_len // window + (ref_len % window != 0) + 1
 
 
 class EngineError(RuntimeError):
@@ -64,6 +72,12 @@ class Pileup(C.Structure):
     """cw_pileup: the column slots of cw_pileup_run."""
 
     _fields_ = [("counts", C.c_void_p), ("col_off", C.c_void_p)]
+
+
+class SwCuts(C.Structure):
+    """cw_sw_cuts: the cut-point slots of cw_sw_cut_run and the window size."""
+
+    _fields_ = [("cuts", C.c_void_p), ("cut_off", C.c_void_p), ("window", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -171,6 +185,11 @@ def _load(p):
     if hasattr(lib, "cw_pileup_run"):
         lib.cw_pileup_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(Pileup), C.c_uint32]
         lib.cw_pileup_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(Pileup), C.c_uint32, C.c_void_p]
+    if hasattr(lib, "cw_sw_cut_run"):
+        lib.cw_sw_cut_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwCuts)]
+        lib.cw_sw_cut_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwCuts), C.c_void_p]
+        lib.cw_cut_groups_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwCuts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p]
     lib.cw_submit.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.POINTER(C.c_int)]
     lib.cw_wait.argtypes = [C.c_void_p, C.c_int]
     lib.cw_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -571,6 +590,48 @@ class PileupRows(SwRows):
         return self.counts(group)[:, : PILE_DEL + 1].sum(axis=1, dtype=np.int64)
 
 
+class SwCutRows(SwRows):
+    """What Engine.sw_cut returns: SwRows, and per query its cut points at the reference's window boundaries: sequence s, where it is a query, owns
+    cuts_buf[cut_off[s] : cut_off[s + 1]], of which the first sw_cuts(reference length, window) words are written."""
+
+    def __init__(self, rows, win_first_seq, rc, cuts_buf, cut_off, window, batch):
+        super().__init__(rows, win_first_seq, rc)
+        self.cuts_buf, self.cut_off, self.window, self.batch = cuts_buf, cut_off, window, batch
+
+    def cuts(self, group, member):
+        """The T + 1 cut points of query `member` (>= 1) of `group`: query positions, non-decreasing; empty when the slot does not hold them."""
+        s = self.index(group, member)
+        if member == 0:
+            raise IndexError("a reference has no cut points")
+        n = int(sw_cuts(int(self.batch.seq_len[int(self.win_first_seq[group])]), self.window))
+        o = int(self.cut_off[s])
+        return self.cuts_buf[o : o + n] if int(self.cut_off[s + 1]) - o >= n else self.cuts_buf[:0]
+
+    def pieces(self, group, member):
+        """The query cut at those points: piece t is what its alignment puts on window t of the reference ('' where it puts nothing)."""
+        c = [int(x) for x in self.cuts(group, member)]
+        q = self.batch.pile(group)[member]
+        return [q[a:b] for a, b in zip(c, c[1:])]
+
+
+class PolishWindow:
+    """One window of a polished reference: `members` pieces were aligned beside the reference's own; `status` is the POA's (WIN_CONSENSUS, or WIN_OVERFLOW
+    for a group that stopped: `kept_reference` is then True and the window's part of the result is the reference's columns)."""
+
+    def __init__(self, members, status, kept_reference):
+        self.members, self.status, self.kept_reference = members, status, kept_reference
+
+    def __repr__(self):
+        return f"PolishWindow(members={self.members}, status={self.status}, kept_reference={self.kept_reference})"
+
+
+class Polished:
+    """One reference of Engine.polish: `sequence`, the windows' consensuses joined in order, and `windows`, a PolishWindow each."""
+
+    def __init__(self, sequence, windows):
+        self.sequence, self.windows = sequence, windows
+
+
 def _result_struct(r):
     return Result(
         _ptr(r.cons), _ptr(r.cons_off), _ptr(r.cons_len), _ptr(r.status),
@@ -726,6 +787,129 @@ class Engine:
         for g in range(n_groups):
             against.append([res.consensus(g)] + list(piles(g)))
         return res, self.pileup(against)
+
+    @staticmethod
+    def _cut_slots(batch, window, slot_words=None):
+        """cut_off of a batch: a query sw_cuts(its reference, window) words (or slot_words: one number, or one per sequence), a reference none."""
+        S = len(batch.seq_len)
+        wfs = np.asarray(batch.win_first_seq, np.int64)
+        lens = np.asarray(batch.seq_len, np.int64)
+        if slot_words is None:
+            ref_of = np.repeat(wfs[:-1], np.diff(wfs))
+            width = sw_cuts(lens[ref_of], window) if S else np.zeros(0, np.int64)
+            width[wfs[:-1][np.diff(wfs) > 0]] = 0
+        else:
+            width = np.broadcast_to(np.asarray(slot_words, np.int64), (S,))
+        cut_off = np.zeros(S + 1, np.uint64)
+        cut_off[1:] = np.cumsum(width)
+        return cut_off
+
+    def sw_cut(self, groups, window, slot_words=None):
+        """The local alignments cut at their reference's window boundaries (cw_sw_cut_run): `groups` as for sw(), `window` >= 1 reference columns.  Returns
+        SwCutRows: the rows of sw_path(), .cuts(group, member) -- word t the query position at reference column t * window -- and .pieces(group, member).
+        Status SW_CUT_SLOT never occurs with the slots made here; slot_words (one number, or one per sequence) makes others."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        S = len(batch.seq_len)
+        cut_off = self._cut_slots(batch, max(int(window), 1), slot_words)
+        cuts_buf = np.zeros(max(int(cut_off[-1]), 1), np.uint32)
+        rows = np.zeros((S, SW_ROW), np.int32)
+        b = batch.c_struct()
+        cuts = SwCuts(_ptr(cuts_buf), _ptr(cut_off), window)
+        rc = _check(self.lib, self.lib.cw_sw_cut_run(self.handle, C.byref(b), _ptr(rows), C.byref(cuts)), "cw_sw_cut_run", allow_capacity=True)
+        return SwCutRows(rows, batch.win_first_seq, rc, cuts_buf, cut_off, window, batch)
+
+    def sw_cut_device(self, batch_struct, rows_ptr, cuts_struct, stream=None):
+        """cw_sw_cut_run_device: device pointers in the batch struct and in `cuts_struct` (SwCuts), `rows_ptr` a device array of n_seqs * SW_ROW int32;
+        asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_sw_cut_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(cuts_struct), stream), "cw_sw_cut_run_device")
+
+    def cut_groups_device(self, batch_struct, rows_ptr, cuts_struct, grp_first=None, win_first_seq=None, seq_len=None, seq_word_off=None, bases=None,
+                          group_cap=0, seq_cap=0, word_cap=0, stream=None):
+        """cw_cut_groups_device: the POA batch of every (reference, window) behind a cut run, device pointers throughout.  Returns (rc, output groups,
+        sequences, words): rc is 0, or -4 when the totals exceed the capacities -- with capacities of 0 that only sizes the output; one synchronisation."""
+        ng, ns, nw = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        rc = self.lib.cw_cut_groups_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(cuts_struct), grp_first, win_first_seq, seq_len, seq_word_off, bases,
+                                           group_cap, seq_cap, word_cap, C.byref(ng), C.byref(ns), C.byref(nw), stream)
+        if rc not in (0, -4):
+            _check(self.lib, rc, "cw_cut_groups_device")
+        return rc, ng.value, ns.value, nw.value
+
+    def polish(self, groups, window=500):
+        """Every group's reference (its first sequence) polished window by window from its other sequences, the reads: the reads are aligned and cut at the
+        window boundaries (cw_sw_cut_run_device), every (reference, window) becomes a POA group of the window's columns and the pieces of the reads whose
+        alignments span it (cw_cut_groups_device), the POA tiers give every group's consensus (cw_poa_run_device), and the consensuses of a reference's windows
+        are joined in order.  Nothing but the result leaves the device.  The reference's columns are the backbone: one voice among the members, and base ties
+        go to it; the first max_msa non-empty sequences of a group are aligned, the backbone included.  Returns a list of Polished, one per input group:
+        .sequence and .windows (PolishWindow: members, status, kept_reference).  A window whose POA group stops keeps the reference's columns.  Raises
+        EngineError when the windows of the batch exceed max_batch_windows(): split the references over calls."""
+        import torch
+
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        window = int(window)
+        if window < 1:
+            raise EngineError("polish: window must be at least 1")
+        G, S = batch.n_windows, len(batch.seq_len)
+        if S == 0:
+            return [Polished("", []) for _ in range(G)]
+        dev = torch.device("cuda", self.device)
+
+        def up(a, dt):
+            return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
+
+        def down(t, dt):
+            return t.cpu().numpy().view(dt)
+
+        t_wfs, t_len, t_off = up(batch.win_first_seq, np.int32), up(batch.seq_len, np.int32), up(batch.seq_word_off, np.int64)
+        t_bases = up(np.concatenate([batch.bases, np.zeros(1, np.uint32)]), np.int32)
+        cut_off = self._cut_slots(batch, window)
+        t_coff = up(cut_off, np.int64)
+        t_cuts = torch.zeros(max(int(cut_off[-1]), 1), dtype=torch.int32, device=dev)
+        t_rows = torch.zeros(S * SW_ROW, dtype=torch.int32, device=dev)
+        t_grp = torch.zeros(G + 1, dtype=torch.int32, device=dev)
+        b = Batch(G, S, len(batch.bases), t_wfs.data_ptr(), t_len.data_ptr(), t_off.data_ptr(), t_bases.data_ptr())
+        cuts = SwCuts(t_cuts.data_ptr(), t_coff.data_ptr(), window)
+        torch.cuda.synchronize(dev)  # the engine launches on its own stream: torch's copies and fills above must have landed
+        self.sw_cut_device(b, t_rows.data_ptr(), cuts)
+        _, ng, ns, nw = self.cut_groups_device(b, t_rows.data_ptr(), cuts)
+        if ng > self.max_batch_windows():
+            raise EngineError(f"polish: {ng} windows exceed the {self.max_batch_windows()} groups of a POA run; split the references over calls")
+        o_wfs = torch.zeros(ng + 1, dtype=torch.int32, device=dev)
+        o_len = torch.zeros(max(ns, 1), dtype=torch.int32, device=dev)
+        o_off = torch.zeros(max(ns, 1), dtype=torch.int64, device=dev)
+        o_bases = torch.zeros(max(nw, 1) + 1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        rc, ng, ns, nw = self.cut_groups_device(b, t_rows.data_ptr(), cuts, t_grp.data_ptr(), o_wfs.data_ptr(), o_len.data_ptr(), o_off.data_ptr(), o_bases.data_ptr(), ng, ns, nw)
+        _check(self.lib, rc, "cw_cut_groups_device")
+        torch.cuda.synchronize(dev)
+        if ng == 0:
+            return [Polished("", []) for _ in range(G)]
+        # the consensus slots: CW_POA_SLOT_BYTES of every group's longest member
+        counts = (o_wfs[1:] - o_wfs[:-1]).to(torch.int64)
+        gid = torch.repeat_interleave(torch.arange(ng, device=dev), counts)
+        longest = torch.zeros(ng, dtype=torch.int64, device=dev).scatter_reduce_(0, gid, o_len[:ns].to(torch.int64), "amax", include_self=True)
+        c_off = torch.zeros(ng + 1, dtype=torch.int64, device=dev)
+        c_off[1:] = torch.cumsum(2 * longest + 2, 0)
+        c_cons = torch.zeros(int(c_off[-1].item()), dtype=torch.uint8, device=dev)
+        c_len = torch.zeros(ng, dtype=torch.int32, device=dev)
+        c_stat = torch.full((ng,), 255, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        pb = Batch(ng, ns, nw, o_wfs.data_ptr(), o_len.data_ptr(), o_off.data_ptr(), o_bases.data_ptr())
+        pr = Result(c_cons.data_ptr(), c_off.data_ptr(), c_len.data_ptr(), c_stat.data_ptr(), None, None, None)
+        self.poa_device(pb, pr)
+        torch.cuda.synchronize(dev)
+        grp, members = down(t_grp, np.uint32), down(counts, np.int64) - 1
+        cons, coff, clen, stat = down(c_cons, np.uint8), down(c_off, np.int64), down(c_len, np.uint32), down(c_stat, np.uint8)
+        out = []
+        for g in range(G):
+            w0, w1 = int(grp[g]), int(grp[g + 1])
+            ref = batch.pile(g)[0] if w1 > w0 else ""
+            parts, wins = [], []
+            for t, w in enumerate(range(w0, w1)):
+                ok = int(stat[w]) == WIN_CONSENSUS
+                parts.append(cons[int(coff[w]) : int(coff[w]) + int(clen[w])].tobytes().decode() if ok else ref[t * window : (t + 1) * window])
+                wins.append(PolishWindow(int(members[w]), int(stat[w]), not ok))
+            out.append(Polished("".join(parts), wins))
+        return out
 
     def extract_piles(self, reads, overlaps, jobs, k):
         """Device-side getAlignmentWindowsSequences (cw_extract_piles_device).  `reads` is a HostBatch-like packing of the read

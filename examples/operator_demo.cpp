@@ -1,4 +1,5 @@
-// Minimal C++ caller of the engine through the adapter: one synthetic window, prints the consensus -- and how the first members of the pile lie against it.
+// Minimal C++ caller of the engine through the adapter: one synthetic window, prints the consensus -- how the first members of the pile lie against it, and where
+// they cross its windows.
 // Build: g++ -std=c++17 -Iinclude examples/operator_demo.cpp -Lconsent_amd -lconsent_amd -Wl,-rpath,$PWD/consent_amd -o /tmp/operator_demo
 #include <cstdio>
 #include <random>
@@ -37,6 +38,13 @@ int main() {
         for (size_t m = 1; m < rows[0].size(); ++m)
             std::printf("member %zu: consensus %d..%d, member %d..%d, score %d, ins %d, del %d\n", m - 1, rows[0][m][CW_SW_REF_BEGIN], rows[0][m][CW_SW_REF_END],
                         rows[0][m][CW_SW_QUERY_BEGIN], rows[0][m][CW_SW_QUERY_END], rows[0][m][CW_SW_SCORE], rows[0][m][CW_SW_INS], rows[0][m][CW_SW_DEL]);
+        // the same members cut where their alignments cross the consensus's windows of 100 columns (cw_sw_cut_run): piece t is what a member puts on window t
+        auto cuts = eng.cutAtWindows(groups, /*window*/ 100);
+        for (size_t m = 1; m < cuts[0].size(); ++m) {
+            std::printf("member %zu: pieces", m - 1);
+            for (size_t t = 0; t + 1 < cuts[0][m].size(); ++t) std::printf(" [%u, %u)", cuts[0][m][t], cuts[0][m][t + 1]);
+            std::printf("\n");
+        }
     } catch (const std::exception& e) {
         std::printf("engine unavailable: %s\n", e.what());
         return 2;

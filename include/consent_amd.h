@@ -16,6 +16,10 @@
  *   cw_sw_path_run / cw_sw_path_run_device <- the same pairs with the alignment itself (ssw's banded traceback, its cigar) as run-length encoded ops.
  *   cw_pileup_run / cw_pileup_run_device <- the same pairs again, their paths counted into the reference's columns on the device (no counterpart: what a caller
  *                               of the above would do with every pair's cigar).
+ *   cw_sw_cut_run / cw_sw_cut_run_device <- the same pairs once more, every query cut where its path crosses the reference's window boundaries (no
+ *                               counterpart: alignmentWindows.cpp cuts by shifting PAF coordinates, without an alignment).
+ *   cw_cut_groups_device     <- those pieces as the POA batch of every (reference, window): what stands between the aligner and cw_poa_run_device when a
+ *                               reference is polished window by window.
  *   cw_window_positions      <- getAlignmentWindowsPositions (alignmentWindows.cpp:27-85), host
  *   cw_extract_piles_device  <- getAlignmentWindowsSequences (alignmentWindows.cpp:87-149) evaluated on the device
  *   cw_stitch_device         <- alignConsensus + trimRead + dropRead (correctionAlignment.cpp:47-140, utils.cpp:96-128, :71-73)
@@ -306,6 +310,60 @@ enum { CW_SW_PILE_SLOT = 7 };     /* row status only these entry points write */
 #define CW_PILE_ACCUMULATE 8u     /* the only flag */
 int cw_pileup_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream);
 int cw_pileup_run(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags);
+
+/* ---- where the queries cross the reference's windows: cw_sw_cut_run ------------------------------------------------------------------------------------------
+ * `groups` and `rows` as for cw_sw_path_run; in place of every pair's ops, the query's cut points at the reference's window boundaries.  A reference of n
+ * columns has T = ceil(n / W) windows of W = cuts->window columns (the last one shorter when W does not divide n); the layout is per SEQUENCE, as ops_off is:
+ * sequence s, where it is a query, owns cuts[cut_off[s] .. cut_off[s+1]) and writes words t = 0 .. T of it -- CW_SW_CUTS(reference length, W) words.
+ * A pair that counts is cw_pileup_run's: one cw_sw_path_run reports CW_SW_ALIGNED with a positive score.  With every position absolute:
+ *   cuts[t] = query_begin       where t x W <= ref_begin
+ *   cuts[t] = query_end + 1     where t x W >  ref_end
+ *   otherwise                   the number of query bases the path has consumed when it takes the step (an M or a D) that consumes column t x W -- counted
+ *                               from the query's first base, so a position in the query.  An insertion run between columns t x W - 1 and t x W therefore
+ *                               belongs to window t - 1: the side on which cw_pileup_run counts its INS event.  A deletion that covers column t x W cuts at
+ *                               the query base that follows it.
+ * cuts is non-decreasing, cuts[0] = query_begin and cuts[T] = query_end + 1.  Piece t of the query is query[cuts[t], cuts[t+1]): what the alignment puts on
+ * window t; the pieces concatenate to the aligned query span.  The words are functions of the pair alone: they depend on no batch composition, order or run.
+ * Every other pair -- score 0, CW_SW_NO_PATH, CW_SW_PATH_OPEN, CW_SW_STOP, an empty query or reference -- gets T + 1 zeros: all its pieces are empty.
+ * The row is cw_sw_path_run's bit for bit, ins / del included, but for
+ *   CW_SW_CUT_SLOT   the slot is shorter than T + 1 words: a pair that would have counted keeps its seven numbers and has this status, and nothing is
+ *                    written to the slot.  A pair that does not count writes nothing to a short slot either and keeps its status.
+ * Never touched: the words of a slot beyond T + 1, a reference's own slot (it may be empty), anything outside the slots.
+ * CW_E_INVALID, before anything is launched: window == 0, NULL rows / cuts / cuts->cuts / cuts->cut_off, more than cw_max_batch_windows(e) groups.
+ * n_seqs == 0 is CW_OK.  The scratch plan is cw_sw_path_run's without op memory, exact, as for the pileup run: the batch runs once.
+ * cw_sw_cut_run_device: every pointer inside groups and cuts, and rows, is a DEVICE pointer; asynchronous on `hip_stream` (NULL = the engine's own); CW_OK
+ * also when pairs stop.  cw_sw_cut_run: host pointers, synchronous, cut_off ascending from any start; of the slots only the T + 1 words of the query slots
+ * that hold them come back; CW_E_CAPACITY only when a row has CW_SW_STOP.
+ * Such runs alternate freely with every other kind of run on one engine.  cw_last_timings names the stages sw_order, cut (queries of up to 640 bases),
+ * cut_wide (up to 2 048), cut_long (beyond). */
+typedef struct cw_sw_cuts {
+    uint32_t* cuts;           /* query positions */
+    const uint64_t* cut_off;  /* [n_seqs + 1]: sequence s, where it is a query, owns cuts[cut_off[s] .. cut_off[s+1]) */
+    uint32_t window;          /* W >= 1 reference columns a window */
+} cw_sw_cuts;
+/* words a query's slot needs: the windows of its reference + 1; no 32-bit overflow for any W */
+#define CW_SW_CUTS(ref_len, window) ((ref_len) / (window) + ((ref_len) % (window) != 0u) + 1u)
+enum { CW_SW_CUT_SLOT = 8 };      /* row status only these entry points write */
+int cw_sw_cut_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, void* hip_stream);
+int cw_sw_cut_run(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts);
+
+/* The POA batch behind a cut run, built on the device: one output group per (reference, window).  `groups`, `rows` and `cuts` are what cw_sw_cut_run_device
+ * took and wrote, all DEVICE pointers, and so are grp_first[groups->n_windows + 1] and the four output arrays laid out as cw_batch (win_first_seq[group_cap + 1],
+ * seq_len[seq_cap], seq_word_off[seq_cap], bases[word_cap]).  Input group g with a non-empty reference of T windows gives output groups grp_first[g] + t,
+ * t = 0 .. T - 1, input groups in order; a group of none or with an empty reference gives none (grp_first[g + 1] = grp_first[g]).
+ *   first sequence of (g, t)   reference columns [t x W, min((t + 1) x W, n))
+ *   members, in query order    piece t of every query of g whose row is CW_SW_ALIGNED with a positive score, whose alignment spans the window --
+ *                              ref_begin <= t x W and ref_end >= min((t + 1) x W, n) - 1 -- and whose piece is not empty
+ * A piece that covers part of a window is no member: it would be aligned end to end against whole-window members (DESIGN.md 4.8 has the figures).  The output
+ * is a valid cw_batch: every sequence starts on a word boundary, the unused low bits of its last word are zero.
+ * *n_groups / *n_seqs / *n_words (HOST pointers) hold the totals on return; the call synchronises once to read them.  CW_E_CAPACITY when they exceed the
+ * capacities, and nothing of the output is then valid: call again with larger arrays (capacities 0 just size the batch; the arrays may then be NULL).
+ * CW_E_INVALID for NULL groups / rows / cuts or totals, window == 0, more than cw_max_batch_windows(e) input groups. */
+int cw_cut_groups_device(cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_sw_cuts* cuts,
+                         uint32_t* grp_first /* [groups->n_windows + 1] */,
+                         uint32_t* win_first_seq, uint32_t* seq_len, uint64_t* seq_word_off, uint32_t* bases,
+                         uint32_t group_cap, uint32_t seq_cap, uint64_t word_cap,
+                         uint32_t* n_groups, uint32_t* n_seqs, uint64_t* n_words, void* hip_stream);
 
 /* 1 when everything the last cw_run_device on this engine launched has completed (or nothing was launched yet), 0 while it is
  * still running, 2 while it is running but past the part that fills the GPU (what is left is the tail: a few long alignment tasks on

@@ -150,6 +150,37 @@ class Engine {
         return out;
     }
 
+    /* The local alignment cut at the reference's window boundaries (cw_sw_cut_run): [g][m] holds the cut points of member m >= 1 of group g -- word t the
+       position in the member at column t x window of the group's first sequence, so that member.substr(c[t], c[t + 1] - c[t]) is what its alignment puts
+       on window t -- and [g][0] is empty.  A member that does not align gets zeros. */
+    std::vector<std::vector<std::vector<uint32_t>>> cutAtWindows(const std::vector<std::vector<std::string>>& groups, uint32_t window) {
+        std::vector<uint32_t> wfs{0}, len, bases;
+        std::vector<uint64_t> off, cut_off{0};
+        for (const auto& group : groups) {
+            for (const auto& s : group) {
+                const uint64_t words = (s.size() + 15) / 16;
+                off.push_back(bases.size());
+                len.push_back((uint32_t)s.size());
+                bases.resize(bases.size() + words);
+                if (words && cw_pack_sequence(s.data(), (uint32_t)s.size(), bases.data() + off.back(), words) < 0)
+                    throw std::runtime_error("consent_amd: cw_pack_sequence failed");
+                cut_off.push_back(cut_off.back() + (&s == &group.front() || window == 0 ? 0u : CW_SW_CUTS((uint32_t)group.front().size(), window)));
+            }
+            wfs.push_back((uint32_t)len.size());
+        }
+        bases.push_back(0);
+        std::vector<int32_t> rows(len.size() * CW_SW_ROW + 1);
+        std::vector<uint32_t> words(cut_off.back() + 1);
+        cw_batch b{(uint32_t)groups.size(), (uint32_t)len.size(), (uint64_t)bases.size() - 1, wfs.data(), len.data(), off.data(), bases.data()};
+        cw_sw_cuts cuts{words.data(), cut_off.data(), window};
+        const int rc = cw_sw_cut_run(eng_, &b, rows.data(), &cuts);
+        if (rc != CW_OK && rc != CW_E_CAPACITY) throw std::runtime_error(std::string("consent_amd: cw_sw_cut_run: ") + cw_strerror(rc));
+        std::vector<std::vector<std::vector<uint32_t>>> out(groups.size());
+        for (size_t g = 0; g < groups.size(); ++g)
+            for (uint32_t s = wfs[g]; s < wfs[g + 1]; ++s) out[g].emplace_back(words.begin() + cut_off[s], words.begin() + cut_off[s + 1]);
+        return out;
+    }
+
   private:
     cw_engine* eng_ = nullptr;
     unsigned solid_;

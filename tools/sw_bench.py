@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the alignment operator alone (cw_sw_run_device, include/consent_amd.h): pairs/s and DP cells/s per shape, with and without the indel totals -- and with
 --path through cw_sw_path_run_device, which returns the alignment's ops, with --pileup also through cw_pileup_run_device, which counts the paths into their
-reference's columns -- with cw_last_timings' stages.
+reference's columns, with --cut also through cw_sw_cut_run_device, which cuts every query at its reference's window boundaries -- with cw_last_timings' stages.
 
 Input is synthetic: a group is one random reference and `--per-group` queries; a query is a stretch of its reference with 8 % substitutions and one deletion
 of four bases (so the banded traceback starts at a band of 5) -- or, where the query is the longer one, the whole reference treated that way between random
@@ -10,13 +10,14 @@ P, M, S and unrelated 40-base G1, G2 -- the traceback's band starts at 1 and dou
 
 The shape 500x600x30, which --pileup adds, is 500 x 600 with 30 queries on every reference instead of --per-group: deeper columns, more adds to the same words.
 
-The batch lives in device memory; a step is one cw_sw_run_device (or cw_sw_path_run_device, cw_pileup_run_device) and a wait for it.  DP cells of a pair are query length x
+The batch lives in device memory; a step is one cw_sw_run_device (or cw_sw_path_run_device, cw_pileup_run_device, cw_sw_cut_run_device) and a wait for it.  DP cells of a pair are query length x
 reference length: the forward sweep's; the reverse sweep and the traceback come on top and are not counted, for any implementation.
 
     python tools/sw_bench.py                              # the six shapes (query x reference), each with and without indel totals
     python tools/sw_bench.py --shape 500x600 --pairs 65536 --steps 10
     python tools/sw_bench.py --path                       # a third measurement per shape: the path run
     python tools/sw_bench.py --pileup                     # a fourth beside it: the pileup run of the same batch, and the shape 500x600x30
+    python tools/sw_bench.py --cut                        # a fifth: the cut run of the same batch at --window columns a window, on the shapes of --pileup
     python tools/sw_bench.py --oracle 4096                # also: so many 500 x 600 pairs through the oracle's cwo_ssw on --threads CPU threads
 
 Prints one JSON line per measurement and a markdown table (DESIGN.md section 4.8 holds the first one, from a --path run).
@@ -35,12 +36,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import consent_amd as ca  # noqa: E402
-from consent_amd.engine import Batch, HostBatch, Pileup, SwPaths  # noqa: E402
+from consent_amd.engine import Batch, HostBatch, Pileup, SwCuts, SwPaths, sw_cuts  # noqa: E402
 
 SHAPES = {"24x150": 262144, "100x600": 131072, "500x600": 65536, "2000x2048": 4096, "8000x2048": 512, "1540x1540": 2048}  # query x reference -> pairs of the default run
 PLANTED = {"1540x1540": (500, 40)}  # shapes built as planted pairs: (part, g)
 DEEP = {"500x600x30": 61440}  # query x reference x queries per reference: what --pileup adds
-PATH, PILE = "path", "pileup"  # the third and fourth mode beside flags 0 and CW_SW_WANT_INDELS
+PATH, PILE, CUT = "path", "pileup", "cut"  # the third, fourth and fifth mode beside flags 0 and CW_SW_WANT_INDELS
 
 
 def pack(codes):
@@ -89,7 +90,7 @@ def make_planted(n_pairs, part, g, seed):
     return HostBatch(np.arange(n_pairs + 1, dtype=np.uint32) * 2, np.full(2 * n_pairs, L, np.uint32), np.arange(2 * n_pairs, dtype=np.uint64) * W, bases)
 
 
-def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
+def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed, window=100):
     import torch
 
     qlen, rlen, *deep = (int(v) for v in shape.split("x"))
@@ -120,6 +121,13 @@ def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
         off = np.concatenate([[0], np.cumsum(width)]).astype(np.uint64)
         t_off, t_counts = up(off, np.int64), torch.zeros((int(off[-1]) + 1, ca.PILE_COL), dtype=torch.int32, device=dev)
         pile = Pileup(t_counts.data_ptr(), t_off.data_ptr())
+    if flags == CUT:  # the slots: CW_SW_CUTS of its reference for a query, none for a reference
+        wfs, lens = hb.win_first_seq.astype(np.int64), hb.seq_len.astype(np.int64)
+        width = sw_cuts(lens[np.repeat(wfs[:-1], np.diff(wfs))], window)
+        width[wfs[:-1]] = 0
+        off = np.concatenate([[0], np.cumsum(width)]).astype(np.uint64)
+        t_off, t_cuts = up(off, np.int64), torch.zeros(int(off[-1]) + 1, dtype=torch.int32, device=dev)
+        cuts = SwCuts(t_cuts.data_ptr(), t_off.data_ptr(), window)
     torch.cuda.synchronize(dev)
     times, stages = [], {}
     for step in range(warmup + steps):
@@ -128,6 +136,8 @@ def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
             eng.sw_path_device(b, C.c_void_p(t_rows.data_ptr()), paths, 0)
         elif flags == PILE:
             eng.pileup_device(b, C.c_void_p(t_rows.data_ptr()), pile, 0)
+        elif flags == CUT:
+            eng.sw_cut_device(b, C.c_void_p(t_rows.data_ptr()), cuts)
         else:
             eng.sw_device(b, C.c_void_p(t_rows.data_ptr()), flags)
         torch.cuda.synchronize(dev)
@@ -149,7 +159,14 @@ def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed):
         assert int(counts[:, ca.PILE_BEGIN].sum()) == int(counts[:, ca.PILE_END].sum()) == counted and int(counts[:, ca.PILE_DEL].sum()) == int(q[:, 6].sum())
         extra = {"counted_rows": counted, "columns": len(counts), "mean_depth": round(float(counts[:, : ca.PILE_DEL + 1].sum() / max(len(counts), 1)), 2),
                  "no_path_rows": int((q[:, 7] == ca.SW_NO_PATH).sum()), "open_rows": int((q[:, 7] == ca.SW_PATH_OPEN).sum()), "mean_indels": round(float(q[:, 5:7].sum(axis=1).mean()), 1)}
-    return {"shape": shape, "pairs": n_pairs, "indels": flags if flags in (PATH, PILE) else bool(flags), "steps": steps, **extra, "ms_per_batch": round(ms, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
+    if flags == CUT:
+        words, is_q = t_cuts.cpu().numpy()[:-1].astype(np.int64), rows[:, 7] != ca.SW_IS_REF
+        first, last = words[off[:-1][is_q].astype(np.int64)], words[off[1:][is_q].astype(np.int64) - 1]
+        counted = (q[:, 7] == ca.SW_ALIGNED) & (q[:, 0] > 0)
+        assert np.array_equal(first[counted], q[counted, 3]) and np.array_equal(last[counted], q[counted, 4] + 1) and not first[~counted].any() and not last[~counted].any()
+        extra = {"window": window, "counted_rows": int(counted.sum()), "cut_words": len(words), "no_path_rows": int((q[:, 7] == ca.SW_NO_PATH).sum()),
+                 "open_rows": int((q[:, 7] == ca.SW_PATH_OPEN).sum()), "slot_rows": int((q[:, 7] == ca.SW_CUT_SLOT).sum()), "mean_indels": round(float(q[:, 5:7].sum(axis=1).mean()), 1)}
+    return {"shape": shape, "pairs": n_pairs, "indels": flags if flags in (PATH, PILE, CUT) else bool(flags), "steps": steps, **extra, "ms_per_batch": round(ms, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
             "pairs_per_s": round(n_pairs / ms * 1e3), "dp_cells_per_s": float(f"{n_pairs * qlen * rlen / ms * 1e3:.4g}"), "mean_score": round(float(q[:, 0].mean()), 1),
             "no_indels_rows": int((q[:, 7] == ca.SW_NO_INDELS).sum()), "stopped_rows": int((q[:, 7] == ca.SW_STOP).sum()),
             "stage_ms": {k: round(float(np.median(v)), 3) for k, v in stages.items()}}
@@ -189,23 +206,27 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--path", action="store_true", help="also time the path run (cw_sw_path_run_device) on every shape")
     ap.add_argument("--pileup", action="store_true", help="time the path run and the pileup run (cw_pileup_run_device) of the same batch on every shape, and on 500x600x30")
+    ap.add_argument("--cut", action="store_true", help="time the path run, the pileup run and the cut run (cw_sw_cut_run_device) of the same batch on the shapes of --pileup")
+    ap.add_argument("--window", type=int, default=100, help="reference columns a window of the cut run")
     ap.add_argument("--oracle", type=int, default=0, help="also time so many 500x600 pairs through the oracle on --threads CPU threads")
     ap.add_argument("--threads", type=int, default=16)
     a = ap.parse_args()
+    a.pileup = a.pileup or a.cut
     eng = ca.Engine(ca.Params(9, 4, 8, 2, 150), device=a.device)
     rows = []
     try:
         for shape in a.shape or list(SHAPES) + (list(DEEP) if a.pileup else []):
-            for flags in (0, ca.SW_WANT_INDELS) + ((PATH,) if a.path or a.pileup else ()) + ((PILE,) if a.pileup else ()):
-                rows.append(bench_shape(eng, shape, a.pairs or SHAPES.get(shape) or DEEP.get(shape, 16384), a.per_group, flags, a.steps, a.warmup, a.seed))
+            for flags in (0, ca.SW_WANT_INDELS) + ((PATH,) if a.path or a.pileup else ()) + ((PILE,) if a.pileup else ()) + ((CUT,) if a.cut else ()):
+                rows.append(bench_shape(eng, shape, a.pairs or SHAPES.get(shape) or DEEP.get(shape, 16384), a.per_group, flags, a.steps, a.warmup, a.seed, a.window))
                 print(json.dumps(rows[-1]), flush=True)
     finally:
         eng.close()
     if a.oracle:
         print(json.dumps(oracle_rate(a.oracle, a.threads, a.seed)), flush=True)
     order = ["sw_order", "sw_align", "sw_align_wide", "sw_align_long", "total"] + (["pile_clear"] if a.pileup else [])
-    # a path run's and a pileup run's stages, in the same columns
-    stage_of = {PATH: {"sw_align": "sw_path", "sw_align_wide": "sw_path_wide", "sw_align_long": "sw_path_long"}, PILE: {"sw_align": "pile", "sw_align_wide": "pile_wide", "sw_align_long": "pile_long"}}
+    # a path run's, a pileup run's and a cut run's stages, in the same columns
+    stage_of = {PATH: {"sw_align": "sw_path", "sw_align_wide": "sw_path_wide", "sw_align_long": "sw_path_long"}, PILE: {"sw_align": "pile", "sw_align_wide": "pile_wide", "sw_align_long": "pile_long"},
+                CUT: {"sw_align": "cut", "sw_align_wide": "cut_wide", "sw_align_long": "cut_long"}}
     print("\n| query x reference | indel totals | pairs | ms / batch | pairs/s | DP cells/s | " + " | ".join(order) + " |")
     print("|---|---|---|---|---|---|" + "---|" * len(order))
     for r in rows:
