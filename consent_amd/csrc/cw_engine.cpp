@@ -446,203 +446,210 @@ int poa_device_locked(cw_engine* e, const cw_batch* groups, const cw_result* res
     return enqueue_end(e, st, sc);
 }
 
-/* CW_OK for a batch of groups whose pairs can be aligned -- and for one without sequences; nothing here touches the device */
-int validate_sw(const cw_engine* e, const cw_batch* groups, const int32_t* rows, uint32_t flags) {
-    if (!e || !groups || (flags & ~CW_SW_WANT_INDELS)) return CW_E_INVALID;
+/* ---- the alignment operator's four runs: cw_sw_run, cw_sw_path_run, cw_pileup_run, cw_sw_cut_run (and their _device forms) ------------------------------- */
+
+/* What the four refuse alike, e and groups given: CW_OK for a batch of groups whose pairs can be aligned -- and for one without sequences, before a look at
+   rows; nothing here touches the device.  Each validate_* below keeps its own checks and their place before or behind these. */
+int validate_groups(const cw_engine* e, const cw_batch* groups, const int32_t* rows) {
     if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID; /* cw_max_batch_windows */
     if (groups->n_windows == 0 || groups->n_seqs == 0) return groups->n_seqs == 0 ? CW_OK : CW_E_INVALID; /* (sequences belong to groups) */
     if (!rows || !groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
     return CW_OK;
 }
 
-/* the body of cw_sw_run_device; the caller holds e->mu.  The order of such a run: sw_order (three small launches), then the alignment launches by query class,
-   one after the other on st: sw_align (up to CW_SW_Q0 bases), sw_align_wide (up to CW_ST_QMAX), sw_align_long (beyond: ends at once when there is no such pair;
-   the order kernel's counts stay on the device, so nothing here waits for it).  The plan lives in the engine's one scratch allocation, like a window run's and a
-   POA run's: runs on one engine are serialised by its mutex and ordered on its stream (or by the caller, include/consent_amd.h "Threading"), so none of them is
-   in flight while another's plan is bound.  (stitch_scratch is cw_stitch_device's alone: nothing here touches it.) */
-int run_sw_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, void* hip_stream) {
-    int rc = validate_sw(e, groups, rows, flags);
-    if (rc || groups->n_seqs == 0) return rc;
-    CW_HIP(hipSetDevice(e->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
-    const uint32_t S = groups->n_seqs;
-    const SwPlan p = plan_sw(groups->n_windows, S, groups->n_words, e->cus, flags); /* exact: no run with a larger plan follows */
-    if ((rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) != CW_OK) return rc;
-    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records: the inspection entry points and the re-run loop's look at the last run refuse (cw_debug_win_info, cw_debug_solid_table) or find nothing to do (grow_if_that_helps, decay_scale) */
-    uint8_t* base = (uint8_t*)e->scratch;
-    SwArgs a;
-    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
-    a.n_seqs = S; a.rows = rows; a.flags = flags;
-    a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
-    a.dir = p.dir_bytes ? (int8_t*)(base + p.dir) : nullptr; a.dir_bytes = p.dir_bytes;
-    a.gref = base + p.gref; a.lstate = base + p.lstate;
-    e->n_stages = 0;
-    e->timings_valid = false;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
-    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_SW_CTR_WORDS * 4, st));
-    const uint32_t og = (S + 255u) / 256u;
-    stage(e, st, "sw_order", [&] {
-        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 0);
-        cw_sw_order_kernel<<<1, 256, 0, st>>>(a, 1);
-        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 2);
-    });
-    stage(e, st, "sw_align", [&] { cw_sw_kernel<0><<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(a); });
-    stage(e, st, "sw_align_wide", [&] { cw_sw_kernel<1><<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(a); });
-    stage(e, st, "sw_align_long", [&] { cw_sw_long_kernel<<<p.wgs_long, 64, 0, st>>>(a); });
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
-    return CW_OK;
+int validate_sw(const cw_engine* e, const cw_batch* groups, const int32_t* rows, uint32_t flags) {
+    if (!e || !groups || (flags & ~CW_SW_WANT_INDELS)) return CW_E_INVALID;
+    return validate_groups(e, groups, rows);
 }
 
-/* what cw_sw_path_run and cw_sw_path_run_device refuse, as validate_sw */
 int validate_sw_path(const cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_sw_paths* paths, uint32_t flags) {
     if (!e || !groups || !paths || (flags & ~CW_SW_PATH_EQX)) return CW_E_INVALID;
-    if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
-    if (groups->n_windows == 0 || groups->n_seqs == 0) return groups->n_seqs == 0 ? CW_OK : CW_E_INVALID;
-    if (!rows || !groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
+    const int rc = validate_groups(e, groups, rows);
+    if (rc || groups->n_seqs == 0) return rc;
     if (!paths->ops || !paths->ops_off || !paths->n_ops) return CW_E_INVALID;
     return CW_OK;
 }
 
-/* the body of cw_sw_path_run_device, in the shape of run_sw_locked: sw_order, then sw_path, sw_path_wide, sw_path_long one after the other on st; the plan is
-   exact and lives in the engine's one scratch allocation. */
-int run_sw_path_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream) {
-    int rc = validate_sw_path(e, groups, rows, paths, flags);
-    if (rc || groups->n_seqs == 0) return rc;
+/* (the pileup and cut runs refuse a missing output for a batch without sequences too) */
+int validate_pileup(const cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_pileup* pile, uint32_t flags) {
+    if (!e || !groups || !pile || (flags & ~CW_PILE_ACCUMULATE)) return CW_E_INVALID;
+    if (!rows || !pile->counts || !pile->col_off) return CW_E_INVALID;
+    return validate_groups(e, groups, rows);
+}
+
+int validate_sw_cut(const cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_sw_cuts* cuts) {
+    if (!e || !groups || !cuts) return CW_E_INVALID;
+    if (!rows || !cuts->cuts || !cuts->cut_off || cuts->window == 0u) return CW_E_INVALID;
+    return validate_groups(e, groups, rows);
+}
+
+/* The device, the stream and the plan's bytes of a run.  The plan lives in the engine's one scratch allocation, like a window run's and a POA run's: runs on one
+   engine are serialised by its mutex and ordered on its stream (or by the caller, include/consent_amd.h "Threading"), so none of them is in flight while
+   another's plan is bound.  (stitch_scratch is cw_stitch_device's alone: nothing here touches it.) */
+int hold_sw(cw_engine* e, size_t total, void* hip_stream, hipStream_t* st) {
     CW_HIP(hipSetDevice(e->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
-    const uint32_t S = groups->n_seqs;
-    const SwPathPlan p = plan_sw_path(groups->n_windows, S, groups->n_words, e->cus);
-    if ((rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) != CW_OK) return rc;
-    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (run_sw_locked) */
+    *st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    return ensure(&e->scratch, &e->scratch_bytes, total);
+}
+
+/* the arguments every kernel of the four runs takes, by the plan's offsets (a path plan is a plan and the steps) */
+SwArgs bind_sw(const cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, const SwPlan& p) {
     uint8_t* base = (uint8_t*)e->scratch;
-    SwPathArgs pa;
-    SwArgs& a = pa.a;
+    SwArgs a;
     a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
-    a.n_seqs = S; a.rows = rows; a.flags = flags;
+    a.n_seqs = groups->n_seqs; a.rows = rows; a.flags = flags;
     a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
-    a.dir = (int8_t*)(base + p.dir); a.dir_bytes = p.dir_bytes;
+    a.dir = p.dir_bytes ? (int8_t*)(base + p.dir) : nullptr; a.dir_bytes = p.dir_bytes;
     a.gref = base + p.gref; a.lstate = base + p.lstate;
-    pa.ops = paths->ops; pa.ops_off = paths->ops_off; pa.n_ops = paths->n_ops; pa.steps = base + p.steps;
+    return a;
+}
+
+/* a run's three alignment stages: their names and kernels, by query class */
+template <class Args>
+struct SwStages { const char* names[3]; void (*k0)(Args); void (*k1)(Args); void (*k_long)(Args); };
+
+/* what one run or another adds around the order stage; all absent for the plain run */
+struct SwExtras {
+    uint32_t* zero = nullptr;       /* the path run: n_seqs words to clear behind the counters (n_ops: rows the order kernel writes, and pairs without a path) */
+    const CutArgs* rest = nullptr;  /* the cut run: cw_sw_cut_rest_kernel inside the order stage */
+    const PileArgs* clear = nullptr; /* the pileup run unless it accumulates: the pile_clear stage behind the order stage */
+};
+
+/* The order of a run: sw_order (three small launches, and the cut run's fourth), pile_clear when asked for, then the alignment launches by query class, one
+   after the other on st: up to CW_SW_Q0 bases, up to CW_ST_QMAX, beyond (ends at once when there is no such pair; the order kernel's counts stay on the device,
+   so nothing here waits for it). */
+template <class Args>
+int enqueue_sw_run(cw_engine* e, hipStream_t st, const SwArgs& a, const SwPlan& p, const SwStages<Args>& k, const Args& args, const SwExtras& x = SwExtras()) {
+    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records: the inspection entry points and the re-run loop's look at the last run refuse (cw_debug_win_info, cw_debug_solid_table) or find nothing to do (grow_if_that_helps, decay_scale) */
     e->n_stages = 0;
     e->timings_valid = false;
     CW_HIP(hipEventRecord(e->ev_begin, st));
     CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_SW_CTR_WORDS * 4, st));
-    CW_HIP(hipMemsetAsync(pa.n_ops, 0, (size_t)S * 4, st)); /* rows the order kernel writes, and pairs without a path */
-    const uint32_t og = (S + 255u) / 256u;
+    if (x.zero) CW_HIP(hipMemsetAsync(x.zero, 0, (size_t)a.n_seqs * 4, st));
+    const uint32_t og = (a.n_seqs + 255u) / 256u;
     stage(e, st, "sw_order", [&] {
         cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 0);
         cw_sw_order_kernel<<<1, 256, 0, st>>>(a, 1);
         cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 2);
+        if (x.rest) cw_sw_cut_rest_kernel<<<og, 256, 0, st>>>(*x.rest);
     });
-    stage(e, st, "sw_path", [&] { cw_sw_path_kernel<0><<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(pa); });
-    stage(e, st, "sw_path_wide", [&] { cw_sw_path_kernel<1><<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(pa); });
-    stage(e, st, "sw_path_long", [&] { cw_sw_path_long_kernel<<<p.wgs_long, 64, 0, st>>>(pa); });
+    if (x.clear) stage(e, st, "pile_clear", [&] { cw_pileup_clear_kernel<<<a.b.n_windows, 256, 0, st>>>(*x.clear); });
+    stage(e, st, k.names[0], [&] { k.k0<<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(args); });
+    stage(e, st, k.names[1], [&] { k.k1<<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(args); });
+    stage(e, st, k.names[2], [&] { k.k_long<<<p.wgs_long, 64, 0, st>>>(args); });
     CW_HIP(hipEventRecord(e->ev_end, st));
     CW_HIP(hipGetLastError());
     e->timings_valid = true;
     return CW_OK;
 }
 
-/* what cw_pileup_run and cw_pileup_run_device refuse, as validate_sw_path */
-int validate_pileup(const cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_pileup* pile, uint32_t flags) {
-    if (!e || !groups || !pile || (flags & ~CW_PILE_ACCUMULATE)) return CW_E_INVALID;
-    if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
-    if (!rows || !pile->counts || !pile->col_off) return CW_E_INVALID;
-    if (groups->n_windows == 0 || groups->n_seqs == 0) return groups->n_seqs == 0 ? CW_OK : CW_E_INVALID;
-    if (!groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
-    return CW_OK;
+/* the body of cw_sw_run_device; the caller holds e->mu.  Stages: sw_order, sw_align, sw_align_wide, sw_align_long. */
+int run_sw_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, void* hip_stream) {
+    int rc = validate_sw(e, groups, rows, flags);
+    if (rc || groups->n_seqs == 0) return rc;
+    const SwPlan p = plan_sw(groups->n_windows, groups->n_seqs, groups->n_words, e->cus, flags); /* exact: no run with a larger plan follows */
+    hipStream_t st;
+    if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
+    const SwArgs a = bind_sw(e, groups, rows, flags, p);
+    return enqueue_sw_run(e, st, a, p, SwStages<SwArgs>{{"sw_align", "sw_align_wide", "sw_align_long"}, cw_sw_kernel<0>, cw_sw_kernel<1>, cw_sw_long_kernel}, a);
 }
 
-/* the body of cw_pileup_run_device, in the shape of run_sw_path_locked: sw_order, pile_clear unless the run accumulates, then pile, pile_wide, pile_long one
-   after the other on st; the plan is plan_sw_path's -- there is no op memory to add -- and lives in the engine's one scratch allocation. */
+/* the body of cw_sw_path_run_device.  Stages: sw_order, sw_path, sw_path_wide, sw_path_long. */
+int run_sw_path_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream) {
+    int rc = validate_sw_path(e, groups, rows, paths, flags);
+    if (rc || groups->n_seqs == 0) return rc;
+    const SwPathPlan p = plan_sw_path(groups->n_windows, groups->n_seqs, groups->n_words, e->cus);
+    hipStream_t st;
+    if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
+    SwPathArgs pa;
+    pa.a = bind_sw(e, groups, rows, flags, p);
+    pa.ops = paths->ops; pa.ops_off = paths->ops_off; pa.n_ops = paths->n_ops; pa.steps = (uint8_t*)e->scratch + p.steps;
+    SwExtras x;
+    x.zero = pa.n_ops;
+    return enqueue_sw_run(e, st, pa.a, p, SwStages<SwPathArgs>{{"sw_path", "sw_path_wide", "sw_path_long"}, cw_sw_path_kernel<0>, cw_sw_path_kernel<1>, cw_sw_path_long_kernel}, pa, x);
+}
+
+/* the body of cw_pileup_run_device.  Stages: sw_order, pile_clear unless the run accumulates, pile, pile_wide, pile_long.  The plan is plan_sw_path's: there is
+   no op memory to add. */
 int run_pileup_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream) {
     int rc = validate_pileup(e, groups, rows, pile, flags);
     if (rc || groups->n_seqs == 0) return rc;
     if ((uintptr_t)pile->counts & 15u) return CW_E_INVALID; /* the clearing stores 16 bytes at a time */
-    CW_HIP(hipSetDevice(e->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
-    const uint32_t S = groups->n_seqs;
-    const SwPathPlan p = plan_sw_path(groups->n_windows, S, groups->n_words, e->cus);
-    if ((rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) != CW_OK) return rc;
-    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (run_sw_locked) */
-    uint8_t* base = (uint8_t*)e->scratch;
+    const SwPathPlan p = plan_sw_path(groups->n_windows, groups->n_seqs, groups->n_words, e->cus);
+    hipStream_t st;
+    if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
     PileArgs pa;
-    SwArgs& a = pa.a;
-    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
-    a.n_seqs = S; a.rows = rows; a.flags = flags;
-    a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
-    a.dir = (int8_t*)(base + p.dir); a.dir_bytes = p.dir_bytes;
-    a.gref = base + p.gref; a.lstate = base + p.lstate;
-    pa.counts = pile->counts; pa.col_off = pile->col_off; pa.steps = base + p.steps;
-    e->n_stages = 0;
-    e->timings_valid = false;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
-    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_SW_CTR_WORDS * 4, st));
-    const uint32_t og = (S + 255u) / 256u;
-    stage(e, st, "sw_order", [&] {
-        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 0);
-        cw_sw_order_kernel<<<1, 256, 0, st>>>(a, 1);
-        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 2);
-    });
-    if (!(flags & CW_PILE_ACCUMULATE)) stage(e, st, "pile_clear", [&] { cw_pileup_clear_kernel<<<groups->n_windows, 256, 0, st>>>(pa); });
-    stage(e, st, "pile", [&] { cw_pileup_kernel<0><<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(pa); });
-    stage(e, st, "pile_wide", [&] { cw_pileup_kernel<1><<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(pa); });
-    stage(e, st, "pile_long", [&] { cw_pileup_long_kernel<<<p.wgs_long, 64, 0, st>>>(pa); });
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
-    return CW_OK;
+    pa.a = bind_sw(e, groups, rows, flags, p);
+    pa.counts = pile->counts; pa.col_off = pile->col_off; pa.steps = (uint8_t*)e->scratch + p.steps;
+    SwExtras x;
+    if (!(flags & CW_PILE_ACCUMULATE)) x.clear = &pa;
+    return enqueue_sw_run(e, st, pa.a, p, SwStages<PileArgs>{{"pile", "pile_wide", "pile_long"}, cw_pileup_kernel<0>, cw_pileup_kernel<1>, cw_pileup_long_kernel}, pa, x);
 }
 
-/* what cw_sw_cut_run and cw_sw_cut_run_device refuse, as validate_pileup */
-int validate_sw_cut(const cw_engine* e, const cw_batch* groups, const int32_t* rows, const cw_sw_cuts* cuts) {
-    if (!e || !groups || !cuts) return CW_E_INVALID;
-    if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID;
-    if (!rows || !cuts->cuts || !cuts->cut_off || cuts->window == 0u) return CW_E_INVALID;
-    if (groups->n_windows == 0 || groups->n_seqs == 0) return groups->n_seqs == 0 ? CW_OK : CW_E_INVALID;
-    if (!groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
-    return CW_OK;
-}
-
-/* the body of cw_sw_cut_run_device, in the shape of run_pileup_locked: sw_order -- with it the zeros of the queries that are no pair -- then cut, cut_wide,
-   cut_long one after the other on st; the plan is plan_sw_path's and lives in the engine's one scratch allocation. */
+/* the body of cw_sw_cut_run_device.  Stages: sw_order -- with it the zeros of the queries that are no pair -- cut, cut_wide, cut_long.  The plan is
+   plan_sw_path's. */
 int run_sw_cut_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, void* hip_stream) {
     int rc = validate_sw_cut(e, groups, rows, cuts);
     if (rc || groups->n_seqs == 0) return rc;
-    CW_HIP(hipSetDevice(e->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
-    const uint32_t S = groups->n_seqs;
-    const SwPathPlan p = plan_sw_path(groups->n_windows, S, groups->n_words, e->cus);
-    if ((rc = ensure(&e->scratch, &e->scratch_bytes, p.total)) != CW_OK) return rc;
-    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (run_sw_locked) */
-    uint8_t* base = (uint8_t*)e->scratch;
+    const SwPathPlan p = plan_sw_path(groups->n_windows, groups->n_seqs, groups->n_words, e->cus);
+    hipStream_t st;
+    if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
     CutArgs ca;
-    SwArgs& a = ca.a;
-    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
-    a.n_seqs = S; a.rows = rows; a.flags = 0u;
-    a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
-    a.dir = (int8_t*)(base + p.dir); a.dir_bytes = p.dir_bytes;
-    a.gref = base + p.gref; a.lstate = base + p.lstate;
-    ca.cuts = cuts->cuts; ca.cut_off = cuts->cut_off; ca.window = cuts->window; ca.steps = base + p.steps;
-    e->n_stages = 0;
-    e->timings_valid = false;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
-    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_SW_CTR_WORDS * 4, st));
-    const uint32_t og = (S + 255u) / 256u;
-    stage(e, st, "sw_order", [&] {
-        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 0);
-        cw_sw_order_kernel<<<1, 256, 0, st>>>(a, 1);
-        cw_sw_order_kernel<<<og, 256, 0, st>>>(a, 2);
-        cw_sw_cut_rest_kernel<<<og, 256, 0, st>>>(ca);
-    });
-    stage(e, st, "cut", [&] { cw_sw_cut_kernel<0><<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(ca); });
-    stage(e, st, "cut_wide", [&] { cw_sw_cut_kernel<1><<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(ca); });
-    stage(e, st, "cut_long", [&] { cw_sw_cut_long_kernel<<<p.wgs_long, 64, 0, st>>>(ca); });
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
+    ca.a = bind_sw(e, groups, rows, 0u, p);
+    ca.cuts = cuts->cuts; ca.cut_off = cuts->cut_off; ca.window = cuts->window; ca.steps = (uint8_t*)e->scratch + p.steps;
+    SwExtras x;
+    x.rest = &ca;
+    return enqueue_sw_run(e, st, ca.a, p, SwStages<CutArgs>{{"cut", "cut_wide", "cut_long"}, cw_sw_cut_kernel<0>, cw_sw_cut_kernel<1>, cw_sw_cut_long_kernel}, ca, x);
+}
+
+/* What the four host-buffer entry points check first: the groups begin at sequence 0, end at n_seqs and never step back, every sequence lies inside n_words, and
+   the run's slot offsets slot_off[0 .. n_seqs], when it has some, never step back. */
+int check_groups(const cw_batch* b, const uint64_t* slot_off, std::vector<uint64_t>* rebased) {
+    const uint32_t G = b->n_windows, S = b->n_seqs;
+    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
+    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
+    for (uint32_t s = 0; s < S; ++s) {
+        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
+        if (slot_off && slot_off[s + 1] < slot_off[s]) return CW_E_INVALID;
+    }
+    if (slot_off) { /* rebased to the first slot: the device copy of the slots begins there */
+        try { rebased->resize((size_t)S + 1); } catch (...) { return CW_E_NOMEM; }
+        for (uint32_t s = 0; s <= S; ++s) (*rebased)[s] = slot_off[s] - slot_off[0];
+    }
+    return CW_OK;
+}
+
+/* The checked batch goes up, on the engine's stream: into the engine's input buffer (the one cw_poa_run uses for its own), every array 256-byte aligned, and
+   behind it the slot offsets rebased to the first slot -- the device copy of the slots begins there.  *db: the batch with device pointers; *rebased: the rebased
+   offsets on the host, which must live until the stream is synchronised; *d_off: the same on the device.  An entry point calls this last before the run: its own
+   host allocations and its output buffer are in place by then, so behind the first copy enqueued here it returns early only as it always did, when the run
+   itself fails. */
+int upload_groups(cw_engine* e, const cw_batch* b, const std::vector<uint64_t>* rebased, cw_batch* db, const uint64_t** d_off) {
+    const uint32_t G = b->n_windows, S = b->n_seqs;
+    size_t o = 0;
+    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
+                 i_soff = rebased ? put((size_t)(S + 1) * 8) : 0;
+    if (int rc = ensure(&e->poa_in, &e->poa_in_bytes, o)) return rc;
+    uint8_t* din = (uint8_t*)e->poa_in;
+    hipStream_t st = e->stream;
+    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
+    if (rebased) {
+        CW_HIP(hipMemcpyAsync(din + i_soff, rebased->data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
+        *d_off = (const uint64_t*)(din + i_soff);
+    }
+    *db = *b;
+    db->win_first_seq = (const uint32_t*)(din + i_wfs); db->seq_len = (const uint32_t*)(din + i_len);
+    db->seq_word_off = (const uint64_t*)(din + i_off); db->bases = (const uint32_t*)(din + i_bases);
+    return CW_OK;
+}
+
+/* what a host-buffer entry point answers for the rows that came back: CW_E_CAPACITY when a pair was beyond a capacity */
+int sw_rows_rc(const int32_t* rows, uint32_t n_seqs) {
+    for (uint32_t s = 0; s < n_seqs; ++s) if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) return CW_E_CAPACITY;
     return CW_OK;
 }
 
@@ -805,39 +812,25 @@ int cw_sw_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32
     return run_sw_locked(e, groups, rows, flags, hip_stream);
 }
 
-/* Host buffers in, host buffers out, synchronous: the batch goes up (into the buffer cw_poa_run uses for its own), cw_sw_run_device on the engine's stream, the
-   rows come back.  The engine's mutex is held throughout: the device buffers are the engine's. */
+/* Host buffers in, host buffers out, synchronous: the batch goes up (upload_groups), cw_sw_run_device on the engine's stream, the rows come back.  The engine's
+   mutex is held throughout: the device buffers are the engine's. */
 int cw_sw_run(cw_engine* e, const cw_batch* b, int32_t* rows, uint32_t flags) {
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
     int rc = validate_sw(e, b, rows, flags);
     if (rc || b->n_seqs == 0) return rc;
-    const uint32_t G = b->n_windows, S = b->n_seqs;
-    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
-    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
-    for (uint32_t s = 0; s < S; ++s)
-        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
-    size_t o = 0;
-    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4);
-    const size_t in_bytes = o, out_bytes = (size_t)S * CW_SW_ROW * 4;
+    const uint32_t S = b->n_seqs;
+    cw_batch db;
+    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
+    const size_t out_bytes = (size_t)S * CW_SW_ROW * 4;
     CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
     if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    uint8_t* din = (uint8_t*)e->poa_in;
+    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
     hipStream_t st = e->stream;
-    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
-    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
-    cw_batch db = *b;
-    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
-    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
     if ((rc = run_sw_locked(e, &db, (int32_t*)e->poa_out, flags, st)) != CW_OK) return rc;
     CW_HIP(hipMemcpyAsync(rows, e->poa_out, out_bytes, hipMemcpyDeviceToHost, st));
     CW_HIP(hipStreamSynchronize(st));
-    for (uint32_t s = 0; s < S; ++s) if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) rc = CW_E_CAPACITY;
-    return rc;
+    return sw_rows_rc(rows, S);
 }
 
 int cw_sw_path_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream) {
@@ -853,53 +846,32 @@ int cw_sw_path_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_p
     std::lock_guard<std::mutex> lk(e->mu);
     int rc = validate_sw_path(e, b, rows, paths, flags);
     if (rc || b->n_seqs == 0) return rc;
-    const uint32_t G = b->n_windows, S = b->n_seqs;
-    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
-    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
-    for (uint32_t s = 0; s < S; ++s) {
-        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
-        if (paths->ops_off[s + 1] < paths->ops_off[s]) return CW_E_INVALID;
-    }
-    const uint64_t p0 = paths->ops_off[0], n_slots = paths->ops_off[S] - p0; /* the device copy begins at the first slot */
+    const uint32_t S = b->n_seqs;
+    cw_batch db;
+    std::vector<uint64_t> poff;
+    cw_sw_paths dp;
+    if ((rc = check_groups(b, paths->ops_off, &poff)) != CW_OK) return rc;
+    const uint64_t n_slots = poff[S];
     size_t o = 0;
     auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
-                 i_poff = put((size_t)(S + 1) * 8);
-    const size_t in_bytes = o;
-    o = 0;
     const size_t o_rows = put((size_t)S * CW_SW_ROW * 4), o_nops = put((size_t)S * 4), o_ops = put((size_t)n_slots * 4);
-    const size_t out_bytes = o;
-    std::vector<uint64_t> poff;
     std::vector<uint32_t> back;
-    try { poff.resize((size_t)S + 1); back.resize((size_t)n_slots); } catch (...) { return CW_E_NOMEM; }
-    for (uint32_t s = 0; s <= S; ++s) poff[s] = paths->ops_off[s] - p0;
+    try { back.resize((size_t)n_slots); } catch (...) { return CW_E_NOMEM; }
     CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    uint8_t *din = (uint8_t*)e->poa_in, *dout = (uint8_t*)e->poa_out;
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, o)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, &poff, &db, &dp.ops_off)) != CW_OK) return rc;
+    uint8_t* dout = (uint8_t*)e->poa_out;
     hipStream_t st = e->stream;
-    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
-    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_poff, poff.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
-    cw_batch db = *b;
-    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
-    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
-    cw_sw_paths dp;
-    dp.ops = (uint32_t*)(dout + o_ops); dp.ops_off = (const uint64_t*)(din + i_poff); dp.n_ops = (uint32_t*)(dout + o_nops);
+    dp.ops = (uint32_t*)(dout + o_ops); dp.n_ops = (uint32_t*)(dout + o_nops);
     if ((rc = run_sw_path_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st)) != CW_OK) return rc;
     CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
     CW_HIP(hipMemcpyAsync(paths->n_ops, dout + o_nops, (size_t)S * 4, hipMemcpyDeviceToHost, st));
     if (n_slots) CW_HIP(hipMemcpyAsync(back.data(), dout + o_ops, (size_t)n_slots * 4, hipMemcpyDeviceToHost, st));
     CW_HIP(hipStreamSynchronize(st));
-    for (uint32_t s = 0; s < S; ++s) {
-        const int status = rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS];
-        if (status == CW_SW_STOP) rc = CW_E_CAPACITY;
-        if (status == CW_SW_ALIGNED && paths->n_ops[s] && paths->n_ops[s] <= poff[s + 1] - poff[s])
+    for (uint32_t s = 0; s < S; ++s)
+        if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_ALIGNED && paths->n_ops[s] && paths->n_ops[s] <= poff[s + 1] - poff[s])
             memcpy(paths->ops + paths->ops_off[s], back.data() + poff[s], (size_t)paths->n_ops[s] * 4);
-    }
-    return rc;
+    return sw_rows_rc(rows, S);
 }
 
 int cw_pileup_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream) {
@@ -917,61 +889,39 @@ int cw_pileup_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileu
     int rc = validate_pileup(e, b, rows, pile, flags);
     if (rc || b->n_seqs == 0) return rc;
     const uint32_t G = b->n_windows, S = b->n_seqs;
-    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
-    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
-    for (uint32_t s = 0; s < S; ++s) {
-        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
-        if (pile->col_off[s + 1] < pile->col_off[s]) return CW_E_INVALID;
-    }
-    const uint64_t c0 = pile->col_off[0], n_cols = pile->col_off[S] - c0; /* the device copy begins at the first slot */
+    cw_batch db;
+    std::vector<uint64_t> coff;
+    cw_pileup dp;
+    if ((rc = check_groups(b, pile->col_off, &coff)) != CW_OK) return rc;
+    const uint64_t c0 = pile->col_off[0], n_cols = coff[S];
     const size_t col_bytes = (size_t)CW_PILE_COL * 4;
     size_t o = 0;
     auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
-                 i_coff = put((size_t)(S + 1) * 8);
-    const size_t in_bytes = o;
-    o = 0;
     const size_t o_rows = put((size_t)S * CW_SW_ROW * 4), o_counts = put((size_t)n_cols * col_bytes);
-    const size_t out_bytes = o;
-    std::vector<uint64_t> coff;
     std::vector<uint32_t> back;
-    try { coff.resize((size_t)S + 1); back.resize((size_t)n_cols * CW_PILE_COL); } catch (...) { return CW_E_NOMEM; }
-    for (uint32_t s = 0; s <= S; ++s) coff[s] = pile->col_off[s] - c0;
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    uint8_t *din = (uint8_t*)e->poa_in, *dout = (uint8_t*)e->poa_out;
-    hipStream_t st = e->stream;
-    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
-    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_coff, coff.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
-    /* the references whose columns the run owns: (sequence, columns) */
-    std::vector<std::pair<uint32_t, uint32_t>> owned;
+    std::vector<std::pair<uint32_t, uint32_t>> owned; /* the references whose columns the run owns: (sequence, columns) */
     try {
+        back.resize((size_t)n_cols * CW_PILE_COL);
         for (uint32_t g = 0; g < G; ++g) {
             const uint32_t r = b->win_first_seq[g];
             if (r < b->win_first_seq[g + 1] && b->seq_len[r] && coff[r + 1] - coff[r] >= b->seq_len[r]) owned.emplace_back(r, b->seq_len[r]);
         }
     } catch (...) { return CW_E_NOMEM; }
-    uint32_t* const dcounts = (uint32_t*)(dout + o_counts);
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, o)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, &coff, &db, &dp.col_off)) != CW_OK) return rc;
+    uint8_t* dout = (uint8_t*)e->poa_out;
+    hipStream_t st = e->stream;
+    dp.counts = (uint32_t*)(dout + o_counts);
     if ((flags & CW_PILE_ACCUMULATE) && n_cols) /* every slot in one copy; the run reads and writes the owned columns only */
-        CW_HIP(hipMemcpyAsync(dcounts, pile->counts + c0 * CW_PILE_COL, (size_t)n_cols * col_bytes, hipMemcpyHostToDevice, st));
-    cw_batch db = *b;
-    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
-    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
-    cw_pileup dp;
-    dp.counts = dcounts; dp.col_off = (const uint64_t*)(din + i_coff);
+        CW_HIP(hipMemcpyAsync(dp.counts, pile->counts + c0 * CW_PILE_COL, (size_t)n_cols * col_bytes, hipMemcpyHostToDevice, st));
     if ((rc = run_pileup_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st)) != CW_OK) return rc;
     CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
-    if (n_cols) CW_HIP(hipMemcpyAsync(back.data(), dcounts, (size_t)n_cols * col_bytes, hipMemcpyDeviceToHost, st));
+    if (n_cols) CW_HIP(hipMemcpyAsync(back.data(), dp.counts, (size_t)n_cols * col_bytes, hipMemcpyDeviceToHost, st));
     CW_HIP(hipStreamSynchronize(st));
     for (const auto& rn : owned)
         memcpy(pile->counts + pile->col_off[rn.first] * CW_PILE_COL, back.data() + coff[rn.first] * CW_PILE_COL, (size_t)rn.second * col_bytes);
-    for (uint32_t s = 0; s < S; ++s)
-        if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) rc = CW_E_CAPACITY;
-    return rc;
+    return sw_rows_rc(rows, S);
 }
 
 int cw_sw_cut_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, void* hip_stream) {
@@ -989,27 +939,18 @@ int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cu
     int rc = validate_sw_cut(e, b, rows, cuts);
     if (rc || b->n_seqs == 0) return rc;
     const uint32_t G = b->n_windows, S = b->n_seqs, W = cuts->window;
-    if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
-    for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
-    for (uint32_t s = 0; s < S; ++s) {
-        if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
-        if (cuts->cut_off[s + 1] < cuts->cut_off[s]) return CW_E_INVALID;
-    }
-    const uint64_t c0 = cuts->cut_off[0], n_slots = cuts->cut_off[S] - c0; /* the device copy begins at the first slot */
+    cw_batch db;
+    std::vector<uint64_t> coff;
+    cw_sw_cuts dc;
+    if ((rc = check_groups(b, cuts->cut_off, &coff)) != CW_OK) return rc;
+    const uint64_t n_slots = coff[S];
     size_t o = 0;
     auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
-                 i_coff = put((size_t)(S + 1) * 8);
-    const size_t in_bytes = o;
-    o = 0;
     const size_t o_rows = put((size_t)S * CW_SW_ROW * 4), o_cuts = put((size_t)n_slots * 4);
-    const size_t out_bytes = o;
-    std::vector<uint64_t> coff;
     std::vector<uint32_t> back;
     std::vector<std::pair<uint32_t, uint32_t>> owned; /* the queries whose words the run owns: (sequence, words) */
     try {
-        coff.resize((size_t)S + 1); back.resize((size_t)n_slots);
-        for (uint32_t s = 0; s <= S; ++s) coff[s] = cuts->cut_off[s] - c0;
+        back.resize((size_t)n_slots);
         for (uint32_t g = 0; g < G; ++g) {
             const uint32_t r = b->win_first_seq[g], end = b->win_first_seq[g + 1];
             if (r >= end) continue;
@@ -1018,20 +959,11 @@ int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cu
         }
     } catch (...) { return CW_E_NOMEM; }
     CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    uint8_t *din = (uint8_t*)e->poa_in, *dout = (uint8_t*)e->poa_out;
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, o)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, &coff, &db, &dc.cut_off)) != CW_OK) return rc;
+    uint8_t* dout = (uint8_t*)e->poa_out;
     hipStream_t st = e->stream;
-    CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
-    if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
-    CW_HIP(hipMemcpyAsync(din + i_coff, coff.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
-    cw_batch db = *b;
-    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
-    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
-    cw_sw_cuts dc;
-    dc.cuts = (uint32_t*)(dout + o_cuts); dc.cut_off = (const uint64_t*)(din + i_coff); dc.window = W;
+    dc.cuts = (uint32_t*)(dout + o_cuts); dc.window = W;
     if ((rc = run_sw_cut_locked(e, &db, (int32_t*)(dout + o_rows), &dc, st)) != CW_OK) return rc;
     CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
     if (n_slots) CW_HIP(hipMemcpyAsync(back.data(), dc.cuts, (size_t)n_slots * 4, hipMemcpyDeviceToHost, st));
@@ -1039,9 +971,7 @@ int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cu
     for (const auto& sw : owned)
         if (rows[(size_t)sw.first * CW_SW_ROW + CW_SW_STATUS] != CW_SW_CUT_SLOT)
             memcpy(cuts->cuts + cuts->cut_off[sw.first], back.data() + coff[sw.first], (size_t)sw.second * 4);
-    for (uint32_t s = 0; s < S; ++s)
-        if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) rc = CW_E_CAPACITY;
-    return rc;
+    return sw_rows_rc(rows, S);
 }
 
 /* One work-group sizes the output groups of every input group, a wave per output group counts its members and words, one work-group scans; the totals come to

@@ -1,8 +1,8 @@
 /*
  * cw_pileup.h -- the alignment operator's pileup run (cw_pileup_run / cw_pileup_run_device, include/consent_amd.h): per pair the row of cw_sw_path_run, and
  * instead of the path's ops what the paths say about the reference: eight counts per reference column (A, C, G, T, deletions, insertion events after it,
- * alignments that begin and that end on it).  The order kernel, the unpacking, sw_align<CLS>, sw_banded_path and sw_walk are those of cw_sw_op.h and
- * cw_sw_path.h, unedited; the kernels keep the launch bounds, LDS slabs, per-wave scratch and pair-claim loop of the three path kernels.  New are:
+ * alignments that begin and that end on it).  The kernels are calls of cw_sw_op.h's sw_class_loop / sw_long_loop (LDS slabs, per-wave scratch, pair-claim loop,
+ * under the launch bounds of the path kernels) around pile_pair, which follows sw_path_pair line by line up to the closed walk.  The run's own are:
  *
  *   cw_pileup_clear_kernel  one work-group per group: columns 0 .. ref_len - 1 of the group's reference, where its slot holds them, in 16-byte stores (two a
  *                           column).  Not launched under CW_PILE_ACCUMULATE.
@@ -99,53 +99,17 @@ __device__ __forceinline__ void pile_pair(const PileArgs& pa, uint32_t s, uint8_
     st_mem_sync(); /* the next pair's unpacking overwrites what this one read */
 }
 
-/* the launch bounds and LDS slabs of cw_sw_path_kernel<CLS> */
 template <int CLS>
 __global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_pileup_kernel(PileArgs pa) {
-    constexpr int QMAX = CLS == 0 ? CW_SW_Q0 : CW_ST_QMAX;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint8_t* const slab = lds + (size_t)wave * CW_SW_SLAB_OF(QMAX);
-    uint8_t* const ref_lds = slab;
-    uint8_t* const qfw = ref_lds + CW_ST_RMAX;
-    uint8_t* const qrv = qfw + QMAX;
-    uint8_t* const rows = qrv + QMAX;
-    const size_t wv = (size_t)blockIdx.x * CW_SW_WAVES + wave;
-    uint8_t* const ref_glb = pa.a.gref + wv * CW_SW_GREF_BYTES;
-    uint8_t* const dirbuf = (uint8_t*)pa.a.dir + wv * pa.a.dir_bytes;
-    uint8_t* const steps = pa.steps + wv * CW_SW_STEP_BYTES;
-    const uint32_t n_pairs = st_uni(pa.a.ctr[3 + CLS]), base = CLS == 0 ? 0u : st_uni(pa.a.ctr[3]);
-    for (;;) {
-        uint32_t pi = 0;
-        if (lane == 0) pi = atomicAdd(pa.a.ctr + CLS, 1u);
-        pi = (uint32_t)cw_lane_value((int)pi, 0);
-        if (pi >= n_pairs) break;
-        const uint32_t s = st_uni(pa.a.order[base + pi]);
-        const uint32_t n = st_uni(pa.a.b.seq_len[st_uni(pa.a.seq_ref[s])]);
-        pile_pair<CLS>(pa, s, n <= (uint32_t)CW_ST_RMAX ? ref_lds : ref_glb, qfw, qrv, (uint32_t)QMAX, true, rows, dirbuf, steps, nullptr, lane);
-    }
+    sw_class_loop<CLS, true>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        pile_pair<CLS>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+    });
 }
 
 __global__ void __launch_bounds__(64, 2) cw_pileup_long_kernel(PileArgs pa) {
-    __shared__ __attribute__((aligned(16))) uint8_t rows[CW_ST_ROWS_BYTES];
-    const int lane = threadIdx.x & 63;
-    const uint32_t n_pairs = st_uni(pa.a.ctr[5]);
-    if (n_pairs == 0u) return; /* normally */
-    const uint32_t base = st_uni(pa.a.ctr[3]) + st_uni(pa.a.ctr[4]);
-    uint8_t* const mem = pa.a.lstate + (size_t)blockIdx.x * CW_SW_LONG_WAVE_BYTES;
-    uint8_t* const refc = mem;
-    uint8_t* const qfw = refc + CW_SW_GREF_BYTES;
-    uint8_t* const qrv = qfw + CW_STH_QMAX;
-    uint8_t* const state = qrv + CW_STH_QMAX;
-    uint8_t* const dirbuf = (uint8_t*)pa.a.dir + (size_t)blockIdx.x * pa.a.dir_bytes;
-    uint8_t* const steps = pa.steps + (size_t)blockIdx.x * CW_SW_STEP_BYTES;
-    for (;;) {
-        uint32_t pi = 0;
-        if (lane == 0) pi = atomicAdd(pa.a.ctr + 2, 1u);
-        pi = (uint32_t)cw_lane_value((int)pi, 0);
-        if (pi >= n_pairs) break;
-        pile_pair<2>(pa, st_uni(pa.a.order[base + pi]), refc, qfw, qrv, 0u, false, rows, dirbuf, steps, state, lane);
-    }
+    sw_long_loop<true>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        pile_pair<2>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+    });
 }
 
 #endif

@@ -225,10 +225,7 @@ static inline SwPlan plan_sw(uint32_t n_groups, uint32_t n_seqs, uint64_t n_word
    and per wave of the largest grid the traceback's CW_SW_PATH_BYTES (directions, a byte a cell, and the rows once they outgrow LDS) and the walk's
    CW_SW_STEP_BYTES.  Exact, like plan_sw.  The grids stop where the direction scratch of a run reaches what plan_sw holds under CW_SW_WANT_INDELS:
    CW_SW_PATH_MAX_WAVES waves x 2 MiB = 1 GiB, so class 0 and class 1 launch at most 128 work-groups of four waves, the long launch its 256 of one. */
-struct SwPathPlan {
-    size_t ctr, seq_ref, order, gref, lstate, dir, steps, total;
-    uint32_t wgs0, wgs1, wgs_long, dir_waves, dir_bytes;
-};
+struct SwPathPlan : SwPlan { size_t steps; }; /* a plan and the steps: what binds and launches a plain run binds and launches this one */
 static inline SwPathPlan plan_sw_path(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus) {
     (void)n_groups; (void)n_words;
     SwPathPlan p;

@@ -2,9 +2,9 @@
  * cw_sw_cut.h -- the alignment operator's cut run (cw_sw_cut_run / cw_sw_cut_run_device, include/consent_amd.h): per pair the row of cw_sw_path_run, and
  * instead of the path's ops where the query crosses the reference's window boundaries: word t of a query's slot is the query position at reference column
  * t x W, so that piece t of the query is what its alignment puts on window t.  And cw_cut_groups_device on top of it: the POA batch of every (reference, window)
- * -- the window's columns first, then piece t of every query whose alignment spans the window.  The order kernel, the unpacking, sw_align<CLS>, sw_banded_path
- * and sw_walk are those of cw_sw_op.h and cw_sw_path.h, unedited; the cut kernels keep the launch bounds, LDS slabs, per-wave scratch and pair-claim loop of the
- * three path kernels.  New are:
+ * -- the window's columns first, then piece t of every query whose alignment spans the window.  The cut kernels are calls of cw_sw_op.h's sw_class_loop / sw_long_loop (LDS slabs,
+ * per-wave scratch, pair-claim loop, under the launch bounds of the path kernels) around cut_pair, which follows sw_path_pair line by line up to the closed walk.
+ * The run's own are:
  *
  *   cw_sw_cut_rest_kernel   one thread per sequence, behind the order kernel: a query whose row the order kernel wrote (beyond a capacity, empty, or on an empty
  *                           reference) never reaches a wave; its T + 1 zeros are stored here, where its slot holds them.
@@ -116,53 +116,17 @@ __device__ __forceinline__ void cut_pair(const CutArgs& ca, uint32_t s, uint8_t*
     st_mem_sync(); /* the next pair's unpacking overwrites what this one read */
 }
 
-/* the launch bounds and LDS slabs of cw_sw_path_kernel<CLS> */
 template <int CLS>
 __global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_sw_cut_kernel(CutArgs ca) {
-    constexpr int QMAX = CLS == 0 ? CW_SW_Q0 : CW_ST_QMAX;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint8_t* const slab = lds + (size_t)wave * CW_SW_SLAB_OF(QMAX);
-    uint8_t* const ref_lds = slab;
-    uint8_t* const qfw = ref_lds + CW_ST_RMAX;
-    uint8_t* const qrv = qfw + QMAX;
-    uint8_t* const rows = qrv + QMAX;
-    const size_t wv = (size_t)blockIdx.x * CW_SW_WAVES + wave;
-    uint8_t* const ref_glb = ca.a.gref + wv * CW_SW_GREF_BYTES;
-    uint8_t* const dirbuf = (uint8_t*)ca.a.dir + wv * ca.a.dir_bytes;
-    uint8_t* const steps = ca.steps + wv * CW_SW_STEP_BYTES;
-    const uint32_t n_pairs = st_uni(ca.a.ctr[3 + CLS]), base = CLS == 0 ? 0u : st_uni(ca.a.ctr[3]);
-    for (;;) {
-        uint32_t pi = 0;
-        if (lane == 0) pi = atomicAdd(ca.a.ctr + CLS, 1u);
-        pi = (uint32_t)cw_lane_value((int)pi, 0);
-        if (pi >= n_pairs) break;
-        const uint32_t s = st_uni(ca.a.order[base + pi]);
-        const uint32_t n = st_uni(ca.a.b.seq_len[st_uni(ca.a.seq_ref[s])]);
-        cut_pair<CLS>(ca, s, n <= (uint32_t)CW_ST_RMAX ? ref_lds : ref_glb, qfw, qrv, (uint32_t)QMAX, true, rows, dirbuf, steps, nullptr, lane);
-    }
+    sw_class_loop<CLS, true>(ca.a, ca.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        cut_pair<CLS>(ca, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+    });
 }
 
 __global__ void __launch_bounds__(64, 2) cw_sw_cut_long_kernel(CutArgs ca) {
-    __shared__ __attribute__((aligned(16))) uint8_t rows[CW_ST_ROWS_BYTES];
-    const int lane = threadIdx.x & 63;
-    const uint32_t n_pairs = st_uni(ca.a.ctr[5]);
-    if (n_pairs == 0u) return; /* normally */
-    const uint32_t base = st_uni(ca.a.ctr[3]) + st_uni(ca.a.ctr[4]);
-    uint8_t* const mem = ca.a.lstate + (size_t)blockIdx.x * CW_SW_LONG_WAVE_BYTES;
-    uint8_t* const refc = mem;
-    uint8_t* const qfw = refc + CW_SW_GREF_BYTES;
-    uint8_t* const qrv = qfw + CW_STH_QMAX;
-    uint8_t* const state = qrv + CW_STH_QMAX;
-    uint8_t* const dirbuf = (uint8_t*)ca.a.dir + (size_t)blockIdx.x * ca.a.dir_bytes;
-    uint8_t* const steps = ca.steps + (size_t)blockIdx.x * CW_SW_STEP_BYTES;
-    for (;;) {
-        uint32_t pi = 0;
-        if (lane == 0) pi = atomicAdd(ca.a.ctr + 2, 1u);
-        pi = (uint32_t)cw_lane_value((int)pi, 0);
-        if (pi >= n_pairs) break;
-        cut_pair<2>(ca, st_uni(ca.a.order[base + pi]), refc, qfw, qrv, 0u, false, rows, dirbuf, steps, state, lane);
-    }
+    sw_long_loop<true>(ca.a, ca.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        cut_pair<2>(ca, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+    });
 }
 
 /* ---- cw_cut_groups_device: the POA batch of every (reference, window) --------------------------------------------------------------------------------------- */

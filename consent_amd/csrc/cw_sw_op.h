@@ -16,6 +16,10 @@
  *
  * The three alignment launches run one after the other on one stream, so they share the per-wave direction scratch and reference scratch.  cw_plan.h plan_sw
  * sizes everything; cw_engine.cpp run_sw_locked launches by it.
+ *
+ * The path, pileup and cut runs (cw_sw_path.h, cw_pileup.h, cw_sw_cut.h) launch kernels of their own names in the same three classes.  What the four runs'
+ * kernels share lives here, once: sw_class_loop<CLS> and sw_long_loop carve a wave's buffers (SwWaveBufs) and claim the pairs; every kernel is a call of one
+ * of the two with what it does per pair.
  */
 #ifndef CW_SW_OP_H
 #define CW_SW_OP_H
@@ -29,6 +33,7 @@
 #define CW_SW_COST_CLASSES 128   /* four per power of two of query length x reference length */
 #define CW_SW_CTR_WORDS (8 + 3 * CW_SW_COST_CLASSES) /* cursors [0..2], pairs per launch class [3..5], then the classes' counts / offsets */
 #define CW_SW_LONG_MAX_WGS 256
+#define CW_SW_STEP_BYTES 49152u  /* a traced run's walk (cw_sw_path.h), per wave: at most query span + reference span steps */
 /* the long launch, per wave: reference codes | query codes | reversed prefix | the sweep's state */
 #define CW_SW_LONG_WAVE_BYTES ((size_t)CW_SW_GREF_BYTES + 2 * (size_t)CW_STH_QMAX + CW_STH_STATE_BYTES)
 /* per wave of cw_sw_kernel: reference codes | query codes | reversed prefix (and the traceback's directions when they are few) | traceback rows */
@@ -182,21 +187,41 @@ __device__ __forceinline__ void sw_pair(const SwArgs& a, uint32_t s, uint8_t* re
     st_mem_sync(); /* the next pair's unpacking overwrites what the traceback's lane 0 read */
 }
 
-/* CLS 0: 128 registers (the five-register sweep is its widest: four waves a SIMD, and the LDS of four work-groups a CU); CLS 1: whatever the sixteen-register
-   sweep takes (one wave a SIMD, as cw_stitch_kernel's wide instance) */
-template <int CLS>
-__global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_sw_kernel(SwArgs a) {
+/* a wave's buffers, carved once per launch; refc is chosen per pair */
+struct SwWaveBufs {
+    uint8_t* ref_lds;    /* CW_ST_RMAX reference codes in the slab; the long launch: none */
+    uint8_t* ref_glb;    /* CW_SW_GREF_BYTES of the wave's global scratch */
+    uint8_t* refc;       /* the pair's reference: ref_lds or ref_glb */
+    uint8_t* qfw;        /* query codes */
+    uint8_t* qrv;        /* reversed prefix */
+    uint32_t qrv_bytes;  /* what qrv offers the traceback's directions: its size when it is LDS */
+    bool qrv_lds;
+    uint8_t* rows;       /* CW_ST_ROWS_BYTES of LDS */
+    uint8_t* dirbuf;     /* a.dir_bytes of direction scratch; NULL when the run has none */
+    uint8_t* steps;      /* CW_SW_STEP_BYTES of step scratch; NULL for the plain run */
+    uint8_t* state;      /* the long launch's sweep state */
+};
+
+/* The one slab carve and pair-claim loop of classes 0 and 1, for the four runs' kernels: query codes and the reversed prefix in the wave's LDS slab, the
+   reference there too up to CW_ST_RMAX bases and in the wave's global scratch beyond.  TRACED: a run with a walk (cw_sw_path.h), which has step scratch at
+   steps_base and always has direction scratch; the plain run passes NULL.  per_pair(s, bufs, lane) does one pair (the kernels' lambdas are always_inline, as every device function
+   here is: a kernel is one function before the optimiser sees it). */
+template <int CLS, bool TRACED, class F>
+__device__ __forceinline__ void sw_class_loop(const SwArgs& a, uint8_t* steps_base, F per_pair) {
     constexpr int QMAX = CLS == 0 ? CW_SW_Q0 : CW_ST_QMAX;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint8_t* const slab = lds + (size_t)wave * CW_SW_SLAB_OF(QMAX);
-    uint8_t* const ref_lds = slab;              /* CW_ST_RMAX reference codes */
-    uint8_t* const qfw = ref_lds + CW_ST_RMAX;  /* QMAX query codes           */
-    uint8_t* const qrv = qfw + QMAX;            /* QMAX reversed prefix       */
-    uint8_t* const rows = qrv + QMAX;           /* CW_ST_ROWS_BYTES           */
     const size_t wv = (size_t)blockIdx.x * CW_SW_WAVES + wave;
-    uint8_t* const ref_glb = a.gref + wv * CW_SW_GREF_BYTES;
-    int8_t* const dirbuf = a.dir ? a.dir + wv * a.dir_bytes : nullptr;
+    SwWaveBufs w;
+    w.ref_lds = slab;                   /* CW_ST_RMAX reference codes */
+    w.qfw = w.ref_lds + CW_ST_RMAX;     /* QMAX query codes           */
+    w.qrv = w.qfw + QMAX;               /* QMAX reversed prefix       */
+    w.rows = w.qrv + QMAX;              /* CW_ST_ROWS_BYTES           */
+    w.qrv_bytes = (uint32_t)QMAX; w.qrv_lds = true; w.state = nullptr;
+    w.ref_glb = a.gref + wv * CW_SW_GREF_BYTES;
+    w.dirbuf = TRACED || a.dir ? (uint8_t*)a.dir + wv * a.dir_bytes : nullptr;
+    w.steps = TRACED ? steps_base + wv * CW_SW_STEP_BYTES : nullptr;
     const uint32_t n_pairs = st_uni(a.ctr[3 + CLS]), base = CLS == 0 ? 0u : st_uni(a.ctr[3]);
     for (;;) {
         uint32_t pi = 0;
@@ -205,31 +230,54 @@ __global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_sw_kern
         if (pi >= n_pairs) break;
         const uint32_t s = st_uni(a.order[base + pi]);
         const uint32_t n = st_uni(a.b.seq_len[st_uni(a.seq_ref[s])]);
-        sw_pair<CLS>(a, s, n <= (uint32_t)CW_ST_RMAX ? ref_lds : ref_glb, qfw, qrv, (uint32_t)QMAX, true, rows, dirbuf, nullptr, lane);
+        w.refc = n <= (uint32_t)CW_ST_RMAX ? w.ref_lds : w.ref_glb;
+        per_pair(s, w, lane);
     }
 }
 
-/* (compiled for 256 registers, two waves a SIMD: at the last launch's 128 of cw_stitch_kernel the memory-state sweep spills 90 registers into its column loop --
-   there a launch that normally finds nothing to do, here the path of every long query) */
-__global__ void __launch_bounds__(64, 2) cw_sw_long_kernel(SwArgs a) {
+/* The long class's: one wave a work-group, every buffer and the sweep's state in the wave's global scratch (CW_SW_LONG_WAVE_BYTES); ends at once when the order
+   kernel counted no such pair. */
+template <bool TRACED, class F>
+__device__ __forceinline__ void sw_long_loop(const SwArgs& a, uint8_t* steps_base, F per_pair) {
     __shared__ __attribute__((aligned(16))) uint8_t rows[CW_ST_ROWS_BYTES];
     const int lane = threadIdx.x & 63;
     const uint32_t n_pairs = st_uni(a.ctr[5]);
     if (n_pairs == 0u) return; /* normally */
     const uint32_t base = st_uni(a.ctr[3]) + st_uni(a.ctr[4]);
-    uint8_t* const mem = a.lstate + (size_t)blockIdx.x * CW_SW_LONG_WAVE_BYTES;
-    uint8_t* const refc = mem;
-    uint8_t* const qfw = refc + CW_SW_GREF_BYTES;
-    uint8_t* const qrv = qfw + CW_STH_QMAX;
-    uint8_t* const state = qrv + CW_STH_QMAX;
-    int8_t* const dirbuf = a.dir ? a.dir + (size_t)blockIdx.x * a.dir_bytes : nullptr;
+    SwWaveBufs w;
+    w.ref_lds = nullptr;
+    w.ref_glb = a.lstate + (size_t)blockIdx.x * CW_SW_LONG_WAVE_BYTES;
+    w.refc = w.ref_glb;
+    w.qfw = w.refc + CW_SW_GREF_BYTES;
+    w.qrv = w.qfw + CW_STH_QMAX;
+    w.state = w.qrv + CW_STH_QMAX;
+    w.qrv_bytes = 0u; w.qrv_lds = false; w.rows = rows;
+    w.dirbuf = TRACED || a.dir ? (uint8_t*)a.dir + (size_t)blockIdx.x * a.dir_bytes : nullptr;
+    w.steps = TRACED ? steps_base + (size_t)blockIdx.x * CW_SW_STEP_BYTES : nullptr;
     for (;;) {
         uint32_t pi = 0;
         if (lane == 0) pi = atomicAdd(a.ctr + 2, 1u);
         pi = (uint32_t)cw_lane_value((int)pi, 0);
         if (pi >= n_pairs) break;
-        sw_pair<2>(a, st_uni(a.order[base + pi]), refc, qfw, qrv, 0u, false, rows, dirbuf, state, lane);
+        per_pair(st_uni(a.order[base + pi]), w, lane);
     }
+}
+
+/* CLS 0: 128 registers (the five-register sweep is its widest: four waves a SIMD, and the LDS of four work-groups a CU); CLS 1: whatever the sixteen-register
+   sweep takes (one wave a SIMD, as cw_stitch_kernel's wide instance).  The path, pileup and cut kernels keep these launch bounds. */
+template <int CLS>
+__global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_sw_kernel(SwArgs a) {
+    sw_class_loop<CLS, false>(a, nullptr, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        sw_pair<CLS>(a, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, (int8_t*)w.dirbuf, w.state, lane);
+    });
+}
+
+/* (compiled for 256 registers, two waves a SIMD: at the last launch's 128 of cw_stitch_kernel the memory-state sweep spills 90 registers into its column loop --
+   there a launch that normally finds nothing to do, here the path of every long query) */
+__global__ void __launch_bounds__(64, 2) cw_sw_long_kernel(SwArgs a) {
+    sw_long_loop<false>(a, nullptr, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        sw_pair<2>(a, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, (int8_t*)w.dirbuf, w.state, lane);
+    });
 }
 
 #endif

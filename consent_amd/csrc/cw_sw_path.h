@@ -1,7 +1,9 @@
 /*
  * cw_sw_path.h -- the alignment operator's path run (cw_sw_path_run / cw_sw_path_run_device, include/consent_amd.h): per pair the row of cw_sw_run and the
  * alignment itself as run-length encoded ops.  One wave per pair, the order kernel, the unpacking, the sweeps and the three launch classes of cw_sw_op.h; new are
- * the traceback behind them and its kernels.  Nothing of cw_sw_op.h or cw_stitch.h is edited: cw_sw_run and the re-assembly keep st_banded_indels.
+ * the traceback behind them and its kernels, which are calls of cw_sw_op.h's sw_class_loop / sw_long_loop.  cw_stitch.h is not edited: cw_sw_run and the
+ * re-assembly keep st_banded_indels.  The pileup and cut runs (cw_pileup.h, cw_sw_cut.h) use sw_banded_path and sw_walk from here; their pair bodies
+ * (pile_pair, cut_pair) are copies of sw_path_pair up to the closed walk: one shared body with a sink per run compiled to other registers and spills.
  *
  *   sw_banded_path   ssw's banded pass between the found ends (oracle/cw_oracle.cpp ssw_banded_indels), its rows on the lanes for EVERY band width: a row of the
  *                    band goes in chunks of 64 cells, lowest first.  The arrays h_b / e_b / h_c and their index rules -- the zeroed `edge` slots, the shift
@@ -23,7 +25,6 @@
 
 #include "cw_sw_op.h"
 
-#define CW_SW_STEP_BYTES 49152u /* a walk's steps: at most query span + reference span */
 #define CW_SW_PATH_MAX_WAVES 512u /* x CW_SW_PATH_BYTES = the 1 GiB of direction scratch an indel run plans at most */
 
 static_assert(CW_SW_QMAX + CW_SW_RMAX <= CW_SW_STEP_BYTES, "every step consumes a base of the query or of the reference");
@@ -213,50 +214,15 @@ __device__ __forceinline__ void sw_path_pair(const SwPathArgs& pa, uint32_t s, u
 /* the launch bounds and LDS slabs of cw_sw_kernel<CLS> */
 template <int CLS>
 __global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_sw_path_kernel(SwPathArgs pa) {
-    constexpr int QMAX = CLS == 0 ? CW_SW_Q0 : CW_ST_QMAX;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint8_t* const slab = lds + (size_t)wave * CW_SW_SLAB_OF(QMAX);
-    uint8_t* const ref_lds = slab;
-    uint8_t* const qfw = ref_lds + CW_ST_RMAX;
-    uint8_t* const qrv = qfw + QMAX;
-    uint8_t* const rows = qrv + QMAX;
-    const size_t wv = (size_t)blockIdx.x * CW_SW_WAVES + wave;
-    uint8_t* const ref_glb = pa.a.gref + wv * CW_SW_GREF_BYTES;
-    uint8_t* const dirbuf = (uint8_t*)pa.a.dir + wv * pa.a.dir_bytes;
-    uint8_t* const steps = pa.steps + wv * CW_SW_STEP_BYTES;
-    const uint32_t n_pairs = st_uni(pa.a.ctr[3 + CLS]), base = CLS == 0 ? 0u : st_uni(pa.a.ctr[3]);
-    for (;;) {
-        uint32_t pi = 0;
-        if (lane == 0) pi = atomicAdd(pa.a.ctr + CLS, 1u);
-        pi = (uint32_t)cw_lane_value((int)pi, 0);
-        if (pi >= n_pairs) break;
-        const uint32_t s = st_uni(pa.a.order[base + pi]);
-        const uint32_t n = st_uni(pa.a.b.seq_len[st_uni(pa.a.seq_ref[s])]);
-        sw_path_pair<CLS>(pa, s, n <= (uint32_t)CW_ST_RMAX ? ref_lds : ref_glb, qfw, qrv, (uint32_t)QMAX, true, rows, dirbuf, steps, nullptr, lane);
-    }
+    sw_class_loop<CLS, true>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        sw_path_pair<CLS>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+    });
 }
 
 __global__ void __launch_bounds__(64, 2) cw_sw_path_long_kernel(SwPathArgs pa) {
-    __shared__ __attribute__((aligned(16))) uint8_t rows[CW_ST_ROWS_BYTES];
-    const int lane = threadIdx.x & 63;
-    const uint32_t n_pairs = st_uni(pa.a.ctr[5]);
-    if (n_pairs == 0u) return; /* normally */
-    const uint32_t base = st_uni(pa.a.ctr[3]) + st_uni(pa.a.ctr[4]);
-    uint8_t* const mem = pa.a.lstate + (size_t)blockIdx.x * CW_SW_LONG_WAVE_BYTES;
-    uint8_t* const refc = mem;
-    uint8_t* const qfw = refc + CW_SW_GREF_BYTES;
-    uint8_t* const qrv = qfw + CW_STH_QMAX;
-    uint8_t* const state = qrv + CW_STH_QMAX;
-    uint8_t* const dirbuf = (uint8_t*)pa.a.dir + (size_t)blockIdx.x * pa.a.dir_bytes;
-    uint8_t* const steps = pa.steps + (size_t)blockIdx.x * CW_SW_STEP_BYTES;
-    for (;;) {
-        uint32_t pi = 0;
-        if (lane == 0) pi = atomicAdd(pa.a.ctr + 2, 1u);
-        pi = (uint32_t)cw_lane_value((int)pi, 0);
-        if (pi >= n_pairs) break;
-        sw_path_pair<2>(pa, st_uni(pa.a.order[base + pi]), refc, qfw, qrv, 0u, false, rows, dirbuf, steps, state, lane);
-    }
+    sw_long_loop<true>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        sw_path_pair<2>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+    });
 }
 
 #endif
