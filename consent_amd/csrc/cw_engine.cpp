@@ -6,7 +6,7 @@
  * cw_wait) and the loop that runs a batch again with a larger plan (cw_run, cw_run_device_sync); the POA stage alone on a batch of groups (cw_poa_run_device,
  * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run); the re-assembly's local aligner alone on a batch of groups
  * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h; cw_pileup_run_device, cw_pileup_run: cw_pileup.h; cw_sw_cut_run_device, cw_sw_cut_run,
- * cw_cut_groups_device: cw_sw_cut.h).
+ * cw_cut_groups_device: cw_sw_cut.h); both strands for them (cw_strand_run_device, cw_strand_run, cw_revcomp_device, cw_revcomp: cw_strand.h).
  * The scratch plan is cw_plan.h (host arithmetic only); the host feeders, cw_window_positions among them, are cw_hostio.cpp.
  */
 #include "cw_internal.h"
@@ -26,6 +26,7 @@
 #include "cw_sw_path.h"
 #include "cw_pileup.h"
 #include "cw_sw_cut.h"
+#include "cw_strand.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -58,6 +59,7 @@ constexpr size_t kLdsFinish = (size_t)CW_FIN_SLAB * CW_FIN_WAVES, kLdsFinishBig 
 constexpr size_t kLdsStitch = (size_t)CW_ST_WAVES * CW_ST_SLAB; /* what the wide re-assembly kernel needs (it is given more: stitch_lds_one) */
 constexpr size_t lds_sw(int cls) { return (size_t)CW_SW_WAVES * (cls == 0 ? CW_SW_SLAB_OF(CW_SW_Q0) : CW_SW_SLAB_OF(CW_ST_QMAX)); } /* the alignment operator's two LDS instances */
 static_assert(4 * lds_sw(0) <= 163840, "cw_sw_kernel<0>: the four work-groups a CU its 128 registers allow");
+constexpr size_t kLdsStrandWide = (size_t)CW_STR_SLOTS_WIDE * 4; /* the strand vote's wide table (the narrow one is static) */
 
 /* tiers M1, M2 and L are instances of cw_poa_slab_kernel: a tier's template arguments and the LDS of its work-group, PASS 0 = its own list, 1 = the overflow pass */
 template <int NC, int EC, int LC, int WAVES, int TIER, size_t LDS>
@@ -120,7 +122,8 @@ int set_kernel_attributes(const hipDeviceProp_t& prop) {
         allow((const void*)cw_sw_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_kernel<1>, lds_sw(1)) &&
         allow((const void*)cw_sw_path_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_path_kernel<1>, lds_sw(1)) &&
         allow((const void*)cw_pileup_kernel<0>, lds_sw(0)) && allow((const void*)cw_pileup_kernel<1>, lds_sw(1)) &&
-        allow((const void*)cw_sw_cut_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_cut_kernel<1>, lds_sw(1));
+        allow((const void*)cw_sw_cut_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_cut_kernel<1>, lds_sw(1)) &&
+        allow((const void*)cw_strand_kernel<1>, kLdsStrandWide);
     return ok ? CW_OK : CW_E_NO_DEVICE;
 }
 
@@ -449,8 +452,9 @@ int poa_device_locked(cw_engine* e, const cw_batch* groups, const cw_result* res
 /* ---- the alignment operator's four runs: cw_sw_run, cw_sw_path_run, cw_pileup_run, cw_sw_cut_run (and their _device forms) ------------------------------- */
 
 /* What the four refuse alike, e and groups given: CW_OK for a batch of groups whose pairs can be aligned -- and for one without sequences, before a look at
-   rows; nothing here touches the device.  Each validate_* below keeps its own checks and their place before or behind these. */
-int validate_groups(const cw_engine* e, const cw_batch* groups, const int32_t* rows) {
+   rows (the strand runs: their per-sequence output); nothing here touches the device.  Each validate_* below keeps its own checks and their place before or
+   behind these. */
+int validate_groups(const cw_engine* e, const cw_batch* groups, const void* rows) {
     if (groups->n_windows > max_batch_windows(e->tmax_plan)) return CW_E_INVALID; /* cw_max_batch_windows */
     if (groups->n_windows == 0 || groups->n_seqs == 0) return groups->n_seqs == 0 ? CW_OK : CW_E_INVALID; /* (sequences belong to groups) */
     if (!rows || !groups->win_first_seq || !groups->seq_len || !groups->seq_word_off || !groups->bases) return CW_E_INVALID;
@@ -650,6 +654,66 @@ int upload_groups(cw_engine* e, const cw_batch* b, const std::vector<uint64_t>* 
 /* what a host-buffer entry point answers for the rows that came back: CW_E_CAPACITY when a pair was beyond a capacity */
 int sw_rows_rc(const int32_t* rows, uint32_t n_seqs) {
     for (uint32_t s = 0; s < n_seqs; ++s) if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_STOP) return CW_E_CAPACITY;
+    return CW_OK;
+}
+
+/* ---- both strands: cw_strand_run, cw_revcomp (and their _device forms) ------------------------------------------------------------------------------------- */
+
+int validate_strand(const cw_engine* e, const cw_batch* groups, const cw_strands* out) {
+    if (!e || !groups || !out || !out->strand) return CW_E_INVALID;
+    if (out->k != 0u && (out->k < CW_STRAND_KMIN || out->k > CW_STRAND_KMAX)) return CW_E_INVALID;
+    return validate_groups(e, groups, out->strand);
+}
+
+int validate_revcomp(const cw_engine* e, const cw_batch* groups, const uint32_t* bases_out) {
+    if (!e || !groups || !bases_out || bases_out == groups->bases) return CW_E_INVALID;
+    return validate_groups(e, groups, bases_out);
+}
+
+/* the body of cw_strand_run_device; the caller holds e->mu.  Stages: strand_order (the units of every group), strand (references of up to CW_ST_RMAX bases),
+   strand_wide (beyond).  The plan lives in the engine's scratch, as an alignment run's. */
+int run_strand_locked(cw_engine* e, const cw_batch* groups, const cw_strands* out, void* hip_stream) {
+    int rc = validate_strand(e, groups, out);
+    if (rc || groups->n_seqs == 0) return rc;
+    const StrandPlan p = plan_strand(groups->n_windows, groups->n_seqs, e->cus); /* exact: the batch runs once */
+    hipStream_t st;
+    if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
+    uint8_t* base = (uint8_t*)e->scratch;
+    StrandArgs a;
+    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.n_seqs = groups->n_seqs; a.strand = out->strand; a.hits = out->hits; a.k = out->k ? out->k : CW_STRAND_K;
+    a.ctr = (uint32_t*)(base + p.ctr); a.unit_off = (uint32_t*)(base + p.unit_off);
+    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (enqueue_sw_run) */
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_STR_CTR_WORDS * 4, st));
+    stage(e, st, "strand_order", [&] { cw_strand_units_kernel<<<1, 1024, 0, st>>>(a); });
+    stage(e, st, "strand", [&] { cw_strand_kernel<0><<<p.wgs, CW_STR_THREADS, 0, st>>>(a); });
+    stage(e, st, "strand_wide", [&] { cw_strand_kernel<1><<<p.wgs_wide, CW_STR_THREADS_WIDE, kLdsStrandWide, st>>>(a); });
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
+}
+
+/* the body of cw_revcomp_device.  One stage: revcomp.  No scratch: what the engine's scratch holds stays what it was. */
+int run_revcomp_locked(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint32_t* bases_out, void* hip_stream) {
+    int rc = validate_revcomp(e, groups, bases_out);
+    if (rc || groups->n_seqs == 0) return rc;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    RevcompArgs a;
+    a.n_seqs = groups->n_seqs; a.seq_len = groups->seq_len; a.seq_word_off = groups->seq_word_off; a.bases = groups->bases; a.strand = strand; a.out = bases_out;
+    const uint32_t per = 256u / CW_RC_LANES; /* sequences a work-group and round */
+    const uint32_t wgs = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(((uint64_t)groups->n_seqs + per - 1u) / per, (uint64_t)e->cus * 32u));
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    stage(e, st, "revcomp", [&] { cw_revcomp_kernel<<<wgs, 256, 0, st>>>(a); });
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
     return CW_OK;
 }
 
@@ -972,6 +1036,81 @@ int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cu
         if (rows[(size_t)sw.first * CW_SW_ROW + CW_SW_STATUS] != CW_SW_CUT_SLOT)
             memcpy(cuts->cuts + cuts->cut_off[sw.first], back.data() + coff[sw.first], (size_t)sw.second * 4);
     return sw_rows_rc(rows, S);
+}
+
+int cw_strand_run_device(cw_engine* e, const cw_batch* groups, const cw_strands* out, void* hip_stream) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_strand_locked(e, groups, out, hip_stream);
+}
+
+/* Host buffers in, host buffers out, synchronous, as cw_sw_run: the batch goes up, cw_strand_run_device on the engine's stream, the strand bytes and -- when asked
+   for -- the hits come back. */
+int cw_strand_run(cw_engine* e, const cw_batch* b, const cw_strands* out) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = validate_strand(e, b, out);
+    if (rc || b->n_seqs == 0) return rc;
+    const uint32_t S = b->n_seqs;
+    cw_batch db;
+    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
+    const size_t o_hits = align_up((size_t)S, 256), out_bytes = o_hits + (out->hits ? (size_t)S * 8 : 0);
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
+    hipStream_t st = e->stream;
+    uint8_t* dout = (uint8_t*)e->poa_out;
+    cw_strands ds;
+    ds.strand = dout; ds.hits = out->hits ? (uint32_t*)(dout + o_hits) : nullptr; ds.k = out->k;
+    if ((rc = run_strand_locked(e, &db, &ds, st)) != CW_OK) return rc;
+    CW_HIP(hipMemcpyAsync(out->strand, ds.strand, (size_t)S, hipMemcpyDeviceToHost, st));
+    if (out->hits) CW_HIP(hipMemcpyAsync(out->hits, ds.hits, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    return CW_OK;
+}
+
+int cw_revcomp_device(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint32_t* bases_out, void* hip_stream) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_revcomp_locked(e, groups, strand, bases_out, hip_stream);
+}
+
+/* Host buffers in, host buffers out, synchronous: the batch and the strand bytes go up, cw_revcomp_device on the engine's stream, and of the words that come back
+   every sequence's own are copied to bases_out: a word that belongs to no sequence is not written on the host either. */
+int cw_revcomp(cw_engine* e, const cw_batch* b, const uint8_t* strand, uint32_t* bases_out) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = validate_revcomp(e, b, bases_out);
+    if (rc || b->n_seqs == 0) return rc;
+    const uint32_t S = b->n_seqs;
+    cw_batch db;
+    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
+    const size_t o_strand = align_up((size_t)(b->n_words + 1) * 4, 256), out_bytes = o_strand + (size_t)S;
+    std::vector<uint32_t> back;
+    try { back.resize((size_t)b->n_words + 1); } catch (...) { return CW_E_NOMEM; }
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
+    hipStream_t st = e->stream;
+    uint8_t* dout = (uint8_t*)e->poa_out;
+    if (strand) CW_HIP(hipMemcpyAsync(dout + o_strand, strand, (size_t)S, hipMemcpyHostToDevice, st));
+    if ((rc = run_revcomp_locked(e, &db, strand ? dout + o_strand : nullptr, (uint32_t*)dout, st)) != CW_OK) return rc;
+    if (b->n_words) CW_HIP(hipMemcpyAsync(back.data(), dout, (size_t)b->n_words * 4, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    for (uint32_t s = 0; s < S; ++s) {
+        const size_t nw = ((size_t)b->seq_len[s] + 15) / 16;
+        if (nw) memcpy(bases_out + b->seq_word_off[s], back.data() + b->seq_word_off[s], nw * 4);
+    }
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): what plan_strand would allocate and its grids (host arithmetic only). */
+int cw_debug_strand_plan(uint32_t n_groups, uint32_t n_seqs, int cus, uint64_t* out5) {
+    if (!out5 || cus < 1) return CW_E_INVALID;
+    const StrandPlan p = plan_strand(n_groups, n_seqs, cus);
+    const uint64_t v[5] = {p.total, (uint64_t)p.unit_off, (uint64_t)(p.total - p.unit_off), p.wgs, p.wgs_wide};
+    for (int i = 0; i < 5; ++i) out5[i] = v[i];
+    return CW_OK;
 }
 
 /* One work-group sizes the output groups of every input group, a wave per output group counts its members and words, one work-group scans; the totals come to

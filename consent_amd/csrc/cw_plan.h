@@ -11,6 +11,7 @@
 #include "cw_index.h"  /* CW_EXG_SLOTS; with each of these: cw_device.h (the records' sizes, CW_TIERS) and include/consent_amd.h */
 #include "cw_poa_q.h"  /* slab and graph sizes of every tier (cw_poa.h comes with it) */
 #include "cw_sw_path.h" /* the alignment operator's per-wave sizes, the path run's too (cw_sw_op.h and cw_stitch.h come with it) */
+#include "cw_strand.h" /* the strand vote's chunk sizes */
 #include "cw_finish.h" /* CW_FIN_*.  (These three are kernel headers, taken for their size macros: nothing here runs on the device, but a translation unit that includes this one is still a HIP one) */
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -245,6 +246,24 @@ static inline SwPathPlan plan_sw_path(uint32_t n_groups, uint32_t n_seqs, uint64
     put(p.lstate, (size_t)p.wgs_long * CW_SW_LONG_WAVE_BYTES);
     put(p.dir, (size_t)p.dir_waves * p.dir_bytes);
     put(p.steps, (size_t)p.dir_waves * CW_SW_STEP_BYTES);
+    p.total = o;
+    return p;
+}
+
+/* The plan of a strand run (cw_strand_run, cw_strand.h): the two claim counters and the class totals, and the first unit of every group.  Exact, and the batch
+   runs once.  The grids are fixed and claim units, whose number only the device knows; the host knows its bound -- a group has at most one unit more than its
+   queries fill chunks -- and launches no more work-groups than that: 256 threads and 16 KB of LDS allow eight a CU, the wide class's 128 KB table one. */
+struct StrandPlan { size_t ctr, unit_off, total; uint32_t wgs, wgs_wide; };
+static inline StrandPlan plan_strand(uint32_t n_groups, uint32_t n_seqs, int cus) {
+    StrandPlan p;
+    memset(&p, 0, sizeof(p));
+    const uint64_t most = (uint64_t)n_groups + n_seqs / CW_STR_CHUNK, most_wide = (uint64_t)n_groups + n_seqs / CW_STR_CHUNK_WIDE;
+    p.wgs = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(most, (uint64_t)cus * 8u));
+    p.wgs_wide = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(most_wide, (uint64_t)cus));
+    size_t o = 0;
+    auto put = [&](size_t& slot, size_t bytes) { slot = o; o = align_up(o + bytes, 256); };
+    put(p.ctr, (size_t)CW_STR_CTR_WORDS * 4);
+    put(p.unit_off, ((size_t)n_groups + 1) * 4);
     p.total = o;
     return p;
 }

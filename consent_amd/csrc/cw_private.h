@@ -51,6 +51,9 @@ int cw_debug_sw_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int c
    class-1 and long launches, [9] waves that have traceback scratch, [10] its bytes per wave, [11] a step buffer's bytes.  CW_E_INVALID for flags other than
    CW_SW_PATH_EQX. */
 int cw_debug_sw_path_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t flags, uint64_t* out12);
+/* The scratch plan of a strand run (cw_strand_run) of n_groups groups and n_seqs sequences, without a device: out[0] total bytes, [1] the claim counters and class
+   totals, [2] the first unit of every group, [3] [4] work-groups of the narrow and the wide launch. */
+int cw_debug_strand_plan(uint32_t n_groups, uint32_t n_seqs, int cus, uint64_t* out5);
 /* cw_max_batch_windows of an engine that cw_configure(max_template_len) will be called on (the native driver sizes its jobs before it has engines) */
 uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len);
 

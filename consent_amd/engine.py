@@ -26,6 +26,9 @@ PILE_ACCUMULATE = 8
 PILE_A, PILE_C, PILE_G, PILE_T, PILE_DEL, PILE_INS, PILE_BEGIN, PILE_END, PILE_COL = 0, 1, 2, 3, 4, 5, 6, 7, 8
 # cw_sw_cut_run: the status only it writes
 SW_CUT_SLOT = 8
+# cw_strand_run: a sequence's strand value, the default k and its range
+STRAND_FWD, STRAND_REV, STRAND_IS_REF, STRAND_NONE = 0, 1, 2, 3
+STRAND_K, STRAND_KMIN, STRAND_KMAX = 11, 8, 15
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -78,6 +81,12 @@ class SwCuts(C.Structure):
     """cw_sw_cuts: the cut-point slots of cw_sw_cut_run and the window size."""
 
     _fields_ = [("cuts", C.c_void_p), ("cut_off", C.c_void_p), ("window", C.c_uint32)]
+
+
+class Strands(C.Structure):
+    """cw_strands: the outputs of cw_strand_run (hits may be NULL) and k (0 = STRAND_K)."""
+
+    _fields_ = [("strand", C.c_void_p), ("hits", C.c_void_p), ("k", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -190,6 +199,12 @@ def _load(p):
         lib.cw_sw_cut_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwCuts), C.c_void_p]
         lib.cw_cut_groups_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwCuts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p]
+    if hasattr(lib, "cw_strand_run"):
+        lib.cw_strand_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Strands)]
+        lib.cw_strand_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Strands), C.c_void_p]
+        lib.cw_revcomp.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]
+        lib.cw_revcomp_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.cw_debug_strand_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
     lib.cw_submit.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.POINTER(C.c_int)]
     lib.cw_wait.argtypes = [C.c_void_p, C.c_int]
     lib.cw_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -614,6 +629,24 @@ class SwCutRows(SwRows):
         return [q[a:b] for a, b in zip(c, c[1:])]
 
 
+class StrandRows:
+    """What Engine.strands returns: `strands`, a uint8 value per sequence of the batch (STRAND_FWD, STRAND_REV, STRAND_IS_REF for a group's reference, STRAND_NONE
+    where no vote is possible), `hit_counts`, an (n_seqs, 2) uint32 array of forward and reverse hits, and the map from (group, member) to them as SwRows has it."""
+
+    def __init__(self, strands, hit_counts, win_first_seq, k):
+        self.strands, self.hit_counts, self.win_first_seq, self.k = strands, hit_counts, win_first_seq, k
+
+    index = SwRows.index
+
+    def strand(self, group, member):
+        return int(self.strands[self.index(group, member)])
+
+    def hits(self, group, member):
+        """(forward hits, reverse hits) of (group, member)."""
+        f, r = self.hit_counts[self.index(group, member)]
+        return int(f), int(r)
+
+
 class PolishWindow:
     """One window of a polished reference: `members` pieces were aligned beside the reference's own; `status` is the POA's (WIN_CONSENSUS, or WIN_OVERFLOW
     for a group that stopped: `kept_reference` is then True and the window's part of the result is the reference's columns)."""
@@ -626,10 +659,11 @@ class PolishWindow:
 
 
 class Polished:
-    """One reference of Engine.polish: `sequence`, the windows' consensuses joined in order, and `windows`, a PolishWindow each."""
+    """One reference of Engine.polish: `sequence`, the windows' consensuses joined in order, `windows`, a PolishWindow each, and `strands`, the strand value of
+    every read of the group under orient=True (empty without)."""
 
-    def __init__(self, sequence, windows):
-        self.sequence, self.windows = sequence, windows
+    def __init__(self, sequence, windows, strands=None):
+        self.sequence, self.windows, self.strands = sequence, windows, [] if strands is None else strands
 
 
 def _result_struct(r):
@@ -834,14 +868,60 @@ class Engine:
             _check(self.lib, rc, "cw_cut_groups_device")
         return rc, ng.value, ns.value, nw.value
 
-    def polish(self, groups, window=500):
+    def strands(self, groups, k=0):
+        """The strand vote (cw_strand_run): `groups` as for sw().  Per query the positions whose k-mer is among its reference's k-mers, as given and reverse-
+        complemented (k = 0: STRAND_K; else STRAND_KMIN .. STRAND_KMAX).  Returns StrandRows: .strand(group, member) is STRAND_REV when the reverse hits are the
+        more, else STRAND_FWD; STRAND_IS_REF for a reference, STRAND_NONE where no vote is possible; .hits(group, member) is (forward, reverse)."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        S = len(batch.seq_len)
+        strand = np.zeros(max(S, 1), np.uint8)
+        hits = np.zeros((max(S, 1), 2), np.uint32)
+        b = batch.c_struct()
+        out = Strands(_ptr(strand), _ptr(hits), k)
+        _check(self.lib, self.lib.cw_strand_run(self.handle, C.byref(b), C.byref(out)), "cw_strand_run")
+        return StrandRows(strand[:S], hits[:S], batch.win_first_seq, k)
+
+    def strand_device(self, batch_struct, strands_struct, stream=None):
+        """cw_strand_run_device: device pointers in the batch struct and in `strands_struct` (Strands); asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_strand_run_device(self.handle, C.byref(batch_struct), C.byref(strands_struct), stream), "cw_strand_run_device")
+
+    def revcomp(self, groups, strand=None):
+        """The batch with the flagged sequences reverse-complemented (cw_revcomp): `strand` is a uint8 value per sequence, of which STRAND_REV flags (a
+        StrandRows' .strands, say); None reverses every sequence.  Returns a HostBatch with new `bases` and the arrays of the input otherwise."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        S = len(batch.seq_len)
+        if strand is not None:
+            strand = np.ascontiguousarray(strand, np.uint8)
+            if len(strand) != S:
+                raise EngineError(f"revcomp: `strand` must have one value per sequence ({S})")
+        out = np.zeros_like(batch.bases)
+        b = batch.c_struct()
+        _check(self.lib, self.lib.cw_revcomp(self.handle, C.byref(b), _ptr(strand) if strand is not None and S else None, _ptr(out)), "cw_revcomp")
+        return HostBatch(batch.win_first_seq, batch.seq_len, batch.seq_word_off, out)
+
+    def revcomp_device(self, batch_struct, strand_ptr, bases_out_ptr, stream=None):
+        """cw_revcomp_device: device pointers in the batch struct, `strand_ptr` a device array of n_seqs bytes or None, `bases_out_ptr` a device array laid out as
+        the batch's bases and not the same; asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_revcomp_device(self.handle, C.byref(batch_struct), strand_ptr, bases_out_ptr, stream), "cw_revcomp_device")
+
+    def orient(self, groups, k=0):
+        """strands() and revcomp() of what it flags: (HostBatch in which every query has its reference's orientation, StrandRows).  Coordinates of what is
+        computed from the oriented batch are the oriented query's: position i there is position len - 1 - i of a query that was turned round."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        rows = self.strands(batch, k)
+        return self.revcomp(batch, rows.strands), rows
+
+    def polish(self, groups, window=500, orient=False, k=0):
         """Every group's reference (its first sequence) polished window by window from its other sequences, the reads: the reads are aligned and cut at the
         window boundaries (cw_sw_cut_run_device), every (reference, window) becomes a POA group of the window's columns and the pieces of the reads whose
         alignments span it (cw_cut_groups_device), the POA tiers give every group's consensus (cw_poa_run_device), and the consensuses of a reference's windows
         are joined in order.  Nothing but the result leaves the device.  The reference's columns are the backbone: one voice among the members, and base ties
         go to it; the first max_msa non-empty sequences of a group are aligned, the backbone included.  Returns a list of Polished, one per input group:
         .sequence and .windows (PolishWindow: members, status, kept_reference).  A window whose POA group stops keeps the reference's columns.  Raises
-        EngineError when the windows of the batch exceed max_batch_windows(): split the references over calls."""
+        EngineError when the windows of the batch exceed max_batch_windows(): split the references over calls.
+        orient=True: the reads may be of either strand.  The uploaded batch goes through the strand vote (cw_strand_run_device, k as for strands()) and the
+        reads it flags are reverse-complemented on the device (cw_revcomp_device) before the cut run; .strands of every Polished then holds its reads' strand
+        values, the only extra that leaves the device.  Without it a read of the other strand aligns by chance and its pieces rarely span a window."""
         import torch
 
         batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
@@ -868,7 +948,19 @@ class Engine:
         t_grp = torch.zeros(G + 1, dtype=torch.int32, device=dev)
         b = Batch(G, S, len(batch.bases), t_wfs.data_ptr(), t_len.data_ptr(), t_off.data_ptr(), t_bases.data_ptr())
         cuts = SwCuts(t_cuts.data_ptr(), t_coff.data_ptr(), window)
+        if orient:
+            t_strand = torch.zeros(S, dtype=torch.uint8, device=dev)
+            t_turned = torch.zeros_like(t_bases)
         torch.cuda.synchronize(dev)  # the engine launches on its own stream: torch's copies and fills above must have landed
+        read_strands = [None] * G
+        if orient:  # the reads the vote flags turned round into a second `bases`: the batch the runs below see
+            self.strand_device(b, Strands(t_strand.data_ptr(), None, k))
+            self.revcomp_device(b, t_strand.data_ptr(), t_turned.data_ptr())
+            b.bases = t_turned.data_ptr()
+            wfs = np.asarray(batch.win_first_seq, np.int64)
+            torch.cuda.synchronize(dev)
+            strand = down(t_strand, np.uint8)
+            read_strands = [[int(v) for v in strand[wfs[g] + 1 : wfs[g + 1]]] for g in range(G)]
         self.sw_cut_device(b, t_rows.data_ptr(), cuts)
         _, ng, ns, nw = self.cut_groups_device(b, t_rows.data_ptr(), cuts)
         if ng > self.max_batch_windows():
@@ -882,7 +974,7 @@ class Engine:
         _check(self.lib, rc, "cw_cut_groups_device")
         torch.cuda.synchronize(dev)
         if ng == 0:
-            return [Polished("", []) for _ in range(G)]
+            return [Polished("", [], read_strands[g]) for g in range(G)]
         # the consensus slots: CW_POA_SLOT_BYTES of every group's longest member
         counts = (o_wfs[1:] - o_wfs[:-1]).to(torch.int64)
         gid = torch.repeat_interleave(torch.arange(ng, device=dev), counts)
@@ -908,7 +1000,7 @@ class Engine:
                 ok = int(stat[w]) == WIN_CONSENSUS
                 parts.append(cons[int(coff[w]) : int(coff[w]) + int(clen[w])].tobytes().decode() if ok else ref[t * window : (t + 1) * window])
                 wins.append(PolishWindow(int(members[w]), int(stat[w]), not ok))
-            out.append(Polished("".join(parts), wins))
+            out.append(Polished("".join(parts), wins, read_strands[g]))
         return out
 
     def extract_piles(self, reads, overlaps, jobs, k):

@@ -20,7 +20,10 @@
  *                               counterpart: alignmentWindows.cpp cuts by shifting PAF coordinates, without an alignment).
  *   cw_cut_groups_device     <- those pieces as the POA batch of every (reference, window): what stands between the aligner and cw_poa_run_device when a
  *                               reference is polished window by window.
- *   cw_window_positions      <- getAlignmentWindowsPositions (alignmentWindows.cpp:27-85), host
+ *   cw_strand_run / cw_strand_run_device <- which queries of such groups are the reverse complement of their reference, by shared k-mers (no counterpart
+ *                               here either: the reference takes the strand from the PAF record, Overlap.h:26-58).
+ *   cw_revcomp / cw_revcomp_device <- the batch with those queries reverse-complemented, for any of the runs above.
+ *   cw_window_positions     <- getAlignmentWindowsPositions (alignmentWindows.cpp:27-85), host
  *   cw_extract_piles_device  <- getAlignmentWindowsSequences (alignmentWindows.cpp:87-149) evaluated on the device
  *   cw_stitch_device         <- alignConsensus + trimRead + dropRead (correctionAlignment.cpp:47-140, utils.cpp:96-128, :71-73)
  *   cw_index_reads / cw_paf_next_pile <- indexReads (utils.cpp:166-205) / getNextReadPile (alignmentPiles.cpp:22-58), host
@@ -364,6 +367,55 @@ int cw_cut_groups_device(cw_engine* e, const cw_batch* groups, const int32_t* ro
                          uint32_t* win_first_seq, uint32_t* seq_len, uint64_t* seq_word_off, uint32_t* bases,
                          uint32_t group_cap, uint32_t seq_cap, uint64_t word_cap,
                          uint32_t* n_groups, uint32_t* n_seqs, uint64_t* n_words, void* hip_stream);
+
+/* ---- both strands for the alignment operators: cw_strand_run, cw_revcomp ----------------------------------------------------------------------------------------
+ * The runs above align a query as it is given.  In a long-read set half the reads are the reverse complement of their reference; these two orient a batch of
+ * groups on the device: a strand vote per (query, reference) pair -- shared k-mers in both orientations, O(m + n) a pair where the aligner costs O(m n) -- and a
+ * reverse complement over the packed layout, which writes the oriented batch.  Reverse complement keeps every length: the oriented batch shares win_first_seq,
+ * seq_len and seq_word_off with the input, only `bases` is new, and every run above takes it unchanged.
+ *
+ * cw_strand_run.  `groups` is read as in cw_sw_run: the first sequence of a group is its reference, the others are queries; params.* is not read.  With k =
+ * out->k (0 = CW_STRAND_K), K the SET of the reference's k-mers (2-bit codes, first base most significant; a non-ACGT letter is already packed as T), m the
+ * query's length:
+ *   hits[2s]     the query positions i in 0 .. m - k whose k-mer is in K: positions count with multiplicity, K is a set
+ *   hits[2s+1]   those whose k-mer's reverse complement is in K -- the forward hits of the reverse-complemented query
+ *   strand[s]    CW_STRAND_REV when reverse hits > forward hits, else CW_STRAND_FWD: ties go forward, both zero included
+ *   CW_STRAND_IS_REF, hits 0, 0   the reference's own entry
+ *   CW_STRAND_NONE, hits 0, 0     no vote is possible: the query or the reference is shorter than k (empty included), the query longer than CW_SW_QMAX or the
+ *                                 reference longer than CW_SW_RMAX -- the aligner's own capacities; there is no CW_E_CAPACITY from this run: the alignment run
+ *                                 that follows reports those pairs
+ * Membership is exact (the table holds the k-mers themselves and compares them), and every number is a function of the pair and k alone: it depends on no batch
+ * composition, order or run.  hits may be NULL.
+ * CW_E_INVALID, before anything is launched: NULL groups / out / out->strand, k other than 0 or CW_STRAND_KMIN .. CW_STRAND_KMAX, more than
+ * cw_max_batch_windows(e) groups.  n_seqs == 0 is CW_OK.  The scratch plan is exact (two counters and a word a group): the batch runs once.
+ * cw_strand_run_device: every pointer inside groups and out is a DEVICE pointer; asynchronous on `hip_stream` (NULL = the engine's own), under cw_run_device's
+ * threading and stream contract.  cw_strand_run: host pointers, synchronous.
+ * Such runs alternate freely with every other kind of run on one engine.  cw_last_timings names the stages strand_order (the units of work: a group's queries in
+ * chunks, so that one group of very many queries spreads over the device), strand (references of up to 2 048 bases), strand_wide (beyond).
+ *
+ * cw_revcomp.  For every sequence s of the batch the words bases_out[seq_word_off[s] .. + ceil(len / 16)) are written:
+ *   strand[s] == CW_STRAND_REV   out base j = 3 - in base (len - 1 - j), the unused low bits of the last word zero
+ *   any other value              the words are copied
+ * strand == NULL: every sequence is reversed.  A flagged reference is reversed too (cw_strand_run never flags one).  Words of bases_out that belong to no
+ * sequence are never written.  bases_out must not be groups->bases: CW_E_INVALID when the two pointers are equal; any other overlap of bases_out with the
+ * batch's arrays is the caller's responsibility (a sequence's words are read while another's are written).  CW_E_INVALID also for NULL groups or bases_out, more
+ * than cw_max_batch_windows(e) groups; n_seqs == 0 is CW_OK.  cw_revcomp_device: device pointers (strand too), asynchronous on `hip_stream`, the contract above;
+ * it uses no scratch.  cw_revcomp: host pointers, synchronous.  cw_last_timings names the one stage revcomp.
+ * Coordinates in rows, CIGARs, pileups and cuts computed from an oriented batch are the ORIENTED query's: position i there is position len - 1 - i of the
+ * original query. */
+enum { CW_STRAND_FWD = 0, CW_STRAND_REV = 1, CW_STRAND_IS_REF = 2, CW_STRAND_NONE = 3 }; /* strand[] values */
+#define CW_STRAND_K    11u   /* k used when cw_strands.k == 0 */
+#define CW_STRAND_KMIN 8u
+#define CW_STRAND_KMAX 15u   /* a k-mer is < 2^30: one 32-bit key with a free "empty" value */
+typedef struct cw_strands {
+    uint8_t*  strand;   /* [n_seqs] */
+    uint32_t* hits;     /* [n_seqs * 2]: forward hits, reverse hits; may be NULL */
+    uint32_t  k;        /* 0 = CW_STRAND_K, else CW_STRAND_KMIN..CW_STRAND_KMAX */
+} cw_strands;
+int cw_strand_run_device(cw_engine* e, const cw_batch* groups, const cw_strands* out, void* hip_stream);
+int cw_strand_run(cw_engine* e, const cw_batch* groups, const cw_strands* out);
+int cw_revcomp_device(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint32_t* bases_out, void* hip_stream);
+int cw_revcomp(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint32_t* bases_out);
 
 /* 1 when everything the last cw_run_device on this engine launched has completed (or nothing was launched yet), 0 while it is
  * still running, 2 while it is running but past the part that fills the GPU (what is left is the tail: a few long alignment tasks on

@@ -181,6 +181,46 @@ class Engine {
         return out;
     }
 
+    /* Both strands (cw_strand_run, cw_revcomp): every group with the members that are the reverse complement of the group's first sequence turned round, so
+       that alignToFirst and cutAtWindows see them in its orientation; strands, when given, receives [g][m], the CW_STRAND_* value of member m of group g
+       ([g][0] is CW_STRAND_IS_REF).  k = 0: CW_STRAND_K.  Positions computed from a turned member count from its other end.  (N packs as T: a turned member
+       reads A where the original had N.) */
+    std::vector<std::vector<std::string>> orientToFirst(const std::vector<std::vector<std::string>>& groups, uint32_t k = 0,
+                                                        std::vector<std::vector<uint8_t>>* strands = nullptr) {
+        std::vector<uint32_t> wfs{0}, len, bases;
+        std::vector<uint64_t> off;
+        for (const auto& group : groups) {
+            for (const auto& s : group) {
+                const uint64_t words = (s.size() + 15) / 16;
+                off.push_back(bases.size());
+                len.push_back((uint32_t)s.size());
+                bases.resize(bases.size() + words);
+                if (words && cw_pack_sequence(s.data(), (uint32_t)s.size(), bases.data() + off.back(), words) < 0)
+                    throw std::runtime_error("consent_amd: cw_pack_sequence failed");
+            }
+            wfs.push_back((uint32_t)len.size());
+        }
+        bases.push_back(0);
+        std::vector<uint8_t> strand(len.size() + 1);
+        std::vector<uint32_t> turned(bases.size());
+        cw_batch b{(uint32_t)groups.size(), (uint32_t)len.size(), (uint64_t)bases.size() - 1, wfs.data(), len.data(), off.data(), bases.data()};
+        cw_strands votes{strand.data(), nullptr, k};
+        int rc = cw_strand_run(eng_, &b, &votes);
+        if (rc != CW_OK) throw std::runtime_error(std::string("consent_amd: cw_strand_run: ") + cw_strerror(rc));
+        if ((rc = cw_revcomp(eng_, &b, strand.data(), turned.data())) != CW_OK) throw std::runtime_error(std::string("consent_amd: cw_revcomp: ") + cw_strerror(rc));
+        std::vector<std::vector<std::string>> out(groups.size());
+        if (strands) strands->assign(groups.size(), {});
+        for (size_t g = 0; g < groups.size(); ++g)
+            for (uint32_t s = wfs[g]; s < wfs[g + 1]; ++s) {
+                if (strands) (*strands)[g].push_back(strand[s]);
+                if (strand[s] != CW_STRAND_REV) { out[g].push_back(groups[g][s - wfs[g]]); continue; }
+                std::string t(len[s], 'A');
+                for (uint32_t j = 0; j < len[s]; ++j) t[j] = "ACGT"[(turned[off[s] + (j >> 4)] >> (30 - 2 * (j & 15))) & 3u];
+                out[g].push_back(t);
+            }
+        return out;
+    }
+
   private:
     cw_engine* eng_ = nullptr;
     unsigned solid_;

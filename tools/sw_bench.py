@@ -18,6 +18,7 @@ reference length: the forward sweep's; the reverse sweep and the traceback come 
     python tools/sw_bench.py --path                       # a third measurement per shape: the path run
     python tools/sw_bench.py --pileup                     # a fourth beside it: the pileup run of the same batch, and the shape 500x600x30
     python tools/sw_bench.py --cut                        # a fifth: the cut run of the same batch at --window columns a window, on the shapes of --pileup
+    python tools/sw_bench.py --strand                     # instead: the strand vote and the reverse complement beside the plain run and a device copy of the same batch
     python tools/sw_bench.py --oracle 4096                # also: so many 500 x 600 pairs through the oracle's cwo_ssw on --threads CPU threads
 
 Prints one JSON line per measurement and a markdown table (DESIGN.md section 4.8 holds the first one, from a --path run).
@@ -36,11 +37,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import consent_amd as ca  # noqa: E402
-from consent_amd.engine import Batch, HostBatch, Pileup, SwCuts, SwPaths, sw_cuts  # noqa: E402
+from consent_amd.engine import Batch, HostBatch, Pileup, Strands, SwCuts, SwPaths, sw_cuts  # noqa: E402
 
 SHAPES = {"24x150": 262144, "100x600": 131072, "500x600": 65536, "2000x2048": 4096, "8000x2048": 512, "1540x1540": 2048}  # query x reference -> pairs of the default run
 PLANTED = {"1540x1540": (500, 40)}  # shapes built as planted pairs: (part, g)
 DEEP = {"500x600x30": 61440}  # query x reference x queries per reference: what --pileup adds
+WIDE_GROUP = {"500x2048": 16384, "500x2048x16384": 16384}  # what --strand adds: 16 queries a reference, and ONE reference with all 16 384 queries -- equal lengths
 PATH, PILE, CUT = "path", "pileup", "cut"  # the third, fourth and fifth mode beside flags 0 and CW_SW_WANT_INDELS
 
 
@@ -172,6 +174,80 @@ def bench_shape(eng, shape, n_pairs, per_group, flags, steps, warmup, seed, wind
             "stage_ms": {k: round(float(np.median(v)), 3) for k, v in stages.items()}}
 
 
+def device_copy(dst, src, n_bytes):
+    """hipMemcpyAsync device to device on the null stream, through the HIP runtime this process has loaded: the yardstick of the reverse complement."""
+    global _HIP
+    if _HIP is None:
+        _HIP = C.CDLL("libamdhip64.so")
+        _HIP.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    rc = _HIP.hipMemcpyAsync(dst, src, n_bytes, 3, None)  # 3: hipMemcpyDeviceToDevice
+    if rc != 0:
+        raise RuntimeError(f"hipMemcpyAsync: {rc}")
+
+
+_HIP = None
+
+
+def bench_strand(eng, shape, n_pairs, per_group, steps, warmup, seed):
+    """One batch in device memory, four measurements in this process: the plain cw_sw_run_device, cw_strand_run_device, cw_revcomp_device of every sequence
+    (strand NULL: the most it can be asked for) and a device-to-device copy of the batch's words.  Per measurement the median of `steps` with the lowest and the
+    highest, wall clock around the call and the wait for it, and the device's own time: between the run's first and last event for the plain and the strand run,
+    between the two events around the one launch for the reverse complement (its stage) and for the copy (HIP events on its stream)."""
+    import torch
+
+    qlen, rlen, *deep = (int(v) for v in shape.split("x"))
+    per_group = deep[0] if deep else per_group
+    hb = make_planted(n_pairs, *PLANTED[shape], seed) if shape in PLANTED else make_groups(n_pairs, qlen, rlen, per_group, seed)[0]
+    S, G, W = len(hb.seq_len), hb.n_windows, len(hb.bases)
+    n_pairs = S - G
+    dev = torch.device("cuda", eng.device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
+
+    t_in = (up(hb.win_first_seq, np.int32), up(hb.seq_len, np.int32), up(hb.seq_word_off, np.int64), up(np.concatenate([hb.bases, np.zeros(4, np.uint32)]), np.int32))
+    t_rows = torch.zeros(S * 8, dtype=torch.int32, device=dev)
+    t_strand = torch.zeros(S, dtype=torch.uint8, device=dev)
+    t_hits = torch.zeros(2 * S, dtype=torch.int32, device=dev)
+    t_out = torch.zeros(W + 4, dtype=torch.int32, device=dev)
+    b = Batch(G, S, W, t_in[0].data_ptr(), t_in[1].data_ptr(), t_in[2].data_ptr(), t_in[3].data_ptr())
+    votes = Strands(t_strand.data_ptr(), t_hits.data_ptr(), 0)
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    torch.cuda.synchronize(dev)
+
+    def copy_words():
+        ev[0].record()
+        device_copy(t_out.data_ptr(), t_in[3].data_ptr(), W * 4)
+        ev[1].record()
+
+    runs = {"sw": lambda: eng.sw_device(b, C.c_void_p(t_rows.data_ptr()), 0), "strand": lambda: eng.strand_device(b, votes),
+            "revcomp": lambda: eng.revcomp_device(b, None, t_out.data_ptr()), "copy": copy_words}
+    out, stages = {}, {}
+    for name, run in runs.items():
+        wall, device = [], []
+        for step in range(warmup + steps):
+            t0 = time.perf_counter()
+            run()
+            torch.cuda.synchronize(dev)
+            if step >= warmup:
+                wall.append((time.perf_counter() - t0) * 1e3)
+                # (the reverse complement is one launch between its stage's two events, as the copy is one call between two events: like with like)
+                device.append(ev[0].elapsed_time(ev[1]) if name == "copy" else eng.timings()["revcomp" if name == "revcomp" else "total"])
+                if name == "strand":
+                    for k, v in eng.timings().items():
+                        stages.setdefault(k, []).append(v)
+        out[name] = {"wall_ms": [round(float(np.median(wall)), 4), round(min(wall), 4), round(max(wall), 4)],
+                     "device_ms": [round(float(np.median(device)), 4), round(min(device), 4), round(max(device), 4)]}
+    strand = t_strand.cpu().numpy()
+    is_q = np.ones(S, bool)
+    is_q[hb.win_first_seq[:-1]] = False
+    assert (strand[~is_q] == ca.STRAND_IS_REF).all() and (strand[is_q] != ca.STRAND_IS_REF).all()
+    return {"shape": shape, "mode": "strand", "pairs": n_pairs, "groups": G, "words": W, "steps": steps, **out,
+            "strand_over_sw": round(out["strand"]["device_ms"][0] / out["sw"]["device_ms"][0], 4), "revcomp_over_copy": round(out["revcomp"]["device_ms"][0] / max(out["copy"]["device_ms"][0], 1e-6), 3),
+            "strand_ns_per_pair": round(out["strand"]["device_ms"][0] * 1e6 / n_pairs, 2), "forward": int((strand == ca.STRAND_FWD).sum()), "reverse": int((strand == ca.STRAND_REV).sum()),
+            "none": int((strand == ca.STRAND_NONE).sum()), "stage_ms": {k: round(float(np.median(v)), 4) for k, v in stages.items()}}
+
+
 def oracle_rate(n_pairs, threads, seed):
     """n_pairs 500 x 600 pairs of the same construction through the oracle's cwo_ssw (oracle/liboracle.so) on `threads` threads: pairs/s, cells/s."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -207,6 +283,8 @@ def main():
     ap.add_argument("--path", action="store_true", help="also time the path run (cw_sw_path_run_device) on every shape")
     ap.add_argument("--pileup", action="store_true", help="time the path run and the pileup run (cw_pileup_run_device) of the same batch on every shape, and on 500x600x30")
     ap.add_argument("--cut", action="store_true", help="time the path run, the pileup run and the cut run (cw_sw_cut_run_device) of the same batch on the shapes of --pileup")
+    ap.add_argument("--strand", action="store_true", help="instead of the alignment modes: cw_strand_run_device and cw_revcomp_device beside the plain run and a device-to-device copy of the same "
+                    "batch, on the shapes of --cut, on 500x2048 and on one group of a 2 048-base reference with 16 384 queries of 500 bases")
     ap.add_argument("--window", type=int, default=100, help="reference columns a window of the cut run")
     ap.add_argument("--oracle", type=int, default=0, help="also time so many 500x600 pairs through the oracle on --threads CPU threads")
     ap.add_argument("--threads", type=int, default=16)
@@ -214,6 +292,19 @@ def main():
     a.pileup = a.pileup or a.cut
     eng = ca.Engine(ca.Params(9, 4, 8, 2, 150), device=a.device)
     rows = []
+    if a.strand:
+        try:
+            for shape in a.shape or list(SHAPES) + list(DEEP) + list(WIDE_GROUP):
+                rows.append(bench_strand(eng, shape, a.pairs or SHAPES.get(shape) or DEEP.get(shape) or WIDE_GROUP.get(shape, 16384), a.per_group, a.steps, a.warmup, a.seed))
+                print(json.dumps(rows[-1]), flush=True)
+        finally:
+            eng.close()
+        cell = lambda m: f"{m['device_ms'][0]:.3f} ({m['device_ms'][1]:.3f} - {m['device_ms'][2]:.3f})"
+        print("\n| query x reference | pairs | plain run ms | strand run ms | strand / plain | ns / pair | reverse complement ms | device copy ms | revcomp / copy |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['shape']} | {r['pairs']} | {cell(r['sw'])} | {cell(r['strand'])} | {r['strand_over_sw']:.4f} | {r['strand_ns_per_pair']:.1f} | {cell(r['revcomp'])} | {cell(r['copy'])} | {r['revcomp_over_copy']:.2f} |")
+        return
     try:
         for shape in a.shape or list(SHAPES) + (list(DEEP) if a.pileup else []):
             for flags in (0, ca.SW_WANT_INDELS) + ((PATH,) if a.path or a.pileup else ()) + ((PILE,) if a.pileup else ()) + ((CUT,) if a.cut else ()):
