@@ -6,7 +6,8 @@
  * cw_wait) and the loop that runs a batch again with a larger plan (cw_run, cw_run_device_sync); the POA stage alone on a batch of groups (cw_poa_run_device,
  * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run); the re-assembly's local aligner alone on a batch of groups
  * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h; cw_pileup_run_device, cw_pileup_run: cw_pileup.h; cw_sw_cut_run_device, cw_sw_cut_run,
- * cw_cut_groups_device: cw_sw_cut.h); both strands for them (cw_strand_run_device, cw_strand_run, cw_revcomp_device, cw_revcomp: cw_strand.h).
+ * cw_cut_groups_device: cw_sw_cut.h); both strands for them (cw_strand_run_device, cw_strand_run, cw_revcomp_device, cw_revcomp: cw_strand.h); reads placed on
+ * their reference (cw_seed_run_device, cw_seed_run: cw_seed.h).
  * The scratch plan is cw_plan.h (host arithmetic only); the host feeders, cw_window_positions among them, are cw_hostio.cpp.
  */
 #include "cw_internal.h"
@@ -27,6 +28,7 @@
 #include "cw_pileup.h"
 #include "cw_sw_cut.h"
 #include "cw_strand.h"
+#include "cw_seed.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -60,6 +62,7 @@ constexpr size_t kLdsStitch = (size_t)CW_ST_WAVES * CW_ST_SLAB; /* what the wide
 constexpr size_t lds_sw(int cls) { return (size_t)CW_SW_WAVES * (cls == 0 ? CW_SW_SLAB_OF(CW_SW_Q0) : CW_SW_SLAB_OF(CW_ST_QMAX)); } /* the alignment operator's two LDS instances */
 static_assert(4 * lds_sw(0) <= 163840, "cw_sw_kernel<0>: the four work-groups a CU its 128 registers allow");
 constexpr size_t kLdsStrandWide = (size_t)CW_STR_SLOTS_WIDE * 4; /* the strand vote's wide table (the narrow one is static) */
+constexpr size_t kLdsSeedWide = (size_t)CW_SEED_LDS_WORDS(CW_STR_SLOTS_WIDE, CW_SW_RMAX, CW_SEED_THREADS_WIDE) * 4; /* the seed run's wide table, reference words and histograms (the narrow ones are static) */
 
 /* tiers M1, M2 and L are instances of cw_poa_slab_kernel: a tier's template arguments and the LDS of its work-group, PASS 0 = its own list, 1 = the overflow pass */
 template <int NC, int EC, int LC, int WAVES, int TIER, size_t LDS>
@@ -123,7 +126,7 @@ int set_kernel_attributes(const hipDeviceProp_t& prop) {
         allow((const void*)cw_sw_path_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_path_kernel<1>, lds_sw(1)) &&
         allow((const void*)cw_pileup_kernel<0>, lds_sw(0)) && allow((const void*)cw_pileup_kernel<1>, lds_sw(1)) &&
         allow((const void*)cw_sw_cut_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_cut_kernel<1>, lds_sw(1)) &&
-        allow((const void*)cw_strand_kernel<1>, kLdsStrandWide);
+        allow((const void*)cw_strand_kernel<1>, kLdsStrandWide) && allow((const void*)cw_seed_kernel<1>, kLdsSeedWide);
     return ok ? CW_OK : CW_E_NO_DEVICE;
 }
 
@@ -697,6 +700,42 @@ int run_strand_locked(cw_engine* e, const cw_batch* groups, const cw_strands* ou
     return CW_OK;
 }
 
+int validate_seed(const cw_engine* e, const cw_batch* groups, const cw_seeds* out) {
+    if (!e || !groups || !out || !out->rows) return CW_E_INVALID;
+    if (out->k != 0u && (out->k < CW_STRAND_KMIN || out->k > CW_STRAND_KMAX)) return CW_E_INVALID;
+    return validate_groups(e, groups, out->rows);
+}
+
+/* the body of cw_seed_run_device; the caller holds e->mu.  Stages: strand_order (the strand run's units kernel as it is: it reads the batch, unit_off and ctr),
+   seed (references of up to CW_ST_RMAX bases), seed_wide (beyond). */
+int run_seed_locked(cw_engine* e, const cw_batch* groups, const cw_seeds* out, void* hip_stream) {
+    int rc = validate_seed(e, groups, out);
+    if (rc || groups->n_seqs == 0) return rc;
+    const StrandPlan p = plan_seed(groups->n_windows, groups->n_seqs, e->cus); /* exact: the batch runs once */
+    hipStream_t st;
+    if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
+    uint8_t* base = (uint8_t*)e->scratch;
+    SeedArgs a;
+    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.n_seqs = groups->n_seqs; a.rows = out->rows; a.strand = out->strand; a.k = out->k ? out->k : CW_STRAND_K;
+    a.ctr = (uint32_t*)(base + p.ctr); a.unit_off = (uint32_t*)(base + p.unit_off);
+    StrandArgs units; /* what cw_strand_units_kernel reads of it: the batch, unit_off and ctr */
+    units.b = a.b; units.n_seqs = a.n_seqs; units.strand = nullptr; units.hits = nullptr; units.k = a.k;
+    units.ctr = a.ctr; units.unit_off = (uint32_t*)(base + p.unit_off);
+    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (enqueue_sw_run) */
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_STR_CTR_WORDS * 4, st));
+    stage(e, st, "strand_order", [&] { cw_strand_units_kernel<<<1, 1024, 0, st>>>(units); });
+    stage(e, st, "seed", [&] { cw_seed_kernel<0><<<p.wgs, CW_STR_THREADS, 0, st>>>(a); });
+    stage(e, st, "seed_wide", [&] { cw_seed_kernel<1><<<p.wgs_wide, CW_SEED_THREADS_WIDE, kLdsSeedWide, st>>>(a); });
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
+}
+
 /* the body of cw_revcomp_device.  One stage: revcomp.  No scratch: what the engine's scratch holds stays what it was. */
 int run_revcomp_locked(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint32_t* bases_out, void* hip_stream) {
     int rc = validate_revcomp(e, groups, bases_out);
@@ -1069,6 +1108,37 @@ int cw_strand_run(cw_engine* e, const cw_batch* b, const cw_strands* out) {
     return CW_OK;
 }
 
+int cw_seed_run_device(cw_engine* e, const cw_batch* groups, const cw_seeds* out, void* hip_stream) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_seed_locked(e, groups, out, hip_stream);
+}
+
+/* Host buffers in, host buffers out, synchronous, as cw_strand_run: the batch goes up, cw_seed_run_device on the engine's stream, the rows and -- when asked
+   for -- the strand bytes come back. */
+int cw_seed_run(cw_engine* e, const cw_batch* b, const cw_seeds* out) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = validate_seed(e, b, out);
+    if (rc || b->n_seqs == 0) return rc;
+    const uint32_t S = b->n_seqs;
+    cw_batch db;
+    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
+    const size_t row_bytes = (size_t)S * CW_SEED_ROW * 4, o_strand = align_up(row_bytes, 256), out_bytes = o_strand + (out->strand ? (size_t)S : 0);
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
+    hipStream_t st = e->stream;
+    uint8_t* dout = (uint8_t*)e->poa_out;
+    cw_seeds ds;
+    ds.rows = (int32_t*)dout; ds.strand = out->strand ? dout + o_strand : nullptr; ds.k = out->k;
+    if ((rc = run_seed_locked(e, &db, &ds, st)) != CW_OK) return rc;
+    CW_HIP(hipMemcpyAsync(out->rows, ds.rows, row_bytes, hipMemcpyDeviceToHost, st));
+    if (out->strand) CW_HIP(hipMemcpyAsync(out->strand, ds.strand, (size_t)S, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    return CW_OK;
+}
+
 int cw_revcomp_device(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint32_t* bases_out, void* hip_stream) {
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1108,6 +1178,15 @@ int cw_revcomp(cw_engine* e, const cw_batch* b, const uint8_t* strand, uint32_t*
 int cw_debug_strand_plan(uint32_t n_groups, uint32_t n_seqs, int cus, uint64_t* out5) {
     if (!out5 || cus < 1) return CW_E_INVALID;
     const StrandPlan p = plan_strand(n_groups, n_seqs, cus);
+    const uint64_t v[5] = {p.total, (uint64_t)p.unit_off, (uint64_t)(p.total - p.unit_off), p.wgs, p.wgs_wide};
+    for (int i = 0; i < 5; ++i) out5[i] = v[i];
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): the same for plan_seed. */
+int cw_debug_seed_plan(uint32_t n_groups, uint32_t n_seqs, int cus, uint64_t* out5) {
+    if (!out5 || cus < 1) return CW_E_INVALID;
+    const StrandPlan p = plan_seed(n_groups, n_seqs, cus);
     const uint64_t v[5] = {p.total, (uint64_t)p.unit_off, (uint64_t)(p.total - p.unit_off), p.wgs, p.wgs_wide};
     for (int i = 0; i < 5; ++i) out5[i] = v[i];
     return CW_OK;

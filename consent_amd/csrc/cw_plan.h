@@ -12,6 +12,7 @@
 #include "cw_poa_q.h"  /* slab and graph sizes of every tier (cw_poa.h comes with it) */
 #include "cw_sw_path.h" /* the alignment operator's per-wave sizes, the path run's too (cw_sw_op.h and cw_stitch.h come with it) */
 #include "cw_strand.h" /* the strand vote's chunk sizes */
+#include "cw_seed.h"   /* the seed run's LDS, which bounds its work-groups a CU */
 #include "cw_finish.h" /* CW_FIN_*.  (These three are kernel headers, taken for their size macros: nothing here runs on the device, but a translation unit that includes this one is still a HIP one) */
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -265,6 +266,14 @@ static inline StrandPlan plan_strand(uint32_t n_groups, uint32_t n_seqs, int cus
     put(p.ctr, (size_t)CW_STR_CTR_WORDS * 4);
     put(p.unit_off, ((size_t)n_groups + 1) * 4);
     p.total = o;
+    return p;
+}
+
+/* The plan of a seed run (cw_seed_run, cw_seed.h) is plan_strand's arithmetic: the same counters, units and chunks.  Only the narrow launch is smaller: 25 KB
+   of LDS a work-group allow six a CU, not eight. */
+static inline StrandPlan plan_seed(uint32_t n_groups, uint32_t n_seqs, int cus) {
+    StrandPlan p = plan_strand(n_groups, n_seqs, cus);
+    p.wgs = (uint32_t)std::min<uint64_t>(p.wgs, (uint64_t)cus * 6u);
     return p;
 }
 

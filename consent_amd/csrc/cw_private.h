@@ -54,6 +54,8 @@ int cw_debug_sw_path_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, 
 /* The scratch plan of a strand run (cw_strand_run) of n_groups groups and n_seqs sequences, without a device: out[0] total bytes, [1] the claim counters and class
    totals, [2] the first unit of every group, [3] [4] work-groups of the narrow and the wide launch. */
 int cw_debug_strand_plan(uint32_t n_groups, uint32_t n_seqs, int cus, uint64_t* out5);
+/* The same of a seed run (cw_seed_run): plan_strand's arithmetic, the narrow launch at most six work-groups a CU. */
+int cw_debug_seed_plan(uint32_t n_groups, uint32_t n_seqs, int cus, uint64_t* out5);
 /* cw_max_batch_windows of an engine that cw_configure(max_template_len) will be called on (the native driver sizes its jobs before it has engines) */
 uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len);
 

@@ -29,6 +29,11 @@ SW_CUT_SLOT = 8
 # cw_strand_run: a sequence's strand value, the default k and its range
 STRAND_FWD, STRAND_REV, STRAND_IS_REF, STRAND_NONE = 0, 1, 2, 3
 STRAND_K, STRAND_KMIN, STRAND_KMAX = 11, 8, 15
+# cw_seed_run: a row's columns, the bin shift, the diagonals of a window; Engine.place's default threshold (its docstring has the measurement)
+SEED_STATUS, SEED_HITS, SEED_DIAG, SEED_OTHER, SEED_ROW = 0, 1, 2, 3, 4
+SEED_SHIFT = 6
+SEED_SPAN = 2 << SEED_SHIFT
+SEED_MIN_HITS, SEED_MIN_K = 14, 11  # (the threshold holds from this k up)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -87,6 +92,12 @@ class Strands(C.Structure):
     """cw_strands: the outputs of cw_strand_run (hits may be NULL) and k (0 = STRAND_K)."""
 
     _fields_ = [("strand", C.c_void_p), ("hits", C.c_void_p), ("k", C.c_uint32)]
+
+
+class Seeds(C.Structure):
+    """cw_seeds: the outputs of cw_seed_run (strand may be NULL) and k (0 = STRAND_K)."""
+
+    _fields_ = [("rows", C.c_void_p), ("strand", C.c_void_p), ("k", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -205,6 +216,10 @@ def _load(p):
         lib.cw_revcomp.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]
         lib.cw_revcomp_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p]
         lib.cw_debug_strand_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
+    if hasattr(lib, "cw_seed_run"):
+        lib.cw_seed_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Seeds)]
+        lib.cw_seed_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Seeds), C.c_void_p]
+        lib.cw_debug_seed_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
     lib.cw_submit.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.POINTER(C.c_int)]
     lib.cw_wait.argtypes = [C.c_void_p, C.c_int]
     lib.cw_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -647,6 +662,30 @@ class StrandRows:
         return int(f), int(r)
 
 
+class SeedRows(SwRows):
+    """What Engine.seeds returns: `rows`, an (n_seqs, SEED_ROW) int32 array -- SEED_STATUS (a STRAND_* value), SEED_HITS, SEED_DIAG, SEED_OTHER -- `strands`, the
+    status bytes as cw_revcomp takes them, and .row(group, member) as SwRows has it."""
+
+    def __init__(self, rows, strands, win_first_seq, k):
+        super().__init__(rows, win_first_seq)
+        self.strands, self.k = strands, k
+
+
+class Placement:
+    """One read of Engine.place: `strand` (STRAND_FWD, or STRAND_REV: its reverse complement lies on the reference), `position`, the lowest reference
+    coordinate of the densest 128 diagonals -- where the read, turned when REV, begins, give or take its indels; negative when it overhangs the start --
+    `hits`, the unique k-mers it shares with the reference there, and `other`, the best the other orientation found."""
+
+    def __init__(self, strand, position, hits, other):
+        self.strand, self.position, self.hits, self.other = strand, position, hits, other
+
+    def __eq__(self, o):
+        return isinstance(o, Placement) and (self.strand, self.position, self.hits, self.other) == (o.strand, o.position, o.hits, o.other)
+
+    def __repr__(self):
+        return f"Placement(strand={self.strand}, position={self.position}, hits={self.hits}, other={self.other})"
+
+
 class PolishWindow:
     """One window of a polished reference: `members` pieces were aligned beside the reference's own; `status` is the POA's (WIN_CONSENSUS, or WIN_OVERFLOW
     for a group that stopped: `kept_reference` is then True and the window's part of the result is the reference's columns)."""
@@ -660,10 +699,18 @@ class PolishWindow:
 
 class Polished:
     """One reference of Engine.polish: `sequence`, the windows' consensuses joined in order, `windows`, a PolishWindow each, and `strands`, the strand value of
-    every read of the group under orient=True (empty without)."""
+    every read of the group under orient=True (empty without).  From Engine.polish_reads: `placements`, a Placement or None per read (empty otherwise)."""
 
-    def __init__(self, sequence, windows, strands=None):
+    def __init__(self, sequence, windows, strands=None, placements=None):
         self.sequence, self.windows, self.strands = sequence, windows, [] if strands is None else strands
+        self.placements = [] if placements is None else placements
+
+
+_COMPLEMENT = str.maketrans("ACGTacgtNn", "TGCAtgcaAA")  # (N is packed as T: its complement is A, as cw_revcomp has it)
+
+
+def _revcomp(s):
+    return s.translate(_COMPLEMENT)[::-1]
 
 
 def _result_struct(r):
@@ -910,6 +957,85 @@ class Engine:
         batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
         rows = self.strands(batch, k)
         return self.revcomp(batch, rows.strands), rows
+
+    def seeds(self, groups, k=0):
+        """Where every query lies on its reference (cw_seed_run): `groups` as for sw().  Per query, over the k-mers that occur exactly once in its reference
+        (k = 0: STRAND_K; else STRAND_KMIN .. STRAND_KMAX), the 128 neighbouring diagonals that hold the most of them, as given and reverse-complemented.
+        Returns SeedRows: .row(group, member) is (SEED_STATUS: STRAND_FWD / STRAND_REV of the better orientation, STRAND_IS_REF, STRAND_NONE; SEED_HITS: the
+        hits in that window; SEED_DIAG: its lowest diagonal, reference position minus position in the oriented query; SEED_OTHER: the other orientation's
+        best), .strands the status bytes, what revcomp() takes."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        S = len(batch.seq_len)
+        rows = np.zeros((max(S, 1), SEED_ROW), np.int32)
+        strand = np.zeros(max(S, 1), np.uint8)
+        b = batch.c_struct()
+        out = Seeds(_ptr(rows), _ptr(strand), k)
+        _check(self.lib, self.lib.cw_seed_run(self.handle, C.byref(b), C.byref(out)), "cw_seed_run")
+        return SeedRows(rows[:S], strand[:S], batch.win_first_seq, k)
+
+    def seed_device(self, batch_struct, seeds_struct, stream=None):
+        """cw_seed_run_device: device pointers in the batch struct and in `seeds_struct` (Seeds); asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_seed_run_device(self.handle, C.byref(batch_struct), C.byref(seeds_struct), stream), "cw_seed_run_device")
+
+    @staticmethod
+    def _tiles(reference, tile):
+        tile = int(tile)
+        if not 1 <= tile <= SW_RMAX:
+            raise EngineError(f"tile must be 1 .. {SW_RMAX} bases")
+        return [reference[a : a + tile] for a in range(0, len(reference), tile)]
+
+    def place(self, reference, reads, tile=8192, k=0, min_hits=None):
+        """Every read of `reads` (ACGT strings, either strand, any order) placed on `reference`, a string of any length: the reference is cut into tiles of
+        `tile` bases (at most SW_RMAX; the last one shorter), one group per tile holds the tile and ALL reads -- the reads' words are packed once and shared
+        by the groups -- and one cw_seed_run votes every (read, tile) pair: O(tiles x reads) votes of O(read + tile) each.  Per read the tile with the most
+        hits wins, ties to the lowest tile.  Returns a list with one Placement(strand, position = tile start + SEED_DIAG, hits, other) per read, or None where
+        its best hits are below min_hits.
+        min_hits=None is SEED_MIN_HITS = 14, twice a measured chance level: over the 45 unrelated random pairs of tests/test_seed_cpu.py -- random reads of
+        300 to 5 000 bases against random tiles of up to 8 192 bases, and 32 768 random bases against 16 383 -- the plain reference's largest SEED_HITS at the
+        default k = 11 is 7 (1 at k = 15), while its planted reads of 300 to 5 000 bases at 10 - 12 % errors have 104 or more (46 at k = 15).  A random k-mer
+        is four times rarer with every base of k, so the default holds from k = SEED_MIN_K = 11 up.  Below it does not (46 at k = 8): EngineError unless
+        min_hits is given."""
+        tiles = self._tiles(reference, tile)
+        reads = list(reads)
+        if min_hits is None and 0 < int(k) < SEED_MIN_K:
+            raise EngineError(f"place: the default min_hits is measured for k >= {SEED_MIN_K}; give min_hits with k = {k}")
+        T, R = len(tiles), len(reads)
+        if T == 0 or R == 0:
+            return [None] * R
+        if T > self.max_batch_windows():
+            raise EngineError(f"place: {T} tiles exceed the {self.max_batch_windows()} groups of a run; use a longer tile")
+        once = pack_piles([tiles + reads])  # every sequence packed once; group g is tile g and the reads' entries again
+        pick = np.concatenate([np.concatenate([[g], T + np.arange(R)]) for g in range(T)]).astype(np.int64)
+        batch = HostBatch(np.arange(T + 1, dtype=np.uint32) * np.uint32(R + 1), once.seq_len[pick], once.seq_word_off[pick], once.bases)
+        rows = self.seeds(batch, k).rows.reshape(T, R + 1, SEED_ROW)[:, 1:, :]
+        voted = rows[:, :, SEED_STATUS] <= STRAND_REV
+        best = np.argmax(np.where(voted, rows[:, :, SEED_HITS], -1), axis=0)  # (the first of equal maxima: the lowest tile)
+        floor = SEED_MIN_HITS if min_hits is None else int(min_hits)
+        out = []
+        for r in range(R):
+            t = int(best[r])
+            status, hits, diag, other = (int(v) for v in rows[t, r])
+            out.append(Placement(status, t * int(tile) + diag, hits, other) if voted[t, r] and hits >= floor else None)
+        return out
+
+    def polish_reads(self, reference, reads, window=500, tile=8192, k=0, min_hits=None):
+        """`reference`, a contig of any length, polished from an unsorted bag of reads of either strand: place() the reads; every placed read, reverse-
+        complemented when STRAND_REV, goes to every tile its footprint [position, position + length + SEED_SPAN) meets; polish() of those groups -- the tile
+        first, its reads in the order given -- and the tiles' sequences joined.  `tile` must be a multiple of `window` (EngineError otherwise): windows then
+        never straddle tiles, and the result is the contig's polish.  Returns one Polished: .sequence, .windows of all tiles in order, and .placements, a
+        Placement or None per read.  The placing costs O(tiles x reads) votes (see place()); the polish aligns a read only against the tiles it lies on."""
+        window, tile = int(window), int(tile)
+        if window < 1 or tile % window:
+            raise EngineError("polish_reads: tile must be a multiple of window")
+        reads = list(reads)
+        placed = self.place(reference, reads, tile, k, min_hits)
+        groups = []
+        for g, t in enumerate(self._tiles(reference, tile)):
+            a = g * tile
+            groups.append([t] + [_revcomp(q) if p.strand == STRAND_REV else q for q, p in zip(reads, placed)
+                                 if p is not None and p.position < a + len(t) and p.position + len(q) + SEED_SPAN > a])
+        done = self.polish(groups, window) if groups else []
+        return Polished("".join(d.sequence for d in done), [w for d in done for w in d.windows], placements=placed)
 
     def polish(self, groups, window=500, orient=False, k=0):
         """Every group's reference (its first sequence) polished window by window from its other sequences, the reads: the reads are aligned and cut at the

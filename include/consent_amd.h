@@ -23,6 +23,8 @@
  *   cw_strand_run / cw_strand_run_device <- which queries of such groups are the reverse complement of their reference, by shared k-mers (no counterpart
  *                               here either: the reference takes the strand from the PAF record, Overlap.h:26-58).
  *   cw_revcomp / cw_revcomp_device <- the batch with those queries reverse-complemented, for any of the runs above.
+ *   cw_seed_run / cw_seed_run_device <- which queries belong to their group's reference at all, on which strand and on which diagonal, by k-mers that are
+ *                               unique in the reference (no counterpart: the reference takes all three from minimap2's PAF records).
  *   cw_window_positions     <- getAlignmentWindowsPositions (alignmentWindows.cpp:27-85), host
  *   cw_extract_piles_device  <- getAlignmentWindowsSequences (alignmentWindows.cpp:87-149) evaluated on the device
  *   cw_stitch_device         <- alignConsensus + trimRead + dropRead (correctionAlignment.cpp:47-140, utils.cpp:96-128, :71-73)
@@ -76,6 +78,9 @@ typedef struct cw_params {
  * sequence sits in word seq_word_off[s] + j/16 at bits [30-2*(j%16), 31-2*(j%16)], so that a k-mer read
  * off the words is already in str2num order.  Every sequence starts on a word boundary; unused low
  * bits of its last word are zero.
+ * Sequences may SHARE words: two entries of seq_word_off may be equal (with equal lengths, one read that is a
+ * member of several groups and packed once); the runs that take groups only read `bases`, and the host forms
+ * check every sequence against n_words on its own.  cw_revcomp writes per sequence: give it no shared words.
  */
 typedef struct cw_batch {
     uint32_t n_windows;
@@ -416,6 +421,44 @@ int cw_strand_run_device(cw_engine* e, const cw_batch* groups, const cw_strands*
 int cw_strand_run(cw_engine* e, const cw_batch* groups, const cw_strands* out);
 int cw_revcomp_device(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint32_t* bases_out, void* hip_stream);
 int cw_revcomp(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint32_t* bases_out);
+
+/* ---- reads placed on a reference by unique shared k-mers: cw_seed_run ---------------------------------------------------------------------------------------------
+ * Every run above starts from groups: somebody knew which reads belong to which reference.  This one answers that per (query, reference) pair in the strand
+ * vote's O(m + n): does the query belong here, on which strand, on which diagonal.  The vote's pass with the place of every hit kept.
+ *
+ * `groups` is read as in cw_sw_run; params.* is not read.  With k = out->k (0 = CW_STRAND_K), n the reference's length and m the query's:
+ *   U        the k-mers that occur at exactly ONE position of the reference, P(K) that position.  A k-mer that occurs twice or more seeds nothing: repeats and
+ *            homopolymer runs do not vote.
+ *   q_0, q_1 the query as given and its reverse complement
+ *   c_o[b]   the positions i in 0 .. m - k of q_o whose k-mer K is in U and whose diagonal d = P(K) - i has the bin b = (d + m) >> CW_SEED_SHIFT (d + m >= k > 0);
+ *            bins run 0 .. B - 1 with B = ((n + m) >> CW_SEED_SHIFT) + 1, and c_o[B] = 0
+ *   w_o[b]   c_o[b] + c_o[b + 1]: a window of two neighbouring bins, 128 diagonals
+ * The best (o, b) maximises w; ties go forward before reverse, then to the lowest b.  Sequence s owns rows[CW_SEED_ROW s ..):
+ *   CW_SEED_STATUS   CW_STRAND_FWD or CW_STRAND_REV, the best orientation
+ *   CW_SEED_HITS     its w
+ *   CW_SEED_DIAG     (b << CW_SEED_SHIFT) - m: the lowest of the window's 128 diagonals.  Negative where the read overhangs the reference's start.  It is the
+ *                    DENSEST window, not the read's start: a long read's diagonal drifts by its net indels, and the window holds the most of it
+ *   CW_SEED_OTHER    the best w of the other orientation
+ *   no hit at all    CW_STRAND_FWD, 0, -m, 0
+ *   CW_STRAND_IS_REF, 0, 0, 0   the reference's own row
+ *   CW_STRAND_NONE, 0, 0, 0     no vote is possible, as in cw_strand_run: the query or the reference shorter than k, the query longer than CW_SW_QMAX, the
+ *                               reference longer than CW_SW_RMAX; never CW_E_CAPACITY
+ * strand[s], when given, is the row's status byte: what cw_revcomp takes.  Membership is exact and every number is a function of the pair and k alone.
+ * CW_E_INVALID, before anything is launched: NULL groups / out / out->rows, k other than 0 or CW_STRAND_KMIN .. CW_STRAND_KMAX, more than
+ * cw_max_batch_windows(e) groups.  n_seqs == 0 is CW_OK.  The scratch plan is the strand run's; the batch runs once.
+ * cw_seed_run_device: device pointers, asynchronous on `hip_stream`, cw_strand_run_device's contract.  cw_seed_run: host pointers, synchronous.
+ * cw_last_timings names the stages strand_order, seed (references of up to 2 048 bases), seed_wide (beyond).
+ * Several groups may hold the same queries: see cw_batch on shared words.  That is how a reference longer than CW_SW_RMAX is searched -- a group per tile of
+ * it, every group the tile and all reads -- at the cost of tiles x reads votes. */
+enum { CW_SEED_STATUS, CW_SEED_HITS, CW_SEED_DIAG, CW_SEED_OTHER, CW_SEED_ROW = 4 };
+#define CW_SEED_SHIFT 6u    /* a bin is 64 diagonals; a window is two neighbouring bins */
+typedef struct cw_seeds {
+    int32_t* rows;     /* [n_seqs * CW_SEED_ROW] */
+    uint8_t* strand;   /* [n_seqs] or NULL: CW_STRAND_* values, what cw_revcomp takes */
+    uint32_t k;        /* 0 = CW_STRAND_K, else CW_STRAND_KMIN .. CW_STRAND_KMAX */
+} cw_seeds;
+int cw_seed_run_device(cw_engine* e, const cw_batch* groups, const cw_seeds* out, void* hip_stream);
+int cw_seed_run(cw_engine* e, const cw_batch* groups, const cw_seeds* out);
 
 /* 1 when everything the last cw_run_device on this engine launched has completed (or nothing was launched yet), 0 while it is
  * still running, 2 while it is running but past the part that fills the GPU (what is left is the tail: a few long alignment tasks on

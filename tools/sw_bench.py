@@ -19,6 +19,7 @@ reference length: the forward sweep's; the reverse sweep and the traceback come 
     python tools/sw_bench.py --pileup                     # a fourth beside it: the pileup run of the same batch, and the shape 500x600x30
     python tools/sw_bench.py --cut                        # a fifth: the cut run of the same batch at --window columns a window, on the shapes of --pileup
     python tools/sw_bench.py --strand                     # instead: the strand vote and the reverse complement beside the plain run and a device copy of the same batch
+    python tools/sw_bench.py --seed                       # instead: the seed run (cw_seed_run_device) beside the strand vote and the plain run of the same batch
     python tools/sw_bench.py --oracle 4096                # also: so many 500 x 600 pairs through the oracle's cwo_ssw on --threads CPU threads
 
 Prints one JSON line per measurement and a markdown table (DESIGN.md section 4.8 holds the first one, from a --path run).
@@ -37,7 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import consent_amd as ca  # noqa: E402
-from consent_amd.engine import Batch, HostBatch, Pileup, Strands, SwCuts, SwPaths, sw_cuts  # noqa: E402
+from consent_amd.engine import Batch, HostBatch, Pileup, Seeds, Strands, SwCuts, SwPaths, sw_cuts  # noqa: E402
 
 SHAPES = {"24x150": 262144, "100x600": 131072, "500x600": 65536, "2000x2048": 4096, "8000x2048": 512, "1540x1540": 2048}  # query x reference -> pairs of the default run
 PLANTED = {"1540x1540": (500, 40)}  # shapes built as planted pairs: (part, g)
@@ -248,6 +249,54 @@ def bench_strand(eng, shape, n_pairs, per_group, steps, warmup, seed):
             "none": int((strand == ca.STRAND_NONE).sum()), "stage_ms": {k: round(float(np.median(v)), 4) for k, v in stages.items()}}
 
 
+def bench_seed(eng, shape, n_pairs, per_group, steps, warmup, seed):
+    """One batch in device memory -- bench_strand's -- and three measurements in this process: the plain cw_sw_run_device, cw_strand_run_device and
+    cw_seed_run_device.  Per measurement the median of `steps` with the lowest and the highest of the device's own time, between the run's first and last
+    event, and the seed run's stages."""
+    import torch
+
+    qlen, rlen, *deep = (int(v) for v in shape.split("x"))
+    per_group = deep[0] if deep else per_group
+    hb = make_planted(n_pairs, *PLANTED[shape], seed) if shape in PLANTED else make_groups(n_pairs, qlen, rlen, per_group, seed)[0]
+    S, G, W = len(hb.seq_len), hb.n_windows, len(hb.bases)
+    n_pairs = S - G
+    dev = torch.device("cuda", eng.device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
+
+    t_in = (up(hb.win_first_seq, np.int32), up(hb.seq_len, np.int32), up(hb.seq_word_off, np.int64), up(np.concatenate([hb.bases, np.zeros(4, np.uint32)]), np.int32))
+    t_rows = torch.zeros(S * 8, dtype=torch.int32, device=dev)
+    t_strand = torch.zeros(S, dtype=torch.uint8, device=dev)
+    t_hits = torch.zeros(2 * S, dtype=torch.int32, device=dev)
+    t_seed = torch.zeros(S * ca.SEED_ROW, dtype=torch.int32, device=dev)
+    t_sbyte = torch.zeros(S, dtype=torch.uint8, device=dev)
+    b = Batch(G, S, W, t_in[0].data_ptr(), t_in[1].data_ptr(), t_in[2].data_ptr(), t_in[3].data_ptr())
+    votes, seeds = Strands(t_strand.data_ptr(), t_hits.data_ptr(), 0), Seeds(t_seed.data_ptr(), t_sbyte.data_ptr(), 0)
+    torch.cuda.synchronize(dev)
+    runs = {"sw": lambda: eng.sw_device(b, C.c_void_p(t_rows.data_ptr()), 0), "strand": lambda: eng.strand_device(b, votes), "seed": lambda: eng.seed_device(b, seeds)}
+    out, stages = {}, {}
+    for name, run in runs.items():
+        device = []
+        for step in range(warmup + steps):
+            run()
+            torch.cuda.synchronize(dev)
+            if step >= warmup:
+                device.append(eng.timings()["total"])
+                if name == "seed":
+                    for k, v in eng.timings().items():
+                        stages.setdefault(k, []).append(v)
+        out[name] = {"device_ms": [round(float(np.median(device)), 4), round(min(device), 4), round(max(device), 4)]}
+    rows = t_seed.cpu().numpy().reshape(S, ca.SEED_ROW)
+    is_q = np.ones(S, bool)
+    is_q[hb.win_first_seq[:-1]] = False
+    assert (rows[~is_q, 0] == ca.STRAND_IS_REF).all() and (rows[is_q, 0] != ca.STRAND_IS_REF).all() and np.array_equal(t_sbyte.cpu().numpy(), rows[:, 0].astype(np.uint8))
+    return {"shape": shape, "mode": "seed", "pairs": n_pairs, "groups": G, "words": W, "steps": steps, **out,
+            "seed_over_sw": round(out["seed"]["device_ms"][0] / out["sw"]["device_ms"][0], 4), "seed_over_strand": round(out["seed"]["device_ms"][0] / out["strand"]["device_ms"][0], 3),
+            "seed_ns_per_pair": round(out["seed"]["device_ms"][0] * 1e6 / n_pairs, 2), "median_hits": int(np.median(rows[is_q, 1])),
+            "stage_ms": {k: round(float(np.median(v)), 4) for k, v in stages.items()}}
+
+
 def oracle_rate(n_pairs, threads, seed):
     """n_pairs 500 x 600 pairs of the same construction through the oracle's cwo_ssw (oracle/liboracle.so) on `threads` threads: pairs/s, cells/s."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -278,13 +327,14 @@ def main():
     ap.add_argument("--per-group", type=int, default=16)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--seed", type=int, default=0x5A11)
+    ap.add_argument("--rng-seed", type=int, default=0x5A11, help="of the synthetic input")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--path", action="store_true", help="also time the path run (cw_sw_path_run_device) on every shape")
     ap.add_argument("--pileup", action="store_true", help="time the path run and the pileup run (cw_pileup_run_device) of the same batch on every shape, and on 500x600x30")
     ap.add_argument("--cut", action="store_true", help="time the path run, the pileup run and the cut run (cw_sw_cut_run_device) of the same batch on the shapes of --pileup")
     ap.add_argument("--strand", action="store_true", help="instead of the alignment modes: cw_strand_run_device and cw_revcomp_device beside the plain run and a device-to-device copy of the same "
                     "batch, on the shapes of --cut, on 500x2048 and on one group of a 2 048-base reference with 16 384 queries of 500 bases")
+    ap.add_argument("--seed", action="store_true", help="instead of the alignment modes: cw_seed_run_device beside cw_strand_run_device and the plain run of the same batch, on the shapes of --strand")
     ap.add_argument("--window", type=int, default=100, help="reference columns a window of the cut run")
     ap.add_argument("--oracle", type=int, default=0, help="also time so many 500x600 pairs through the oracle on --threads CPU threads")
     ap.add_argument("--threads", type=int, default=16)
@@ -292,10 +342,23 @@ def main():
     a.pileup = a.pileup or a.cut
     eng = ca.Engine(ca.Params(9, 4, 8, 2, 150), device=a.device)
     rows = []
+    if a.seed:
+        try:
+            for shape in a.shape or list(SHAPES) + list(DEEP) + list(WIDE_GROUP):
+                rows.append(bench_seed(eng, shape, a.pairs or SHAPES.get(shape) or DEEP.get(shape) or WIDE_GROUP.get(shape, 16384), a.per_group, a.steps, a.warmup, a.rng_seed))
+                print(json.dumps(rows[-1]), flush=True)
+        finally:
+            eng.close()
+        cell = lambda m: f"{m['device_ms'][0]:.3f} ({m['device_ms'][1]:.3f} - {m['device_ms'][2]:.3f})"
+        print("\n| query x reference | pairs | plain run ms | strand run ms | seed run ms | seed / plain | seed / strand | ns / pair |")
+        print("|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['shape']} | {r['pairs']} | {cell(r['sw'])} | {cell(r['strand'])} | {cell(r['seed'])} | {r['seed_over_sw']:.4f} | {r['seed_over_strand']:.2f} | {r['seed_ns_per_pair']:.1f} |")
+        return
     if a.strand:
         try:
             for shape in a.shape or list(SHAPES) + list(DEEP) + list(WIDE_GROUP):
-                rows.append(bench_strand(eng, shape, a.pairs or SHAPES.get(shape) or DEEP.get(shape) or WIDE_GROUP.get(shape, 16384), a.per_group, a.steps, a.warmup, a.seed))
+                rows.append(bench_strand(eng, shape, a.pairs or SHAPES.get(shape) or DEEP.get(shape) or WIDE_GROUP.get(shape, 16384), a.per_group, a.steps, a.warmup, a.rng_seed))
                 print(json.dumps(rows[-1]), flush=True)
         finally:
             eng.close()
@@ -308,12 +371,12 @@ def main():
     try:
         for shape in a.shape or list(SHAPES) + (list(DEEP) if a.pileup else []):
             for flags in (0, ca.SW_WANT_INDELS) + ((PATH,) if a.path or a.pileup else ()) + ((PILE,) if a.pileup else ()) + ((CUT,) if a.cut else ()):
-                rows.append(bench_shape(eng, shape, a.pairs or SHAPES.get(shape) or DEEP.get(shape, 16384), a.per_group, flags, a.steps, a.warmup, a.seed, a.window))
+                rows.append(bench_shape(eng, shape, a.pairs or SHAPES.get(shape) or DEEP.get(shape, 16384), a.per_group, flags, a.steps, a.warmup, a.rng_seed, a.window))
                 print(json.dumps(rows[-1]), flush=True)
     finally:
         eng.close()
     if a.oracle:
-        print(json.dumps(oracle_rate(a.oracle, a.threads, a.seed)), flush=True)
+        print(json.dumps(oracle_rate(a.oracle, a.threads, a.rng_seed)), flush=True)
     order = ["sw_order", "sw_align", "sw_align_wide", "sw_align_long", "total"] + (["pile_clear"] if a.pileup else [])
     # a path run's, a pileup run's and a cut run's stages, in the same columns
     stage_of = {PATH: {"sw_align": "sw_path", "sw_align_wide": "sw_path_wide", "sw_align_long": "sw_path_long"}, PILE: {"sw_align": "pile", "sw_align_wide": "pile_wide", "sw_align_long": "pile_long"},
