@@ -101,9 +101,11 @@ enum CwProfSlot : int {
     CW_PS_IDX_CAND = 58, CW_PS_IDX_PFILL = 59, CW_PS_IDX_CLEAN = 60, CW_PS_IDX_DIRTY = 61, CW_PS_IDX_PRESENCE = 62,
     CW_PS_IDX_ROUTE = 63,                                     /* -DCW_TEST_AIDS: the CW_IR_* bits of every window of the batch, ORed (cw_index.h; no cycles: a probe alone in its batch reads its own route) */
     CW_PS_POAH = 64,                                          /* tier H's phases */
+    CW_PS_POA_ROUTE = 69,                                     /* -DCW_TEST_AIDS: the CW_PR_* bits of every task of the batch, ORed (cw_poa.h): 69 tiers S (low word) and M1 (high word), 70 M2 and L, 71 G and X */
     CW_PS_DIAG = 72, CW_PS_DIAG_STRIDE = 12,                  /* -DCW_DIAG: row / trip counts of slab tier t (S .. L) at CW_PS_DIAG + CW_PS_DIAG_STRIDE * t (PoaMem::diag) */
     CW_PS_VERIFY_MEMBERS = 120, CW_PS_VERIFY_DIFFER = 121,    /* -DCW_POA_VERIFY: members compared, members differing ... */
-    CW_PS_VERIFY_WHERE = 122, CW_PS_VERIFY_SIZE = 123, CW_PS_VERIFY_END = 124, CW_PS_VERIFY_COLS = 125 /* ... and the first difference: window | member, columns | rows, end rows, columns */
+    CW_PS_VERIFY_WHERE = 122, CW_PS_VERIFY_SIZE = 123, CW_PS_VERIFY_END = 124, CW_PS_VERIFY_COLS = 125, /* ... and the first difference: window | member, columns | rows, end rows, columns */
+    CW_PS_POA_RC2 = 126                                       /* -DCW_TEST_AIDS: why poa_run returned 2, the CW_PR2_* bits, a byte per tier S .. X from bit 0 (cw_poa.h) */
 };
 static_assert(CW_PS_POA == 8 && CW_PS_POA_STRIDE == 5 && CW_PS_POAQ == 28 && CW_PS_POAH == 64, "phase slots: bench.py reads them by number");
 static_assert(CW_PS_POA + CW_PS_POA_STRIDE * 4 == CW_PS_POAQ, "tier G's phases share tier Q's slots");
@@ -113,6 +115,7 @@ static_assert(CW_PS_DIAG == 72 && CW_PS_DIAG_STRIDE == 12 && CW_PS_DIAG + CW_PS_
 static_assert(CW_PS_VERIFY_MEMBERS == 120 && CW_PS_VERIFY_COLS == 125 && CW_PS_VERIFY_COLS < CW_PROF_SLOTS, "verify slots: tools/verify_codes.py reads them by number");
 static_assert(CW_PS_CHAIN_ANCHORS == 42 && CW_PS_CHAIN_WINDOWS == 44 && CW_PS_CHAIN_ROUTE == 45 && CW_PS_CHAIN_ROUTE < CW_PS_L_CHUNK_ROWS && CW_PS_CHAIN_STAGE == 48 && CW_PS_CHAIN_SLOW_CYCLES == 54 && CW_PS_IDX_STAGE == 55 && CW_PS_IDX_PRESENCE == 62, "chain and index slots");
 static_assert(CW_PS_FIN_ROUTE == 33 && CW_PS_FIN_LINKS == 34 && CW_PS_FIN_NBRS == 35 && CW_PS_POAQ + CW_PS_POA_STRIDE <= CW_PS_FIN_ROUTE && CW_PS_FIN_NBRS < CW_PS_LONGEST, "the finish kernel's witness has the three slots between tier Q's phases and the longest-task slots: consent_amd/engine.py reads them by number");
+static_assert(CW_PS_POA_ROUTE == 69 && CW_PS_POAH + CW_PS_POA_STRIDE <= CW_PS_POA_ROUTE && CW_PS_POA_ROUTE + 2 < CW_PS_DIAG && CW_PS_POA_RC2 == 126 && CW_PS_VERIFY_COLS < CW_PS_POA_RC2 && CW_PS_POA_RC2 < CW_PROF_SLOTS, "the POA tiers' route witness has the three slots between tier H's phases and the diag slots, and one behind the verify slots: consent_amd/engine.py reads them by number");
 static_assert(CW_PS_IDX_ROUTE == 63 && CW_PS_IDX_PRESENCE < CW_PS_IDX_ROUTE && CW_PS_IDX_ROUTE < CW_PS_POAH, "the route witness has the one slot between the index phases and tier H's: consent_amd/engine.py reads it by number");
 
 /* Batch-wide counters (one struct in scratch, zeroed before every run). */

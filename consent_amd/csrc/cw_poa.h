@@ -123,8 +123,64 @@
 static_assert(CW_POAB_EC <= 8192 && CW_POAL_EC <= 8192 && CW_POAM2_EC <= 8192 && CW_POAM1_EC <= 8192 && CW_POA_EC <= 8192, "the row word's x field (13 bits) holds a list offset < EC or a DP row <= NC");
 static_assert(CW_POAB_NC <= 8191 && CW_POAL_NC <= 8191, "the row word's x field (13 bits) holds a DP row <= NC");
 #define CW_RM_WORD(base, np, lin, sink, kind, x) ((uint32_t)(base) | ((lin) ? 4u : 0u) | ((sink) ? 8u : 0u) | ((uint32_t)(kind) << 5) | ((uint32_t)(np) << 8) | ((uint32_t)(x) << 19))
+/* Which way a task's members went through poa_run, one bit per decision of this file: a -DCW_TEST_AIDS build ORs them, per tier, into
+   prof[CW_PS_POA_ROUTE ..] (32 bits a tier: slot CW_PS_POA_ROUTE + tier / 2, the odd tier in the high word; tiers 0 S, 1 M1, 2 M2, 3 L, 4 G, 5 X) and
+   the cause of every rc 2 into prof[CW_PS_POA_RC2] (a byte a tier).  The product's kernels have none of it.  consent_amd/engine.py POA_ROUTE / POA_RC2
+   hold the same bits by name; tests/poa_probes.py states, per probe, the bits it must have and must lack. */
+enum CwPoaRoute : uint32_t {
+    CW_PR_FILL_CODED = 1u << 0,   /* poa_fill_c: recorded decisions (cols <= 64, tiers S / M1)                            */
+    CW_PR_FILL_PAD = 1u << 1,     /* poa_fill<1, PAD>: one column a lane, rows stored by all 64 lanes (slab tiers)          */
+    CW_PR_FILL_W1 = 1u << 2,      /* poa_fill<1>: one column a lane, masked stores (tiers G / X)                            */
+    CW_PR_FILL_W2 = 1u << 3,      /* poa_fill<2>  (cols 65 .. 128)                                                          */
+    CW_PR_FILL_W4 = 1u << 4,      /* poa_fill<4>  (.. 256)                                                                  */
+    CW_PR_FILL_W8 = 1u << 5,      /* poa_fill<8>  (.. 512)                                                                  */
+    CW_PR_FILL_W16 = 1u << 6,     /* poa_fill<16> (.. 1024)                                                                 */
+    CW_PR_FILL_W32 = 1u << 7,     /* poa_fill<32> (.. 2048: tier G, and tier X's members of one column block)               */
+    CW_PR_FILL_BLOCKS = 1u << 8,  /* tier X: more than one block of 2048 columns (j0 > 0)                                   */
+    CW_PR_FILL_PK1 = 1u << 9,     /* poa_fill_pk<1>: two columns a lane (cols 65 .. 128)                                    */
+    CW_PR_FILL_PK2 = 1u << 10,    /* poa_fill_pk<2> (.. 256)                                                                */
+    CW_PR_FILL_PK4 = 1u << 11,    /* poa_fill_pk<4> (.. 512)                                                                */
+    CW_PR_FILL_PK8 = 1u << 12,    /* poa_fill_pk<8> (.. 1024)                                                               */
+    CW_PR_FILL_GROUP = 1u << 13,  /* poa_fill_pk4: the group fill                                                           */
+    CW_PR_WALK_RUNS = 1u << 14,   /* poa_trace_runs                                                                         */
+    CW_PR_WALK_DIRS = 1u << 15,   /* poa_trace_dirs                                                                         */
+    CW_PR_WALK_TILES = 1u << 16,  /* poa_trace_tiles                                                                        */
+    CW_PR_WALK_CODED = 1u << 17,  /* poa_trace_c                                                                            */
+    CW_PR_GRP_2 = 1u << 18,       /* a member opened a group fill with one member behind it                                 */
+    CW_PR_GRP_3 = 1u << 19,       /* ... with two                                                                           */
+    CW_PR_GRP_4 = 1u << 20,       /* ... with three                                                                         */
+    CW_PR_GRP_READ = 1u << 21,    /* a member's rows were read from the group fill made before it                           */
+    CW_PR_GRP_ABANDONED = 1u << 22, /* members of a group were still unread when a merge changed the graph (meta_ok fell)    */
+    CW_PR_REPLAY = 1u << 23,      /* poa_replay took a member                                                               */
+    CW_PR_REPLAY_GRP = 1u << 24,  /* ... whose rows of a group fill stayed unread                                           */
+    CW_PR_META_REUSED = 1u << 25, /* a member was aligned with the row metadata of the member before it                     */
+    CW_PR_ROW_FAR = 1u << 26,     /* the coded fill met a row with a predecessor more than CW_RING ranks back               */
+    CW_PR_ROW_FAN4 = 1u << 27,    /* ... a row with more than three predecessors                                            */
+    CW_PR_ROW_SLAB = 1u << 28     /* ... a row with the slab bit                                                            */
+};
+enum CwPoaRc2 : uint32_t {
+    CW_PR2_LCAP = 1u << 0,   /* a member longer than the tier's l_cap                                       */
+    CW_PR2_FIRST = 1u << 1,  /* the first member beyond n_cap / e_cap                                        */
+    CW_PR2_HCAP = 1u << 2,   /* the matrix beyond h_cap                                                      */
+    CW_PR2_CCAP = 1u << 3,   /* the coded path's code words beyond c_cap (or its 64-column rows beyond h_cap) */
+    CW_PR2_NODES = 1u << 4,  /* poa_merge out of nodes                                                       */
+    CW_PR2_EDGES = 1u << 5,  /* poa_merge out of edges                                                       */
+    CW_PR2_INDEG = 1u << 6   /* poa_row_meta: an in-degree beyond the row word's count                       */
+};
+#ifdef CW_TEST_AIDS
+#define CW_PR_FIELDS unsigned long long* wit; int wit_tier; /* BatchCounters::prof and the tier, NULL where nothing is witnessed (tiers Q / H) */
+#define CW_PR_MEM(mem, sc_, tier_) poa_witnessed(mem, (sc_).ctr->prof, tier_)
+#define CW_PR_MARK(M_, bits) do { if ((threadIdx.x & 63) == 0 && (M_).wit) atomicOr((M_).wit + CW_PS_POA_ROUTE + ((M_).wit_tier >> 1), (unsigned long long)(bits) << (32 * ((M_).wit_tier & 1))); } while (0)
+#define CW_PR_RC2(M_, cause) do { if ((threadIdx.x & 63) == 0 && (M_).wit) atomicOr((M_).wit + CW_PS_POA_RC2, (unsigned long long)(cause) << (8 * (M_).wit_tier)); } while (0)
+#else
+#define CW_PR_FIELDS
+#define CW_PR_MEM(mem, sc_, tier_) (mem)
+#define CW_PR_MARK(M_, bits) do { } while (0)
+#define CW_PR_RC2(M_, cause) do { } while (0)
+#endif
 template <typename HT>
 struct PoaMem {
+    CW_PR_FIELDS
     HT* H;
     unsigned long long* dirs; /* traceback codes, 2 bits per cell as two ballots per (row, chunk): 0 diagonal and
                                  1 vertical through the first predecessor, 2 horizontal, 3 = compare cell values */
@@ -206,8 +262,15 @@ __device__ __forceinline__ PoaMem<HT> poa_carve(uint8_t* base, uint32_t nc, uint
 #ifdef CW_DIAG
     M.diag = nullptr;
 #endif
+#ifdef CW_TEST_AIDS
+    M.wit = nullptr; M.wit_tier = 0;
+#endif
     return M;
 }
+#ifdef CW_TEST_AIDS
+template <typename HT>
+__device__ __forceinline__ PoaMem<HT> poa_witnessed(PoaMem<HT> M, unsigned long long* prof, const int tier) { M.wit = prof; M.wit_tier = tier; return M; } /* CW_PR_MEM */
+#endif
 
 /*
  * DP fill with the previous row resident in registers: NCH chunks of 64 columns per row (cols <= 64*NCH).
@@ -732,8 +795,9 @@ __device__ __forceinline__ bool poa_replay(const PoaMem<HT>& M, PoaSt& S, const 
         if (__ballot(!same) == 0ull) {
             for (int j = lane; j < L; j += 64) { const int cur = M.pcur[j]; M.ncov[cur] = (uint16_t)(M.ncov[cur] + 1); } /* (a path visits a node once; lane j owns position j, as in the merge) */
             S.nseq++;
+            CW_PR_MARK(M, CW_PR_REPLAY);
             if constexpr (poa_group_tier<HT, PK, CM, LCAP>) {
-                if (S.gf_left > 0 && S.meta_ok) { ++S.gf_idx; --S.gf_left; } /* its rows of a group fill stay unread */
+                if (S.gf_left > 0 && S.meta_ok) { ++S.gf_idx; --S.gf_left; CW_PR_MARK(M, CW_PR_REPLAY_GRP); } /* its rows of a group fill stay unread */
             }
             cw_wave_sync();
             return true;
@@ -768,12 +832,13 @@ __device__ __forceinline__ void poa_group_plan(const PoaMem<HT>& M, PoaSt& S, Po
     bool grp = false, grp_fill = false;
     int jo = 0, gk = 1;
     if constexpr (poa_group_tier<HT, PK, CM, LCAP>) {
-        if (gf_left > 0 && S.meta_ok) { grp = true; jo = 32 * (++gf_idx); --gf_left; }
+        if (gf_left > 0 && S.meta_ok) { grp = true; jo = 32 * (++gf_idx); --gf_left; CW_PR_MARK(M, CW_PR_GRP_READ); }
         else {
+            if (gf_left > 0) CW_PR_MARK(M, CW_PR_GRP_ABANDONED);
             gf_left = 0; gf_idx = 0;
             if (L <= CW_GF_LC && (uint32_t)((n + 1) * CW_GF_HS) <= M.h_cap && n + 32 <= CW_POA_PK_SPAN) {
                 while (gk < 4 && mi + (uint32_t)gk < t.n_members && __builtin_amdgcn_readfirstlane((int)sc.members[t.member_off + mi + gk].len) <= CW_GF_LC) ++gk;
-                if (gk >= 2) { grp = true; grp_fill = true; gf_left = gk - 1; }
+                if (gk >= 2) { grp = true; grp_fill = true; gf_left = gk - 1; CW_PR_MARK(M, CW_PR_GRP_2 << (gk - 2)); }
             }
         }
     }
@@ -882,28 +947,31 @@ __device__ __forceinline__ void poa_fill_matrix(const PoaMem<HT>& M, const int n
                         lens4 |= (uint32_t)__builtin_amdgcn_readfirstlane((int)pg.len) << (8 * g_);
                     }
                     cw_wave_sync();
+                    CW_PR_MARK(M, CW_PR_FILL_GROUP);
                     poa_fill_pk4<PK == 2>(M, n, lane, use_dirs, lens4);
                 }
             }
         }
         else if (!packed) {
-            if (cols <= 64) { if (pad) poa_fill<HT, 1, PK == 2, true>(M, n, cols, lane, use_dirs); else poa_fill<HT, 1, PK == 2>(M, n, cols, lane, use_dirs); }
+            if (cols <= 64) { CW_PR_MARK(M, pad ? CW_PR_FILL_PAD : CW_PR_FILL_W1); if (pad) poa_fill<HT, 1, PK == 2, true>(M, n, cols, lane, use_dirs); else poa_fill<HT, 1, PK == 2>(M, n, cols, lane, use_dirs); }
             else if constexpr (PK == 2 && LCAP > 511) { /* a very large graph in tier L: one column per lane */
+                CW_PR_MARK(M, cols <= 128 ? CW_PR_FILL_W2 : cols <= 256 ? CW_PR_FILL_W4 : cols <= 512 ? CW_PR_FILL_W8 : CW_PR_FILL_W16);
                 if (cols <= 128) poa_fill<HT, 2, PK == 2>(M, n, cols, lane, use_dirs);
                 else if (cols <= 256) poa_fill<HT, 4, PK == 2>(M, n, cols, lane, use_dirs);
                 else if (cols <= 512) poa_fill<HT, 8, PK == 2>(M, n, cols, lane, use_dirs);
                 else poa_fill<HT, 16, PK == 2>(M, n, cols, lane, use_dirs);
             }
         }
-        else if (cols <= 128) poa_fill_pk<1, PK == 2>(M, n, cols, hs, lane, use_dirs);
+        else if (cols <= 128) { CW_PR_MARK(M, CW_PR_FILL_PK1); poa_fill_pk<1, PK == 2>(M, n, cols, hs, lane, use_dirs); }
         else if constexpr (LCAP > 127) {
-            if (cols <= 256) poa_fill_pk<2, PK == 2>(M, n, cols, hs, lane, use_dirs);
+            if (cols <= 256) { CW_PR_MARK(M, CW_PR_FILL_PK2); poa_fill_pk<2, PK == 2>(M, n, cols, hs, lane, use_dirs); }
             else if constexpr (LCAP > 255) {
-                if (cols <= 512) poa_fill_pk<4, PK == 2>(M, n, cols, hs, lane, use_dirs);
-                else if constexpr (PK == 2 && LCAP > 511) poa_fill_pk<8, PK == 2>(M, n, cols, hs, lane, use_dirs);
+                if (cols <= 512) { CW_PR_MARK(M, CW_PR_FILL_PK4); poa_fill_pk<4, PK == 2>(M, n, cols, hs, lane, use_dirs); }
+                else if constexpr (PK == 2 && LCAP > 511) { CW_PR_MARK(M, CW_PR_FILL_PK8); poa_fill_pk<8, PK == 2>(M, n, cols, hs, lane, use_dirs); }
             }
         }
     } else if constexpr (WX) { /* tier X: the wide row word; members of more than 2047 bases in blocks of 2048 columns */
+        CW_PR_MARK(M, cols <= 64 ? CW_PR_FILL_W1 : cols <= 128 ? CW_PR_FILL_W2 : cols <= 256 ? CW_PR_FILL_W4 : cols <= 512 ? CW_PR_FILL_W8 : cols <= 1024 ? CW_PR_FILL_W16 : cols <= 2048 ? CW_PR_FILL_W32 : (CW_PR_FILL_W32 | CW_PR_FILL_BLOCKS));
         if (cols <= 64) poa_fill<HT, 1, false, false, true>(M, n, cols, lane, false);
         else if (cols <= 128) poa_fill<HT, 2, false, false, true>(M, n, cols, lane, false);
         else if (cols <= 256) poa_fill<HT, 4, false, false, true>(M, n, cols, lane, false);
@@ -911,6 +979,7 @@ __device__ __forceinline__ void poa_fill_matrix(const PoaMem<HT>& M, const int n
         else if (cols <= 1024) poa_fill<HT, 16, false, false, true>(M, n, cols, lane, false);
         else for (int j0 = 0; j0 < cols; j0 += 2048) poa_fill<HT, 32, false, false, true>(M, n, cols, lane, false, j0);
     } else {
+        CW_PR_MARK(M, cols <= 64 ? CW_PR_FILL_W1 : cols <= 128 ? CW_PR_FILL_W2 : cols <= 256 ? CW_PR_FILL_W4 : cols <= 512 ? CW_PR_FILL_W8 : cols <= 1024 ? CW_PR_FILL_W16 : CW_PR_FILL_W32);
         if (cols <= 64) poa_fill<HT, 1, PK == 2>(M, n, cols, lane, use_dirs);
         else if (cols <= 128) poa_fill<HT, 2, PK == 2>(M, n, cols, lane, use_dirs);
         else if (cols <= 256) poa_fill<HT, 4, PK == 2>(M, n, cols, lane, use_dirs);
@@ -1222,7 +1291,7 @@ __device__ __forceinline__ int poa_merge(const PoaMem<HT>& M, PoaSt& S, const in
         }
         fresh_total += __popcll(fb);
     }
-    if ((uint32_t)(n_old + fresh_total) > M.n_cap) return 2;
+    if ((uint32_t)(n_old + fresh_total) > M.n_cap) { CW_PR_RC2(M, CW_PR2_NODES); return 2; }
     cw_wave_sync();
     /* pass C: place the fresh nodes in the rank order (one histogram + one prefix sum) */
     if (fresh_total > 0) {
@@ -1276,7 +1345,7 @@ __device__ __forceinline__ int poa_merge(const PoaMem<HT>& M, PoaSt& S, const in
         }
         const unsigned long long ab = __ballot(add);
         const int total = __popcll(ab);
-        if ((uint32_t)(ne + total) > M.e_cap) return 2;
+        if ((uint32_t)(ne + total) > M.e_cap) { CW_PR_RC2(M, CW_PR2_EDGES); return 2; }
         if (add) {
             const int e = ne + __popcll(ab & lt_mask);
             M.efrom[e] = (uint16_t)head; M.enext[e] = CW_NONE16;
@@ -1370,6 +1439,23 @@ __device__ __forceinline__ void poa_verify_compare(const PoaMem<HT>& M, const De
 }
 #endif
 
+#ifdef CW_TEST_AIDS
+/* route witness: what the coded fill will meet in the row words of this graph (poa_row_meta wrote them) */
+__device__ __forceinline__ void poa_witness_rows(const PoaMem<int16_t>& M, const int n, const int lane) {
+    bool far_ = false, fan_ = false, slab_ = false;
+    for (int r = lane; r < n; r += 64) {
+        const uint32_t m = M.rmeta[r];
+        const int np_ = CW_RM_NP(m);
+        fan_ = fan_ || np_ > 3;
+        slab_ = slab_ || (m & 16u) != 0u;
+        if (np_ == 1) far_ = far_ || (M.rpred0[r] != 0 && r + 1 - (int)M.rpred0[r] > CW_RING);
+        else for (int q = 0; q < np_; ++q) far_ = far_ || r + 1 - (int)M.plist[CW_RM_X(m) + q] > CW_RING;
+    }
+    const uint32_t rows_ = (__ballot(far_) ? CW_PR_ROW_FAR : 0u) | (__ballot(fan_) ? CW_PR_ROW_FAN4 : 0u) | (__ballot(slab_) ? CW_PR_ROW_SLAB : 0u); /* (all lanes vote: CW_PR_MARK runs on lane 0) */
+    CW_PR_MARK(M, CW_PR_FILL_CODED | CW_PR_WALK_CODED | rows_);
+}
+#endif
+
 /* Returns 1 = done, 2 = a capacity of this memory class was exceeded, 3 = output capacity exceeded / internal. */
 template <typename HT, int PK, int CM = 0, int LCAP = 1023, bool WX = false> /* LCAP: the tier's longest member -- fills for wider rows are not compiled into its kernel; WX: tier X's row word */
 __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, const DevBatch& b, const DevScratch& sc, const int lane,
@@ -1384,7 +1470,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
         const PoaMember pm = sc.members[t.member_off + mi];
         const int L = __builtin_amdgcn_readfirstlane((int)pm.len); /* sizes steer every loop below: keep them in scalar registers */
         S.n = __builtin_amdgcn_readfirstlane(S.n); S.ne = __builtin_amdgcn_readfirstlane(S.ne);
-        if ((uint32_t)L > M.l_cap) return 2;
+        if ((uint32_t)L > M.l_cap) { CW_PR_RC2(M, CW_PR2_LCAP); return 2; }
         if (poa_replay<HT, PK, CM, LCAP>(M, S, pm, L, b, lane)) continue;
         {
             const uint32_t* words = b.bases + b.seq_word_off[pm.seq];
@@ -1394,7 +1480,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
         S.nseq++;
         S.prev_clean = false; S.prev_L = L;
         if (S.n == 0) {
-            if (!poa_first_member(M, S, L, lane)) return 2;
+            if (!poa_first_member(M, S, L, lane)) { CW_PR_RC2(M, CW_PR2_FIRST); return 2; }
             continue;
         }
         const int n = S.n, cols = L + 1;
@@ -1402,8 +1488,9 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
         poa_matrix_plan<HT, PK, CM, LCAP>(M, S, P, t, sc, mi, L);
         const int hs = P.hs;
         if constexpr (WX) { if (lane == 0) atomicMax(&sc.ctr->x_cells, (uint32_t)((n + 1) * hs) * (CW_POA_AFFINE ? 3u : 1u)); } /* the largest alignment tier X was asked for */
-        if ((uint32_t)((n + 1) * hs + (P.pad ? 64 : 0)) > M.h_cap) return 2;
-        if (!S.meta_ok && !poa_row_meta<HT, CM, WX>(M, S, lane)) return 2;
+        if ((uint32_t)((n + 1) * hs + (P.pad ? 64 : 0)) > M.h_cap) { CW_PR_RC2(M, CW_PR2_HCAP); return 2; }
+        if (S.meta_ok) CW_PR_MARK(M, CW_PR_META_REUSED);
+        if (!S.meta_ok && !poa_row_meta<HT, CM, WX>(M, S, lane)) { CW_PR_RC2(M, CW_PR2_INDEG); return 2; }
         POA_PROF(0);
 
         /* ---- DP fill, end cell, traceback ---- */
@@ -1411,7 +1498,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
         bool coded = false; /* members of <= 63 bases in tiers S / M1 / M2: the fill records the traceback's decisions (cw_poa_c.h) */
         if constexpr (CM != 0 && CW_POA_CODES != 0) {
             if (cols <= 64 && M.codes != nullptr) {
-                if ((uint32_t)(((n + 7) >> 3) * 64) > M.c_cap || (uint32_t)((n + 1) * 64) > M.h_cap) return 2;
+                if ((uint32_t)(((n + 7) >> 3) * 64) > M.c_cap || (uint32_t)((n + 1) * 64) > M.h_cap) { CW_PR_RC2(M, CW_PR2_CCAP); return 2; }
                 coded = true;
             }
         }
@@ -1439,6 +1526,7 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
         int bi, bj;
         poa_end_cell(M, V, n, L, hs, lane, &bi, &bj);
         bool walked; /* direction words a run at a time (tier L) or a step at a time; without them (the matrix lives in the slab) 8x8 tiles of the matrix */
+        CW_PR_MARK(M, P.use_dirs && M.runs ? CW_PR_WALK_RUNS : P.use_dirs ? CW_PR_WALK_DIRS : CW_PR_WALK_TILES);
         if (P.use_dirs && M.runs) walked = poa_trace_runs<HT, WX>(M, V, P, bi, bj, lane);
         else if (P.use_dirs) walked = poa_trace_dirs<HT, WX>(M, V, P, bi, bj, lane);
         else walked = poa_trace_tiles<HT, WX>(M, V, hs, bi, bj, lane);
@@ -1452,6 +1540,9 @@ __device__ __forceinline__ int poa_run(const PoaMem<HT>& M, const PoaTask& t, co
                 cw_wave_sync();
 #ifdef CW_DIAG
                 if (lane == 0 && M.diag) atomicAdd(&M.diag[9], 1ull); /* members on this path */
+#endif
+#ifdef CW_TEST_AIDS
+                poa_witness_rows(M, n, lane);
 #endif
                 const int be_c = poa_fill_c<CM>(M, n, cols, lane);
                 const int bi_c = be_c & 0xFFFF, bj_c = be_c >> 16; /* end row, end column (the last one unless cw_policy.h's overlap mode) */
@@ -1586,7 +1677,7 @@ __global__ void __launch_bounds__(64 * CW_POA_WAVES, CW_S_EU) cw_poa_kernel(DevB
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t gw = poa_claim_slab(sc, 0, CW_POA_WAVES);
-    PoaMem<int16_t> M = poa_slab_mem<CW_POA_NC, CW_POA_EC, CW_POA_LC>(sc, 0, gw, lds + (size_t)wave * CW_POA_SLAB_BYTES, CW_POA_SLAB_BYTES, 0, false, true);
+    PoaMem<int16_t> M = CW_PR_MEM((poa_slab_mem<CW_POA_NC, CW_POA_EC, CW_POA_LC>(sc, 0, gw, lds + (size_t)wave * CW_POA_SLAB_BYTES, CW_POA_SLAB_BYTES, 0, false, true)), sc, 0);
     static_assert(CW_POA_SMAX * (CW_POA_NC + CW_POA_LC) <= CW_POA_I16_BOUND && 4 * CW_POA_SMAX * (CW_POA_NC + 64) <= CW_POA_I16_BOUND, "include/cw_policy.h \"Bounds\": tier S");
     const uint32_t n_tasks = min(sc.ctr->n_tasks, sc.task_cap);
     unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
@@ -1643,7 +1734,7 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
     const bool yields = PASS == 0 && blockIdx.x + sc.persist_wgs[TIER] < gridDim.x;
     constexpr uint32_t slab = TIER <= 2 ? CW_POA_HOT2T_BYTES(TIER, NC, EC, LC) : CW_POA_HOT2L_BYTES(NC, EC, LC);
     constexpr bool codes = TIER == 1 || (TIER == 2 && CW_M2_CODES);
-    PoaMem<int16_t> M = poa_slab_mem<NC, EC, LC>(sc, TIER, gw, lds + (size_t)wave * slab, slab, TIER >= 3 ? CW_POA_DSLAB_PAIRS(NC, LC) : 0, true, codes);
+    PoaMem<int16_t> M = CW_PR_MEM((poa_slab_mem<NC, EC, LC>(sc, TIER, gw, lds + (size_t)wave * slab, slab, TIER >= 3 ? CW_POA_DSLAB_PAIRS(NC, LC) : 0, true, codes)), sc, TIER);
     /* include/cw_policy.h "Bounds": the int16 values of this tier's fills stay inside +-CW_POA_I16_BOUND -- by its capacities, or (tier L under scores
        beyond 11) by handing a graph of more nodes than that allows on to tier G */
     static_assert(TIER == 3 || CW_POA_SMAX * (NC + LC) <= CW_POA_I16_BOUND, "matrix / packed fills of this tier");
@@ -1854,7 +1945,7 @@ __global__ void __launch_bounds__(64 * CW_POA_WAVES) cw_poa_big_kernel(DevBatch 
     const int lane = threadIdx.x & 63;
     const uint32_t gw = blockIdx.x * CW_POA_WAVES + (threadIdx.x >> 6);
     if (gw >= sc.slots[4]) return;
-    const PoaMem<int32_t> M = poa_carve<int32_t>(sc.slab[4] + (size_t)gw * sc.slab_bytes[4], CW_POAB_NC, CW_POAB_EC, CW_POAB_LC, CW_POAB_HC, 0);
+    const PoaMem<int32_t> M = CW_PR_MEM(poa_carve<int32_t>(sc.slab[4] + (size_t)gw * sc.slab_bytes[4], CW_POAB_NC, CW_POAB_EC, CW_POAB_LC, CW_POAB_HC, 0), sc, 4);
     const uint32_t n_big = min(sc.ctr->n_over[4], sc.list_cap);
     unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
     for (;;) {
@@ -1884,8 +1975,8 @@ __global__ void __launch_bounds__(64) cw_poa_x_kernel(DevBatch b, DevScratch sc,
     uint8_t* const pool = sc.slab[4];
     const uint64_t pool_bytes = (uint64_t)min(sc.slots[4], CW_POAX_MIN_SLABS) * sc.slab_bytes[4];
     const uint64_t cells = pool_bytes > (uint64_t)CW_POAX_GRAPH_BYTES ? (pool_bytes - (uint64_t)CW_POAX_GRAPH_BYTES) / 4u : 0u;
-    PoaMem<int32_t> M = poa_carve<int32_t>(pool, CW_POAX_NC, CW_POAX_PLIST_EC, CW_POAX_LC, (uint32_t)min(cells, (uint64_t)0xFFFFFFFFu), 0,
-                                           (int32_t*)(pool + CW_POAX_GRAPH_BYTES));
+    PoaMem<int32_t> M = CW_PR_MEM(poa_carve<int32_t>(pool, CW_POAX_NC, CW_POAX_PLIST_EC, CW_POAX_LC, (uint32_t)min(cells, (uint64_t)0xFFFFFFFFu), 0,
+                                                     (int32_t*)(pool + CW_POAX_GRAPH_BYTES)), sc, 5);
     M.e_cap = CW_POAX_EC;
     M.rx = (uint32_t*)(pool + CW_POA_GRAPH_BYTES(CW_POAX_NC, CW_POAX_PLIST_EC, CW_POAX_LC));
     unsigned long long acc[6] = {0, 0, 0, 0, 0, 0}; /* (tier X keeps no cycle totals: cw_debug_profile's slots are tiers S .. G's) */

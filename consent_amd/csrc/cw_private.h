@@ -66,7 +66,8 @@ int cw_add_offsets_device(uint32_t* a32, uint64_t n32, uint32_t add32, uint64_t*
  * next_over with one entry per POA tier: 6 + 4 * 6 = 30 words) and its GPU cycle counts (uint64, 128 words: index kernel 0-7; POA tier t at
  * 8+5t..12+5t: metadata, fill, traceback, merge, consensus; 36+t: the longest single task of tier t; 63: the index kernel's route bits and 45: the chain
  * kernel's, written by a -DCW_TEST_AIDS build only (cw_index.h CwIdxRoute, cw_chain.h CwChRoute), as are 33-35: the finish kernel's route bits, the frames its
- * fin_link entered and the fin_neighbours calls it made (cw_finish.h CwFinRoute); 72+12t..: row counts of a -DCW_DIAG build).  The caller passes the capacity of each buffer in words and receives min(capacity, available); the counts come back through
+ * fin_link entered and the fin_neighbours calls it made (cw_finish.h CwFinRoute), and 69-71 and 126: the slab POA tiers' route bits, 32 a tier, and the causes of
+ * their rc 2, a byte a tier (cw_poa.h CwPoaRoute, CwPoaRc2); 72+12t..: row counts of a -DCW_DIAG build).  The caller passes the capacity of each buffer in words and receives min(capacity, available); the counts come back through
  * counters_n / prof_n when those are not NULL. */
 /* cw_run_device + wait for the stream + one more run with larger task / member / arena capacities, or the full matrix slot, when windows stopped on those only */
 int cw_run_device_sync(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream);

@@ -292,6 +292,26 @@ FINISH_ROUTE = {"staged": 1 << 0, "compact": 1 << 1, "global": 1 << 2, "cnt16": 
                 "count_scan": 1 << 8, "head": 1 << 9, "tail": 1 << 10, "linked": 1 << 11, "first_pass": 1 << 12, "second_pass": 1 << 13}
 
 
+# The POA tiers' route witness (csrc/cw_poa.h enums CwPoaRoute and CwPoaRc2, csrc/cw_device.h CW_PS_POA_ROUTE and CW_PS_POA_RC2): which fills, walks, group
+# fills, replays and coded row kinds the members of the last batch's tasks took in each slab tier, and why a tier gave a task up (rc 2).  32 route bits a
+# tier, two tiers a slot from POA_ROUTE_SLOT; a byte of causes a tier in POA_RC2_SLOT.
+POA_ROUTE_SLOT, POA_RC2_SLOT = 69, 126
+POA_TIERS = ("S", "M1", "M2", "L", "G", "X")
+POA_ROUTE = {"fill_coded": 1 << 0, "fill_pad": 1 << 1, "fill_w1": 1 << 2, "fill_w2": 1 << 3, "fill_w4": 1 << 4, "fill_w8": 1 << 5, "fill_w16": 1 << 6, "fill_w32": 1 << 7,
+             "fill_blocks": 1 << 8, "fill_pk1": 1 << 9, "fill_pk2": 1 << 10, "fill_pk4": 1 << 11, "fill_pk8": 1 << 12, "fill_group": 1 << 13, "walk_runs": 1 << 14,
+             "walk_dirs": 1 << 15, "walk_tiles": 1 << 16, "walk_coded": 1 << 17, "grp_2": 1 << 18, "grp_3": 1 << 19, "grp_4": 1 << 20, "grp_read": 1 << 21,
+             "grp_abandoned": 1 << 22, "replay": 1 << 23, "replay_grp": 1 << 24, "meta_reused": 1 << 25, "row_far": 1 << 26, "row_fan4": 1 << 27, "row_slab": 1 << 28}
+POA_RC2 = {"rc2_lcap": 1 << 0, "rc2_first": 1 << 1, "rc2_hcap": 1 << 2, "rc2_ccap": 1 << 3, "rc2_nodes": 1 << 4, "rc2_edges": 1 << 5, "rc2_indeg": 1 << 6}
+
+
+def poa_route_names(route):
+    """Engine.poa_route()'s answer as a set of 'tier.bit' names ('M2.fill_pk2', 'S.rc2_nodes')."""
+    out = set()
+    for tier, (bits, rc2) in route.items():
+        out |= {f"{tier}.{n}" for n, b in POA_ROUTE.items() if bits & b} | {f"{tier}.{n}" for n, b in POA_RC2.items() if rc2 & b}
+    return out
+
+
 def route_names(bits, table=None):
     """The names of the bits of `table` (default INDEX_ROUTE) set in `bits`, for messages."""
     return sorted(n for n, b in (table or INDEX_ROUTE).items() if bits & b)
@@ -1263,6 +1283,15 @@ class Engine:
         own.  Zeros from the product library."""
         p = self.profile()[1]
         return int(p[FINISH_ROUTE_SLOT]), int(p[FINISH_ROUTE_SLOT + 1]), int(p[FINISH_ROUTE_SLOT + 2])
+
+    def poa_route(self):
+        """{tier: (POA_ROUTE bits, POA_RC2 bits)} of the last batch's POA tasks, ORed per slab tier S .. X (a group alone in its batch: its own route through
+        every tier it visited).  Zeros from the product library."""
+        p = self.profile()[1]
+        out = {}
+        for t, tier in enumerate(POA_TIERS):
+            out[tier] = ((int(p[POA_ROUTE_SLOT + t // 2]) >> (32 * (t & 1))) & 0xFFFFFFFF, (int(p[POA_RC2_SLOT]) >> (8 * t)) & 0xFF)
+        return out
 
     def segments(self, w):
         """cw_debug_segments: the chain kernel's segmentation of window w of the last run -- (n_segs, seg_len, tasks).  n_segs is chain anchors + 1, or 0 for a

@@ -62,6 +62,19 @@
 /* order beyond being topological: the tie-break between equally good end nodes, and the order in    */
 /* which independent insertion columns appear in the consensus.                                       */
 
+/* What the rules above leave to be said (made precise for tests/poa_ref.py, the plain reference written from this prose; the oracle's behaviour    */
+/* is the norm):                                                                                                                                   */
+/*  - The DP has one row before any node: row[j] = j * CW_POA_GAP.  It is the one predecessor of every node without in-edges, for the diagonal    */
+/*    and the vertical move alike; the walk back ends in its column 0, through horizontal moves once it is reached.                               */
+/*  - A base aligned to a node joins that node's column: it takes the column's node that carries its base if there is one (the aligned node       */
+/*    itself on a match), and a fresh node only if there is none.                                                                                  */
+/*  - The bases aligned to nodes are resolved first, in sequence order, and their fresh nodes ranked by (a); then the insertions, in sequence     */
+/*    order, by (b) -- "the next path node that already has a rank" is the next base of the sequence that was aligned to a node, whether it took   */
+/*    an old node or a fresh one of (a).  Consecutive insertions go in front of the same column, in sequence order.                                */
+/*  - An edge joins the nodes of consecutive bases of a sequence, added at the end of the target's in-edge list the first time a sequence uses it. */
+/*  - A column's base counts are the sequences through its nodes; "the template's base" is the base of the first sequence's node in the column    */
+/*    (a column the first sequence has no node in has none: the smallest code among the tied).                                                    */
+
 /* Consensus of a segment = column-majority vote over the MSA encoded by the graph (BMEAN's        */
 /* "easy consensus"), NOT the heaviest bundle: with anchors that occasionally hit a spurious copy of  */
 /* a k-mer, one member of a segment can be hundreds of bases longer than the others, and a           */

@@ -315,6 +315,26 @@ def test_long_and_outlier_segments_exercise_all_tiers(engines):
     got = engines(*prm).run(hb)
     exp, _ = oracle_lib.oracle_run(ca.Params(*prm), hb)
     assert_same(got, exp, len(piles), "tiers")
+    # ... and the counters: every task is on the list of the tier the routing rule names for it, and is handed on exactly where the graph of the plain
+    # reference (tests/poa_ref.py) outgrows a tier's capacities (tests/poa_probes.py visits)
+    import poa_probes
+
+    e = engines(*prm)
+    ctr, _ = e.profile()
+    n_tier, n_over = [int(v) for v in ctr[6:12]], [int(v) for v in ctr[18:24]]
+    want_tier, want_over, tasks = [0] * 6, [0] * 6, 0
+    for w, pile in enumerate(piles):
+        for _seg, _n, _mx, members in e.segments(w)[2]:
+            tiers, stops, _why = poa_probes.visits([pile[s][a : a + l] for s, a, l in members])
+            tasks += 1
+            assert not stops
+            want_tier[{"Q": 0, "S": 0, "M1": 1, "M2": 2, "L": 3}[tiers[0]]] += tiers[0] != "S"  # (tier S has no list)
+            want_over[3] += "L" in tiers[1:]
+            want_over[4] += "G" in tiers[1:]
+    print(f"{tasks} tasks: n_tier {n_tier} (the rule: {want_tier}), n_over {n_over} (the reference's graphs: {want_over})")
+    assert int(ctr[0]) == tasks and n_tier == want_tier, (n_tier, want_tier)
+    assert n_over[3:5] == want_over[3:5], (n_over, want_over)
+    assert all(v > 0 for v in n_tier[:4]) and tasks > sum(n_tier), f"the piles no longer reach tiers Q, S, M1, M2 and L: n_tier {n_tier} of {tasks} tasks"  # (no task of theirs outgrows its tier)
 
 
 def test_graph_of_more_than_2048_nodes(engines):
