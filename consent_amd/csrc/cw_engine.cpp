@@ -215,6 +215,7 @@ int hold_and_bind(cw_engine* e, uint32_t n_windows, uint32_t big_slots, const Sc
     e->last_tasks_off = p.tasks; e->last_tdbg_off = p.tdbg; e->last_task_cap = p.task_cap;
     e->last_solid_key_off = p.solid_key; e->last_solid_cnt_off = p.solid_cnt;
     e->last_seg_len_off = p.seg_len; e->last_members_off = p.members;
+    e->last_ablock_off = p.ablock; e->last_ablock_units = p.ablock_units;
     if (!e->step_clock) { CW_HIP(hipMalloc((void**)&e->step_clock, 16)); CW_HIP(hipMemset(e->step_clock, 0, 16)); }
     *sc = bind_scratch(p, (uint8_t*)e->scratch);
     sc->step_clock = e->step_clock;
@@ -1404,6 +1405,41 @@ int cw_debug_solid_table(cw_engine* e, uint32_t window, uint32_t* keys, uint32_t
         CW_HIP(hipMemcpy(keys, (const uint8_t*)e->scratch + e->last_solid_key_off + (size_t)wi.solid_base * 4, take * 4, hipMemcpyDeviceToHost));
         CW_HIP(hipMemcpy(counts, (const uint8_t*)e->scratch + e->last_solid_cnt_off + (size_t)wi.solid_base * 4, take * 4, hipMemcpyDeviceToHost));
     }
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): the anchor block of one window of the last run, as idx_hand_over left it (cw_index.h CwAbCarve) -- the window's slice of
+ * the scratch plan's ablock region (WinInfo::ab_base, ab_cap), which nothing else lies in and which cw_chain_kernel only reads.  *n = cw_ab_bytes of the
+ * block's own header; the first min(*n, cap) bytes are copied. */
+int cw_debug_anchor_block(cw_engine* e, uint32_t window, uint8_t* out, uint64_t cap, uint64_t* n) {
+    if (!e || !e->scratch || !n || (cap && !out)) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (window >= e->last_windows) return CW_E_INVALID;
+    CW_HIP(hipSetDevice(e->device));
+    CW_HIP(hipDeviceSynchronize());
+    WinInfo wi;
+    CW_HIP(hipMemcpy(&wi, (const uint8_t*)e->scratch + (size_t)window * sizeof(WinInfo), sizeof(wi), hipMemcpyDeviceToHost));
+    /* no block: a POA-only run, a window without a template k-mer, or one the setup or index phase stopped (the later phases stop a window behind its block) */
+    if (wi.ab_cap == 0 || wi.status == CW_WIN_TEMPLATE) return CW_E_INVALID;
+    if (wi.status == CW_WIN_OVERFLOW && (wi.pad_ == CW_WHY_SETUP || wi.pad_ == CW_WHY_COUNT || wi.pad_ == CW_WHY_SOLIDCAP || wi.pad_ == CW_WHY_TEMPLATE || wi.pad_ == CW_WHY_MATRIX)) return CW_E_INVALID;
+    if ((uint64_t)wi.ab_base + wi.ab_cap > e->last_ablock_units) return CW_E_INVALID; /* (never: cw_setup_kernel stops such a window) */
+    const uint8_t* blk = (const uint8_t*)e->scratch + e->last_ablock_off + ((size_t)wi.ab_base << 4);
+    uint32_t hdr[5];
+    CW_HIP(hipMemcpy(hdr, blk, sizeof(hdr), hipMemcpyDeviceToHost));
+    const uint64_t bytes = cw_ab_bytes(hdr[0], hdr[1], hdr[2], hdr[4]);
+    if (bytes > ((uint64_t)wi.ab_cap << 4)) return CW_E_INVALID;
+    *n = bytes;
+    const uint64_t take = bytes < cap ? bytes : cap;
+    if (take) CW_HIP(hipMemcpy(out, blk, (size_t)take, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): the nine offsets of cw_ab_carve<uint64_t>(0, ...), in the order of CwAbCarve (host arithmetic only). */
+int cw_debug_ab_layout(uint32_t A, uint32_t N, uint32_t n_dirty, uint32_t n_rows, uint64_t* out9) {
+    if (!out9) return CW_E_INVALID;
+    const CwAbCarve<uint64_t> c = cw_ab_carve<uint64_t>(0, A, N, n_dirty, n_rows);
+    const uint64_t v[9] = {c.hdr, c.ckey, c.pres, c.dirty, c.badm, c.rowid, c.delta, c.P, c.end};
+    for (int i = 0; i < 9; ++i) out9[i] = v[i];
     return CW_OK;
 }
 

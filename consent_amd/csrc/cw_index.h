@@ -49,7 +49,9 @@ typedef __attribute__((address_space(1))) uint16_t* cw_g16w;      /* ... or in t
 #define CW_IDX_STAGE_WORDS ((CW_IDX_LDS_BYTES - CW_IDX_STAGE_OFF - 16 - CW_IDX_STAGE_N * 8) / 4)
 
 /* Which way a window went, one bit per decision of this file: a -DCW_TEST_AIDS build ORs them into prof[CW_PS_IDX_ROUTE] (the product's kernel has none of
-   it), and a test that names a path asks for its bit (consent_amd/engine.py INDEX_ROUTE, the same table by name; tests/test_index_counts_cpu.py compares the two) */
+   it), and a test that names a path asks for its bit (consent_amd/engine.py INDEX_ROUTE, the same table by name; tests/test_index_counts_cpu.py compares the two).
+   Bits 0-9 are the count phase's (tests/index_probes.py), 10-16 the anchor phase's (tests/anchor_probes.py).  The last two name decisions that are no
+   variable of the kernel's state but the outcome of a loop, and exist in the test-aid build only, like the code that finds them out. */
 enum CwIdxRoute : unsigned {
     CW_IR_STAGED = 1u << 0,       /* the pile's words are staged in LDS (IdxPile::stw)                        */
     CW_IR_BYTES_DONE = 1u << 1,   /* idx_count_bytes counted and exported the window (done8)                  */
@@ -66,11 +68,18 @@ enum CwIdxRoute : unsigned {
     CW_IR_PG = 1u << 12,          /* IdxMatrix::pg                                                            */
     CW_IR_HIT_LIST = 1u << 13,    /* idx_hit_list                                                             */
     CW_IR_USE_BITS = 1u << 14     /* IdxPres::use_bits                                                        */
+#ifdef CW_TEST_AIDS
+    ,
+    CW_IR_SECOND_PASS = 1u << 15, /* idx_hit_list held but the rows were filled by the second pass over the pile: a hit at position >= 2048 or more than CW_IDX_HIT_CAP hits (from_list false) */
+    CW_IR_BUCKET_WALK = 1u << 16  /* some lookup of idx_support went on to a second bucket of the template table: the pend loop (k <= 10) or cw_tpl_lookup leaving the home bucket */
+#endif
 };
 #ifdef CW_TEST_AIDS
 #define CW_IDX_ROUTE(ctr, cond, bits) do { if (cond) atomicOr(&(ctr)->prof[CW_PS_IDX_ROUTE], (unsigned long long)(bits)); } while (0)
+#define CW_IDX_WITNESS true
 #else
 #define CW_IDX_ROUTE(ctr, cond, bits) do { } while (0)
+#define CW_IDX_WITNESS false /* (the code that finds out what only the witness wants to know compiles to nothing) */
 #endif
 
 /* ------------------------------------------------------------------------------------------------ */
@@ -221,8 +230,9 @@ __device__ __forceinline__ uint32_t cw_hash32(uint32_t x) { return x * 265443576
 #define CW_TH_HOME(key) (cw_hash32(key) >> (32 - 10))
 static_assert(CW_TH_BUCKETS == 1024, "CW_TH_HOME takes ten bits of the hash");
 static_assert(CW_TMAX + 1 <= 4095, "an entry holds the template position + 1 in twelve bits");
-/* lookup of a template k-mer: returns its representative template position or -1 */
-__device__ __forceinline__ int cw_tpl_lookup(const uint32_t* th, const uint32_t* tkey, uint32_t key) {
+/* lookup of a template k-mer: returns its representative template position or -1.  WITNESS (the test-aid build's support pass, for the route witness):
+   *walked is set when the search leaves the key's home bucket (CW_IR_BUCKET_WALK); without it the pointer is not touched */
+template <bool WITNESS> __device__ __forceinline__ int cw_tpl_lookup_t(const uint32_t* th, const uint32_t* tkey, uint32_t key, bool* walked) {
     uint32_t bkt = CW_TH_HOME(key);
     const uint32_t fp = CW_TH_FP(key);
     for (;;) {
@@ -232,8 +242,10 @@ __device__ __forceinline__ int cw_tpl_lookup(const uint32_t* th, const uint32_t*
             if ((e & ~4095u) == fp && tkey[CW_TH_POS(e) - 1] == key) return (int)CW_TH_POS(e) - 1;
         }
         bkt = (bkt + 1) & (CW_TH_BUCKETS - 1);
+        if constexpr (WITNESS) *walked = true;
     }
 }
+__device__ __forceinline__ int cw_tpl_lookup(const uint32_t* th, const uint32_t* tkey, uint32_t key) { return cw_tpl_lookup_t<false>(th, tkey, key, nullptr); }
 
 /* ------------------------------------------------------------------------------------------------ */
 /* ---- the index kernel's state ------------------------------------------------------------------ */
@@ -1003,6 +1015,7 @@ __device__ __forceinline__ void idx_support(const IdxLds& L, const IdxPile& pl, 
 #pragma unroll
                 for (uint32_t q = 0; q < 4u; ++q) { e1[q] = match(v4[q], CW_TH_FP(key4[q]) + 1u); if (e1[q] >= (uint32_t)CW_TMAX && v4[q].w != 0u) pend |= 1u << q; }
                 while (__ballot(pend != 0u) != 0ull) { /* a full bucket without the key: the next one (rare) */
+                    CW_IDX_ROUTE(sc.ctr, pend != 0u, CW_IR_BUCKET_WALK);
 #pragma unroll
                     for (uint32_t q = 0; q < 4u; ++q) {
                         if ((pend >> q) & 1u) {
@@ -1014,8 +1027,10 @@ __device__ __forceinline__ void idx_support(const IdxLds& L, const IdxPile& pl, 
                     }
                 }
             } else {
+                bool walked = false; /* (written in the test-aid build only) */
 #pragma unroll
-                for (uint32_t q = 0; q < 4u; ++q) e1[q] = p0 + q < nk ? (uint32_t)cw_tpl_lookup(th, tkey, key4[q]) : 0xFFFFFFFFu; /* (-1: not there) */
+                for (uint32_t q = 0; q < 4u; ++q) e1[q] = p0 + q < nk ? (uint32_t)cw_tpl_lookup_t<CW_IDX_WITNESS>(th, tkey, key4[q], &walked) : 0xFFFFFFFFu; /* (-1: not there) */
+                CW_IDX_ROUTE(sc.ctr, walked, CW_IR_BUCKET_WALK);
             }
             uint32_t old4[4];
 #pragma unroll
@@ -1097,6 +1112,7 @@ __device__ __forceinline__ bool idx_fill_matrix(const IdxLds& L, const IdxPile& 
     const uint32_t* const hitlist = (const uint32_t*)idx_wg_scratch(sc);
     const uint32_t n_hits = L.misc()[4];
     const bool from_list = idx_hit_list(M, N) && n_hits <= CW_IDX_HIT_CAP && L.misc()[5] == 0u;
+    CW_IDX_ROUTE(sc.ctr, tid == 0 && idx_hit_list(M, N) && !from_list, CW_IR_SECOND_PASS);
     if (!M.tfit) {
         if (!M.pg) M.clear_lds(A * Np);
         else for (uint32_t i = tid; i < A * Np; i += CW_IDX_THREADS) M.wr(i, CW_NONE16);

@@ -78,6 +78,7 @@ struct cw_engine {
     size_t last_tasks_off = 0, last_tdbg_off = 0;
     size_t last_solid_key_off = 0, last_solid_cnt_off = 0; /* the last run's solid table (cw_debug_solid_table) */
     size_t last_seg_len_off = 0, last_members_off = 0;     /* the last run's segment lengths and member array (cw_debug_segments) */
+    size_t last_ablock_off = 0; uint64_t last_ablock_units = 0; /* the last run's anchor blocks (cw_debug_anchor_block) */
     const uint32_t* last_win_first_seq = nullptr;          /* the last run's window -> first sequence array, a device pointer (the caller's in cw_run_device) */
     uint32_t last_task_cap = 0;
 };

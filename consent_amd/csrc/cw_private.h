@@ -20,6 +20,13 @@ int cw_debug_win_info(cw_engine* e, uint32_t n_windows, uint32_t* out16);
  * the solid table, WinInfo::solid_base / n_solid).  *n receives the number of entries, the first min(*n, cap) of them are copied; a window that was
  * stopped before or in the count phase has none.  Valid when cw_debug_win_info is: after a run, until the next one on this engine. */
 int cw_debug_solid_table(cw_engine* e, uint32_t window, uint32_t* keys, uint32_t* counts, uint32_t cap, uint32_t* n);
+/* the anchor block of one window of the last run, the bytes idx_hand_over wrote (cw_index.h CwAbCarve: header A, N, n_dirty, flags, n_rows; ckey, pres,
+ * dirty, badm, rowid, delta, P).  *n receives cw_ab_bytes of the block's own header, the first min(*n, cap) bytes are copied.  CW_E_INVALID for a window the
+ * index kernel did not finish (stopped by the setup or index phase, or without a template k-mer), after a POA-only run (no blocks), and for a header that
+ * claims more than the window's slice.  Host code only, in both builds; valid when cw_debug_solid_table is.  DESIGN.md says which bytes are specified. */
+int cw_debug_anchor_block(cw_engine* e, uint32_t window, uint8_t* out, uint64_t cap, uint64_t* n);
+/* the nine offsets of that layout for a block of these numbers -- hdr, ckey, pres, dirty, badm, rowid, delta, P, end -- without an engine or a device */
+int cw_debug_ab_layout(uint32_t A, uint32_t N, uint32_t n_dirty, uint32_t n_rows, uint64_t* out9);
 /* the chain kernel's segmentation of one window of the last run.  *n_segs: WinInfo::n_segs (chain anchors + 1; 0 for a window without a chain); seg_len: the
  * first min(*n_segs, seg_cap) of the window's segment lengths (of a segment that became a POA task: the length of the tier's consensus); tasks4: four words
  * per task record that names the window, in the order of the task array -- segment index (seg_slot - seg_base), n_members, longest member, index of its

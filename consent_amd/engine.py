@@ -236,6 +236,9 @@ def _load(p):
         lib.cw_debug_tier_x.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "cw_debug_solid_table"):
         lib.cw_debug_solid_table.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    if hasattr(lib, "cw_debug_anchor_block"):
+        lib.cw_debug_anchor_block.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.cw_debug_ab_layout.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     if hasattr(lib, "cw_debug_segments"):
         lib.cw_debug_segments.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
                                           C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -276,7 +279,56 @@ def _load(p):
 # the last batch went through cw_index_kernel.  Only the -DCW_TEST_AIDS library writes it.
 INDEX_ROUTE_SLOT = 63
 INDEX_ROUTE = {"staged": 1 << 0, "bytes_done": 1 << 1, "nibbles": 1 << 2, "big_ex": 1 << 3, "export_masks": 1 << 4, "export_walk": 1 << 5, "rewalk": 1 << 6,
-               "hashed": 1 << 7, "hash_passes": 1 << 8, "hash_gsort": 1 << 9, "wide": 1 << 10, "tfit": 1 << 11, "pg": 1 << 12, "hit_list": 1 << 13, "use_bits": 1 << 14}
+               "hashed": 1 << 7, "hash_passes": 1 << 8, "hash_gsort": 1 << 9, "wide": 1 << 10, "tfit": 1 << 11, "pg": 1 << 12, "hit_list": 1 << 13, "use_bits": 1 << 14,
+               "second_pass": 1 << 15, "bucket_walk": 1 << 16}
+
+
+# The anchor block of a window (csrc/cw_index.h CwAbCarve: what cw_index_kernel hands to cw_chain_kernel).  ab_layout restates cw_ab_carve<uint64_t>(0, ...):
+# tests/test_anchor_ref_cpu.py holds it to cw_debug_ab_layout, and tests/chain_probes.py takes the block's size from it.
+AB_HDR, AB_NONE16 = 64, 0xFFFF
+AB_PARTS = ("hdr", "ckey", "pres", "dirty", "badm", "rowid", "delta", "P", "end")
+
+
+def ab_np(N):
+    """cw_ab_np: a matrix row's u16 entries -- N rounded up to twice an odd number."""
+    Np = (N + 1) & ~1
+    return Np + 2 if (Np >> 1) & 1 == 0 else Np
+
+
+def ab_layout(A, N, n_dirty, n_rows):
+    """The nine byte offsets of cw_ab_carve, in the order of AB_PARTS.  Without correction rows there are neither row ids nor rows: P starts at rowid."""
+    al = lambda x: (x + 15) & ~15
+    o = {"hdr": 0, "ckey": AB_HDR}
+    o["pres"] = o["ckey"] + al(4 * A)
+    o["dirty"] = o["pres"] + al(8 * A * ((N + 63) // 64))
+    o["badm"] = o["dirty"] + al(2 * n_dirty)
+    o["rowid"] = o["badm"] + al(8 * A)
+    o["delta"] = o["rowid"] + al(A)
+    o["P"] = o["delta"] + n_rows * ((A + 15) & ~15) if n_rows else o["rowid"]
+    o["end"] = o["P"] + al(2 * A * ab_np(N))
+    return tuple(o[n] for n in AB_PARTS)
+
+
+class AnchorBlock:
+    """A window's anchor block as read back (Engine.anchor_block): the header's numbers and numpy views of the parts, cut by ab_layout.  Views of parts the
+    kernel does not write under the block's flags (badm without has_bm, the alignment gaps) show whatever the scratch held."""
+
+    def __init__(self, raw):
+        self.raw = raw
+        self.A, self.N, self.n_dirty, self.flags, self.n_rows = (int(x) for x in raw[:20].view(np.uint32))
+        self.use_bits, self.has_bm, self.has_delta = bool(self.flags & 1), bool(self.flags & 2), bool(self.flags & 4)
+        A, N = self.A, self.N
+        self.Nw, self.Np, self.Ap = (N + 63) // 64, ab_np(N), (A + 15) & ~15
+        off = dict(zip(AB_PARTS, ab_layout(A, N, self.n_dirty, self.n_rows)))
+        assert off["end"] == len(raw), (off["end"], len(raw))
+        cut = lambda name, dtype, count: raw[off[name] : off[name] + count * np.dtype(dtype).itemsize].view(dtype)
+        self.ckey = cut("ckey", np.uint32, A)
+        self.pres = cut("pres", np.uint64, A * self.Nw).reshape(A, self.Nw)
+        self.dirty = cut("dirty", np.uint16, self.n_dirty)
+        self.badm = cut("badm", np.uint64, A)
+        self.rowid = cut("rowid", np.uint8, A if self.n_rows else 0)
+        self.delta = cut("delta", np.uint8, self.n_rows * self.Ap).reshape(self.n_rows, self.Ap)
+        self.P = cut("P", np.uint16, A * self.Np).reshape(A, self.Np)
 
 
 # The chain kernel's route witness (csrc/cw_chain.h enum CwChRoute, csrc/cw_device.h CW_PS_CHAIN_ROUTE): the same for cw_chain_kernel.
@@ -1269,6 +1321,14 @@ class Engine:
         keys, counts = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
         _check(self.lib, self.lib.cw_debug_solid_table(self.handle, w, _ptr(keys), _ptr(counts), len(keys), C.byref(n)), "cw_debug_solid_table")
         return keys[: n.value], counts[: n.value]
+
+    def anchor_block(self, w):
+        """cw_debug_anchor_block: window w's anchor block of the last run, as the index kernel handed it to the chain kernel (AnchorBlock)."""
+        n = C.c_uint64()
+        _check(self.lib, self.lib.cw_debug_anchor_block(self.handle, w, None, 0, C.byref(n)), "cw_debug_anchor_block")
+        raw = np.zeros(n.value, np.uint8)
+        _check(self.lib, self.lib.cw_debug_anchor_block(self.handle, w, _ptr(raw), len(raw), C.byref(n)), "cw_debug_anchor_block")
+        return AnchorBlock(raw[: n.value])
 
     def index_route(self):
         """The INDEX_ROUTE bits of the last batch's windows, ORed (a window alone in its batch: its route).  Zero from the product library."""

@@ -42,7 +42,8 @@ four counters of the product's profile -- written down by hand from these consta
   key       `wide_key` unless A * N < 2^21 and A < 2047
   flush     `early_flush`: rounds of 64 segments queue their tasks and long single pieces, and a round that would take the queue past 64 entries
             empties it first; `long_single`: a one-member segment of more than 16 bases (and not by_anchor)
-arithmetic(ref, slab) below does these sums for the CPU test, which compares them with what is written in the catalogue.
+arithmetic(ref, slab) below does these sums for the CPU test, which compares them with what is written in the catalogue; the index kernel's share of them
+(`index` above, and where its matrix lies: tfit, pg, hit_list, wide) is index_arithmetic, which tests/anchor_ref.py and tests/anchor_probes.py use too.
 
 Arithmetic of the probes whose placement is close (room = 18688 - off_var):
   dirty rows in LDS     A 200: off_var 2408, room 16280; presence 1600 + ids 208 + 55 rows x 208 = 13248: fits; block 32528 of 34672 bytes (332 template k-mers)
@@ -55,7 +56,7 @@ import random
 
 import numpy as np
 
-from consent_amd.engine import CHAIN_ROUTE
+from consent_amd.engine import CHAIN_ROUTE, ab_layout, ab_np
 from index_probes import mutate, pack, rand_seq, substitute
 
 __all__ = ["PROBES", "reference", "arithmetic", "pack"]
@@ -124,9 +125,11 @@ def chain_of(P, sup, tie="smallest"):
     return chain, far_step
 
 
-def classify(P):
-    """(dirty sequences, number of correction rows)."""
-    dirty, bad_anchors = [], set()
+def classify(P, detail=False):
+    """(dirty sequences, number of correction rows); detail: also {dirty sequence: "forward" | "backward"} and {dirty sequence: its bad anchors, ascending}.
+    An anchor is bad in a dirty sequence when it sets no new record in the sequence's direction: forward unless the backward scan has strictly fewer bad
+    anchors."""
+    dirty, bad_anchors, direction, bad = [], set(), {}, {}
     for s in range(P.shape[1]):
         a_of = np.nonzero(P[:, s] >= 0)[0]
         pos = P[a_of, s].astype(np.int64)
@@ -138,8 +141,11 @@ def classify(P):
         dirty.append(s)
         rev = -pos[::-1]
         bwd = np.concatenate([[False], rev[1:] <= np.maximum.accumulate(rev)[:-1]])[::-1]
-        bad_anchors.update(int(a) for a in a_of[bwd if bwd.sum() < fwd.sum() else fwd])
-    return dirty, len(bad_anchors)
+        back = bwd.sum() < fwd.sum()
+        direction[s] = "backward" if back else "forward"
+        bad[s] = [int(a) for a in a_of[bwd if back else fwd]]
+        bad_anchors.update(bad[s])
+    return (dirty, len(bad_anchors), direction, bad) if detail else (dirty, len(bad_anchors))
 
 
 def segments_of(pile, P, chain, k, max_msa):
@@ -198,11 +204,7 @@ def pieces(pile, members):
 
 def block_bytes(A, N, n_dirty, n_rows):
     """cw_ab_bytes of cw_index.h: header, keys, presence, dirty list, one-word masks, and with rows the row ids and rows, then the matrix; all 16-byte aligned."""
-    al = lambda x: (x + 15) & ~15
-    Np = (N + 1) & ~1
-    Np += 2 if (Np >> 1) & 1 == 0 else 0
-    rows = al(A) + n_rows * ((A + 15) & ~15) if n_rows else 0
-    return 64 + al(4 * A) + al(8 * A * ((N + 63) // 64)) + al(2 * n_dirty) + al(8 * A) + rows + al(2 * A * Np)
+    return ab_layout(A, N, n_dirty, n_rows)[-1]  # (consent_amd/engine.py restates cw_ab_carve; tests/test_anchor_ref_cpu.py holds it to the library's)
 
 
 def slab_fits(A, slab=CH_SLAB):
@@ -211,24 +213,42 @@ def slab_fits(A, slab=CH_SLAB):
     return ((off_csc + 4 * A + 7) & ~7) <= slab - CH_LIST_BYTES and off_csc + 65 * CH_TILE_STRIDE * 2 + 4 + 256 <= slab - CH_LIST_BYTES
 
 
-def arithmetic(ref, slab=CH_SLAB):
-    """(route names, (fix, rows, masks, slow)) by the sums of the module docstring, from the reference's numbers."""
-    A, N, nd, nk0 = ref.A, ref.N, len(ref.dirty), ref.template_kmers
-    Nw = (N + 63) // 64
-    Np = (N + 1) & ~1
-    Np += 2 if (Np >> 1) & 1 == 0 else 0
-    lds = 139776 - (47360 if nk0 > 1024 else 32000)  # the index kernel's room, see `index` above
-    need = lambda rows: rows * Np * 2 + rows * Nw * 8 + 2 * N + 16
-    matrix = ((nk0 * Np + 3) & ~3) * 2 if need(nk0) <= lds else ((A * Np + 3) & ~3) * 2 if need(A) <= lds else 0
+def index_room(nk0):
+    """The index kernel's LDS between its template arrays and the staged pile: narrow layout, and wide for a template of more than 1024 k-mers."""
+    return 139776 - (47360 if nk0 > 1024 else 32000)
+
+
+def matrix_need(rows, N):
+    """cw_index.h idx_matrix_need: matrix, presence bits and dirty list of `rows` rows."""
+    return rows * ab_np(N) * 2 + rows * ((N + 63) // 64) * 8 + 2 * N + 16
+
+
+def index_arithmetic(A, N, nd, nk0, rows):
+    """What the index kernel's anchor phase decides for a window of A anchors among nk0 template k-mers, N sequences, nd dirty ones and `rows` anchors bad
+    somewhere, by the sums of `index` in the module docstring: a dict of wide, tfit, pg, hit_list (idx_hit_list: the support pass writes the list),
+    use_bits, n_dirty (what the block says: 0 without bitsets), W, masks (they exist), masks_count (the presence bits go by them: one word, or rows made of
+    wider ones), one_word (the chain kernel sees them: the header's flag 2), fix (rows exist: flag 4), n_rows."""
+    Nw, Np, lds = (N + 63) // 64, ab_np(N), index_room(nk0)
+    tfit = matrix_need(nk0, N) <= lds
+    pg = not tfit and matrix_need(A, N) > lds
+    matrix = ((nk0 * Np + 3) & ~3) * 2 if tfit else ((A * Np + 3) & ~3) * 2 if not pg else 0
     lists_end = matrix + A * Nw * 8 + 2 * N
     use_bits = N <= 2048 and lists_end <= lds
     if not use_bits:
         nd = 0  # no classification without bitsets: the block says no dirty sequence
     W = max(1, (nd + 63) // 64)
     masks = 0 < nd <= 255 and W <= (4 if N <= 1024 else 1) and ((((lists_end + 7) & ~7) + 33 * A + 1) & ~1) + 508 <= lds
-    fix = masks and 1 <= ref.rows <= 254 and block_bytes(A, N, nd, ref.rows) <= block_bytes(ref.template_kmers, N, N, 0)
-    n_rows = ref.rows if fix else 0
-    one_word = masks and W == 1
+    fix = masks and 1 <= rows <= 254 and block_bytes(A, N, nd, rows) <= block_bytes(nk0, N, N, 0)
+    return dict(wide=nk0 > 1024, tfit=tfit, pg=pg, hit_list=not tfit and N <= 1024, use_bits=use_bits, n_dirty=nd, W=W, masks=masks,
+                masks_count=masks and (W == 1 or fix), one_word=masks and W == 1, fix=fix, n_rows=rows if fix else 0)
+
+
+def arithmetic(ref, slab=CH_SLAB):
+    """(route names, (fix, rows, masks, slow)) by the sums of the module docstring, from the reference's numbers."""
+    A, N = ref.A, ref.N
+    Nw = (N + 63) // 64
+    ia = index_arithmetic(A, N, len(ref.dirty), ref.template_kmers, ref.rows)
+    use_bits, nd, fix, n_rows, one_word = ia["use_bits"], ia["n_dirty"], ia["fix"], ia["n_rows"], ia["one_word"]
     off_csc = (8 * A + 5) & ~3
     room = slab - CH_LIST_BYTES - ((off_csc + 4 * A + 7) & ~7)
     Ap = (A + 15) & ~15
