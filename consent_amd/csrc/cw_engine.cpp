@@ -122,10 +122,14 @@ int set_kernel_attributes(const hipDeviceProp_t& prop) {
         allow(TierM1::kernel<1>(), TierM1::lds) && allow(TierM2::kernel<1>(), TierM2::lds) && allow(TierL::kernel<1>(), TierL::lds) &&
         allow((const void*)cw_finish_kernel<CW_FIN_CB, CW_FIN_WAVES, false>, kLdsFinish) && allow((const void*)cw_finish_kernel<CW_FIN_CB_BIG, 1, true>, kLdsFinishBig) &&
         allow((const void*)cw_stitch_kernel<CW_ST_QMAX, CW_ST_RMAX, 16, CW_ST_WAVES>, lds_st) &&
-        allow((const void*)cw_sw_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_kernel<1>, lds_sw(1)) &&
-        allow((const void*)cw_sw_path_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_path_kernel<1>, lds_sw(1)) &&
-        allow((const void*)cw_pileup_kernel<0>, lds_sw(0)) && allow((const void*)cw_pileup_kernel<1>, lds_sw(1)) &&
-        allow((const void*)cw_sw_cut_kernel<0>, lds_sw(0)) && allow((const void*)cw_sw_cut_kernel<1>, lds_sw(1)) &&
+        allow((const void*)cw_sw_kernel<0, false>, lds_sw(0)) && allow((const void*)cw_sw_kernel<1, false>, lds_sw(1)) &&
+        allow((const void*)cw_sw_path_kernel<0, false>, lds_sw(0)) && allow((const void*)cw_sw_path_kernel<1, false>, lds_sw(1)) &&
+        allow((const void*)cw_pileup_kernel<0, false>, lds_sw(0)) && allow((const void*)cw_pileup_kernel<1, false>, lds_sw(1)) &&
+        allow((const void*)cw_sw_cut_kernel<0, false>, lds_sw(0)) && allow((const void*)cw_sw_cut_kernel<1, false>, lds_sw(1)) &&
+        allow((const void*)cw_sw_kernel<0, true>, lds_sw(0)) && allow((const void*)cw_sw_kernel<1, true>, lds_sw(1)) &&
+        allow((const void*)cw_sw_path_kernel<0, true>, lds_sw(0)) && allow((const void*)cw_sw_path_kernel<1, true>, lds_sw(1)) &&
+        allow((const void*)cw_pileup_kernel<0, true>, lds_sw(0)) && allow((const void*)cw_pileup_kernel<1, true>, lds_sw(1)) &&
+        allow((const void*)cw_sw_cut_kernel<0, true>, lds_sw(0)) && allow((const void*)cw_sw_cut_kernel<1, true>, lds_sw(1)) &&
         allow((const void*)cw_strand_kernel<1>, kLdsStrandWide) && allow((const void*)cw_seed_kernel<1>, kLdsSeedWide);
     return ok ? CW_OK : CW_E_NO_DEVICE;
 }
@@ -491,6 +495,12 @@ int validate_sw_cut(const cw_engine* e, const cw_batch* groups, const int32_t* r
     return validate_groups(e, groups, rows);
 }
 
+/* What a span run (cw_sw_span_run and its kin) refuses on top of its counterpart, once the batch is known to hold sequences: a missing member.  spans is NULL
+   for the entry points without spans; the span entry points refuse a NULL of their own before they come here. */
+int validate_spans(const cw_sw_spans* spans, uint32_t n_seqs) {
+    return spans && n_seqs > 0 && (!spans->ref_lo || !spans->ref_hi) ? CW_E_INVALID : CW_OK;
+}
+
 /* The device, the stream and the plan's bytes of a run.  The plan lives in the engine's one scratch allocation, like a window run's and a POA run's: runs on one
    engine are serialised by its mutex and ordered on its stream (or by the caller, include/consent_amd.h "Threading"), so none of them is in flight while
    another's plan is bound.  (stitch_scratch is cw_stitch_device's alone: nothing here touches it.) */
@@ -501,7 +511,7 @@ int hold_sw(cw_engine* e, size_t total, void* hip_stream, hipStream_t* st) {
 }
 
 /* the arguments every kernel of the four runs takes, by the plan's offsets (a path plan is a plan and the steps) */
-SwArgs bind_sw(const cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, const SwPlan& p) {
+SwArgs bind_sw(const cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, const SwPlan& p, const cw_sw_spans* spans) {
     uint8_t* base = (uint8_t*)e->scratch;
     SwArgs a;
     a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
@@ -509,6 +519,7 @@ SwArgs bind_sw(const cw_engine* e, const cw_batch* groups, int32_t* rows, uint32
     a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
     a.dir = p.dir_bytes ? (int8_t*)(base + p.dir) : nullptr; a.dir_bytes = p.dir_bytes;
     a.gref = base + p.gref; a.lstate = base + p.lstate;
+    a.ref_lo = spans ? spans->ref_lo : nullptr; a.ref_hi = spans ? spans->ref_hi : nullptr;
     return a;
 }
 
@@ -551,63 +562,71 @@ int enqueue_sw_run(cw_engine* e, hipStream_t st, const SwArgs& a, const SwPlan& 
     return CW_OK;
 }
 
-/* the body of cw_sw_run_device; the caller holds e->mu.  Stages: sw_order, sw_align, sw_align_wide, sw_align_long. */
-int run_sw_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, void* hip_stream) {
+/* the body of cw_sw_run_device and of cw_sw_span_run_device (spans: NULL for the first; the same in the three bodies below); the caller holds e->mu.  Stages: sw_order, sw_align, sw_align_wide, sw_align_long. */
+int run_sw_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, void* hip_stream, const cw_sw_spans* spans = nullptr) {
     int rc = validate_sw(e, groups, rows, flags);
+    if (!rc) rc = validate_spans(spans, groups->n_seqs);
     if (rc || groups->n_seqs == 0) return rc;
     const SwPlan p = plan_sw(groups->n_windows, groups->n_seqs, groups->n_words, e->cus, flags); /* exact: no run with a larger plan follows */
     hipStream_t st;
     if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
-    const SwArgs a = bind_sw(e, groups, rows, flags, p);
-    return enqueue_sw_run(e, st, a, p, SwStages<SwArgs>{{"sw_align", "sw_align_wide", "sw_align_long"}, cw_sw_kernel<0>, cw_sw_kernel<1>, cw_sw_long_kernel}, a);
+    const SwArgs a = bind_sw(e, groups, rows, flags, p, spans);
+    return enqueue_sw_run(e, st, a, p, spans ? SwStages<SwArgs>{{"sw_align", "sw_align_wide", "sw_align_long"}, cw_sw_kernel<0, true>, cw_sw_kernel<1, true>, cw_sw_long_kernel<true>}
+                                       : SwStages<SwArgs>{{"sw_align", "sw_align_wide", "sw_align_long"}, cw_sw_kernel<0, false>, cw_sw_kernel<1, false>, cw_sw_long_kernel<false>}, a);
 }
 
 /* the body of cw_sw_path_run_device.  Stages: sw_order, sw_path, sw_path_wide, sw_path_long. */
-int run_sw_path_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream) {
+int run_sw_path_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream, const cw_sw_spans* spans = nullptr) {
     int rc = validate_sw_path(e, groups, rows, paths, flags);
+    if (!rc) rc = validate_spans(spans, groups->n_seqs);
     if (rc || groups->n_seqs == 0) return rc;
     const SwPathPlan p = plan_sw_path(groups->n_windows, groups->n_seqs, groups->n_words, e->cus);
     hipStream_t st;
     if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
     SwPathArgs pa;
-    pa.a = bind_sw(e, groups, rows, flags, p);
+    pa.a = bind_sw(e, groups, rows, flags, p, spans);
     pa.ops = paths->ops; pa.ops_off = paths->ops_off; pa.n_ops = paths->n_ops; pa.steps = (uint8_t*)e->scratch + p.steps;
     SwExtras x;
     x.zero = pa.n_ops;
-    return enqueue_sw_run(e, st, pa.a, p, SwStages<SwPathArgs>{{"sw_path", "sw_path_wide", "sw_path_long"}, cw_sw_path_kernel<0>, cw_sw_path_kernel<1>, cw_sw_path_long_kernel}, pa, x);
+    return enqueue_sw_run(e, st, pa.a, p, spans ? SwStages<SwPathArgs>{{"sw_path", "sw_path_wide", "sw_path_long"}, cw_sw_path_kernel<0, true>, cw_sw_path_kernel<1, true>, cw_sw_path_long_kernel<true>}
+                                       : SwStages<SwPathArgs>{{"sw_path", "sw_path_wide", "sw_path_long"}, cw_sw_path_kernel<0, false>, cw_sw_path_kernel<1, false>, cw_sw_path_long_kernel<false>}, pa, x);
 }
 
 /* the body of cw_pileup_run_device.  Stages: sw_order, pile_clear unless the run accumulates, pile, pile_wide, pile_long.  The plan is plan_sw_path's: there is
    no op memory to add. */
-int run_pileup_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream) {
+int run_pileup_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream, const cw_sw_spans* spans = nullptr) {
     int rc = validate_pileup(e, groups, rows, pile, flags);
+    if (!rc) rc = validate_spans(spans, groups->n_seqs);
     if (rc || groups->n_seqs == 0) return rc;
     if ((uintptr_t)pile->counts & 15u) return CW_E_INVALID; /* the clearing stores 16 bytes at a time */
     const SwPathPlan p = plan_sw_path(groups->n_windows, groups->n_seqs, groups->n_words, e->cus);
     hipStream_t st;
     if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
     PileArgs pa;
-    pa.a = bind_sw(e, groups, rows, flags, p);
+    pa.a = bind_sw(e, groups, rows, flags, p, spans);
     pa.counts = pile->counts; pa.col_off = pile->col_off; pa.steps = (uint8_t*)e->scratch + p.steps;
     SwExtras x;
     if (!(flags & CW_PILE_ACCUMULATE)) x.clear = &pa;
-    return enqueue_sw_run(e, st, pa.a, p, SwStages<PileArgs>{{"pile", "pile_wide", "pile_long"}, cw_pileup_kernel<0>, cw_pileup_kernel<1>, cw_pileup_long_kernel}, pa, x);
+    return enqueue_sw_run(e, st, pa.a, p, spans ? SwStages<PileArgs>{{"pile", "pile_wide", "pile_long"}, cw_pileup_kernel<0, true>, cw_pileup_kernel<1, true>, cw_pileup_long_kernel<true>}
+                                       : SwStages<PileArgs>{{"pile", "pile_wide", "pile_long"}, cw_pileup_kernel<0, false>, cw_pileup_kernel<1, false>, cw_pileup_long_kernel<false>}, pa, x);
 }
 
 /* the body of cw_sw_cut_run_device.  Stages: sw_order -- with it the zeros of the queries that are no pair -- cut, cut_wide, cut_long.  The plan is
    plan_sw_path's. */
-int run_sw_cut_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, void* hip_stream) {
+int run_sw_cut_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, void* hip_stream, const cw_sw_spans* spans = nullptr) {
     int rc = validate_sw_cut(e, groups, rows, cuts);
+    if (!rc) rc = validate_spans(spans, groups->n_seqs);
     if (rc || groups->n_seqs == 0) return rc;
     const SwPathPlan p = plan_sw_path(groups->n_windows, groups->n_seqs, groups->n_words, e->cus);
     hipStream_t st;
     if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
     CutArgs ca;
-    ca.a = bind_sw(e, groups, rows, 0u, p);
+    ca.a = bind_sw(e, groups, rows, 0u, p, spans);
     ca.cuts = cuts->cuts; ca.cut_off = cuts->cut_off; ca.window = cuts->window; ca.steps = (uint8_t*)e->scratch + p.steps;
     SwExtras x;
     x.rest = &ca;
-    return enqueue_sw_run(e, st, ca.a, p, SwStages<CutArgs>{{"cut", "cut_wide", "cut_long"}, cw_sw_cut_kernel<0>, cw_sw_cut_kernel<1>, cw_sw_cut_long_kernel}, ca, x);
+    return enqueue_sw_run(e, st, ca.a, p, spans ? SwStages<CutArgs>{{"cut", "cut_wide", "cut_long"}, cw_sw_cut_kernel<0, true>, cw_sw_cut_kernel<1, true>, cw_sw_cut_long_kernel<true>}
+                                       : SwStages<CutArgs>{{"cut", "cut_wide", "cut_long"}, cw_sw_cut_kernel<0, false>, cw_sw_cut_kernel<1, false>, cw_sw_cut_long_kernel<false>}, ca, x);
 }
 
 /* What the four host-buffer entry points check first: the groups begin at sequence 0, end at n_seqs and never step back, every sequence lies inside n_words, and
@@ -631,13 +650,14 @@ int check_groups(const cw_batch* b, const uint64_t* slot_off, std::vector<uint64
    behind it the slot offsets rebased to the first slot -- the device copy of the slots begins there.  *db: the batch with device pointers; *rebased: the rebased
    offsets on the host, which must live until the stream is synchronised; *d_off: the same on the device.  An entry point calls this last before the run: its own
    host allocations and its output buffer are in place by then, so behind the first copy enqueued here it returns early only as it always did, when the run
-   itself fails. */
-int upload_groups(cw_engine* e, const cw_batch* b, const std::vector<uint64_t>* rebased, cw_batch* db, const uint64_t** d_off) {
+   itself fails.  A span run's two arrays (spans, when not NULL) go up behind those; *dspans: the same on the device. */
+int upload_groups(cw_engine* e, const cw_batch* b, const std::vector<uint64_t>* rebased, cw_batch* db, const uint64_t** d_off, const cw_sw_spans* spans = nullptr,
+                  cw_sw_spans* dspans = nullptr) {
     const uint32_t G = b->n_windows, S = b->n_seqs;
     size_t o = 0;
     auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
     const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
-                 i_soff = rebased ? put((size_t)(S + 1) * 8) : 0;
+                 i_soff = rebased ? put((size_t)(S + 1) * 8) : 0, i_lo = spans ? put((size_t)S * 4) : 0, i_hi = spans ? put((size_t)S * 4) : 0;
     if (int rc = ensure(&e->poa_in, &e->poa_in_bytes, o)) return rc;
     uint8_t* din = (uint8_t*)e->poa_in;
     hipStream_t st = e->stream;
@@ -648,6 +668,11 @@ int upload_groups(cw_engine* e, const cw_batch* b, const std::vector<uint64_t>* 
     if (rebased) {
         CW_HIP(hipMemcpyAsync(din + i_soff, rebased->data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
         *d_off = (const uint64_t*)(din + i_soff);
+    }
+    if (spans) {
+        CW_HIP(hipMemcpyAsync(din + i_lo, spans->ref_lo, (size_t)S * 4, hipMemcpyHostToDevice, st));
+        CW_HIP(hipMemcpyAsync(din + i_hi, spans->ref_hi, (size_t)S * 4, hipMemcpyHostToDevice, st));
+        dspans->ref_lo = (const uint32_t*)(din + i_lo); dspans->ref_hi = (const uint32_t*)(din + i_hi);
     }
     *db = *b;
     db->win_first_seq = (const uint32_t*)(din + i_wfs); db->seq_len = (const uint32_t*)(din + i_len);
@@ -916,26 +941,38 @@ int cw_sw_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32
     return run_sw_locked(e, groups, rows, flags, hip_stream);
 }
 
+int cw_sw_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_spans* spans, uint32_t flags, void* hip_stream) {
+    if (!e || !spans) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_sw_locked(e, groups, rows, flags, hip_stream, spans);
+}
+
 /* Host buffers in, host buffers out, synchronous: the batch goes up (upload_groups), cw_sw_run_device on the engine's stream, the rows come back.  The engine's
-   mutex is held throughout: the device buffers are the engine's. */
-int cw_sw_run(cw_engine* e, const cw_batch* b, int32_t* rows, uint32_t flags) {
+   mutex is held throughout: the device buffers are the engine's.  One body for cw_sw_run and cw_sw_span_run, as for the three pairs of host forms below: a span
+   run's two arrays go up with the batch. */
+static int sw_run_host(cw_engine* e, const cw_batch* b, int32_t* rows, uint32_t flags, const cw_sw_spans* spans) {
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
     int rc = validate_sw(e, b, rows, flags);
+    if (!rc) rc = validate_spans(spans, b->n_seqs);
     if (rc || b->n_seqs == 0) return rc;
+    cw_sw_spans dsp;
     const uint32_t S = b->n_seqs;
     cw_batch db;
     if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
     const size_t out_bytes = (size_t)S * CW_SW_ROW * 4;
     CW_HIP(hipSetDevice(e->device));
     if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, nullptr, &db, nullptr, spans, &dsp)) != CW_OK) return rc;
     hipStream_t st = e->stream;
-    if ((rc = run_sw_locked(e, &db, (int32_t*)e->poa_out, flags, st)) != CW_OK) return rc;
+    if ((rc = run_sw_locked(e, &db, (int32_t*)e->poa_out, flags, st, spans ? &dsp : nullptr)) != CW_OK) return rc;
     CW_HIP(hipMemcpyAsync(rows, e->poa_out, out_bytes, hipMemcpyDeviceToHost, st));
     CW_HIP(hipStreamSynchronize(st));
     return sw_rows_rc(rows, S);
 }
+
+int cw_sw_run(cw_engine* e, const cw_batch* b, int32_t* rows, uint32_t flags) { return sw_run_host(e, b, rows, flags, nullptr); }
+int cw_sw_span_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_spans* spans, uint32_t flags) { return spans ? sw_run_host(e, b, rows, flags, spans) : CW_E_INVALID; }
 
 int cw_sw_path_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream) {
     if (!e) return CW_E_INVALID;
@@ -943,13 +980,21 @@ int cw_sw_path_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, c
     return run_sw_path_locked(e, groups, rows, paths, flags, hip_stream);
 }
 
+int cw_sw_path_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, const cw_sw_spans* spans, uint32_t flags, void* hip_stream) {
+    if (!e || !spans) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_sw_path_locked(e, groups, rows, paths, flags, hip_stream, spans);
+}
+
 /* Host buffers in, host buffers out, synchronous, as cw_sw_run: the batch and the slots' offsets go up, cw_sw_path_run_device on the engine's stream, rows and
    op counts come back -- and of the ops only what was written: a slot's words beyond its path, and every slot without one, stay the caller's. */
-int cw_sw_path_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_paths* paths, uint32_t flags) {
+static int sw_path_run_host(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, const cw_sw_spans* spans) {
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
     int rc = validate_sw_path(e, b, rows, paths, flags);
+    if (!rc) rc = validate_spans(spans, b->n_seqs);
     if (rc || b->n_seqs == 0) return rc;
+    cw_sw_spans dsp;
     const uint32_t S = b->n_seqs;
     cw_batch db;
     std::vector<uint64_t> poff;
@@ -963,11 +1008,11 @@ int cw_sw_path_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_p
     try { back.resize((size_t)n_slots); } catch (...) { return CW_E_NOMEM; }
     CW_HIP(hipSetDevice(e->device));
     if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, o)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, &poff, &db, &dp.ops_off)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, &poff, &db, &dp.ops_off, spans, &dsp)) != CW_OK) return rc;
     uint8_t* dout = (uint8_t*)e->poa_out;
     hipStream_t st = e->stream;
     dp.ops = (uint32_t*)(dout + o_ops); dp.n_ops = (uint32_t*)(dout + o_nops);
-    if ((rc = run_sw_path_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st)) != CW_OK) return rc;
+    if ((rc = run_sw_path_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st, spans ? &dsp : nullptr)) != CW_OK) return rc;
     CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
     CW_HIP(hipMemcpyAsync(paths->n_ops, dout + o_nops, (size_t)S * 4, hipMemcpyDeviceToHost, st));
     if (n_slots) CW_HIP(hipMemcpyAsync(back.data(), dout + o_ops, (size_t)n_slots * 4, hipMemcpyDeviceToHost, st));
@@ -978,20 +1023,33 @@ int cw_sw_path_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_p
     return sw_rows_rc(rows, S);
 }
 
+int cw_sw_path_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_paths* paths, uint32_t flags) { return sw_path_run_host(e, b, rows, paths, flags, nullptr); }
+int cw_sw_path_span_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_paths* paths, const cw_sw_spans* spans, uint32_t flags) {
+    return spans ? sw_path_run_host(e, b, rows, paths, flags, spans) : CW_E_INVALID;
+}
+
 int cw_pileup_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream) {
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
     return run_pileup_locked(e, groups, rows, pile, flags, hip_stream);
 }
 
+int cw_pileup_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, const cw_sw_spans* spans, uint32_t flags, void* hip_stream) {
+    if (!e || !spans) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_pileup_locked(e, groups, rows, pile, flags, hip_stream, spans);
+}
+
 /* Host buffers in, host buffers out, synchronous, as cw_sw_path_run: the batch and the slots' offsets go up -- the caller's counts too, but only under
    CW_PILE_ACCUMULATE -- cw_pileup_run_device on the engine's stream, the rows come back, and of the counts what a run owns: columns 0 .. ref_len - 1 of every
    reference whose slot holds them.  A slot's words beyond those, a slot that is too short and every query's slot stay the caller's. */
-int cw_pileup_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileup* pile, uint32_t flags) {
+static int pileup_run_host(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileup* pile, uint32_t flags, const cw_sw_spans* spans) {
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
     int rc = validate_pileup(e, b, rows, pile, flags);
+    if (!rc) rc = validate_spans(spans, b->n_seqs);
     if (rc || b->n_seqs == 0) return rc;
+    cw_sw_spans dsp;
     const uint32_t G = b->n_windows, S = b->n_seqs;
     cw_batch db;
     std::vector<uint64_t> coff;
@@ -1013,13 +1071,13 @@ int cw_pileup_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileu
     } catch (...) { return CW_E_NOMEM; }
     CW_HIP(hipSetDevice(e->device));
     if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, o)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, &coff, &db, &dp.col_off)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, &coff, &db, &dp.col_off, spans, &dsp)) != CW_OK) return rc;
     uint8_t* dout = (uint8_t*)e->poa_out;
     hipStream_t st = e->stream;
     dp.counts = (uint32_t*)(dout + o_counts);
     if ((flags & CW_PILE_ACCUMULATE) && n_cols) /* every slot in one copy; the run reads and writes the owned columns only */
         CW_HIP(hipMemcpyAsync(dp.counts, pile->counts + c0 * CW_PILE_COL, (size_t)n_cols * col_bytes, hipMemcpyHostToDevice, st));
-    if ((rc = run_pileup_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st)) != CW_OK) return rc;
+    if ((rc = run_pileup_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st, spans ? &dsp : nullptr)) != CW_OK) return rc;
     CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
     if (n_cols) CW_HIP(hipMemcpyAsync(back.data(), dp.counts, (size_t)n_cols * col_bytes, hipMemcpyDeviceToHost, st));
     CW_HIP(hipStreamSynchronize(st));
@@ -1028,20 +1086,33 @@ int cw_pileup_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileu
     return sw_rows_rc(rows, S);
 }
 
+int cw_pileup_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileup* pile, uint32_t flags) { return pileup_run_host(e, b, rows, pile, flags, nullptr); }
+int cw_pileup_span_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileup* pile, const cw_sw_spans* spans, uint32_t flags) {
+    return spans ? pileup_run_host(e, b, rows, pile, flags, spans) : CW_E_INVALID;
+}
+
 int cw_sw_cut_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, void* hip_stream) {
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
     return run_sw_cut_locked(e, groups, rows, cuts, hip_stream);
 }
 
+int cw_sw_cut_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, const cw_sw_spans* spans, void* hip_stream) {
+    if (!e || !spans) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_sw_cut_locked(e, groups, rows, cuts, hip_stream, spans);
+}
+
 /* Host buffers in, host buffers out, synchronous, as cw_pileup_run: the batch and the slots' offsets go up, cw_sw_cut_run_device on the engine's stream, the
    rows come back, and of the slots what a run owns: the T + 1 words of every query whose slot holds them.  A slot's words beyond those, a slot that is too
    short and every reference's slot stay the caller's. */
-int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cuts* cuts) {
+static int sw_cut_run_host(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cuts* cuts, const cw_sw_spans* spans) {
     if (!e) return CW_E_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
     int rc = validate_sw_cut(e, b, rows, cuts);
+    if (!rc) rc = validate_spans(spans, b->n_seqs);
     if (rc || b->n_seqs == 0) return rc;
+    cw_sw_spans dsp;
     const uint32_t G = b->n_windows, S = b->n_seqs, W = cuts->window;
     cw_batch db;
     std::vector<uint64_t> coff;
@@ -1064,11 +1135,11 @@ int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cu
     } catch (...) { return CW_E_NOMEM; }
     CW_HIP(hipSetDevice(e->device));
     if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, o)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, &coff, &db, &dc.cut_off)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, &coff, &db, &dc.cut_off, spans, &dsp)) != CW_OK) return rc;
     uint8_t* dout = (uint8_t*)e->poa_out;
     hipStream_t st = e->stream;
     dc.cuts = (uint32_t*)(dout + o_cuts); dc.window = W;
-    if ((rc = run_sw_cut_locked(e, &db, (int32_t*)(dout + o_rows), &dc, st)) != CW_OK) return rc;
+    if ((rc = run_sw_cut_locked(e, &db, (int32_t*)(dout + o_rows), &dc, st, spans ? &dsp : nullptr)) != CW_OK) return rc;
     CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
     if (n_slots) CW_HIP(hipMemcpyAsync(back.data(), dc.cuts, (size_t)n_slots * 4, hipMemcpyDeviceToHost, st));
     CW_HIP(hipStreamSynchronize(st));
@@ -1077,6 +1148,9 @@ int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cu
             memcpy(cuts->cuts + cuts->cut_off[sw.first], back.data() + coff[sw.first], (size_t)sw.second * 4);
     return sw_rows_rc(rows, S);
 }
+
+int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cuts* cuts) { return sw_cut_run_host(e, b, rows, cuts, nullptr); }
+int cw_sw_cut_span_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cuts* cuts, const cw_sw_spans* spans) { return spans ? sw_cut_run_host(e, b, rows, cuts, spans) : CW_E_INVALID; }
 
 int cw_strand_run_device(cw_engine* e, const cw_batch* groups, const cw_strands* out, void* hip_stream) {
     if (!e) return CW_E_INVALID;
@@ -1136,6 +1210,59 @@ int cw_seed_run(cw_engine* e, const cw_batch* b, const cw_seeds* out) {
     if ((rc = run_seed_locked(e, &db, &ds, st)) != CW_OK) return rc;
     CW_HIP(hipMemcpyAsync(out->rows, ds.rows, row_bytes, hipMemcpyDeviceToHost, st));
     if (out->strand) CW_HIP(hipMemcpyAsync(out->strand, ds.strand, (size_t)S, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    return CW_OK;
+}
+
+/* the body of cw_seed_spans_device; the caller holds e->mu.  One stage: seed_spans.  No scratch, as the reverse complement. */
+static int run_seed_spans_locked(cw_engine* e, const cw_batch* groups, const int32_t* seed_rows, uint32_t min_hits, uint32_t pad, uint32_t pad_shift, uint32_t* ref_lo, uint32_t* ref_hi,
+                          void* hip_stream) {
+    if (!e || !groups || pad_shift > 31u) return CW_E_INVALID;
+    int rc = validate_groups(e, groups, seed_rows);
+    if (rc || groups->n_seqs == 0) return rc;
+    if (!ref_lo || !ref_hi) return CW_E_INVALID;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    SeedSpanArgs a;
+    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.n_seqs = groups->n_seqs; a.rows = seed_rows; a.min_hits = min_hits; a.pad = pad; a.pad_shift = pad_shift; a.ref_lo = ref_lo; a.ref_hi = ref_hi;
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    stage(e, st, "seed_spans", [&] { cw_seed_spans_kernel<<<(a.n_seqs + 255u) / 256u, 256, 0, st>>>(a); });
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
+}
+
+int cw_seed_spans_device(cw_engine* e, const cw_batch* groups, const int32_t* seed_rows, uint32_t min_hits, uint32_t pad, uint32_t pad_shift, uint32_t* ref_lo, uint32_t* ref_hi,
+                         void* hip_stream) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return run_seed_spans_locked(e, groups, seed_rows, min_hits, pad, pad_shift, ref_lo, ref_hi, hip_stream);
+}
+
+/* Host buffers in, host buffers out, synchronous: the batch and the seed rows go up, cw_seed_spans_device on the engine's stream, the two arrays come back. */
+int cw_seed_spans(cw_engine* e, const cw_batch* b, const int32_t* seed_rows, uint32_t min_hits, uint32_t pad, uint32_t pad_shift, uint32_t* ref_lo, uint32_t* ref_hi) {
+    if (!e || !b || pad_shift > 31u) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = validate_groups(e, b, seed_rows);
+    if (rc || b->n_seqs == 0) return rc;
+    if (!ref_lo || !ref_hi) return CW_E_INVALID;
+    const uint32_t S = b->n_seqs;
+    cw_batch db;
+    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
+    const size_t row_bytes = (size_t)S * CW_SEED_ROW * 4, o_lo = align_up(row_bytes, 256), o_hi = o_lo + align_up((size_t)S * 4, 256), out_bytes = o_hi + (size_t)S * 4;
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
+    hipStream_t st = e->stream;
+    uint8_t* dout = (uint8_t*)e->poa_out;
+    CW_HIP(hipMemcpyAsync(dout, seed_rows, row_bytes, hipMemcpyHostToDevice, st));
+    if ((rc = run_seed_spans_locked(e, &db, (const int32_t*)dout, min_hits, pad, pad_shift, (uint32_t*)(dout + o_lo), (uint32_t*)(dout + o_hi), st)) != CW_OK) return rc;
+    CW_HIP(hipMemcpyAsync(ref_lo, dout + o_lo, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipMemcpyAsync(ref_hi, dout + o_hi, (size_t)S * 4, hipMemcpyDeviceToHost, st));
     CW_HIP(hipStreamSynchronize(st));
     return CW_OK;
 }

@@ -70,16 +70,16 @@ __device__ __forceinline__ void pile_count(const uint8_t* steps, uint32_t n, uin
 }
 
 /* one pair on one wave, its buffers in place, as sw_path_pair: align, the banded pass, the walk -- then the counts in place of the ops -- the row */
-template <int CLS>
+template <int CLS, bool SPAN>
 __device__ __forceinline__ void pile_pair(const PileArgs& pa, uint32_t s, uint8_t* refc, uint8_t* qfw, uint8_t* qrv, uint32_t qrv_bytes, bool qrv_lds, uint8_t* rows, uint8_t* dirbuf, uint8_t* steps,
                                           uint8_t* state, int lane) {
     const SwArgs& a = pa.a;
     const uint32_t r = st_uni(a.seq_ref[s]);
     const uint32_t m = st_uni(a.b.seq_len[s]), n = st_uni(a.b.seq_len[r]);
-    sw_unpack(refc, a.b.bases + a.b.seq_word_off[r], n, lane);
+    const uint32_t sn = sw_unpack_ref<SPAN>(a, refc, s, r, n, lane);
     sw_unpack(qfw, a.b.bases + a.b.seq_word_off[s], m, lane);
     st_mem_sync();
-    const StAlign al = sw_align<CLS>(qfw, (int)m, qrv, refc, (int)n, lane, state);
+    const StAlign al = sw_align<CLS>(qfw, (int)m, qrv, refc, (int)sn, lane, state); /* in the span's coordinates, as everything up to the walk */
     uint32_t ins = 0, del = 0;
     int status = CW_SW_ALIGNED;
     if (al.score > 0) {
@@ -91,24 +91,31 @@ __device__ __forceinline__ void pile_pair(const PileArgs& pa, uint32_t s, uint8_
             const SwWalk w = sw_walk(bd, refLen, readLen, steps, lane);
             ins = w.ins; del = w.del;
             if (!w.closed) status = CW_SW_PATH_OPEN;
-            else if (!pile_slot_holds(pa.col_off, r, n) || al.ref_begin < 0 || (uint32_t)al.ref_begin + (uint32_t)refLen > n) status = CW_SW_PILE_SLOT; /* (the ends lie inside the reference) */
-            else pile_count(steps, w.n_steps, (uint32_t)refLen, read0, pa.counts + (pa.col_off[r] + (uint64_t)al.ref_begin) * CW_PILE_COL, lane);
+            else {
+                const SwSpan sl{st_uni(sw_pair_lo<SPAN>(a, s)), st_uni(sw_pair_len<SPAN>(a, s, n))};
+                if (!pile_slot_holds(pa.col_off, r, n) || al.ref_begin < 0 || (uint32_t)al.ref_begin + (uint32_t)refLen > sl.len) status = CW_SW_PILE_SLOT; /* (the ends lie inside the span, the span inside the reference) */
+                else pile_count(steps, w.n_steps, (uint32_t)refLen, read0, pa.counts + (pa.col_off[r] + (uint64_t)sl.lo + (uint64_t)al.ref_begin) * CW_PILE_COL, lane); /* columns are absolute */
+            }
         }
     }
-    if (lane == 0) sw_write_row(a.rows + (size_t)s * CW_SW_ROW, al.score, al.ref_begin, al.ref_end, al.query_begin, al.query_end, ins, del, status);
+    if (lane == 0) {
+        const int lo = al.score > 0 ? (int)sw_pair_lo<SPAN>(a, s) : 0; /* the row is absolute */
+        sw_write_row(a.rows + (size_t)s * CW_SW_ROW, al.score, al.ref_begin + lo, al.ref_end + lo, al.query_begin, al.query_end, ins, del, status);
+    }
     st_mem_sync(); /* the next pair's unpacking overwrites what this one read */
 }
 
-template <int CLS>
+template <int CLS, bool SPAN>
 __global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_pileup_kernel(PileArgs pa) {
-    sw_class_loop<CLS, true>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
-        pile_pair<CLS>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+    sw_class_loop<CLS, true, SPAN>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        pile_pair<CLS, SPAN>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
     });
 }
 
+template <bool SPAN>
 __global__ void __launch_bounds__(64, 2) cw_pileup_long_kernel(PileArgs pa) {
     sw_long_loop<true>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
-        pile_pair<2>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+        pile_pair<2, SPAN>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
     });
 }
 

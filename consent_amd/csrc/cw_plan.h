@@ -214,7 +214,7 @@ static inline SwPlan plan_sw(uint32_t n_groups, uint32_t n_seqs, uint64_t n_word
     size_t o = 0;
     auto put = [&](size_t& slot, size_t bytes) { slot = o; o = align_up(o + bytes, 256); };
     put(p.ctr, (size_t)CW_SW_CTR_WORDS * 4);
-    put(p.seq_ref, (size_t)n_seqs * 4);
+    put(p.seq_ref, (size_t)n_seqs * 12); /* a pair's reference, its span's first column, its span's columns */
     put(p.order, (size_t)n_seqs * 4);
     put(p.gref, (size_t)std::max(p.wgs0, p.wgs1) * CW_SW_WAVES * CW_SW_GREF_BYTES);
     put(p.lstate, (size_t)p.wgs_long * CW_SW_LONG_WAVE_BYTES);
@@ -241,7 +241,7 @@ static inline SwPathPlan plan_sw_path(uint32_t n_groups, uint32_t n_seqs, uint64
     size_t o = 0;
     auto put = [&](size_t& slot, size_t bytes) { slot = o; o = align_up(o + bytes, 256); };
     put(p.ctr, (size_t)CW_SW_CTR_WORDS * 4);
-    put(p.seq_ref, (size_t)n_seqs * 4);
+    put(p.seq_ref, (size_t)n_seqs * 12); /* a pair's reference, its span's first column, its span's columns */
     put(p.order, (size_t)n_seqs * 4);
     put(p.gref, (size_t)std::max(p.wgs0, p.wgs1) * CW_SW_WAVES * CW_SW_GREF_BYTES);
     put(p.lstate, (size_t)p.wgs_long * CW_SW_LONG_WAVE_BYTES);

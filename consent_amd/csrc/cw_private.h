@@ -53,7 +53,7 @@ int cw_debug_poa_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int 
    and sweep state, [4] banded-traceback directions (0 without CW_SW_WANT_INDELS), [5] [6] [7] work-groups of the class-0, class-1 and long launches, [8] waves
    that have direction scratch, [9] its bytes per wave.  CW_E_INVALID for flags cw_sw_run refuses. */
 int cw_debug_sw_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, int cus, uint32_t flags, uint64_t* out10);
-/* The scratch plan of a path run (cw_sw_path_run) likewise: out[0] total bytes, [1] counters + reference index + place in the order, [2] unpacked long references,
+/* The scratch plan of a path run (cw_sw_path_run) likewise: out[0] total bytes, [1] counters + reference index, span begin and span length + place in the order, [2] unpacked long references,
    [3] the long launch's state, [4] the traceback's scratch (directions, and rows beyond LDS), [5] the walks' step buffers, [6] [7] [8] work-groups of the class-0,
    class-1 and long launches, [9] waves that have traceback scratch, [10] its bytes per wave, [11] a step buffer's bytes.  CW_E_INVALID for flags other than
    CW_SW_PATH_EQX. */

@@ -18,6 +18,8 @@
  *                largest w, then the lowest b -- and lane 0 stores STATUS, HITS, DIAG = (b << 6) - m, OTHER with plain stores: reverse only when its best w is
  *                the larger.
  *
+ * cw_seed_spans_kernel (cw_seed_spans / cw_seed_spans_device) turns the rows into the reference spans the aligner's span runs take: one thread a sequence.
+ *
  * LDS.  WIDE = 0 (references of up to CW_ST_RMAX = 2 048 bases): 16 KB table + 512 B words + 4 waves x 2 x 273 words of histogram (B <= 545 bins and the
  * zero bin behind them) = 25 632 B static, 256 threads, six work-groups a CU.  WIDE = 1 (up to CW_SW_RMAX): 128 KB table + 4 KB words + 8 waves x 2 x 385
  * words (B <= 768) = 159 808 B dynamic, 512 threads, one work-group a CU.
@@ -76,6 +78,36 @@ __device__ __forceinline__ uint32_t seed_find(const uint32_t* tab, const uint32_
 
 __device__ __forceinline__ void seed_count(uint32_t* hist, uint32_t bin) { atomicAdd(&hist[bin >> 1], 1u << (16u * (bin & 1u))); }
 __device__ __forceinline__ uint32_t seed_bin(const uint32_t* hist, uint32_t bin) { return (hist[bin >> 1] >> (16u * (bin & 1u))) & 0xFFFFu; }
+
+/* cw_seed_spans_device: the reference columns a placed query can reach, for the span runs of the aligner (cw_sw_span_run and its kin).  One thread per sequence,
+   its group by bisection as the order kernel finds it; 64-bit signed arithmetic, so no DIAG, pad or shift overflows.  A row that places nothing -- a reference's
+   own, CW_STRAND_NONE, fewer than min_hits -- gives the empty span (0, 0). */
+struct SeedSpanArgs {
+    DevBatch b;
+    uint32_t n_seqs;
+    const int32_t* rows;      /* [n_seqs * CW_SEED_ROW], a seed run's */
+    uint32_t min_hits, pad, pad_shift;
+    uint32_t* ref_lo;         /* [n_seqs] */
+    uint32_t* ref_hi;
+};
+
+__global__ void __launch_bounds__(256) cw_seed_spans_kernel(SeedSpanArgs a) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= a.n_seqs) return;
+    uint32_t lo = 0, hi = a.b.n_windows; /* win_first_seq[lo] <= s < win_first_seq[hi] */
+    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (a.b.win_first_seq[mid] <= s) lo = mid; else hi = mid; }
+    const int32_t* const row = a.rows + (size_t)s * CW_SEED_ROW;
+    const int64_t n = (int64_t)a.b.seq_len[a.b.win_first_seq[lo]], m = (int64_t)a.b.seq_len[s];
+    const int32_t status = row[CW_SEED_STATUS];
+    int64_t c0 = 0, c1 = 0;
+    if ((status == CW_STRAND_FWD || status == CW_STRAND_REV) && (int64_t)row[CW_SEED_HITS] >= (int64_t)a.min_hits) {
+        const int64_t P = (int64_t)a.pad + (m >> a.pad_shift), d = (int64_t)row[CW_SEED_DIAG];
+        c0 = d - P; c1 = d + (int64_t)(2u << CW_SEED_SHIFT) + m + P;
+        c0 = c0 < 0 ? 0 : c0 > n ? n : c0;
+        c1 = c1 < 0 ? 0 : c1 > n ? n : c1;
+    }
+    a.ref_lo[s] = (uint32_t)c0; a.ref_hi[s] = (uint32_t)c1;
+}
 
 template <int WIDE>
 __global__ void __launch_bounds__(WIDE ? CW_SEED_THREADS_WIDE : CW_STR_THREADS) cw_seed_kernel(SeedArgs a) {

@@ -79,16 +79,16 @@ __device__ __forceinline__ void cut_mark(const uint8_t* steps, uint32_t n, uint3
 }
 
 /* one pair on one wave, its buffers in place, as sw_path_pair: align, the banded pass, the walk -- then the cut points in place of the ops -- the row */
-template <int CLS>
+template <int CLS, bool SPAN>
 __device__ __forceinline__ void cut_pair(const CutArgs& ca, uint32_t s, uint8_t* refc, uint8_t* qfw, uint8_t* qrv, uint32_t qrv_bytes, bool qrv_lds, uint8_t* rows, uint8_t* dirbuf, uint8_t* steps,
                                          uint8_t* state, int lane) {
     const SwArgs& a = ca.a;
     const uint32_t r = st_uni(a.seq_ref[s]);
     const uint32_t m = st_uni(a.b.seq_len[s]), n = st_uni(a.b.seq_len[r]);
-    sw_unpack(refc, a.b.bases + a.b.seq_word_off[r], n, lane);
+    const uint32_t sn = sw_unpack_ref<SPAN>(a, refc, s, r, n, lane);
     sw_unpack(qfw, a.b.bases + a.b.seq_word_off[s], m, lane);
     st_mem_sync();
-    const StAlign al = sw_align<CLS>(qfw, (int)m, qrv, refc, (int)n, lane, state);
+    const StAlign al = sw_align<CLS>(qfw, (int)m, qrv, refc, (int)sn, lane, state); /* in the span's coordinates, as everything up to the walk */
     uint32_t ins = 0, del = 0;
     int status = CW_SW_ALIGNED;
     const uint32_t T = cut_windows(n, ca.window);
@@ -104,28 +104,35 @@ __device__ __forceinline__ void cut_pair(const CutArgs& ca, uint32_t s, uint8_t*
             const SwWalk w = sw_walk(bd, refLen, readLen, steps, lane);
             ins = w.ins; del = w.del;
             if (!w.closed) status = CW_SW_PATH_OPEN;
-            else if (!holds || al.ref_begin < 0 || al.query_begin < 0 || (uint32_t)al.ref_begin + (uint32_t)refLen > n) status = CW_SW_CUT_SLOT; /* (the ends lie inside the reference) */
             else {
-                cut_mark(steps, w.n_steps, (uint32_t)al.ref_begin, (uint32_t)al.ref_end, (uint32_t)al.query_begin, (uint32_t)al.query_end, ca.window, T, slot, lane);
-                marked = true;
+                const SwSpan sl{st_uni(sw_pair_lo<SPAN>(a, s)), st_uni(sw_pair_len<SPAN>(a, s, n))};
+                if (!holds || al.ref_begin < 0 || al.query_begin < 0 || (uint32_t)al.ref_begin + (uint32_t)refLen > sl.len) status = CW_SW_CUT_SLOT; /* (the ends lie inside the span, the span inside the reference) */
+                else { /* the boundaries are the whole reference's: absolute ends */
+                    cut_mark(steps, w.n_steps, sl.lo + (uint32_t)al.ref_begin, sl.lo + (uint32_t)al.ref_end, (uint32_t)al.query_begin, (uint32_t)al.query_end, ca.window, T, slot, lane);
+                    marked = true;
+                }
             }
         }
     }
     if (!marked && holds && status != CW_SW_CUT_SLOT) cut_zero(slot, T, lane); /* a pair that does not count */
-    if (lane == 0) sw_write_row(a.rows + (size_t)s * CW_SW_ROW, al.score, al.ref_begin, al.ref_end, al.query_begin, al.query_end, ins, del, status);
+    if (lane == 0) {
+        const int lo = al.score > 0 ? (int)sw_pair_lo<SPAN>(a, s) : 0; /* the row is absolute */
+        sw_write_row(a.rows + (size_t)s * CW_SW_ROW, al.score, al.ref_begin + lo, al.ref_end + lo, al.query_begin, al.query_end, ins, del, status);
+    }
     st_mem_sync(); /* the next pair's unpacking overwrites what this one read */
 }
 
-template <int CLS>
+template <int CLS, bool SPAN>
 __global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_sw_cut_kernel(CutArgs ca) {
-    sw_class_loop<CLS, true>(ca.a, ca.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
-        cut_pair<CLS>(ca, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+    sw_class_loop<CLS, true, SPAN>(ca.a, ca.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        cut_pair<CLS, SPAN>(ca, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
     });
 }
 
+template <bool SPAN>
 __global__ void __launch_bounds__(64, 2) cw_sw_cut_long_kernel(CutArgs ca) {
     sw_long_loop<true>(ca.a, ca.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
-        cut_pair<2>(ca, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+        cut_pair<2, SPAN>(ca, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
     });
 }
 

@@ -20,6 +20,9 @@
  * The path, pileup and cut runs (cw_sw_path.h, cw_pileup.h, cw_sw_cut.h) launch kernels of their own names in the same three classes.  What the four runs'
  * kernels share lives here, once: sw_class_loop<CLS> and sw_long_loop carve a wave's buffers (SwWaveBufs) and claim the pairs; every kernel is a call of one
  * of the two with what it does per pair.
+ *
+ * Every alignment kernel has two instances, SPAN = false and SPAN = true (cw_sw_span_run and its kin: a query confined to a span of its reference's columns;
+ * SwSpan below).  The first is the kernel as it always was.
  */
 #ifndef CW_SW_OP_H
 #define CW_SW_OP_H
@@ -52,13 +55,34 @@ struct SwArgs {
     int32_t* rows;       /* the caller's [n_seqs * CW_SW_ROW] */
     uint32_t flags;
     uint32_t* ctr;       /* CW_SW_CTR_WORDS, zero before phase 0 */
-    uint32_t* seq_ref;   /* [n_seqs] a pair's reference sequence (phase 0) */
+    uint32_t* seq_ref;   /* [3 n_seqs] a pair's reference sequence (phase 0); a span run: behind those its span's first column, behind those its span's columns */
     uint32_t* order;     /* [n_seqs] the pairs: class 0's, then class 1's, then class 2's, each costliest first (phase 2) */
     int8_t* dir;         /* dir_bytes per wave of the largest grid; NULL without CW_SW_WANT_INDELS */
     uint32_t dir_bytes;
     uint8_t* gref;       /* CW_SW_GREF_BYTES per wave of cw_sw_kernel's largest grid */
     uint8_t* lstate;     /* CW_SW_LONG_WAVE_BYTES per work-group of cw_sw_long_kernel */
+    const uint32_t* ref_lo; /* [n_seqs] the span runs (cw_sw_span_run and its kin): the reference columns [ref_lo[s], ref_hi[s]) query s may use, clamped */
+    const uint32_t* ref_hi; /*          to the reference; both NULL for the runs without spans: every column.  Only the order kernel reads them */
 };
+
+/* A pair's span: its first reference column and its columns.  (0, n) without spans; len = 0 when the clamped span is empty.  Everything between the unpacking
+   and the row is in span-relative coordinates: the unpacked reference begins at lo.  In a span run the order kernel works a span out once (sw_span_of) and
+   leaves it behind the pair's reference in seq_ref[]; the alignment kernels read it there (sw_pair_lo, sw_pair_len) where they need it and keep nothing of it
+   in a register across the sweeps: with the caller's two pointers and a recomputation in the pair, the 128-register kernels spilled scalar registers
+   (DESIGN.md 4.8 has the table).  A run without spans touches none of this: its kernels are the SPAN = false instances, compiled to the code they always
+   were; a span run launches the SPAN = true instances of the same functions.  (One set of kernels for both, with a wave-uniform test a pair, leaves the runs
+   without spans with more scalar registers and spills and a path run 3 to 6 % slower at short queries: DESIGN.md 4.8 has the measurements.) */
+struct SwSpan { uint32_t lo, len; };
+__device__ __forceinline__ SwSpan sw_span_of(const SwArgs& a, uint32_t s, uint32_t n) {
+    if (!a.ref_lo) return SwSpan{0u, n};
+    const uint32_t lo = min(a.ref_lo[s], n), hi = min(a.ref_hi[s], n);
+    return SwSpan{lo, hi > lo ? hi - lo : 0u};
+}
+/* a pair's span as the order kernel left it; n: its reference's length */
+template <bool SPAN>
+__device__ __forceinline__ uint32_t sw_pair_lo(const SwArgs& a, uint32_t s) { if constexpr (SPAN) return a.seq_ref[(size_t)a.n_seqs + s]; else return 0u; }
+template <bool SPAN>
+__device__ __forceinline__ uint32_t sw_pair_len(const SwArgs& a, uint32_t s, uint32_t n) { if constexpr (SPAN) return a.seq_ref[2u * (size_t)a.n_seqs + s]; else return n; }
 
 __device__ __forceinline__ uint32_t sw_launch_class(uint32_t m) { return m <= (uint32_t)CW_SW_Q0 ? 0u : m <= (uint32_t)CW_ST_QMAX ? 1u : 2u; }
 /* cost class of a pair of m x n cells, both > 0: 4 x floor(log2) + the next two bits -- monotone in the cost */
@@ -101,16 +125,20 @@ __global__ void __launch_bounds__(256) cw_sw_order_kernel(SwArgs a, int phase) {
         int32_t* row = a.rows + (size_t)s * CW_SW_ROW;
         a.seq_ref[s] = 0xFFFFFFFFu;
         if (s == r) { sw_write_row(row, 0, 0, -1, 0, -1, 0, 0, CW_SW_IS_REF); return; }
-        if (m > (uint32_t)CW_SW_QMAX || n > (uint32_t)CW_SW_RMAX) { sw_write_row(row, 0, 0, -1, 0, -1, 0, 0, CW_SW_STOP); return; }
-        if (m == 0u || n == 0u) { sw_write_row(row, 0, 0, -1, 0, -1, 0, 0, CW_SW_ALIGNED); return; }
+        /* the sweep's capacity is the span's: a span run takes a reference of any length that a row's 32 bits hold */
+        const SwSpan sp = sw_span_of(a, s, n);
+        const uint32_t sn = sp.len;
+        if (m > (uint32_t)CW_SW_QMAX || sn > (uint32_t)CW_SW_RMAX || n > 0x7FFFFFFFu) { sw_write_row(row, 0, 0, -1, 0, -1, 0, 0, CW_SW_STOP); return; }
+        if (m == 0u || sn == 0u) { sw_write_row(row, 0, 0, -1, 0, -1, 0, 0, CW_SW_ALIGNED); return; }
         a.seq_ref[s] = r;
-        atomicAdd(&cls_ctr[sw_launch_class(m) * CW_SW_COST_CLASSES + sw_cost_class(m, n)], 1u);
+        if (a.ref_lo) { a.seq_ref[(size_t)a.n_seqs + s] = sp.lo; a.seq_ref[2u * (size_t)a.n_seqs + s] = sn; }
+        atomicAdd(&cls_ctr[sw_launch_class(m) * CW_SW_COST_CLASSES + sw_cost_class(m, sn)], 1u);
         return;
     }
     const uint32_t r = a.seq_ref[s];
     if (r == 0xFFFFFFFFu) return;
-    const uint32_t m = a.b.seq_len[s], n = a.b.seq_len[r];
-    a.order[atomicAdd(&cls_ctr[sw_launch_class(m) * CW_SW_COST_CLASSES + sw_cost_class(m, n)], 1u)] = s;
+    const uint32_t m = a.b.seq_len[s], sn = a.ref_lo ? a.seq_ref[2u * (size_t)a.n_seqs + s] : a.b.seq_len[r];
+    a.order[atomicAdd(&cls_ctr[sw_launch_class(m) * CW_SW_COST_CLASSES + sw_cost_class(m, sn)], 1u)] = s;
 }
 
 /* 2-bit words to one code a byte, a word of 16 bases per lane and step; writes whole words: dst holds len rounded up to 16 */
@@ -125,6 +153,36 @@ __device__ __forceinline__ void sw_unpack(uint8_t* dst, const uint32_t* words, u
             d[k] = ((by >> 6) & 3u) | (((by >> 4) & 3u) << 8) | (((by >> 2) & 3u) << 16) | ((by & 3u) << 24);
         }
     }
+}
+
+/* The same from a base that need not begin a word: codes first_base .. first_base + len - 1 of a sequence to dst[0 ..), 16 a lane and step, every output
+   word a funnel shift over two neighbouring packed words.  The second of them is loaded only where one of the len codes lies in it -- so it is a word of the
+   sequence: nothing beyond the sequence's last word, which may be the batch's last, is ever read.  Writes whole words as sw_unpack does; what lies in dst
+   beyond len are the sequence's next bases or zeros, not padding a reader may rely on.  first_base % 16 == 0: the words sw_unpack reads, code for code. */
+__device__ __forceinline__ void sw_unpack_from(uint8_t* dst, const uint32_t* words, uint32_t first_base, uint32_t len, int lane) {
+    const uint32_t nw = (len + 15u) >> 4, sh = (first_base & 15u) * 2u;
+    const uint32_t* const src = words + (first_base >> 4);
+    const uint32_t reach = len + (first_base & 15u); /* the codes wanted end at bit pair `reach` of src[] */
+    for (uint32_t w = (uint32_t)lane; w < nw; w += 64u) {
+        uint32_t x = src[w]; /* (16 w < len: its first code is wanted) */
+        if (sh) x = (x << sh) | ((16u * (w + 1u) < reach ? src[w + 1u] : 0u) >> (32u - sh));
+        uint32_t* d = (uint32_t*)(dst + 16u * w);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t by = (x >> (24 - 8 * k)) & 0xFFu;
+            d[k] = ((by >> 6) & 3u) | (((by >> 4) & 3u) << 8) | (((by >> 2) & 3u) << 16) | ((by & 3u) << 24);
+        }
+    }
+}
+
+/* a pair's reference columns to refc, and their number: the whole reference by sw_unpack as ever, or in a span run its span */
+template <bool SPAN>
+__device__ __forceinline__ uint32_t sw_unpack_ref(const SwArgs& a, uint8_t* refc, uint32_t s, uint32_t r, uint32_t n, int lane) {
+    const uint32_t* const words = a.b.bases + a.b.seq_word_off[r];
+    if constexpr (!SPAN) { sw_unpack(refc, words, n, lane); return n; }
+    const uint32_t sn = st_uni(sw_pair_len<true>(a, s, n));
+    sw_unpack_from(refc, words, st_uni(sw_pair_lo<true>(a, s)), sn, lane);
+    return sn;
 }
 
 /* the sweeps of a launch class: class 0 is st_sweep_any's ladder up to its five-register instance (what a 128-register kernel holds), class 1 the whole
@@ -166,14 +224,14 @@ __device__ __forceinline__ StAlign sw_align(const uint8_t* qfw, int m, uint8_t* 
 }
 
 /* one pair on one wave, its buffers in place: align, the indel totals when asked for, the row */
-template <int CLS>
+template <int CLS, bool SPAN>
 __device__ __forceinline__ void sw_pair(const SwArgs& a, uint32_t s, uint8_t* refc, uint8_t* qfw, uint8_t* qrv, uint32_t qrv_bytes, bool qrv_lds, uint8_t* rows, int8_t* dirbuf, uint8_t* state, int lane) {
     const uint32_t r = st_uni(a.seq_ref[s]);
     const uint32_t m = st_uni(a.b.seq_len[s]), n = st_uni(a.b.seq_len[r]);
-    sw_unpack(refc, a.b.bases + a.b.seq_word_off[r], n, lane);
+    const uint32_t sn = sw_unpack_ref<SPAN>(a, refc, s, r, n, lane);
     sw_unpack(qfw, a.b.bases + a.b.seq_word_off[s], m, lane);
     st_mem_sync();
-    const StAlign al = sw_align<CLS>(qfw, (int)m, qrv, refc, (int)n, lane, state);
+    const StAlign al = sw_align<CLS>(qfw, (int)m, qrv, refc, (int)sn, lane, state); /* in the span's coordinates, as everything up to the row */
     unsigned ins = 0, del = 0;
     int status = CW_SW_ALIGNED;
     if ((a.flags & CW_SW_WANT_INDELS) && al.score > 0) {
@@ -183,7 +241,10 @@ __device__ __forceinline__ void sw_pair(const SwArgs& a, uint32_t s, uint8_t* re
             ins = 0; del = 0; status = CW_SW_NO_INDELS;
         }
     }
-    if (lane == 0) sw_write_row(a.rows + (size_t)s * CW_SW_ROW, al.score, al.ref_begin, al.ref_end, al.query_begin, al.query_end, ins, del, status);
+    if (lane == 0) {
+        const int lo = al.score > 0 ? (int)sw_pair_lo<SPAN>(a, s) : 0; /* the row is absolute */
+        sw_write_row(a.rows + (size_t)s * CW_SW_ROW, al.score, al.ref_begin + lo, al.ref_end + lo, al.query_begin, al.query_end, ins, del, status);
+    }
     st_mem_sync(); /* the next pair's unpacking overwrites what the traceback's lane 0 read */
 }
 
@@ -206,7 +267,7 @@ struct SwWaveBufs {
    reference there too up to CW_ST_RMAX bases and in the wave's global scratch beyond.  TRACED: a run with a walk (cw_sw_path.h), which has step scratch at
    steps_base and always has direction scratch; the plain run passes NULL.  per_pair(s, bufs, lane) does one pair (the kernels' lambdas are always_inline, as every device function
    here is: a kernel is one function before the optimiser sees it). */
-template <int CLS, bool TRACED, class F>
+template <int CLS, bool TRACED, bool SPAN, class F>
 __device__ __forceinline__ void sw_class_loop(const SwArgs& a, uint8_t* steps_base, F per_pair) {
     constexpr int QMAX = CLS == 0 ? CW_SW_Q0 : CW_ST_QMAX;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -229,8 +290,8 @@ __device__ __forceinline__ void sw_class_loop(const SwArgs& a, uint8_t* steps_ba
         pi = (uint32_t)cw_lane_value((int)pi, 0);
         if (pi >= n_pairs) break;
         const uint32_t s = st_uni(a.order[base + pi]);
-        const uint32_t n = st_uni(a.b.seq_len[st_uni(a.seq_ref[s])]);
-        w.refc = n <= (uint32_t)CW_ST_RMAX ? w.ref_lds : w.ref_glb;
+        const uint32_t sn = st_uni(sw_pair_len<SPAN>(a, s, a.b.seq_len[st_uni(a.seq_ref[s])]));
+        w.refc = sn <= (uint32_t)CW_ST_RMAX ? w.ref_lds : w.ref_glb;
         per_pair(s, w, lane);
     }
 }
@@ -265,18 +326,19 @@ __device__ __forceinline__ void sw_long_loop(const SwArgs& a, uint8_t* steps_bas
 
 /* CLS 0: 128 registers (the five-register sweep is its widest: four waves a SIMD, and the LDS of four work-groups a CU); CLS 1: whatever the sixteen-register
    sweep takes (one wave a SIMD, as cw_stitch_kernel's wide instance).  The path, pileup and cut kernels keep these launch bounds. */
-template <int CLS>
+template <int CLS, bool SPAN>
 __global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_sw_kernel(SwArgs a) {
-    sw_class_loop<CLS, false>(a, nullptr, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
-        sw_pair<CLS>(a, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, (int8_t*)w.dirbuf, w.state, lane);
+    sw_class_loop<CLS, false, SPAN>(a, nullptr, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        sw_pair<CLS, SPAN>(a, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, (int8_t*)w.dirbuf, w.state, lane);
     });
 }
 
 /* (compiled for 256 registers, two waves a SIMD: at the last launch's 128 of cw_stitch_kernel the memory-state sweep spills 90 registers into its column loop --
    there a launch that normally finds nothing to do, here the path of every long query) */
+template <bool SPAN>
 __global__ void __launch_bounds__(64, 2) cw_sw_long_kernel(SwArgs a) {
     sw_long_loop<false>(a, nullptr, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
-        sw_pair<2>(a, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, (int8_t*)w.dirbuf, w.state, lane);
+        sw_pair<2, SPAN>(a, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, (int8_t*)w.dirbuf, w.state, lane);
     });
 }
 

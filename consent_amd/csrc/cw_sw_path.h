@@ -174,16 +174,16 @@ __device__ __forceinline__ uint32_t sw_emit(const uint8_t* steps, uint32_t n, bo
 }
 
 /* one pair on one wave, its buffers in place: align, the banded pass, the walk, the ops, the row */
-template <int CLS>
+template <int CLS, bool SPAN>
 __device__ __forceinline__ void sw_path_pair(const SwPathArgs& pa, uint32_t s, uint8_t* refc, uint8_t* qfw, uint8_t* qrv, uint32_t qrv_bytes, bool qrv_lds, uint8_t* rows, uint8_t* dirbuf, uint8_t* steps,
                                              uint8_t* state, int lane) {
     const SwArgs& a = pa.a;
     const uint32_t r = st_uni(a.seq_ref[s]);
     const uint32_t m = st_uni(a.b.seq_len[s]), n = st_uni(a.b.seq_len[r]);
-    sw_unpack(refc, a.b.bases + a.b.seq_word_off[r], n, lane);
+    const uint32_t sn = sw_unpack_ref<SPAN>(a, refc, s, r, n, lane);
     sw_unpack(qfw, a.b.bases + a.b.seq_word_off[s], m, lane);
     st_mem_sync();
-    const StAlign al = sw_align<CLS>(qfw, (int)m, qrv, refc, (int)n, lane, state);
+    const StAlign al = sw_align<CLS>(qfw, (int)m, qrv, refc, (int)sn, lane, state); /* in the span's coordinates, as everything up to the walk */
     uint32_t ins = 0, del = 0, n_ops = 0;
     int status = CW_SW_ALIGNED;
     if (al.score > 0) {
@@ -205,23 +205,25 @@ __device__ __forceinline__ void sw_path_pair(const SwPathArgs& pa, uint32_t s, u
         }
     }
     if (lane == 0) {
-        sw_write_row(a.rows + (size_t)s * CW_SW_ROW, al.score, al.ref_begin, al.ref_end, al.query_begin, al.query_end, ins, del, status);
+        const int lo = al.score > 0 ? (int)sw_pair_lo<SPAN>(a, s) : 0; /* the row is absolute */
+        sw_write_row(a.rows + (size_t)s * CW_SW_ROW, al.score, al.ref_begin + lo, al.ref_end + lo, al.query_begin, al.query_end, ins, del, status);
         pa.n_ops[s] = n_ops;
     }
     st_mem_sync(); /* the next pair's unpacking overwrites what this one read */
 }
 
 /* the launch bounds and LDS slabs of cw_sw_kernel<CLS> */
-template <int CLS>
+template <int CLS, bool SPAN>
 __global__ void __launch_bounds__(64 * CW_SW_WAVES, CLS == 0 ? 4 : 1) cw_sw_path_kernel(SwPathArgs pa) {
-    sw_class_loop<CLS, true>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
-        sw_path_pair<CLS>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+    sw_class_loop<CLS, true, SPAN>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
+        sw_path_pair<CLS, SPAN>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
     });
 }
 
+template <bool SPAN>
 __global__ void __launch_bounds__(64, 2) cw_sw_path_long_kernel(SwPathArgs pa) {
     sw_long_loop<true>(pa.a, pa.steps, [&](uint32_t s, const SwWaveBufs& w, int lane) __attribute__((always_inline)) {
-        sw_path_pair<2>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
+        sw_path_pair<2, SPAN>(pa, s, w.refc, w.qfw, w.qrv, w.qrv_bytes, w.qrv_lds, w.rows, w.dirbuf, w.steps, w.state, lane);
     });
 }
 

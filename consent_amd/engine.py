@@ -34,6 +34,9 @@ SEED_STATUS, SEED_HITS, SEED_DIAG, SEED_OTHER, SEED_ROW = 0, 1, 2, 3, 4
 SEED_SHIFT = 6
 SEED_SPAN = 2 << SEED_SHIFT
 SEED_MIN_HITS, SEED_MIN_K = 14, 11  # (the threshold holds from this k up)
+# cw_seed_spans: a placed query's span is its window's diagonals over the whole query, widened by SPAN_PAD + (query length >> SPAN_PAD_SHIFT) on either side;
+# the shift is measured (tests/test_sw_span_cpu.py)
+SPAN_PAD, SPAN_PAD_SHIFT = 64, 4
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -98,6 +101,12 @@ class Seeds(C.Structure):
     """cw_seeds: the outputs of cw_seed_run (strand may be NULL) and k (0 = STRAND_K)."""
 
     _fields_ = [("rows", C.c_void_p), ("strand", C.c_void_p), ("k", C.c_uint32)]
+
+
+class SwSpans(C.Structure):
+    """cw_sw_spans: per sequence the reference columns [ref_lo, ref_hi) a query may use (the span runs)."""
+
+    _fields_ = [("ref_lo", C.c_void_p), ("ref_hi", C.c_void_p)]
 
 
 class Result(C.Structure):
@@ -220,6 +229,17 @@ def _load(p):
         lib.cw_seed_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Seeds)]
         lib.cw_seed_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Seeds), C.c_void_p]
         lib.cw_debug_seed_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
+    if hasattr(lib, "cw_sw_span_run"):
+        lib.cw_sw_span_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwSpans), C.c_uint32]
+        lib.cw_sw_span_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwSpans), C.c_uint32, C.c_void_p]
+        lib.cw_sw_path_span_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwPaths), C.POINTER(SwSpans), C.c_uint32]
+        lib.cw_sw_path_span_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwPaths), C.POINTER(SwSpans), C.c_uint32, C.c_void_p]
+        lib.cw_pileup_span_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(Pileup), C.POINTER(SwSpans), C.c_uint32]
+        lib.cw_pileup_span_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(Pileup), C.POINTER(SwSpans), C.c_uint32, C.c_void_p]
+        lib.cw_sw_cut_span_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwCuts), C.POINTER(SwSpans)]
+        lib.cw_sw_cut_span_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwCuts), C.POINTER(SwSpans), C.c_void_p]
+        lib.cw_seed_spans.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.cw_seed_spans_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cw_submit.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.POINTER(C.c_int)]
     lib.cw_wait.argtypes = [C.c_void_p, C.c_int]
     lib.cw_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -785,6 +805,32 @@ def _revcomp(s):
     return s.translate(_COMPLEMENT)[::-1]
 
 
+def span_arrays(spans, n_seqs):
+    """`spans` as the two uint32 arrays of cw_sw_spans: a pair of per-sequence arrays (lo, hi), or one (n_seqs, 2) array.  Values are clipped to 32 bits; a
+    negative one is 0."""
+    pair = isinstance(spans, (tuple, list)) and len(spans) == 2  # (two sequences: a tuple or list of two is the pair, an array the (n_seqs, 2) form)
+    a = np.asarray(spans, dtype=np.int64)
+    if a.shape == (n_seqs, 2) and not (pair and np.ndim(spans[0]) == 1):
+        a = a.T
+    if a.shape != (2, n_seqs):
+        raise EngineError(f"spans: a pair of arrays of {n_seqs} values, or one of shape ({n_seqs}, 2)")
+    a = np.clip(a, 0, 0xFFFFFFFF).astype(np.uint32)
+    return np.ascontiguousarray(a[0]), np.ascontiguousarray(a[1])
+
+
+def seed_spans_rule(seq_len, ref_len, seed_rows, min_hits=SEED_MIN_HITS, pad=SPAN_PAD, pad_shift=SPAN_PAD_SHIFT):
+    """cw_seed_spans' rule on the host (numpy, 64-bit): per sequence of length seq_len on a reference of ref_len, with its seed row (STATUS, HITS, DIAG, ..),
+    (lo, hi) = (clamp(DIAG - P, 0, n), clamp(DIAG + SEED_SPAN + m + P, 0, n)), P = pad + (m >> pad_shift), where the row is FWD / REV with HITS >= min_hits;
+    (0, 0) elsewhere."""
+    m, n = np.asarray(seq_len, np.int64), np.asarray(ref_len, np.int64)
+    rows = np.asarray(seed_rows, np.int64).reshape(-1, SEED_ROW)
+    placed = (rows[:, SEED_STATUS] <= STRAND_REV) & (rows[:, SEED_STATUS] >= STRAND_FWD) & (rows[:, SEED_HITS] >= int(min_hits))
+    P = int(pad) + (m >> int(pad_shift))
+    lo = np.clip(rows[:, SEED_DIAG] - P, 0, n)
+    hi = np.clip(rows[:, SEED_DIAG] + SEED_SPAN + m + P, 0, n)
+    return np.where(placed, lo, 0).astype(np.uint32), np.where(placed, hi, 0).astype(np.uint32)
+
+
 def _result_struct(r):
     return Result(
         _ptr(r.cons), _ptr(r.cons_off), _ptr(r.cons_len), _ptr(r.status),
@@ -854,23 +900,36 @@ class Engine:
         """cw_poa_run_device: as run_device, device pointers in both structs (the result's solid fields NULL), asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_poa_run_device(self.handle, C.byref(batch_struct), C.byref(result_struct), stream), "cw_poa_run_device")
 
-    def sw(self, groups, want_indels=False):
+    def sw(self, groups, want_indels=False, spans=None):
         """Only the local alignment (cw_sw_run): `groups` is a list of lists of ACGT strings (or a HostBatch of them); every group's first sequence is its
         reference, every other one a query aligned locally against it.  Returns SwRows: .rows is (n_seqs, SW_ROW) int32 -- score, ref_begin, ref_end,
         query_begin, query_end (inclusive, 0-based; ends -1 when nothing aligns), ins, del (0 unless want_indels), status (SW_ALIGNED, SW_NO_INDELS, SW_STOP
         for a pair beyond SW_QMAX / SW_RMAX, SW_IS_REF for the reference's own row) -- and .row(group, member) finds a row; .rc is cw_sw_run's return value
-        (0, or -4 when a pair stopped)."""
+        (0, or -4 when a pair stopped).
+        spans (here and in sw_path(), pileup(), sw_cut()): a pair of per-sequence arrays (lo, hi), or one (n_seqs, 2) array -- query s is aligned against
+        reference columns [lo[s], hi[s]) only (cw_sw_span_run and its kin): the result of the run on reference[lo:hi] in the whole reference's coordinates,
+        an empty span the row of an empty reference; SW_STOP then for a span, not a reference, of more than SW_RMAX columns.  None: every column, as ever."""
         batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
         rows = np.zeros((len(batch.seq_len), SW_ROW), np.int32)
         b = batch.c_struct()
-        rc = _check(self.lib, self.lib.cw_sw_run(self.handle, C.byref(b), _ptr(rows), SW_WANT_INDELS if want_indels else 0), "cw_sw_run", allow_capacity=True)
+        flags = SW_WANT_INDELS if want_indels else 0
+        if spans is None:
+            rc = _check(self.lib, self.lib.cw_sw_run(self.handle, C.byref(b), _ptr(rows), flags), "cw_sw_run", allow_capacity=True)
+        else:
+            lo, hi = span_arrays(spans, len(batch.seq_len))
+            sp = SwSpans(_ptr(lo), _ptr(hi))
+            rc = _check(self.lib, self.lib.cw_sw_span_run(self.handle, C.byref(b), _ptr(rows), C.byref(sp), flags), "cw_sw_span_run", allow_capacity=True)
         return SwRows(rows, batch.win_first_seq, rc)
 
     def sw_device(self, batch_struct, rows_ptr, flags=0, stream=None):
         """cw_sw_run_device: device pointers in the batch struct, `rows_ptr` a device array of n_seqs * SW_ROW int32; asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_sw_run_device(self.handle, C.byref(batch_struct), rows_ptr, flags, stream), "cw_sw_run_device")
 
-    def sw_path(self, groups, eqx=False, slot_ops=None):
+    def sw_span_device(self, batch_struct, rows_ptr, spans_struct, flags=0, stream=None):
+        """cw_sw_span_run_device: sw_device() with `spans_struct` (SwSpans, device arrays of n_seqs uint32 each)."""
+        _check(self.lib, self.lib.cw_sw_span_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(spans_struct), flags, stream), "cw_sw_span_run_device")
+
+    def sw_path(self, groups, eqx=False, slot_ops=None, spans=None):
         """The local alignment with its path (cw_sw_path_run): `groups` as for sw().  Returns SwPathRows: the rows of sw() with ins / del always filled in,
         .n_ops, .ops(group, member) and .cigar(group, member).  Statuses beyond sw()'s: SW_NO_PATH (the traceback's directions outgrow a wave's scratch),
         SW_PATH_OPEN, SW_PATH_SLOT (the ops outgrow the slot: n_ops is the number needed).  slot_ops: ops a sequence's slot holds, one number or one per
@@ -889,7 +948,13 @@ class Engine:
         rows = np.zeros((S, SW_ROW), np.int32)
         b = batch.c_struct()
         paths = SwPaths(_ptr(ops_buf), _ptr(ops_off), _ptr(n_ops))
-        rc = _check(self.lib, self.lib.cw_sw_path_run(self.handle, C.byref(b), _ptr(rows), C.byref(paths), SW_PATH_EQX if eqx else 0), "cw_sw_path_run", allow_capacity=True)
+        if spans is None:
+            rc = _check(self.lib, self.lib.cw_sw_path_run(self.handle, C.byref(b), _ptr(rows), C.byref(paths), SW_PATH_EQX if eqx else 0), "cw_sw_path_run", allow_capacity=True)
+        else:
+            lo, hi = span_arrays(spans, S)
+            sp = SwSpans(_ptr(lo), _ptr(hi))
+            rc = _check(self.lib, self.lib.cw_sw_path_span_run(self.handle, C.byref(b), _ptr(rows), C.byref(paths), C.byref(sp), SW_PATH_EQX if eqx else 0), "cw_sw_path_span_run",
+                        allow_capacity=True)
         return SwPathRows(rows, batch.win_first_seq, rc, n_ops[:S], ops_buf, ops_off)
 
     def sw_path_device(self, batch_struct, rows_ptr, paths_struct, flags=0, stream=None):
@@ -897,7 +962,12 @@ class Engine:
         asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_sw_path_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(paths_struct), flags, stream), "cw_sw_path_run_device")
 
-    def pileup(self, groups, into=None):
+    def sw_path_span_device(self, batch_struct, rows_ptr, paths_struct, spans_struct, flags=0, stream=None):
+        """cw_sw_path_span_run_device: sw_path_device() with `spans_struct` (SwSpans, device arrays)."""
+        _check(self.lib, self.lib.cw_sw_path_span_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(paths_struct), C.byref(spans_struct), flags, stream),
+               "cw_sw_path_span_run_device")
+
+    def pileup(self, groups, into=None, spans=None):
         """The local alignments counted into their reference's columns (cw_pileup_run): `groups` as for sw().  Returns PileupRows: the rows of sw_path() --
         status SW_PILE_SLOT never occurs with the slots made here -- .counts(group), an (ref_len, PILE_COL) array of how many queries put an A, C, G, T on the
         column, skip it, insert after it, begin and end on it, and .coverage(group).  into: a PileupRows of an earlier call over the same references, or its
@@ -921,13 +991,24 @@ class Engine:
         rows = np.zeros((S, SW_ROW), np.int32)
         b = batch.c_struct()
         pile = Pileup(_ptr(counts), _ptr(col_off))
-        rc = _check(self.lib, self.lib.cw_pileup_run(self.handle, C.byref(b), _ptr(rows), C.byref(pile), 0 if into is None else PILE_ACCUMULATE), "cw_pileup_run", allow_capacity=True)
+        flags = 0 if into is None else PILE_ACCUMULATE
+        if spans is None:
+            rc = _check(self.lib, self.lib.cw_pileup_run(self.handle, C.byref(b), _ptr(rows), C.byref(pile), flags), "cw_pileup_run", allow_capacity=True)
+        else:
+            lo, hi = span_arrays(spans, S)
+            sp = SwSpans(_ptr(lo), _ptr(hi))
+            rc = _check(self.lib, self.lib.cw_pileup_span_run(self.handle, C.byref(b), _ptr(rows), C.byref(pile), C.byref(sp), flags), "cw_pileup_span_run", allow_capacity=True)
         return PileupRows(rows, batch.win_first_seq, rc, counts, col_off, batch.seq_len)
 
     def pileup_device(self, batch_struct, rows_ptr, pile_struct, flags=0, stream=None):
         """cw_pileup_run_device: device pointers in the batch struct and in `pile_struct` (Pileup; counts 16-byte aligned), `rows_ptr` a device array of
         n_seqs * SW_ROW int32; flags 0 or PILE_ACCUMULATE; asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_pileup_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(pile_struct), flags, stream), "cw_pileup_run_device")
+
+    def pileup_span_device(self, batch_struct, rows_ptr, pile_struct, spans_struct, flags=0, stream=None):
+        """cw_pileup_span_run_device: pileup_device() with `spans_struct` (SwSpans, device arrays)."""
+        _check(self.lib, self.lib.cw_pileup_span_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(pile_struct), C.byref(spans_struct), flags, stream),
+               "cw_pileup_span_run_device")
 
     def poa_support(self, groups):
         """The support behind every consensus base: poa(groups), then every group's members piled against that group's consensus (packed on the host; two
@@ -957,7 +1038,7 @@ class Engine:
         cut_off[1:] = np.cumsum(width)
         return cut_off
 
-    def sw_cut(self, groups, window, slot_words=None):
+    def sw_cut(self, groups, window, slot_words=None, spans=None):
         """The local alignments cut at their reference's window boundaries (cw_sw_cut_run): `groups` as for sw(), `window` >= 1 reference columns.  Returns
         SwCutRows: the rows of sw_path(), .cuts(group, member) -- word t the query position at reference column t * window -- and .pieces(group, member).
         Status SW_CUT_SLOT never occurs with the slots made here; slot_words (one number, or one per sequence) makes others."""
@@ -968,13 +1049,23 @@ class Engine:
         rows = np.zeros((S, SW_ROW), np.int32)
         b = batch.c_struct()
         cuts = SwCuts(_ptr(cuts_buf), _ptr(cut_off), window)
-        rc = _check(self.lib, self.lib.cw_sw_cut_run(self.handle, C.byref(b), _ptr(rows), C.byref(cuts)), "cw_sw_cut_run", allow_capacity=True)
+        if spans is None:
+            rc = _check(self.lib, self.lib.cw_sw_cut_run(self.handle, C.byref(b), _ptr(rows), C.byref(cuts)), "cw_sw_cut_run", allow_capacity=True)
+        else:
+            lo, hi = span_arrays(spans, S)
+            sp = SwSpans(_ptr(lo), _ptr(hi))
+            rc = _check(self.lib, self.lib.cw_sw_cut_span_run(self.handle, C.byref(b), _ptr(rows), C.byref(cuts), C.byref(sp)), "cw_sw_cut_span_run", allow_capacity=True)
         return SwCutRows(rows, batch.win_first_seq, rc, cuts_buf, cut_off, window, batch)
 
     def sw_cut_device(self, batch_struct, rows_ptr, cuts_struct, stream=None):
         """cw_sw_cut_run_device: device pointers in the batch struct and in `cuts_struct` (SwCuts), `rows_ptr` a device array of n_seqs * SW_ROW int32;
         asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_sw_cut_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(cuts_struct), stream), "cw_sw_cut_run_device")
+
+    def sw_cut_span_device(self, batch_struct, rows_ptr, cuts_struct, spans_struct, stream=None):
+        """cw_sw_cut_span_run_device: sw_cut_device() with `spans_struct` (SwSpans, device arrays)."""
+        _check(self.lib, self.lib.cw_sw_cut_span_run_device(self.handle, C.byref(batch_struct), rows_ptr, C.byref(cuts_struct), C.byref(spans_struct), stream),
+               "cw_sw_cut_span_run_device")
 
     def cut_groups_device(self, batch_struct, rows_ptr, cuts_struct, grp_first=None, win_first_seq=None, seq_len=None, seq_word_off=None, bases=None,
                           group_cap=0, seq_cap=0, word_cap=0, stream=None):
@@ -1049,6 +1140,28 @@ class Engine:
         """cw_seed_run_device: device pointers in the batch struct and in `seeds_struct` (Seeds); asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_seed_run_device(self.handle, C.byref(batch_struct), C.byref(seeds_struct), stream), "cw_seed_run_device")
 
+    def seed_spans(self, groups, seed_rows, min_hits=None, pad=SPAN_PAD, pad_shift=SPAN_PAD_SHIFT):
+        """The reference columns every placed query can reach (cw_seed_spans): `groups` as for seeds(), `seed_rows` its SeedRows or their (n_seqs, SEED_ROW)
+        array.  Returns (lo, hi), uint32 per sequence: what the `spans` of sw(), sw_path(), pileup() and sw_cut() take -- for the batch ORIENTED by the seed
+        run's strands (revcomp(groups, rows.strands)), since SEED_DIAG is the oriented query's.  A reference, a query without a vote or with fewer than
+        min_hits (None: SEED_MIN_HITS) gets (0, 0): it is not aligned at all."""
+        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        S = len(batch.seq_len)
+        rows = np.ascontiguousarray(seed_rows.rows if isinstance(seed_rows, SwRows) else seed_rows, np.int32).reshape(-1, SEED_ROW)
+        if len(rows) != S:
+            raise EngineError(f"seed_spans: `seed_rows` must have one row per sequence ({S})")
+        lo, hi = np.zeros(max(S, 1), np.uint32), np.zeros(max(S, 1), np.uint32)
+        b = batch.c_struct()
+        _check(self.lib, self.lib.cw_seed_spans(self.handle, C.byref(b), _ptr(rows) if S else None, SEED_MIN_HITS if min_hits is None else int(min_hits), pad, pad_shift,
+                                                _ptr(lo), _ptr(hi)), "cw_seed_spans")
+        return lo[:S], hi[:S]
+
+    def seed_spans_device(self, batch_struct, seed_rows_ptr, lo_ptr, hi_ptr, min_hits=None, pad=SPAN_PAD, pad_shift=SPAN_PAD_SHIFT, stream=None):
+        """cw_seed_spans_device: device pointers in the batch struct, `seed_rows_ptr` a seed run's rows, `lo_ptr` / `hi_ptr` device arrays of n_seqs uint32;
+        asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_seed_spans_device(self.handle, C.byref(batch_struct), seed_rows_ptr, SEED_MIN_HITS if min_hits is None else int(min_hits), pad, pad_shift,
+                                                       lo_ptr, hi_ptr, stream), "cw_seed_spans_device")
+
     @staticmethod
     def _tiles(reference, tile):
         tile = int(tile)
@@ -1090,17 +1203,34 @@ class Engine:
             out.append(Placement(status, t * int(tile) + diag, hits, other) if voted[t, r] and hits >= floor else None)
         return out
 
-    def polish_reads(self, reference, reads, window=500, tile=8192, k=0, min_hits=None):
+    def polish_reads(self, reference, reads, window=500, tile=8192, k=0, min_hits=None, seeded=False):
         """`reference`, a contig of any length, polished from an unsorted bag of reads of either strand: place() the reads; every placed read, reverse-
         complemented when STRAND_REV, goes to every tile its footprint [position, position + length + SEED_SPAN) meets; polish() of those groups -- the tile
         first, its reads in the order given -- and the tiles' sequences joined.  `tile` must be a multiple of `window` (EngineError otherwise): windows then
         never straddle tiles, and the result is the contig's polish.  Returns one Polished: .sequence, .windows of all tiles in order, and .placements, a
-        Placement or None per read.  The placing costs O(tiles x reads) votes (see place()); the polish aligns a read only against the tiles it lies on."""
+        Placement or None per read.  The placing costs O(tiles x reads) votes (see place()); the polish aligns a read only against the tiles it lies on.
+        seeded=True: place() as above -- the seed run keeps its tiles -- then ONE group, the whole contig and the placed reads, oriented, each confined to the
+        span of reference columns its Placement.position gives by cw_seed_spans' rule (seed_spans_rule): polish(that group, spans=...).  No read is aligned
+        twice or cut at a tile's edge, no tiles are joined, and `tile` need not be a multiple of `window`.  What the one group costs instead, unmeasured: every
+        read's cut slot holds the windows of the WHOLE contig + 1 words, and cw_cut_groups_device looks at every read of the group for every window --
+        O(windows x reads) words and tests, where the tiled polish has O(windows x reads of a tile)."""
         window, tile = int(window), int(tile)
-        if window < 1 or tile % window:
+        if window < 1 or (tile % window and not seeded):
             raise EngineError("polish_reads: tile must be a multiple of window")
         reads = list(reads)
         placed = self.place(reference, reads, tile, k, min_hits)
+        if seeded:
+            if not reference:
+                return Polished("", [], placements=placed)
+            kept = [(q, p) for q, p in zip(reads, placed) if p is not None]
+            group = [reference] + [_revcomp(q) if p.strand == STRAND_REV else q for q, p in kept]
+            rows = np.zeros((len(group), SEED_ROW), np.int64)
+            rows[0, SEED_STATUS] = STRAND_IS_REF
+            for i, (q, p) in enumerate(kept):
+                rows[i + 1] = (p.strand, p.hits, p.position, p.other)
+            spans = seed_spans_rule([len(x) for x in group], len(reference), rows, min_hits=0)  # (place() has applied the threshold)
+            done = self.polish([group], window, spans=spans)[0]
+            return Polished(done.sequence, done.windows, placements=placed)
         groups = []
         for g, t in enumerate(self._tiles(reference, tile)):
             a = g * tile
@@ -1109,7 +1239,7 @@ class Engine:
         done = self.polish(groups, window) if groups else []
         return Polished("".join(d.sequence for d in done), [w for d in done for w in d.windows], placements=placed)
 
-    def polish(self, groups, window=500, orient=False, k=0):
+    def polish(self, groups, window=500, orient=False, k=0, seeded=False, min_hits=None, spans=None):
         """Every group's reference (its first sequence) polished window by window from its other sequences, the reads: the reads are aligned and cut at the
         window boundaries (cw_sw_cut_run_device), every (reference, window) becomes a POA group of the window's columns and the pieces of the reads whose
         alignments span it (cw_cut_groups_device), the POA tiers give every group's consensus (cw_poa_run_device), and the consensuses of a reference's windows
@@ -1119,8 +1249,22 @@ class Engine:
         EngineError when the windows of the batch exceed max_batch_windows(): split the references over calls.
         orient=True: the reads may be of either strand.  The uploaded batch goes through the strand vote (cw_strand_run_device, k as for strands()) and the
         reads it flags are reverse-complemented on the device (cw_revcomp_device) before the cut run; .strands of every Polished then holds its reads' strand
-        values, the only extra that leaves the device.  Without it a read of the other strand aligns by chance and its pieces rarely span a window."""
+        values, the only extra that leaves the device.  Without it a read of the other strand aligns by chance and its pieces rarely span a window.
+        seeded=True: the reads may be of either strand and need not all belong: the seed run (cw_seed_run_device, k as for seeds()) places every read on its
+        reference, cw_seed_spans_device turns the rows into spans (min_hits=None: SEED_MIN_HITS, with place()'s guard for k below SEED_MIN_K), the reads
+        are turned by the seed run's strand bytes (cw_revcomp_device) and the cut run aligns each inside its span only (cw_sw_cut_span_run_device): a read of
+        m bases costs m x (m + a pad) cells, not m x reference, and a read the seed run could not place costs nothing.  .strands as under orient=True.  A
+        reference of more than SW_RMAX bases gets STRAND_NONE from the seed run, so empty spans: it comes back unpolished -- polish_reads(seeded=True)
+        places by tiles and takes any length.  seeded and orient together: EngineError.
+        spans: explicit spans for the cut run, as for sw_cut(); the reads are aligned as given (not with seeded or orient)."""
         import torch
+
+        if seeded and (orient or spans is not None):
+            raise EngineError("polish: seeded=True takes neither orient=True nor spans")
+        if orient and spans is not None:
+            raise EngineError("polish: spans are the given reads' coordinates; orient them first")
+        if seeded and min_hits is None and 0 < int(k) < SEED_MIN_K:
+            raise EngineError(f"polish: the default min_hits is measured for k >= {SEED_MIN_K}; give min_hits with k = {k}")
 
         batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
         window = int(window)
@@ -1146,20 +1290,33 @@ class Engine:
         t_grp = torch.zeros(G + 1, dtype=torch.int32, device=dev)
         b = Batch(G, S, len(batch.bases), t_wfs.data_ptr(), t_len.data_ptr(), t_off.data_ptr(), t_bases.data_ptr())
         cuts = SwCuts(t_cuts.data_ptr(), t_coff.data_ptr(), window)
-        if orient:
+        if orient or seeded:
             t_strand = torch.zeros(S, dtype=torch.uint8, device=dev)
             t_turned = torch.zeros_like(t_bases)
+        if seeded:
+            t_seed = torch.zeros(S * SEED_ROW, dtype=torch.int32, device=dev)
+        if seeded or spans is not None:
+            lo, hi = span_arrays(spans, S) if spans is not None else (np.zeros(S, np.uint32), np.zeros(S, np.uint32))
+            t_lo, t_hi = up(lo, np.int32), up(hi, np.int32)
+            dspans = SwSpans(t_lo.data_ptr(), t_hi.data_ptr())
         torch.cuda.synchronize(dev)  # the engine launches on its own stream: torch's copies and fills above must have landed
         read_strands = [None] * G
-        if orient:  # the reads the vote flags turned round into a second `bases`: the batch the runs below see
-            self.strand_device(b, Strands(t_strand.data_ptr(), None, k))
+        if orient or seeded:  # the reads the vote flags turned round into a second `bases`: the batch the runs below see
+            if seeded:
+                self.seed_device(b, Seeds(t_seed.data_ptr(), t_strand.data_ptr(), k))
+                self.seed_spans_device(b, t_seed.data_ptr(), t_lo.data_ptr(), t_hi.data_ptr(), min_hits)
+            else:
+                self.strand_device(b, Strands(t_strand.data_ptr(), None, k))
             self.revcomp_device(b, t_strand.data_ptr(), t_turned.data_ptr())
             b.bases = t_turned.data_ptr()
             wfs = np.asarray(batch.win_first_seq, np.int64)
             torch.cuda.synchronize(dev)
             strand = down(t_strand, np.uint8)
             read_strands = [[int(v) for v in strand[wfs[g] + 1 : wfs[g + 1]]] for g in range(G)]
-        self.sw_cut_device(b, t_rows.data_ptr(), cuts)
+        if seeded or spans is not None:
+            self.sw_cut_span_device(b, t_rows.data_ptr(), cuts, dspans)
+        else:
+            self.sw_cut_device(b, t_rows.data_ptr(), cuts)
         _, ng, ns, nw = self.cut_groups_device(b, t_rows.data_ptr(), cuts)
         if ng > self.max_batch_windows():
             raise EngineError(f"polish: {ng} windows exceed the {self.max_batch_windows()} groups of a POA run; split the references over calls")

@@ -25,6 +25,9 @@
  *   cw_revcomp / cw_revcomp_device <- the batch with those queries reverse-complemented, for any of the runs above.
  *   cw_seed_run / cw_seed_run_device <- which queries belong to their group's reference at all, on which strand and on which diagonal, by k-mers that are
  *                               unique in the reference (no counterpart: the reference takes all three from minimap2's PAF records).
+ *   cw_sw_span_run, cw_sw_path_span_run, cw_pileup_span_run, cw_sw_cut_span_run (and _device) <- the four alignment runs with every query confined to a span
+ *                               of its reference's columns, and cw_seed_spans / cw_seed_spans_device <- those spans from a seed run's rows (no counterpart:
+ *                               the reference aligns a read against the window its PAF record names).
  *   cw_window_positions     <- getAlignmentWindowsPositions (alignmentWindows.cpp:27-85), host
  *   cw_extract_piles_device  <- getAlignmentWindowsSequences (alignmentWindows.cpp:87-149) evaluated on the device
  *   cw_stitch_device         <- alignConsensus + trimRead + dropRead (correctionAlignment.cpp:47-140, utils.cpp:96-128, :71-73)
@@ -459,6 +462,55 @@ typedef struct cw_seeds {
 } cw_seeds;
 int cw_seed_run_device(cw_engine* e, const cw_batch* groups, const cw_seeds* out, void* hip_stream);
 int cw_seed_run(cw_engine* e, const cw_batch* groups, const cw_seeds* out);
+
+/* ---- align a query only where it was placed: reference spans ------------------------------------------------------------------------------------------------------
+ * The four alignment runs sweep every query over ALL columns of its reference.  Each has a span form that confines query s to the reference columns
+ * [ref_lo[s], ref_hi[s]): cw_sw_span_run, cw_sw_path_span_run, cw_pileup_span_run, cw_sw_cut_span_run and their _device forms -- the counterpart's
+ * arguments with `spans` before flags / hip_stream, and the counterpart's pointer conventions (host / device, the two arrays of spans included), stream
+ * contract, flags, statuses and stage names.  Per query s with reference r of n bases, each a function of the pair and its two span words alone:
+ *   clamping       lo = min(ref_lo[s], n), hi = min(ref_hi[s], n).  The entries of references are not read.
+ *   empty span     hi <= lo (lo > hi as given included): the row of an empty reference -- score 0, begins 0, ends -1, CW_SW_ALIGNED -- no ops, nothing counted,
+ *                  T + 1 zero cut words.
+ *   otherwise      what the counterpart gives for a group whose reference is reference[lo, hi), with lo added to CW_SW_REF_BEGIN and CW_SW_REF_END when the
+ *                  score is positive: score, query ends, ins / del, status and ops are identical.  Pileup columns and cut boundaries are ABSOLUTE, on the
+ *                  whole reference: col_off slots, T = ceil(n / W), CW_SW_CUTS(n, W), the clearing of columns 0 .. n - 1, CW_SW_PILE_SLOT and CW_SW_CUT_SLOT
+ *                  refer to n, and the cut formula above holds with the absolute ref_begin / ref_end.  A base just outside [lo, hi) never takes part, even
+ *                  when it would extend the alignment.
+ *   capacities     CW_SW_STOP for a query of more than CW_SW_QMAX bases, for a clamped span of more than CW_SW_RMAX columns -- CW_SW_RMAX is a capacity of the
+ *                  sweep, which holds a column in 16 bits, not of the reference -- and for n > INT32_MAX (a row holds a column in 32).  A reference of any
+ *                  other length is valid here; the entry points without spans keep their stop at n > CW_SW_RMAX.
+ * CW_E_INVALID on top of the counterpart's: spans == NULL, or one of its members while n_seqs > 0.  The host forms upload the two arrays with the batch.
+ * cw_cut_groups_device takes the rows and cuts of a span run as they come.
+ *
+ * cw_seed_spans_device: the spans of a seed run, on the device, one thread a sequence.  With m the query's length, n its reference's and
+ * P = pad + (m >> pad_shift), in 64-bit signed arithmetic:
+ *   a placed query    (CW_SEED_STATUS is CW_STRAND_FWD or CW_STRAND_REV and CW_SEED_HITS >= min_hits)
+ *                     lo = clamp(CW_SEED_DIAG - P, 0, n), hi = clamp(CW_SEED_DIAG + (2 << CW_SEED_SHIFT) + m + P, 0, n): the window's 128 diagonals over the
+ *                     whole query, and the pad for the drift of a read's diagonal from its densest window
+ *   everything else   (CW_STRAND_IS_REF, CW_STRAND_NONE, fewer hits) lo = hi = 0: an unplaced read then costs the aligner nothing
+ * CW_SEED_DIAG is in the ORIENTED query's coordinates: the spans are meant for the batch cw_revcomp_device wrote from the seed run's strand bytes, not for the
+ * batch the seed run read.  CW_E_INVALID for pad_shift > 31, NULL groups / seed_rows, NULL ref_lo / ref_hi while n_seqs > 0, more than
+ * cw_max_batch_windows(e) groups.  Device pointers, asynchronous on `hip_stream`, cw_strand_run_device's contract; no scratch; one stage, seed_spans.
+ * cw_seed_spans: host pointers, synchronous.  CW_SPAN_PAD_SHIFT is measured: the smallest pad of pad_shift 4, 3, 2 at pad 64 under which every
+ * planted read of the project's tests aligns inside its span exactly as on the whole reference. */
+typedef struct cw_sw_spans {
+    const uint32_t* ref_lo;   /* [n_seqs] first reference column a query may use       */
+    const uint32_t* ref_hi;   /* [n_seqs] one past the last; entries of references are not read */
+} cw_sw_spans;
+#define CW_SPAN_PAD 64u
+#define CW_SPAN_PAD_SHIFT 4u
+int cw_sw_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_spans* spans, uint32_t flags, void* hip_stream);
+int cw_sw_span_run(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_spans* spans, uint32_t flags);
+int cw_sw_path_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, const cw_sw_spans* spans, uint32_t flags, void* hip_stream);
+int cw_sw_path_span_run(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, const cw_sw_spans* spans, uint32_t flags);
+int cw_pileup_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, const cw_sw_spans* spans, uint32_t flags, void* hip_stream);
+int cw_pileup_span_run(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, const cw_sw_spans* spans, uint32_t flags);
+int cw_sw_cut_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, const cw_sw_spans* spans, void* hip_stream);
+int cw_sw_cut_span_run(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, const cw_sw_spans* spans);
+int cw_seed_spans_device(cw_engine* e, const cw_batch* groups, const int32_t* seed_rows, uint32_t min_hits, uint32_t pad, uint32_t pad_shift,
+                         uint32_t* ref_lo, uint32_t* ref_hi, void* hip_stream);
+int cw_seed_spans(cw_engine* e, const cw_batch* groups, const int32_t* seed_rows, uint32_t min_hits, uint32_t pad, uint32_t pad_shift,
+                  uint32_t* ref_lo, uint32_t* ref_hi);
 
 /* 1 when everything the last cw_run_device on this engine launched has completed (or nothing was launched yet), 0 while it is
  * still running, 2 while it is running but past the part that fills the GPU (what is left is the tail: a few long alignment tasks on

@@ -20,6 +20,7 @@ reference length: the forward sweep's; the reverse sweep and the traceback come 
     python tools/sw_bench.py --cut                        # a fifth: the cut run of the same batch at --window columns a window, on the shapes of --pileup
     python tools/sw_bench.py --strand                     # instead: the strand vote and the reverse complement beside the plain run and a device copy of the same batch
     python tools/sw_bench.py --seed                       # instead: the seed run (cw_seed_run_device) beside the strand vote and the plain run of the same batch
+    python tools/sw_bench.py --span                       # instead: the plain and the cut run with and without the spans of a seed run, reads of 1 000 and 3 000 bases on 8 192
     python tools/sw_bench.py --oracle 4096                # also: so many 500 x 600 pairs through the oracle's cwo_ssw on --threads CPU threads
 
 Prints one JSON line per measurement and a markdown table (DESIGN.md section 4.8 holds the first one, from a --path run).
@@ -38,12 +39,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import consent_amd as ca  # noqa: E402
-from consent_amd.engine import Batch, HostBatch, Pileup, Seeds, Strands, SwCuts, SwPaths, sw_cuts  # noqa: E402
+from consent_amd.engine import Batch, HostBatch, Pileup, Seeds, Strands, SwCuts, SwPaths, SwSpans, sw_cuts  # noqa: E402
 
 SHAPES = {"24x150": 262144, "100x600": 131072, "500x600": 65536, "2000x2048": 4096, "8000x2048": 512, "1540x1540": 2048}  # query x reference -> pairs of the default run
 PLANTED = {"1540x1540": (500, 40)}  # shapes built as planted pairs: (part, g)
 DEEP = {"500x600x30": 61440}  # query x reference x queries per reference: what --pileup adds
 WIDE_GROUP = {"500x2048": 16384, "500x2048x16384": 16384}  # what --strand adds: 16 queries a reference, and ONE reference with all 16 384 queries -- equal lengths
+SPAN = {"1000x8192": 2048, "3000x8192": 512}  # what --span runs: reads planted at 10 - 12 % errors in references of 8 192 bases, 16 a reference
 PATH, PILE, CUT = "path", "pileup", "cut"  # the third, fourth and fifth mode beside flags 0 and CW_SW_WANT_INDELS
 
 
@@ -297,6 +299,97 @@ def bench_seed(eng, shape, n_pairs, per_group, steps, warmup, seed):
             "stage_ms": {k: round(float(np.median(v)), 4) for k, v in stages.items()}}
 
 
+def make_planted_reads(n_pairs, qlen, rlen, per_group, seed):
+    """HostBatch of groups of one random reference and per_group reads: a read copies qlen reference bases from a random start with 10 - 12 % errors (a rate
+    drawn per read; substitutions, insertions and deletions a third each), every second read reverse-complemented."""
+    rng = np.random.default_rng(seed)
+    G = max(1, n_pairs // per_group)
+    refs = rng.integers(0, 4, (G, rlen), dtype=np.uint8)
+    seqs = []
+    for g in range(G):
+        seqs.append(refs[g])
+        for k in range(per_group):
+            a = int(rng.integers(0, rlen - qlen + 1))
+            src = refs[g, a : a + qlen]
+            rate = rng.uniform(0.10, 0.12)
+            x = rng.random(qlen)
+            take = np.where(x < rate / 3, 0, np.where(x < 2 * rate / 3, 2, 1))  # a deletion, an insertion behind the base, the base
+            out = np.repeat(src, take)
+            first = np.cumsum(take) - take  # where a base's copies begin
+            ins = first[take == 2] + 1
+            out[ins] = rng.integers(0, 4, len(ins), dtype=np.uint8)
+            sub = first[(x >= 2 * rate / 3) & (x < rate)]
+            out[sub] = (out[sub] + rng.integers(1, 4, len(sub), dtype=np.uint8)) & 3
+            seqs.append((3 - out[::-1]).astype(np.uint8) if k % 2 else out)
+    lens = np.array([len(x) for x in seqs], np.uint32)
+    words = [pack(x[None, :])[0] for x in seqs]
+    offs = np.concatenate([[0], np.cumsum([len(w) for w in words])[:-1]]).astype(np.uint64)
+    return HostBatch(np.arange(G + 1, dtype=np.uint32) * (1 + per_group), lens, offs, np.concatenate(words))
+
+
+def bench_span(eng, shape, n_pairs, per_group, steps, warmup, seed, window):
+    """One batch of planted reads in device memory.  The seed side once per step -- cw_seed_run_device, cw_seed_spans_device, cw_revcomp_device by the seed
+    run's strand bytes -- then, on the oriented batch, the plain run and the cut run without spans (cw_sw_run_device, cw_sw_cut_run_device) and with them
+    (cw_sw_span_run_device, cw_sw_cut_span_run_device).  Device time between a run's first and last event, the median of `steps` with the lowest and highest."""
+    import torch
+
+    qlen, rlen = (int(v) for v in shape.split("x"))
+    hb = make_planted_reads(n_pairs, qlen, rlen, per_group, seed)
+    S, G, Wd = len(hb.seq_len), hb.n_windows, len(hb.bases)
+    n_pairs = S - G
+    dev = torch.device("cuda", eng.device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
+
+    t_in = (up(hb.win_first_seq, np.int32), up(hb.seq_len, np.int32), up(hb.seq_word_off, np.int64), up(np.concatenate([hb.bases, np.zeros(4, np.uint32)]), np.int32))
+    t_turned = torch.zeros(Wd + 4, dtype=torch.int32, device=dev)
+    t_rows, t_rows_s = torch.zeros(S * 8, dtype=torch.int32, device=dev), torch.zeros(S * 8, dtype=torch.int32, device=dev)
+    t_seed, t_sbyte = torch.zeros(S * ca.SEED_ROW, dtype=torch.int32, device=dev), torch.zeros(S, dtype=torch.uint8, device=dev)
+    t_lo, t_hi = torch.zeros(S, dtype=torch.int32, device=dev), torch.zeros(S, dtype=torch.int32, device=dev)
+    wfs, lens = hb.win_first_seq.astype(np.int64), hb.seq_len.astype(np.int64)
+    width = sw_cuts(lens[np.repeat(wfs[:-1], np.diff(wfs))], window)
+    width[wfs[:-1]] = 0
+    off = np.concatenate([[0], np.cumsum(width)]).astype(np.uint64)
+    t_off = up(off, np.int64)
+    t_cuts, t_cuts_s = torch.zeros(int(off[-1]) + 1, dtype=torch.int32, device=dev), torch.zeros(int(off[-1]) + 1, dtype=torch.int32, device=dev)
+    b = Batch(G, S, Wd, t_in[0].data_ptr(), t_in[1].data_ptr(), t_in[2].data_ptr(), t_in[3].data_ptr())
+    bo = Batch(G, S, Wd, t_in[0].data_ptr(), t_in[1].data_ptr(), t_in[2].data_ptr(), t_turned.data_ptr())  # the oriented batch
+    seeds, spans = Seeds(t_seed.data_ptr(), t_sbyte.data_ptr(), 0), SwSpans(t_lo.data_ptr(), t_hi.data_ptr())
+    cuts, cuts_s = SwCuts(t_cuts.data_ptr(), t_off.data_ptr(), window), SwCuts(t_cuts_s.data_ptr(), t_off.data_ptr(), window)
+    torch.cuda.synchronize(dev)
+    runs = {"seed": lambda: eng.seed_device(b, seeds), "seed_spans": lambda: eng.seed_spans_device(b, t_seed.data_ptr(), t_lo.data_ptr(), t_hi.data_ptr()),
+            "revcomp": lambda: eng.revcomp_device(b, t_sbyte.data_ptr(), t_turned.data_ptr()),
+            "sw": lambda: eng.sw_device(bo, C.c_void_p(t_rows.data_ptr()), 0), "sw_span": lambda: eng.sw_span_device(bo, C.c_void_p(t_rows_s.data_ptr()), spans, 0),
+            "cut": lambda: eng.sw_cut_device(bo, C.c_void_p(t_rows.data_ptr()), cuts), "cut_span": lambda: eng.sw_cut_span_device(bo, C.c_void_p(t_rows_s.data_ptr()), cuts_s, spans)}
+    out, stages, same = {}, {}, {}
+    for name, run in runs.items():
+        device = []
+        for step in range(warmup + steps):
+            run()
+            torch.cuda.synchronize(dev)
+            if step >= warmup:
+                t = eng.timings()
+                device.append(t["total"])
+                for k, v in t.items():
+                    stages.setdefault(name, {}).setdefault(k, []).append(v)
+        out[name] = {"device_ms": [round(float(np.median(device)), 4), round(min(device), 4), round(max(device), 4)]}
+        if name in ("sw_span", "cut_span"):  # the rows of the run without spans just before it
+            same[name] = float((t_rows.cpu().numpy().reshape(S, 8) == t_rows_s.cpu().numpy().reshape(S, 8)).all(axis=1).mean())
+    lo, hi = t_lo.cpu().numpy().view(np.uint32).astype(np.int64), t_hi.cpu().numpy().view(np.uint32).astype(np.int64)
+    is_q = np.ones(S, bool)
+    is_q[hb.win_first_seq[:-1]] = False
+    span_len = (hi - lo)[is_q]
+    med = lambda name: out[name]["device_ms"][0]
+    seed_side = med("seed") + med("seed_spans") + med("revcomp")
+    return {"shape": shape, "mode": "span", "pairs": n_pairs, "groups": G, "steps": steps, "window": window, **out, "placed": int((span_len > 0).sum()),
+            "mean_span": round(float(span_len.mean()), 1), "cell_ratio": round(rlen / max(float(span_len.mean()), 1.0), 3),
+            "sw_ratio": round(med("sw") / med("sw_span"), 3), "cut_ratio": round(med("cut") / med("cut_span"), 3),
+            "sw_ratio_with_seed_side": round(med("sw") / (med("sw_span") + seed_side), 3), "cut_ratio_with_seed_side": round(med("cut") / (med("cut_span") + seed_side), 3),
+            "seed_side_ms": round(seed_side, 4), "rows_equal": {k: round(v, 5) for k, v in same.items()},
+            "stage_ms": {n: {k: round(float(np.median(v)), 4) for k, v in st.items()} for n, st in stages.items()}}
+
+
 def oracle_rate(n_pairs, threads, seed):
     """n_pairs 500 x 600 pairs of the same construction through the oracle's cwo_ssw (oracle/liboracle.so) on `threads` threads: pairs/s, cells/s."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -335,6 +428,8 @@ def main():
     ap.add_argument("--strand", action="store_true", help="instead of the alignment modes: cw_strand_run_device and cw_revcomp_device beside the plain run and a device-to-device copy of the same "
                     "batch, on the shapes of --cut, on 500x2048 and on one group of a 2 048-base reference with 16 384 queries of 500 bases")
     ap.add_argument("--seed", action="store_true", help="instead of the alignment modes: cw_seed_run_device beside cw_strand_run_device and the plain run of the same batch, on the shapes of --strand")
+    ap.add_argument("--span", action="store_true", help="instead of the alignment modes: the plain run and the cut run without spans and with the spans of a seed run "
+                    "(cw_seed_run_device + cw_seed_spans_device, timed beside them), reads of 1 000 and 3 000 bases planted at 10 - 12 % errors in references of 8 192")
     ap.add_argument("--window", type=int, default=100, help="reference columns a window of the cut run")
     ap.add_argument("--oracle", type=int, default=0, help="also time so many 500x600 pairs through the oracle on --threads CPU threads")
     ap.add_argument("--threads", type=int, default=16)
@@ -342,6 +437,20 @@ def main():
     a.pileup = a.pileup or a.cut
     eng = ca.Engine(ca.Params(9, 4, 8, 2, 150), device=a.device)
     rows = []
+    if a.span:
+        try:
+            for shape in a.shape or list(SPAN):
+                rows.append(bench_span(eng, shape, a.pairs or SPAN.get(shape, 1024), a.per_group, a.steps, a.warmup, a.rng_seed, a.window if a.window != 100 else 500))
+                print(json.dumps(rows[-1]), flush=True)
+        finally:
+            eng.close()
+        cell = lambda m: f"{m['device_ms'][0]:.2f} ({m['device_ms'][1]:.2f} - {m['device_ms'][2]:.2f})"
+        print("\n| read x reference | pairs | mean span | cells n / span | plain ms | plain span ms | ratio | cut ms | cut span ms | ratio | seed + spans + revcomp ms | cut ratio with those | rows equal |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['shape']} | {r['pairs']} | {r['mean_span']:.0f} | {r['cell_ratio']:.2f} | {cell(r['sw'])} | {cell(r['sw_span'])} | {r['sw_ratio']:.2f} | {cell(r['cut'])} | {cell(r['cut_span'])} | "
+                  f"{r['cut_ratio']:.2f} | {r['seed_side_ms']:.3f} | {r['cut_ratio_with_seed_side']:.2f} | {min(r['rows_equal'].values()):.4f} |")
+        return
     if a.seed:
         try:
             for shape in a.shape or list(SHAPES) + list(DEEP) + list(WIDE_GROUP):
