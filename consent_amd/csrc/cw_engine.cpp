@@ -7,7 +7,11 @@
  * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run); the re-assembly's local aligner alone on a batch of groups
  * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h; cw_pileup_run_device, cw_pileup_run: cw_pileup.h; cw_sw_cut_run_device, cw_sw_cut_run,
  * cw_cut_groups_device: cw_sw_cut.h); both strands for them (cw_strand_run_device, cw_strand_run, cw_revcomp_device, cw_revcomp: cw_strand.h); reads placed on
- * their reference (cw_seed_run_device, cw_seed_run: cw_seed.h).
+ * their reference (cw_seed_run_device, cw_seed_run, cw_seed_spans_device, cw_seed_spans: cw_seed.h).
+ * What the operators' entry points share exists once, in the anonymous namespace: Layout (arrays 256-byte aligned in one allocation), locked (a _device entry
+ * point is its run_*_locked body under the engine's mutex), dev_batch (cw_batch -> DevBatch), run_begin / run_end (the bracket round the stages of every run,
+ * a window run's included) and HostTrip (a host form's round trip: lock, check_groups, the output layout, upload_groups, up / down / sync); each host form
+ * states only its validation, its slots, its outputs, what else goes up, its device form and what it copies back.
  * The scratch plan is cw_plan.h (host arithmetic only); the host feeders, cw_window_positions among them, are cw_hostio.cpp.
  */
 #include "cw_internal.h"
@@ -91,6 +95,27 @@ int ensure(void** ptr, size_t* have, size_t need) {
     return CW_OK;
 }
 
+/* arrays laid one behind the other in one allocation, each 256-byte aligned: put returns where an array begins, bytes is what all of them take */
+struct Layout {
+    size_t bytes = 0;
+    size_t put(size_t n) { const size_t at = bytes; bytes = align_up(bytes + n, 256); return at; }
+};
+
+/* an entry point that is `body` under the engine's mutex; a NULL engine is refused before the lock */
+template <class F>
+int locked(cw_engine* e, F body) {
+    if (!e) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return body();
+}
+
+/* the batch as the kernels take it */
+DevBatch dev_batch(const cw_batch* b) {
+    DevBatch d;
+    d.n_windows = b->n_windows; d.win_first_seq = b->win_first_seq; d.seq_len = b->seq_len; d.seq_word_off = b->seq_word_off; d.bases = b->bases;
+    return d;
+}
+
 int check_params(const cw_params* p) {
     if (!p) return CW_E_INVALID;
     if (p->k < 2 || p->k > 16) return CW_E_INVALID; /* k-mers are 32-bit keys; k <= 9 counts in a direct LDS table, larger k in a hashed one */
@@ -142,6 +167,26 @@ void stage(cw_engine* e, hipStream_t st, const char* name, L launch) {
     (void)hipEventRecord(e->ev0[i], st);
     launch();
     (void)hipEventRecord(e->ev1[i], st);
+}
+
+/* The bracket round the stages of every run: no stage recorded and ev_begin on st before them; ev_end, a look at the launches' errors and valid timings behind
+   them.  takes_scratch: the run puts a plan of its own over the engine's scratch, which then no longer holds a window or POA run's records -- the inspection
+   entry points and the re-run loop's look at the last run refuse (cw_debug_win_info, cw_debug_solid_table) or find nothing to do (grow_if_that_helps,
+   decay_scale).  A window or POA run has noted its windows by then (hold_and_bind); the reverse complement and the seed spans use no scratch: all three pass
+   false. */
+int run_begin(cw_engine* e, hipStream_t st, bool takes_scratch) {
+    if (takes_scratch) e->last_windows = 0;
+    e->n_stages = 0;
+    e->timings_valid = false;
+    CW_HIP(hipEventRecord(e->ev_begin, st));
+    return CW_OK;
+}
+
+int run_end(cw_engine* e, hipStream_t st) {
+    CW_HIP(hipEventRecord(e->ev_end, st));
+    CW_HIP(hipGetLastError());
+    e->timings_valid = true;
+    return CW_OK;
 }
 
 /* what a plan of this engine is made from, for a batch of these totals: its parameters, its device, the tier-G slots of its last run, its current scale and
@@ -317,10 +362,8 @@ LaunchShape launch_shape(cw_engine* e, const cw_batch* batch, const ScratchPlan&
 
 /* what every run starts from: no stage recorded, the batch counters at zero, every slab free, tier L's live queue empty */
 int enqueue_begin(cw_engine* e, hipStream_t st, const DevScratch& sc, const ScratchPlan& p) {
-    if (sc.task_dbg) CW_HIP(hipMemsetAsync(sc.task_dbg, 0, (size_t)p.task_cap * 16, st));
-    e->n_stages = 0;
-    e->timings_valid = false;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
+    if (sc.task_dbg) CW_HIP(hipMemsetAsync(sc.task_dbg, 0, (size_t)p.task_cap * 16, st)); /* (before ev_begin: not part of the run's time) */
+    if (int rc = run_begin(e, st, false)) return rc;
     CW_HIP(hipMemsetAsync(sc.ctr, 0, sizeof(BatchCounters), st));
     CW_HIP(hipMemsetAsync(sc.slot_busy[0], 0, p.sbusy[CW_TIERS - 1] + (size_t)p.tier[CW_TIERS - 1].slots * 4 - p.sbusy[0], st)); /* every slab free */
     CW_HIP(hipMemsetAsync(sc.over_list[3], 0xFF, (size_t)p.task_cap * 4, st)); /* live queue: an entry is its own flag */
@@ -330,10 +373,7 @@ int enqueue_begin(cw_engine* e, hipStream_t st, const DevScratch& sc, const Scra
 /* ... and ends with: the feedback for the next batch's linger_wgs (pinned destination: asynchronous) */
 int enqueue_end(cw_engine* e, hipStream_t st, const DevScratch& sc) {
     CW_HIP(hipMemcpyAsync(&e->host_fb->handed_over, &sc.ctr->n_over[3], 4, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
-    return CW_OK;
+    return run_end(e, st);
 }
 
 /* The POA stage of a run, window or POA-only: sort, fork; tiers L / M2 / M1 on the side streams and Q (H) S on the engine's own, all concurrently; join; the
@@ -413,8 +453,7 @@ int run_device_locked(cw_engine* e, const cw_batch* batch, const cw_result* res,
     ScratchPlan p; DevScratch sc;
     if ((rc = plan_and_bind(e, batch, pf_full, &p, &sc)) != CW_OK) return rc;
     const LaunchShape ls = launch_shape(e, batch, p, sc);
-    DevBatch db;
-    db.n_windows = batch->n_windows; db.win_first_seq = batch->win_first_seq; db.seq_len = batch->seq_len; db.seq_word_off = batch->seq_word_off; db.bases = batch->bases;
+    const DevBatch db = dev_batch(batch);
     e->last_win_first_seq = batch->win_first_seq;
     FinOut fo;
     fo.cons = res->cons; fo.cons_off = res->cons_off; fo.cons_len = res->cons_len; fo.win_status = res->win_status;
@@ -444,8 +483,7 @@ int poa_device_locked(cw_engine* e, const cw_batch* groups, const cw_result* res
     DevScratch sc;
     if ((rc = hold_and_bind(e, G, big_slots, p, &sc)) != CW_OK) return rc;
     const LaunchShape ls = launch_shape(e, groups, p, sc);
-    DevBatch db;
-    db.n_windows = G; db.win_first_seq = groups->win_first_seq; db.seq_len = groups->seq_len; db.seq_word_off = groups->seq_word_off; db.bases = groups->bases;
+    const DevBatch db = dev_batch(groups);
     e->last_win_first_seq = groups->win_first_seq;
     PoaOut po;
     po.cons = res->cons; po.cons_off = res->cons_off; po.cons_len = res->cons_len; po.win_status = res->win_status;
@@ -514,7 +552,7 @@ int hold_sw(cw_engine* e, size_t total, void* hip_stream, hipStream_t* st) {
 SwArgs bind_sw(const cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, const SwPlan& p, const cw_sw_spans* spans) {
     uint8_t* base = (uint8_t*)e->scratch;
     SwArgs a;
-    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.b = dev_batch(groups);
     a.n_seqs = groups->n_seqs; a.rows = rows; a.flags = flags;
     a.ctr = (uint32_t*)(base + p.ctr); a.seq_ref = (uint32_t*)(base + p.seq_ref); a.order = (uint32_t*)(base + p.order);
     a.dir = p.dir_bytes ? (int8_t*)(base + p.dir) : nullptr; a.dir_bytes = p.dir_bytes;
@@ -539,10 +577,7 @@ struct SwExtras {
    so nothing here waits for it). */
 template <class Args>
 int enqueue_sw_run(cw_engine* e, hipStream_t st, const SwArgs& a, const SwPlan& p, const SwStages<Args>& k, const Args& args, const SwExtras& x = SwExtras()) {
-    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records: the inspection entry points and the re-run loop's look at the last run refuse (cw_debug_win_info, cw_debug_solid_table) or find nothing to do (grow_if_that_helps, decay_scale) */
-    e->n_stages = 0;
-    e->timings_valid = false;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
+    if (int rc = run_begin(e, st, true)) return rc;
     CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_SW_CTR_WORDS * 4, st));
     if (x.zero) CW_HIP(hipMemsetAsync(x.zero, 0, (size_t)a.n_seqs * 4, st));
     const uint32_t og = (a.n_seqs + 255u) / 256u;
@@ -556,10 +591,7 @@ int enqueue_sw_run(cw_engine* e, hipStream_t st, const SwArgs& a, const SwPlan& 
     stage(e, st, k.names[0], [&] { k.k0<<<p.wgs0, 64 * CW_SW_WAVES, lds_sw(0), st>>>(args); });
     stage(e, st, k.names[1], [&] { k.k1<<<p.wgs1, 64 * CW_SW_WAVES, lds_sw(1), st>>>(args); });
     stage(e, st, k.names[2], [&] { k.k_long<<<p.wgs_long, 64, 0, st>>>(args); });
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
-    return CW_OK;
+    return run_end(e, st);
 }
 
 /* the body of cw_sw_run_device and of cw_sw_span_run_device (spans: NULL for the first; the same in the three bodies below); the caller holds e->mu.  Stages: sw_order, sw_align, sw_align_wide, sw_align_long. */
@@ -629,9 +661,39 @@ int run_sw_cut_locked(cw_engine* e, const cw_batch* groups, int32_t* rows, const
                                        : SwStages<CutArgs>{{"cut", "cut_wide", "cut_long"}, cw_sw_cut_kernel<0, false>, cw_sw_cut_kernel<1, false>, cw_sw_cut_long_kernel<false>}, ca, x);
 }
 
-/* What the four host-buffer entry points check first: the groups begin at sequence 0, end at n_seqs and never step back, every sequence lies inside n_words, and
-   the run's slot offsets slot_off[0 .. n_seqs], when it has some, never step back. */
-int check_groups(const cw_batch* b, const uint64_t* slot_off, std::vector<uint64_t>* rebased) {
+/* ---- host buffers in, host buffers out: what cw_sw_run and the other host forms of the operators do alike ------------------------------------------------------ */
+
+/* One synchronous call on host buffers, under the engine's mutex from its construction on: the device buffers are the engine's.  A host form validates (its
+   own validate_*, which answers a batch without sequences before anything here), then: check_groups with its slot offsets if it has some; its outputs laid
+   out in `out` and its own host allocations; upload_groups; up() of what else its run reads; its device form on `st` with `db`, dev_spans() and at() of its
+   outputs; down() of what comes back; sync(); and the caller's bytes it owns written on the host.  Checks and host allocations, the two device buffers, then
+   the uploads, then the run: behind the first enqueued copy a form returns early only when the runtime or the run itself fails. */
+struct HostTrip {
+    cw_engine* const e;
+    const cw_batch* const b;
+    const cw_sw_spans* const spans; /* a span form's two host arrays: they go up with the batch; NULL otherwise */
+    std::lock_guard<std::mutex> lk;
+    Layout out;                     /* the form's outputs, and what else it sends up, in e->poa_out */
+    std::vector<uint64_t> slot;     /* check_groups: the slot offsets rebased to the first slot -- the device copy of the slots begins there; lives until sync() */
+    cw_batch db;                    /* upload_groups: the batch with device pointers, */
+    const uint64_t* d_slot = nullptr; /* `slot` on the device, */
+    cw_sw_spans dsp;                /* the spans on the device (dev_spans()), */
+    hipStream_t st = nullptr;       /* the engine's stream */
+    uint8_t* dout = nullptr;        /* and e->poa_out, out.bytes of it */
+
+    HostTrip(cw_engine* e_, const cw_batch* b_, const cw_sw_spans* spans_ = nullptr) : e(e_), b(b_), spans(spans_), lk(e_->mu) {}
+    int check_groups(const uint64_t* slot_off);
+    int upload_groups();
+    const cw_sw_spans* dev_spans() const { return spans ? &dsp : nullptr; }
+    template <class T> T* at(size_t off) const { return (T*)(dout + off); }
+    hipError_t up(size_t off, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dout + off, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; }
+    hipError_t down(void* dst, size_t off, size_t bytes) { return bytes ? hipMemcpyAsync(dst, dout + off, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; }
+    hipError_t sync() { return hipStreamSynchronize(st); }
+};
+
+/* What the host forms check first: the groups begin at sequence 0, end at n_seqs and never step back, every sequence lies inside n_words, and the run's slot
+   offsets slot_off[0 .. n_seqs], when it has some (else NULL), never step back. */
+int HostTrip::check_groups(const uint64_t* slot_off) {
     const uint32_t G = b->n_windows, S = b->n_seqs;
     if (b->win_first_seq[0] != 0 || b->win_first_seq[G] != S) return CW_E_INVALID;
     for (uint32_t g = 0; g < G; ++g) if (b->win_first_seq[g + 1] < b->win_first_seq[g]) return CW_E_INVALID;
@@ -639,44 +701,48 @@ int check_groups(const cw_batch* b, const uint64_t* slot_off, std::vector<uint64
         if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words) return CW_E_INVALID;
         if (slot_off && slot_off[s + 1] < slot_off[s]) return CW_E_INVALID;
     }
-    if (slot_off) { /* rebased to the first slot: the device copy of the slots begins there */
-        try { rebased->resize((size_t)S + 1); } catch (...) { return CW_E_NOMEM; }
-        for (uint32_t s = 0; s <= S; ++s) (*rebased)[s] = slot_off[s] - slot_off[0];
+    if (slot_off) {
+        try { slot.resize((size_t)S + 1); } catch (...) { return CW_E_NOMEM; }
+        for (uint32_t s = 0; s <= S; ++s) slot[s] = slot_off[s] - slot_off[0];
     }
     return CW_OK;
 }
 
-/* The checked batch goes up, on the engine's stream: into the engine's input buffer (the one cw_poa_run uses for its own), every array 256-byte aligned, and
-   behind it the slot offsets rebased to the first slot -- the device copy of the slots begins there.  *db: the batch with device pointers; *rebased: the rebased
-   offsets on the host, which must live until the stream is synchronised; *d_off: the same on the device.  An entry point calls this last before the run: its own
-   host allocations and its output buffer are in place by then, so behind the first copy enqueued here it returns early only as it always did, when the run
-   itself fails.  A span run's two arrays (spans, when not NULL) go up behind those; *dspans: the same on the device. */
-int upload_groups(cw_engine* e, const cw_batch* b, const std::vector<uint64_t>* rebased, cw_batch* db, const uint64_t** d_off, const cw_sw_spans* spans = nullptr,
-                  cw_sw_spans* dspans = nullptr) {
+/* the engine's two buffers for host forms, of at least these sizes, on its device: the hold step of every host form, cw_poa_run included */
+int hold_io(cw_engine* e, size_t in_bytes, size_t out_bytes) {
+    CW_HIP(hipSetDevice(e->device));
+    if (int rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) return rc;
+    return ensure(&e->poa_out, &e->poa_out_bytes, out_bytes);
+}
+
+/* The checked batch goes up, on the engine's stream: into the engine's input buffer (the one cw_poa_run uses for its own), every array 256-byte aligned, behind
+   it the rebased slot offsets when the form has slots, behind those a span form's two arrays.  The buffers are held here, both of them and before the first
+   copy; a host form calls this last before its own uploads and the run, with its host allocations made and `out` laid out. */
+int HostTrip::upload_groups() {
     const uint32_t G = b->n_windows, S = b->n_seqs;
-    size_t o = 0;
-    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
-                 i_soff = rebased ? put((size_t)(S + 1) * 8) : 0, i_lo = spans ? put((size_t)S * 4) : 0, i_hi = spans ? put((size_t)S * 4) : 0;
-    if (int rc = ensure(&e->poa_in, &e->poa_in_bytes, o)) return rc;
+    Layout in;
+    const size_t i_wfs = in.put((size_t)(G + 1) * 4), i_len = in.put((size_t)S * 4), i_off = in.put((size_t)S * 8), i_bases = in.put((size_t)(b->n_words + 1) * 4),
+                 i_slot = slot.empty() ? 0 : in.put((size_t)(S + 1) * 8), i_lo = spans ? in.put((size_t)S * 4) : 0, i_hi = spans ? in.put((size_t)S * 4) : 0;
+    if (int rc = hold_io(e, in.bytes, out.bytes)) return rc;
     uint8_t* din = (uint8_t*)e->poa_in;
-    hipStream_t st = e->stream;
+    dout = (uint8_t*)e->poa_out;
+    st = e->stream;
     CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
     CW_HIP(hipMemcpyAsync(din + i_len, b->seq_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
     CW_HIP(hipMemcpyAsync(din + i_off, b->seq_word_off, (size_t)S * 8, hipMemcpyHostToDevice, st));
     if (b->n_words) CW_HIP(hipMemcpyAsync(din + i_bases, b->bases, (size_t)b->n_words * 4, hipMemcpyHostToDevice, st));
-    if (rebased) {
-        CW_HIP(hipMemcpyAsync(din + i_soff, rebased->data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
-        *d_off = (const uint64_t*)(din + i_soff);
+    if (!slot.empty()) {
+        CW_HIP(hipMemcpyAsync(din + i_slot, slot.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
+        d_slot = (const uint64_t*)(din + i_slot);
     }
     if (spans) {
         CW_HIP(hipMemcpyAsync(din + i_lo, spans->ref_lo, (size_t)S * 4, hipMemcpyHostToDevice, st));
         CW_HIP(hipMemcpyAsync(din + i_hi, spans->ref_hi, (size_t)S * 4, hipMemcpyHostToDevice, st));
-        dspans->ref_lo = (const uint32_t*)(din + i_lo); dspans->ref_hi = (const uint32_t*)(din + i_hi);
+        dsp.ref_lo = (const uint32_t*)(din + i_lo); dsp.ref_hi = (const uint32_t*)(din + i_hi);
     }
-    *db = *b;
-    db->win_first_seq = (const uint32_t*)(din + i_wfs); db->seq_len = (const uint32_t*)(din + i_len);
-    db->seq_word_off = (const uint64_t*)(din + i_off); db->bases = (const uint32_t*)(din + i_bases);
+    db = *b;
+    db.win_first_seq = (const uint32_t*)(din + i_wfs); db.seq_len = (const uint32_t*)(din + i_len);
+    db.seq_word_off = (const uint64_t*)(din + i_off); db.bases = (const uint32_t*)(din + i_bases);
     return CW_OK;
 }
 
@@ -709,21 +775,15 @@ int run_strand_locked(cw_engine* e, const cw_batch* groups, const cw_strands* ou
     if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
     uint8_t* base = (uint8_t*)e->scratch;
     StrandArgs a;
-    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.b = dev_batch(groups);
     a.n_seqs = groups->n_seqs; a.strand = out->strand; a.hits = out->hits; a.k = out->k ? out->k : CW_STRAND_K;
     a.ctr = (uint32_t*)(base + p.ctr); a.unit_off = (uint32_t*)(base + p.unit_off);
-    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (enqueue_sw_run) */
-    e->n_stages = 0;
-    e->timings_valid = false;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
+    if ((rc = run_begin(e, st, true)) != CW_OK) return rc;
     CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_STR_CTR_WORDS * 4, st));
     stage(e, st, "strand_order", [&] { cw_strand_units_kernel<<<1, 1024, 0, st>>>(a); });
     stage(e, st, "strand", [&] { cw_strand_kernel<0><<<p.wgs, CW_STR_THREADS, 0, st>>>(a); });
     stage(e, st, "strand_wide", [&] { cw_strand_kernel<1><<<p.wgs_wide, CW_STR_THREADS_WIDE, kLdsStrandWide, st>>>(a); });
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
-    return CW_OK;
+    return run_end(e, st);
 }
 
 int validate_seed(const cw_engine* e, const cw_batch* groups, const cw_seeds* out) {
@@ -742,24 +802,18 @@ int run_seed_locked(cw_engine* e, const cw_batch* groups, const cw_seeds* out, v
     if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
     uint8_t* base = (uint8_t*)e->scratch;
     SeedArgs a;
-    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.b = dev_batch(groups);
     a.n_seqs = groups->n_seqs; a.rows = out->rows; a.strand = out->strand; a.k = out->k ? out->k : CW_STRAND_K;
     a.ctr = (uint32_t*)(base + p.ctr); a.unit_off = (uint32_t*)(base + p.unit_off);
     StrandArgs units; /* what cw_strand_units_kernel reads of it: the batch, unit_off and ctr */
     units.b = a.b; units.n_seqs = a.n_seqs; units.strand = nullptr; units.hits = nullptr; units.k = a.k;
     units.ctr = a.ctr; units.unit_off = (uint32_t*)(base + p.unit_off);
-    e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (enqueue_sw_run) */
-    e->n_stages = 0;
-    e->timings_valid = false;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
+    if ((rc = run_begin(e, st, true)) != CW_OK) return rc;
     CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_STR_CTR_WORDS * 4, st));
     stage(e, st, "strand_order", [&] { cw_strand_units_kernel<<<1, 1024, 0, st>>>(units); });
     stage(e, st, "seed", [&] { cw_seed_kernel<0><<<p.wgs, CW_STR_THREADS, 0, st>>>(a); });
     stage(e, st, "seed_wide", [&] { cw_seed_kernel<1><<<p.wgs_wide, CW_SEED_THREADS_WIDE, kLdsSeedWide, st>>>(a); });
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
-    return CW_OK;
+    return run_end(e, st);
 }
 
 /* the body of cw_revcomp_device.  One stage: revcomp.  No scratch: what the engine's scratch holds stays what it was. */
@@ -772,14 +826,26 @@ int run_revcomp_locked(cw_engine* e, const cw_batch* groups, const uint8_t* stra
     a.n_seqs = groups->n_seqs; a.seq_len = groups->seq_len; a.seq_word_off = groups->seq_word_off; a.bases = groups->bases; a.strand = strand; a.out = bases_out;
     const uint32_t per = 256u / CW_RC_LANES; /* sequences a work-group and round */
     const uint32_t wgs = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(((uint64_t)groups->n_seqs + per - 1u) / per, (uint64_t)e->cus * 32u));
-    e->n_stages = 0;
-    e->timings_valid = false;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
+    if ((rc = run_begin(e, st, false)) != CW_OK) return rc;
     stage(e, st, "revcomp", [&] { cw_revcomp_kernel<<<wgs, 256, 0, st>>>(a); });
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
-    return CW_OK;
+    return run_end(e, st);
+}
+
+/* the body of cw_seed_spans_device; the caller holds e->mu.  One stage: seed_spans.  No scratch, as the reverse complement. */
+int run_seed_spans_locked(cw_engine* e, const cw_batch* groups, const int32_t* seed_rows, uint32_t min_hits, uint32_t pad, uint32_t pad_shift, uint32_t* ref_lo, uint32_t* ref_hi,
+                          void* hip_stream) {
+    if (!e || !groups || pad_shift > 31u) return CW_E_INVALID;
+    int rc = validate_groups(e, groups, seed_rows);
+    if (rc || groups->n_seqs == 0) return rc;
+    if (!ref_lo || !ref_hi) return CW_E_INVALID;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    SeedSpanArgs a;
+    a.b = dev_batch(groups);
+    a.n_seqs = groups->n_seqs; a.rows = seed_rows; a.min_hits = min_hits; a.pad = pad; a.pad_shift = pad_shift; a.ref_lo = ref_lo; a.ref_hi = ref_hi;
+    if ((rc = run_begin(e, st, false)) != CW_OK) return rc;
+    stage(e, st, "seed_spans", [&] { cw_seed_spans_kernel<<<(a.n_seqs + 255u) / 256u, 256, 0, st>>>(a); });
+    return run_end(e, st);
 }
 
 } // namespace
@@ -866,23 +932,17 @@ void cw_destroy(cw_engine* e) {
 }
 
 int cw_run_device(cw_engine* e, const cw_batch* batch, const cw_result* res, void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_device_locked(e, batch, res, hip_stream);
+    return locked(e, [&] { return run_device_locked(e, batch, res, hip_stream); });
 }
 
 int cw_poa_run_device(cw_engine* e, const cw_batch* groups, const cw_result* res, void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return poa_device_locked(e, groups, res, hip_stream);
+    return locked(e, [&] { return poa_device_locked(e, groups, res, hip_stream); });
 }
 
 /* Host buffers in, host buffers out, synchronous: the batch and the slot offsets go up, cw_poa_run_device on the engine's stream, lengths, statuses and the
-   slots come back, and every consensus is copied into the caller's slot -- its own bytes only.  The engine's mutex is held throughout: the two device
-   buffers are the engine's. */
-int cw_poa_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
+   slots come back, and every consensus is copied into the caller's slot -- its own bytes only.  The caller holds e->mu throughout: the two device buffers are
+   the engine's.  Its checks and its upload are its own; the layout, the hold step and the lock are the other host forms'. */
+static int poa_run_host(cw_engine* e, const cw_batch* b, const cw_result* r) {
     int rc = validate_poa(e, b, r);
     if (rc || b->n_windows == 0) return rc;
     const uint32_t G = b->n_windows, S = b->n_seqs;
@@ -891,21 +951,15 @@ int cw_poa_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
     for (uint32_t s = 0; s < S; ++s)
         if (b->seq_word_off[s] + ((uint64_t)b->seq_len[s] + 15) / 16 > b->n_words || b->seq_len[s] > 65535u) return CW_E_INVALID;
     const uint64_t c0 = r->cons_off[0], cons_bytes = r->cons_off[G] - c0;
-    size_t o = 0;
-    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t i_wfs = put((size_t)(G + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4),
-                 i_coff = put((size_t)(G + 1) * 8);
-    const size_t in_bytes = o;
-    o = 0;
-    const size_t o_cons = put(cons_bytes), o_clen = put((size_t)G * 4), o_stat = put(G);
-    const size_t out_bytes = o;
+    Layout in, out;
+    const size_t i_wfs = in.put((size_t)(G + 1) * 4), i_len = in.put((size_t)S * 4), i_off = in.put((size_t)S * 8), i_bases = in.put((size_t)(b->n_words + 1) * 4),
+                 i_coff = in.put((size_t)(G + 1) * 8);
+    const size_t o_cons = out.put(cons_bytes), o_clen = out.put((size_t)G * 4), o_stat = out.put(G);
     std::vector<uint8_t> back;
     std::vector<uint64_t> coff; /* the slots' offsets in the device copy, which begins at the first slot */
-    try { back.resize(out_bytes); coff.resize((size_t)G + 1); } catch (...) { return CW_E_NOMEM; }
+    try { back.resize(out.bytes); coff.resize((size_t)G + 1); } catch (...) { return CW_E_NOMEM; }
     for (uint32_t g = 0; g <= G; ++g) coff[g] = r->cons_off[g] - c0;
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_in, &e->poa_in_bytes, in_bytes)) != CW_OK) return rc;
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
+    if ((rc = hold_io(e, in.bytes, out.bytes)) != CW_OK) return rc;
     uint8_t *din = (uint8_t*)e->poa_in, *dout = (uint8_t*)e->poa_out;
     hipStream_t st = e->stream;
     CW_HIP(hipMemcpyAsync(din + i_wfs, b->win_first_seq, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
@@ -922,7 +976,7 @@ int cw_poa_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
     dr.cons_off = (const uint64_t*)(din + i_coff); dr.cons_len = (uint32_t*)(dout + o_clen); dr.win_status = dout + o_stat;
     dr.solid = nullptr; dr.solid_off = nullptr; dr.solid_len = nullptr;
     if ((rc = poa_device_locked(e, &db, &dr, st)) != CW_OK) return rc;
-    CW_HIP(hipMemcpyAsync(back.data(), dout, out_bytes, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipMemcpyAsync(back.data(), dout, out.bytes, hipMemcpyDeviceToHost, st));
     CW_HIP(hipStreamSynchronize(st));
     const uint32_t* clen = (const uint32_t*)(back.data() + o_clen);
     for (uint32_t g = 0; g < G; ++g) {
@@ -935,39 +989,34 @@ int cw_poa_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
     return rc;
 }
 
+int cw_poa_run(cw_engine* e, const cw_batch* b, const cw_result* r) {
+    return locked(e, [&] { return poa_run_host(e, b, r); });
+}
+
 int cw_sw_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, uint32_t flags, void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_sw_locked(e, groups, rows, flags, hip_stream);
+    return locked(e, [&] { return run_sw_locked(e, groups, rows, flags, hip_stream); });
 }
 
 int cw_sw_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_spans* spans, uint32_t flags, void* hip_stream) {
-    if (!e || !spans) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_sw_locked(e, groups, rows, flags, hip_stream, spans);
+    return spans ? locked(e, [&] { return run_sw_locked(e, groups, rows, flags, hip_stream, spans); }) : CW_E_INVALID;
 }
 
-/* Host buffers in, host buffers out, synchronous: the batch goes up (upload_groups), cw_sw_run_device on the engine's stream, the rows come back.  The engine's
-   mutex is held throughout: the device buffers are the engine's.  One body for cw_sw_run and cw_sw_span_run, as for the three pairs of host forms below: a span
-   run's two arrays go up with the batch. */
+/* The host forms (HostTrip, above): each states its validation, its slot offsets, its outputs, what else goes up, its device form and what of the caller's
+   bytes it writes on the way back.  One body for cw_sw_run and cw_sw_span_run, as for the three pairs below: a span run's two arrays go up with the batch.
+   This one: the rows come back. */
 static int sw_run_host(cw_engine* e, const cw_batch* b, int32_t* rows, uint32_t flags, const cw_sw_spans* spans) {
     if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
+    HostTrip t(e, b, spans);
     int rc = validate_sw(e, b, rows, flags);
     if (!rc) rc = validate_spans(spans, b->n_seqs);
     if (rc || b->n_seqs == 0) return rc;
-    cw_sw_spans dsp;
+    if ((rc = t.check_groups(nullptr)) != CW_OK) return rc;
     const uint32_t S = b->n_seqs;
-    cw_batch db;
-    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
-    const size_t out_bytes = (size_t)S * CW_SW_ROW * 4;
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, nullptr, &db, nullptr, spans, &dsp)) != CW_OK) return rc;
-    hipStream_t st = e->stream;
-    if ((rc = run_sw_locked(e, &db, (int32_t*)e->poa_out, flags, st, spans ? &dsp : nullptr)) != CW_OK) return rc;
-    CW_HIP(hipMemcpyAsync(rows, e->poa_out, out_bytes, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipStreamSynchronize(st));
+    const size_t row_bytes = (size_t)S * CW_SW_ROW * 4, o_rows = t.out.put(row_bytes);
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
+    if ((rc = run_sw_locked(e, &t.db, t.at<int32_t>(o_rows), flags, t.st, t.dev_spans())) != CW_OK) return rc;
+    CW_HIP(t.down(rows, o_rows, row_bytes));
+    CW_HIP(t.sync());
     return sw_rows_rc(rows, S);
 }
 
@@ -975,48 +1024,35 @@ int cw_sw_run(cw_engine* e, const cw_batch* b, int32_t* rows, uint32_t flags) { 
 int cw_sw_span_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_spans* spans, uint32_t flags) { return spans ? sw_run_host(e, b, rows, flags, spans) : CW_E_INVALID; }
 
 int cw_sw_path_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_sw_path_locked(e, groups, rows, paths, flags, hip_stream);
+    return locked(e, [&] { return run_sw_path_locked(e, groups, rows, paths, flags, hip_stream); });
 }
 
 int cw_sw_path_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_paths* paths, const cw_sw_spans* spans, uint32_t flags, void* hip_stream) {
-    if (!e || !spans) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_sw_path_locked(e, groups, rows, paths, flags, hip_stream, spans);
+    return spans ? locked(e, [&] { return run_sw_path_locked(e, groups, rows, paths, flags, hip_stream, spans); }) : CW_E_INVALID;
 }
 
-/* Host buffers in, host buffers out, synchronous, as cw_sw_run: the batch and the slots' offsets go up, cw_sw_path_run_device on the engine's stream, rows and
-   op counts come back -- and of the ops only what was written: a slot's words beyond its path, and every slot without one, stay the caller's. */
+/* Rows and op counts come back -- and of the ops only what was written: a slot's words beyond its path, and every slot without one, stay the caller's. */
 static int sw_path_run_host(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_paths* paths, uint32_t flags, const cw_sw_spans* spans) {
     if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
+    HostTrip t(e, b, spans);
     int rc = validate_sw_path(e, b, rows, paths, flags);
     if (!rc) rc = validate_spans(spans, b->n_seqs);
     if (rc || b->n_seqs == 0) return rc;
-    cw_sw_spans dsp;
+    if ((rc = t.check_groups(paths->ops_off)) != CW_OK) return rc;
     const uint32_t S = b->n_seqs;
-    cw_batch db;
-    std::vector<uint64_t> poff;
-    cw_sw_paths dp;
-    if ((rc = check_groups(b, paths->ops_off, &poff)) != CW_OK) return rc;
-    const uint64_t n_slots = poff[S];
-    size_t o = 0;
-    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t o_rows = put((size_t)S * CW_SW_ROW * 4), o_nops = put((size_t)S * 4), o_ops = put((size_t)n_slots * 4);
+    const std::vector<uint64_t>& poff = t.slot;
+    const size_t row_bytes = (size_t)S * CW_SW_ROW * 4, op_bytes = (size_t)poff[S] * 4;
+    const size_t o_rows = t.out.put(row_bytes), o_nops = t.out.put((size_t)S * 4), o_ops = t.out.put(op_bytes);
     std::vector<uint32_t> back;
-    try { back.resize((size_t)n_slots); } catch (...) { return CW_E_NOMEM; }
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, o)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, &poff, &db, &dp.ops_off, spans, &dsp)) != CW_OK) return rc;
-    uint8_t* dout = (uint8_t*)e->poa_out;
-    hipStream_t st = e->stream;
-    dp.ops = (uint32_t*)(dout + o_ops); dp.n_ops = (uint32_t*)(dout + o_nops);
-    if ((rc = run_sw_path_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st, spans ? &dsp : nullptr)) != CW_OK) return rc;
-    CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipMemcpyAsync(paths->n_ops, dout + o_nops, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-    if (n_slots) CW_HIP(hipMemcpyAsync(back.data(), dout + o_ops, (size_t)n_slots * 4, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipStreamSynchronize(st));
+    try { back.resize((size_t)poff[S]); } catch (...) { return CW_E_NOMEM; }
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
+    cw_sw_paths dp;
+    dp.ops = t.at<uint32_t>(o_ops); dp.ops_off = t.d_slot; dp.n_ops = t.at<uint32_t>(o_nops);
+    if ((rc = run_sw_path_locked(e, &t.db, t.at<int32_t>(o_rows), &dp, flags, t.st, t.dev_spans())) != CW_OK) return rc;
+    CW_HIP(t.down(rows, o_rows, row_bytes));
+    CW_HIP(t.down(paths->n_ops, o_nops, (size_t)S * 4));
+    CW_HIP(t.down(back.data(), o_ops, op_bytes));
+    CW_HIP(t.sync());
     for (uint32_t s = 0; s < S; ++s)
         if (rows[(size_t)s * CW_SW_ROW + CW_SW_STATUS] == CW_SW_ALIGNED && paths->n_ops[s] && paths->n_ops[s] <= poff[s + 1] - poff[s])
             memcpy(paths->ops + paths->ops_off[s], back.data() + poff[s], (size_t)paths->n_ops[s] * 4);
@@ -1029,58 +1065,44 @@ int cw_sw_path_span_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw
 }
 
 int cw_pileup_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, uint32_t flags, void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_pileup_locked(e, groups, rows, pile, flags, hip_stream);
+    return locked(e, [&] { return run_pileup_locked(e, groups, rows, pile, flags, hip_stream); });
 }
 
 int cw_pileup_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_pileup* pile, const cw_sw_spans* spans, uint32_t flags, void* hip_stream) {
-    if (!e || !spans) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_pileup_locked(e, groups, rows, pile, flags, hip_stream, spans);
+    return spans ? locked(e, [&] { return run_pileup_locked(e, groups, rows, pile, flags, hip_stream, spans); }) : CW_E_INVALID;
 }
 
-/* Host buffers in, host buffers out, synchronous, as cw_sw_path_run: the batch and the slots' offsets go up -- the caller's counts too, but only under
-   CW_PILE_ACCUMULATE -- cw_pileup_run_device on the engine's stream, the rows come back, and of the counts what a run owns: columns 0 .. ref_len - 1 of every
+/* The caller's counts go up too, but only under CW_PILE_ACCUMULATE; the rows come back, and of the counts what a run owns: columns 0 .. ref_len - 1 of every
    reference whose slot holds them.  A slot's words beyond those, a slot that is too short and every query's slot stay the caller's. */
 static int pileup_run_host(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_pileup* pile, uint32_t flags, const cw_sw_spans* spans) {
     if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
+    HostTrip t(e, b, spans);
     int rc = validate_pileup(e, b, rows, pile, flags);
     if (!rc) rc = validate_spans(spans, b->n_seqs);
     if (rc || b->n_seqs == 0) return rc;
-    cw_sw_spans dsp;
+    if ((rc = t.check_groups(pile->col_off)) != CW_OK) return rc;
     const uint32_t G = b->n_windows, S = b->n_seqs;
-    cw_batch db;
-    std::vector<uint64_t> coff;
-    cw_pileup dp;
-    if ((rc = check_groups(b, pile->col_off, &coff)) != CW_OK) return rc;
-    const uint64_t c0 = pile->col_off[0], n_cols = coff[S];
-    const size_t col_bytes = (size_t)CW_PILE_COL * 4;
-    size_t o = 0;
-    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t o_rows = put((size_t)S * CW_SW_ROW * 4), o_counts = put((size_t)n_cols * col_bytes);
+    const std::vector<uint64_t>& coff = t.slot;
+    const size_t col_bytes = (size_t)CW_PILE_COL * 4, row_bytes = (size_t)S * CW_SW_ROW * 4, count_bytes = (size_t)coff[S] * col_bytes;
+    const size_t o_rows = t.out.put(row_bytes), o_counts = t.out.put(count_bytes);
     std::vector<uint32_t> back;
     std::vector<std::pair<uint32_t, uint32_t>> owned; /* the references whose columns the run owns: (sequence, columns) */
     try {
-        back.resize((size_t)n_cols * CW_PILE_COL);
+        back.resize((size_t)coff[S] * CW_PILE_COL);
         for (uint32_t g = 0; g < G; ++g) {
             const uint32_t r = b->win_first_seq[g];
             if (r < b->win_first_seq[g + 1] && b->seq_len[r] && coff[r + 1] - coff[r] >= b->seq_len[r]) owned.emplace_back(r, b->seq_len[r]);
         }
     } catch (...) { return CW_E_NOMEM; }
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, o)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, &coff, &db, &dp.col_off, spans, &dsp)) != CW_OK) return rc;
-    uint8_t* dout = (uint8_t*)e->poa_out;
-    hipStream_t st = e->stream;
-    dp.counts = (uint32_t*)(dout + o_counts);
-    if ((flags & CW_PILE_ACCUMULATE) && n_cols) /* every slot in one copy; the run reads and writes the owned columns only */
-        CW_HIP(hipMemcpyAsync(dp.counts, pile->counts + c0 * CW_PILE_COL, (size_t)n_cols * col_bytes, hipMemcpyHostToDevice, st));
-    if ((rc = run_pileup_locked(e, &db, (int32_t*)(dout + o_rows), &dp, flags, st, spans ? &dsp : nullptr)) != CW_OK) return rc;
-    CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
-    if (n_cols) CW_HIP(hipMemcpyAsync(back.data(), dp.counts, (size_t)n_cols * col_bytes, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipStreamSynchronize(st));
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
+    cw_pileup dp;
+    dp.counts = t.at<uint32_t>(o_counts); dp.col_off = t.d_slot;
+    if (flags & CW_PILE_ACCUMULATE) /* every slot in one copy; the run reads and writes the owned columns only */
+        CW_HIP(t.up(o_counts, pile->counts + pile->col_off[0] * CW_PILE_COL, count_bytes));
+    if ((rc = run_pileup_locked(e, &t.db, t.at<int32_t>(o_rows), &dp, flags, t.st, t.dev_spans())) != CW_OK) return rc;
+    CW_HIP(t.down(rows, o_rows, row_bytes));
+    CW_HIP(t.down(back.data(), o_counts, count_bytes));
+    CW_HIP(t.sync());
     for (const auto& rn : owned)
         memcpy(pile->counts + pile->col_off[rn.first] * CW_PILE_COL, back.data() + coff[rn.first] * CW_PILE_COL, (size_t)rn.second * col_bytes);
     return sw_rows_rc(rows, S);
@@ -1092,40 +1114,30 @@ int cw_pileup_span_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_
 }
 
 int cw_sw_cut_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_sw_cut_locked(e, groups, rows, cuts, hip_stream);
+    return locked(e, [&] { return run_sw_cut_locked(e, groups, rows, cuts, hip_stream); });
 }
 
 int cw_sw_cut_span_run_device(cw_engine* e, const cw_batch* groups, int32_t* rows, const cw_sw_cuts* cuts, const cw_sw_spans* spans, void* hip_stream) {
-    if (!e || !spans) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_sw_cut_locked(e, groups, rows, cuts, hip_stream, spans);
+    return spans ? locked(e, [&] { return run_sw_cut_locked(e, groups, rows, cuts, hip_stream, spans); }) : CW_E_INVALID;
 }
 
-/* Host buffers in, host buffers out, synchronous, as cw_pileup_run: the batch and the slots' offsets go up, cw_sw_cut_run_device on the engine's stream, the
-   rows come back, and of the slots what a run owns: the T + 1 words of every query whose slot holds them.  A slot's words beyond those, a slot that is too
+/* The rows come back, and of the slots what a run owns: the T + 1 words of every query whose slot holds them.  A slot's words beyond those, a slot that is too
    short and every reference's slot stay the caller's. */
 static int sw_cut_run_host(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cuts* cuts, const cw_sw_spans* spans) {
     if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
+    HostTrip t(e, b, spans);
     int rc = validate_sw_cut(e, b, rows, cuts);
     if (!rc) rc = validate_spans(spans, b->n_seqs);
     if (rc || b->n_seqs == 0) return rc;
-    cw_sw_spans dsp;
+    if ((rc = t.check_groups(cuts->cut_off)) != CW_OK) return rc;
     const uint32_t G = b->n_windows, S = b->n_seqs, W = cuts->window;
-    cw_batch db;
-    std::vector<uint64_t> coff;
-    cw_sw_cuts dc;
-    if ((rc = check_groups(b, cuts->cut_off, &coff)) != CW_OK) return rc;
-    const uint64_t n_slots = coff[S];
-    size_t o = 0;
-    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t o_rows = put((size_t)S * CW_SW_ROW * 4), o_cuts = put((size_t)n_slots * 4);
+    const std::vector<uint64_t>& coff = t.slot;
+    const size_t row_bytes = (size_t)S * CW_SW_ROW * 4, cut_bytes = (size_t)coff[S] * 4;
+    const size_t o_rows = t.out.put(row_bytes), o_cuts = t.out.put(cut_bytes);
     std::vector<uint32_t> back;
     std::vector<std::pair<uint32_t, uint32_t>> owned; /* the queries whose words the run owns: (sequence, words) */
     try {
-        back.resize((size_t)n_slots);
+        back.resize((size_t)coff[S]);
         for (uint32_t g = 0; g < G; ++g) {
             const uint32_t r = b->win_first_seq[g], end = b->win_first_seq[g + 1];
             if (r >= end) continue;
@@ -1133,16 +1145,13 @@ static int sw_cut_run_host(cw_engine* e, const cw_batch* b, int32_t* rows, const
             for (uint32_t s = r + 1; s < end; ++s) if (coff[s + 1] - coff[s] >= words) owned.emplace_back(s, words);
         }
     } catch (...) { return CW_E_NOMEM; }
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, o)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, &coff, &db, &dc.cut_off, spans, &dsp)) != CW_OK) return rc;
-    uint8_t* dout = (uint8_t*)e->poa_out;
-    hipStream_t st = e->stream;
-    dc.cuts = (uint32_t*)(dout + o_cuts); dc.window = W;
-    if ((rc = run_sw_cut_locked(e, &db, (int32_t*)(dout + o_rows), &dc, st, spans ? &dsp : nullptr)) != CW_OK) return rc;
-    CW_HIP(hipMemcpyAsync(rows, dout + o_rows, (size_t)S * CW_SW_ROW * 4, hipMemcpyDeviceToHost, st));
-    if (n_slots) CW_HIP(hipMemcpyAsync(back.data(), dc.cuts, (size_t)n_slots * 4, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipStreamSynchronize(st));
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
+    cw_sw_cuts dc;
+    dc.cuts = t.at<uint32_t>(o_cuts); dc.cut_off = t.d_slot; dc.window = W;
+    if ((rc = run_sw_cut_locked(e, &t.db, t.at<int32_t>(o_rows), &dc, t.st, t.dev_spans())) != CW_OK) return rc;
+    CW_HIP(t.down(rows, o_rows, row_bytes));
+    CW_HIP(t.down(back.data(), o_cuts, cut_bytes));
+    CW_HIP(t.sync());
     for (const auto& sw : owned)
         if (rows[(size_t)sw.first * CW_SW_ROW + CW_SW_STATUS] != CW_SW_CUT_SLOT)
             memcpy(cuts->cuts + cuts->cut_off[sw.first], back.data() + coff[sw.first], (size_t)sw.second * 4);
@@ -1153,148 +1162,96 @@ int cw_sw_cut_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cu
 int cw_sw_cut_span_run(cw_engine* e, const cw_batch* b, int32_t* rows, const cw_sw_cuts* cuts, const cw_sw_spans* spans) { return spans ? sw_cut_run_host(e, b, rows, cuts, spans) : CW_E_INVALID; }
 
 int cw_strand_run_device(cw_engine* e, const cw_batch* groups, const cw_strands* out, void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_strand_locked(e, groups, out, hip_stream);
+    return locked(e, [&] { return run_strand_locked(e, groups, out, hip_stream); });
 }
 
-/* Host buffers in, host buffers out, synchronous, as cw_sw_run: the batch goes up, cw_strand_run_device on the engine's stream, the strand bytes and -- when asked
-   for -- the hits come back. */
+/* The strand bytes and -- when asked for -- the hits come back. */
 int cw_strand_run(cw_engine* e, const cw_batch* b, const cw_strands* out) {
     if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
+    HostTrip t(e, b);
     int rc = validate_strand(e, b, out);
     if (rc || b->n_seqs == 0) return rc;
+    if ((rc = t.check_groups(nullptr)) != CW_OK) return rc;
     const uint32_t S = b->n_seqs;
-    cw_batch db;
-    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
-    const size_t o_hits = align_up((size_t)S, 256), out_bytes = o_hits + (out->hits ? (size_t)S * 8 : 0);
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
-    hipStream_t st = e->stream;
-    uint8_t* dout = (uint8_t*)e->poa_out;
+    const size_t o_strand = t.out.put(S), o_hits = t.out.put(out->hits ? (size_t)S * 8 : 0);
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
     cw_strands ds;
-    ds.strand = dout; ds.hits = out->hits ? (uint32_t*)(dout + o_hits) : nullptr; ds.k = out->k;
-    if ((rc = run_strand_locked(e, &db, &ds, st)) != CW_OK) return rc;
-    CW_HIP(hipMemcpyAsync(out->strand, ds.strand, (size_t)S, hipMemcpyDeviceToHost, st));
-    if (out->hits) CW_HIP(hipMemcpyAsync(out->hits, ds.hits, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipStreamSynchronize(st));
+    ds.strand = t.at<uint8_t>(o_strand); ds.hits = out->hits ? t.at<uint32_t>(o_hits) : nullptr; ds.k = out->k;
+    if ((rc = run_strand_locked(e, &t.db, &ds, t.st)) != CW_OK) return rc;
+    CW_HIP(t.down(out->strand, o_strand, S));
+    if (out->hits) CW_HIP(t.down(out->hits, o_hits, (size_t)S * 8));
+    CW_HIP(t.sync());
     return CW_OK;
 }
 
 int cw_seed_run_device(cw_engine* e, const cw_batch* groups, const cw_seeds* out, void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_seed_locked(e, groups, out, hip_stream);
+    return locked(e, [&] { return run_seed_locked(e, groups, out, hip_stream); });
 }
 
-/* Host buffers in, host buffers out, synchronous, as cw_strand_run: the batch goes up, cw_seed_run_device on the engine's stream, the rows and -- when asked
-   for -- the strand bytes come back. */
+/* The rows and -- when asked for -- the strand bytes come back. */
 int cw_seed_run(cw_engine* e, const cw_batch* b, const cw_seeds* out) {
     if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
+    HostTrip t(e, b);
     int rc = validate_seed(e, b, out);
     if (rc || b->n_seqs == 0) return rc;
+    if ((rc = t.check_groups(nullptr)) != CW_OK) return rc;
     const uint32_t S = b->n_seqs;
-    cw_batch db;
-    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
-    const size_t row_bytes = (size_t)S * CW_SEED_ROW * 4, o_strand = align_up(row_bytes, 256), out_bytes = o_strand + (out->strand ? (size_t)S : 0);
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
-    hipStream_t st = e->stream;
-    uint8_t* dout = (uint8_t*)e->poa_out;
+    const size_t row_bytes = (size_t)S * CW_SEED_ROW * 4, o_rows = t.out.put(row_bytes), o_strand = t.out.put(out->strand ? (size_t)S : 0);
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
     cw_seeds ds;
-    ds.rows = (int32_t*)dout; ds.strand = out->strand ? dout + o_strand : nullptr; ds.k = out->k;
-    if ((rc = run_seed_locked(e, &db, &ds, st)) != CW_OK) return rc;
-    CW_HIP(hipMemcpyAsync(out->rows, ds.rows, row_bytes, hipMemcpyDeviceToHost, st));
-    if (out->strand) CW_HIP(hipMemcpyAsync(out->strand, ds.strand, (size_t)S, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipStreamSynchronize(st));
-    return CW_OK;
-}
-
-/* the body of cw_seed_spans_device; the caller holds e->mu.  One stage: seed_spans.  No scratch, as the reverse complement. */
-static int run_seed_spans_locked(cw_engine* e, const cw_batch* groups, const int32_t* seed_rows, uint32_t min_hits, uint32_t pad, uint32_t pad_shift, uint32_t* ref_lo, uint32_t* ref_hi,
-                          void* hip_stream) {
-    if (!e || !groups || pad_shift > 31u) return CW_E_INVALID;
-    int rc = validate_groups(e, groups, seed_rows);
-    if (rc || groups->n_seqs == 0) return rc;
-    if (!ref_lo || !ref_hi) return CW_E_INVALID;
-    CW_HIP(hipSetDevice(e->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
-    SeedSpanArgs a;
-    a.b.n_windows = groups->n_windows; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
-    a.n_seqs = groups->n_seqs; a.rows = seed_rows; a.min_hits = min_hits; a.pad = pad; a.pad_shift = pad_shift; a.ref_lo = ref_lo; a.ref_hi = ref_hi;
-    e->n_stages = 0;
-    e->timings_valid = false;
-    CW_HIP(hipEventRecord(e->ev_begin, st));
-    stage(e, st, "seed_spans", [&] { cw_seed_spans_kernel<<<(a.n_seqs + 255u) / 256u, 256, 0, st>>>(a); });
-    CW_HIP(hipEventRecord(e->ev_end, st));
-    CW_HIP(hipGetLastError());
-    e->timings_valid = true;
+    ds.rows = t.at<int32_t>(o_rows); ds.strand = out->strand ? t.at<uint8_t>(o_strand) : nullptr; ds.k = out->k;
+    if ((rc = run_seed_locked(e, &t.db, &ds, t.st)) != CW_OK) return rc;
+    CW_HIP(t.down(out->rows, o_rows, row_bytes));
+    if (out->strand) CW_HIP(t.down(out->strand, o_strand, S));
+    CW_HIP(t.sync());
     return CW_OK;
 }
 
 int cw_seed_spans_device(cw_engine* e, const cw_batch* groups, const int32_t* seed_rows, uint32_t min_hits, uint32_t pad, uint32_t pad_shift, uint32_t* ref_lo, uint32_t* ref_hi,
                          void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_seed_spans_locked(e, groups, seed_rows, min_hits, pad, pad_shift, ref_lo, ref_hi, hip_stream);
+    return locked(e, [&] { return run_seed_spans_locked(e, groups, seed_rows, min_hits, pad, pad_shift, ref_lo, ref_hi, hip_stream); });
 }
 
-/* Host buffers in, host buffers out, synchronous: the batch and the seed rows go up, cw_seed_spans_device on the engine's stream, the two arrays come back. */
+/* The seed rows go up with the batch; the two arrays come back. */
 int cw_seed_spans(cw_engine* e, const cw_batch* b, const int32_t* seed_rows, uint32_t min_hits, uint32_t pad, uint32_t pad_shift, uint32_t* ref_lo, uint32_t* ref_hi) {
     if (!e || !b || pad_shift > 31u) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
+    HostTrip t(e, b);
     int rc = validate_groups(e, b, seed_rows);
     if (rc || b->n_seqs == 0) return rc;
     if (!ref_lo || !ref_hi) return CW_E_INVALID;
+    if ((rc = t.check_groups(nullptr)) != CW_OK) return rc;
     const uint32_t S = b->n_seqs;
-    cw_batch db;
-    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
-    const size_t row_bytes = (size_t)S * CW_SEED_ROW * 4, o_lo = align_up(row_bytes, 256), o_hi = o_lo + align_up((size_t)S * 4, 256), out_bytes = o_hi + (size_t)S * 4;
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
-    hipStream_t st = e->stream;
-    uint8_t* dout = (uint8_t*)e->poa_out;
-    CW_HIP(hipMemcpyAsync(dout, seed_rows, row_bytes, hipMemcpyHostToDevice, st));
-    if ((rc = run_seed_spans_locked(e, &db, (const int32_t*)dout, min_hits, pad, pad_shift, (uint32_t*)(dout + o_lo), (uint32_t*)(dout + o_hi), st)) != CW_OK) return rc;
-    CW_HIP(hipMemcpyAsync(ref_lo, dout + o_lo, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipMemcpyAsync(ref_hi, dout + o_hi, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipStreamSynchronize(st));
+    const size_t row_bytes = (size_t)S * CW_SEED_ROW * 4, o_rows = t.out.put(row_bytes), o_lo = t.out.put((size_t)S * 4), o_hi = t.out.put((size_t)S * 4);
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
+    CW_HIP(t.up(o_rows, seed_rows, row_bytes));
+    if ((rc = run_seed_spans_locked(e, &t.db, t.at<int32_t>(o_rows), min_hits, pad, pad_shift, t.at<uint32_t>(o_lo), t.at<uint32_t>(o_hi), t.st)) != CW_OK) return rc;
+    CW_HIP(t.down(ref_lo, o_lo, (size_t)S * 4));
+    CW_HIP(t.down(ref_hi, o_hi, (size_t)S * 4));
+    CW_HIP(t.sync());
     return CW_OK;
 }
 
 int cw_revcomp_device(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint32_t* bases_out, void* hip_stream) {
-    if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return run_revcomp_locked(e, groups, strand, bases_out, hip_stream);
+    return locked(e, [&] { return run_revcomp_locked(e, groups, strand, bases_out, hip_stream); });
 }
 
-/* Host buffers in, host buffers out, synchronous: the batch and the strand bytes go up, cw_revcomp_device on the engine's stream, and of the words that come back
-   every sequence's own are copied to bases_out: a word that belongs to no sequence is not written on the host either. */
+/* The strand bytes go up with the batch; of the words that come back every sequence's own are copied to bases_out: a word that belongs to no sequence is not
+   written on the host either. */
 int cw_revcomp(cw_engine* e, const cw_batch* b, const uint8_t* strand, uint32_t* bases_out) {
     if (!e) return CW_E_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
+    HostTrip t(e, b);
     int rc = validate_revcomp(e, b, bases_out);
     if (rc || b->n_seqs == 0) return rc;
+    if ((rc = t.check_groups(nullptr)) != CW_OK) return rc;
     const uint32_t S = b->n_seqs;
-    cw_batch db;
-    if ((rc = check_groups(b, nullptr, nullptr)) != CW_OK) return rc;
-    const size_t o_strand = align_up((size_t)(b->n_words + 1) * 4, 256), out_bytes = o_strand + (size_t)S;
+    const size_t o_words = t.out.put((size_t)(b->n_words + 1) * 4), o_strand = t.out.put(S);
     std::vector<uint32_t> back;
     try { back.resize((size_t)b->n_words + 1); } catch (...) { return CW_E_NOMEM; }
-    CW_HIP(hipSetDevice(e->device));
-    if ((rc = ensure(&e->poa_out, &e->poa_out_bytes, out_bytes)) != CW_OK) return rc;
-    if ((rc = upload_groups(e, b, nullptr, &db, nullptr)) != CW_OK) return rc;
-    hipStream_t st = e->stream;
-    uint8_t* dout = (uint8_t*)e->poa_out;
-    if (strand) CW_HIP(hipMemcpyAsync(dout + o_strand, strand, (size_t)S, hipMemcpyHostToDevice, st));
-    if ((rc = run_revcomp_locked(e, &db, strand ? dout + o_strand : nullptr, (uint32_t*)dout, st)) != CW_OK) return rc;
-    if (b->n_words) CW_HIP(hipMemcpyAsync(back.data(), dout, (size_t)b->n_words * 4, hipMemcpyDeviceToHost, st));
-    CW_HIP(hipStreamSynchronize(st));
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
+    if (strand) CW_HIP(t.up(o_strand, strand, S));
+    if ((rc = run_revcomp_locked(e, &t.db, strand ? t.at<uint8_t>(o_strand) : nullptr, t.at<uint32_t>(o_words), t.st)) != CW_OK) return rc;
+    CW_HIP(t.down(back.data(), o_words, (size_t)b->n_words * 4));
+    CW_HIP(t.sync());
     for (uint32_t s = 0; s < S; ++s) {
         const size_t nw = ((size_t)b->seq_len[s] + 15) / 16;
         if (nw) memcpy(bases_out + b->seq_word_off[s], back.data() + b->seq_word_off[s], nw * 4);
@@ -1342,16 +1299,15 @@ int cw_cut_groups_device(cw_engine* e, const cw_batch* groups, const int32_t* ro
     const uint32_t G = groups->n_windows;
     const uint64_t most = 16ull * groups->n_words / cuts->window + G;
     if (most > 0x7FFFFFFFull) return CW_E_INVALID;
-    size_t o = 0;
-    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t o_grp = put((size_t)(G + 1) * 4), o_ws = put((size_t)(most + 1) * 4), o_ww = put((size_t)(most + 1) * 8), o_st = put(32);
-    int rc = ensure(&e->scratch, &e->scratch_bytes, o);
+    Layout work;
+    const size_t o_grp = work.put((size_t)(G + 1) * 4), o_ws = work.put((size_t)(most + 1) * 4), o_ww = work.put((size_t)(most + 1) * 8), o_st = work.put(32);
+    int rc = ensure(&e->scratch, &e->scratch_bytes, work.bytes);
     if (rc) return rc;
     e->last_windows = 0; /* the scratch no longer holds a window or POA run's records (run_sw_locked) */
     uint8_t* base = (uint8_t*)e->scratch;
     CW_HIP(hipMemsetAsync(base + o_st, 0, 32, st));
     CutGroupArgs a;
-    a.b.n_windows = G; a.b.win_first_seq = groups->win_first_seq; a.b.seq_len = groups->seq_len; a.b.seq_word_off = groups->seq_word_off; a.b.bases = groups->bases;
+    a.b = dev_batch(groups);
     a.rows = rows; a.cuts = cuts->cuts; a.cut_off = cuts->cut_off; a.window = cuts->window; a.out_cap = (uint32_t)most;
     a.grp = (uint32_t*)(base + o_grp); a.win_seqs = (uint32_t*)(base + o_ws); a.win_words = (uint64_t*)(base + o_ww);
     a.grp_first = grp_first; a.win_first_seq = win_first_seq; a.seq_len = seq_len; a.seq_word_off = seq_word_off; a.bases = bases;
@@ -1685,11 +1641,10 @@ int cw_extract_impl(cw_engine* e, const cw_read_set* reads, const cw_overlap* ov
         if ((uint64_t)hj[w].ovl_first + hj[w].ovl_count > n_overlaps || hj[w].tpl_read >= reads->n_reads || hj[w].q_end < hj[w].q_beg) return CW_E_INVALID;
         doff[w + 1] = doff[w] + hj[w].ovl_count;
     }
-    size_t o = 0;
-    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t o_desc = put((size_t)doff[n_jobs] * sizeof(ExtractDesc) + 16), o_doff = put((size_t)(n_jobs + 1) * 8),
-                 o_ws = put((size_t)(n_jobs + 1) * 4), o_ww = put((size_t)(n_jobs + 1) * 8), o_st = put(16);
-    int rc = ensure(&e->xscratch, &e->xscratch_bytes, o);
+    Layout work;
+    const size_t o_desc = work.put((size_t)doff[n_jobs] * sizeof(ExtractDesc) + 16), o_doff = work.put((size_t)(n_jobs + 1) * 8),
+                 o_ws = work.put((size_t)(n_jobs + 1) * 4), o_ww = work.put((size_t)(n_jobs + 1) * 8), o_st = work.put(16);
+    int rc = ensure(&e->xscratch, &e->xscratch_bytes, work.bytes);
     if (rc) return rc;
     uint8_t* base = (uint8_t*)e->xscratch;
     CW_HIP(hipMemcpyAsync(base + o_doff, doff.data(), (size_t)(n_jobs + 1) * 8, hipMemcpyHostToDevice, st));
@@ -1860,25 +1815,21 @@ static int submit_locked(cw_engine* e, const cw_batch* b, const cw_result* r, in
     if (W == 0) { sl.busy = true; sl.waiting = false; *ticket = si; return CW_OK; }
     CW_HIP(hipSetDevice(e->device));
 
-    size_t o = 0;
-    auto put = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t i_wfs = put((size_t)(W + 1) * 4), i_len = put((size_t)S * 4), i_off = put((size_t)S * 8), i_bases = put((size_t)(b->n_words + 1) * 4);
-    const size_t in_bytes = o;
-    o = 0;
+    Layout in, out;
+    const size_t i_wfs = in.put((size_t)(W + 1) * 4), i_len = in.put((size_t)S * 4), i_off = in.put((size_t)S * 8), i_bases = in.put((size_t)(b->n_words + 1) * 4);
     sl.cons_cap = r->cons_off[W];
     sl.solid_cap = want_solid ? r->solid_off[W] : 0;
-    const size_t o_cons = put(sl.cons_cap), o_coff = put((size_t)(W + 1) * 8);
-    sl.o_clen = put((size_t)W * 4); sl.o_stat = put(W);
-    const size_t o_solid = put(sl.solid_cap * 4), o_soff = put((size_t)(W + 1) * 8);
-    sl.o_slen = put((size_t)W * 4);
-    sl.o_pc = put(sl.cons_cap); sl.o_ps = put(sl.solid_cap * 4); /* the compacted copies */
-    const size_t o_pco = put((size_t)(W + 1) * 8), o_pso = put((size_t)(W + 1) * 8);
-    sl.o_tot = put(48);
+    const size_t o_cons = out.put(sl.cons_cap), o_coff = out.put((size_t)(W + 1) * 8);
+    sl.o_clen = out.put((size_t)W * 4); sl.o_stat = out.put(W);
+    const size_t o_solid = out.put(sl.solid_cap * 4), o_soff = out.put((size_t)(W + 1) * 8);
+    sl.o_slen = out.put((size_t)W * 4);
+    sl.o_pc = out.put(sl.cons_cap); sl.o_ps = out.put(sl.solid_cap * 4); /* the compacted copies */
+    const size_t o_pco = out.put((size_t)(W + 1) * 8), o_pso = out.put((size_t)(W + 1) * 8);
+    sl.o_tot = out.put(48);
     sl.o_cons = o_cons; sl.o_solid = o_solid;
-    const size_t out_bytes = o;
-    int rc = ensure(&sl.dev_in, &sl.dev_in_bytes, in_bytes);
+    int rc = ensure(&sl.dev_in, &sl.dev_in_bytes, in.bytes);
     if (rc) return rc;
-    rc = ensure(&sl.dev_out, &sl.dev_out_bytes, out_bytes);
+    rc = ensure(&sl.dev_out, &sl.dev_out_bytes, out.bytes);
     if (rc) return rc;
     uint8_t* din = (uint8_t*)sl.dev_in;
     uint8_t* dout = (uint8_t*)sl.dev_out;

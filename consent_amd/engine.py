@@ -831,6 +831,11 @@ def seed_spans_rule(seq_len, ref_len, seed_rows, min_hits=SEED_MIN_HITS, pad=SPA
     return np.where(placed, lo, 0).astype(np.uint32), np.where(placed, hi, 0).astype(np.uint32)
 
 
+def _as_batch(groups):
+    """`groups` as the operators take them: a HostBatch as it is, a list of lists of ACGT strings packed."""
+    return groups if isinstance(groups, HostBatch) else pack_piles(groups)
+
+
 def _result_struct(r):
     return Result(
         _ptr(r.cons), _ptr(r.cons_off), _ptr(r.cons_len), _ptr(r.status),
@@ -889,7 +894,7 @@ class Engine:
         given -- zero-length ones skipped, the first max_msa others taken -- and its consensus returned: WindowResults with consensus(g) and status[g]
         (WIN_CONSENSUS, or WIN_OVERFLOW for a group that stopped).  slot_bytes: the consensus slot, one number or one per group (default: poa_slot_bytes
         of the group's longest sequence, what the window path reserves for a segment)."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         res = alloc_poa_results(batch, slot_bytes)
         b = batch.c_struct()
         r = _result_struct(res)
@@ -900,6 +905,15 @@ class Engine:
         """cw_poa_run_device: as run_device, device pointers in both structs (the result's solid fields NULL), asynchronous on `stream`."""
         _check(self.lib, self.lib.cw_poa_run_device(self.handle, C.byref(batch_struct), C.byref(result_struct), stream), "cw_poa_run_device")
 
+    def _run_spans(self, name, batch, spans, head, tail=()):
+        """The host form `name` (cw_sw_run, ..) on (*head, *tail) -- or, with `spans`, its span form (cw_sw_span_run, ..) with the SwSpans of span_arrays()
+        between the two.  Returns what it returned: 0, or -4 when a pair stopped."""
+        mid = ()
+        if spans is not None:
+            lo, hi = span_arrays(spans, len(batch.seq_len))
+            name, mid = name[: -len("run")] + "span_run", (C.byref(SwSpans(_ptr(lo), _ptr(hi))),)
+        return _check(self.lib, getattr(self.lib, name)(self.handle, *head, *mid, *tail), name, allow_capacity=True)
+
     def sw(self, groups, want_indels=False, spans=None):
         """Only the local alignment (cw_sw_run): `groups` is a list of lists of ACGT strings (or a HostBatch of them); every group's first sequence is its
         reference, every other one a query aligned locally against it.  Returns SwRows: .rows is (n_seqs, SW_ROW) int32 -- score, ref_begin, ref_end,
@@ -909,16 +923,10 @@ class Engine:
         spans (here and in sw_path(), pileup(), sw_cut()): a pair of per-sequence arrays (lo, hi), or one (n_seqs, 2) array -- query s is aligned against
         reference columns [lo[s], hi[s]) only (cw_sw_span_run and its kin): the result of the run on reference[lo:hi] in the whole reference's coordinates,
         an empty span the row of an empty reference; SW_STOP then for a span, not a reference, of more than SW_RMAX columns.  None: every column, as ever."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         rows = np.zeros((len(batch.seq_len), SW_ROW), np.int32)
         b = batch.c_struct()
-        flags = SW_WANT_INDELS if want_indels else 0
-        if spans is None:
-            rc = _check(self.lib, self.lib.cw_sw_run(self.handle, C.byref(b), _ptr(rows), flags), "cw_sw_run", allow_capacity=True)
-        else:
-            lo, hi = span_arrays(spans, len(batch.seq_len))
-            sp = SwSpans(_ptr(lo), _ptr(hi))
-            rc = _check(self.lib, self.lib.cw_sw_span_run(self.handle, C.byref(b), _ptr(rows), C.byref(sp), flags), "cw_sw_span_run", allow_capacity=True)
+        rc = self._run_spans("cw_sw_run", batch, spans, (C.byref(b), _ptr(rows)), (SW_WANT_INDELS if want_indels else 0,))
         return SwRows(rows, batch.win_first_seq, rc)
 
     def sw_device(self, batch_struct, rows_ptr, flags=0, stream=None):
@@ -934,7 +942,7 @@ class Engine:
         .n_ops, .ops(group, member) and .cigar(group, member).  Statuses beyond sw()'s: SW_NO_PATH (the traceback's directions outgrow a wave's scratch),
         SW_PATH_OPEN, SW_PATH_SLOT (the ops outgrow the slot: n_ops is the number needed).  slot_ops: ops a sequence's slot holds, one number or one per
         sequence (default: sw_ops_bound of the sequence and its group's reference, which every path fits)."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         S = len(batch.seq_len)
         if slot_ops is None:
             wfs = np.asarray(batch.win_first_seq, np.int64)
@@ -948,13 +956,7 @@ class Engine:
         rows = np.zeros((S, SW_ROW), np.int32)
         b = batch.c_struct()
         paths = SwPaths(_ptr(ops_buf), _ptr(ops_off), _ptr(n_ops))
-        if spans is None:
-            rc = _check(self.lib, self.lib.cw_sw_path_run(self.handle, C.byref(b), _ptr(rows), C.byref(paths), SW_PATH_EQX if eqx else 0), "cw_sw_path_run", allow_capacity=True)
-        else:
-            lo, hi = span_arrays(spans, S)
-            sp = SwSpans(_ptr(lo), _ptr(hi))
-            rc = _check(self.lib, self.lib.cw_sw_path_span_run(self.handle, C.byref(b), _ptr(rows), C.byref(paths), C.byref(sp), SW_PATH_EQX if eqx else 0), "cw_sw_path_span_run",
-                        allow_capacity=True)
+        rc = self._run_spans("cw_sw_path_run", batch, spans, (C.byref(b), _ptr(rows), C.byref(paths)), (SW_PATH_EQX if eqx else 0,))
         return SwPathRows(rows, batch.win_first_seq, rc, n_ops[:S], ops_buf, ops_off)
 
     def sw_path_device(self, batch_struct, rows_ptr, paths_struct, flags=0, stream=None):
@@ -972,7 +974,7 @@ class Engine:
         status SW_PILE_SLOT never occurs with the slots made here -- .counts(group), an (ref_len, PILE_COL) array of how many queries put an A, C, G, T on the
         column, skip it, insert after it, begin and end on it, and .coverage(group).  into: a PileupRows of an earlier call over the same references, or its
         counts_buf; the run then adds to those counts (PILE_ACCUMULATE) instead of beginning at zero -- for a reference whose queries are split over calls."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         S = len(batch.seq_len)
         wfs = np.asarray(batch.win_first_seq, np.int64)
         lens = np.asarray(batch.seq_len, np.int64)
@@ -991,13 +993,7 @@ class Engine:
         rows = np.zeros((S, SW_ROW), np.int32)
         b = batch.c_struct()
         pile = Pileup(_ptr(counts), _ptr(col_off))
-        flags = 0 if into is None else PILE_ACCUMULATE
-        if spans is None:
-            rc = _check(self.lib, self.lib.cw_pileup_run(self.handle, C.byref(b), _ptr(rows), C.byref(pile), flags), "cw_pileup_run", allow_capacity=True)
-        else:
-            lo, hi = span_arrays(spans, S)
-            sp = SwSpans(_ptr(lo), _ptr(hi))
-            rc = _check(self.lib, self.lib.cw_pileup_span_run(self.handle, C.byref(b), _ptr(rows), C.byref(pile), C.byref(sp), flags), "cw_pileup_span_run", allow_capacity=True)
+        rc = self._run_spans("cw_pileup_run", batch, spans, (C.byref(b), _ptr(rows), C.byref(pile)), (0 if into is None else PILE_ACCUMULATE,))
         return PileupRows(rows, batch.win_first_seq, rc, counts, col_off, batch.seq_len)
 
     def pileup_device(self, batch_struct, rows_ptr, pile_struct, flags=0, stream=None):
@@ -1042,19 +1038,14 @@ class Engine:
         """The local alignments cut at their reference's window boundaries (cw_sw_cut_run): `groups` as for sw(), `window` >= 1 reference columns.  Returns
         SwCutRows: the rows of sw_path(), .cuts(group, member) -- word t the query position at reference column t * window -- and .pieces(group, member).
         Status SW_CUT_SLOT never occurs with the slots made here; slot_words (one number, or one per sequence) makes others."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         S = len(batch.seq_len)
         cut_off = self._cut_slots(batch, max(int(window), 1), slot_words)
         cuts_buf = np.zeros(max(int(cut_off[-1]), 1), np.uint32)
         rows = np.zeros((S, SW_ROW), np.int32)
         b = batch.c_struct()
         cuts = SwCuts(_ptr(cuts_buf), _ptr(cut_off), window)
-        if spans is None:
-            rc = _check(self.lib, self.lib.cw_sw_cut_run(self.handle, C.byref(b), _ptr(rows), C.byref(cuts)), "cw_sw_cut_run", allow_capacity=True)
-        else:
-            lo, hi = span_arrays(spans, S)
-            sp = SwSpans(_ptr(lo), _ptr(hi))
-            rc = _check(self.lib, self.lib.cw_sw_cut_span_run(self.handle, C.byref(b), _ptr(rows), C.byref(cuts), C.byref(sp)), "cw_sw_cut_span_run", allow_capacity=True)
+        rc = self._run_spans("cw_sw_cut_run", batch, spans, (C.byref(b), _ptr(rows), C.byref(cuts)))
         return SwCutRows(rows, batch.win_first_seq, rc, cuts_buf, cut_off, window, batch)
 
     def sw_cut_device(self, batch_struct, rows_ptr, cuts_struct, stream=None):
@@ -1082,7 +1073,7 @@ class Engine:
         """The strand vote (cw_strand_run): `groups` as for sw().  Per query the positions whose k-mer is among its reference's k-mers, as given and reverse-
         complemented (k = 0: STRAND_K; else STRAND_KMIN .. STRAND_KMAX).  Returns StrandRows: .strand(group, member) is STRAND_REV when the reverse hits are the
         more, else STRAND_FWD; STRAND_IS_REF for a reference, STRAND_NONE where no vote is possible; .hits(group, member) is (forward, reverse)."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         S = len(batch.seq_len)
         strand = np.zeros(max(S, 1), np.uint8)
         hits = np.zeros((max(S, 1), 2), np.uint32)
@@ -1098,7 +1089,7 @@ class Engine:
     def revcomp(self, groups, strand=None):
         """The batch with the flagged sequences reverse-complemented (cw_revcomp): `strand` is a uint8 value per sequence, of which STRAND_REV flags (a
         StrandRows' .strands, say); None reverses every sequence.  Returns a HostBatch with new `bases` and the arrays of the input otherwise."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         S = len(batch.seq_len)
         if strand is not None:
             strand = np.ascontiguousarray(strand, np.uint8)
@@ -1117,7 +1108,7 @@ class Engine:
     def orient(self, groups, k=0):
         """strands() and revcomp() of what it flags: (HostBatch in which every query has its reference's orientation, StrandRows).  Coordinates of what is
         computed from the oriented batch are the oriented query's: position i there is position len - 1 - i of a query that was turned round."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         rows = self.strands(batch, k)
         return self.revcomp(batch, rows.strands), rows
 
@@ -1127,7 +1118,7 @@ class Engine:
         Returns SeedRows: .row(group, member) is (SEED_STATUS: STRAND_FWD / STRAND_REV of the better orientation, STRAND_IS_REF, STRAND_NONE; SEED_HITS: the
         hits in that window; SEED_DIAG: its lowest diagonal, reference position minus position in the oriented query; SEED_OTHER: the other orientation's
         best), .strands the status bytes, what revcomp() takes."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         S = len(batch.seq_len)
         rows = np.zeros((max(S, 1), SEED_ROW), np.int32)
         strand = np.zeros(max(S, 1), np.uint8)
@@ -1145,7 +1136,7 @@ class Engine:
         array.  Returns (lo, hi), uint32 per sequence: what the `spans` of sw(), sw_path(), pileup() and sw_cut() take -- for the batch ORIENTED by the seed
         run's strands (revcomp(groups, rows.strands)), since SEED_DIAG is the oriented query's.  A reference, a query without a vote or with fewer than
         min_hits (None: SEED_MIN_HITS) gets (0, 0): it is not aligned at all."""
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         S = len(batch.seq_len)
         rows = np.ascontiguousarray(seed_rows.rows if isinstance(seed_rows, SwRows) else seed_rows, np.int32).reshape(-1, SEED_ROW)
         if len(rows) != S:
@@ -1266,7 +1257,7 @@ class Engine:
         if seeded and min_hits is None and 0 < int(k) < SEED_MIN_K:
             raise EngineError(f"polish: the default min_hits is measured for k >= {SEED_MIN_K}; give min_hits with k = {k}")
 
-        batch = groups if isinstance(groups, HostBatch) else pack_piles(groups)
+        batch = _as_batch(groups)
         window = int(window)
         if window < 1:
             raise EngineError("polish: window must be at least 1")
