@@ -1725,13 +1725,27 @@ int cw_stitch_device(cw_engine* e, const cw_read_set* reads, const cw_stitch_rea
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
     const bool want_trace = CW_AID_ENV("CW_STITCH_TRACE") != nullptr;
     const size_t trace_bytes = want_trace ? (size_t)batch->n_windows * 32 : 0;
-    int rc = ensure(&e->xscratch, &e->xscratch_bytes, 256 + trace_bytes + (size_t)n_reads * 4);
+#if CW_ST_WITNESS /* the route witness (cw_stitch.h CwStRoute): its records lie behind the order */
+    const size_t route_bytes = want_trace ? ((size_t)batch->n_windows * CW_ST_WIT_WORDS + n_reads) * 4 : 0;
+#else
+    const size_t route_bytes = 0;
+#endif
+    int rc = ensure(&e->xscratch, &e->xscratch_bytes, 256 + trace_bytes + (size_t)n_reads * 4 + route_bytes);
     if (rc) return rc;
+    e->stitch_route_off = 0;
     CW_HIP(hipMemsetAsync(e->xscratch, 0, 16, st)); /* a.cursor: three words (cw_stitch.h) */
     StitchArgs a;
     a.order = (uint32_t*)((uint8_t*)e->xscratch + 256 + trace_bytes);
     a.trace = want_trace ? (uint32_t*)((uint8_t*)e->xscratch + 256) : nullptr;
     if (want_trace) CW_HIP(hipMemsetAsync(a.trace, 0xFF, (size_t)batch->n_windows * 32, st));
+#if CW_ST_WITNESS
+    if (want_trace) {
+        e->stitch_route_off = 256 + trace_bytes + (size_t)n_reads * 4;
+        a.route = (uint32_t*)((uint8_t*)e->xscratch + e->stitch_route_off);
+        a.read_route = a.route + (size_t)batch->n_windows * CW_ST_WIT_WORDS;
+        CW_HIP(hipMemsetAsync(a.route, 0xFF, route_bytes, st));
+    }
+#endif
     a.reads = *reads; a.jobs = jobs; a.n_reads = n_reads; a.win_pos = win_pos;
     a.batch.n_windows = batch->n_windows; a.batch.win_first_seq = batch->win_first_seq; a.batch.seq_len = batch->seq_len;
     a.batch.seq_word_off = batch->seq_word_off; a.batch.bases = batch->bases;
@@ -1775,6 +1789,19 @@ int cw_debug_stitch_trace(cw_engine* e, uint32_t n_windows, uint32_t* out) {
     CW_HIP(hipDeviceSynchronize());
     CW_HIP(hipMemcpy(out, (uint8_t*)e->xscratch + 256, (size_t)n_windows * 32, hipMemcpyDeviceToHost));
     return CW_OK;
+}
+
+int cw_debug_stitch_route(cw_engine* e, uint32_t n_windows, uint32_t n_reads, uint32_t* win_out, uint32_t* read_out) {
+    if (!e || !win_out || !read_out) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    const size_t off = e->stitch_route_off, win_bytes = (size_t)n_windows * CW_ST_WIT_WORDS * 4;
+    if (off == 0) return 0; /* the product library, or a call without CW_STITCH_TRACE: nothing was recorded */
+    if (!e->xscratch || e->xscratch_bytes < off + win_bytes + (size_t)n_reads * 4) return CW_E_INVALID;
+    CW_HIP(hipSetDevice(e->device));
+    CW_HIP(hipDeviceSynchronize());
+    CW_HIP(hipMemcpy(win_out, (uint8_t*)e->xscratch + off, win_bytes, hipMemcpyDeviceToHost));
+    CW_HIP(hipMemcpy(read_out, (uint8_t*)e->xscratch + off + win_bytes, (size_t)n_reads * 4, hipMemcpyDeviceToHost));
+    return 1;
 }
 
 /* ---- host batches: cw_submit / cw_wait (and cw_run = both) -------------------------------------------------------------------

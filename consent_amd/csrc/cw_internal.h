@@ -58,6 +58,7 @@ struct cw_engine {
     size_t poa_in_bytes = 0, poa_out_bytes = 0;
     void* stitch_scratch = nullptr; /* banded-traceback directions of cw_stitch_device, per wave */
     size_t stitch_scratch_bytes = 0;
+    size_t stitch_route_off = 0; /* where in xscratch the last cw_stitch_device call put its route witness (a -DCW_TEST_AIDS build with CW_STITCH_TRACE); 0: none */
     cw_host_fb* host_fb = nullptr;
     /* per-stage timing of the last run */
     hipStream_t side[3] = {nullptr, nullptr, nullptr}; /* POA tiers run concurrently on their own streams (M1, M2, L) */

@@ -89,6 +89,11 @@ int cw_debug_task_trace(cw_engine* e, uint32_t cap_tasks, uint32_t* out12, uint3
 /* with CW_STITCH_TRACE set in the environment the last cw_stitch_device call records, per window, 8 words (al_pos, size_al, score,
  * ref_begin, ref_end, query_begin, query_end, query_len); 0xFFFFFFFF = window not aligned */
 int cw_debug_stitch_trace(cw_engine* e, uint32_t n_windows, uint32_t* out);
+/* the route witness of the same call (cw_stitch.h CwStRoute / CwStBand / CwStRead): 16 words per window (route, band, then beg, end, overlap, s1, s2, the
+ * sub-alignment's score, ins, del, cut, cl, cur_pos handed on, the gap's move; 0xFFFFFFFF = not reached) and one word per read of the call, the reads
+ * in the order of its jobs.  Returns 1 when they were copied, 0 when nothing was recorded (only a -DCW_TEST_AIDS build records, and only with
+ * CW_STITCH_TRACE set), a negative error otherwise. */
+int cw_debug_stitch_route(cw_engine* e, uint32_t n_windows, uint32_t n_reads, uint32_t* win_out, uint32_t* read_out);
 
 /* ---- synthetic PacBio/ONT-profile piles (bench + tests; SURVEY 8d generator) --------------------- */
 typedef struct cw_synth_spec {

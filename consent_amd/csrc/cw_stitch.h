@@ -35,6 +35,78 @@
 #define CW_ST_SLAB_OF(QMAX, RMAX) ((RMAX) + 2 * (QMAX) + CW_ST_ROWS_BYTES + 2 * (QMAX))
 #define CW_ST_SLAB CW_ST_SLAB_OF(CW_ST_QMAX, CW_ST_RMAX)
 
+/* Which way a window and a read went through cw_stitch_kernel, one bit per decision from its read loop to its end, and the numbers of the
+   reconciliation of two overlapping windows: a -DCW_TEST_AIDS build whose call has CW_STITCH_TRACE set writes, next to the 8-word trace, CW_ST_WIT_WORDS
+   words per window (word 0: CwStRoute; 1: CwStBand, from st_banded_indels; 2..: beg, end, overlap, s1, s2, the sub-alignment's score, ins, del, cut,
+   cl after the splice, cur_pos handed on, the gap's move; 0xFFFFFFFF: not reached) and one word per read (CwStRead; the last launch ORs its bits into
+   the wide kernel's).  Lane 0 stores a word where it is decided, so every `continue` and `break` leaves what was decided before it.  The product's
+   kernel has none of it.  consent_amd/engine.py STITCH_ROUTE names the same bits; tests/stitch_ref.py derives them from the same inputs. */
+enum CwStRoute : unsigned {
+    CW_SR_OVERFLOW = 1u << 0,     /* CW_WIN_OVERFLOW: skipped                              */
+    CW_SR_TEMPLATE = 1u << 1,     /* consensus shorter than k: the template is aligned     */
+    CW_SR_NO_TEMPLATE = 1u << 2,  /* ... and the window has no sequence                    */
+    CW_SR_CLAMPED = 1u << 3,      /* al_pos clamped to 0                                   */
+    CW_SR_CLIPPED = 1u << 4,      /* slice clipped at the read's end                       */
+    CW_SR_NO_SLICE = 1u << 5,     /* size_al <= 0                                          */
+    CW_SR_NO_ALIGN = 1u << 6,     /* score <= 0                                            */
+    CW_SR_QCLIP = 1u << 7,        /* query clipped in front (shift down)                   */
+    CW_SR_OVERLAP = 1u << 8,      /* overlap with the previous window                      */
+    CW_SR_G_SHORT = 1u << 9,      /* not reconciled: the window is on its template         */
+    CW_SR_G_OLD = 1u << 10,       /* not reconciled: old_len < overlap                     */
+    CW_SR_G_CUR = 1u << 11,       /* not reconciled: cl < overlap                          */
+    CW_SR_EQUAL = 1u << 12,       /* overlap equal ignoring case                           */
+    CW_SR_SOLID = 1u << 13,       /* counted by solid k-mers                               */
+    CW_SR_UPPER = 1u << 14,       /* counted by upper case                                 */
+    CW_SR_OLD_WINS = 1u << 15, CW_SR_TIE = 1u << 16, CW_SR_CUR_WINS = 1u << 17,
+    CW_SR_SUB_NONE = 1u << 18,    /* sub-alignment without score                           */
+    CW_SR_INDELS = 1u << 19,      /* ins or del met                                        */
+    CW_SR_SPLICED = 1u << 20, CW_SR_EMPTIED = 1u << 21,
+    CW_SR_LONGER = 1u << 22, CW_SR_SHORTER = 1u << 23, CW_SR_SAME = 1u << 24, /* the replace */
+    CW_SR_GAP_R = 1u << 25, CW_SR_GAP_L = 1u << 26, CW_SR_GAP_R_FAR = 1u << 27, CW_SR_GAP_L_FAR = 1u << 28, /* FAR: by more than 64 */
+    CW_SR_LAST = 1u << 29,        /* last window: no hand-over                             */
+};
+enum CwStBand : unsigned { /* the band st_banded_indels ended with */
+    CW_SB_LANES = 1u << 0, CW_SB_SERIAL = 1u << 1, CW_SB_ROWS_GLOBAL = 1u << 2, CW_SB_DIRS_LDS = 1u << 3, CW_SB_DIRS_GLOBAL = 1u << 4,
+    CW_SB_DOUBLED = 1u << 5,
+    CW_SB_MEM_SWEEP = 1u << 6,    /* (the kernel's: the sub-alignment swept with its state in memory) */
+};
+enum CwStRead : unsigned {
+    CW_SD_SLOT = 1u << 0,         /* slot smaller than the read                            */
+    CW_SD_NO_WINDOW = 1u << 1, CW_SD_OUTGROWN = 1u << 2, CW_SD_LAST_LAUNCH = 1u << 3, CW_SD_NO_UPPER = 1u << 4, CW_SD_ONE_UPPER = 1u << 5,
+    CW_SD_TRIM_SHIFT = 1u << 6, CW_SD_DROPPED = 1u << 7,
+    CW_SD_HANDED = 1u << 8,       /* the wide kernel's nl > CW_ST_QMAX hand-over           */
+};
+#define CW_ST_WIT_WORDS 16
+#if defined(CW_TEST_AIDS) && !CW_ST_PROF /* (a CW_ST_PROF build times the phases: nothing else stores in them) */
+#define CW_ST_WITNESS 1
+#define CW_ST_WITNESS_FIELDS uint32_t* route = nullptr; uint32_t* read_route = nullptr;
+#define CW_ST_BAND_PARAM , uint32_t* wit = nullptr
+#define CW_ST_BAND_WIT(expr) do { if (wit) { expr; } } while (0)
+#define CW_ST_BAND_ARG , &wit_band
+#define CW_ST_WIT_BEGIN(w) uint32_t wit_route = 0u, wit_band = 0u; uint32_t* const wit_rec = a.route && lane == 0 ? a.route + (size_t)CW_ST_WIT_WORDS * (w) : nullptr; \
+                           if (wit_rec) { wit_rec[0] = 0u; wit_rec[1] = 0u; }
+#define CW_ST_WIT(cond, bits) do { if (cond) { wit_route |= (bits); if (wit_rec) wit_rec[0] = wit_route; } } while (0)
+#define CW_ST_WIT_BAND(cond, bits) do { if (cond) wit_band |= (bits); if (wit_rec) wit_rec[1] = wit_band; } while (0)
+#define CW_ST_FACT(i, v) do { if (wit_rec) wit_rec[2 + (i)] = (uint32_t)(v); } while (0)
+#define CW_ST_READ_BEGIN() uint32_t wit_read = 0u
+#define CW_ST_READ_WIT(cond, bits) do { if (cond) wit_read |= (bits); } while (0)
+#define CW_ST_READ_WRITE(ri, huge) do { if (a.read_route && lane == 0) a.read_route[ri] = (huge) ? (a.read_route[ri] | wit_read | CW_SD_LAST_LAUNCH) : wit_read; } while (0)
+#else
+#define CW_ST_WITNESS 0
+#define CW_ST_WITNESS_FIELDS
+#define CW_ST_BAND_PARAM
+#define CW_ST_BAND_WIT(expr) ((void)0)
+#define CW_ST_BAND_ARG
+#define CW_ST_WIT_BEGIN(w) ((void)0)
+#define CW_ST_WIT(cond, bits) ((void)0)
+#define CW_ST_WIT_BAND(cond, bits) ((void)0)
+#define CW_ST_FACT(i, v) ((void)0)
+#define CW_ST_READ_BEGIN() ((void)0)
+#define CW_ST_READ_WIT(cond, bits) ((void)0)
+#define CW_ST_READ_WRITE(ri, huge) ((void)0)
+#endif
+enum { CW_SF_BEG, CW_SF_END, CW_SF_OVERLAP, CW_SF_S1, CW_SF_S2, CW_SF_SUB, CW_SF_INS, CW_SF_DEL, CW_SF_CUT, CW_SF_CL, CW_SF_CUR_POS, CW_SF_GAP };
+
 struct StitchArgs {
     cw_read_set reads;
     const cw_stitch_read* jobs;
@@ -61,6 +133,7 @@ struct StitchArgs {
     uint32_t* trace; /* debug: 8 words per window, NULL in production */
     int prio;        /* wave priorities by read length (CW_STITCH_PRIO) */
     uint8_t* huge;   /* CW_STH_WAVE_BYTES per wave of the last launch (consensuses beyond CW_ST_QMAX): its buffers and the sweep's state, in global memory */
+    CW_ST_WITNESS_FIELDS /* (-DCW_TEST_AIDS only: the route witness's records) */
 };
 
 __device__ __forceinline__ int st_code(uint8_t c) {
@@ -413,7 +486,7 @@ __device__ __forceinline__ StSweep st_sweep_any(const uint8_t* q, int m, const u
  * (lane 0 walks the band; rare: only when two overlapping windows disagree and the earlier one wins).
  * rows: int32 h_b/e_b/h_c (3*width) in LDS; dir: the direction bytes (width_d*readLen*3) in this wave's global scratch. */
 __device__ __forceinline__ bool st_banded_indels(const uint8_t* ref, int refLen, const uint8_t* read, int readLen, int score, uint8_t* rows, uint32_t rows_bytes,
-                                 int8_t* dir_all, uint32_t dir_bytes, unsigned* ins, unsigned* del, int lane, int8_t* dir_lds = nullptr, uint32_t dir_lds_bytes = 0) {
+                                 int8_t* dir_all, uint32_t dir_bytes, unsigned* ins, unsigned* del, int lane, int8_t* dir_lds = nullptr, uint32_t dir_lds_bytes = 0 CW_ST_BAND_PARAM) {
     const int GO = CW_SSW_GAP_OPEN, GE = CW_SSW_GAP_EXT;
     *ins = 0; *del = 0;
     refLen = st_uni(refLen); readLen = st_uni(readLen); score = st_uni(score);
@@ -438,6 +511,8 @@ __device__ __forceinline__ bool st_banded_indels(const uint8_t* ref, int refLen,
         for (int x = lane; x < 3 * w_rows; x += 64) h_b[x] = 0; /* h_b, e_b, h_c are one block */
         for (int x = lane; x < stride_d * readLen * 3; x += 64) dir[x] = 0; /* cells outside the band read as "stop" */
         dir_cur = dir;
+        CW_ST_BAND_WIT(*wit = (*wit & (CW_SB_DOUBLED | CW_SB_MEM_SWEEP)) | (rows_in_lds && width_d <= 64 ? CW_SB_LANES : CW_SB_SERIAL) | (rows_in_lds ? 0u : CW_SB_ROWS_GLOBAL) |
+                              (dir == dir_lds ? CW_SB_DIRS_LDS : CW_SB_DIRS_GLOBAL));
         st_mem_sync();
         int mx = 0;
         if (rows_in_lds && width_d <= 64) {
@@ -525,6 +600,7 @@ __device__ __forceinline__ bool st_banded_indels(const uint8_t* ref, int refLen,
         st_mem_sync();
         if (mx >= score || band > refLen + readLen) break;
         band *= 2;
+        CW_ST_BAND_WIT(*wit |= CW_SB_DOUBLED);
     }
     unsigned ni = 0, nd = 0;
     if (lane == 0) {
@@ -660,6 +736,9 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
            followed by `continue` lets the compiler send lane 0 round a back edge of its own; the cross-lane broadcast at the
            top of the next iteration then runs without it.) */
         uint32_t status = g.cap < rlen ? (uint32_t)CW_READ_CAPACITY : 0u;
+        CW_ST_READ_BEGIN();
+        CW_ST_READ_WIT(status != 0u, CW_SD_SLOT);
+        CW_ST_READ_WIT(status == 0u && jb.win_count == 0u, CW_SD_NO_WINDOW);
         const uint32_t n_fill = status ? 0u : rlen;
         /* outSequence = lower-case read (:56-57), everything in the right part: the gap starts at 0 */
         for (uint32_t x = lane; x < n_fill; x += 64) g.buf[g.cap - rlen + x] = "acgt"[cw_base_at(rwords, x)];
@@ -677,6 +756,8 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
 #else
 #define ST_PROF(k) do { } while (0)
 #endif
+            CW_ST_WIT_BEGIN(w);
+            CW_ST_WIT(st_uni((int)a.win_status[w]) == CW_WIN_OVERFLOW, CW_SR_OVERFLOW);
             if (st_uni((int)a.win_status[w]) == CW_WIN_OVERFLOW) continue;                 /* no consensus for this window: leave the read as it is */
             uint32_t clen = st_uni(a.cons_len[w]);
             const bool long_enough = clen >= a.mer_size;                      /* :75 / :98 / :125 */
@@ -687,6 +768,7 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
             } else {                                                          /* :76 the window's template */
                 const uint32_t ts = a.batch.win_first_seq[w];
                 clen = st_uni((a.batch.win_first_seq[w + 1] > ts) ? a.batch.seq_len[ts] : 0u);
+                CW_ST_WIT(true, a.batch.win_first_seq[w + 1] > ts ? CW_SR_TEMPLATE : CW_SR_NO_TEMPLATE);
                 if (clen > QMAX) { status = too_big; break; }
                 const uint32_t* tw = a.batch.bases + a.batch.seq_word_off[ts];
                 for (uint32_t x = lane; x < clen; x += 64) cur[x] = CW_ACGT(cw_base_at(tw, x));
@@ -695,8 +777,11 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
             const int al_pos = max(0, cur_pos - (int)a.window_overlap);                                    /* :83 */
             const uint32_t tot = g.len();
             int size_al;
+            CW_ST_WIT(cur_pos - (int)a.window_overlap < 0, CW_SR_CLAMPED);
+            CW_ST_WIT((uint64_t)al_pos + a.window_size + 2ull * a.window_overlap >= tot, CW_SR_CLIPPED);
             if ((uint64_t)al_pos + a.window_size + 2ull * a.window_overlap >= tot) size_al = (int)tot - al_pos;   /* :84-88 */
             else size_al = (int)(a.window_size + 2 * a.window_overlap);
+            CW_ST_WIT(size_al <= 0, CW_SR_NO_SLICE);
             if (size_al <= 0 || clen == 0) continue;
             if (size_al > RMAX) { status = too_big; break; }
             for (int x = lane; x < size_al; x += 64) refc[x] = (uint8_t)st_code(g.at((uint32_t)al_pos + x));
@@ -710,21 +795,28 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
                 t[0] = (uint32_t)al_pos; t[1] = (uint32_t)size_al; t[2] = (uint32_t)al.score; t[3] = (uint32_t)al.ref_begin; t[4] = (uint32_t)al.ref_end;
                 t[5] = (uint32_t)al.query_begin; t[6] = (uint32_t)al.query_end; t[7] = clen;
             }
+            CW_ST_WIT(al.score <= 0, CW_SR_NO_ALIGN);
             if (al.score <= 0) continue;
             const uint32_t beg = (uint32_t)(al.ref_begin + al_pos), end = (uint32_t)(al.ref_end + al_pos); /* :91-92 */
             /* curCons = curCons.substr(query_begin, ...) (:93): shift down in place */
             uint32_t cl = (uint32_t)(al.query_end - al.query_begin + 1);
+            CW_ST_WIT(al.query_begin > 0, CW_SR_QCLIP);
+            CW_ST_FACT(CW_SF_BEG, beg); CW_ST_FACT(CW_SF_END, end);
             if (al.query_begin > 0) st_shift_down(cur, (uint32_t)al.query_begin, cl, lane);
             bool emptied = false;
             ST_PROF(2);
             if (wi != 0 && have_old && old_end >= beg) {                                                   /* :96 */
                 const uint32_t overlap = old_end - beg + 1;
+                CW_ST_WIT(true, CW_SR_OVERLAP | (long_enough ? 0u : CW_SR_G_SHORT) | (old_len >= overlap ? 0u : CW_SR_G_OLD) | (cl >= overlap ? 0u : CW_SR_G_CUR));
+                CW_ST_FACT(CW_SF_OVERLAP, overlap);
                 if (long_enough && old_len >= overlap && cl >= overlap) {                                   /* :98 */
                     const uint8_t* seq1 = old + (old_len - overlap);                                        /* :99 */
                     bool diff = false;
                     for (uint32_t x = lane; x < overlap; x += 64) diff = diff || (st_upper(seq1[x]) != st_upper(cur[x]));
+                    CW_ST_WIT(__ballot(diff) == 0ull, CW_SR_EQUAL);
                     if (__ballot(diff) != 0ull) {                                                           /* :101 */
                         int s1, s2;
+                        CW_ST_WIT(true, overlap >= a.mer_size ? CW_SR_SOLID : CW_SR_UPPER);
                         if (overlap >= a.mer_size) {                                                        /* :102-104 */
                             s1 = st_nb_solid(seq1, (int)overlap, a.solid + a.solid_off[old_w], a.solid_len[old_w], a.mer_size, lane);
                             s2 = st_nb_solid(cur, (int)overlap, a.solid + a.solid_off[w], a.solid_len[w], a.mer_size, lane);
@@ -734,6 +826,8 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
                             s1 = st_uni(cw_wave_sum(u1)); s2 = st_uni(cw_wave_sum(u2));
                         }
                         ST_PROF(3);
+                        CW_ST_WIT(true, s1 > s2 ? CW_SR_OLD_WINS : s1 == s2 ? CW_SR_TIE : CW_SR_CUR_WINS);
+                        CW_ST_FACT(CW_SF_S1, s1); CW_ST_FACT(CW_SF_S2, s2);
                         if (s1 > s2) {                                                                      /* :109-119 */
                             /* Align(seq1, seq2, min(len)) then the cigar's indel totals */
                             if (overlap > RMAX) { status = (uint32_t)CW_READ_CAPACITY; break; } /* (the last launch only: elsewhere a consensus is no longer than a slice may be) */
@@ -741,14 +835,21 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
                             st_mem_sync();
                             const StAlign sub = st_align<HUGE>(qfw, (int)overlap, qrv, refc, (int)overlap, lane, state);
                             unsigned ins = 0, del = 0;
+                            CW_ST_WIT(sub.score <= 0, CW_SR_SUB_NONE);
+                            CW_ST_WIT_BAND(HUGE && overlap > 640u, CW_SB_MEM_SWEEP);
                             if (sub.score > 0) {
                                 if (!st_banded_indels(refc + sub.ref_begin, sub.ref_end - sub.ref_begin + 1, qfw + sub.query_begin, sub.query_end - sub.query_begin + 1,
-                                                      sub.score, rows, CW_ST_ROWS_BYTES, dirbuf, a.dir_bytes, &ins, &del, lane, (int8_t*)qrv, a.dir_bytes >= QMAX ? QMAX : 0)) { status = 2; break; }
+                                                      sub.score, rows, CW_ST_ROWS_BYTES, dirbuf, a.dir_bytes, &ins, &del, lane, (int8_t*)qrv, a.dir_bytes >= QMAX ? QMAX : 0 CW_ST_BAND_ARG)) { status = 2; break; }
                             }
                             ST_PROF(4);
                             const uint32_t cut = overlap - ins + del;
+                            CW_ST_WIT_BAND(false, 0u);
+                            CW_ST_WIT(ins != 0u || del != 0u, CW_SR_INDELS);
+                            CW_ST_FACT(CW_SF_SUB, sub.score); CW_ST_FACT(CW_SF_INS, ins); CW_ST_FACT(CW_SF_DEL, del); CW_ST_FACT(CW_SF_CUT, cut);
+                            CW_ST_WIT(true, cut < cl ? CW_SR_SPLICED : CW_SR_EMPTIED);
                             if (cut < cl) {                                                                 /* :114-115 curCons = seq1 + curCons.substr(cut) */
                                 const uint32_t tail = cl - cut, nl = overlap + tail;
+                                CW_ST_READ_WIT(nl > QMAX, CW_SD_HANDED);
                                 if (nl > QMAX) { status = too_big; break; }
                                 /* build in qrv (free now), then copy back */
                                 for (uint32_t x = lane; x < nl; x += 64) qrv[x] = x < overlap ? seq1[x] : cur[cut + (x - overlap)];
@@ -764,10 +865,15 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
                 }
             }
             ST_PROF(3);
+            CW_ST_FACT(CW_SF_CL, emptied ? 0u : cl);
             if (!emptied && cl > 0) {                                                                       /* :124 */
                 if (long_enough) {                                                                          /* :125-129 replace(beg, end-beg+1, upper(cur)) */
                     const uint32_t rl = end - beg + 1;
+                    CW_ST_READ_WIT(g.len() - rl + cl > g.cap, CW_SD_OUTGROWN);
                     if (g.len() - rl + cl > g.cap) { status = 2; break; }
+                    CW_ST_WIT(true, beg + rl > g.L ? (beg + rl - g.L > 64u ? CW_SR_GAP_R_FAR : CW_SR_GAP_R) : beg + rl < g.L ? (g.L - (beg + rl) > 64u ? CW_SR_GAP_L_FAR : CW_SR_GAP_L) : 0u);
+                    CW_ST_WIT(true, cl > rl ? CW_SR_LONGER : cl < rl ? CW_SR_SHORTER : CW_SR_SAME);
+                    CW_ST_FACT(CW_SF_GAP, (int)(beg + rl) - (int)g.L);
                     st_gap_to(g, beg + rl, lane);
                     g.L = beg;
                     for (uint32_t x = lane; x < cl; x += 64) g.buf[g.L + x] = st_upper(cur[x]);
@@ -777,11 +883,13 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
                 if (wi + 1 < jb.win_count) {                                                                /* :130-135 */
                     const long long np = (long long)cur_pos + (long long)st_uni(a.win_pos[2 * (w + 1)]) - (long long)st_uni(a.win_pos[2 * w]) - (long long)(end - beg + 1) + (long long)cl;
                     cur_pos = (int)(uint32_t)np;
+                    CW_ST_FACT(CW_SF_CUR_POS, cur_pos);
                     for (uint32_t x = lane; x < cl; x += 64) old[x] = cur[x];
                     old_len = cl; old_w = w; have_old = true;
                     old_end = beg + cl - 1;
                     st_mem_sync();
                 }
+                CW_ST_WIT(wi + 1 >= jb.win_count, CW_SR_LAST);
             }
 #if CW_ST_PROF
             ST_PROF(5);
@@ -796,14 +904,19 @@ __global__ void __launch_bounds__(64 * WAVES, NCHK == 0 ? 4 : 1) cw_stitch_kerne
             for (uint32_t x = lane; x < flen; x += 64) if (st_is_upper(g.buf[x])) { first = min(first, x); last = max(last, x); ups++; }
             for (int o = 32; o > 0; o >>= 1) { first = min(first, (uint32_t)__shfl_xor((int)first, o)); last = max(last, (uint32_t)__shfl_xor((int)last, o)); }
             ups = st_uni((uint32_t)cw_wave_sum((int)ups)); first = st_uni(first); last = st_uni(last);
+            CW_ST_READ_WIT(first == 0xFFFFFFFFu, CW_SD_NO_UPPER);
+            CW_ST_READ_WIT(ups == 1u, CW_SD_ONE_UPPER);
             if (first == 0xFFFFFFFFu || !(last > first)) { flen = 0; }            /* utils.cpp:123-127: end > beg else "" */
             else {
                 fbeg = first; flen = last - first + 1;
+                CW_ST_READ_WIT(first > 0u, CW_SD_TRIM_SHIFT);
                 if ((float)ups / (float)flen < 0.1) { flen = 0; status = 1; }     /* dropRead on the trimmed read (CONSENT-correction.cpp:52) */
             }
             if (flen && fbeg) st_shift_down(g.buf, fbeg, flen, lane);
         }
         flen = st_uni(flen); status = st_uni(status);
+        CW_ST_READ_WIT(status == 1u, CW_SD_DROPPED);
+        CW_ST_READ_WRITE(ri, HUGE);
         if (lane == 0) {
             a.out_len[ri] = flen; a.read_status[ri] = (uint8_t)status;
             if (!HUGE && status == (uint32_t)CW_READ_REDO) atomicAdd(a.cursor + 2, 1u); /* the last launch looks at this count first */

@@ -364,6 +364,20 @@ FINISH_ROUTE = {"staged": 1 << 0, "compact": 1 << 1, "global": 1 << 2, "cnt16": 
                 "count_scan": 1 << 8, "head": 1 << 9, "tail": 1 << 10, "linked": 1 << 11, "first_pass": 1 << 12, "second_pass": 1 << 13}
 
 
+# The re-assembly kernel's witness (csrc/cw_stitch.h enums CwStRoute, CwStBand, CwStRead; cw_debug_stitch_route): per window of the last Engine.stitch call a route
+# word, the word of the banded traceback and the numbers of the overlap reconciliation, per read a route word.  Only the -DCW_TEST_AIDS library records it,
+# and only under CW_STITCH_TRACE.  The names are those of tests/stitch_ref.py.
+STITCH_ROUTE = {n: 1 << i for i, n in enumerate((
+    "overflow_skipped", "template_aligned", "template_absent", "al_pos_clamped", "slice_clipped", "no_slice", "no_alignment", "query_clipped", "overlap",
+    "guard_short_consensus", "guard_old_shorter", "guard_cur_shorter", "equal_ignoring_case", "by_solid", "by_upper", "old_wins", "tie", "cur_wins", "sub_no_score",
+    "indels", "spliced", "emptied", "replaced_longer", "replaced_shorter", "replaced_same", "gap_right", "gap_left", "gap_right_far", "gap_left_far", "last_window"))}
+STITCH_BAND = {n: 1 << i for i, n in enumerate(("band_lanes", "band_serial", "rows_global", "dirs_lds", "dirs_global", "band_doubled", "sub_mem_sweep"))}
+STITCH_READ = {n: 1 << i for i, n in enumerate(("slot_too_small", "no_window", "outgrown", "last_launch", "no_upper", "one_upper", "trim_shift", "dropped", "handed_over"))}
+STITCH_FACTS = ("beg", "end", "overlap", "s1", "s2", "sub_score", "ins", "del", "cut", "cl", "cur_pos", "gap_move")
+STITCH_WIT_WORDS = 16
+STITCH_GUARD = 64  # bytes behind every out slot of Engine.stitch that no read may touch
+
+
 # The POA tiers' route witness (csrc/cw_poa.h enums CwPoaRoute and CwPoaRc2, csrc/cw_device.h CW_PS_POA_ROUTE and CW_PS_POA_RC2): which fills, walks, group
 # fills, replays and coded row kinds the members of the last batch's tasks took in each slab tier, and why a tier gave a task up (rc 2).  32 route bits a
 # tier, two tiers a slot from POA_ROUTE_SLOT; a byte of causes a tier in POA_RC2_SLOT.
@@ -1381,10 +1395,11 @@ class Engine:
         return HostBatch(o_wfs.cpu().numpy().view(np.uint32), o_len.cpu().numpy().view(np.uint32)[: ns.value], o_off.cpu().numpy().view(np.uint64)[: ns.value],
                          o_bases.cpu().numpy().view(np.uint32)[: max(nw.value, 1)])
 
-    def stitch(self, reads, jobs, win_pos, batch, results, window_size=500, window_overlap=50, do_trim=True):
+    def stitch(self, reads, jobs, win_pos, batch, results, window_size=500, window_overlap=50, do_trim=True, capacity=None):
         """Device-side alignConsensus + trimRead + dropRead (cw_stitch_device).  `reads`: HostBatch-like packing of the read set;
         `jobs`: (n,3) uint32 (read, win_first, win_count); `win_pos`: (W,2) uint32 window (beg,end); `batch`/`results`: the piles
-        and what the engine returned for them.  Returns [(corrected_read, status)]."""
+        and what the engine returned for them; `capacity`: bytes of every read's out slot (default: twice the read + 1024).  Behind each slot
+        lie STITCH_GUARD bytes that must come back as they were sent (AssertionError otherwise).  Returns [(corrected_read, status)]."""
         import torch
 
         dev = torch.device("cuda", self.device)
@@ -1396,8 +1411,23 @@ class Engine:
             return torch.from_numpy(a.view(dt)).to(dev)
 
         jb = np.ascontiguousarray(jobs, np.uint32).reshape(-1, 3)
-        t_len, t_off, t_bases = up(reads.seq_len, np.int32), up(reads.seq_word_off, np.int64), up(np.concatenate([reads.bases, np.zeros(1, np.uint32)]), np.int32)
-        rs = ReadSet(len(reads.seq_len), t_len.data_ptr(), t_off.data_ptr(), t_bases.data_ptr())
+        n = len(jb)
+        seq_len, seq_off = np.asarray(reads.seq_len), np.asarray(reads.seq_word_off)
+        stride = 1
+        if capacity is None:
+            cap = 2 * seq_len[jb[:, 0]].astype(np.int64) + 1024
+        else:
+            # a slot's capacity is the distance to the next slot's offset (cw_stitch_device), so the guard behind a slot is a slot of its own: that of a job
+            # without windows over an empty read appended to the read set, which writes nothing
+            stride = 2
+            seq_len, seq_off = np.concatenate([seq_len, np.zeros(1, seq_len.dtype)]), np.concatenate([seq_off, seq_off[-1:] if len(seq_off) else np.zeros(1, np.uint64)])
+            both = np.zeros((2 * n, 3), np.uint32)
+            both[0::2], both[1::2, 0] = jb, len(seq_len) - 1
+            cap = np.full(2 * n, STITCH_GUARD, np.int64)
+            cap[0::2] = np.ascontiguousarray(capacity, np.int64).reshape(n)
+            jb = both
+        t_len, t_off, t_bases = up(seq_len, np.int32), up(seq_off, np.int64), up(np.concatenate([reads.bases, np.zeros(1, np.uint32)]), np.int32)
+        rs = ReadSet(len(seq_len), t_len.data_ptr(), t_off.data_ptr(), t_bases.data_ptr())
         b_wfs, b_len, b_off, b_bases = up(batch.win_first_seq, np.int32), up(batch.seq_len, np.int32), up(batch.seq_word_off, np.int64), up(np.concatenate([batch.bases, np.zeros(1, np.uint32)]), np.int32)
         bs = Batch(batch.n_windows, len(batch.seq_len), len(batch.bases), b_wfs.data_ptr(), b_len.data_ptr(), b_off.data_ptr(), b_bases.data_ptr())
         r = results
@@ -1405,19 +1435,50 @@ class Engine:
         r_sol, r_soff, r_slen = up(r.solid, np.int32), up(r.solid_off, np.int64), up(r.solid_len, np.int32)
         rstruct = Result(r_cons.data_ptr(), r_coff.data_ptr(), r_clen.data_ptr(), r_st.data_ptr(), r_sol.data_ptr(), r_soff.data_ptr(), r_slen.data_ptr())
         t_jb, t_pos = up(jb, np.int32), up(np.ascontiguousarray(win_pos, np.uint32).reshape(-1), np.int32)
-        cap = 2 * reads.seq_len[jb[:, 0]].astype(np.int64) + 1024
         out_off = np.zeros(len(jb) + 1, np.uint64)
         out_off[1:] = np.cumsum(cap)
         t_ooff = up(out_off, np.int64)
-        t_out = torch.zeros(int(out_off[-1]) + 1, dtype=torch.uint8, device=dev)
+        sent = np.zeros(int(out_off[-1]) + 1, np.uint8)
+        for i in range(1, len(jb), stride) if stride == 2 else ():
+            sent[int(out_off[i]) : int(out_off[i + 1])] = 0xA5
+        t_out = torch.from_numpy(sent).to(dev)
         t_olen = torch.zeros(len(jb) + 1, dtype=torch.int32, device=dev)
         t_ost = torch.full((len(jb) + 1,), 255, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)  # the engine launches on its own stream: torch's fills above must have landed
         _check(self.lib, self.lib.cw_stitch_device(self.handle, C.byref(rs), t_jb.data_ptr(), len(jb), t_pos.data_ptr(), C.byref(bs), C.byref(rstruct), window_size, window_overlap,
                                                    int(bool(do_trim)), t_out.data_ptr(), t_ooff.data_ptr(), t_olen.data_ptr(), t_ost.data_ptr(), None), "cw_stitch_device")
         torch.cuda.synchronize(dev)
+        self._stitch_shape = (int(batch.n_windows), len(jb), stride)
         out, olen, ost = t_out.cpu().numpy(), t_olen.cpu().numpy(), t_ost.cpu().numpy()
-        return [(out[int(out_off[i]) : int(out_off[i]) + int(olen[i])].tobytes().decode("latin-1"), int(ost[i])) for i in range(len(jb))]
+        for i in range(1, len(jb), stride) if stride == 2 else ():
+            lo, hi = int(out_off[i]), int(out_off[i + 1])
+            assert (out[lo:hi] == 0xA5).all() and olen[i] == 0 and ost[i] == 0, f"cw_stitch_device: the guard behind the slot of read {i // 2} was written"
+        return [(out[int(out_off[i]) : int(out_off[i]) + int(olen[i])].tobytes().decode("latin-1"), int(ost[i])) for i in range(0, len(jb), stride)]
+
+    def stitch_trace(self):
+        """The last stitch call's 8 words per window (cw_debug_stitch_trace: al_pos, size_al, score, ref_begin, ref_end, query_begin, query_end, the length
+        aligned; 0xFFFFFFFF where no alignment was tried) as an (n_windows, 8) uint32 array.  Needs CW_STITCH_TRACE set during the call, and the
+        -DCW_TEST_AIDS library."""
+        n_windows = self._stitch_shape[0]
+        out = np.zeros((max(n_windows, 1), 8), np.uint32)
+        self.lib.cw_debug_stitch_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        _check(self.lib, self.lib.cw_debug_stitch_trace(self.handle, n_windows, _ptr(out)), "cw_debug_stitch_trace")
+        return out[:n_windows]
+
+    def stitch_route(self):
+        """The last stitch call's route witness (cw_debug_stitch_route): (windows, reads) -- an (n_windows, STITCH_WIT_WORDS) uint32 array (word 0: STITCH_ROUTE
+        bits, word 1: STITCH_BAND bits, then STITCH_FACTS) and the reads' STITCH_READ words -- or None where nothing was recorded: the product library, or a
+        call without CW_STITCH_TRACE."""
+        n_windows, n_jobs, stride = self._stitch_shape
+        win, rd = np.zeros((max(n_windows, 1), STITCH_WIT_WORDS), np.uint32), np.zeros(max(n_jobs, 1), np.uint32)
+        self.lib.cw_debug_stitch_route.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        self.lib.cw_debug_stitch_route.restype = C.c_int
+        rc = self.lib.cw_debug_stitch_route(self.handle, n_windows, n_jobs, _ptr(win), _ptr(rd))
+        if rc == 0:
+            return None
+        if rc < 0:
+            _check(self.lib, rc, "cw_debug_stitch_route")
+        return win[:n_windows], rd[:n_jobs:stride]
 
     def configure(self, max_template_len):
         """cw_configure: the longest template (window) this engine will see, before its first run -- templates beyond 1024 + k - 1 bases need a larger

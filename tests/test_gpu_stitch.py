@@ -267,14 +267,17 @@ def test_stitch_sweep_width_edges(aids, monkeypatch):
     """Consensus lengths on both sides of every threshold of st_sweep_any, exactly: the wide kernel's nine register sweeps (SWEEP_EDGES, two reads) and,
     in a read that a 2049-character consensus sends to the last launch, 640 and 641 on the two sides of its register-sweep / memory-state-sweep edge.
     Every length must have been placed; the kernel's trace (word 7 of a window's record: the consensus length it loaded) shows each was aligned at
-    that length; the strings are the oracle's."""
+    that length; the strings are the oracle's.  All eight words of every window are those of the plain reference (tests/stitch_ref.py)."""
+    import stitch_ref
+
     monkeypatch.setenv("CW_STITCH_TRACE", "1")
     spec = edge_spec()
-    _, jobs, _, piles = build(spec, EDGE_WINDOW, EDGE_OVERLAP)
-    placed, trace = {}, np.zeros((len(piles), 8), np.uint32)
+    reads, jobs, pos, piles = build(spec, EDGE_WINDOW, EDGE_OVERLAP)
+    placed, trace, kept = {}, np.zeros((len(piles), 8), np.uint32), []
 
     def mutate(res, _piles):
         placed.update(place_edge_lengths(res, jobs, random.Random(23)))
+        kept.append(res)
 
     def probe(eng):
         eng.lib.cw_debug_stitch_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -288,3 +291,13 @@ def test_stitch_sweep_width_edges(aids, monkeypatch):
     for w, n in placed.items():
         assert int(trace[w, 7]) == n, (w, n, trace[w].tolist())
     assert n_up > 0 and all(st == 0 for _, st in got)
+    res = kept[0]
+    for (ri, w0, wn), (g, st) in zip(jobs, got):
+        ws = range(w0, w0 + wn)
+        p = dict(read=reads[ri], pos=pos[w0 : w0 + wn], cons=[res.consensus(w) for w in ws], solid=[list(res.solid_kmers(w)) for w in ws],
+                 tpls=[piles[w][0] if piles[w] else None for w in ws], status=[int(res.status[w]) for w in ws])
+        r = stitch_ref.stitch(p, 7, EDGE_WINDOW, EDGE_OVERLAP)
+        assert (r.string, r.status) == (g, st)
+        for w, rw in zip(ws, r.windows):
+            want = (0xFFFFFFFF,) * 8 if rw.trace is None else tuple(x & 0xFFFFFFFF for x in rw.trace)
+            assert tuple(int(x) for x in trace[w]) == want, (w, trace[w].tolist(), rw.trace)
