@@ -14,6 +14,7 @@
 #define CW_DEVICE_H
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/consent_amd.h"
@@ -141,7 +142,12 @@ struct BatchCounters {
     uint32_t x_stopped;           /* ... that outgrew it too (their windows stop on CW_WHY_POA) */
     uint32_t x_cells;             /* the largest alignment it was asked for, in int32 cells (all three layers under the affine gap model) */
     uint32_t poa_arena_used;      /* a POA-only run (cw_poa_op.h): bytes of the arena its groups' slots have taken */
+    uint32_t q_split;             /* tier Q's list (cw_poa_q.h): its first so many entries are the long tasks (16 lanes each), the rest the short ones (8 lanes); written by the tier sort */
+    uint32_t next_q_short;        /* work-stealing cursor of the short range (next_tier[0] is the long range's) */
+    uint32_t q_short_done;        /* short tasks the eight-lane loop finished */
+    uint32_t q_short_on;          /* ... and those it handed on to tier S (they outgrew PoaQ8) */
 };
+static_assert(offsetof(BatchCounters, q_split) == offsetof(BatchCounters, poa_arena_used) + 4, "tier Q's split and counters are appended: no earlier offset moves (cw_debug_profile, bench.py)");
 
 struct DevBatch {
     uint32_t n_windows;
@@ -231,6 +237,8 @@ __device__ __forceinline__ void cw_wave_sync() {
 /* DPP controls (gfx9 family): row_shr:n = 0x110+n, wave_shr:1 = 0x138, row_bcast:15 = 0x142, row_bcast:31 = 0x143.
  * With bound_ctrl = false a lane without a source keeps `old`, which is the identity of the reduction. */
 #define CW_DPP(old, src, ctrl, row_mask) __builtin_amdgcn_update_dpp((old), (src), (ctrl), (row_mask), 0xF, false)
+/* ... with a bank mask as well: only the banks (four lanes of a row each) whose bit is set are written, the others keep `old` */
+#define CW_DPP_BANK(old, src, ctrl, row_mask, bank_mask) __builtin_amdgcn_update_dpp((old), (src), (ctrl), (row_mask), (bank_mask), false)
 
 /* inclusive prefix max over the 64 lanes: 4 row shifts + 2 row broadcasts, all VALU (no LDS crossbar).  The fill value of the
    shifts is the identity of the operation (INT_MIN / 0), which lets the compiler fold each shift into its max: one v_max_*_dpp per

@@ -1593,6 +1593,17 @@ int cw_debug_tier_x(cw_engine* e, uint32_t* out4) {
     return CW_OK;
 }
 
+/* Debug/inspection (cw_private.h): tier Q's two ranges in the last run -- long entries of its list (BatchCounters::q_split), short tasks the eight-lane loop
+ * finished, short tasks it handed on to tier S.  A build without the eight-lane loop reports every entry as long. */
+int cw_debug_tier_q(cw_engine* e, uint32_t* out3) {
+    if (!e || !e->scratch || !out3) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    BatchCounters c;
+    if (int rc = read_counters_idle(e, &c)) return rc;
+    out3[0] = c.q_split; out3[1] = c.q_short_done; out3[2] = c.q_short_on;
+    return CW_OK;
+}
+
 /* Debug/inspection (cw_private.h): with CW_TASK_TRACE set, 12 words per POA task of the last run: the PoaTask record (window, seg_slot,
  * member_off, n_members, max_len, out_off, out_cap, state) + start and duration in 10 ns units, tier | rc << 8 | pass << 16, wave */
 int cw_debug_task_trace(cw_engine* e, uint32_t cap_tasks, uint32_t* out12, uint32_t* n_tasks) {

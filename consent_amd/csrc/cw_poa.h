@@ -1839,8 +1839,30 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
  * the order inside a class does not matter), with per-wave counters so that the LDS atomics of one wave do not queue behind the
  * other fifteen.  The second buffer is the tier's hand-over list, which nothing uses before the tier kernels run (tier L's is
  * re-initialised afterwards by the kernel itself). */
-#define CW_SORT_CLASSES 128
+/* Tier Q's list has two halves (cw_poa_q.h, PoaQ8): the LONG tasks, which take a 16-lane row each, and behind them the SHORT ones, whose members of at
+   most CW_POAQ8_LC bases leave the upper eight lanes of a row without a column and which the kernel runs eight to a wave.  The half is the sort's first key;
+   the tier-0 work-group writes the number of long entries to BatchCounters::q_split.  -DCW_POAQ_SHORT=0, or tier Q's matrix build (-DCW_Q_CODES=0, which has
+   no eight-lane form): every task is long. */
+#ifndef CW_Q_CODES
+#define CW_Q_CODES 1
+#endif
+#ifndef CW_POAQ_SHORT
+#define CW_POAQ_SHORT 1
+#endif
+#define CW_POAQ8 (CW_POAQ_SHORT && CW_Q_CODES)
+#define CW_POAQ8_LC 15
+#ifndef CW_POAQ8_NC
+#define CW_POAQ8_NC 40
+#endif
+#ifndef CW_POAQ8_ROUTE_NODES
+#define CW_POAQ8_ROUTE_NODES 36 /* a short task is expected (the depth-aware estimate of cw_poa_route) to stay below this many nodes: 0.9 x NC8, as 60 stands to 64 */
+#endif
+#define CW_SORT_COST_CLASSES 128            /* classes of one key */
+#define CW_SORT_CLASSES (CW_POAQ8 ? 256 : 128) /* tier Q: the classes of the long tasks, then the same classes of the short ones (a class is a byte between the two passes) */
 #define CW_SORT_LDS_CLS 131072 /* classes of the first so many list entries are kept in LDS between the two passes */
+__device__ __forceinline__ bool cw_poaq_is_short(uint32_t n_members, uint32_t max_len) {
+    return CW_POAQ8 && max_len <= (uint32_t)CW_POAQ8_LC && (max_len * (15u + n_members / 5u) + 9u) / 10u <= (uint32_t)CW_POAQ8_ROUTE_NODES;
+}
 __device__ __forceinline__ uint32_t cw_sort_class(uint32_t n_members, uint32_t len_pair, int tier) {
     /* PoaTask::max_len = longest member | mean member length << 16.  A task's time is its members' fills: rows (the graph: about the
        longest member, growing with every member) x columns (that member's length), so members x mean length x longest member; the
@@ -1856,11 +1878,11 @@ __device__ __forceinline__ uint32_t cw_sort_class(uint32_t n_members, uint32_t l
            unchanged within its noise over four alternating runs: not kept.  Nor is the order by the members that are NOT repeats, counted by the chain kernel where
            it writes the member lists: tier Q's kernel 8.85 -> 8.45 ms, the chain kernel 2.61 -> 3.05 ms for reading every member's bases: even) */
         const uint32_t mc = n_members < 4u ? 0u : n_members < 8u ? 1u : n_members < 12u ? 2u : n_members < 16u ? 3u : n_members < 24u ? 4u : n_members < 32u ? 5u : n_members < 64u ? 6u : 7u;
-        return (CW_SORT_CLASSES - 1) - (mc * 16u + ((max_len < 32u ? max_len : 31u) >> 1));
+        return (cw_poaq_is_short(n_members, max_len) ? (uint32_t)CW_SORT_COST_CLASSES : 0u) + (CW_SORT_COST_CLASSES - 1) - (mc * 16u + ((max_len < 32u ? max_len : 31u) >> 1));
     }
     if (tier == 5) { /* tier H (cw_poa_q.h): as tier Q, the longest member in steps of four */
         const uint32_t mc = n_members < 4u ? 0u : n_members < 8u ? 1u : n_members < 12u ? 2u : n_members < 16u ? 3u : n_members < 24u ? 4u : n_members < 32u ? 5u : n_members < 64u ? 6u : 7u;
-        return (CW_SORT_CLASSES - 1) - (mc * 16u + ((max_len < 64u ? max_len : 63u) >> 2));
+        return (CW_SORT_COST_CLASSES - 1) - (mc * 16u + ((max_len < 64u ? max_len : 63u) >> 2));
     }
     if (tier == 1) {
         c = ((max_len * (15u + n_members / 5u) + 9u) / 10u) >> 2;
@@ -1873,7 +1895,7 @@ __device__ __forceinline__ uint32_t cw_sort_class(uint32_t n_members, uint32_t l
         const int q = lg * 8 + (int)frac - 8 * 13;                                      /* costs below 2^13 share the last class */
         c = q < 0 ? 0u : (uint32_t)q;
     }
-    return (CW_SORT_CLASSES - 1) - (c < CW_SORT_CLASSES ? c : CW_SORT_CLASSES - 1); /* class 0 = the largest */
+    return (CW_SORT_COST_CLASSES - 1) - (c < CW_SORT_COST_CLASSES ? c : CW_SORT_COST_CLASSES - 1); /* class 0 = the largest */
 }
 __global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc, uint32_t lds_cls) {
     __shared__ uint32_t cnt[16][CW_SORT_CLASSES];
@@ -1885,7 +1907,15 @@ __global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc, uint3
     const uint32_t nthr = blockDim.x, nwv = nthr >> 6; /* 4 .. 16 waves: a small work-group finds room beside another batch's persistent kernels */
     uint32_t* list = sc.tier_list[tier];
     uint32_t* tmp = sc.over_list[tier];
-    if (n < 2) return;
+    if (n < 2) { /* nothing to order; tier Q's split is still owed: 0 or 1 long entries */
+        if (tier == 0 && threadIdx.x == 0) {
+            uint32_t split = n;
+            if (CW_POAQ8 && n == 1) { const uint2 v = *(const uint2*)&sc.tasks[list[0]].n_members; split = cw_poaq_is_short(v.x, v.y & 0xFFFFu) ? 0u : 1u; }
+            sc.ctr->q_split = split;
+        }
+        return;
+    }
+    if (!CW_POAQ8 && tier == 0 && threadIdx.x == 0) sc.ctr->q_split = n; /* every task is long */
     for (uint32_t x = threadIdx.x; x < 16 * CW_SORT_CLASSES; x += nthr) (&cnt[0][0])[x] = 0;
     __syncthreads();
     /* every wave owns a contiguous slice of the list in both passes; eight entries per lane in flight (two dependent global reads each) */
@@ -1908,12 +1938,13 @@ __global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc, uint3
         }
     }
     __syncthreads();
-    if (threadIdx.x < CW_SORT_CLASSES) { uint32_t t = 0; for (uint32_t w = 0; w < nwv; ++w) t += cnt[w][threadIdx.x]; tot_c[threadIdx.x] = t; }
+    for (uint32_t k = threadIdx.x; k < CW_SORT_CLASSES; k += nthr) { uint32_t t = 0; for (uint32_t w = 0; w < nwv; ++w) t += cnt[w][k]; tot_c[k] = t; } /* (a work-group may have fewer threads than there are classes) */
     __syncthreads();
-    if (threadIdx.x < CW_SORT_CLASSES) { /* class-major, then wave: exclusive offsets */
+    for (uint32_t k = threadIdx.x; k < CW_SORT_CLASSES; k += nthr) { /* class-major, then wave: exclusive offsets */
         uint32_t before = 0;
-        for (uint32_t c = 0; c < threadIdx.x; ++c) before += tot_c[c];
-        for (uint32_t w = 0; w < nwv; ++w) { const uint32_t k = cnt[w][threadIdx.x]; cnt[w][threadIdx.x] = before; before += k; }
+        for (uint32_t c = 0; c < k; ++c) before += tot_c[c];
+        if (CW_POAQ8 && tier == 0 && k == (uint32_t)CW_SORT_COST_CLASSES) sc.ctr->q_split = before; /* the first class of the short half starts where the long entries end (n clamped to list_cap included) */
+        for (uint32_t w = 0; w < nwv; ++w) { const uint32_t kk = cnt[w][k]; cnt[w][k] = before; before += kk; }
     }
     __syncthreads();
     for (uint32_t x0 = lo; x0 < hi; x0 += 512) {

@@ -28,6 +28,10 @@
  * What that buys: 64 nodes / 184 edges (tasks of tier S with members of up to 31 bases come here: 43 % of tier S's DP work at depth
  * 150), half again as many tasks resident, and a traceback step of one or two LDS round trips instead of seven.
  *
+ * Tasks whose members have at most 15 bases (58 % of this tier's at depth 150) would leave lanes 8-15 of their row without a column: they are the SHORT half of
+ * the tier's list and run EIGHT to a wave on half rows, in a second loop of the same kernel over the same LDS and slab (PoaQ8, poaq_kernel_body_q; the split is
+ * the tier sort's first key, cw_poa.h).  -DCW_POAQ_SHORT=0 builds the one-loop kernel.
+ *
  * Same policy, same arithmetic, same results as poa_run (cw_poa.h; include/cw_policy.h): the tests compare every tier with the
  * oracle.  A task that outgrows a capacity is handed to tier S (which runs after this kernel on the same stream).
  * -DCW_Q_CODES=0 builds the matrix version of rounds 3-4 (cw_poa_q0.h; tests/test_gpu_variants.py).
@@ -130,18 +134,50 @@ typedef PoaQT<32, CW_POAH_NC, CW_POAH_EC, 8, true> PoaQ32;
 #endif
 #define CW_POAH_MIN_LEN 1
 
-/* ---- GW-lane group primitives ----------------------------------------------------------------------------------------------- */
+/* the third shape: eight tasks per wave on 8-lane HALF rows, members of up to CW_POAQ8_LC = 15 bases (the short half of tier Q's list, cw_poa.h).  A wave's
+   LDS region and its slice of q_slab are those of its four 16-lane tasks, carved again: eight tasks must fit where four were (1 696 bytes a task with 40
+   nodes and 104 edges: 8 x 1 696 = 4 x 3 392, to the byte). */
+#ifndef CW_POAQ8_EC
+#define CW_POAQ8_EC (CW_CONS_HEAVIEST_BUNDLE ? 96 : 104) /* (the heaviest-bundle policy's edge weights are a fourth byte per edge) */
+#endif
+typedef PoaQT<8, CW_POAQ8_NC, CW_POAQ8_EC, 8, false> PoaQ8;
+static_assert(PoaQ8::LC == CW_POAQ8_LC, "the sort's short half (cw_poa.h) is what PoaQ8's columns hold");
+static_assert(8 * PoaQ8::TASK_BYTES <= 4 * PoaQ16::TASK_BYTES, "eight short tasks in the LDS of a wave's four long ones");
+static_assert(8 * PoaQ8::SLAB_BYTES <= 4 * PoaQ16::SLAB_BYTES, "... and in their slice of q_slab");
+static_assert(PoaQ8::TASK_BYTES % 16 == 0 && PoaQ8::SLAB_BYTES % 16 == 0, "a re-carved task starts on a 16-byte boundary, as a long one does");
+static_assert(CW_POAQ8_ROUTE_NODES <= CW_POAQ8_NC, "the short half's bound is a node count inside PoaQ8");
+
+/* ---- GW-lane group primitives -----------------------------------------------------------------------------------------------
+   A group of 16 lanes is a DPP row and one of 32 is two; a group of 8 is HALF a row, so a row shift can carry lane 7 of one task into lane 8, the first lane
+   of the next.  The rule for GW = 8: no lane may ever see another group's value -- each primitive says why it cannot.  (Lanes of another group that are
+   switched off -- the groups of a wave diverge -- read as "no source" to a DPP move, which keeps `old`; the masks below do not rest on that.) */
 template <class T> __device__ __forceinline__ unsigned g_ballot(bool p) {
-    if constexpr (T::GW == 16) return (unsigned)(__ballot(p) >> (threadIdx.x & 48u)) & 0xFFFFu;
+    if constexpr (T::GW == 8) return (unsigned)(__ballot(p) >> (threadIdx.x & 56u)) & 0xFFu; /* shifted to the group's first lane and cut to its eight bits */
+    else if constexpr (T::GW == 16) return (unsigned)(__ballot(p) >> (threadIdx.x & 48u)) & 0xFFFFu;
     else return (unsigned)(__ballot(p) >> (threadIdx.x & 32u));
 }
+/* src < GW: the source is a lane of the caller's own group (8 lanes: threadIdx.x & 56 is its first lane) */
 template <class T> __device__ __forceinline__ int g_bcast(int v, int src) { return __shfl(v, (int)(threadIdx.x & (unsigned)(64 - T::GW)) + src); }
-template <class T> __device__ __forceinline__ int g_scan_add(int v) {
+/* the three steps of an 8-lane ladder.  row_shr:1 and row_shr:2 hand lanes 8 / 8-9 of a row the last lanes of the task before: those lanes (gl < 1, gl < 2)
+   take the identity instead.  row_shr:4 writes only banks 1 and 3 (bank mask 0xA: lanes 4-7 and 12-15, whose source is the lower half of their OWN group);
+   banks 0 and 2, where lanes 8-11 would receive lanes 4-7 of the other task, keep `old`, the identity.  There is no fourth step.
+   (The move comes first and the select after it: a move under `gl >= 1 ? .. : ..` would run with lane 0 switched off, and lane 1 would find no source.) */
+__device__ __forceinline__ int cw_g8_step1(int idn, int v, int gl) { const int s_ = CW_DPP(idn, v, 0x111, 0xF); return gl >= 1 ? s_ : idn; }
+__device__ __forceinline__ int cw_g8_step2(int idn, int v, int gl) { const int s_ = CW_DPP(idn, v, 0x112, 0xF); return gl >= 2 ? s_ : idn; }
+#define CW_G8_STEP1(idn, v, gl) cw_g8_step1((idn), (v), (gl))
+#define CW_G8_STEP2(idn, v, gl) cw_g8_step2((idn), (v), (gl))
+#define CW_G8_STEP4(idn, v) CW_DPP_BANK((idn), (v), 0x114, 0xF, 0xA)
+template <class T> __device__ __forceinline__ int g_scan_add(int v, int gl) {
+    if constexpr (T::GW == 8) { v += CW_G8_STEP1(0, v, gl); v += CW_G8_STEP2(0, v, gl); v += CW_G8_STEP4(0, v); return v; }
     v += CW_DPP(0, v, 0x111, 0xF); v += CW_DPP(0, v, 0x112, 0xF); v += CW_DPP(0, v, 0x114, 0xF); v += CW_DPP(0, v, 0x118, 0xF);
     if constexpr (T::GW == 32) v += CW_DPP(0, v, 0x142, 0xA); /* lane 15 of the group's first row into its second row */
     return v;
 }
-template <class T> __device__ __forceinline__ unsigned g_scan_max_u32(unsigned v) {
+template <class T> __device__ __forceinline__ unsigned g_scan_max_u32(unsigned v, int gl) {
+    if constexpr (T::GW == 8) {
+        v = max(v, (unsigned)CW_G8_STEP1(0, (int)v, gl)); v = max(v, (unsigned)CW_G8_STEP2(0, (int)v, gl)); v = max(v, (unsigned)CW_G8_STEP4(0, (int)v));
+        return v;
+    }
     v = max(v, (unsigned)CW_DPP(0, (int)v, 0x111, 0xF)); v = max(v, (unsigned)CW_DPP(0, (int)v, 0x112, 0xF));
     v = max(v, (unsigned)CW_DPP(0, (int)v, 0x114, 0xF)); v = max(v, (unsigned)CW_DPP(0, (int)v, 0x118, 0xF));
     if constexpr (T::GW == 32) v = max(v, (unsigned)CW_DPP(0, (int)v, 0x142, 0xA));
@@ -150,6 +186,7 @@ template <class T> __device__ __forceinline__ unsigned g_scan_max_u32(unsigned v
 /* lane gl receives v of lane gl - 1 of its group; lane 0 of the group receives 0 */
 template <class T> __device__ __forceinline__ int g_shr1(int v, int gl) {
     if constexpr (T::GW == 16) return CW_DPP(0, v, 0x111, 0xF);
+    else if constexpr (T::GW == 8) return CW_G8_STEP1(0, v, gl); /* (row_shr:1 hands lane 8 of a row the other task's lane 7: lane 0 of a group takes 0, whichever half it is) */
     else { const int s_ = CW_DPP(0, v, 0x138, 0xF); return gl == 0 ? 0 : s_; } /* (wave_shr:1 would hand lane 32 the other task's last lane) */
 }
 
@@ -291,7 +328,7 @@ __device__ __forceinline__ int poaq_fill_c(const PoaQ<T>& M, const int n, const 
         int v = pk_max(kD, kV);
         if (CW_POA_OV && gl == 0) v = (int)(((unsigned)v & 0xFFFF0000u) | 3u); /* overlap mode (cw_policy.h): column 0 is free */
         int w = pk_max(v, (v << 16) | (CW_NEG16 & 0xFFFF));                   /* the odd column sees the even one of its lane */
-        const unsigned inc = g_scan_max_u32<T>(((unsigned)w >> 16) ^ 0x8000u); /* the lanes' running maxima as biased unsigned numbers */
+        const unsigned inc = g_scan_max_u32<T>(((unsigned)w >> 16) ^ 0x8000u, gl); /* the lanes' running maxima as biased unsigned numbers */
         const unsigned ex = (unsigned)g_shr1<T>((int)inc, gl);                 /* exclusive; 0 = nothing to the left */
         w = pk_max(w, pk_splat_lo((int)(ex ^ 0x8000u)));
         const int nv = w | 0x00030003;
@@ -326,7 +363,7 @@ __device__ __forceinline__ int poaq_fill_c(const PoaQ<T>& M, const int n, const 
         int bs = bs0, br = bi0, bc = j0;
         if (bs1 > bs || (bs1 == bs && bi1 < br)) { bs = bs1; br = bi1; bc = j1; }
         if (bs == (int)0x80000000) br = 0x7FFFFFFF;
-        for (int o = GW / 2; o > 0; o >>= 1) {
+        for (int o = GW / 2; o > 0; o >>= 1) { /* (lane ^ o with o < GW stays inside a group of GW lanes that starts at a multiple of GW) */
             const int os = __shfl_xor(bs, o), orr = __shfl_xor(br, o), oc = __shfl_xor(bc, o);
             if (os > bs || (os == bs && (orr < br || (orr == br && oc < bc)))) { bs = os; br = orr; bc = oc; }
         }
@@ -545,7 +582,7 @@ __device__ __forceinline__ int poaq_member(const PoaQ<T>& M, PoaQSt& S, const in
             const int r = r0 + gl;
             const int node = r < n ? M.r2n[r] : 0;
             const int d = r < n ? M.indeg[node] : 0;
-            const int inc = g_scan_add<T>(d);
+            const int inc = g_scan_add<T>(d, gl);
             const int off = run + inc - d;
             if (r < n) {
                 int q = off, first = 0;
@@ -673,7 +710,7 @@ __device__ __forceinline__ int poaq_member(const PoaQ<T>& M, PoaQSt& S, const in
             for (int r0 = 0; r0 < n_old; r0 += GW) {
                 const int r = r0 + gl;
                 const int hcount = r < n_old ? (int)hist[r] : 0;
-                const int inc = g_scan_add<T>(hcount);
+                const int inc = g_scan_add<T>(hcount, gl);
                 if (r < n_old) {
                     const int nr = r + run + inc;
                     const int v = M.r2n[r];
@@ -834,10 +871,72 @@ __device__ __forceinline__ void poaq_kernel_body(const DevBatch& b, const DevScr
 }
 #undef POAQ_PROF
 
+#if CW_POAQ8
+/* One range of tier Q's list: a group claims entry after entry of list[0, n_work) from *cursor until the range is empty; a task that outgrows T (rc 2) goes on
+   hand-over list 0.  done / on: the tasks this group finished / handed on. */
+template <class T>
+__device__ __forceinline__ void poaq_range(const PoaQ<T>& M, const DevBatch& b, const DevScratch& sc, const uint32_t* list, const uint32_t n_work, uint32_t* cursor,
+                                           const int gl, unsigned long long (&acc)[5], uint32_t& done, uint32_t& on) {
+    for (;;) {
+        uint32_t mi = 0;
+        if (gl == 0) mi = atomicAdd(cursor, 1u);
+        mi = (uint32_t)g_bcast<T>((int)mi, 0);
+        if (mi >= n_work) break;
+        const uint32_t ti = list[mi];
+        const PoaTask t = sc.tasks[ti];
+        if (t.n_members == 0) continue; /* a neutral entry (cw_chain.h "cap_ok") */
+        const int rc = poaq_run<T>(M, t, b, sc, gl, acc);
+        if (gl == 0) poa_hand_over(sc, t, ti, rc, 0);
+        done += rc == 1 ? 1u : 0u; on += rc == 2 ? 1u : 0u;
+        cw_wave_sync();
+    }
+}
+/* Tier Q's two ranges, one after the other in every wave (so the kernel's registers are the larger loop's, not the sum): four groups of 16 lanes over the
+   long entries list[0, q_split), then the wave's LDS region and its slice of q_slab carved again for eight groups of 8 lanes over the short entries
+   list[q_split, n).  A wave's region is its own -- no other wave reads or writes it -- and a task's kept rows have all arrived in the slab when its fill ends
+   (poaq_fill_c waits for them), so the second carve needs no more than the wave-level ordering point between the loops.  The long loop's slab and LDS
+   addresses are those of the one-range kernel. */
+__device__ __forceinline__ void poaq_kernel_body_q(const DevBatch& b, const DevScratch& sc, uint8_t* lds, uint8_t* slab_base) {
+    typedef __attribute__((address_space(1))) uint8_t* cw_gptr;
+    const uint32_t wave = threadIdx.x >> 6;
+    uint8_t* const wlds = lds + (size_t)wave * 4 * PoaQ16::TASK_BYTES;
+    uint8_t* const wslab = slab_base + (size_t)(blockIdx.x * (blockDim.x >> 6) + wave) * 4 * PoaQ16::SLAB_BYTES;
+    const uint32_t* list = sc.tier_list[0];
+    const uint32_t n_work = min(sc.ctr->n_tier[0], sc.list_cap);
+    const uint32_t split = min(sc.ctr->q_split, n_work);
+    unsigned long long acc[5] = {0, 0, 0, 0, 0};
+    uint32_t done = 0, on = 0;
+    {
+        const int gl = threadIdx.x & 15;
+        const uint32_t g = (threadIdx.x >> 4) & 3u;
+        const PoaQ<PoaQ16> M = poaq_carve<PoaQ16>(wlds + (size_t)g * PoaQ16::TASK_BYTES, (uint8_t*)(cw_gptr)(wslab + (size_t)g * PoaQ16::SLAB_BYTES));
+        poaq_range<PoaQ16>(M, b, sc, list, split, &sc.ctr->next_tier[0], gl, acc, done, on);
+    }
+    cw_wave_sync();
+    done = 0; on = 0;
+    {
+        const int gl = threadIdx.x & 7;
+        const uint32_t g = (threadIdx.x >> 3) & 7u;
+        const PoaQ<PoaQ8> M = poaq_carve<PoaQ8>(wlds + (size_t)g * PoaQ8::TASK_BYTES, (uint8_t*)(cw_gptr)(wslab + (size_t)g * PoaQ8::SLAB_BYTES));
+        poaq_range<PoaQ8>(M, b, sc, list + split, n_work - split, &sc.ctr->next_q_short, gl, acc, done, on);
+        if (gl == 0) {
+            if (done) atomicAdd(&sc.ctr->q_short_done, done);
+            if (on) atomicAdd(&sc.ctr->q_short_on, on);
+        }
+    }
+    /* per-phase cycles as the first group of every wave saw them, in both loops (the groups of a wave share one instruction stream) */
+    if ((threadIdx.x & 63) == 0) for (int q = 0; q < 5; ++q) atomicAdd(&sc.ctr->prof[CW_PS_POAQ + q], acc[q]);
+}
+#endif
+
 /* tier Q: a task that outgrows it (rc 2) is redone in tier S, whose kernel follows on the stream (hand-over list 0) */
 __global__ void __launch_bounds__(64 * CW_POAQ_WAVES) cw_poa_q_kernel(DevBatch b, DevScratch sc) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+#if CW_POAQ8
+    poaq_kernel_body_q(b, sc, lds, sc.q_slab);
+#else
     poaq_kernel_body<PoaQ16, 0, 0, CW_PS_POAQ, false>(b, sc, lds, sc.q_slab);
+#endif
 }
 #ifdef CW_TEST_AIDS /* (opt-in, measured no faster: only the test-aid build carries the kernel) */
 /* tier H: members of up to 63 bases, graphs of up to 128 nodes; a task that outgrows it goes to tier L's live queue, like tier S's */

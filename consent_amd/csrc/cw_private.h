@@ -82,6 +82,7 @@ int cw_debug_profile(cw_engine* e, uint32_t* counters, uint32_t counters_cap, un
 /* tier X's counters of the last run (4 uint32): tasks tier G handed on to it, tasks it aligned, tasks that outgrew it too (their windows stop on
  * CW_WHY_POA), the largest alignment it was asked for in int32 cells (three layers under the affine gap model) */
 int cw_debug_tier_x(cw_engine* e, uint32_t* out4);
+int cw_debug_tier_q(cw_engine* e, uint32_t* out3); /* tier Q's split (long entries of its list), short tasks finished by the eight-lane loop, short tasks handed on */
 
 /* with CW_TASK_TRACE set in the environment: 12 words per POA task of the last run (see cw_engine.cpp); tier 6 = tier X */
 int cw_debug_task_trace(cw_engine* e, uint32_t cap_tasks, uint32_t* out12, uint32_t* n_tasks);

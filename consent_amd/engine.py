@@ -254,6 +254,8 @@ def _load(p):
     lib.cw_debug_win_info.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     if hasattr(lib, "cw_debug_tier_x"):  # (a library built before tier X has no such entry)
         lib.cw_debug_tier_x.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "cw_debug_tier_q"):
+        lib.cw_debug_tier_q.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "cw_debug_solid_table"):
         lib.cw_debug_solid_table.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     if hasattr(lib, "cw_debug_anchor_block"):
@@ -1522,6 +1524,13 @@ class Engine:
         c = np.zeros(4, np.uint32)
         _check(self.lib, self.lib.cw_debug_tier_x(self.handle, _ptr(c)), "cw_debug_tier_x")
         return {"routed": int(c[0]), "done": int(c[1]), "stopped": int(c[2]), "max_cells": int(c[3])}
+
+    def tier_q_counters(self):
+        """Tier Q's two ranges in the last run (cw_debug_tier_q): `split`, the long entries at the head of its list (16 lanes a task); `short_done`, the short
+        tasks behind them that the eight-lane loop finished; `short_handed_on`, those that outgrew it and went to tier S."""
+        c = np.zeros(3, np.uint32)
+        _check(self.lib, self.lib.cw_debug_tier_q(self.handle, _ptr(c)), "cw_debug_tier_q")
+        return {"split": int(c[0]), "short_done": int(c[1]), "short_handed_on": int(c[2])}
 
     def solid_table(self, w):
         """cw_debug_solid_table: (keys, counts) of window w of the last run -- the index kernel's ascending solid k-mers and their exact pile-wide counts."""

@@ -60,6 +60,17 @@ def notes(co):
     return [k for k in kernels if "vgpr_count" in k]
 
 
+def code_bytes(co):
+    """{symbol: size in bytes} of the functions of the code object (llvm-readelf --symbols): what a kernel takes of the instruction cache."""
+    txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--symbols", "--wide", co], capture_output=True, text=True).stdout
+    out = {}
+    for line in txt.splitlines():
+        f = line.split()
+        if len(f) >= 8 and f[3] == "FUNC":
+            out[f[7]] = int(f[2], 0) if f[2].startswith("0x") else int(f[2])
+    return out
+
+
 def disasm(co):
     """{symbol: [(label, mnemonic, text)]} with, per instruction, the innermost loop it sits in: labels are llvm-objdump's
     --symbolize-operands block labels (L0, L1, ... per function); a loop is the span between a label and a later branch back to it."""
@@ -131,10 +142,12 @@ def main():
         co = lib if lib.endswith(".co") else unbundle(lib, tmp)  # a device-only object (hipcc --cuda-device-only -c) is read as it is
         ks = notes(co)
         fns = disasm(co)
+        size = code_bytes(co)
     names = demangle([k["name"] for k in ks])
     print(f"# {os.path.relpath(lib, ROOT)}: gfx950 code object, {len(ks)} kernels (llvm-readelf --notes, llvm-objdump -d)")
-    print("# scratch = private_segment_fixed_size, bytes per lane; waves/SIMD = what the VGPR count allows (512 / VGPRs, at most 8)")
-    hdr = f"{'kernel':58s} {'VGPR':>5s} {'SGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'scratchB':>8s} {'LDS_B':>7s} {'w/SIMD':>6s} {'insts':>7s} {'scr_ld':>6s} {'scr_st':>6s} {'glob':>5s} {'ds':>5s} {'dpp':>5s} {'v_pk':>5s} {'scr_in_loop':>11s}"
+    print("# scratch = private_segment_fixed_size, bytes per lane; waves/SIMD = what the VGPR count allows (512 / VGPRs, at most 8); codeB = the kernel's size in bytes")
+    print("# cw_poa_q_kernel holds two task loops, one after the other (16-lane groups, then 8-lane groups: cw_poa_q.h): its registers are the larger loop's, its code both loops'")
+    hdr = f"{'kernel':58s} {'VGPR':>5s} {'SGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'scratchB':>8s} {'LDS_B':>7s} {'w/SIMD':>6s} {'insts':>7s} {'codeB':>7s} {'scr_ld':>6s} {'scr_st':>6s} {'glob':>5s} {'ds':>5s} {'dpp':>5s} {'v_pk':>5s} {'scr_in_loop':>11s}"
     print(hdr)
     for k in ks:
         nm = names[k["name"]]
@@ -147,7 +160,7 @@ def main():
         gran = max(8, (v + 7) // 8 * 8)
         wps = min(8, 512 // gran)
         print(f"{nm[:58]:58s} {k['vgpr_count']:>5s} {k['sgpr_count']:>5s} {k['vgpr_spill_count']:>6s} {k['sgpr_spill_count']:>6s} "
-              f"{k['private_segment_fixed_size']:>8s} {k['group_segment_fixed_size']:>7s} {wps:>6d} {sum(1 for x in ins if x[1]):>7d} "
+              f"{k['private_segment_fixed_size']:>8s} {k['group_segment_fixed_size']:>7s} {wps:>6d} {sum(1 for x in ins if x[1]):>7d} {size.get(k['name'], 0):>7d} "
               f"{count(ins, lambda m, s: m.startswith('scratch_load')):>6d} {count(ins, lambda m, s: m.startswith('scratch_store')):>6d} "
               f"{count(ins, lambda m, s: m.startswith('global_') or m.startswith('flat_') or m.startswith('buffer_')):>5d} "
               f"{count(ins, lambda m, s: m.startswith('ds_')):>5d} {count(ins, lambda m, s: 'dpp' in s or 'row_shr' in s or 'row_bcast' in s):>5d} "
