@@ -267,6 +267,7 @@ def _load(p):
     lib.cw_debug_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.cw_extract_piles_device.argtypes = [C.c_void_p, C.POINTER(ReadSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p]
+    lib.cw_plan_results_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
     lib.cw_stitch_device.argtypes = [C.c_void_p, C.POINTER(ReadSet), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Batch), C.POINTER(Result), C.c_uint32, C.c_uint32,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cw_index_reads.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
@@ -1396,6 +1397,28 @@ class Engine:
         torch.cuda.synchronize(dev)
         return HostBatch(o_wfs.cpu().numpy().view(np.uint32), o_len.cpu().numpy().view(np.uint32)[: ns.value], o_off.cpu().numpy().view(np.uint64)[: ns.value],
                          o_bases.cpu().numpy().view(np.uint32)[: max(nw.value, 1)])
+
+    def plan_results(self, batch, fill=0):
+        """The result slots of a device-resident batch (cw_plan_results_device): (cons_off, solid_off, cons_total, solid_total), the two exclusive offset arrays
+        of n_windows + 1 entries as uint64.  Only the batch's window and length arrays are read.  `fill`: what both arrays hold before the call (a test's
+        sentinel: an entry the library did not write comes back as it)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+
+        def up(a, dt):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy((a if a.size else np.zeros(1, a.dtype)).view(dt)).to(dev)
+
+        n = batch.n_windows
+        t_wfs, t_len = up(batch.win_first_seq, np.int32), up(batch.seq_len, np.int32)
+        o_cons, o_solid = (torch.full((n + 1,), int(np.uint64(fill).astype(np.int64)), dtype=torch.int64, device=dev) for _ in range(2))
+        torch.cuda.synchronize(dev)  # the engine launches on its own stream: torch's fills above must have landed
+        b = Batch(n, len(batch.seq_len), len(batch.bases), t_wfs.data_ptr(), t_len.data_ptr(), None, None)
+        ct, st = C.c_uint64(), C.c_uint64()
+        _check(self.lib, self.lib.cw_plan_results_device(self.handle, C.byref(b), o_cons.data_ptr(), o_solid.data_ptr(), C.byref(ct), C.byref(st), None), "cw_plan_results_device")
+        torch.cuda.synchronize(dev)
+        return o_cons.cpu().numpy().view(np.uint64), o_solid.cpu().numpy().view(np.uint64), ct.value, st.value
 
     def stitch(self, reads, jobs, win_pos, batch, results, window_size=500, window_overlap=50, do_trim=True, capacity=None):
         """Device-side alignConsensus + trimRead + dropRead (cw_stitch_device).  `reads`: HostBatch-like packing of the read set;
