@@ -128,6 +128,7 @@ __device__ __forceinline__ uint32_t ch_pair_rows(ROW row_at, const uint32_t row_
 /* the five tier lists of the flush in the order of their tier codes (cw_poa_route) 1 .. 5 = M1, M2, L, Q, H: list li takes tier code li + 1 and is
    tier_list / n_tier [ch_list_id(li)] */
 #define CW_CH_LISTS 5
+#define CW_CH_FLUSH_ROUNDS 4 /* the flush stages an entry's anchor rows for this many rounds of 64 sequences at once (piles of up to 256 sequences: all of them) */
 __device__ __forceinline__ constexpr int ch_list_id(const int li) { return li < 3 ? li + 1 : li == 3 ? 0 : 5; }
 
 #if CW_SEG_MISSING_ANCHOR == CW_SEG_MISSING_ANCHOR_EXTRAPOLATE
@@ -512,7 +513,7 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                         for (int li = 0; li < CW_CH_LISTS; ++li) {
                             const uint32_t n_l = (uint32_t)__popcll(tm[li]);
                             for (uint32_t x = lane; x < n_l; x += 64)
-                                if ((uint64_t)lb[li] + x < sc.list_cap) sc.tier_list[ch_list_id(li)][lb[li] + x] = sc.task_cap;
+                                if ((uint64_t)lb[li] + x < sc.list_cap) sc.tier_list[ch_list_id(li)][lb[li] + x] = cw_list_entry(sc, sc.task_cap, 0u, 0u, ch_list_id(li)); /* the neutral task's class: no members */
                         }
                     }
                     else {
@@ -529,13 +530,47 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                             uint32_t at = 0;
 #pragma unroll
                             for (int li = 0; li < CW_CH_LISTS; ++li) if (tier == (uint32_t)li + 1u) { list = sc.tier_list[ch_list_id(li)]; at = lb[li] + (uint32_t)__popcll(tm[li] & below); }
-                            if (tier) list[at] = t_idx;
+                            if (tier) list[at] = cw_list_entry(sc, t_idx, e_n, t.max_len, tier == 4u ? 0 : (int)tier); /* with the class the tier sort goes by (cw_poa.h) */
                             sc.seg_off[t.seg_slot] = t.out_off; sc.seg_len[t.seg_slot] = 0;
                         }
-                        /* the wave-wide part, entry by entry: member lists (coalesced matrix rows) and long single pieces */
-                        for (uint32_t q = 0; q < q_cnt; ++q) {
-                            const uint32_t g_seg = Q->seg[q], g_n = Q->n[q], g_mx = Q->mx[q], g_off = Q->off[q];
+                        /* The wave-wide part, entry by entry: member lists (coalesced matrix rows) and long single pieces.  A member list needs the rows of
+                           the entry's two anchors, lanes = sequences: all CW_CH_FLUSH_ROUNDS x 64 sequences of them are loaded before the first ballot (the
+                           loads do not depend on how many members are written, only the store index does), and the rows of the entry after this one are in
+                           flight while this one's members are stored -- two row sets, A and B, in turn.  One rule for the three kinds of segment, as in the
+                           scan above: the piece runs from pa (0 in front of the first anchor) to pb (the sequence's end behind the last one). */
+                        struct ChRows { uint32_t a[CW_CH_FLUSH_ROUNDS], b[CW_CH_FLUSH_ROUNDS]; };
+                        auto rows_load = [&](const uint32_t q, const uint32_t sb0, ChRows& R) {
+                            if (Q->n[q] == 1u) return; /* a long single piece reads no rows */
+                            const uint32_t g_seg = Q->seg[q];
                             const int g_ca = Q->ca[q], g_cb = Q->cb[q];
+                            const uint16_t* const row_a = P + (uint32_t)(g_ca >= 0 ? g_ca : 0) * Np;
+                            const uint16_t* const row_b = P + (uint32_t)(g_cb >= 0 ? g_cb : 0) * Np;
+#pragma unroll
+                            for (uint32_t r = 0; r < (uint32_t)CW_CH_FLUSH_ROUNDS; ++r) {
+                                const uint32_t s = sb0 + r * 64u + (uint32_t)lane;
+                                const bool in = s < N;
+                                R.a[r] = !in ? (uint32_t)CW_NONE16 : g_seg == 0u ? 0u : (uint32_t)row_a[s];
+                                R.b[r] = !in ? 0u : g_seg == m ? b.seq_len[s0 + s] : (uint32_t)row_b[s]; /* (the last segment: pa < length always, unless the position is an extrapolated one) */
+                            }
+                        };
+                        auto rows_emit = [&](const uint32_t sb0, const ChRows& R, const bool seg_last, const uint32_t g_n, const uint32_t g_moff, uint32_t& done) {
+#pragma unroll
+                            for (uint32_t r = 0; r < (uint32_t)CW_CH_FLUSH_ROUNDS; ++r) {
+                                const uint32_t s = sb0 + r * 64u + (uint32_t)lane;
+                                const uint32_t pa = R.a[r], pb = R.b[r];
+                                const bool is = pa != CW_NONE16 && (seg_last || pb != CW_NONE16) && pa < pb; /* (a lane beyond N holds pa = none) */
+                                const unsigned long long bal = __ballot(is);
+                                const uint32_t idx = done + (uint32_t)__popcll(bal & below);
+                                if (is && idx < g_n) {
+                                    PoaMember pmb;
+                                    pmb.seq = s0 + s; pmb.start = (uint16_t)pa; pmb.len = (uint16_t)(pb - pa);
+                                    sc.members[g_moff + idx] = pmb;
+                                }
+                                done += (uint32_t)__popcll(bal);
+                            }
+                        };
+                        auto entry = [&](const uint32_t q, const ChRows& R) {
+                            const uint32_t g_seg = Q->seg[q], g_n = Q->n[q], g_mx = Q->mx[q], g_off = Q->off[q];
                             if (g_n == 1u) {
                                 CW_CH_ROUTE(sc.ctr, lane == 0, CW_CR_LONG_SINGLE);
                                 const uint32_t* words = b.bases + b.seq_word_off[s0 + Q->fs[q]];
@@ -545,28 +580,23 @@ __global__ void __launch_bounds__(64 * CW_CH_WAVES) cw_chain_kernel(DevBatch b, 
                             } else {
                                 const uint32_t g_moff = (uint32_t)cw_lane_value((int)m_off, (int)q);
                                 uint32_t done = 0;
-                                for (uint32_t sb = 0; sb < N && done < g_n; sb += 64) {
-                                    const uint32_t s = sb + lane;
-                                    bool is = false;
-                                    uint32_t st = 0, ln = 0;
-                                    if (s < N) {
-                                        const uint32_t pa = g_ca >= 0 ? (uint32_t)P[(uint32_t)g_ca * Np + s] : 0u;
-                                        const uint32_t pb = g_cb >= 0 ? (uint32_t)P[(uint32_t)g_cb * Np + s] : 0u;
-                                        if (g_seg == 0) { is = pb != CW_NONE16 && pb > 0; st = 0; ln = pb; }
-                                        else if (g_seg == m) { const uint32_t sl_ = b.seq_len[s0 + s]; is = pa != CW_NONE16 && pa < sl_; st = pa; ln = sl_ - pa; } /* (pa < length: always, unless the position is an extrapolated one) */
-                                        else { is = pa != CW_NONE16 && pb != CW_NONE16 && pa < pb; st = pa; ln = pb - pa; }
-                                    }
-                                    const unsigned long long bal = __ballot(is);
-                                    const uint32_t idx = done + (uint32_t)__popcll(bal & below);
-                                    if (is && idx < g_n) {
-                                        PoaMember pmb;
-                                        pmb.seq = s0 + s; pmb.start = (uint16_t)st; pmb.len = (uint16_t)ln;
-                                        sc.members[g_moff + idx] = pmb;
-                                    }
-                                    done += (uint32_t)__popcll(bal);
+                                rows_emit(0u, R, g_seg == m, g_n, g_moff, done);
+                                for (uint32_t sb0 = 64u * CW_CH_FLUSH_ROUNDS; sb0 < N && done < g_n; sb0 += 64u * CW_CH_FLUSH_ROUNDS) { /* piles beyond 256 sequences: the rest, a set at a time */
+                                    ChRows T;
+                                    rows_load(q, sb0, T);
+                                    rows_emit(sb0, T, g_seg == m, g_n, g_moff, done);
                                 }
                             }
-                            cw_wave_sync();
+                        };
+                        ChRows A, B;
+#pragma unroll
+                        for (uint32_t r = 0; r < (uint32_t)CW_CH_FLUSH_ROUNDS; ++r) { A.a[r] = A.b[r] = B.a[r] = B.b[r] = 0u; }
+                        if (q_cnt) rows_load(0u, 0u, A);
+                        for (uint32_t q = 0; q < q_cnt; q += 2u) {
+                            if (q + 1u < q_cnt) rows_load(q + 1u, 0u, B);
+                            entry(q, A);
+                            if (q + 2u < q_cnt) rows_load(q + 2u, 0u, A);
+                            if (q + 1u < q_cnt) entry(q + 1u, B);
                         }
                     }
                     q_cnt = 0;

@@ -199,6 +199,8 @@ struct DevScratch {
     uint32_t h_min_len;            /* shortest "longest member" tier H takes (CW_H_MIN_LEN, default CW_POAH_MIN_LEN) */
     uint32_t linger_wgs;           /* tier-L work-groups that stay on the live overflow queue */
     uint32_t producer_wgs;         /* work-groups launched for tiers S + M1 + M2 (tier L's live queue waits for them) */
+    uint32_t list_cls;             /* 1: an entry of a routed list carries its sort class in its top byte from emission to the tier sort (cw_poa.h cw_list_entry);
+                                      0 (a plan of more than 2^24 - 1 task slots): plain task indices, the sort reads the classes' inputs from the task records */
 };
 
 /* ---- packed-sequence access ------------------------------------------------------------------- */

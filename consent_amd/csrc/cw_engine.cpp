@@ -57,7 +57,6 @@ static_assert(CW_FIN_CB_BIG == CW_CONS_SLOT_MAX, "the largest consensus slot (in
    set_kernel_attributes allows each kernel the most its launch can ask for, and the launch passes the same name. */
 constexpr size_t kLdsIndex = CW_IDX_LDS_BYTES;
 constexpr size_t lds_chain(size_t slab) { return CW_CH_WAVES * slab; } /* CW_CH_SLAB, or CW_CH_SLAB_LONG for an engine configured for long templates */
-constexpr size_t kLdsSortMax = CW_SORT_LDS_CLS; /* the launch keeps CW_SORT_LDS bytes of classes of it (launch_shape) */
 constexpr size_t kLdsTierS = (size_t)CW_POA_SLAB_BYTES * CW_POA_WAVES;
 constexpr size_t lds_tier_q(uint32_t waves) { return (size_t)CW_POAQ_TASK_BYTES * 4 * waves; } /* four tasks per wave */
 constexpr size_t lds_tier_h(uint32_t waves) { return (size_t)CW_POAH_TASK_BYTES * 2 * waves; } /* two tasks per wave; six waves at most: cw_poa_h_kernel's launch bounds */
@@ -138,7 +137,6 @@ int set_kernel_attributes(const hipDeviceProp_t& prop) {
     const size_t lds_st = stitch_lds_one(prop);
     const bool ok = allow((const void*)cw_index_kernel, kLdsIndex) &&
         allow((const void*)cw_chain_kernel<CW_CH_SLAB>, lds_chain(CW_CH_SLAB)) && allow((const void*)cw_chain_kernel<CW_CH_SLAB_LONG>, lds_chain(CW_CH_SLAB_LONG)) &&
-        allow((const void*)cw_sort_tier_kernel, kLdsSortMax) &&
         allow((const void*)cw_poa_kernel, kLdsTierS) && allow((const void*)cw_poa_q_kernel, lds_tier_q(CW_POAQ_WAVES)) &&
 #if CW_Q_CODES && defined(CW_TEST_AIDS) /* tier H: an opt-in kernel of the test-aid build (CW_TIER_H), not in the product's code object */
         allow((const void*)cw_poa_h_kernel, lds_tier_h(6)) &&
@@ -233,6 +231,7 @@ DevScratch bind_scratch(const ScratchPlan& p, uint8_t* base) {
     sc.members = (PoaMember*)(base + p.members); sc.member_cap = p.member_cap;
     sc.ctr = (BatchCounters*)(base + p.ctr);
     sc.list_cap = p.task_cap;
+    sc.list_cls = p.task_cap <= CW_LIST_IDX_MASK ? 1u : 0u; /* the neutral entry, task_cap itself, has to fit under the class byte too */
     for (int t = 0; t < CW_TIERS; ++t) {
         sc.tier_list[t] = (uint32_t*)(base + p.list[t]); sc.over_list[t] = (uint32_t*)(base + p.over[t]);
         sc.slab[t] = base + p.slab[t]; sc.slab_bytes[t] = p.tier[t].slab_bytes; sc.slots[t] = p.tier[t].slots;
@@ -264,6 +263,8 @@ int hold_and_bind(cw_engine* e, uint32_t n_windows, uint32_t big_slots, const Sc
     e->last_tasks_off = p.tasks; e->last_tdbg_off = p.tdbg; e->last_task_cap = p.task_cap;
     e->last_solid_key_off = p.solid_key; e->last_solid_cnt_off = p.solid_cnt;
     e->last_seg_len_off = p.seg_len; e->last_members_off = p.members;
+    static_assert(CW_TIERS == 6, "cw_engine::last_list_off");
+    for (int t = 0; t < CW_TIERS; ++t) e->last_list_off[t] = p.list[t];
     e->last_ablock_off = p.ablock; e->last_ablock_units = p.ablock_units;
     if (!e->step_clock) { CW_HIP(hipMalloc((void**)&e->step_clock, 16)); CW_HIP(hipMemset(e->step_clock, 0, 16)); }
     *sc = bind_scratch(p, (uint8_t*)e->scratch);
@@ -340,11 +341,11 @@ LaunchShape launch_shape(cw_engine* e, const cw_batch* batch, const ScratchPlan&
     /* Launch shapes chosen for two batches in flight on one GPU (two engines, or the driver's two workers): while the other batch's
        persistent tier kernels hold the LDS of every CU, a work-group that needs most of a CU waits for tens of milliseconds in the
        middle of this batch's chain (rocprofv3 timeline, depth 150: tier sort 0.45 -> 13-34 ms, tier Q 8.7 -> 55-94 ms with tier S
-       queued behind it, the two overflow passes 0.05 -> 12-32 ms).  So: the sort keeps 16 KB of classes in LDS instead of 128 (the
-       rest are recomputed), tier Q runs as two-wave work-groups (38 KB; the same 8 waves per CU when it has the machine to itself),
+       queued behind it, the two overflow passes 0.05 -> 12-32 ms).  So: the sort is a small work-group (and since the classes
+       travel in the list entries it keeps none of them in LDS: 17 KB of counters, static), tier Q runs as two-wave work-groups (38 KB; the same 8 waves per CU when it has the machine to itself),
        and the overflow passes -- normally a handful of tasks -- are 64 / 16 work-groups instead of two per CU.  Alone on the GPU the
        step time is unchanged. */
-    ls.sort_lds = knob_u("CW_SORT_LDS", 16384, 0, kLdsSortMax);
+    ls.sort_lds = 0; /* no dynamic LDS: the class cache went when the classes moved into the list entries (cw_poa.h cw_list_entry) */
     ls.sort_thr = knob_u("CW_SORT_THREADS", 256, 128, 1024) / 64 * 64;
     ls.q_waves = knob_u("CW_Q_WAVES", CW_POAQ_WAVES % 3 == 0 ? 3 : CW_POAQ_WAVES % 2 == 0 ? 2 : 1, 1, CW_POAQ_WAVES); /* waves per tier-Q work-group (four tasks per wave; round 5: three-wave work-groups of 40 KB, four per CU) */
     const uint32_t q_fit = wgs_lds_fit(lds_tier_q(ls.q_waves));
@@ -380,7 +381,13 @@ int enqueue_end(cw_engine* e, hipStream_t st, const DevScratch& sc) {
    overflow pass (L, G, X).  It depends on what comes before it only through tasks[], members[], the tier lists and seg_off / seg_len / arena. */
 int enqueue_poa_stage(cw_engine* e, hipStream_t st, const DevBatch& db, const DevScratch& sc, const LaunchShape& ls) {
     const uint32_t* wgs = sc.persist_wgs;
-    cw_sort_tier_kernel<<<5, ls.sort_thr, ls.sort_lds, st>>>(sc, ls.sort_lds); /* tiers M1, M2 and L: largest tasks first; tiers Q and H: like with like */
+    e->emitted_cap = 0;
+    if (CW_AID_ENV("CW_KEEP_EMITTED")) { /* test aid: the lists as emitted, class bytes and all (cw_debug_tier_lists) */
+        if (int rc = ensure(&e->emitted, &e->emitted_bytes, (size_t)CW_TIERS * sc.task_cap * 4)) return rc;
+        for (int t = 0; t < CW_TIERS; ++t) CW_HIP(hipMemcpyAsync((uint32_t*)e->emitted + (size_t)t * sc.task_cap, sc.tier_list[t], (size_t)sc.task_cap * 4, hipMemcpyDeviceToDevice, st));
+        e->emitted_cap = sc.task_cap;
+    }
+    cw_sort_tier_kernel<<<5, ls.sort_thr, ls.sort_lds, st>>>(sc); /* tiers M1, M2 and L: largest tasks first; tiers Q and H: like with like */
     /* pass 0: every tier works through its own routed list, all four concurrently; the long-running large tiers are
        dispatched first so that their tail overlaps the bulk of the small tasks */
     CW_HIP(hipEventRecord(e->ev_fork, st));
@@ -401,7 +408,7 @@ int enqueue_poa_stage(cw_engine* e, hipStream_t st, const DevBatch& db, const De
     if (wgs[5]) /* two tasks per wave; hands what outgrows it to tier L's live queue, as tier S does */
         stage(e, ms, "poa_h", [&] { cw_poa_h_kernel<<<wgs[5], 64 * ls.h_waves, lds_tier_h(ls.h_waves), ms>>>(db, sc); });
 #endif
-    stage(e, ms, "poa", [&] { cw_poa_kernel<<<wgs[0], 64 * CW_POA_WAVES, kLdsTierS, ms>>>(db, sc); }); /* 11.3 KiB per wave: three work-groups per CU */
+    stage(e, ms, "poa", [&] { cw_poa_kernel<<<wgs[0], 64 * CW_POA_WAVES, kLdsTierS, ms>>>(db, sc); }); /* CW_POA_SLAB_BYTES (about 7.7 KB) per wave */
     if (ms != st) { CW_HIP(hipEventRecord(e->ev_join_s, ms)); CW_HIP(hipStreamWaitEvent(st, e->ev_join_s, 0)); }
     for (int i = 0; i < 3; ++i) { CW_HIP(hipEventRecord(e->ev_join[i], e->side[i])); CW_HIP(hipStreamWaitEvent(st, e->ev_join[i], 0)); }
     /* pass 1: tasks that outgrew their tier (normally a handful) go straight to tier L, and from there to G */
@@ -917,6 +924,7 @@ void cw_destroy(cw_engine* e) {
     if (e->poa_out) (void)hipFree(e->poa_out);
     if (e->step_clock) (void)hipFree(e->step_clock);
     if (e->stitch_scratch) (void)hipFree(e->stitch_scratch);
+    if (e->emitted) (void)hipFree(e->emitted);
     if (e->host_fb) (void)hipHostFree(e->host_fb);
     for (int i = 0; i < CW_MAX_STAGES; ++i) { if (e->ev0[i]) (void)hipEventDestroy(e->ev0[i]); if (e->ev1[i]) (void)hipEventDestroy(e->ev1[i]); }
     for (int i = 0; i < 3; ++i) { if (e->ev_join[i]) (void)hipEventDestroy(e->ev_join[i]); if (e->side[i]) (void)hipStreamDestroy(e->side[i]); }
@@ -1601,6 +1609,29 @@ int cw_debug_tier_q(cw_engine* e, uint32_t* out3) {
     BatchCounters c;
     if (int rc = read_counters_idle(e, &c)) return rc;
     out3[0] = c.q_split; out3[1] = c.q_short_done; out3[2] = c.q_short_on;
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): one routed list of the last run after the tier sort, the same list as it was emitted where the run kept it, and the batch's
+ * task records.  Host code only. */
+int cw_debug_tier_lists(cw_engine* e, uint32_t list, uint32_t* sorted, uint32_t* emitted, uint32_t cap, uint32_t* n, uint32_t* kept, uint32_t* tasks4, uint32_t task_cap,
+                        uint32_t* n_tasks) {
+    if (!e || !e->scratch || !n || !kept || !n_tasks || list >= (uint32_t)CW_TIERS || list == (uint32_t)CW_POAX_LIST || (cap && (!sorted || !emitted)) || (task_cap && !tasks4)) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    BatchCounters c;
+    if (int rc = read_counters_idle(e, &c)) return rc;
+    const uint8_t* base = (const uint8_t*)e->scratch;
+    const uint32_t have = c.n_tier[list] < e->last_task_cap ? c.n_tier[list] : e->last_task_cap; /* clamped, as the sort and the tiers clamp it */
+    *n = have; *kept = e->emitted_cap ? 1u : 0u;
+    const uint32_t take = have < cap ? have : cap;
+    if (take) CW_HIP(hipMemcpy(sorted, base + e->last_list_off[list], (size_t)take * 4, hipMemcpyDeviceToHost));
+    if (take && e->emitted_cap) CW_HIP(hipMemcpy(emitted, (const uint32_t*)e->emitted + (size_t)list * e->emitted_cap, (size_t)take * 4, hipMemcpyDeviceToHost));
+    const uint32_t nt = c.n_tasks < e->last_task_cap ? c.n_tasks : e->last_task_cap;
+    *n_tasks = nt;
+    const uint32_t tt = nt < task_cap ? nt : task_cap;
+    std::vector<PoaTask> tasks(tt);
+    if (tt) CW_HIP(hipMemcpy(tasks.data(), base + e->last_tasks_off, (size_t)tt * sizeof(PoaTask), hipMemcpyDeviceToHost));
+    for (uint32_t t = 0; t < tt; ++t) { uint32_t* o = tasks4 + (size_t)t * 4; o[0] = tasks[t].window; o[1] = tasks[t].seg_slot; o[2] = tasks[t].n_members; o[3] = tasks[t].max_len; }
     return CW_OK;
 }
 

@@ -82,6 +82,10 @@ struct cw_engine {
     size_t last_ablock_off = 0; uint64_t last_ablock_units = 0; /* the last run's anchor blocks (cw_debug_anchor_block) */
     const uint32_t* last_win_first_seq = nullptr;          /* the last run's window -> first sequence array, a device pointer (the caller's in cw_run_device) */
     uint32_t last_task_cap = 0;
+    size_t last_list_off[6] = {}; /* the last run's routed lists, by list index (cw_debug_tier_lists) */
+    void* emitted = nullptr;      /* a -DCW_TEST_AIDS build with CW_KEEP_EMITTED: the routed lists as they were emitted, copied in front of the tier sort */
+    size_t emitted_bytes = 0;
+    uint32_t emitted_cap = 0;     /* entries per list in it; 0: the last run kept none */
 };
 
 extern "C" int cw_extract_impl(cw_engine* e, const cw_read_set* reads, const cw_overlap* overlaps, uint64_t n_overlaps, const cw_window_job* jobs,

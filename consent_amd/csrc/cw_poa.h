@@ -1858,8 +1858,7 @@ cw_poa_slab_kernel(DevBatch b, DevScratch sc) {
 #define CW_POAQ8_ROUTE_NODES 36 /* a short task is expected (the depth-aware estimate of cw_poa_route) to stay below this many nodes: 0.9 x NC8, as 60 stands to 64 */
 #endif
 #define CW_SORT_COST_CLASSES 128            /* classes of one key */
-#define CW_SORT_CLASSES (CW_POAQ8 ? 256 : 128) /* tier Q: the classes of the long tasks, then the same classes of the short ones (a class is a byte between the two passes) */
-#define CW_SORT_LDS_CLS 131072 /* classes of the first so many list entries are kept in LDS between the two passes */
+#define CW_SORT_CLASSES (CW_POAQ8 ? 256 : 128) /* tier Q: the classes of the long tasks, then the same classes of the short ones (a class is the top byte of a list entry from its emission to the sort: cw_list_entry) */
 __device__ __forceinline__ bool cw_poaq_is_short(uint32_t n_members, uint32_t max_len) {
     return CW_POAQ8 && max_len <= (uint32_t)CW_POAQ8_LC && (max_len * (15u + n_members / 5u) + 9u) / 10u <= (uint32_t)CW_POAQ8_ROUTE_NODES;
 }
@@ -1897,45 +1896,54 @@ __device__ __forceinline__ uint32_t cw_sort_class(uint32_t n_members, uint32_t l
     }
     return (CW_SORT_COST_CLASSES - 1) - (c < CW_SORT_COST_CLASSES ? c : CW_SORT_COST_CLASSES - 1); /* class 0 = the largest */
 }
-__global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc, uint32_t lds_cls) {
+/* A routed list's entry from its emission (the chain kernel's flush, cw_poa_tasks_kernel) to the tier sort: the task index, and in the top byte the class
+   the sort orders by -- whoever emits the entry has the class's inputs in registers, and the sort then reads nothing but its list.  `list` is the list's index
+   (0 = tier Q's, 5 = tier H's).  A plan with more than CW_LIST_IDX_MASK task slots (DevScratch::list_cls == 0) emits plain indices. */
+#define CW_LIST_CLS_SHIFT 24
+#define CW_LIST_IDX_MASK 0x00FFFFFFu
+static_assert(CW_SORT_CLASSES <= 256, "a class is the entry's top byte");
+__device__ __forceinline__ uint32_t cw_list_entry(const DevScratch& sc, uint32_t ti, uint32_t n_members, uint32_t len_pair, int list) {
+    return sc.list_cls ? ti | (cw_sort_class(n_members, len_pair, list) << CW_LIST_CLS_SHIFT) : ti;
+}
+__global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc) {
     __shared__ uint32_t cnt[16][CW_SORT_CLASSES];
     __shared__ uint32_t tot_c[CW_SORT_CLASSES];
-    extern __shared__ __attribute__((aligned(16))) uint8_t cls_lds[]; /* lds_cls bytes (<= CW_SORT_LDS_CLS) */
     const int tier = blockIdx.x == 3 ? 0 : blockIdx.x == 4 ? 5 : 1 + (int)blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63; /* 0 = tier Q's list, 5 = tier H's */
     if (blockIdx.x == 0 && threadIdx.x == 0) sc.ctr->prof[CW_PS_SORT_CLOCK] = wall_clock64(); /* time base of the task trace */
     const uint32_t n = min(sc.ctr->n_tier[tier], sc.list_cap);
     const uint32_t nthr = blockDim.x, nwv = nthr >> 6; /* 4 .. 16 waves: a small work-group finds room beside another batch's persistent kernels */
     uint32_t* list = sc.tier_list[tier];
     uint32_t* tmp = sc.over_list[tier];
-    if (n < 2) { /* nothing to order; tier Q's split is still owed: 0 or 1 long entries */
-        if (tier == 0 && threadIdx.x == 0) {
+    const bool in_entry = sc.list_cls != 0u; /* else: the class from the task record, a dependent read per entry in both passes */
+    auto class_of = [&](uint32_t entry) -> uint32_t {
+        if (in_entry) return entry >> CW_LIST_CLS_SHIFT;
+        const uint2 v = *(const uint2*)&sc.tasks[entry].n_members; /* n_members, max_len */
+        return cw_sort_class(v.x, v.y, tier);
+    };
+    const uint32_t idx_mask = in_entry ? CW_LIST_IDX_MASK : 0xFFFFFFFFu;
+    if (n < 2) { /* nothing to order: the one entry becomes a plain task index; tier Q's split is still owed: 0 or 1 long entries */
+        if (threadIdx.x == 0) {
             uint32_t split = n;
-            if (CW_POAQ8 && n == 1) { const uint2 v = *(const uint2*)&sc.tasks[list[0]].n_members; split = cw_poaq_is_short(v.x, v.y & 0xFFFFu) ? 0u : 1u; }
-            sc.ctr->q_split = split;
+            if (n == 1) {
+                const uint32_t en = list[0];
+                if (CW_POAQ8 && tier == 0) split = class_of(en) >= (uint32_t)CW_SORT_COST_CLASSES ? 0u : 1u;
+                list[0] = en & idx_mask;
+            }
+            if (tier == 0) sc.ctr->q_split = split;
         }
         return;
     }
     if (!CW_POAQ8 && tier == 0 && threadIdx.x == 0) sc.ctr->q_split = n; /* every task is long */
     for (uint32_t x = threadIdx.x; x < 16 * CW_SORT_CLASSES; x += nthr) (&cnt[0][0])[x] = 0;
     __syncthreads();
-    /* every wave owns a contiguous slice of the list in both passes; eight entries per lane in flight (two dependent global reads each) */
+    /* every wave owns a contiguous slice of the list in both passes; eight entries per lane in flight, coalesced */
     const uint32_t per = (n + nwv - 1u) / nwv, lo = min(n, (uint32_t)wave * per), hi = min(n, lo + per);
     for (uint32_t x0 = lo; x0 < hi; x0 += 512) {
-        uint32_t ti[8];
-        uint2 nm[8];
+        uint32_t en[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const uint32_t x = x0 + (uint32_t)j * 64u + (uint32_t)lane; ti[j] = x < hi ? list[x] : 0xFFFFFFFFu; }
+        for (int j = 0; j < 8; ++j) { const uint32_t x = x0 + (uint32_t)j * 64u + (uint32_t)lane; en[j] = x < hi ? list[x] : 0xFFFFFFFFu; }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) nm[j] = ti[j] != 0xFFFFFFFFu ? *(const uint2*)&sc.tasks[ti[j]].n_members : make_uint2(0, 0); /* n_members, max_len */
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint32_t x = x0 + (uint32_t)j * 64u + (uint32_t)lane;
-            if (ti[j] != 0xFFFFFFFFu) {
-                const uint32_t c = cw_sort_class(nm[j].x, nm[j].y, tier);
-                atomicAdd(&cnt[wave][c], 1u);
-                if (x < lds_cls) cls_lds[x] = (uint8_t)c;
-            }
-        }
+        for (int j = 0; j < 8; ++j) { const uint32_t x = x0 + (uint32_t)j * 64u + (uint32_t)lane; if (x < hi) atomicAdd(&cnt[wave][class_of(en[j])], 1u); }
     }
     __syncthreads();
     for (uint32_t k = threadIdx.x; k < CW_SORT_CLASSES; k += nthr) { uint32_t t = 0; for (uint32_t w = 0; w < nwv; ++w) t += cnt[w][k]; tot_c[k] = t; } /* (a work-group may have fewer threads than there are classes) */
@@ -1948,18 +1956,13 @@ __global__ void __launch_bounds__(1024) cw_sort_tier_kernel(DevScratch sc, uint3
     }
     __syncthreads();
     for (uint32_t x0 = lo; x0 < hi; x0 += 512) {
-        uint32_t ti[8];
+        uint32_t en[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const uint32_t x = x0 + (uint32_t)j * 64u + (uint32_t)lane; ti[j] = x < hi ? list[x] : 0xFFFFFFFFu; }
+        for (int j = 0; j < 8; ++j) { const uint32_t x = x0 + (uint32_t)j * 64u + (uint32_t)lane; en[j] = x < hi ? list[x] : 0xFFFFFFFFu; }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const uint32_t x = x0 + (uint32_t)j * 64u + (uint32_t)lane;
-            if (ti[j] != 0xFFFFFFFFu) {
-                uint32_t c;
-                if (x < lds_cls) c = cls_lds[x];
-                else { const uint2 v = *(const uint2*)&sc.tasks[ti[j]].n_members; c = cw_sort_class(v.x, v.y, tier); }
-                tmp[atomicAdd(&cnt[wave][c], 1u)] = ti[j];
-            }
+            if (x < hi) tmp[atomicAdd(&cnt[wave][class_of(en[j])], 1u)] = en[j] & idx_mask; /* plain task indices from here on */
         }
     }
     __threadfence_block();

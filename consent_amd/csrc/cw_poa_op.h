@@ -91,10 +91,10 @@ __global__ void __launch_bounds__(64 * CW_POAOP_WAVES) cw_poa_tasks_kernel(DevBa
         if (poa && fits) {
             t.n_members = n; t.max_len = mx | ((sum / n) << 16); /* longest member | mean member length: what the tier sort goes by (cw_chain.h) */
             t.state = tier ? 2u : 0u; /* 0 = tier S takes it from the task array; anything else is on a list */
-            if (tier) sc.tier_list[tier == 4u ? 0 : tier][li] = g;
+            if (tier) sc.tier_list[tier == 4u ? 0 : tier][li] = cw_list_entry(sc, g, t.n_members, t.max_len, tier == 4u ? 0 : (int)tier); /* with its sort class, as the chain kernel's flush emits it */
         } else { /* nothing to align: a finished task without members */
             t.n_members = 0; t.max_len = 0; t.state = 1u;
-            if (tier != 0xFFu && tier != 0u && li < sc.list_cap) sc.tier_list[tier == 4u ? 0 : tier][li] = sc.task_cap;
+            if (tier != 0xFFu && tier != 0u && li < sc.list_cap) sc.tier_list[tier == 4u ? 0 : tier][li] = cw_list_entry(sc, sc.task_cap, 0u, 0u, tier == 4u ? 0 : (int)tier);
         }
         sc.tasks[g] = t;
         sc.seg_off[g] = off; sc.seg_len[g] = (n == 1u && !stop && fits) ? mx : 0u;

@@ -83,6 +83,13 @@ int cw_debug_profile(cw_engine* e, uint32_t* counters, uint32_t counters_cap, un
  * CW_WHY_POA), the largest alignment it was asked for in int32 cells (three layers under the affine gap model) */
 int cw_debug_tier_x(cw_engine* e, uint32_t* out4);
 int cw_debug_tier_q(cw_engine* e, uint32_t* out3); /* tier Q's split (long entries of its list), short tasks finished by the eight-lane loop, short tasks handed on */
+/* One routed list of the last run (list: 0 tier Q's, 1 M1, 2 M2, 3 L, 5 H): *n its entries, the first min(*n, cap) of them in `sorted` as the tier sort left
+ * them (plain task indices) and -- *kept = 1: a -DCW_TEST_AIDS build run with CW_KEEP_EMITTED set; otherwise 0 -- in `emitted` as the chain kernel
+ * (cw_poa_tasks_kernel) wrote them: task index | sort class << 24.  tasks4: four words per task record of the batch in the order of the task array -- window,
+ * segment slot, n_members, longest member | mean member length << 16 (what the class is computed from); *n_tasks of them, the first task_cap copied.  A task
+ * index equal to the plan's task capacity (cw_debug_plan_caps [7]) names the batch's neutral task. */
+int cw_debug_tier_lists(cw_engine* e, uint32_t list, uint32_t* sorted, uint32_t* emitted, uint32_t cap, uint32_t* n, uint32_t* kept, uint32_t* tasks4, uint32_t task_cap,
+                        uint32_t* n_tasks);
 
 /* with CW_TASK_TRACE set in the environment: 12 words per POA task of the last run (see cw_engine.cpp); tier 6 = tier X */
 int cw_debug_task_trace(cw_engine* e, uint32_t cap_tasks, uint32_t* out12, uint32_t* n_tasks);

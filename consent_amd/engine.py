@@ -148,6 +148,10 @@ class SynthSpec(C.Structure):
         return cls(seed, first_window, n_windows, depth, window_len, 120, 30, 30, 40, (window_len + 60) // 16 + 2)
 
 
+TIER_LISTS = {"Q": 0, "M1": 1, "M2": 2, "L": 3, "H": 5}  # the routed lists by index (csrc/cw_chain.h ch_list_id); tier S has none: it walks the task array
+LIST_CLS_SHIFT, LIST_IDX_MASK = 24, 0x00FFFFFF      # an emitted entry: task index | sort class << 24 (csrc/cw_poa.h cw_list_entry)
+
+
 def lib_path():
     """The in-tree library; CONSENT_AMD_LIB names another build of the same sources (tests/test_gpu_policy.py: a non-default policy)."""
     return os.environ.get("CONSENT_AMD_LIB") or os.path.join(_HERE, "libconsent_amd.so")
@@ -256,6 +260,9 @@ def _load(p):
         lib.cw_debug_tier_x.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "cw_debug_tier_q"):
         lib.cw_debug_tier_q.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "cw_debug_tier_lists"):
+        lib.cw_debug_tier_lists.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32,
+                                            C.POINTER(C.c_uint32)]
     if hasattr(lib, "cw_debug_solid_table"):
         lib.cw_debug_solid_table.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     if hasattr(lib, "cw_debug_anchor_block"):
@@ -1554,6 +1561,22 @@ class Engine:
         c = np.zeros(3, np.uint32)
         _check(self.lib, self.lib.cw_debug_tier_q(self.handle, _ptr(c)), "cw_debug_tier_q")
         return {"split": int(c[0]), "short_done": int(c[1]), "short_handed_on": int(c[2])}
+
+    def tier_lists(self):
+        """cw_debug_tier_lists: the routed lists of the last run and its task records -- (lists, tasks).  lists[name] for name in TIER_LISTS is (sorted, emitted):
+        the list as the tier sort left it (plain task indices) and as it was emitted (task index | sort class << 24), the latter None unless the test-aid
+        library ran with CW_KEEP_EMITTED set.  tasks[t] = (window, segment slot, n_members, longest member | mean member length << 16)."""
+        n, ne, nt = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(self.lib, self.lib.cw_debug_tier_lists(self.handle, 0, None, None, 0, C.byref(n), C.byref(ne), None, 0, C.byref(nt)), "cw_debug_tier_lists")
+        tasks = np.zeros((max(nt.value, 1), 4), np.uint32)
+        lists = {}
+        for name, li in TIER_LISTS.items():
+            _check(self.lib, self.lib.cw_debug_tier_lists(self.handle, li, None, None, 0, C.byref(n), C.byref(ne), None, 0, C.byref(nt)), "cw_debug_tier_lists")
+            srt, emi = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
+            _check(self.lib, self.lib.cw_debug_tier_lists(self.handle, li, _ptr(srt), _ptr(emi), len(srt), C.byref(n), C.byref(ne), _ptr(tasks), len(tasks), C.byref(nt)),
+                   "cw_debug_tier_lists")
+            lists[name] = (srt[: n.value], emi[: n.value] if ne.value else None)
+        return lists, tasks[: nt.value]
 
     def solid_table(self, w):
         """cw_debug_solid_table: (keys, counts) of window w of the last run -- the index kernel's ascending solid k-mers and their exact pile-wide counts."""
