@@ -7,7 +7,8 @@
  * cw_poa_run: kernels in cw_poa_op.h, the same enqueue_poa_stage as a window run); the re-assembly's local aligner alone on a batch of groups
  * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h; cw_pileup_run_device, cw_pileup_run: cw_pileup.h; cw_sw_cut_run_device, cw_sw_cut_run,
  * cw_cut_groups_device: cw_sw_cut.h); both strands for them (cw_strand_run_device, cw_strand_run, cw_revcomp_device, cw_revcomp: cw_strand.h); reads placed on
- * their reference (cw_seed_run_device, cw_seed_run, cw_seed_spans_device, cw_seed_spans: cw_seed.h).
+ * their reference (cw_seed_run_device, cw_seed_run, cw_seed_spans_device, cw_seed_spans: cw_seed.h), or through an index of the whole reference
+ * (cw_locate_build_device, cw_locate_run_device, cw_locate_run: cw_locate.h).
  * What the operators' entry points share exists once, in the anonymous namespace: Layout (arrays 256-byte aligned in one allocation), locked (a _device entry
  * point is its run_*_locked body under the engine's mutex), dev_batch (cw_batch -> DevBatch), run_begin / run_end (the bracket round the stages of every run,
  * a window run's included) and HostTrip (a host form's round trip: lock, check_groups, the output layout, upload_groups, up / down / sync); each host form
@@ -33,6 +34,7 @@
 #include "cw_sw_cut.h"
 #include "cw_strand.h"
 #include "cw_seed.h"
+#include "cw_locate.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -855,6 +857,68 @@ int run_seed_spans_locked(cw_engine* e, const cw_batch* groups, const int32_t* s
     return run_end(e, st);
 }
 
+/* ---- reads placed through an index of the whole reference: cw_locate_* ---------------------------------------------------------------------------------------- */
+
+int validate_locate_ref(const cw_engine* e, const cw_locate_ref* ref) {
+    if (!e || !ref || !ref->table || (ref->len > 0 && !ref->bases) || ref->len > CW_LOCATE_RMAX) return CW_E_INVALID;
+    if (ref->k != 0u && (ref->k < CW_STRAND_KMIN || ref->k > CW_STRAND_KMAX)) return CW_E_INVALID;
+    return CW_OK;
+}
+
+int validate_locate(const cw_engine* e, const cw_locate_ref* ref, const cw_batch* reads, const cw_seeds* out) {
+    if (int rc = validate_locate_ref(e, ref)) return rc;
+    if (!reads || !out || !out->rows) return CW_E_INVALID;
+    if (out->k != 0u && out->k != (ref->k ? ref->k : CW_LOCATE_K)) return CW_E_INVALID;
+    if (reads->n_seqs != 0 && (!reads->seq_len || !reads->seq_word_off || !reads->bases)) return CW_E_INVALID;
+    return CW_OK;
+}
+
+LocateRefArgs locate_ref_args(const cw_locate_ref* ref) {
+    LocateRefArgs r;
+    r.ref = ref->bases; r.n = (uint32_t)ref->len; r.table = ref->table; r.bits = cw_loc_table_bits(ref->len); r.k = ref->k ? ref->k : CW_LOCATE_K;
+    return r;
+}
+
+/* the body of cw_locate_build_device; the caller holds e->mu.  One stage: locate_build, the clear and the inserts.  No scratch, as the reverse complement. */
+int run_locate_build_locked(cw_engine* e, const cw_locate_ref* ref, void* hip_stream) {
+    int rc = validate_locate_ref(e, ref);
+    if (rc) return rc;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    const LocateRefArgs r = locate_ref_args(ref);
+    const uint64_t positions = r.n >= r.k ? (uint64_t)r.n - r.k + 1u : 0u;
+    const uint32_t wgs = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>((positions + 255u) / 256u, (uint64_t)e->cus * 32u));
+    if ((rc = run_begin(e, st, false)) != CW_OK) return rc;
+    hipError_t cleared = hipSuccess;
+    stage(e, st, "locate_build", [&] {
+        cleared = hipMemsetAsync(r.table, 0xFF, ((size_t)1 << r.bits) * 4, st); /* CW_STR_EMPTY in every slot */
+        cw_locate_build_kernel<<<wgs, 256, 0, st>>>(r);
+    });
+    CW_HIP(cleared);
+    return run_end(e, st);
+}
+
+/* the body of cw_locate_run_device; the caller holds e->mu.  Stages: locate (every read, the votes in LDS), locate_dense (the reads that route abandoned). */
+int run_locate_locked(cw_engine* e, const cw_locate_ref* ref, const cw_batch* reads, const cw_seeds* out, void* hip_stream) {
+    int rc = validate_locate(e, ref, reads, out);
+    if (rc || reads->n_seqs == 0) return rc;
+    const LocatePlan p = plan_locate(reads->n_seqs, e->cus); /* exact: the batch runs once */
+    hipStream_t st;
+    if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
+    if (!e->locate_routes) CW_HIP(hipMalloc((void**)&e->locate_routes, 8));
+    uint8_t* base = (uint8_t*)e->scratch;
+    LocateArgs a;
+    a.r = locate_ref_args(ref);
+    a.n_seqs = reads->n_seqs; a.seq_len = reads->seq_len; a.seq_word_off = reads->seq_word_off; a.bases = reads->bases;
+    a.rows = out->rows; a.strand = out->strand;
+    a.ctr = (uint32_t*)(base + p.ctr); a.redo = (uint32_t*)(base + p.redo); a.dense = (uint32_t*)(base + p.dense); a.routes = e->locate_routes;
+    if ((rc = run_begin(e, st, true)) != CW_OK) return rc;
+    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_LOC_CTR_WORDS * 4, st));
+    stage(e, st, "locate", [&] { cw_locate_kernel<0><<<p.wgs, CW_LOC_THREADS, 0, st>>>(a); });
+    stage(e, st, "locate_dense", [&] { cw_locate_kernel<1><<<p.wgs_dense, CW_LOC_THREADS, 0, st>>>(a); });
+    return run_end(e, st);
+}
+
 } // namespace
 
 extern "C" {
@@ -925,6 +989,8 @@ void cw_destroy(cw_engine* e) {
     if (e->step_clock) (void)hipFree(e->step_clock);
     if (e->stitch_scratch) (void)hipFree(e->stitch_scratch);
     if (e->emitted) (void)hipFree(e->emitted);
+    if (e->locate_tab) (void)hipFree(e->locate_tab);
+    if (e->locate_routes) (void)hipFree(e->locate_routes);
     if (e->host_fb) (void)hipHostFree(e->host_fb);
     for (int i = 0; i < CW_MAX_STAGES; ++i) { if (e->ev0[i]) (void)hipEventDestroy(e->ev0[i]); if (e->ev1[i]) (void)hipEventDestroy(e->ev1[i]); }
     for (int i = 0; i < 3; ++i) { if (e->ev_join[i]) (void)hipEventDestroy(e->ev_join[i]); if (e->side[i]) (void)hipStreamDestroy(e->side[i]); }
@@ -1273,6 +1339,69 @@ int cw_debug_strand_plan(uint32_t n_groups, uint32_t n_seqs, int cus, uint64_t* 
     const StrandPlan p = plan_strand(n_groups, n_seqs, cus);
     const uint64_t v[5] = {p.total, (uint64_t)p.unit_off, (uint64_t)(p.total - p.unit_off), p.wgs, p.wgs_wide};
     for (int i = 0; i < 5; ++i) out5[i] = v[i];
+    return CW_OK;
+}
+
+uint64_t cw_locate_table_words(uint64_t ref_len) { return ref_len > CW_LOCATE_RMAX ? 0u : (uint64_t)1 << cw_loc_table_bits(ref_len); }
+
+int cw_locate_build_device(cw_engine* e, const cw_locate_ref* ref, void* hip_stream) {
+    return locked(e, [&] { return run_locate_build_locked(e, ref, hip_stream); });
+}
+
+int cw_locate_run_device(cw_engine* e, const cw_locate_ref* ref, const cw_batch* reads, const cw_seeds* out, void* hip_stream) {
+    return locked(e, [&] { return run_locate_locked(e, ref, reads, out, hip_stream); });
+}
+
+/* The reference goes up behind the reads, the index is built into the engine's own table, the rows and -- when asked for -- the strand bytes come back.  The
+   reads travel as one group: their grouping is not read, so the caller's is not looked at. */
+int cw_locate_run(cw_engine* e, const uint32_t* ref_bases, uint64_t ref_len, uint32_t k, const cw_batch* reads, const cw_seeds* out) {
+    if (!e) return CW_E_INVALID;
+    uint32_t dummy_table = 0; /* (validation asks for a table: the engine's is held below) */
+    cw_locate_ref ref;
+    ref.bases = ref_bases; ref.len = ref_len; ref.table = &dummy_table; ref.k = k;
+    const uint32_t one_group[2] = {0u, reads ? reads->n_seqs : 0u};
+    cw_batch one;
+    memset(&one, 0, sizeof(one));
+    if (reads) { one = *reads; one.n_windows = 1; one.win_first_seq = one_group; }
+    HostTrip t(e, &one);
+    int rc = validate_locate(e, &ref, reads, out);
+    if (rc || reads->n_seqs == 0) return rc;
+    if ((rc = t.check_groups(nullptr)) != CW_OK) return rc;
+    const uint32_t S = reads->n_seqs;
+    const size_t ref_bytes = (size_t)((ref_len + 15) / 16) * 4, table_bytes = (size_t)cw_locate_table_words(ref_len) * 4;
+    const size_t row_bytes = (size_t)S * CW_SEED_ROW * 4, o_rows = t.out.put(row_bytes), o_strand = t.out.put(out->strand ? (size_t)S : 0), o_ref = t.out.put(ref_bytes + 4);
+    CW_HIP(hipSetDevice(e->device));
+    if ((rc = ensure(&e->locate_tab, &e->locate_tab_bytes, table_bytes)) != CW_OK) return rc;
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
+    CW_HIP(t.up(o_ref, ref_bases, ref_bytes));
+    ref.bases = t.at<uint32_t>(o_ref); ref.table = (uint32_t*)e->locate_tab;
+    cw_seeds ds;
+    ds.rows = t.at<int32_t>(o_rows); ds.strand = out->strand ? t.at<uint8_t>(o_strand) : nullptr; ds.k = out->k;
+    if ((rc = run_locate_build_locked(e, &ref, t.st)) != CW_OK) return rc;
+    if ((rc = run_locate_locked(e, &ref, &t.db, &ds, t.st)) != CW_OK) return rc;
+    CW_HIP(t.down(out->rows, o_rows, row_bytes));
+    if (out->strand) CW_HIP(t.down(out->strand, o_strand, S));
+    CW_HIP(t.sync());
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): what plan_locate would allocate and its grids (host arithmetic only). */
+int cw_debug_locate_plan(uint32_t n_seqs, int cus, uint64_t* out6) {
+    if (!out6 || cus < 1) return CW_E_INVALID;
+    const LocatePlan p = plan_locate(n_seqs, cus);
+    const uint64_t v[6] = {p.total, (uint64_t)(p.redo - p.ctr), (uint64_t)(p.dense - p.redo), (uint64_t)(p.total - p.dense), p.wgs, p.wgs_dense};
+    for (int i = 0; i < 6; ++i) out6[i] = v[i];
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): the two words the last locate run's dense launch wrote, once everything on the device has ended. */
+int cw_debug_locate_routes(cw_engine* e, uint32_t* out2) {
+    if (!e || !out2) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->locate_routes) return CW_E_INVALID;
+    CW_HIP(hipSetDevice(e->device));
+    CW_HIP(hipDeviceSynchronize());
+    CW_HIP(hipMemcpy(out2, e->locate_routes, 8, hipMemcpyDeviceToHost));
     return CW_OK;
 }
 

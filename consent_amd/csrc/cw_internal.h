@@ -59,6 +59,9 @@ struct cw_engine {
     void* stitch_scratch = nullptr; /* banded-traceback directions of cw_stitch_device, per wave */
     size_t stitch_scratch_bytes = 0;
     size_t stitch_route_off = 0; /* where in xscratch the last cw_stitch_device call put its route witness (a -DCW_TEST_AIDS build with CW_STITCH_TRACE); 0: none */
+    void* locate_tab = nullptr; /* cw_locate_run's index of the caller's reference: the host form builds into device memory of its own */
+    size_t locate_tab_bytes = 0;
+    uint32_t* locate_routes = nullptr; /* the reads of each route in the last locate run (cw_debug_locate_routes): two words the dense launch writes */
     cw_host_fb* host_fb = nullptr;
     /* per-stage timing of the last run */
     hipStream_t side[3] = {nullptr, nullptr, nullptr}; /* POA tiers run concurrently on their own streams (M1, M2, L) */

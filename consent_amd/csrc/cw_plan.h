@@ -13,6 +13,7 @@
 #include "cw_sw_path.h" /* the alignment operator's per-wave sizes, the path run's too (cw_sw_op.h and cw_stitch.h come with it) */
 #include "cw_strand.h" /* the strand vote's chunk sizes */
 #include "cw_seed.h"   /* the seed run's LDS, which bounds its work-groups a CU */
+#include "cw_locate.h" /* the locate run's LDS and the dense route's table */
 #include "cw_finish.h" /* CW_FIN_*.  (These three are kernel headers, taken for their size macros: nothing here runs on the device, but a translation unit that includes this one is still a HIP one) */
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -274,6 +275,25 @@ static inline StrandPlan plan_strand(uint32_t n_groups, uint32_t n_seqs, int cus
 static inline StrandPlan plan_seed(uint32_t n_groups, uint32_t n_seqs, int cus) {
     StrandPlan p = plan_strand(n_groups, n_seqs, cus);
     p.wgs = (uint32_t)std::min<uint64_t>(p.wgs, (uint64_t)cus * 6u);
+    return p;
+}
+
+/* The plan of a locate run (cw_locate_run_device, cw_locate.h), exact: the counters, the redo list -- every read can be on it -- and one dense table per work-group
+   of the dense launch.  The LDS launch: a work-group a read, at most six a CU (24 KB each).  The dense launch: at most CW_LOC_DENSE_WGS work-groups -- the route is
+   meant to be rare, and a table is 768 KB. */
+#define CW_LOC_DENSE_WGS 64u
+struct LocatePlan { size_t ctr, redo, dense, total; uint32_t wgs, wgs_dense; };
+static inline LocatePlan plan_locate(uint32_t n_seqs, int cus) {
+    LocatePlan p;
+    memset(&p, 0, sizeof(p));
+    p.wgs = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_seqs, (uint64_t)cus * 6u));
+    p.wgs_dense = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_seqs, CW_LOC_DENSE_WGS));
+    size_t o = 0;
+    auto put = [&](size_t& slot, size_t bytes) { slot = o; o = align_up(o + bytes, 256); };
+    put(p.ctr, (size_t)CW_LOC_CTR_WORDS * 4);
+    put(p.redo, (size_t)n_seqs * 4);
+    put(p.dense, (size_t)p.wgs_dense * CW_LOC_DENSE_WORDS * 4);
+    p.total = o;
     return p;
 }
 

@@ -63,6 +63,12 @@ int cw_debug_sw_path_plan(uint32_t n_groups, uint32_t n_seqs, uint64_t n_words, 
 int cw_debug_strand_plan(uint32_t n_groups, uint32_t n_seqs, int cus, uint64_t* out5);
 /* The same of a seed run (cw_seed_run): plan_strand's arithmetic, the narrow launch at most six work-groups a CU. */
 int cw_debug_seed_plan(uint32_t n_groups, uint32_t n_seqs, int cus, uint64_t* out5);
+/* The scratch plan of a locate run (cw_locate_run_device) of n_seqs reads, without a device: out[0] total bytes, [1] the counters, [2] the redo list, [3] the
+   dense route's tables, [4] [5] work-groups of the LDS and the dense launch. */
+int cw_debug_locate_plan(uint32_t n_seqs, int cus, uint64_t* out6);
+/* The reads each route took in the engine's last locate run: out[0] the LDS route (the reads without a vote among them), out[1] the dense route.  Waits for the
+   device.  CW_E_INVALID before the first locate run. */
+int cw_debug_locate_routes(cw_engine* e, uint32_t* out2);
 /* cw_max_batch_windows of an engine that cw_configure(max_template_len) will be called on (the native driver sizes its jobs before it has engines) */
 uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len);
 

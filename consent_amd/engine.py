@@ -34,6 +34,9 @@ SEED_STATUS, SEED_HITS, SEED_DIAG, SEED_OTHER, SEED_ROW = 0, 1, 2, 3, 4
 SEED_SHIFT = 6
 SEED_SPAN = 2 << SEED_SHIFT
 SEED_MIN_HITS, SEED_MIN_K = 14, 11  # (the threshold holds from this k up)
+# cw_locate_*: the default k, the longest reference; Engine.locate's default threshold and the k it is measured for (its docstring has the measurement)
+LOCATE_K, LOCATE_RMAX = 15, (1 << 28) - 1
+LOCATE_MIN_HITS, LOCATE_MIN_K = 4, 15
 # cw_seed_spans: a placed query's span is its window's diagonals over the whole query, widened by SPAN_PAD + (query length >> SPAN_PAD_SHIFT) on either side;
 # the shift is measured (tests/test_sw_span_cpu.py)
 SPAN_PAD, SPAN_PAD_SHIFT = 64, 4
@@ -101,6 +104,12 @@ class Seeds(C.Structure):
     """cw_seeds: the outputs of cw_seed_run (strand may be NULL) and k (0 = STRAND_K)."""
 
     _fields_ = [("rows", C.c_void_p), ("strand", C.c_void_p), ("k", C.c_uint32)]
+
+
+class LocateRef(C.Structure):
+    """cw_locate_ref: the packed reference, its length, the caller's table of cw_locate_table_words(len) words, and k (0 = LOCATE_K)."""
+
+    _fields_ = [("bases", C.c_void_p), ("len", C.c_uint64), ("table", C.c_void_p), ("k", C.c_uint32)]
 
 
 class SwSpans(C.Structure):
@@ -233,6 +242,14 @@ def _load(p):
         lib.cw_seed_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Seeds)]
         lib.cw_seed_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Seeds), C.c_void_p]
         lib.cw_debug_seed_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
+    if hasattr(lib, "cw_locate_run"):
+        lib.cw_locate_table_words.argtypes = [C.c_uint64]
+        lib.cw_locate_table_words.restype = C.c_uint64
+        lib.cw_locate_build_device.argtypes = [C.c_void_p, C.POINTER(LocateRef), C.c_void_p]
+        lib.cw_locate_run_device.argtypes = [C.c_void_p, C.POINTER(LocateRef), C.POINTER(Batch), C.POINTER(Seeds), C.c_void_p]
+        lib.cw_locate_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(Batch), C.POINTER(Seeds)]
+        lib.cw_debug_locate_plan.argtypes = [C.c_uint32, C.c_int, C.c_void_p]
+        lib.cw_debug_locate_routes.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "cw_sw_span_run"):
         lib.cw_sw_span_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwSpans), C.c_uint32]
         lib.cw_sw_span_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwSpans), C.c_uint32, C.c_void_p]
@@ -787,6 +804,17 @@ class SeedRows(SwRows):
         self.strands, self.k = strands, k
 
 
+class LocateIndex:
+    """What Engine.locate_index returns: the reference packed on the device (`bases`) and the index built over it (`table`), both torch tensors this handle
+    keeps alive; `ref_len`, and `k` as it was given (0 = LOCATE_K).  .c_struct() is the cw_locate_ref the device entry points take."""
+
+    def __init__(self, ref_len, k, bases, table):
+        self.ref_len, self.k, self.bases, self.table = ref_len, k, bases, table
+
+    def c_struct(self):
+        return LocateRef(self.bases.data_ptr(), self.ref_len, self.table.data_ptr(), self.k)
+
+
 class Placement:
     """One read of Engine.place: `strand` (STRAND_FWD, or STRAND_REV: its reverse complement lies on the reference), `position`, the lowest reference
     coordinate of the densest 128 diagonals -- where the read, turned when REV, begins, give or take its indels; negative when it overhangs the start --
@@ -1218,7 +1246,89 @@ class Engine:
             out.append(Placement(status, t * int(tile) + diag, hits, other) if voted[t, r] and hits >= floor else None)
         return out
 
-    def polish_reads(self, reference, reads, window=500, tile=8192, k=0, min_hits=None, seeded=False):
+    def locate_index(self, reference, k=0):
+        """The device index of `reference`, a string of up to LOCATE_RMAX bases, for locate_rows() and locate(): the reference packed and uploaded, a table of
+        cw_locate_table_words(len) words, and cw_locate_build_device over both.  k = 0 is LOCATE_K = 15, else STRAND_KMIN .. STRAND_KMAX.  Build once, look any
+        number of batches up.  Returns a LocateIndex, which holds the device memory."""
+        import torch
+
+        n = len(reference)
+        words = int(self.lib.cw_locate_table_words(n))
+        if words == 0:
+            raise EngineError(f"locate_index: a reference has at most {LOCATE_RMAX} bases")
+        dev = torch.device("cuda", self.device)
+        packed = pack_piles([[reference]]).bases
+        t_bases = torch.from_numpy(np.concatenate([packed, np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
+        index = LocateIndex(n, int(k), t_bases, torch.empty(words, dtype=torch.int32, device=dev))
+        torch.cuda.synchronize(dev)  # the engine launches on its own stream
+        ref = index.c_struct()
+        _check(self.lib, self.lib.cw_locate_build_device(self.handle, C.byref(ref), None), "cw_locate_build_device")
+        torch.cuda.synchronize(dev)
+        return index
+
+    def locate_rows(self, index, reads):
+        """cw_locate_run_device of `reads` (ACGT strings, or a HostBatch whose grouping is ignored) against a LocateIndex: SeedRows as seeds() returns them, with
+        one row per READ and no reference row -- .rows[s] is read s, .row(0, s) too."""
+        import torch
+
+        batch = reads if isinstance(reads, HostBatch) else pack_piles([list(reads)])
+        S = len(batch.seq_len)
+        one_group = np.array([0, S], np.uint32)
+        if S == 0:
+            return SeedRows(np.zeros((0, SEED_ROW), np.int32), np.zeros(0, np.uint8), one_group, index.k)
+        dev = torch.device("cuda", self.device)
+
+        def up(a, dt):
+            return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
+
+        t_len, t_off = up(batch.seq_len, np.int32), up(batch.seq_word_off, np.int64)
+        t_bases = up(np.concatenate([batch.bases, np.zeros(1, np.uint32)]), np.int32)
+        t_rows = torch.zeros(S * SEED_ROW, dtype=torch.int32, device=dev)
+        t_strand = torch.zeros(S, dtype=torch.uint8, device=dev)
+        b = Batch(0, S, len(batch.bases), None, t_len.data_ptr(), t_off.data_ptr(), t_bases.data_ptr())
+        torch.cuda.synchronize(dev)
+        self.locate_device(index.c_struct(), b, Seeds(t_rows.data_ptr(), t_strand.data_ptr(), 0))
+        torch.cuda.synchronize(dev)
+        return SeedRows(t_rows.cpu().numpy().reshape(S, SEED_ROW), t_strand.cpu().numpy(), one_group, index.k)
+
+    def locate_device(self, ref_struct, batch_struct, seeds_struct, stream=None):
+        """cw_locate_run_device: device pointers in `ref_struct` (LocateRef, built by cw_locate_build_device), in the reads' batch struct and in `seeds_struct`
+        (Seeds); asynchronous on `stream`."""
+        _check(self.lib, self.lib.cw_locate_run_device(self.handle, C.byref(ref_struct), C.byref(batch_struct), C.byref(seeds_struct), stream), "cw_locate_run_device")
+
+    def locate_routes(self):
+        """(reads of the LDS route, reads of the dense route) of the last locate run (cw_debug_locate_routes)."""
+        out = np.zeros(2, np.uint32)
+        _check(self.lib, self.lib.cw_debug_locate_routes(self.handle, _ptr(out)), "cw_debug_locate_routes")
+        return int(out[0]), int(out[1])
+
+    def locate(self, index_or_reference, reads, k=0, min_hits=None):
+        """Every read of `reads` (ACGT strings, either strand, any order) placed on a reference of up to LOCATE_RMAX bases through ONE index of its unique k-mers
+        (cw_locate_*): O(read) a read, whatever the reference's length, where place() costs O(tiles x reads) votes.  `index_or_reference` is a LocateIndex
+        (its k holds; `k` is not read) or a string, indexed here with k (0 = LOCATE_K = 15).  Returns what place() returns: one
+        Placement(strand, position = SEED_DIAG, hits, other) per read, or None where no vote is possible or the hits are below min_hits.
+        This is not place()'s answer: there a k-mer counts when it is unique in its TILE, here when it is unique in the whole reference -- a stretch present
+        twice, 40 000 bases apart, seeds nothing here and seeds in both tiles there.
+        min_hits=None is LOCATE_MIN_HITS = 4, twice a measured chance level (tests/test_locate_cpu.py): over 24 unrelated random reads of 300 to 5 000 bases
+        against a random reference of 70 000 bases, the largest the CPU test builds, the plain reference's largest SEED_HITS at the default k = 15 is 2 (6 at
+        k = 11), while the 24 planted reads of that test at 10 - 12 % errors have 76 or more (138 at k = 11).  For longer references the figure is an
+        extrapolation: chance hits grow with n m / 4^k, which at 4.6 Mbp and 5 000 bases is still 21 spread over 72 000 bins.  It holds from
+        k = LOCATE_MIN_K = 15 up; below, EngineError unless min_hits is given."""
+        reads = list(reads)
+        given = isinstance(index_or_reference, LocateIndex)
+        kk = index_or_reference.k if given else int(k)
+        if min_hits is None and 0 < kk < LOCATE_MIN_K:
+            raise EngineError(f"locate: the default min_hits is measured for k >= {LOCATE_MIN_K}; give min_hits with k = {kk}")
+        if not reads:
+            return []
+        index = index_or_reference if given else self.locate_index(index_or_reference, kk)
+        floor = LOCATE_MIN_HITS if min_hits is None else int(min_hits)
+        out = []
+        for status, hits, diag, other in self.locate_rows(index, reads).rows.tolist():
+            out.append(Placement(status, diag, hits, other) if status <= STRAND_REV and hits >= floor else None)
+        return out
+
+    def polish_reads(self, reference, reads, window=500, tile=8192, k=0, min_hits=None, seeded=False, index=False):
         """`reference`, a contig of any length, polished from an unsorted bag of reads of either strand: place() the reads; every placed read, reverse-
         complemented when STRAND_REV, goes to every tile its footprint [position, position + length + SEED_SPAN) meets; polish() of those groups -- the tile
         first, its reads in the order given -- and the tiles' sequences joined.  `tile` must be a multiple of `window` (EngineError otherwise): windows then
@@ -1228,12 +1338,14 @@ class Engine:
         span of reference columns its Placement.position gives by cw_seed_spans' rule (seed_spans_rule): polish(that group, spans=...).  No read is aligned
         twice or cut at a tile's edge, no tiles are joined, and `tile` need not be a multiple of `window`.  What the one group costs instead, unmeasured: every
         read's cut slot holds the windows of the WHOLE contig + 1 words, and cw_cut_groups_device looks at every read of the group for every window --
-        O(windows x reads) words and tests, where the tiled polish has O(windows x reads of a tile)."""
+        O(windows x reads) words and tests, where the tiled polish has O(windows x reads of a tile).
+        index=True: the placements come from locate() instead of place(), in both forms: one index of the whole contig, O(read) a read (k = 0 is LOCATE_K = 15,
+        min_hits=None LOCATE_MIN_HITS; at most LOCATE_RMAX bases).  Everything after the placing is as above.  locate() is not place(): see there."""
         window, tile = int(window), int(tile)
         if window < 1 or (tile % window and not seeded):
             raise EngineError("polish_reads: tile must be a multiple of window")
         reads = list(reads)
-        placed = self.place(reference, reads, tile, k, min_hits)
+        placed = self.locate(reference, reads, k, min_hits) if index else self.place(reference, reads, tile, k, min_hits)
         if seeded:
             if not reference:
                 return Polished("", [], placements=placed)

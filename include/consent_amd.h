@@ -25,6 +25,8 @@
  *   cw_revcomp / cw_revcomp_device <- the batch with those queries reverse-complemented, for any of the runs above.
  *   cw_seed_run / cw_seed_run_device <- which queries belong to their group's reference at all, on which strand and on which diagonal, by k-mers that are
  *                               unique in the reference (no counterpart: the reference takes all three from minimap2's PAF records).
+ *   cw_locate_build_device, cw_locate_run_device / cw_locate_run <- the same three for reads against a reference of any length, through one device index of
+ *                               the whole reference's unique k-mers: O(read) a read, whatever the reference's length (no counterpart either).
  *   cw_sw_span_run, cw_sw_path_span_run, cw_pileup_span_run, cw_sw_cut_span_run (and _device) <- the four alignment runs with every query confined to a span
  *                               of its reference's columns, and cw_seed_spans / cw_seed_spans_device <- those spans from a seed run's rows (no counterpart:
  *                               the reference aligns a read against the window its PAF record names).
@@ -452,7 +454,7 @@ int cw_revcomp(cw_engine* e, const cw_batch* groups, const uint8_t* strand, uint
  * cw_seed_run_device: device pointers, asynchronous on `hip_stream`, cw_strand_run_device's contract.  cw_seed_run: host pointers, synchronous.
  * cw_last_timings names the stages strand_order, seed (references of up to 2 048 bases), seed_wide (beyond).
  * Several groups may hold the same queries: see cw_batch on shared words.  That is how a reference longer than CW_SW_RMAX is searched -- a group per tile of
- * it, every group the tile and all reads -- at the cost of tiles x reads votes. */
+ * it, every group the tile and all reads -- at the cost of tiles x reads votes; cw_locate_run_device below looks every read up in one index instead. */
 enum { CW_SEED_STATUS, CW_SEED_HITS, CW_SEED_DIAG, CW_SEED_OTHER, CW_SEED_ROW = 4 };
 #define CW_SEED_SHIFT 6u    /* a bin is 64 diagonals; a window is two neighbouring bins */
 typedef struct cw_seeds {
@@ -462,6 +464,55 @@ typedef struct cw_seeds {
 } cw_seeds;
 int cw_seed_run_device(cw_engine* e, const cw_batch* groups, const cw_seeds* out, void* hip_stream);
 int cw_seed_run(cw_engine* e, const cw_batch* groups, const cw_seeds* out);
+
+/* ---- reads placed through a device k-mer index of the whole reference: cw_locate_* ---------------------------------------------------------------------------------
+ * cw_seed_run's row with its reference allowed any length.  The seed run rebuilds an LDS table per (reference, chunk of queries) and stops at CW_SW_RMAX bases; a
+ * longer reference is searched there by tiles, at tiles x reads votes.  Here the reference's unique k-mers go into ONE table in device memory, built once, and a
+ * read is looked up in it: O(m) a read, and the reference's length stops mattering.
+ *
+ * With n = ref->len (0 .. CW_LOCATE_RMAX), m the read's length and k = ref->k (0 = CW_LOCATE_K; else CW_STRAND_KMIN .. CW_STRAND_KMAX -- 15 because 4^11 k-mers
+ * are fewer than the positions of a 4.6 Mbp contig: at the strand vote's 11 about a third of such a contig's k-mers are unique, at 15 nearly all):
+ *   U        the k-mers that occur at exactly ONE position of the WHOLE reference, P(K) that position
+ *   q_0, q_1 the read as given and its reverse complement
+ *   c_o[b]   the positions i in 0 .. m - k of q_o whose k-mer K is in U, counted by the bin b = (P(K) - i + m) >> CW_SEED_SHIFT; bins run 0 .. B - 1 with
+ *            B = ((n + m) >> CW_SEED_SHIFT) + 1, and c_o[B] = 0
+ *   w_o[b]   c_o[b] + c_o[b + 1]
+ * Per orientation the best b maximises w, ties to the lowest b.  Sequence s of `reads` owns rows[CW_SEED_ROW s ..):
+ *   CW_SEED_STATUS   CW_STRAND_REV only when w_1's best is LARGER than w_0's, otherwise CW_STRAND_FWD
+ *   CW_SEED_HITS     the chosen w
+ *   CW_SEED_DIAG     (b << CW_SEED_SHIFT) - m; it fits an int32 because n + m < 2^31
+ *   CW_SEED_OTHER    the other orientation's best w
+ *   no hit at all    CW_STRAND_FWD, 0, -m, 0
+ *   CW_STRAND_NONE, 0, 0, 0     m < k, m > CW_SW_QMAX or n < k; never CW_E_CAPACITY
+ * There is no reference row: every sequence of `reads` is a read, and its grouping (n_windows, win_first_seq) is not read.  strand[s], when given, is the status
+ * byte.  Every number is a function of (reference, read, k) alone: batch composition, read order, run, and which of the kernels' two routes a read took do not
+ * change it.  For n <= CW_SW_RMAX a read's row is bit for bit cw_seed_run's row of that read in a group behind that reference.
+ * This is NOT the answer of a tiled seed run (Engine.place): there a k-mer is unique when it is unique in its TILE, here when it is unique in the whole reference.
+ * A stretch present twice, 40 000 bases apart, seeds nothing here and seeds in both tiles there.  Neither is changed to match the other.
+ *
+ * The table is the caller's, cw_locate_table_words(len) words: a power of two, at least twice the reference's positions and at least 1 024; 0 beyond
+ * CW_LOCATE_RMAX.  cw_locate_build_device clears it and fills it -- one piece of memory serves one reference after another -- and any number of
+ * cw_locate_run_device calls follow.  Its content is private and may differ from build to build (the order of insertion is a race); the rows never do.
+ * `bases` is the reference packed as a cw_batch sequence from word 0.
+ * CW_E_INVALID, before anything is allocated or launched: NULL ref, bases (while len > 0), table, reads, out or out->rows; NULL seq_len, seq_word_off or bases
+ * of reads while n_seqs > 0; len > CW_LOCATE_RMAX; k outside its range; out->k neither 0 nor the reference's k.  n_seqs == 0 is CW_OK.
+ * The device forms: device pointers, asynchronous on `hip_stream`, cw_strand_run_device's threading and stream contract.  cw_locate_run: host pointers,
+ * synchronous; it uploads the reference and the reads, builds into device memory of the engine's own (CW_E_NOMEM when it cannot have it), runs, and brings the
+ * rows and bytes back.  Locate runs share the engine's one scratch allocation and alternate freely with every other run; the scratch plan is exact, the batch
+ * runs once.  cw_last_timings names the stages locate_build (the build), locate and locate_dense (a run: the reads whose votes fit a work-group's LDS, and the
+ * few that do not). */
+#define CW_LOCATE_K 15u                        /* k used when cw_locate_ref.k == 0 */
+#define CW_LOCATE_RMAX ((1u << 28) - 1u)       /* longest reference: a position takes 28 bits of a slot */
+typedef struct cw_locate_ref {
+    const uint32_t* bases;  /* the reference, packed as a cw_batch sequence from word 0 */
+    uint64_t len;
+    uint32_t* table;        /* [cw_locate_table_words(len)], the caller's */
+    uint32_t k;             /* 0 = CW_LOCATE_K, else CW_STRAND_KMIN .. CW_STRAND_KMAX */
+} cw_locate_ref;
+uint64_t cw_locate_table_words(uint64_t ref_len);
+int cw_locate_build_device(cw_engine* e, const cw_locate_ref* ref, void* hip_stream);
+int cw_locate_run_device(cw_engine* e, const cw_locate_ref* ref, const cw_batch* reads, const cw_seeds* out, void* hip_stream);
+int cw_locate_run(cw_engine* e, const uint32_t* ref_bases, uint64_t ref_len, uint32_t k, const cw_batch* reads, const cw_seeds* out);
 
 /* ---- align a query only where it was placed: reference spans ------------------------------------------------------------------------------------------------------
  * The four alignment runs sweep every query over ALL columns of its reference.  Each has a span form that confines query s to the reference columns

@@ -21,6 +21,7 @@ reference length: the forward sweep's; the reverse sweep and the traceback come 
     python tools/sw_bench.py --strand                     # instead: the strand vote and the reverse complement beside the plain run and a device copy of the same batch
     python tools/sw_bench.py --seed                       # instead: the seed run (cw_seed_run_device) beside the strand vote and the plain run of the same batch
     python tools/sw_bench.py --span                       # instead: the plain and the cut run with and without the spans of a seed run, reads of 1 000 and 3 000 bases on 8 192
+    python tools/sw_bench.py --locate                     # instead: the tiled seed run as Engine.place batches it beside cw_locate_build_device + cw_locate_run_device, one reference and one bag of reads
     python tools/sw_bench.py --oracle 4096                # also: so many 500 x 600 pairs through the oracle's cwo_ssw on --threads CPU threads
 
 Prints one JSON line per measurement and a markdown table (DESIGN.md section 4.8 holds the first one, from a --path run).
@@ -39,13 +40,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import consent_amd as ca  # noqa: E402
-from consent_amd.engine import Batch, HostBatch, Pileup, Seeds, Strands, SwCuts, SwPaths, SwSpans, sw_cuts  # noqa: E402
+from consent_amd.engine import Batch, HostBatch, LocateRef, Pileup, Seeds, Strands, SwCuts, SwPaths, SwSpans, sw_cuts  # noqa: E402
 
 SHAPES = {"24x150": 262144, "100x600": 131072, "500x600": 65536, "2000x2048": 4096, "8000x2048": 512, "1540x1540": 2048}  # query x reference -> pairs of the default run
 PLANTED = {"1540x1540": (500, 40)}  # shapes built as planted pairs: (part, g)
 DEEP = {"500x600x30": 61440}  # query x reference x queries per reference: what --pileup adds
 WIDE_GROUP = {"500x2048": 16384, "500x2048x16384": 16384}  # what --strand adds: 16 queries a reference, and ONE reference with all 16 384 queries -- equal lengths
 SPAN = {"1000x8192": 2048, "3000x8192": 512}  # what --span runs: reads planted at 10 - 12 % errors in references of 8 192 bases, 16 a reference
+LOCATE = {"5000x65536": 2048, "5000x1048576": 2048, "5000x4194304": 2048, "500x1048576": 16384}  # what --locate runs: read x reference -> reads of the bag
+LOCATE_TILE = 8192  # Engine.place's default tile
 PATH, PILE, CUT = "path", "pileup", "cut"  # the third, fourth and fifth mode beside flags 0 and CW_SW_WANT_INDELS
 
 
@@ -299,6 +302,82 @@ def bench_seed(eng, shape, n_pairs, per_group, steps, warmup, seed):
             "stage_ms": {k: round(float(np.median(v)), 4) for k, v in stages.items()}}
 
 
+def bench_locate(eng, shape, n_reads, steps, warmup, seed, k=0):
+    """One random reference and one bag of reads -- slices of it with 10 % substitutions, every second one reverse-complemented -- in device memory, and in this
+    process: the tiled seed run exactly as Engine.place batches it (a group per tile of LOCATE_TILE bases, each the tile and ALL reads, the words packed once and
+    shared), cw_locate_build_device, and cw_locate_run_device against that index.  Per measurement the median of `steps` with the lowest and the highest of the
+    device's own time, the locate run's stages, the reads of its two routes, and how many reads either way puts on the slice they were cut from."""
+    import torch
+
+    qlen, rlen = (int(v) for v in shape.split("x"))
+    rng = np.random.default_rng(seed)
+    ref = rng.integers(0, 4, (1, rlen), dtype=np.uint8)
+    start = rng.integers(0, rlen - qlen + 1, n_reads)
+    reads = ref[0][start[:, None] + np.arange(qlen)[None, :]]
+    sub = rng.random(reads.shape) < 0.10
+    reads = np.where(sub, (reads + rng.integers(1, 4, reads.shape, dtype=np.uint8)) & 3, reads).astype(np.uint8)
+    turned = np.arange(n_reads) % 2 == 1
+    reads[turned] = 3 - reads[turned][:, ::-1]
+    rw, qw = pack(ref)[0], pack(reads)
+    R, QW, T = n_reads, qw.shape[1], (rlen + LOCATE_TILE - 1) // LOCATE_TILE
+    bases = np.concatenate([rw, qw.reshape(-1)])
+    tile_len = np.minimum(LOCATE_TILE, rlen - LOCATE_TILE * np.arange(T)).astype(np.uint32)
+    tile_off = (np.arange(T, dtype=np.uint64) * (LOCATE_TILE // 16)).astype(np.uint64)
+    read_off = (len(rw) + np.arange(R, dtype=np.uint64) * QW).astype(np.uint64)
+    lens = np.concatenate([np.concatenate([[tile_len[t]], np.full(R, qlen, np.uint32)]) for t in range(T)]).astype(np.uint32)
+    offs = np.concatenate([np.concatenate([[tile_off[t]], read_off]) for t in range(T)]).astype(np.uint64)
+    tiled = HostBatch(np.arange(T + 1, dtype=np.uint32) * np.uint32(R + 1), lens, offs, bases)
+    dev = torch.device("cuda", eng.device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
+
+    t_bases = up(np.concatenate([bases, np.zeros(4, np.uint32)]), np.int32)
+    t_in = (up(tiled.win_first_seq, np.int32), up(tiled.seq_len, np.int32), up(tiled.seq_word_off, np.int64))
+    S = len(tiled.seq_len)
+    t_seed = torch.zeros(S * ca.SEED_ROW, dtype=torch.int32, device=dev)
+    t_rlen, t_roff = up(np.full(R, qlen, np.uint32), np.int32), up(read_off, np.int64)
+    t_rows = torch.zeros(R * ca.SEED_ROW, dtype=torch.int32, device=dev)
+    t_table = torch.empty(int(eng.lib.cw_locate_table_words(rlen)), dtype=torch.int32, device=dev)
+    kk = k or ca.LOCATE_K
+    b = Batch(T, S, len(bases), t_in[0].data_ptr(), t_in[1].data_ptr(), t_in[2].data_ptr(), t_bases.data_ptr())
+    rb = Batch(0, R, len(bases), None, t_rlen.data_ptr(), t_roff.data_ptr(), t_bases.data_ptr())
+    lref = LocateRef(t_bases.data_ptr(), rlen, t_table.data_ptr(), kk)
+    seeds, lrows = Seeds(t_seed.data_ptr(), None, kk), Seeds(t_rows.data_ptr(), None, kk)
+    torch.cuda.synchronize(dev)
+
+    def build():
+        if eng.lib.cw_locate_build_device(eng.handle, C.byref(lref), None) != 0:
+            raise RuntimeError("cw_locate_build_device failed")
+
+    runs = {"tiled": lambda: eng.seed_device(b, seeds), "build": build, "locate": lambda: eng.locate_device(lref, rb, lrows)}
+    out, stages = {}, {}
+    for name, run in runs.items():
+        device = []
+        for step in range(warmup + steps):
+            run()
+            torch.cuda.synchronize(dev)
+            if step >= warmup:
+                device.append(eng.timings()["total"])
+                if name == "locate":
+                    for key, v in eng.timings().items():
+                        stages.setdefault(key, []).append(v)
+        out[name] = {"device_ms": [round(float(np.median(device)), 4), round(min(device), 4), round(max(device), 4)]}
+    routes = eng.locate_routes()
+    # where the read, turned when it was planted turned, begins: its start; a window of SEED_SPAN diagonals holds it (substitutions only: no drift)
+    rows = t_rows.cpu().numpy().reshape(R, ca.SEED_ROW)
+    on = lambda st, dg: float(np.mean((st == turned) & (dg <= start) & (start < dg + ca.SEED_SPAN)))
+    trows = t_seed.cpu().numpy().reshape(T, R + 1, ca.SEED_ROW)[:, 1:, :]
+    best = np.argmax(np.where(trows[:, :, ca.SEED_STATUS] <= ca.STRAND_REV, trows[:, :, ca.SEED_HITS], -1), axis=0)
+    pick = trows[best, np.arange(R)]
+    return {"shape": shape, "mode": "locate", "k": kk, "reads": R, "tiles": T, "table_mb": round(t_table.numel() * 4 / 2**20, 1), "steps": steps, **out,
+            "tiled_ns_per_pair": round(out["tiled"]["device_ms"][0] * 1e6 / (T * R), 1), "locate_ns_per_read": round(out["locate"]["device_ms"][0] * 1e6 / R, 1),
+            "build_ns_per_base": round(out["build"]["device_ms"][0] * 1e6 / rlen, 3), "tiled_over_locate": round(out["tiled"]["device_ms"][0] / out["locate"]["device_ms"][0], 2),
+            "routes": list(routes), "median_hits": int(np.median(rows[:, ca.SEED_HITS])), "locate_on_slice": round(on(rows[:, ca.SEED_STATUS] == ca.STRAND_REV, rows[:, ca.SEED_DIAG]), 4),
+            "tiled_on_slice": round(on(pick[:, ca.SEED_STATUS] == ca.STRAND_REV, best * LOCATE_TILE + pick[:, ca.SEED_DIAG]), 4),
+            "stage_ms": {key: round(float(np.median(v)), 4) for key, v in stages.items()}}
+
+
 def make_planted_reads(n_pairs, qlen, rlen, per_group, seed):
     """HostBatch of groups of one random reference and per_group reads: a read copies qlen reference bases from a random start with 10 - 12 % errors (a rate
     drawn per read; substitutions, insertions and deletions a third each), every second read reverse-complemented."""
@@ -430,6 +509,9 @@ def main():
     ap.add_argument("--seed", action="store_true", help="instead of the alignment modes: cw_seed_run_device beside cw_strand_run_device and the plain run of the same batch, on the shapes of --strand")
     ap.add_argument("--span", action="store_true", help="instead of the alignment modes: the plain run and the cut run without spans and with the spans of a seed run "
                     "(cw_seed_run_device + cw_seed_spans_device, timed beside them), reads of 1 000 and 3 000 bases planted at 10 - 12 % errors in references of 8 192")
+    ap.add_argument("--locate", action="store_true", help="instead of the alignment modes: one reference and one bag of reads; the tiled seed run as Engine.place batches it beside "
+                    "cw_locate_build_device and cw_locate_run_device, on 2 048 reads of 5 000 bases on 65 536, 1 048 576 and 4 194 304 bases and 16 384 reads of 500 on 1 048 576")
+    ap.add_argument("--k", type=int, default=0, help="of --locate: k of both runs (0 = CW_LOCATE_K)")
     ap.add_argument("--window", type=int, default=100, help="reference columns a window of the cut run")
     ap.add_argument("--oracle", type=int, default=0, help="also time so many 500x600 pairs through the oracle on --threads CPU threads")
     ap.add_argument("--threads", type=int, default=16)
@@ -437,6 +519,21 @@ def main():
     a.pileup = a.pileup or a.cut
     eng = ca.Engine(ca.Params(9, 4, 8, 2, 150), device=a.device)
     rows = []
+    if a.locate:
+        try:
+            for shape in a.shape or list(LOCATE):
+                rows.append(bench_locate(eng, shape, a.pairs or LOCATE.get(shape, 2048), a.steps, a.warmup, a.rng_seed, a.k))
+                print(json.dumps(rows[-1]), flush=True)
+        finally:
+            eng.close()
+        cell = lambda m: f"{m['device_ms'][0]:.3f} ({m['device_ms'][1]:.3f} - {m['device_ms'][2]:.3f})"
+        print("\n| read x reference | reads | tiles | tiled seed run ms | ns / pair | build ms | ns / base | locate run ms | ns / read | locate, locate_dense ms | tiled / locate | dense reads | on the slice: tiled, locate |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['shape']} | {r['reads']} | {r['tiles']} | {cell(r['tiled'])} | {r['tiled_ns_per_pair']:.1f} | {cell(r['build'])} | {r['build_ns_per_base']:.3f} | {cell(r['locate'])} | "
+                  f"{r['locate_ns_per_read']:.1f} | {r['stage_ms'].get('locate', 0):.3f}, {r['stage_ms'].get('locate_dense', 0):.3f} | {r['tiled_over_locate']:.1f} | {r['routes'][1]} | "
+                  f"{r['tiled_on_slice']:.3f}, {r['locate_on_slice']:.3f} |")
+        return
     if a.span:
         try:
             for shape in a.shape or list(SPAN):
