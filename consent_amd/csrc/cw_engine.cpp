@@ -8,7 +8,8 @@
  * (cw_sw_run_device, cw_sw_run: kernels in cw_sw_op.h; cw_sw_path_run_device, cw_sw_path_run: cw_sw_path.h; cw_pileup_run_device, cw_pileup_run: cw_pileup.h; cw_sw_cut_run_device, cw_sw_cut_run,
  * cw_cut_groups_device: cw_sw_cut.h); both strands for them (cw_strand_run_device, cw_strand_run, cw_revcomp_device, cw_revcomp: cw_strand.h); reads placed on
  * their reference (cw_seed_run_device, cw_seed_run, cw_seed_spans_device, cw_seed_spans: cw_seed.h), or through an index of the whole reference
- * (cw_locate_build_device, cw_locate_run_device, cw_locate_run: cw_locate.h).
+ * (cw_locate_build_device, cw_locate_run_device, cw_locate_run: cw_locate.h); the reads of a set that overlap each other (cw_overlap_count_device,
+ * cw_overlap_build_device, cw_overlap_run_device, cw_overlap_run, cw_overlap_to_pile_device: cw_overlap.h).
  * What the operators' entry points share exists once, in the anonymous namespace: Layout (arrays 256-byte aligned in one allocation), locked (a _device entry
  * point is its run_*_locked body under the engine's mutex), dev_batch (cw_batch -> DevBatch), run_begin / run_end (the bracket round the stages of every run,
  * a window run's included) and HostTrip (a host form's round trip: lock, check_groups, the output layout, upload_groups, up / down / sync); each host form
@@ -35,6 +36,7 @@
 #include "cw_strand.h"
 #include "cw_seed.h"
 #include "cw_locate.h"
+#include "cw_overlap.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -919,6 +921,129 @@ int run_locate_locked(cw_engine* e, const cw_locate_ref* ref, const cw_batch* re
     return run_end(e, st);
 }
 
+/* ---- the reads of a set that overlap each other: cw_overlap_* -------------------------------------------------------------------------------------------------- */
+
+int validate_overlap_reads(const cw_engine* e, const cw_batch* reads, const cw_overlap_params* prm) {
+    if (!e || !reads || !prm) return CW_E_INVALID;
+    if (prm->k != 0u && (prm->k < CW_STRAND_KMIN || prm->k > CW_STRAND_KMAX)) return CW_E_INVALID;
+    if (prm->sample > CW_OVL_SAMPLE_MAX || prm->max_occ > CW_OVL_MAX_OCC_MAX) return CW_E_INVALID;
+    if (reads->n_seqs > CW_OVL_READS_MAX) return CW_E_INVALID;
+    if (reads->n_seqs != 0 && (!reads->seq_len || !reads->seq_word_off || !reads->bases)) return CW_E_INVALID;
+    return CW_OK;
+}
+
+int validate_overlap_index(const cw_engine* e, const cw_batch* reads, const cw_overlap_index* index) {
+    if (!index) return CW_E_INVALID;
+    if (int rc = validate_overlap_reads(e, reads, &index->prm)) return rc;
+    if (!index->mem || ((uintptr_t)index->mem & 7u) || index->n_entries > 0xFFFFFFFFull || index->prm.min_hits < 1u) return CW_E_INVALID;
+    return CW_OK;
+}
+
+OvlIndexArgs overlap_index_args(const cw_batch* reads, const cw_overlap_params* prm, uint32_t* mem, uint64_t n_entries) {
+    OvlIndexArgs x;
+    memset(&x, 0, sizeof(x));
+    x.bits = cw_ovl_table_bits(n_entries);
+    const size_t slots = (size_t)1 << x.bits;
+    x.hdr = mem;
+    if (mem) { x.keys = mem + CW_OVL_HDR; x.cnt = x.keys + slots; x.off = x.cnt + slots; x.post = (unsigned long long*)(x.off + slots); x.counted = (unsigned long long*)(mem + 2); }
+    x.n_entries = n_entries;
+    x.k = prm->k ? prm->k : CW_OVL_K; x.sample = prm->sample; x.max_occ = prm->max_occ ? prm->max_occ : CW_OVL_MAX_OCC; x.min_hits = prm->min_hits;
+    x.n_reads = reads->n_seqs; x.seq_len = reads->seq_len; x.seq_word_off = reads->seq_word_off; x.bases = reads->bases;
+    return x;
+}
+
+uint32_t overlap_read_wgs(const cw_engine* e, uint32_t n_reads) { return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_reads, (uint64_t)e->cus * 32u)); }
+
+/* the body of cw_overlap_count_device; the caller holds e->mu.  One stage, ovl_count, into the plan's counters; the one synchronisation reads them. */
+int run_overlap_count_locked(cw_engine* e, const cw_batch* reads, const cw_overlap_params* prm, uint64_t* n_entries, void* hip_stream) {
+    int rc = validate_overlap_reads(e, reads, prm);
+    if (rc || !n_entries) return rc ? rc : CW_E_INVALID;
+    *n_entries = 0;
+    if (reads->n_seqs == 0) return CW_OK;
+    const OverlapPlan p = plan_overlap(0, e->cus);
+    hipStream_t st;
+    if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
+    OvlIndexArgs x = overlap_index_args(reads, prm, nullptr, 0);
+    x.counted = (unsigned long long*)((uint8_t*)e->scratch + p.ctr);
+    if ((rc = run_begin(e, st, true)) != CW_OK) return rc;
+    CW_HIP(hipMemsetAsync(x.counted, 0, (size_t)CW_OVL_CTR_WORDS * 4, st));
+    stage(e, st, "ovl_count", [&] { cw_overlap_index_kernel<0><<<overlap_read_wgs(e, x.n_reads), 256, 0, st>>>(x); });
+    if ((rc = run_end(e, st)) != CW_OK) return rc;
+    unsigned long long got = 0;
+    CW_HIP(hipMemcpyAsync(&got, x.counted, 8, hipMemcpyDeviceToHost, st));
+    CW_HIP(hipStreamSynchronize(st));
+    *n_entries = got;
+    return CW_OK;
+}
+
+/* the body of cw_overlap_build_device; the caller holds e->mu.  No scratch: everything lives in the caller's memory. */
+int run_overlap_build_locked(cw_engine* e, const cw_batch* reads, const cw_overlap_index* index, void* hip_stream) {
+    int rc = validate_overlap_index(e, reads, index);
+    if (rc) return rc;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    const OvlIndexArgs x = overlap_index_args(reads, &index->prm, index->mem, index->n_entries);
+    const size_t slots = (size_t)1 << x.bits;
+    const uint32_t wgs = overlap_read_wgs(e, x.n_reads), wgs_slots = (uint32_t)std::min<uint64_t>(slots / 256u, (uint64_t)e->cus * 32u);
+    if ((rc = run_begin(e, st, false)) != CW_OK) return rc;
+    hipError_t c0 = hipSuccess, c1 = hipSuccess, c2 = hipSuccess;
+    stage(e, st, "ovl_build_count", [&] {
+        c0 = hipMemsetAsync(x.hdr, 0, (size_t)CW_OVL_HDR * 4, st);
+        c1 = hipMemsetAsync(x.keys, 0xFF, slots * 4, st); /* CW_STR_EMPTY in every slot */
+        c2 = hipMemsetAsync(x.cnt, 0, slots * 8, st);     /* the counts and the offsets */
+        cw_overlap_index_kernel<0><<<wgs, 256, 0, st>>>(x);
+    });
+    stage(e, st, "ovl_build_insert", [&] { cw_overlap_index_kernel<1><<<wgs, 256, 0, st>>>(x); });
+    stage(e, st, "ovl_build_assign", [&] { cw_overlap_assign_kernel<<<wgs_slots, 256, 0, st>>>(x); });
+    stage(e, st, "ovl_build_fill", [&] { cw_overlap_index_kernel<3><<<wgs, 256, 0, st>>>(x); cw_overlap_seal_kernel<<<1, 64, 0, st>>>(x); });
+    CW_HIP(c0); CW_HIP(c1); CW_HIP(c2);
+    return run_end(e, st);
+}
+
+int validate_overlap_run(const cw_engine* e, const cw_overlap_index* index, const cw_batch* reads, uint32_t first, uint32_t n_queries, const cw_overlaps* out) {
+    if (int rc = validate_overlap_index(e, reads, index)) return rc;
+    if (!out || (uint64_t)first + n_queries > reads->n_seqs) return CW_E_INVALID;
+    if (n_queries != 0 && (!out->rows || !out->row_off || !out->n_rows || !out->status)) return CW_E_INVALID;
+    return CW_OK;
+}
+
+/* the body of cw_overlap_run_device; the caller holds e->mu.  Stages: ovl (every query, the tables in LDS), ovl_dense (the queries that route abandoned). */
+int run_overlap_locked(cw_engine* e, const cw_overlap_index* index, const cw_batch* reads, uint32_t first, uint32_t n_queries, const cw_overlaps* out, void* hip_stream) {
+    int rc = validate_overlap_run(e, index, reads, first, n_queries, out);
+    if (rc || n_queries == 0) return rc;
+    const OverlapPlan p = plan_overlap(n_queries, e->cus); /* exact: the queries run once */
+    hipStream_t st;
+    if ((rc = hold_sw(e, p.total, hip_stream, &st)) != CW_OK) return rc;
+    if (!e->ovl_routes) CW_HIP(hipMalloc((void**)&e->ovl_routes, 8));
+    uint8_t* base = (uint8_t*)e->scratch;
+    OvlArgs a;
+    a.x = overlap_index_args(reads, &index->prm, index->mem, index->n_entries);
+    a.first = first; a.n_queries = n_queries;
+    a.rows = out->rows; a.row_off = out->row_off; a.n_rows = out->n_rows; a.status = out->status;
+    a.ctr = (uint32_t*)(base + p.ctr); a.redo = (uint32_t*)(base + p.redo); a.dense = (uint32_t*)(base + p.dense); a.routes = e->ovl_routes;
+    if ((rc = run_begin(e, st, true)) != CW_OK) return rc;
+    CW_HIP(hipMemsetAsync(a.ctr, 0, (size_t)CW_OVL_CTR_WORDS * 4, st));
+    stage(e, st, "ovl", [&] { cw_overlap_kernel<0><<<p.wgs, CW_OVL_THREADS, 0, st>>>(a); });
+    stage(e, st, "ovl_dense", [&] { cw_overlap_kernel<1><<<p.wgs_dense, CW_OVL_THREADS, 0, st>>>(a); });
+    return run_end(e, st);
+}
+
+/* the body of cw_overlap_to_pile_device; the caller holds e->mu.  No scratch. */
+int run_overlap_pile_locked(cw_engine* e, const cw_overlaps* rows, uint32_t n_queries, uint32_t max_support, cw_overlap* pile, const uint64_t* pile_off, uint32_t* pile_n, void* hip_stream) {
+    if (!e || !rows) return CW_E_INVALID;
+    if (n_queries == 0) return CW_OK;
+    if (!rows->rows || !rows->row_off || !rows->n_rows || !rows->status || !pile || !pile_off || !pile_n) return CW_E_INVALID;
+    CW_HIP(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    OvlPileArgs a;
+    a.rows = rows->rows; a.row_off = rows->row_off; a.n_rows = rows->n_rows; a.status = rows->status;
+    a.n_queries = n_queries; a.max_support = max_support; a.pile = pile; a.pile_off = pile_off; a.pile_n = pile_n;
+    int rc;
+    if ((rc = run_begin(e, st, false)) != CW_OK) return rc;
+    stage(e, st, "ovl_pile", [&] { cw_overlap_to_pile_kernel<<<(uint32_t)std::min<uint64_t>(((uint64_t)n_queries + 255u) / 256u, (uint64_t)e->cus * 8u), 256, 0, st>>>(a); });
+    return run_end(e, st);
+}
+
 } // namespace
 
 extern "C" {
@@ -991,6 +1116,8 @@ void cw_destroy(cw_engine* e) {
     if (e->emitted) (void)hipFree(e->emitted);
     if (e->locate_tab) (void)hipFree(e->locate_tab);
     if (e->locate_routes) (void)hipFree(e->locate_routes);
+    if (e->ovl_index) (void)hipFree(e->ovl_index);
+    if (e->ovl_routes) (void)hipFree(e->ovl_routes);
     if (e->host_fb) (void)hipHostFree(e->host_fb);
     for (int i = 0; i < CW_MAX_STAGES; ++i) { if (e->ev0[i]) (void)hipEventDestroy(e->ev0[i]); if (e->ev1[i]) (void)hipEventDestroy(e->ev1[i]); }
     for (int i = 0; i < 3; ++i) { if (e->ev_join[i]) (void)hipEventDestroy(e->ev_join[i]); if (e->side[i]) (void)hipStreamDestroy(e->side[i]); }
@@ -1402,6 +1529,81 @@ int cw_debug_locate_routes(cw_engine* e, uint32_t* out2) {
     CW_HIP(hipSetDevice(e->device));
     CW_HIP(hipDeviceSynchronize());
     CW_HIP(hipMemcpy(out2, e->locate_routes, 8, hipMemcpyDeviceToHost));
+    return CW_OK;
+}
+
+uint64_t cw_overlap_index_words(uint64_t n_entries) { return n_entries > 0xFFFFFFFFull ? 0u : cw_ovl_index_words(n_entries); }
+
+int cw_overlap_count_device(cw_engine* e, const cw_batch* reads, const cw_overlap_params* prm, uint64_t* n_entries, void* hip_stream) {
+    return locked(e, [&] { return run_overlap_count_locked(e, reads, prm, n_entries, hip_stream); });
+}
+
+int cw_overlap_build_device(cw_engine* e, const cw_batch* reads, const cw_overlap_index* index, void* hip_stream) {
+    return locked(e, [&] { return run_overlap_build_locked(e, reads, index, hip_stream); });
+}
+
+int cw_overlap_run_device(cw_engine* e, const cw_overlap_index* index, const cw_batch* reads, uint32_t first_query, uint32_t n_queries, const cw_overlaps* out, void* hip_stream) {
+    return locked(e, [&] { return run_overlap_locked(e, index, reads, first_query, n_queries, out, hip_stream); });
+}
+
+int cw_overlap_to_pile_device(cw_engine* e, const cw_overlaps* rows, uint32_t n_queries, uint32_t max_support, cw_overlap* pile, const uint64_t* pile_off, uint32_t* pile_n, void* hip_stream) {
+    return locked(e, [&] { return run_overlap_pile_locked(e, rows, n_queries, max_support, pile, pile_off, pile_n, hip_stream); });
+}
+
+/* The reads go up as one group, are counted (the form's one extra wait), indexed in the engine's own memory and run, all of them; rows, counts and statuses
+   come back.  The slots' offsets are rebased to the first, as every host form's. */
+int cw_overlap_run(cw_engine* e, const cw_batch* reads, const cw_overlap_params* prm, const cw_overlaps* out) {
+    if (!e) return CW_E_INVALID;
+    const uint32_t one_group[2] = {0u, reads ? reads->n_seqs : 0u};
+    cw_batch one;
+    memset(&one, 0, sizeof(one));
+    if (reads) { one = *reads; one.n_windows = 1; one.win_first_seq = one_group; }
+    HostTrip t(e, &one);
+    int rc = validate_overlap_reads(e, reads, prm);
+    if (rc) return rc;
+    if (prm->min_hits < 1u || !out) return CW_E_INVALID;
+    const uint32_t S = reads->n_seqs;
+    if (S == 0) return CW_OK;
+    if (!out->rows || !out->row_off || !out->n_rows || !out->status) return CW_E_INVALID;
+    if ((rc = t.check_groups(out->row_off)) != CW_OK) return rc;
+    const size_t row_bytes = (size_t)t.slot[S] * CW_OVL_ROW * 4;
+    const size_t o_rows = t.out.put(row_bytes), o_n = t.out.put((size_t)S * 4), o_status = t.out.put(S);
+    if ((rc = t.upload_groups()) != CW_OK) return rc;
+    uint64_t n_entries = 0;
+    if ((rc = run_overlap_count_locked(e, &t.db, prm, &n_entries, t.st)) != CW_OK) return rc;
+    if (n_entries > 0xFFFFFFFFull) return CW_E_CAPACITY;
+    if ((rc = ensure(&e->ovl_index, &e->ovl_index_bytes, (size_t)cw_ovl_index_words(n_entries) * 4)) != CW_OK) return rc;
+    cw_overlap_index index;
+    index.mem = (uint32_t*)e->ovl_index; index.n_entries = n_entries; index.prm = *prm;
+    cw_overlaps d;
+    d.rows = t.at<int32_t>(o_rows); d.row_off = t.d_slot; d.n_rows = t.at<uint32_t>(o_n); d.status = t.at<uint8_t>(o_status);
+    if ((rc = run_overlap_build_locked(e, &t.db, &index, t.st)) != CW_OK) return rc;
+    if ((rc = run_overlap_locked(e, &index, &t.db, 0, S, &d, t.st)) != CW_OK) return rc;
+    CW_HIP(t.down(out->rows + out->row_off[0] * CW_OVL_ROW, o_rows, row_bytes));
+    CW_HIP(t.down(out->n_rows, o_n, (size_t)S * 4));
+    CW_HIP(t.down(out->status, o_status, S));
+    CW_HIP(t.sync());
+    for (uint32_t s = 0; s < S; ++s) if (out->status[s] == CW_OVL_SLOT || out->status[s] == CW_OVL_DENSE) return CW_E_CAPACITY;
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): what plan_overlap would allocate and its grids (host arithmetic only). */
+int cw_debug_overlap_plan(uint32_t n_queries, int cus, uint64_t* out6) {
+    if (!out6 || cus < 1) return CW_E_INVALID;
+    const OverlapPlan p = plan_overlap(n_queries, cus);
+    const uint64_t v[6] = {p.total, (uint64_t)(p.redo - p.ctr), (uint64_t)(p.dense - p.redo), (uint64_t)(p.total - p.dense), p.wgs, p.wgs_dense};
+    for (int i = 0; i < 6; ++i) out6[i] = v[i];
+    return CW_OK;
+}
+
+/* Debug/inspection (cw_private.h): the two words the last overlap run's dense launch wrote, once everything on the device has ended. */
+int cw_debug_overlap_routes(cw_engine* e, uint32_t* out2) {
+    if (!e || !out2) return CW_E_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->ovl_routes) return CW_E_INVALID;
+    CW_HIP(hipSetDevice(e->device));
+    CW_HIP(hipDeviceSynchronize());
+    CW_HIP(hipMemcpy(out2, e->ovl_routes, 8, hipMemcpyDeviceToHost));
     return CW_OK;
 }
 

@@ -62,6 +62,9 @@ struct cw_engine {
     void* locate_tab = nullptr; /* cw_locate_run's index of the caller's reference: the host form builds into device memory of its own */
     size_t locate_tab_bytes = 0;
     uint32_t* locate_routes = nullptr; /* the reads of each route in the last locate run (cw_debug_locate_routes): two words the dense launch writes */
+    void* ovl_index = nullptr; /* cw_overlap_run's index of the caller's read set: the host form builds into device memory of its own */
+    size_t ovl_index_bytes = 0;
+    uint32_t* ovl_routes = nullptr; /* the queries of each route in the last overlap run (cw_debug_overlap_routes) */
     cw_host_fb* host_fb = nullptr;
     /* per-stage timing of the last run */
     hipStream_t side[3] = {nullptr, nullptr, nullptr}; /* POA tiers run concurrently on their own streams (M1, M2, L) */

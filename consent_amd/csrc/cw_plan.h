@@ -14,6 +14,7 @@
 #include "cw_strand.h" /* the strand vote's chunk sizes */
 #include "cw_seed.h"   /* the seed run's LDS, which bounds its work-groups a CU */
 #include "cw_locate.h" /* the locate run's LDS and the dense route's table */
+#include "cw_overlap.h" /* the overlap run's the same */
 #include "cw_finish.h" /* CW_FIN_*.  (These three are kernel headers, taken for their size macros: nothing here runs on the device, but a translation unit that includes this one is still a HIP one) */
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -293,6 +294,24 @@ static inline LocatePlan plan_locate(uint32_t n_seqs, int cus) {
     put(p.ctr, (size_t)CW_LOC_CTR_WORDS * 4);
     put(p.redo, (size_t)n_seqs * 4);
     put(p.dense, (size_t)p.wgs_dense * CW_LOC_DENSE_WORDS * 4);
+    p.total = o;
+    return p;
+}
+
+/* The plan of an overlap run (cw_overlap_run_device, cw_overlap.h), exact: plan_locate's shape.  The LDS launch: a work-group a query, at most three a CU (48 KB
+   each).  The dense launch: at most CW_OVL_DENSE_WGS work-groups, a pair of tables of 6 MB each.  n_queries == 0 plans the count alone: the counters. */
+#define CW_OVL_DENSE_WGS 16u
+struct OverlapPlan { size_t ctr, redo, dense, total; uint32_t wgs, wgs_dense; };
+static inline OverlapPlan plan_overlap(uint32_t n_queries, int cus) {
+    OverlapPlan p;
+    memset(&p, 0, sizeof(p));
+    p.wgs = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_queries, (uint64_t)cus * 3u));
+    p.wgs_dense = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_queries, CW_OVL_DENSE_WGS));
+    size_t o = 0;
+    auto put = [&](size_t& slot, size_t bytes) { slot = o; o = align_up(o + bytes, 256); };
+    put(p.ctr, (size_t)CW_OVL_CTR_WORDS * 4);
+    put(p.redo, (size_t)n_queries * 4);
+    put(p.dense, n_queries ? (size_t)p.wgs_dense * CW_OVL_DENSE_WORDS * 4 : 0);
     p.total = o;
     return p;
 }

@@ -69,6 +69,12 @@ int cw_debug_locate_plan(uint32_t n_seqs, int cus, uint64_t* out6);
 /* The reads each route took in the engine's last locate run: out[0] the LDS route (the reads without a vote among them), out[1] the dense route.  Waits for the
    device.  CW_E_INVALID before the first locate run. */
 int cw_debug_locate_routes(cw_engine* e, uint32_t* out2);
+/* The scratch plan of an overlap run (cw_overlap_run_device) of n_queries queries, without a device: out[0] total bytes, [1] the counters, [2] the redo list, [3]
+   the dense route's tables, [4] [5] work-groups of the LDS and the dense launch. */
+int cw_debug_overlap_plan(uint32_t n_queries, int cus, uint64_t* out6);
+/* The queries each route took in the engine's last overlap run: out[0] the LDS route (CW_OVL_NONE among them), out[1] the dense route.  Waits for the device.
+   CW_E_INVALID before the first overlap run. */
+int cw_debug_overlap_routes(cw_engine* e, uint32_t* out2);
 /* cw_max_batch_windows of an engine that cw_configure(max_template_len) will be called on (the native driver sizes its jobs before it has engines) */
 uint32_t cw_plan_max_batch_windows(uint32_t k, uint32_t max_template_len);
 

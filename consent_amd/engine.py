@@ -37,6 +37,12 @@ SEED_MIN_HITS, SEED_MIN_K = 14, 11  # (the threshold holds from this k up)
 # cw_locate_*: the default k, the longest reference; Engine.locate's default threshold and the k it is measured for (its docstring has the measurement)
 LOCATE_K, LOCATE_RMAX = 15, (1 << 28) - 1
 LOCATE_MIN_HITS, LOCATE_MIN_K = 4, 15
+# cw_overlap_*: the defaults of cw_overlap_params, the row and the statuses; Engine.overlaps' default threshold and the k it is measured for, the shortest planted
+# overlap it finds without exception and how far an end lies from the truth (tests/test_overlap_cpu.py measures all three)
+OVL_K, OVL_SAMPLE, OVL_MAX_OCC = 15, 3, 512
+OVL_TARGET, OVL_STRAND, OVL_HITS, OVL_DIAG, OVL_Q_START, OVL_Q_END, OVL_T_START, OVL_T_END, OVL_ROW = 0, 1, 2, 3, 4, 5, 6, 7, 8
+OVL_OK, OVL_NONE, OVL_SLOT, OVL_DENSE, OVL_BAD_INDEX = 0, 1, 2, 3, 4
+OVL_MIN_HITS, OVL_MIN_K, OVL_MIN_OVERLAP, OVL_END_SLACK = 2, 15, 2000, 143
 # cw_seed_spans: a placed query's span is its window's diagonals over the whole query, widened by SPAN_PAD + (query length >> SPAN_PAD_SHIFT) on either side;
 # the shift is measured (tests/test_sw_span_cpu.py)
 SPAN_PAD, SPAN_PAD_SHIFT = 64, 4
@@ -110,6 +116,24 @@ class LocateRef(C.Structure):
     """cw_locate_ref: the packed reference, its length, the caller's table of cw_locate_table_words(len) words, and k (0 = LOCATE_K)."""
 
     _fields_ = [("bases", C.c_void_p), ("len", C.c_uint64), ("table", C.c_void_p), ("k", C.c_uint32)]
+
+
+class OverlapParams(C.Structure):
+    """cw_overlap_params: k (0 = OVL_K), sample (0 .. 8), max_occ (0 = OVL_MAX_OCC), min_hits (>= 1)."""
+
+    _fields_ = [("k", C.c_uint32), ("sample", C.c_uint32), ("max_occ", C.c_uint32), ("min_hits", C.c_uint32)]
+
+
+class OverlapIndexRef(C.Structure):
+    """cw_overlap_index: the caller's device memory of cw_overlap_index_words(n_entries) words, the counted entries, the parameters."""
+
+    _fields_ = [("mem", C.c_void_p), ("n_entries", C.c_uint64), ("prm", OverlapParams)]
+
+
+class Overlaps(C.Structure):
+    """cw_overlaps: rows, row_off[n_queries + 1] in rows, n_rows[n_queries], status[n_queries]."""
+
+    _fields_ = [("rows", C.c_void_p), ("row_off", C.c_void_p), ("n_rows", C.c_void_p), ("status", C.c_void_p)]
 
 
 class SwSpans(C.Structure):
@@ -250,6 +274,16 @@ def _load(p):
         lib.cw_locate_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(Batch), C.POINTER(Seeds)]
         lib.cw_debug_locate_plan.argtypes = [C.c_uint32, C.c_int, C.c_void_p]
         lib.cw_debug_locate_routes.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "cw_overlap_run"):
+        lib.cw_overlap_index_words.argtypes = [C.c_uint64]
+        lib.cw_overlap_index_words.restype = C.c_uint64
+        lib.cw_overlap_count_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OverlapParams), C.POINTER(C.c_uint64), C.c_void_p]
+        lib.cw_overlap_build_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OverlapIndexRef), C.c_void_p]
+        lib.cw_overlap_run_device.argtypes = [C.c_void_p, C.POINTER(OverlapIndexRef), C.POINTER(Batch), C.c_uint32, C.c_uint32, C.POINTER(Overlaps), C.c_void_p]
+        lib.cw_overlap_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OverlapParams), C.POINTER(Overlaps)]
+        lib.cw_overlap_to_pile_device.argtypes = [C.c_void_p, C.POINTER(Overlaps), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.cw_debug_overlap_plan.argtypes = [C.c_uint32, C.c_int, C.c_void_p]
+        lib.cw_debug_overlap_routes.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "cw_sw_span_run"):
         lib.cw_sw_span_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwSpans), C.c_uint32]
         lib.cw_sw_span_run_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(SwSpans), C.c_uint32, C.c_void_p]
@@ -536,6 +570,19 @@ def synth_host(spec):
     return HostBatch(wfs, lens, offs, bases)
 
 
+def write_paf(path, names, lengths, per_query):
+    """The PAF file of overlap rows: per_query[q] is the rows (OVL_ROW numbers each) of read q, names and lengths those of every read.  One line per row,
+    fields as Engine.overlaps_paf states them.  Returns the number of lines."""
+    n = 0
+    with open(path, "w") as f:
+        for q, rows in enumerate(per_query):
+            for t, o, hits, _, qs, qe, ts, te in rows:
+                f.write("%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\n" % (names[q], lengths[q], qs, qe + 1, "-" if o == STRAND_REV else "+", names[t], lengths[t], ts, te + 1,
+                                                                            hits, max(qe + 1 - qs, te + 1 - ts)))
+                n += 1
+    return n
+
+
 def paf_reformat(in_path, out_path):
     """reformatPAF (src/reformatPAF.cpp): swap the query and target columns of a PAF file."""
     lib = load_library()
@@ -813,6 +860,54 @@ class LocateIndex:
 
     def c_struct(self):
         return LocateRef(self.bases.data_ptr(), self.ref_len, self.table.data_ptr(), self.k)
+
+
+class OverlapIndex:
+    """What Engine.overlap_index returns: the read set on the device (`seq_len`, `seq_word_off`, `bases`) and the index built over it (`mem`), torch tensors
+    this handle keeps alive; `lengths` (the reads' lengths on the host), `n_entries`, and k, sample, max_occ as they were given.  .batch() is the cw_batch
+    and .c_struct(min_hits) the cw_overlap_index the device entry points take."""
+
+    def __init__(self, lengths, n_words, k, sample, max_occ, n_entries, seq_len, seq_word_off, bases, mem):
+        self.lengths, self.n_words, self.k, self.sample, self.max_occ, self.n_entries = lengths, n_words, k, sample, max_occ, n_entries
+        self.seq_len, self.seq_word_off, self.bases, self.mem = seq_len, seq_word_off, bases, mem
+
+    def batch(self):
+        return Batch(0, len(self.lengths), self.n_words, None, self.seq_len.data_ptr(), self.seq_word_off.data_ptr(), self.bases.data_ptr())
+
+    def c_struct(self, min_hits):
+        return OverlapIndexRef(self.mem.data_ptr(), self.n_entries, OverlapParams(self.k, self.sample, self.max_occ, int(min_hits)))
+
+
+class OverlapRows:
+    """What Engine.overlap_rows returns for queries first .. first + count - 1: `rows` (total, OVL_ROW) int32, `row_off` (count + 1, in rows), `n_rows`, `status`.
+    .of(j) is the (n_rows[j], OVL_ROW) rows of query first + j."""
+
+    def __init__(self, rows, row_off, n_rows, status, first):
+        self.rows, self.row_off, self.n_rows, self.status, self.first = rows, row_off, n_rows, status, first
+
+    def of(self, j):
+        a = int(self.row_off[j])
+        return self.rows[a : a + (int(self.n_rows[j]) if self.status[j] == OVL_OK else 0)]
+
+
+class Overlap:
+    """One row of Engine.overlaps: read `target` overlaps the query on `strand` (STRAND_FWD, or STRAND_REV: its reverse complement does) with `hits` shared
+    sampled k-mers in the best 128 diagonals from `diag`; q_start .. q_end on the query as given and t_start .. t_end on the target, ends inclusive -- the
+    dovetail that diagonal implies, up to OVL_END_SLACK bases from an aligned end."""
+
+    __slots__ = ("target", "strand", "hits", "diag", "q_start", "q_end", "t_start", "t_end")
+
+    def __init__(self, target, strand, hits, diag, q_start, q_end, t_start, t_end):
+        self.target, self.strand, self.hits, self.diag, self.q_start, self.q_end, self.t_start, self.t_end = target, strand, hits, diag, q_start, q_end, t_start, t_end
+
+    def astuple(self):
+        return (self.target, self.strand, self.hits, self.diag, self.q_start, self.q_end, self.t_start, self.t_end)
+
+    def __eq__(self, o):
+        return isinstance(o, Overlap) and self.astuple() == o.astuple()
+
+    def __repr__(self):
+        return "Overlap(target=%d, strand=%d, hits=%d, diag=%d, q_start=%d, q_end=%d, t_start=%d, t_end=%d)" % self.astuple()
 
 
 class Placement:
@@ -1327,6 +1422,111 @@ class Engine:
         for status, hits, diag, other in self.locate_rows(index, reads).rows.tolist():
             out.append(Placement(status, diag, hits, other) if status <= STRAND_REV and hits >= floor else None)
         return out
+
+    def overlap_index(self, reads, k=0, sample=OVL_SAMPLE, max_occ=0):
+        """The device index of the read set `reads` (ACGT strings, or a HostBatch whose grouping is ignored) for overlap_rows(): the reads uploaded,
+        cw_overlap_count_device, memory of cw_overlap_index_words(entries) words and cw_overlap_build_device.  k = 0 is OVL_K = 15, sample 0 .. 8 (0 = every
+        k-mer), max_occ = 0 is OVL_MAX_OCC.  Build once, run any number of query ranges.  Returns an OverlapIndex, which holds the device memory."""
+        import torch
+
+        batch = reads if isinstance(reads, HostBatch) else pack_piles([list(reads)])
+        S = len(batch.seq_len)
+        dev = torch.device("cuda", self.device)
+
+        def up(a, dt):
+            return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
+
+        t_len, t_off = up(batch.seq_len if S else np.zeros(1, np.uint32), np.int32), up(batch.seq_word_off if S else np.zeros(1, np.uint64), np.int64)
+        t_bases = up(np.concatenate([batch.bases, np.zeros(1, np.uint32)]), np.int32)
+        index = OverlapIndex(np.array(batch.seq_len, np.int64), len(batch.bases), int(k), int(sample), int(max_occ), 0, t_len, t_off, t_bases, None)
+        torch.cuda.synchronize(dev)  # the engine launches on its own stream
+        b, prm, n = index.batch(), OverlapParams(int(k), int(sample), int(max_occ), 1), C.c_uint64()
+        _check(self.lib, self.lib.cw_overlap_count_device(self.handle, C.byref(b), C.byref(prm), C.byref(n), None), "cw_overlap_count_device")
+        words = int(self.lib.cw_overlap_index_words(n.value))
+        if words == 0:
+            raise EngineError("overlap_index: more than 2^32 - 1 sampled k-mers; raise `sample`")
+        index.n_entries, index.mem = int(n.value), torch.empty(words // 2 + 1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        ref = index.c_struct(1)
+        _check(self.lib, self.lib.cw_overlap_build_device(self.handle, C.byref(b), C.byref(ref), None), "cw_overlap_build_device")
+        torch.cuda.synchronize(dev)
+        return index
+
+    def overlap_device(self, index_struct, batch_struct, first, count, overlaps_struct, stream=None):
+        """cw_overlap_run_device: device pointers in `index_struct` (OverlapIndexRef), the reads' batch struct and `overlaps_struct` (Overlaps); asynchronous
+        on `stream`."""
+        _check(self.lib, self.lib.cw_overlap_run_device(self.handle, C.byref(index_struct), C.byref(batch_struct), first, count, C.byref(overlaps_struct), stream),
+               "cw_overlap_run_device")
+
+    def overlap_routes(self):
+        """(queries of the LDS route, queries of the dense route) of the last overlap run (cw_debug_overlap_routes)."""
+        out = np.zeros(2, np.uint32)
+        _check(self.lib, self.lib.cw_debug_overlap_routes(self.handle, _ptr(out)), "cw_debug_overlap_routes")
+        return int(out[0]), int(out[1])
+
+    def overlap_rows(self, index, first=0, count=None, min_hits=OVL_MIN_HITS, slots=32, grow=True):
+        """cw_overlap_run_device of the queries first .. first + count - 1 (count=None: to the end) of an OverlapIndex: OverlapRows.  `slots` is the rows of
+        every query's slot, or an array of them; when a query answers OVL_SLOT and `grow` holds, the run is repeated once with the slots the counts ask for."""
+        import torch
+
+        S = len(index.lengths)
+        first = int(first)
+        count = S - first if count is None else int(count)
+        dev = torch.device("cuda", self.device)
+        slot = np.full(count, slots, np.uint64) if np.isscalar(slots) else np.asarray(slots, np.uint64)
+        while True:
+            row_off = np.concatenate([np.zeros(1, np.uint64), np.cumsum(slot, dtype=np.uint64)])
+            t_off = torch.from_numpy(row_off.view(np.int64)).to(dev)
+            t_rows = torch.zeros(max(int(row_off[-1]) * OVL_ROW, 1), dtype=torch.int32, device=dev)
+            t_n = torch.zeros(max(count, 1), dtype=torch.int32, device=dev)
+            t_status = torch.zeros(max(count, 1), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            self.overlap_device(index.c_struct(min_hits), index.batch(), first, count, Overlaps(t_rows.data_ptr(), t_off.data_ptr(), t_n.data_ptr(), t_status.data_ptr()))
+            torch.cuda.synchronize(dev)
+            n_rows, status = t_n.cpu().numpy().view(np.uint32)[:count], t_status.cpu().numpy()[:count]
+            if grow and (status == OVL_SLOT).any():
+                slot, grow = np.maximum(slot, n_rows.astype(np.uint64)), False
+                continue
+            return OverlapRows(t_rows.cpu().numpy()[: int(row_off[-1]) * OVL_ROW].reshape(-1, OVL_ROW), row_off, n_rows, status, first)
+
+    def overlap_run_host(self, reads, k=0, sample=OVL_SAMPLE, max_occ=0, min_hits=OVL_MIN_HITS, slots=32):
+        """cw_overlap_run, the host form, of every read: (rc, OverlapRows) -- rc is 0 or CW_E_CAPACITY (-4) when a query has OVL_SLOT or OVL_DENSE."""
+        batch = reads if isinstance(reads, HostBatch) else pack_piles([list(reads)])
+        S = len(batch.seq_len)
+        slot = np.full(S, slots, np.uint64) if np.isscalar(slots) else np.asarray(slots, np.uint64)
+        row_off = np.concatenate([np.zeros(1, np.uint64), np.cumsum(slot, dtype=np.uint64)])
+        rows, n_rows, status = np.zeros((int(row_off[-1]), OVL_ROW), np.int32), np.zeros(max(S, 1), np.uint32), np.zeros(max(S, 1), np.uint8)
+        b = Batch(0, S, len(batch.bases), None, _ptr(batch.seq_len), _ptr(batch.seq_word_off), _ptr(batch.bases))
+        prm, out = OverlapParams(int(k), int(sample), int(max_occ), int(min_hits)), Overlaps(_ptr(rows) if rows.size else _ptr(np.zeros(1, np.int32)), _ptr(row_off), _ptr(n_rows), _ptr(status))
+        rc = _check(self.lib, self.lib.cw_overlap_run(self.handle, C.byref(b), C.byref(prm), C.byref(out)), "cw_overlap_run", allow_capacity=True)
+        return rc, OverlapRows(rows, row_off, n_rows[:S], status[:S], 0)
+
+    def overlaps(self, reads, k=0, sample=OVL_SAMPLE, max_occ=0, min_hits=None):
+        """Per read of `reads` (ACGT strings, either strand, any order) the reads of the same set that overlap it: a list of Overlap, the most hits first
+        (cw_overlap_*: one device index of every sampled k-mer of the set, one run).  `reads` may be an OverlapIndex (its k, sample and max_occ hold).
+        min_hits=None is OVL_MIN_HITS = 2, twice a measured chance level (tests/test_overlap_cpu.py): on 120 reads of 1 500 to 5 000 bases at 10 - 12 % errors
+        from a random genome of 30 000 bases, at k = 15 and sample = 3, the plain reference's largest HITS between reads whose true intervals lie 1 000 bases
+        or more apart is 1, and every planted overlap of OVL_MIN_OVERLAP = 2 000 bases or more is reported with the right strand.  It holds from
+        k = OVL_MIN_K = 15 up; below, EngineError unless min_hits is given.  A read outside k .. 32 768 bases has no overlaps and is nobody's."""
+        given = isinstance(reads, OverlapIndex)
+        kk = reads.k if given else int(k)
+        if min_hits is None and 0 < kk < OVL_MIN_K:
+            raise EngineError(f"overlaps: the default min_hits is measured for k >= {OVL_MIN_K}; give min_hits with k = {kk}")
+        index = reads if given else self.overlap_index(reads, kk, sample, max_occ)
+        if len(index.lengths) == 0:
+            return []
+        got = self.overlap_rows(index, 0, None, OVL_MIN_HITS if min_hits is None else int(min_hits))
+        if (got.status >= OVL_SLOT).any():
+            raise EngineError(f"overlaps: {int((got.status >= OVL_SLOT).sum())} reads vote for more distinct (target, strand, bin) keys than the run holds; raise sample or lower max_occ")
+        return [[Overlap(*row) for row in got.of(j).tolist()] for j in range(len(index.lengths))]
+
+    def overlaps_paf(self, reads, names, path, k=0, sample=OVL_SAMPLE, max_occ=0, min_hits=None):
+        """overlaps() written as the PAF file cw_paf_open / cw_run_correction read: one line per row, a query's lines together and in row order -- query name,
+        length, Q_START, Q_END + 1 (PAF ends are exclusive), + or -, target name, length, T_START, T_END + 1, residue matches = HITS, block length = the
+        longer span, mapping quality 255.  `reads` are ACGT strings, a HostBatch or an OverlapIndex.  Returns the number of lines."""
+        per = self.overlaps(reads, k, sample, max_occ, min_hits)
+        lens = reads.lengths if isinstance(reads, OverlapIndex) else (reads.seq_len if isinstance(reads, HostBatch) else [len(r) for r in reads])
+        return write_paf(path, names, lens, [[o.astuple() for o in rows] for rows in per])
 
     def polish_reads(self, reference, reads, window=500, tile=8192, k=0, min_hits=None, seeded=False, index=False):
         """`reference`, a contig of any length, polished from an unsorted bag of reads of either strand: place() the reads; every placed read, reverse-

@@ -83,16 +83,49 @@ def correct_reads(reads_path, paf_path, out=None, *, min_support=3, max_support=
     return [(lines[i][1:], lines[i + 1]) for i in range(0, len(lines) - 1, 2)]
 
 
-USAGE = "Usage: %s -a overlaps.paf -r reads.fasta [-R reads.fasta] [-s N] [-S N] [-M N] [-l N] [-m N] [-k N] [-c N] [-A N] [-f N] [-j GPUs] (-i, -p accepted and ignored)\n\n"
+def correct_from_reads(reads_path, out_fd, *, paf_path=None, k=0, sample=None, max_occ=0, min_hits=None, device=0, **correction):
+    """Self-correction of a read set from its FASTA / FASTQ file alone: cw_index_reads, the reads' overlaps found on the device and written as PAF
+    (Engine.overlaps_paf: cw_overlap_*, which stands in for minimap2 with coordinates from a diagonal), then run_correction with that file.  The PAF goes to
+    `paf_path`, or to a temporary file that is removed.  k, sample, max_occ, min_hits are Engine.overlaps'; `correction` are run_correction's keywords.
+    Returns run_correction's counters."""
+    from .engine import OVL_SAMPLE, Engine, HostBatch, Params, ReadIndex
+
+    import numpy as np
+
+    idx = ReadIndex(reads_path)
+    eng = Engine(Params(correction.get("mer_size", 9), correction.get("solid_thresh", 4), correction.get("common_kmers", 8), correction.get("min_anchors", 10),
+                        correction.get("max_msa", 150)), device=device)
+    tmp = None
+    try:
+        if paf_path is None:
+            fd, tmp = tempfile.mkstemp(suffix=".paf")
+            os.close(fd)
+        reads = HostBatch(np.array([0, len(idx.seq_len)], np.uint32), idx.seq_len, idx.seq_word_off, idx.bases)
+        eng.overlaps_paf(reads, idx.names, paf_path or tmp, k, OVL_SAMPLE if sample is None else sample, max_occ, min_hits)
+        eng.close()
+        idx.close()
+        correction.setdefault("devices", [device])
+        return run_correction(reads_path, paf_path or tmp, out_fd, **correction)
+    finally:
+        eng.close()
+        idx.close()
+        if tmp is not None and os.path.exists(tmp):
+            os.remove(tmp)
+
+
+USAGE = "Usage: %s -a overlaps.paf -r reads.fasta [-R reads.fasta] [-s N] [-S N] [-M N] [-l N] [-m N] [-k N] [-c N] [-A N] [-f N] [-j GPUs] (-i, -p accepted and ignored)\n       %s --from-reads -r reads.fasta [...]   (no PAF: the overlaps are found on the device)\n\n"
 
 
 def main(argv=None, polishing=False):
     """The reference's command line (src/main.cpp:29-76): same getopt string, same defaults; -d -e -w -n fall into its `default` case."""
-    argv = sys.argv[1:] if argv is None else argv
+    argv = list(sys.argv[1:] if argv is None else argv)
+    from_reads = "--from-reads" in argv  # no -a needed: the overlaps are found on the device (correct_from_reads); with -a, the PAF is also kept there
+    if from_reads:
+        argv.remove("--from-reads")
     try:
         opts, _ = getopt.getopt(argv, "a:A:d:k:s:S:M:l:f:e:p:c:m:j:w:m:r:R:n:i:")
     except getopt.GetoptError:
-        sys.stderr.write(USAGE % "consent_amd.pipeline")
+        sys.stderr.write(USAGE % ("consent_amd.pipeline", "consent_amd.pipeline"))
         raise SystemExit(1)
     kw = dict(min_support=3, max_support=1000, max_msa=150, window_size=500, mer_size=9, common_kmers=8, min_anchors=10, solid_thresh=4, window_overlap=50, nb_threads=1)
     names = {"-s": "min_support", "-S": "max_support", "-M": "max_msa", "-l": "window_size", "-k": "mer_size", "-c": "common_kmers", "-A": "min_anchors", "-f": "solid_thresh",
@@ -111,9 +144,12 @@ def main(argv=None, polishing=False):
         elif o in ("-i", "-p"):
             pass  # stored and never read by the reference
         else:
-            sys.stderr.write(USAGE % "consent_amd.pipeline")
+            sys.stderr.write(USAGE % ("consent_amd.pipeline", "consent_amd.pipeline"))
             raise SystemExit(1)
     sys.stdout.flush()
+    if from_reads:
+        correct_from_reads(reads, sys.stdout.fileno(), paf_path=paf or None, proof_path=proof, polishing=polishing, **kw)
+        return
     run_correction(reads, paf, sys.stdout.fileno(), proof_path=proof, polishing=polishing, **kw)
 
 

@@ -27,6 +27,8 @@
  *                               unique in the reference (no counterpart: the reference takes all three from minimap2's PAF records).
  *   cw_locate_build_device, cw_locate_run_device / cw_locate_run <- the same three for reads against a reference of any length, through one device index of
  *                               the whole reference's unique k-mers: O(read) a read, whatever the reference's length (no counterpart either).
+ *   cw_overlap_count_device, cw_overlap_build_device, cw_overlap_run_device / cw_overlap_run, cw_overlap_to_pile_device <- the reads of a set that overlap
+ *                               each other, through one device index of every sampled k-mer of the set (no counterpart: the reference reads minimap2's PAF).
  *   cw_sw_span_run, cw_sw_path_span_run, cw_pileup_span_run, cw_sw_cut_span_run (and _device) <- the four alignment runs with every query confined to a span
  *                               of its reference's columns, and cw_seed_spans / cw_seed_spans_device <- those spans from a seed run's rows (no counterpart:
  *                               the reference aligns a read against the window its PAF record names).
@@ -513,6 +515,72 @@ uint64_t cw_locate_table_words(uint64_t ref_len);
 int cw_locate_build_device(cw_engine* e, const cw_locate_ref* ref, void* hip_stream);
 int cw_locate_run_device(cw_engine* e, const cw_locate_ref* ref, const cw_batch* reads, const cw_seeds* out, void* hip_stream);
 int cw_locate_run(cw_engine* e, const uint32_t* ref_bases, uint64_t ref_len, uint32_t k, const cw_batch* reads, const cw_seeds* out);
+
+/* ---- the reads of a set that overlap each other: cw_overlap_* -------------------------------------------------------------------------------------------------------
+ * What the window runs and cw_run_correction take from minimap2's PAF file, found on the device: per read the reads that share enough sampled k-mers with it on one
+ * diagonal, with strand, diagonal and PAF-style coordinates.  The locate index keeps a k-mer that is unique in ONE reference; a read set at depth d holds every
+ * k-mer d times, so this index keeps EVERY occurrence.  `reads` is a cw_batch whose grouping (n_windows, win_first_seq) is not read; its bases end in one spare
+ * word, as everywhere.
+ *
+ * The function, with prm = {k, sample, max_occ, min_hits} (k: 0 = CW_OVL_K, else CW_STRAND_KMIN .. CW_STRAND_KMAX; sample 0 .. 8, 0 = every k-mer, CW_OVL_SAMPLE
+ * the named default; max_occ: 0 = CW_OVL_MAX_OCC, at most 65 535; min_hits >= 1, CW_OVL_MIN_HITS the measured default):
+ *   occurrences  position i of read r (0 <= i <= len - k), K the k-mer there, R its reverse complement.  K == R (even k only): skipped.  c = min(K, R), the
+ *                occurrence's strand s = (K > R).  Sampled when sample == 0 or ((c * 0x9E3779B1) mod 2^32) >> (32 - sample) == 0.  The index holds (c, r, i, s)
+ *                of every sampled position of every read with k <= len <= CW_SW_QMAX; other reads contribute nothing.  occ(c) = the entries of c.
+ *   votes        of query q (m bases): every sampled occurrence (c, i, sq) of q with occ(c) <= max_occ, against every entry (c, t, p, st) with t != q (read
+ *                INDICES: a second copy of a sequence is a target).  o = sq ^ st; the bin b = (p - i + m) >> CW_SEED_SHIFT for o = 0, (p + k + i) >>
+ *                CW_SEED_SHIFT for o = 1 -- cw_locate_run's arithmetic with t as the reference.  c[t, o, b] counts them, w[t, o, b] = c[t, o, b] + c[t, o, b + 1];
+ *                per (t, o) the best b maximises w, ties to the lowest b.  A candidate is a (t, o) whose best w >= min_hits; both orientations of a target may be.
+ *   rows         the candidates by hits descending, then t, then o ascending, CW_OVL_ROW int32 each: TARGET, STRAND (CW_STRAND_FWD / CW_STRAND_REV), HITS,
+ *                DIAG = (b << 6) - m, then with n the target's length c0 = clamp(DIAG + 64, -(m - k), n - k), a = max(0, -c0), z = min(m, n - c0):
+ *                T_START = a + c0, T_END = z + c0 - 1; forward Q_START = a, Q_END = z - 1; reverse Q_START = m - z, Q_END = m - 1 - a.  Ends INCLUSIVE, query
+ *                coordinates on the query as given: cw_overlap's convention.  These are the dovetail the window's middle diagonal implies, not aligned ends: on
+ *                the planted set of tests/test_overlap_cpu.py (10 - 12 % errors) an end lies up to CW_OVL_END_SLACK bases from the true overlap's end.
+ *   per query    n_rows[j] the candidates, status[j]: CW_OVL_OK; CW_OVL_NONE (m < k or m > CW_SW_QMAX: 0 rows, never an error); CW_OVL_SLOT (the candidates
+ *                outgrow the slot row_off[j + 1] - row_off[j], counted in ROWS: n_rows is the number needed, nothing is written, never a truncation);
+ *                CW_OVL_DENSE (the query's distinct (t, o, b) keys pass 131 072, the scratch table's capacity: 0 rows); CW_OVL_BAD_INDEX (the memory was
+ *                built with an n_entries that is not the read set's count: 0 rows).  Words of a slot beyond the rows written are never touched.
+ * Every number is a function of (read set, prm, query) alone: not of how the queries are batched, their order, the run, or the kernels' route.
+ *
+ * cw_overlap_count_device: *n_entries (a HOST pointer) = the sampled occurrences; it synchronises once.  cw_overlap_index_words(n_entries): the index's size in
+ * 32-bit words (0 beyond the limits).  cw_overlap_build_device: clears and fills index->mem (8-byte aligned, the caller's device memory; one piece serves one read
+ * set after another); index->n_entries is what the count gave.  Its content is private and may differ from build to build; the rows never do.
+ * cw_overlap_run_device: the queries are reads first_query .. first_query + n_queries - 1 of the indexed set, j = q - first_query indexes out's arrays.
+ * cw_overlap_run: host pointers, synchronous; counts, builds into memory of the engine's own, runs every read, brings rows, counts and statuses back;
+ * CW_E_CAPACITY when a query has CW_OVL_SLOT or CW_OVL_DENSE.  cw_overlap_to_pile_device: per query the first min(n_rows, max_support, its pile slot) rows as
+ * cw_overlap tuples for cw_extract_piles_device -- the rows are in pile order already -- and pile_n[j] how many.
+ * Limits: n_seqs < 2^24, n_entries < 2^32, reads beyond CW_SW_QMAX are CW_OVL_NONE and no targets (a bin fits 11 bits).
+ * CW_E_INVALID before anything is launched: NULL arguments or members, parameters outside their ranges, n_seqs >= 2^24, a misaligned index, first_query +
+ * n_queries beyond the set.  Pointers, streams and threading: cw_locate_*'s contract.  cw_last_timings names the stages ovl_count; ovl_build_count,
+ * ovl_build_insert, ovl_build_assign, ovl_build_fill; ovl, ovl_dense; ovl_pile. */
+#define CW_OVL_K 15u
+#define CW_OVL_SAMPLE 3u
+#define CW_OVL_MAX_OCC 512u
+#define CW_OVL_MIN_HITS 2u     /* twice the largest HITS of unrelated reads on the planted set (tests/test_overlap_cpu.py) */
+#define CW_OVL_END_SLACK 143u  /* the largest distance of a reported end from the true overlap's end on that set, plus one bin */
+enum { CW_OVL_TARGET, CW_OVL_STRAND, CW_OVL_HITS, CW_OVL_DIAG, CW_OVL_Q_START, CW_OVL_Q_END, CW_OVL_T_START, CW_OVL_T_END, CW_OVL_ROW = 8 };
+enum { CW_OVL_OK = 0, CW_OVL_NONE = 1, CW_OVL_SLOT = 2, CW_OVL_DENSE = 3, CW_OVL_BAD_INDEX = 4 };
+typedef struct cw_overlap_params { uint32_t k, sample, max_occ, min_hits; } cw_overlap_params;
+typedef struct cw_overlap_index {
+    uint32_t* mem;          /* [cw_overlap_index_words(n_entries)], the caller's, 8-byte aligned */
+    uint64_t n_entries;     /* cw_overlap_count_device's answer for the read set and prm */
+    cw_overlap_params prm;
+} cw_overlap_index;
+typedef struct cw_overlaps {
+    int32_t* rows;
+    const uint64_t* row_off; /* [n_queries + 1], in rows, ascending */
+    uint32_t* n_rows;        /* [n_queries] */
+    uint8_t* status;         /* [n_queries] */
+} cw_overlaps;
+struct cw_overlap; /* (declared below) */
+int cw_overlap_count_device(cw_engine* e, const cw_batch* reads, const cw_overlap_params* prm, uint64_t* n_entries, void* hip_stream);
+uint64_t cw_overlap_index_words(uint64_t n_entries);
+int cw_overlap_build_device(cw_engine* e, const cw_batch* reads, const cw_overlap_index* index, void* hip_stream);
+int cw_overlap_run_device(cw_engine* e, const cw_overlap_index* index, const cw_batch* reads, uint32_t first_query, uint32_t n_queries, const cw_overlaps* out,
+                          void* hip_stream);
+int cw_overlap_run(cw_engine* e, const cw_batch* reads, const cw_overlap_params* prm, const cw_overlaps* out);
+int cw_overlap_to_pile_device(cw_engine* e, const cw_overlaps* rows, uint32_t n_queries, uint32_t max_support, struct cw_overlap* pile, const uint64_t* pile_off,
+                              uint32_t* pile_n, void* hip_stream);
 
 /* ---- align a query only where it was placed: reference spans ------------------------------------------------------------------------------------------------------
  * The four alignment runs sweep every query over ALL columns of its reference.  Each has a span form that confines query s to the reference columns
